@@ -4,6 +4,7 @@
     python bench.py                              # 1 GPU, raft 436x1024, 32 iterations, fp32
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --dump-outputs DIR           # also write the last timed step's outputs as DIR/<name>.npy (float32)
 
 A *step* is one forward of `ptlflow_amd.RAFT` (both encoders, correlation volume + pyramid + 32 x {lookup, update block,
 coordinate update, convex upsample} — every kernel libpfk's, no MIOpen / rocBLAS call in the forward) over one batch of
@@ -95,6 +96,9 @@ def parse():
                     help="dropin leg: also time the un-patched torch / MIOpen forward of the same model (first call compiles MIOpen kernels)")
     ap.add_argument("--cpu-forwards", type=int, default=3)
     ap.add_argument("--cpu-budget-s", type=float, default=30.0, help="stop timing CPU forwards after this many seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last timed step as DIR/<name>.npy (float32; a "
+                         "fixed, seeded sample of each array when all of them together exceed 64 MB)")
     return ap.parse_args()
 
 
@@ -166,6 +170,28 @@ def roofline_b16(model, inputs):
                          "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS, "avg_us": lookup["avg_us"],
                          "algorithmic_bytes_per_launch": lookup["bytes_per_launch"]}
     return obj
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out: dict, path: str) -> dict:
+    """Every tensor of the forward's output dict as `path/<name>.npy` in float32.  When they exceed DUMP_BUDGET_BYTES together,
+    each array is cut to the same fraction of its elements, picked by a generator seeded with 0 (flat indices, sorted): the
+    same arguments give the same sample, so two builds can be compared file for file.  Returns {name: stored shape}."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+    total = sum(a.size for a in arrays.values()) * 4
+    os.makedirs(path, exist_ok=True)
+    stored = {}
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, a.size * (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // total)      # (room for the .npy headers)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        stored[name] = list(a.shape)
+    return stored
 
 
 def timed(fn, warmup: int, steps: int) -> float:
@@ -584,6 +610,8 @@ def main():
     faults = model.engine(dev).faults()
     if faults:
         raise SystemExit(f"stream-K workspace reports {faults} timed-out fix-up(s): results invalid")
+    # before any other leg runs the model again: these are the arrays the last timed step handed its caller
+    dumped = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     pairs = args.batch * args.steps * world
     result = {
@@ -611,6 +639,8 @@ def main():
                                   else "mask head + convex upsample on every iteration as the reference"),
                    "global_batch": args.batch * world, "parallelism": f"dp{world} (independent replicas, no collectives)"},
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if shared:
         result["config"]["shared_device"] = "all ranks on cuda:0 over gloo (N > 1 code-path smoke on a one-GPU box, not a scaling number)"
 

@@ -66,3 +66,25 @@ def test_self_launch_shared_device_smoke_flag(bench, monkeypatch):
     with pytest.raises(SystemExit):
         bench.self_launch(_args(2))
     assert "--nproc-per-node=2" in seen["cmd"]
+
+
+def test_dump_outputs_writes_float32_arrays_within_budget(bench, tmp_path):
+    """`--dump-outputs DIR`: every tensor of the output dict as DIR/<name>.npy in float32 (bf16 widened, lists left out); above the
+    64 MB budget the same seeded sample on every call, so that two builds compare file for file."""
+    import numpy as np
+    small = {"flows": torch.randn(2, 1, 2, 8, 16), "flow_small": torch.randn(2, 2, 1, 2).bfloat16(), "flow_preds": [torch.zeros(1)]}
+    shapes = bench.dump_outputs(small, str(tmp_path / "a"))
+    assert shapes == {"flows": [2, 1, 2, 8, 16], "flow_small": [2, 2, 1, 2]}
+    got = np.load(tmp_path / "a" / "flows.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small["flows"].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "flow_small.npy"), small["flow_small"].float().numpy())
+    big = {"flows": torch.randn(24, 1, 2, 436, 1024), "flow_small": torch.randn(24, 2, 55, 128)}
+    bench.dump_outputs(big, str(tmp_path / "b"))
+    bench.dump_outputs(big, str(tmp_path / "c"))
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["flow_small.npy", "flows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_BUDGET_BYTES
+    for f in files:
+        a, b = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.array_equal(a, b)
+        assert np.isin(a, big[f[:-4]].numpy().reshape(-1)).all()
