@@ -28,6 +28,8 @@
  *   pfk_flow_delta_f32    ptlflow/models/raft/update.py:10,14 (FlowHead.conv2) fused with
  *                         ptlflow/models/raft/raft.py:174,178 (flow = coords1-coords0; coords1 += d)
  *   pfk_convex_upsample_f32  ptlflow/models/raft/raft.py:112-123 RAFT.upsample_flow
+ *   pfk_dwconv_layernorm_f32  ptlflow/models/sea_raft/layer.py:54-58,71-75 (ConvNextBlock dwconv + norm)
+ *   pfk_convex_upsample_info_pm_f32  ptlflow/models/sea_raft/sea_raft.py:147-163 SEARAFT.upsample_data
  *   pfk_altcorr_forward_f32  ptlflow/utils/external/alt_cuda_corr/correlation_kernel.cu:258-285 (alt_cuda_corr.forward)
  *   pfk_corr_lookup_bwd_f32 / pfk_corr_volume_bwd_f32 / pfk_convex_upsample_bwd_f32
  *                         what torch.autograd runs for corr.py:29-64 and raft.py:112-123 in a training step (train.py;
@@ -197,7 +199,12 @@ enum pfk_epilogue {
                           out[p*out_ld + out_coff + co] = v */
   PFK_EPI_GRU_ZR = 1,  /* cout = 2*Ch: v = acc + bias [+ residual[p*residual_ld+co]]; co<Ch: z=sigmoid(v) -> aux_z[p*Ch+co];
                           co>=Ch: r=sigmoid(v) -> aux_rh[p*Ch + co-Ch] = r * h[p*h_ld + co-Ch] */
-  PFK_EPI_GRU_Q = 2    /* cout = Ch: q=tanh(acc + bias [+ residual]); h[p*h_ld+co] = (1-z)*h + z*q, z = aux_z[p*Ch+co] */
+  PFK_EPI_GRU_Q = 2,   /* cout = Ch: q=tanh(acc + bias [+ residual]); h[p*h_ld+co] = (1-z)*h + z*q, z = aux_z[p*Ch+co] */
+  PFK_EPI_LINEAR_GELU = 3  /* (added in ABI 7) LINEAR with the exact GELU in place of relu: v = (acc+bias) ;
+                              v = 0.5*v*(1 + erf(v/sqrt(2))) ; v *= scale ; [v = residual + v] ; out = v.  `relu` must be 0;
+                              `relu_after_residual` as LINEAR.  sea_raft/layer.py:60-62,74-75 (pwconv1 + nn.GELU()).
+                              pfk_conv2d_f32 only (tile grid and stream-K, no cout_active / cout_split): pfk_conv2d_group_f32,
+                              pfk_conv2d_bf16s and pfk_conv2d_b16 return PFK_ERR_UNSUPPORTED for it */
 };
 
 typedef struct {
@@ -415,6 +422,26 @@ int pfk_convex_upsample_pm_f32(const float* flow_pm, int flow_ld, const float* m
  * writes them — what `0.25 * self.mask(net)` is under the reference's reduced-precision switch; softmax and combination in fp32 */
 int pfk_convex_upsample_pm_b16(const float* flow_pm, int flow_ld, const void* mask_bf16, int mask_ld, float* out,
                                int B, int H, int W, pfk_stream_t stream);
+
+/* ---- SEA-RAFT refinement (additions of ABI 7) ------------------------------------------------------------------------------
+ * pfk_dwconv_layernorm_f32: ConvNextBlock.dwconv followed by .norm (sea_raft/layer.py:54-58, :71-75): a depthwise k x k "same"
+ * convolution (zero padding k/2, bias) followed by a LayerNorm over the C channels of each pixel (biased variance, `eps`, weight
+ * and bias).  in: pixel-major rows in[p*in_ld + c], p = (b*H + y)*W + x, C channels (C % 4 == 0, 4 <= C <= 512; in 16-byte
+ * aligned, in_ld % 4 == 0 — e.g. the update engine's [net | context | motion | flow] rows); dw_weight [C][k*k] (tap ky*k + kx),
+ * dw_bias [C] or NULL, ln_weight / ln_bias [C]; out [M][out_ld] (out_ld >= C; must not overlap the input rows).  k odd, 1 <= k <= 7.  One launch, one read of every input row from HBM (halo tiles staged in LDS), the
+ * statistics finished in the kernel. */
+int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                             const float* ln_bias, float eps, float* out, int out_ld, int B, int H, int W, int C, int k,
+                             pfk_stream_t stream);
+
+/* pfk_convex_upsample_info_pm_f32: SEARAFT.upsample_data (sea_raft/sea_raft.py:147-163).  flow_pm [M][flow_ld] (channels 0..1),
+ * info_pm [M][info_ld] (channels 0..n-1, 1 <= n <= 8), mask [M][mask_ld] fp32 logits with channel c = k*64 + sy*8 + sx, already
+ * multiplied by 0.25 (16-byte aligned rows, mask_ld % 4 == 0, mask_ld >= 576).  Softmax over the nine taps; convex combination of
+ * the zero-padded 3x3 neighbourhood of 8*flow -> flow_out [B][2][8H][8W] and of info (no factor) -> info_out [B][n][8H][8W]
+ * (both NCHW, contiguous, 16-byte aligned).  flow_out is bit-identical to pfk_convex_upsample_pm_f32 on the same flow and mask. */
+int pfk_convex_upsample_info_pm_f32(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
+                                    const float* mask, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
+                                    pfk_stream_t stream);
 
 /* ---- on-demand correlation behind the reference's alt_cuda_corr ABI --------------------------------
  * replaces corr_cuda_forward (ptlflow/utils/external/alt_cuda_corr/correlation_kernel.cu:258-285; pybind

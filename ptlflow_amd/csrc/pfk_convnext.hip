@@ -1,0 +1,162 @@
+// SEA-RAFT's ConvNeXt block (ptlflow/models/sea_raft/layer.py:54-83): the depthwise k x k convolution fused with the channel
+// LayerNorm that follows it (pfk_dwconv_layernorm_f32, include/pfk.h).  The two 1x1 "Linear" layers of the block, its GELU, layer
+// scale and residual are implicit GEMMs on pfk_conv2d_f32 (PFK_EPI_LINEAR_GELU / LINEAR with a residual).
+//
+// Bandwidth-bound: per pixel C floats in, C floats out.  A block owns a TY x TX tile of output pixels and ALL their channels:
+//   * channel chunks of CC: the (TY+k-1) x (TX+k-1) halo of the chunk and its k*k weights are staged in LDS (a pixel row piece is
+//     read once per block from memory; neighbouring blocks' halo overlap comes from L2), every thread then forms one
+//     (pixel, four channels) output from LDS and parks it in the block's [TY*TX][C] output tile, also in LDS;
+//   * after the last chunk each wave normalises eight pixels: mean and biased variance of the pixel's C values (two passes over
+//     the LDS row, wave reductions), then (x - mean) * rstd * weight + bias straight to `out`.
+// Nothing but the final rows goes back to memory: one read, one write per element.
+#include "pfk_common.h"
+
+namespace {
+
+constexpr int DW_TY = 4, DW_TX = 8;       // output tile: 32 pixels, 224 blocks for a batch-1 55 x 128 grid
+constexpr int DW_PIX = DW_TY * DW_TX;
+constexpr int DW_CC = 32;                 // channels per staged chunk: 8 float4 groups x 32 pixels = one item per thread
+constexpr int DW_G = DW_CC / 4;
+constexpr int DW_THREADS = 256;
+static_assert(DW_PIX * DW_G == DW_THREADS, "one (pixel, float4) item per thread and chunk");
+constexpr int DW_MAX_C = 512;
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <int K>
+__global__ __launch_bounds__(DW_THREADS) void dwconv_ln_kernel(const float* __restrict__ in, int in_ld, const float* __restrict__ dw_w,
+                                                               const float* __restrict__ dw_b, const float* __restrict__ ln_w,
+                                                               const float* __restrict__ ln_b, float eps, float* __restrict__ out,
+                                                               int out_ld, int H, int W, int C) {
+  constexpr int R = K / 2, HY = DW_TY + K - 1, HX = DW_TX + K - 1;
+  __shared__ f32x4 halo[HY * HX * DW_G];          // [halo pixel][group]: 17.5 KB at k = 7
+  __shared__ f32x4 wts[K * K * DW_G];             // [tap][group]
+  extern __shared__ float tile[];                 // [DW_PIX][C + 4] (+4: the float4 stores of one wave spread over the banks)
+  const int CP = C + 4;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x * DW_TX, y0 = blockIdx.y * DW_TY;
+  const long long img = (long long)blockIdx.z * H * W;
+  const int q = tid / DW_G, g = tid % DW_G;       // compute item: output pixel q of the tile, channels 4g .. 4g+3 of the chunk
+  const int qy = q / DW_TX, qx = q % DW_TX;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int c0 = 0; c0 < C; c0 += DW_CC) {
+    const int cn = (C - c0) < DW_CC ? (C - c0) : DW_CC;     // a multiple of 4
+    __syncthreads();                                          // the previous chunk's LDS reads are done
+    for (int i = tid; i < HY * HX * DW_G; i += DW_THREADS) {
+      const int hp = i / DW_G, gg = i % DW_G;
+      const int hy = hp / HX, hx = hp - hy * HX;
+      const int yy = y0 + hy - R, xx = x0 + hx - R;
+      f32x4 v = zero;
+      if (gg * 4 < cn && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+        v = *reinterpret_cast<const f32x4*>(in + (img + (long long)yy * W + xx) * in_ld + c0 + gg * 4);
+      halo[i] = v;
+    }
+    for (int i = tid; i < K * K * DW_G; i += DW_THREADS) {
+      const int t = i / DW_G, gg = i % DW_G;
+      f32x4 v = zero;
+      if (gg * 4 < cn) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = dw_w[(long long)(c0 + gg * 4 + e) * (K * K) + t];
+      }
+      wts[i] = v;
+    }
+    __syncthreads();
+    if (g * 4 < cn) {
+      f32x4 acc = zero;
+      if (dw_b != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = dw_b[c0 + g * 4 + e];
+      }
+#pragma unroll
+      for (int ky = 0; ky < K; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < K; ++kx) acc += halo[((qy + ky) * HX + qx + kx) * DW_G + g] * wts[(ky * K + kx) * DW_G + g];
+      }
+      *reinterpret_cast<f32x4*>(tile + q * CP + c0 + g * 4) = acc;
+    }
+  }
+  __syncthreads();
+  // LayerNorm: wave wv normalises tile pixels wv*8 .. wv*8+7; lane holds channels lane + 64 t
+  const int lane = tid & 63, wv = tid >> 6;
+  constexpr int NT = DW_MAX_C / 64;
+  const float inv_c = 1.0f / (float)C;
+  for (int j = 0; j < DW_PIX / (DW_THREADS / 64); ++j) {
+    const int qq = wv * (DW_PIX / (DW_THREADS / 64)) + j;
+    const int y = y0 + qq / DW_TX, x = x0 + qq % DW_TX;
+    if (y >= H || x >= W) continue;                            // wave-uniform
+    const float* row = tile + qq * CP;
+    float v[NT];
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = lane + 64 * t;
+      v[t] = c < C ? row[c] : 0.f;
+      s += v[t];
+    }
+    const float mean = wave_sum(s) * inv_c;
+    float s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = lane + 64 * t;
+      const float d = v[t] - mean;
+      if (c < C) s2 += d * d;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(s2) * inv_c + eps);
+    float* orow = out + (img + (long long)y * W + x) * out_ld;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int c = lane + 64 * t;
+      if (c < C) orow[c] = (v[t] - mean) * rstd * ln_w[c] + ln_b[c];
+    }
+  }
+}
+
+template <int K>
+int launch_dwconv_ln(const float* in, int in_ld, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float eps,
+                     float* out, int out_ld, int B, int H, int W, int C, hipStream_t st) {
+  const size_t smem = (size_t)DW_PIX * (C + 4) * sizeof(float);
+  auto kern = dwconv_ln_kernel<K>;
+  static pfk_device_once attr_once;
+  attr_once.run([&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((size_t)DW_PIX * (DW_MAX_C + 4) * sizeof(float)));
+  });
+  dim3 grid((unsigned)((W + DW_TX - 1) / DW_TX), (unsigned)((H + DW_TY - 1) / DW_TY), (unsigned)B);
+  hipLaunchKernelGGL(kern, grid, dim3(DW_THREADS), smem, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C);
+  return pfk_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                             const float* ln_bias, float eps, float* out, int out_ld, int B, int H, int W, int C, int k,
+                             pfk_stream_t stream) {
+  if (!in || !dw_weight || !ln_weight || !ln_bias || !out || B <= 0 || H <= 0 || W <= 0 || C < 4 || in_ld < C || out_ld < C)
+    return PFK_ERR_BAD_ARG;
+  if (k < 1 || !(k & 1)) return PFK_ERR_BAD_ARG;
+  if (k > 7 || C > DW_MAX_C || B > 65535 || (H + DW_TY - 1) / DW_TY > 65535) return PFK_ERR_UNSUPPORTED;
+  if ((C & 3) || (in_ld & 3) || !pfk_aligned16(in)) return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  // `out` must not overlap the input rows (other blocks still read the halo of pixels this block has written)
+  const char* ib = reinterpret_cast<const char*>(in);
+  const char* ie = reinterpret_cast<const char*>(in + (M - 1) * in_ld + C);
+  const char* ob = reinterpret_cast<const char*>(out);
+  const char* oe = reinterpret_cast<const char*>(out + (M - 1) * out_ld + C);
+  if (ob < ie && ib < oe) return PFK_ERR_BAD_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k) {
+    case 1: return launch_dwconv_ln<1>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    case 3: return launch_dwconv_ln<3>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    case 5: return launch_dwconv_ln<5>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    default: return launch_dwconv_ln<7>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+  }
+}
+
+}  // extern "C"

@@ -97,6 +97,12 @@ __host__ __device__ __forceinline__ unsigned fastdiv_u32(unsigned n, unsigned mu
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// GemmArgs::relu == ACT_GELU: the LINEAR epilogue applies the exact GELU where it would apply relu (PFK_EPI_LINEAR_GELU of
+// include/pfk.h; desc_to_args sets it, every other producer of GemmArgs leaves relu at 0 / 1)
+constexpr int ACT_GELU = 2;
+// nn.GELU() (approximate='none'): 0.5 * v * (1 + erf(v / sqrt(2)))
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned OOB = 0x80000000u;  // >= num_records of every descriptor below
 
@@ -124,7 +130,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x16 (&acc)[
         if (!nok || p >= a.M) continue;
         float v = acc[mt][nt][r] + bias;
         if constexpr (EPI == PFK_EPI_LINEAR) {
-          if (a.relu) v = (v < 0.f) ? 0.f : v;  // NaN-propagating like torch.relu (fmaxf would drop NaN)
+          if (a.relu == ACT_GELU) v = gelu_erf(v);
+          else if (a.relu) v = (v < 0.f) ? 0.f : v;  // NaN-propagating like torch.relu (fmaxf would drop NaN)
           v *= a.scale;
           if (a.residual != nullptr) v = a.residual[p * a.residual_ld + n] + v;
           if (a.relu2) v = (v < 0.f) ? 0.f : v;
@@ -240,7 +247,10 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& a, const f32x16 (&a
         if (p >= a.M) continue;
         v += bias;
         if constexpr (EPI == PFK_EPI_LINEAR) {
-          if (a.relu) {
+          if (a.relu == ACT_GELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
+          } else if (a.relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];   // NaN-propagating like torch.relu
           }

@@ -1431,12 +1431,16 @@ int desc_to_args(const pfk_conv_desc* d, GemmArgs& a, int kpad) {
   a.relu2 = d->relu_after_residual;
   a.bias = d->bias; a.b_rows = d->cout;
   a.ktot = conv_ktot(d, kpad);
-  a.relu = d->relu; a.scale = d->scale;
+  a.relu = d->relu ? 1 : 0; a.scale = d->scale;     // (any non-zero `relu` is relu: ACT_GELU comes from the epilogue value only)
   a.M = (long long)d->B * a.Ho * a.Wo;
   a.sk_steps = a.ktot / kpad;
   for (int i = 0; i < d->num_src; ++i)   // kernels address sources with 32-bit byte offsets
     if ((long long)d->B * d->H * d->W * s[i].ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
   switch (d->epilogue) {
+    case PFK_EPI_LINEAR_GELU:   // the LINEAR epilogue with GELU in relu's place (pfk.h); launched as PFK_EPI_LINEAR
+      if (d->relu) return PFK_ERR_BAD_ARG;
+      a.relu = ACT_GELU;
+      [[fallthrough]];
     case PFK_EPI_LINEAR:
       if (!d->out || d->out_ld < d->out_coff + d->cout) return PFK_ERR_BAD_ARG;
       a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
@@ -1458,7 +1462,7 @@ int desc_to_args(const pfk_conv_desc* d, GemmArgs& a, int kpad) {
     default:
       return PFK_ERR_BAD_ARG;
   }
-  if (d->epilogue != PFK_EPI_LINEAR && d->residual) {
+  if (d->epilogue != PFK_EPI_LINEAR && d->epilogue != PFK_EPI_LINEAR_GELU && d->residual) {
     // GRU epilogues: an additive pre-activation term [M][cout] (the loop-invariant context part), float4 accesses
     if (d->residual_ld < d->cout) return PFK_ERR_BAD_ARG;
     if (!pfk_aligned16(d->residual) || (d->residual_ld & 3)) return PFK_ERR_ALIGNMENT;
@@ -1515,7 +1519,7 @@ int pfk_conv2d_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
     a.sk_ws = static_cast<float*>(d->workspace);
     a.sk_flags = reinterpret_cast<unsigned*>(static_cast<char*>(d->workspace) + (size_t)SK_MAX_BLOCKS * 64 * 64 * 4);
   }
-  return launch(a, d->epilogue, 1, static_cast<hipStream_t>(stream));
+  return launch(a, d->epilogue == PFK_EPI_LINEAR_GELU ? PFK_EPI_LINEAR : d->epilogue, 1, static_cast<hipStream_t>(stream));
 }
 
 int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream) {
@@ -1525,6 +1529,7 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
   long long total = 0;
   for (int i = 0; i < n; ++i) {
     const pfk_conv_desc* d = &descs[i];
+    if (d->epilogue == PFK_EPI_LINEAR_GELU) return PFK_ERR_UNSUPPORTED;      // pfk_conv2d_f32 only (pfk.h)
     if (!d->weight || d->epilogue != PFK_EPI_LINEAR) return PFK_ERR_BAD_ARG;
     if ((d->cout_active > 0 && d->cout_active < d->cout) || d->cout_split > 0) return PFK_ERR_UNSUPPORTED;
     if (!pfk_aligned16(d->weight)) return PFK_ERR_ALIGNMENT;
@@ -1609,6 +1614,7 @@ int pfk_mask_upsample_f32(const float* x, int x_ld, int cin, const float* weight
 }
 
 int pfk_conv2d_bf16s(const pfk_conv_desc* d, const void* weight_planes, int nsplit, pfk_stream_t stream) {
+  if (d && d->epilogue == PFK_EPI_LINEAR_GELU) return PFK_ERR_UNSUPPORTED;       // pfk_conv2d_f32 only (pfk.h)
   if (d && ((d->cout_active > 0 && d->cout_active < d->cout) || d->cout_split > 0)) return PFK_ERR_UNSUPPORTED;   // the fp32 kernels' features (pfk.h)
   GemmArgs a{};
   if (!d || !weight_planes || nsplit < 1 || nsplit > 3) return PFK_ERR_BAD_ARG;

@@ -894,6 +894,7 @@ int pfk_mask_upsample_b16(const void* x_bf16, int x_ld, int cin, const void* wei
 }
 
 int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
+  if (d && d->epilogue == PFK_EPI_LINEAR_GELU) return PFK_ERR_UNSUPPORTED;       // pfk_conv2d_f32 only (pfk.h)
   if (!d || !d->weight || d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
   if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return PFK_ERR_BAD_ARG;
   if (d->kh <= 0 || d->kw <= 0 || !(d->kh & 1) || !(d->kw & 1) || d->kh * d->kw > 32) return PFK_ERR_BAD_ARG;

@@ -471,6 +471,80 @@ __global__ __launch_bounds__(256) void convex_upsample4_kernel(const float* __re
   *reinterpret_cast<f32x4*>(out + (b * 2 + 1) * HW8 + o) = oy;
 }
 
+// SEARAFT.upsample_data (sea_raft.py:147-163): convex_upsample4_kernel's flow, operation for operation (same bits), plus the
+// same convex combination of the zero-padded 3x3 neighbourhood of `n` info channels (no factor 8) -> info_out [B][n][8H][8W].
+constexpr int UP_MAX_INFO = 8;
+__global__ __launch_bounds__(256) void convex_upsample_info4_kernel(const float* __restrict__ flow, int flow_ld,
+                                                                    const float* __restrict__ info, int info_ld, int n_info,
+                                                                    const float* __restrict__ mask, int mask_ld,
+                                                                    float* __restrict__ out, float* __restrict__ info_out,
+                                                                    long long M, int H, int W) {
+  const int lane = threadIdx.x & 63;
+  const long long p = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
+  if (p >= M) return;
+  const int idx = lane & 15;
+  const long long hw = (long long)H * W;
+  const long long b = p / hw;
+  const int pix = (int)(p - b * hw);
+  const int y = pix / W, x = pix - y * W;
+  const float* mrow = mask + p * mask_ld + idx * 4;
+  f32x4 m[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m[k] = load4_widen(mrow + k * 64);
+  float vx[9], vy[9], vi[9][UP_MAX_INFO];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
+    vx[k] = 0.f; vy[k] = 0.f;
+#pragma unroll
+    for (int c = 0; c < UP_MAX_INFO; ++c) vi[k][c] = 0.f;
+    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+      const long long q = b * hw + (long long)yy * W + xx;
+      const float* f = flow + q * flow_ld;
+      vx[k] = 8.0f * f[0];
+      vy[k] = 8.0f * f[1];
+      const float* fi = info + q * info_ld;
+#pragma unroll
+      for (int c = 0; c < UP_MAX_INFO; ++c)
+        if (c < n_info) vi[k][c] = fi[c];
+    }
+  }
+  f32x4 ox, oy, oi[UP_MAX_INFO];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) mx = fmaxf(mx, m[k][c]);
+    float e[9], sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { e[k] = expf(m[k][c] - mx); sum += e[k]; }
+    const float inv = 1.0f / sum;
+    float ax = 0.f, ay = 0.f, ai[UP_MAX_INFO];
+#pragma unroll
+    for (int i = 0; i < UP_MAX_INFO; ++i) ai[i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const float wk = e[k] * inv;
+      ax += wk * vx[k];
+      ay += wk * vy[k];
+#pragma unroll
+      for (int i = 0; i < UP_MAX_INFO; ++i) ai[i] += wk * vi[k][i];
+    }
+    ox[c] = ax;
+    oy[c] = ay;
+#pragma unroll
+    for (int i = 0; i < UP_MAX_INFO; ++i) oi[i][c] = ai[i];
+  }
+  const int sy = idx >> 1, sx = (idx & 1) * 4;
+  const long long HW8 = hw * 64;
+  const long long o = (long long)(8 * y + sy) * (8 * W) + 8 * x + sx;
+  *reinterpret_cast<f32x4*>(out + (b * 2 + 0) * HW8 + o) = ox;
+  *reinterpret_cast<f32x4*>(out + (b * 2 + 1) * HW8 + o) = oy;
+#pragma unroll
+  for (int i = 0; i < UP_MAX_INFO; ++i)
+    if (i < n_info) *reinterpret_cast<f32x4*>(info_out + (b * n_info + i) * HW8 + o) = oi[i];
+}
+
 int launch_convex_upsample(const float* flow, int flow_ld, const float* mask, int mask_ld, float* out, long long M, int H, int W,
                            hipStream_t st) {
   if (pfk_aligned16(mask) && pfk_aligned16(out) && (mask_ld & 3) == 0) {
@@ -770,6 +844,21 @@ int pfk_convex_upsample_pm_f32(const float* flow_pm, int flow_ld, const float* m
                                int B, int H, int W, pfk_stream_t stream) {
   if (!flow_pm || !mask || !out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
   return launch_convex_upsample(flow_pm, flow_ld, mask, mask_ld, out, (long long)B * H * W, H, W, static_cast<hipStream_t>(stream));
+}
+
+int pfk_convex_upsample_info_pm_f32(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
+                                    const float* mask, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
+                                    pfk_stream_t stream) {
+  if (!flow_pm || !info_pm || !mask || !flow_out || !info_out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0)
+    return PFK_ERR_BAD_ARG;
+  if (n_info < 1 || n_info > UP_MAX_INFO || info_ld < n_info) return PFK_ERR_BAD_ARG;
+  if (!pfk_aligned16(mask) || (mask_ld & 3) || !pfk_aligned16(flow_out) || !pfk_aligned16(info_out)) return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  const long long blocks = (M + 15) / 16;
+  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(convex_upsample_info4_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
+                     flow_ld, info_pm, info_ld, n_info, mask, mask_ld, flow_out, info_out, M, H, W);
+  return pfk_launch_status();
 }
 
 int pfk_nchw_to_pm_f32(const float* in, float* out, int out_ld, int out_coff, int B, int C, int H,

@@ -422,6 +422,47 @@ void convex_upsample_pm(const Tensor& flow_pm, const Tensor& mask, Tensor out) {
                                       cur_stream()), "convex_upsample_pm");
 }
 
+// SEARAFT.upsample_data: flow_pm [M, >=2] / info_pm [M, >=n] / mask [M, 576] views, flow_out [B, 2, 8H, 8W], info_out [B, n, 8H, 8W]
+void convex_upsample_info_pm(const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask, Tensor flow_out, Tensor info_out) {
+  OpScope scope(flow_pm);
+  check_pm(flow_pm, "flow_pm"); check_pm(info_pm, "info_pm"); check_pm(mask, "mask");
+  check_dev_f32(flow_out, "flow_out"); check_dev_f32(info_out, "info_out");
+  TORCH_CHECK(flow_out.dim() == 4 && flow_out.size(1) == 2 && flow_out.is_contiguous() && flow_out.size(2) % 8 == 0 && flow_out.size(3) % 8 == 0,
+              "convex_upsample_info_pm: flow_out [B, 2, 8H, 8W] contiguous");
+  const int B = flow_out.size(0), H = flow_out.size(2) / 8, W = flow_out.size(3) / 8;
+  const int n = info_out.dim() == 4 ? (int)info_out.size(1) : 0;
+  TORCH_CHECK(info_out.dim() == 4 && info_out.is_contiguous() && info_out.size(0) == B && info_out.size(2) == 8 * H && info_out.size(3) == 8 * W,
+              "convex_upsample_info_pm: info_out [B, n, 8H, 8W] contiguous");
+  const int64_t M = (int64_t)B * H * W;
+  TORCH_CHECK(mask.size(0) == M && mask.size(1) == 576 && flow_pm.size(0) == M && flow_pm.size(1) >= 2 && info_pm.size(0) == M &&
+              info_pm.size(1) >= n, "convex_upsample_info_pm: row counts / widths");
+  check_ok(pfk_convex_upsample_info_pm_f32(fptr(flow_pm), flow_pm.stride(0), fptr(info_pm), info_pm.stride(0), n, fptr(mask),
+                                           mask.stride(0), fptr(flow_out), fptr(info_out), B, H, W, cur_stream()),
+           "convex_upsample_info_pm");
+}
+
+// ConvNextBlock dwconv + LayerNorm: in [B*H*W, C] view (e.g. a slice of the update engine's hx), dw_weight [C, 1, k, k] or [C, k*k]
+// contiguous, out [B*H*W, >= C] view
+void dwconv_layernorm(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                      const Tensor& ln_bias, double eps, Tensor out, int64_t B, int64_t H, int64_t W, int64_t k) {
+  OpScope scope(in);
+  check_pm(in, "in"); check_pm(out, "out");
+  check_dev_f32(dw_weight, "dw_weight"); check_dev_f32(ln_weight, "ln_weight"); check_dev_f32(ln_bias, "ln_bias");
+  const int64_t C = in.size(1);
+  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == in.size(0) && out.size(1) >= C, "dwconv_layernorm: in / out rows");
+  TORCH_CHECK(dw_weight.is_contiguous() && dw_weight.numel() == C * k * k, "dwconv_layernorm: dw_weight [C, k*k] contiguous");
+  TORCH_CHECK(ln_weight.is_contiguous() && ln_weight.numel() == C && ln_bias.is_contiguous() && ln_bias.numel() == C,
+              "dwconv_layernorm: LayerNorm weight / bias [C]");
+  const float* db = nullptr;
+  if (dw_bias.has_value()) {
+    check_dev_f32(*dw_bias, "dw_bias");
+    TORCH_CHECK(dw_bias->is_contiguous() && dw_bias->numel() == C, "dwconv_layernorm: dw_bias [C]");
+    db = fptr(*dw_bias);
+  }
+  check_ok(pfk_dwconv_layernorm_f32(fptr(in), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps, fptr(out),
+                                    out.stride(0), B, H, W, C, k, cur_stream()), "dwconv_layernorm");
+}
+
 // fused mask conv2 + softmax + convex upsampling: x [M, cin] (a view of the fh|mask hidden buffer), weight / bias row-permuted (pfk.h)
 void mask_upsample(const Tensor& x, const Tensor& weight_perm, const c10::optional<Tensor>& bias_perm, double scale,
                    const Tensor& flow_pm, Tensor out) {
@@ -936,6 +977,9 @@ TORCH_LIBRARY(pfk, m) {
   m.def("flow_from_coords(Tensor coords0, Tensor coords1, Tensor(a!) flow_out) -> ()");
   m.def("convex_upsample(Tensor flow, Tensor mask, Tensor(a!) out) -> ()");
   m.def("convex_upsample_pm(Tensor flow_pm, Tensor mask, Tensor(a!) out) -> ()");
+  m.def("convex_upsample_info_pm(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor(a!) flow_out, Tensor(b!) info_out) -> ()");
+  m.def("dwconv_layernorm(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, Tensor(a!) out, "
+        "int B, int H, int W, int k) -> ()");
   m.def("mask_upsample(Tensor x, Tensor weight_perm, Tensor? bias_perm, float scale, Tensor flow_pm, Tensor(a!) out) -> ()");
   m.def("upflow8(Tensor coords0, Tensor coords1, Tensor(a!) out) -> ()");
   m.def("altcorr_forward(Tensor fmap1, Tensor fmap2, Tensor coords, int radius) -> Tensor");
@@ -966,6 +1010,8 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("convex_upsample", &convex_upsample);
   m.impl("convex_upsample_pm", &convex_upsample_pm);
   m.impl("mask_upsample", &mask_upsample);
+  m.impl("convex_upsample_info_pm", &convex_upsample_info_pm);
+  m.impl("dwconv_layernorm", &dwconv_layernorm);
   m.impl("upflow8", &upflow8);
   m.impl("altcorr_forward", &altcorr_forward);
   m.impl("altcorr_backward", &altcorr_backward);

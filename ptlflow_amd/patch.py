@@ -74,6 +74,74 @@ _ENCODERS = {
 _PYRAMID = {"ptlflow.models.sea_raft.sea_raft": "bilinear_f2"}
 
 
+# (module of the class, class name) of SEA-RAFT update blocks (sea_raft/update.py:39-54: RAFT's motion encoder + ConvNeXt blocks,
+# `forward(net, inp, corr, flow) -> net`); installed only with `accelerate(model, sea_raft_update=True)` (extendable with
+# `register_sea_raft_update_block`), and only when the state_dict names / shapes are exactly sea_update.sea_block_shapes
+_SEA_UPDATE_BLOCKS = {("ptlflow.models.sea_raft.update", "BasicUpdateBlock")}
+_SEA_UPSAMPLE = "_pfk_original_upsample_data"
+
+
+def register_sea_raft_update_block(module: str, cls: str = "BasicUpdateBlock") -> None:
+    """Declare another module's block to be SEA-RAFT's BasicUpdateBlock (the shape check still applies)."""
+    _SEA_UPDATE_BLOCKS.add((module, cls))
+
+
+def match_sea_raft(model: torch.nn.Module) -> Optional[Tuple[int, int]]:
+    """(corr_channels, num_blocks) when `model.update_block`, `model.flow_head` and `model.upsample_weight` are provably SEA-RAFT's
+    (sea_raft/update.py:39-54, sea_raft.py:114-126 at dim = 128), else None."""
+    from .sea_update import HEAD_SHAPES, sea_block_shapes
+    block = getattr(model, "update_block", None)
+    if block is None or (type(block).__module__, type(block).__name__) not in _SEA_UPDATE_BLOCKS:
+        return None
+    sd = {k: tuple(v.shape) for k, v in block.state_dict().items()}
+    w = sd.get("encoder.convc1.weight")
+    if w is None or len(w) != 4:
+        return None
+    nb = len({k.split(".")[1] for k in sd if k.startswith("refine.")})
+    if nb < 1 or sd != sea_block_shapes(int(w[1]), nb):
+        return None
+    for attr, want in HEAD_SHAPES.items():
+        head = getattr(model, attr, None)
+        if not isinstance(head, torch.nn.Sequential) or len(head) != 3 or not isinstance(head[1], torch.nn.ReLU):
+            return None
+        if {k: tuple(v.shape) for k, v in head.state_dict().items()} != want:
+            return None
+    return int(w[1]), nb
+
+
+def _install_sea_raft(model: torch.nn.Module) -> bool:
+    """SEA-RAFT's update block, heads and `upsample_data` (sea_update.py); True when installed (or already there)."""
+    from .sea_update import PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam
+    if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):
+        return True
+    m = match_sea_raft(model)
+    if m is None:
+        return False
+    block = PfkSeaRaftUpdateBlock(model.update_block, num_blocks=m[1], corr_channels=m[0])
+    block._heads = {"flow_head": model.flow_head, "upsample_weight": model.upsample_weight}
+    model.update_block = block
+    model.flow_head = _SeaHeadSeam(model.flow_head, block, "flow_head")
+    model.upsample_weight = _SeaHeadSeam(model.upsample_weight, block, "upsample_weight")
+    if callable(getattr(model, "upsample_data", None)) and _SEA_UPSAMPLE not in model.__dict__:
+        model.__dict__[_SEA_UPSAMPLE] = model.upsample_data
+        model.__dict__["upsample_data"] = _UpsampleDataSeam(model.upsample_data)
+    return True
+
+
+def _restore_sea_raft(model: torch.nn.Module) -> None:
+    from .sea_update import PfkSeaRaftUpdateBlock, _SeaHeadSeam
+    if _SEA_UPSAMPLE in model.__dict__:
+        del model.__dict__[_SEA_UPSAMPLE]
+        model.__dict__.pop("upsample_data", None)
+    for attr in ("flow_head", "upsample_weight"):
+        head = getattr(model, attr, None)
+        if isinstance(head, _SeaHeadSeam):
+            setattr(model, attr, head._ref[0])
+    ub = getattr(model, "update_block", None)
+    if isinstance(ub, PfkSeaRaftUpdateBlock):
+        model.update_block = ub._ref[0]
+
+
 def _with_corr_channels(spec: UpdateSpec, corr_channels: int) -> UpdateSpec:
     from dataclasses import replace
     return replace(spec, corr_channels=corr_channels)
@@ -487,7 +555,8 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
 
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
-               skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None) -> torch.nn.Module:
+               skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
+               sea_raft_update: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -500,7 +569,10 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     model is in eval mode when it is accelerated — silently off otherwise; ``True``: the same, with a warning saying why when it
     is refused; ``False`` (opt-out): every iteration keeps its mask head and upsampling, as the reference (the fused kernel
     still serves them where the same checks pass; ``fuse_mask_upsample=False`` keeps the two separate launches).  Re-armed per
-    forward: train mode, a gradient graph, a half / bf16 model or a changed `iters` are honoured (`_DeadWorkSkip`)."""
+    forward: train mode, a gradient graph, a half / bf16 model or a changed `iters` are honoured (`_DeadWorkSkip`).
+    ``sea_raft_update`` (default False): on a SEA-RAFT model, also replace its update block (motion encoder + ConvNeXt blocks), its
+    `flow_head` / `upsample_weight` heads and its `upsample_data` by the kernels of sea_update.py (fp32 inference; anything else
+    keeps the model's modules).  Off by default: plain `accelerate(model)` leaves SEA-RAFT's block to torch as before."""
     load_native()
     mod_name = type(model).__module__
     # registered classes (`class raft(RAFT)`) live in the same module as the implementation
@@ -512,9 +584,10 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
         spec = match_update_block(model.update_block)
         if spec is not None:
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
+    sea = bool(sea_raft_update) and _install_sea_raft(model)
     hook = getattr(mod, "get_corr_block", None)
     if corr and hasattr(mod, _ORIG) and hasattr(hook, "channels_last"):      # (default for callers that are not a model's forward)
-        hook.channels_last = isinstance(getattr(model, "update_block", None), PfkUpdateBlock)
+        hook.channels_last = sea or isinstance(getattr(model, "update_block", None), PfkUpdateBlock)
         _bracket_forward_with_layout(model, hook.channels_last)
     cb = getattr(model, "corr_block", None)
     if corr and isinstance(cb, torch.nn.Module) and (type(cb).__module__, type(cb).__name__) in _BILINEAR_VOLUMES \
@@ -549,6 +622,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
 
 
 def restore(model: torch.nn.Module) -> torch.nn.Module:
+    _restore_sea_raft(model)
     state = model.__dict__.pop(_LAYOUT_HOOKS, None)
     if state is not None:
         for h in state["handles"]:

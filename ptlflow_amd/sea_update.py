@@ -1,0 +1,385 @@
+"""SEA-RAFT's refinement loop on gfx950 kernels: the update block (ptlflow/models/sea_raft/update.py:18-54, the ConvNeXt blocks of
+layer.py:44-83), the flow / upsample-weight heads (sea_raft.py:114-126) and `upsample_data` (sea_raft.py:147-163).
+
+`SeaUpdateEngine` is an `UpdateEngine` without GRU passes.  Its `hx` buffer is RAFT's `[h (128) | inp (128) | motion (126) | flow (2)]`
+and that is exactly the ConvNeXt block input `cat([net, cat([context, motion_features])])` (update.py:50-53): 384 channels.  Per
+iteration, after the caller's lookup:
+
+    motion encoder                       UpdateEngine.motion / motion_grouped    -> hx[:, 256:382]
+    per ConvNeXt block i (2):
+      dwconv 7x7 + LayerNorm             pfk_dwconv_layernorm_f32  (hx)          -> ln   [M, 384]
+      pwconv1 + GELU                     pfk_conv2d_f32, PFK_EPI_LINEAR_GELU     -> mid  [M, 512]
+      gamma * pwconv2 + input            pfk_conv2d_f32, LINEAR + residual hx    -> res  [M, 384]   (gamma folded into W2, b2)
+      final 1x1 384 -> 128               pfk_conv2d_f32                          -> hx[:, :128]
+    flow_head[0] | upsample_weight[0]    UpdateEngine.heads_conv1 (one GEMM, relu) -> fm [M, 512]
+    flow_head[2] 3x3 256 -> 6            pfk_conv2d_f32, cout 6                  -> fo   [M, 8]
+    upsample_weight[2] 1x1 256 -> 576    UpdateEngine._conv                       -> mask [M, 576]
+    upsample_data                        pfk_convex_upsample_info_pm_f32          -> flow_up, info_up
+
+Layer scale: `gamma * (x @ W2^T + b2)` is computed as `x @ (gamma W2)^T + gamma b2`, one rounding moved.
+
+The seams (`accelerate(model, sea_raft_update=True)`, patch.py) hand the model's own loop (sea_raft.py:217-236) views of these
+buffers, the way `PfkUpdateBlock` does for RAFT: `update_block(net, context, corr, flow) -> net` is the engine's h slice, and
+`flow_head(net)` / `upsample_weight(net)` recognise that very object and run the heads from it.  Everything the kernels do not
+implement — CPU tensors, gradient graphs, other dtypes, autocast — is passed to the wrapped modules unchanged.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from .packing import pack_conv_weight
+from .update import EPI_LINEAR, UpdateEngine, UpdateSpec
+
+EPI_LINEAR_GELU = 3        # enum pfk_epilogue (include/pfk.h)
+LN_EPS = 1e-6              # sea_raft/layer.py:57 (LayerNorm(dim, eps=1e-6))
+
+
+def sea_spec(corr_channels: int = 324) -> UpdateSpec:
+    """SEA-RAFT's BasicUpdateBlock at cdim = hdim = 128 (sea_raft/update.py:39-47): RAFT's motion encoder, no GRU, heads of
+    sea_raft.py:114-126 (both hidden convolutions 128 -> 256, mask 576)."""
+    return UpdateSpec(128, 128, corr_channels, 256, 192, 128, 64, 126, (), 256, True)
+
+
+def sea_block_shapes(corr_channels: int, num_blocks: int) -> Dict[str, tuple]:
+    """state_dict names / shapes of sea_raft/update.py:BasicUpdateBlock (cdim = hdim = 128, ConvNextBlock(384, 128))."""
+    sh: Dict[str, tuple] = {}
+
+    def conv(name, co, ci, k):
+        sh[name + ".weight"] = (co, ci, k, k)
+        sh[name + ".bias"] = (co,)
+
+    conv("encoder.convc1", 256, corr_channels, 1)
+    conv("encoder.convc2", 192, 256, 3)
+    conv("encoder.convf1", 128, 2, 7)
+    conv("encoder.convf2", 64, 128, 3)
+    conv("encoder.conv", 126, 256, 3)
+    for i in range(num_blocks):
+        p = f"refine.{i}."
+        sh[p + "dwconv.weight"] = (384, 1, 7, 7)
+        sh[p + "dwconv.bias"] = (384,)
+        sh[p + "norm.weight"] = (384,)
+        sh[p + "norm.bias"] = (384,)
+        sh[p + "pwconv1.weight"] = (512, 384)
+        sh[p + "pwconv1.bias"] = (512,)
+        sh[p + "pwconv2.weight"] = (384, 512)
+        sh[p + "pwconv2.bias"] = (384,)
+        sh[p + "gamma"] = (384,)
+        conv(p + "final", 128, 384, 1)
+    return sh
+
+
+HEAD_SHAPES = {
+    "flow_head": {"0.weight": (256, 128, 3, 3), "0.bias": (256,), "2.weight": (6, 256, 3, 3), "2.bias": (6,)},
+    "upsample_weight": {"0.weight": (256, 128, 3, 3), "0.bias": (256,), "2.weight": (576, 256, 1, 1), "2.bias": (576,)},
+}
+
+
+class SeaUpdateEngine(UpdateEngine):
+    """Packed weights and pixel-major buffers of SEA-RAFT's refinement (module docstring).  `params`: the update block's parameters
+    (`encoder.*`, `refine.{i}.*`) and the heads' as `flow_head.{0,2}.*`, `upsample_weight.{0,2}.*`.  fp32 only."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], spec: UpdateSpec, device: torch.device, num_blocks: int = 2):
+        self.num_blocks = int(num_blocks)
+        super().__init__(params, spec, device, "fp32")
+
+    # ------------------------------------------------------------------ weights
+    def pack(self, P: Dict[str, torch.Tensor]) -> None:
+        # the motion encoder, the fused flow_head[0] | upsample_weight[0] GEMM (`fm`) and the 576-channel mask conv (`mk`) are RAFT's:
+        # packed by UpdateEngine under its names
+        alias = {"flow_head.conv1.": "flow_head.0.", "mask.0.": "upsample_weight.0.", "mask.2.": "upsample_weight.2."}
+        Q = {k: v for k, v in P.items() if k.startswith("encoder.")}
+        for dst, src in alias.items():
+            for t in ("weight", "bias"):
+                Q[dst + t] = P[src + t]
+        super().pack(Q)
+        dev = self.device
+
+        def g(name):
+            return P[name].detach().to(device=dev, dtype=torch.float32)
+
+        C = self.spec.hx_channels
+        w = self.w
+        for i in range(self.num_blocks):
+            p = f"refine.{i}."
+            w[f"dw{i}.w"] = g(p + "dwconv.weight").reshape(C, -1).contiguous()
+            w[f"dw{i}.b"] = g(p + "dwconv.bias").contiguous()
+            w[f"ln{i}.w"] = g(p + "norm.weight").contiguous()
+            w[f"ln{i}.b"] = g(p + "norm.bias").contiguous()
+            w1 = g(p + "pwconv1.weight")
+            w[f"p1{i}.w"] = pack_conv_weight(w1[:, :, None, None], [(0, C, C)])
+            w[f"p1{i}.b"] = g(p + "pwconv1.bias").contiguous()
+            gamma = g(p + "gamma") if (p + "gamma") in P else torch.ones(C, device=dev)
+            w2 = g(p + "pwconv2.weight")
+            w[f"p2{i}.w"] = pack_conv_weight((gamma[:, None] * w2)[:, :, None, None], [(0, w2.shape[1], w2.shape[1])])
+            w[f"p2{i}.b"] = (gamma * g(p + "pwconv2.bias")).contiguous()
+            w[f"fi{i}.w"] = pack_conv_weight(g(p + "final.weight"), [(0, C, C)])
+            w[f"fi{i}.b"] = g(p + "final.bias").contiguous()
+            self._real_cin.update({f"p1{i}": C, f"p2{i}": w2.shape[1], f"fi{i}": C})
+        w["fo.w"] = pack_conv_weight(g("flow_head.2.weight"), [(0, self.spec.fh_hidden, self.spec.fh_hidden)])
+        w["fo.b"] = g("flow_head.2.bias").contiguous()
+        self._real_cin["fo"] = self.spec.fh_hidden
+        self.mid_channels = int(P["refine.0.pwconv1.weight"].shape[0]) if self.num_blocks else 0
+
+    # ------------------------------------------------------------------ buffers
+    def bind(self, B: int, H: int, W: int) -> None:
+        if self._shape == (B, H, W):
+            return
+        super().bind(B, H, W)
+        M, dev = B * H * W, self.device
+        C = self.spec.hx_channels
+        self.ln = torch.zeros(M, C, device=dev, dtype=torch.float32)
+        self.mid = torch.zeros(M, self.mid_channels, device=dev, dtype=torch.float32)
+        self.res = torch.zeros(M, C, device=dev, dtype=torch.float32)
+        self.fo = torch.zeros(M, 8, device=dev, dtype=torch.float32)      # flow_head output: delta (2) | info (4) | pad
+
+    # ------------------------------------------------------------------ one iteration
+    def refine(self) -> None:
+        """`for blk in self.refine: net = blk(cat([net, inp]))` (update.py:52-53) on hx: each block's `final` writes the new net
+        into hx[:, :128], which the next block (and the heads) read."""
+        B, H, W = self._shape
+        C = self.spec.hx_channels
+        for i in range(self.num_blocks):
+            self.ops.dwconv_layernorm(self.hx, self.w[f"dw{i}.w"], self.w[f"dw{i}.b"], self.w[f"ln{i}.w"], self.w[f"ln{i}.b"], LN_EPS,
+                                      self.ln, B, H, W, 7)
+            self._conv([self.ln], 1, 1, f"p1{i}", self.mid_channels, relu=False, out=self.mid, epi=EPI_LINEAR_GELU)
+            self._conv([self.mid], 1, 1, f"p2{i}", C, relu=False, out=self.res, residual=self.hx)
+            self._conv([self.res], 1, 1, f"fi{i}", self.spec.hidden, relu=False, out=self.hx[:, : self.spec.hidden])
+
+    def update(self, corr_pm: torch.Tensor) -> None:
+        """update.py:49-54: motion encoder into hx, then the ConvNeXt blocks; `flow` must already be in hx."""
+        B, H, W = self._shape
+        if self.can_group and B * H * W < 28160:
+            self.motion_grouped(corr_pm)       # convc1 | convf2 as one grouped launch (same bits as motion())
+        else:
+            self.motion(corr_pm)
+        self.refine()
+
+    def flow_head_out(self) -> None:
+        """flow_head[2] (3x3, 256 -> 6) on the flow-head half of fm -> fo[:, :6]: delta flow (2) | info (4)"""
+        self._conv([self.fm[:, : self.spec.fh_hidden]], 3, 3, "fo", 6, relu=False, out=self.fo[:, :6])
+
+    def mask_logits(self, scale: float = 1.0) -> None:
+        """upsample_weight[2] (1x1, 256 -> 576) on the mask half of fm, times `scale` -> mask"""
+        self._conv([self.fm[:, self.spec.fh_hidden:]], 1, 1, "mk", self.spec.mask_channels, relu=False, scale=scale, out=self.mask,
+                   epi=EPI_LINEAR)
+
+    def upsample(self, flow_pm: torch.Tensor, info_pm: torch.Tensor, mask_pm: torch.Tensor, flow_up: torch.Tensor,
+                 info_up: torch.Tensor) -> None:
+        """upsample_data (sea_raft.py:147-163) on pixel-major rows; mask_pm already scaled by 0.25"""
+        self.ops.convex_upsample_info_pm(flow_pm, info_pm, mask_pm, flow_up, info_up)
+
+    def fo_nchw(self) -> torch.Tensor:
+        B, H, W = self._shape
+        return self.fo[:, :6].unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
+
+
+def _fp32_eligible(*tensors) -> bool:
+    """GPU fp32 tensors, no gradient graph, no autocast region: what the kernels implement"""
+    t0 = tensors[0]
+    if not t0.is_cuda or torch.is_autocast_enabled("cuda"):
+        return False
+    for t in tensors:
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != t0.device:
+            return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+
+
+class PfkSeaRaftUpdateBlock(torch.nn.Module):
+    """Drop-in for SEA-RAFT's ``model.update_block``: ``forward(net, inp, corr, flow) -> net`` NCHW (sea_raft/update.py:49-54), a
+    view of the engine's h slice with channels-last strides, overwritten by the next call (the reference loop rebinds `net` every
+    iteration, sea_raft.py:223).  Keeps the wrapped sub-modules (`encoder`, `refine`): state_dict keys, checkpoints and optimizers
+    are unchanged.  The heads' parameters are read through `_heads` (not registered here: they stay the model's own children)."""
+
+    def __init__(self, ref_block: torch.nn.Module, num_blocks: int, corr_channels: int):
+        super().__init__()
+        for name, child in ref_block.named_children():
+            self.add_module(name, child)
+        self._ref = [ref_block]
+        self.training = ref_block.training
+        self.spec = sea_spec(corr_channels)
+        self.num_blocks = num_blocks
+        self._heads: Dict[str, torch.nn.Module] = {}   # "flow_head" / "upsample_weight" -> the model's modules (set by patch)
+        self._engine: Optional[SeaUpdateEngine] = None
+        self._versions = None
+        self._inp_ref, self._inp_version = None, -1
+        self._last_out, self._last_version = None, -1
+        self._fm_for = None        # the `net` object whose flow_head[0] | upsample_weight[0] activation `fm` holds
+        self.calls = 0             # kernel-path calls (tests count them)
+
+    def _all_params(self) -> Dict[str, torch.nn.Parameter]:
+        P = dict(self.named_parameters())
+        for name, mod in self._heads.items():
+            P.update({f"{name}.{k}": v for k, v in mod.named_parameters()})
+        return P
+
+    def _get_engine(self, device) -> SeaUpdateEngine:
+        P = self._all_params()
+        v = tuple((p.data_ptr(), p._version) for p in P.values())
+        if self._engine is None or self._engine.device != device:
+            self._engine = SeaUpdateEngine(P, self.spec, device, self.num_blocks)
+            self._versions = v
+        elif v != self._versions:
+            self._engine.pack(P)
+            self._versions = v
+        return self._engine
+
+    def owns(self, x: torch.Tensor) -> bool:
+        """`x` is the net this block handed out last, untouched since"""
+        return x is self._last_out and x._version == self._last_version
+
+    @staticmethod
+    def _corr_pm(corr: torch.Tensor, M: int) -> Optional[torch.Tensor]:
+        """the [M, C] rows behind a channel view of the lookup (what ptlflow_amd.CorrBlock hands out), or None"""
+        padded = getattr(corr, "_pfk_padded_pm", None)
+        if padded is not None and padded.shape[0] == M and padded.dtype == torch.float32:
+            return padded
+        cpm = corr.permute(0, 2, 3, 1)
+        if corr.dtype == torch.float32 and cpm.is_contiguous() and corr.shape[1] % 4 == 0 and corr.data_ptr() % 16 == 0:
+            return cpm.reshape(M, corr.shape[1])
+        return None
+
+    def forward(self, net, inp, corr, flow):
+        params = list(self.parameters()) + [p for m in self._heads.values() for p in m.parameters()]
+        ok = (torch.is_tensor(corr) and _fp32_eligible(net, inp, corr, flow, *params) and net.dim() == 4
+              and corr.shape[1] == self.spec.corr_channels and net.shape[1] == self.spec.hidden and inp.shape[1] == self.spec.context)
+        B, _, H, W = net.shape if net.dim() == 4 else (0, 0, 0, 0)
+        corr_pm = self._corr_pm(corr, B * H * W) if ok else None
+        if corr_pm is None:
+            # the wrapped module, on the NCHW tensor the family's own correlation block would have handed it (the B1 hook's
+            # channel view holds the same values; a dense copy keeps the module's convolutions on their usual layout)
+            self._last_out, self._fm_for = None, None
+            return self._ref[0](net, inp, corr.contiguous() if torch.is_tensor(corr) else corr, flow)
+        with torch.no_grad():
+            eng = self._get_engine(net.device)
+            eng.bind(B, H, W)
+            ops = eng.ops
+            new_forward = not self.owns(net)
+            if new_forward:
+                eng.watch_faults()
+                ops.nchw_to_pm(net.contiguous(), eng.h_view)
+            if new_forward or inp is not self._inp_ref or inp._version != self._inp_version:
+                ops.nchw_to_pm(inp.contiguous(), eng.inp_view)
+                self._inp_ref, self._inp_version = inp, inp._version
+            ops.nchw_to_pm(flow.contiguous(), eng.flow_view)
+            eng.update(corr_pm)
+            out = eng.net_nchw()
+        self.calls += 1
+        self._last_out, self._last_version, self._fm_for = out, out._version, None
+        return out
+
+    def heads_fm(self, net: torch.Tensor) -> SeaUpdateEngine:
+        """flow_head[0] | upsample_weight[0] (+ relu) from the engine's h, once per handed-out net"""
+        eng = self._engine
+        if self._fm_for is not net:
+            with torch.no_grad():
+                eng.heads_conv1(True)
+            self._fm_for = net
+        return eng
+
+
+class _SeaHeadSeam(torch.nn.Module):
+    """Wraps ``model.flow_head`` / ``model.upsample_weight`` (sea_raft.py:114-126), keeping their children 0 / 1 / 2.  Called with the
+    net view the update block just handed out, it runs from the engine's pixel-major state; any other input (the `init_conv` split
+    before the loop, sea_raft.py:191-197, CPU, half, autocast, gradient graphs) goes to the original module."""
+
+    def __init__(self, ref: torch.nn.Module, block: PfkSeaRaftUpdateBlock, kind: str):
+        super().__init__()
+        for name, child in ref.named_children():
+            self.add_module(name, child)
+        self._ref = [ref]
+        self._block = [block]
+        self.kind = kind
+        self.training = ref.training
+        self.calls = 0
+
+    def __getitem__(self, i):          # model.flow_head[0] etc. keep working (nn.Sequential indexing)
+        return list(self._modules.values())[i]
+
+    def __len__(self):
+        return len(self._modules)
+
+    def forward(self, x):
+        blk = self._block[0]
+        if not (torch.is_tensor(x) and blk.owns(x) and _fp32_eligible(x, *self.parameters())):
+            return self._ref[0](x)
+        eng = blk.heads_fm(x)
+        with torch.no_grad():
+            if self.kind == "flow_head":
+                eng.flow_head_out()
+                out = eng.fo_nchw()
+            else:
+                eng.mask_logits(1.0)
+                out = eng.mask_nchw()
+        self.calls += 1
+        return out
+
+
+class _UpsampleDataSeam:
+    """`model.upsample_data(flow, info, mask)` (sea_raft.py:147-163) shadowed on the instance by `pfk_convex_upsample_info_pm_f32`,
+    behind a behaviour probe like seam B5's: on the first eligible call the model's own method and the kernel run on a small random
+    input and the kernel is used only if they agree to 1e-5.  Pixel-major rows are read without a copy where the strides allow
+    (the channels-last `0.25 * upsample_weight(net)` and the info slice of `flow_head(net)`)."""
+
+    def __init__(self, original):
+        self.original = original
+        self.ok = None
+        self.calls = 0
+
+    @staticmethod
+    def _rows(t: torch.Tensor, aligned: bool = False) -> torch.Tensor:
+        """[B, C, H, W] -> its [B*H*W, C] pixel-major rows: a view where the strides allow, else one copy.  `aligned`: 16-byte rows"""
+        B, C, H, W = t.shape
+        r = t.permute(0, 2, 3, 1).reshape(B * H * W, C)
+        if r.stride(1) != 1 or (aligned and (r.data_ptr() % 16 or r.stride(0) % 4)):
+            r = r.clone(memory_format=torch.contiguous_format)
+        return r
+
+    @classmethod
+    def _kernel(cls, flow, info, mask):
+        B, _, H, W = flow.shape
+        n = info.shape[1]
+        flow_up = torch.empty(B, 2, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
+        info_up = torch.empty(B, n, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
+        torch.ops.pfk.convex_upsample_info_pm(cls._rows(flow), cls._rows(info), cls._rows(mask, aligned=True), flow_up, info_up)
+        return flow_up, info_up
+
+    def _probe(self, device) -> bool:
+        g = torch.Generator().manual_seed(7)
+        flow = (torch.randn(2, 2, 5, 7, generator=g) * 3).to(device)
+        info = torch.randn(2, 4, 5, 7, generator=g).to(device)
+        mask = torch.randn(2, 576, 5, 7, generator=g).to(device)
+        try:
+            with torch.no_grad():
+                want = self.original(flow, info, mask)
+            got = self._kernel(flow, info, mask)
+            ok = len(want) == 2 and all(tuple(a.shape) == tuple(b.shape) and
+                                        float((a.float() - b).abs().max()) <= 1e-5 * max(1.0, float(a.float().abs().max()))
+                                        for a, b in zip(want, got))
+        except Exception:
+            ok = False
+        if not ok:
+            import warnings
+            warnings.warn("ptlflow_amd: this model's upsample_data is not SEA-RAFT's; it keeps the model's own method",
+                          RuntimeWarning, stacklevel=3)
+        return ok
+
+    def __call__(self, *args, **kwargs):
+        if kwargs or len(args) != 3 or not all(torch.is_tensor(a) for a in args):
+            return self.original(*args, **kwargs)
+        flow, info, mask = args
+        eligible = (_fp32_eligible(flow, info, mask) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
+                    and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
+                    and info.shape[0] == flow.shape[0] == mask.shape[0]
+                    and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
+        if not eligible:
+            return self.original(flow, info, mask)
+        if self.ok is None:
+            if torch.cuda.is_current_stream_capturing():
+                return self.original(flow, info, mask)
+            self.ok = self._probe(flow.device)
+        if not self.ok:
+            return self.original(flow, info, mask)
+        self.calls += 1
+        return self._kernel(flow, info, mask)

@@ -239,8 +239,9 @@ class UpdateEngine:
             w["tv.b"] = None
             self.gamma = float(P["aggregator.gamma"].detach().float().cpu().item())   # one host read per (re)pack
             self._real_cin["tv"] = s.motion_channels
-        w["fh2.w"] = pack_flow_head_weight(g("flow_head.conv2.weight"))
-        w["fh2.b"] = g("flow_head.conv2.bias").contiguous()
+        if "flow_head.conv2.weight" in P:     # (SEA-RAFT's 6-channel flow head conv2 is packed by its own engine, sea_update.py)
+            w["fh2.w"] = pack_flow_head_weight(g("flow_head.conv2.weight"))
+            w["fh2.b"] = g("flow_head.conv2.bias").contiguous()
         self.w = w
 
     # ------------------------------------------------------------------ buffers

@@ -1,0 +1,65 @@
+"""Writes tests/golden/sea_raft_update.pt from the reference's OWN SEA-RAFT modules (imported unmodified through
+oracle/ref_loader.py; build container only):
+
+    python scripts/make_sea_raft_golden.py
+
+A reference `SEARAFT` is built, its `update_block`, `flow_head`, `upsample_weight` get seeded weights (tests/sea_seam_model.py
+`seeded_params`: every parameter in name-sorted order from one seed, the layer scale gamma at O(1)) and one refinement step runs
+at B = 1 on a 7 x 8 grid with 324 correlation channels (small: the fixture stays a few hundred KB;
+the kernels are checked on large grids by their own tests):
+
+    net_out = update_block(net, inp, corr, flow)                    sea_raft/update.py:49-54
+    flow_update = flow_head(net_out); weight_update = 0.25 * upsample_weight(net_out)
+    flow_8x = flow + flow_update[:, :2]; info_8x = flow_update[:, 2:]
+    up_flow, up_info = upsample_data(flow_8x, info_8x, weight_update)  sea_raft.py:147-163
+
+Inputs and outputs are stored, weights are not (tests/test_gpu_sea_raft.py regenerates them from the seed).
+"""
+from __future__ import annotations
+
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from oracle import ref_loader  # noqa: E402
+from sea_seam_model import seeded_params  # noqa: E402
+
+SEED = 2024
+B, H, W = 1, 7, 8
+OUT = os.path.join(ROOT, "tests", "golden", "sea_raft_update.pt")
+
+
+def main() -> None:
+    mod = ref_loader.ref_module("ptlflow.models.sea_raft.sea_raft")
+    torch.manual_seed(0)
+    model = mod.SEARAFT(block_dims=[64, 128, 256], iters=4).eval()
+    keys = {k: tuple(v.shape) for k, v in model.state_dict().items()
+            if k.split(".")[0] in ("update_block", "flow_head", "upsample_weight")}
+    model.load_state_dict(seeded_params(keys, SEED), strict=False)
+    g = torch.Generator().manual_seed(SEED + 1)
+    net = torch.tanh(torch.randn(B, 128, H, W, generator=g))
+    inp = torch.relu(torch.randn(B, 128, H, W, generator=g))
+    corr = torch.randn(B, 324, H, W, generator=g)
+    flow = torch.randn(B, 2, H, W, generator=g) * 2
+    with torch.no_grad():
+        net_out = model.update_block(net, inp, corr, flow)
+        flow_update = model.flow_head(net_out)
+        weight_update = 0.25 * model.upsample_weight(net_out)
+        flow_8x = flow + flow_update[:, :2]
+        info_8x = flow_update[:, 2:]
+        up_flow, up_info = model.upsample_data(flow_8x, info_8x, weight_update)
+    data = {"seed": SEED, "net": net, "inp": inp, "corr": corr, "flow": flow, "net_out": net_out, "flow_update": flow_update,
+            "weight_update": weight_update, "flow_8x": flow_8x, "info_8x": info_8x.contiguous(), "up_flow": up_flow,
+            "up_info": up_info}
+    data = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in data.items()}
+    torch.save(data, OUT)
+    print(f"wrote {OUT} ({os.path.getsize(OUT) / 1e6:.2f} MB)")
+
+
+if __name__ == "__main__":
+    main()
