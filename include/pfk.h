@@ -277,6 +277,19 @@ int pfk_conv2d_f32(const pfk_conv_desc* d, pfk_stream_t stream);
 #define PFK_CONV_GROUP_MAX 4
 int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream);
 
+/* Winograd F(2x2,3x3) form of pfk_conv2d_f32 for 3x3 stride-1 convolutions (fp32 MFMA, fp32 accumulate): 16 GEMMs over the
+ * transformed input, 2.25x fewer products than the direct form.  Supported: one source with channels % 32 == 0, kh = kw = 3,
+ * stride 0 or 1, the LINEAR epilogue without residual or relu_after_residual, `cout_active` (0, >= cout, or a multiple of 64:
+ * exactly the bits the full launch gives those channels).  Anything else returns PFK_ERR_UNSUPPORTED.  `workspace` and
+ * `cout_split` are ignored (one schedule, no workspace: safe under graph capture).  Results differ from pfk_conv2d_f32 by fp32
+ * rounding (other products, other order); the same inputs give the same bits on every run.
+ * d->weight = the transformed weight, pfk_conv_wino_weight_floats(cin, cout) floats, 16-byte aligned:
+ *   U = G g G^T per (co, c), G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1], rounded to fp32 once, laid out
+ *   [ceil(cout/64)][cin/8][16 (xi = 4*row + col of U)][64 (nl)][8 (slot)] with co = 64*cb + nl, c = 8*ks + cc,
+ *   slot = ((cc & 3)*2 + (cc >> 2)) ^ (((nl >> 2) & 3)*2), zeros for co >= cout (ptlflow_amd/packing.py, pack_wino_weight) */
+long long pfk_conv_wino_weight_floats(int cin, int cout);   /* < 0 (PFK_ERR_BAD_ARG) unless cin % 32 == 0, cin, cout > 0 */
+int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream);
+
 /* Same convolution on the bf16 matrix cores with split operands (fp32 in HBM, fp32 accumulate, fp32 epilogue).
  * Every fp32 operand x is replaced by the sum of its first `nsplit` bf16 planes x0 = bf16(x), x1 = bf16(x - x0),
  * x2 = bf16(x - x0 - x1); a product keeps the terms a_i*b_j with i + j < nsplit:

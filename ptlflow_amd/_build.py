@@ -38,6 +38,7 @@ HIP_SOURCES = [
     ("pfk_gemm.hip", []),
     ("pfk_gemm_bf.hip", []),
     ("pfk_gemm_b16.hip", []),                 # K8b: bf16 activation storage, LDS-DMA for both operands
+    ("pfk_wino.hip", []),                     # Winograd F(2x2,3x3) for the update block's 3x3 convolutions
     ("pfk_corr.hip", ["-ffp-contract=off"]),  # index-exact coordinate arithmetic
     ("pfk_misc.hip", ["-ffp-contract=off"]),
     ("pfk_altcorr.hip", []),

@@ -209,6 +209,33 @@ void conv2d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, in
   else check_ok(pfk_conv2d_f32(&d, cur_stream()), "conv2d");
 }
 
+// Winograd F(2x2,3x3) 3x3 convolution (pfk_conv2d_wino_f32): one fp32 source [B*H*W, cin] view, the transformed weight of
+// packing.pack_wino_weight (flat, pfk_conv_wino_weight_floats(cin, cout) floats), LINEAR epilogue into an [M, cout] view
+void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                 int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active) {
+  OpScope scope(weight);
+  check_pm(src, "src");
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, "conv2d_wino: sizes");
+  TORCH_CHECK(src.size(0) == B * H * W, "conv2d_wino: src rows != B*H*W");
+  TORCH_CHECK(src.size(1) % 32 == 0, "conv2d_wino: input channels must be a multiple of 32, got ", src.size(1));
+  pfk_conv_desc d{};
+  d.src[0].ptr = fptr(src); d.src[0].ld = src.stride(0); d.src[0].channels = src.size(1);
+  d.num_src = 1;
+  d.B = B; d.H = H; d.W = W; d.kh = 3; d.kw = 3; d.stride = 1; d.cout = cout;
+  d.epilogue = PFK_EPI_LINEAR; d.relu = relu; d.scale = (float)scale;
+  d.cout_active = (int)cout_active;
+  check_dev_f32(weight, "weight");
+  const long long wn = pfk_conv_wino_weight_floats((int)src.size(1), (int)cout);
+  TORCH_CHECK(weight.is_contiguous() && weight.numel() == wn, "conv2d_wino: transformed weight must be contiguous with ", wn,
+              " elements, got ", weight.numel());
+  d.weight = fptr(weight);
+  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); d.bias = fptr(*bias); }
+  check_pm(out, "out");
+  TORCH_CHECK(out.size(0) == B * H * W && out.size(1) == cout, "conv2d_wino: out must be a [M, cout] view");
+  d.out = fptr(out); d.out_ld = out.stride(0); d.out_coff = 0;
+  check_ok(pfk_conv2d_wino_f32(&d, cur_stream()), "conv2d_wino");
+}
+
 // Grouped launch (pfk_conv2d_group_f32): problem i = one fp32 source srcs[i] ([B*H*W, cin_i] view), k[i] x k[i] taps, stride 1, packed
 // weight weights[i] [cout_i, ktot_i], bias biases[i] (an empty tensor = none), relu[i], scale[i], out = outs[i] ([B*H*W, cout_i] view),
 // residuals[i] (optional; an empty tensor = none): added after relu / scale
@@ -962,6 +989,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("conv2d(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, "
         "int epilogue, bool relu, float scale, Tensor(a!)? out, Tensor(b!)? h, Tensor(c!)? aux_z, Tensor(d!)? aux_rh, "
         "Tensor(e!)? workspace=None, Tensor? residual=None, int stride=1, bool relu_after_residual=False, int cout_active=0, int cout_split=0) -> ()");
+  m.def("conv2d_wino(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
+        "int cout_active=0) -> ()");
   m.def("conv2d_group(Tensor[] srcs, int B, int H, int W, int[] k, Tensor[] weights, Tensor[] biases, int[] relu, float[] scale, Tensor(a!)[] outs, Tensor[] residuals) -> ()");
   m.def("conv2d_b16(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, int epilogue, bool relu, "
         "float scale, Tensor(a!)? out, Tensor(b!)? h=None, Tensor(c!)? h_b16=None, Tensor(d!)? aux_z=None, Tensor(e!)? aux_rh=None, "
@@ -1004,6 +1033,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv2d", &conv2d);
   m.impl("conv2d_b16", &conv2d_b16);
   m.impl("conv2d_group", &conv2d_group);
+  m.impl("conv2d_wino", &conv2d_wino);
   m.impl("conv_cin2", &conv_cin2);
   m.impl("flow_delta", &flow_delta);
   m.impl("flow_from_coords", &flow_from_coords);

@@ -1,0 +1,255 @@
+// K4w: 3x3 stride-1 "same" convolution as Winograd F(2x2,3x3) on the gfx950 fp32 matrix cores (v_mfma_f32_16x16x4_f32).
+//
+// Lavin & Gray 2016: for a 2x2 output tile whose 4x4 input patch d starts one pixel up-left of it (the zero padding),
+//   Y = A^T [ sum_c (G g_c G^T) (.) (B^T d_c B) ] A
+//   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1],  G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1],  A^T = [1 1 1 0; 0 1 -1 -1]
+// i.e. 16 independent GEMMs, one per transform component xi = 4*row + col:  M_xi[tile][co] = sum_c V_xi[tile][c] * U_xi[c][co],
+// 16 * 2 * tiles * cin * cout flops instead of the direct form's 2 * 4 * tiles * 9 * cin * cout: 2.25x fewer fp32 products.
+//
+// U = G g G^T is made once per weight on the host (packing.pack_wino_weight: fp64, rounded to fp32 once).  Its layout is the LDS
+// image of one (64-channel column block, 8-channel K-step), 32 KB contiguous, so a block copies it with b128 loads:
+//   weight[cb][ks][xi][nl (64)][slot (8)],  co = 64*cb + nl,  c = 8*ks + cc,
+//   slot = ((cc & 3) * 2 + (cc >> 2)) ^ (((nl >> 2) & 3) * 2)
+// (pad columns co >= cout are zero).  The slot order gives the MFMA lane (k = lane >> 4 of sub-step s = cc >> 2) both sub-steps'
+// values in one 8-byte read; the XOR with bits 2-3 of the row spreads the 16 rows a lane group reads over all banks, for both forms
+// the compiler emits (ds_read_b64: 32-lane groups, 64 banks; ds_read2st64_b64: 16-lane groups, 32 banks).  V in LDS uses the
+// same slot order with the tile as the row.
+//
+// Block = 32 consecutive 2x2 tiles (row-major over batch, tile row, tile column) x 64 output channels, 4 waves, each wave
+// 16 tiles x 32 channels with ALL 16 components in registers (16 x 2 accumulators of 16x16: 128 per lane).  K-step = 8 input
+// channels: each thread transforms one (tile, channel) — 16 dword buffer loads (out-of-image taps read zero through an
+// out-of-range offset: that zero is the padding), B^T d B on the VALU, 16 ds_write_b32 — and copies 128 B of U; the next
+// K-step's loads are in flight during the MFMAs.  48 KB LDS, <= 256 registers: two blocks per CU.
+//
+// Epilogue: an MFMA 16x16 accumulator gives a lane four rows (tiles) of one column, at the same place in every component, so
+// A^T m A is lane-local; then PFK_EPI_LINEAR's bias, NaN-propagating relu, scale.  A column's K order and transforms do not
+// depend on which other columns are in the launch: `cout_active` launches fewer column blocks and gives the full launch's bits.
+#include "pfk_gemm.h"
+
+using namespace pfkg;
+
+namespace {
+
+constexpr int WT = 32;   // 2x2 output tiles per block
+constexpr int WN = 64;   // output channels per block
+constexpr int WK = 8;    // input channels per K-step
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct WinoArgs {
+  const float* src; int ld;      // pixel-major source, row stride in floats
+  unsigned src_bytes;            // readable bytes from src
+  int H, W;
+  int tw, tpi;                   // tiles per row, tiles per image
+  int ntiles;                    // B * tiles per image
+  int nks;                       // cin / 8
+  const float* weight; unsigned w_bytes;
+  const float* bias;
+  int cout;
+  int ncb;                       // column blocks launched
+  int relu; float scale;
+  float* out; int out_ld, out_coff;
+};
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+
+// One K-step's operands into registers: 16 input taps of this thread's (tile, channel), 128 B of the block's U image.
+// (a plain function rather than a lambda: by-reference captures can put register state in scratch, see pfk_gemm.hip)
+__device__ __forceinline__ void wino_load(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rw, const unsigned (&voff)[16],
+                                          unsigned wvoff, unsigned wk, int ks, float (&d)[16], f32x4 (&wr)[8]) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    d[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff[q], ks * WK * 4, 0));
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    wr[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wk + j * 4096u, 0));
+}
+
+__global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoArgs a) {
+  __shared__ __attribute__((aligned(16))) float sV[16 * WT * WK];   // [xi][tile][slot]      16 KB
+  __shared__ __attribute__((aligned(16))) float sU[16 * WN * WK];   // [xi][column][slot]    32 KB
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int cb = blockIdx.x % a.ncb;
+  const int t0 = (blockIdx.x / a.ncb) * WT;
+
+  const __amdgpu_buffer_rsrc_t rs = rsrc_n(a.src, a.src_bytes);
+  const __amdgpu_buffer_rsrc_t rw = rsrc_n(a.weight, a.w_bytes);
+
+  // ---- staging role: tile lt, channel cc of the K-step
+  const int lt = tid >> 3, cc = tid & 7;
+  unsigned voff[16];
+  {
+    const int g = t0 + lt;
+    const bool tok = g < a.ntiles;
+    const int b = g / a.tpi, r = g - b * a.tpi;
+    const int ty = r / a.tw, tx = r - ty * a.tw;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int y = 2 * ty - 1 + i, x = 2 * tx - 1 + j;
+        const bool ok = tok && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+        voff[i * 4 + j] = ok ? ((unsigned)((b * a.H + y) * a.W + x) * (unsigned)a.ld + (unsigned)cc) * 4u : OOB;
+      }
+  }
+  const int vslot = ((cc & 3) * 2 + (cc >> 2)) ^ (((lt >> 2) & 3) * 2);
+  float* const vdst = sV + lt * WK + vslot;
+  const unsigned wvoff = (unsigned)tid * 16u;
+  const unsigned wbase = (unsigned)cb * (unsigned)a.nks * (16u * WN * WK * 4u);   // this column block's U
+
+  float d[16];
+  f32x4 wr[8];
+  // ---- MFMA role: wave tile rows wt*16.., columns wc*32..
+  const int wt = wid & 1, wc = wid >> 1;
+  const int rl = lane & 15, kq = lane >> 4;
+  const float* const aV = sV + (wt * 16 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
+  const float* const aU = sU + (wc * 32 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
+
+  f32x4 acc[16][2];
+#pragma unroll
+  for (int x = 0; x < 16; ++x)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) acc[x][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  constexpr unsigned KSTEP_BYTES = 16u * WN * WK * 4u;   // one K-step of one column block's U
+  wino_load(rs, rw, voff, wvoff, wbase, 0, d, wr);
+  for (int ks = 0; ks < a.nks; ++ks) {
+    // V = B^T d B (rows, then columns), one channel of one tile
+    float t[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
+      t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
+      t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
+      t[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      vdst[(i * 4 + 0) * WT * WK] = t[i * 4 + 0] - t[i * 4 + 2];
+      vdst[(i * 4 + 1) * WT * WK] = t[i * 4 + 1] + t[i * 4 + 2];
+      vdst[(i * 4 + 2) * WT * WK] = t[i * 4 + 2] - t[i * 4 + 1];
+      vdst[(i * 4 + 3) * WT * WK] = t[i * 4 + 1] - t[i * 4 + 3];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(sU + j * 1024 + tid * 4) = wr[j];
+    __syncthreads();
+    if (ks + 1 < a.nks) wino_load(rs, rw, voff, wvoff, wbase + (unsigned)(ks + 1) * KSTEP_BYTES, ks + 1, d, wr);
+    // operands of component x + 1 are read while the MFMAs of x run (the LDS latency hides under the matrix pipe)
+    f32x2 va[2], u0[2], u1[2];
+    va[0] = *reinterpret_cast<const f32x2*>(aV);
+    u0[0] = *reinterpret_cast<const f32x2*>(aU);
+    u1[0] = *reinterpret_cast<const f32x2*>(aU + 16 * WK);
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+      const int c = x & 1, n = c ^ 1;
+      if (x + 1 < 16) {
+        va[n] = *reinterpret_cast<const f32x2*>(aV + (x + 1) * WT * WK);
+        u0[n] = *reinterpret_cast<const f32x2*>(aU + (x + 1) * WN * WK);
+        u1[n] = *reinterpret_cast<const f32x2*>(aU + (x + 1) * WN * WK + 16 * WK);
+      }
+      __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc hoists the reads of x + 1 behind the MFMAs of x again)
+      acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u0[c][0], acc[x][0], 0, 0, 0);
+      acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u1[c][0], acc[x][1], 0, 0, 0);
+      acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u0[c][1], acc[x][0], 0, 0, 0);
+      acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u1[c][1], acc[x][1], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue: lane holds tiles 4*kq + r (r = 0..3) of column rl in every component
+  typedef __attribute__((address_space(1))) float gfloat;
+  gfloat* const outp = (gfloat*)a.out;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int n = cb * WN + wc * 32 + c * 16 + rl;
+    const bool nok = n < a.cout;
+    const float bias = (a.bias != nullptr && nok) ? a.bias[n] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int g = t0 + wt * 16 + kq * 4 + r;
+      float m[16];
+#pragma unroll
+      for (int x = 0; x < 16; ++x) m[x] = acc[x][c][r];
+      float s0[4], s1[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s0[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
+        s1[j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
+      }
+      float y[4];
+      y[0] = s0[0] + s0[1] + s0[2];
+      y[1] = s0[1] - s0[2] - s0[3];
+      y[2] = s1[0] + s1[1] + s1[2];
+      y[3] = s1[1] - s1[2] - s1[3];
+      if (!nok || g >= a.ntiles) continue;
+      const int b = g / a.tpi, rr = g - b * a.tpi;
+      const int ty = rr / a.tw, tx = rr - ty * a.tw;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int oy = 2 * ty + (e >> 1), ox = 2 * tx + (e & 1);
+        if (oy >= a.H || ox >= a.W) continue;
+        float v = y[e] + bias;
+        if (a.relu) v = (v < 0.f) ? 0.f : v;   // NaN-propagating like torch.relu
+        v *= a.scale;
+        const long long p = ((long long)b * a.H + oy) * a.W + ox;
+        outp[p * a.out_ld + a.out_coff + n] = v;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+long long pfk_conv_wino_weight_floats(int cin, int cout) {
+  if (cin <= 0 || cout <= 0 || (cin & 31)) return PFK_ERR_BAD_ARG;
+  return 16LL * cin * ((cout + WN - 1) / WN * WN);
+}
+
+int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
+  if (!d) return PFK_ERR_BAD_ARG;
+  if (d->num_src != 1 || d->kh != 3 || d->kw != 3 || d->stride > 1 || d->epilogue != PFK_EPI_LINEAR || d->residual ||
+      d->relu_after_residual)
+    return PFK_ERR_UNSUPPORTED;
+  const pfk_conv_src& s = d->src[0];
+  if (!s.ptr || !d->weight || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || s.channels <= 0 ||
+      s.ld < s.channels || d->out_coff < 0 || d->out_ld < d->out_coff + d->cout)
+    return PFK_ERR_BAD_ARG;
+  if (s.channels & 31) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_aligned16(d->weight) || (reinterpret_cast<uintptr_t>(s.ptr) & 3u) || (reinterpret_cast<uintptr_t>(d->out) & 3u))
+    return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)d->B * d->H * d->W;
+  const long long src_bytes = ((M - 1) * s.ld + s.channels) * 4;
+  const long long wfloats = pfk_conv_wino_weight_floats(s.channels, d->cout);
+  if (M * s.ld * 4 >= 0x7fffffffLL || wfloats * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
+  int ncb = (d->cout + WN - 1) / WN;
+  if (d->cout_active > 0 && d->cout_active < d->cout) {
+    if (d->cout_active & (WN - 1)) return PFK_ERR_UNSUPPORTED;
+    ncb = d->cout_active / WN;
+  }
+  WinoArgs a{};
+  a.src = s.ptr; a.ld = s.ld; a.src_bytes = (unsigned)src_bytes;
+  a.H = d->H; a.W = d->W;
+  a.tw = (d->W + 1) / 2;
+  a.tpi = a.tw * ((d->H + 1) / 2);
+  const long long ntiles = (long long)d->B * a.tpi;
+  const long long nblk = (ntiles + WT - 1) / WT * ncb;
+  if (nblk >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  a.ntiles = (int)ntiles;
+  a.nks = s.channels / WK;
+  a.weight = d->weight; a.w_bytes = (unsigned)(wfloats * 4);
+  a.bias = d->bias;
+  a.cout = d->cout;
+  a.ncb = ncb;
+  a.relu = d->relu ? 1 : 0; a.scale = d->scale;
+  a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
+  hipLaunchKernelGGL(conv_gemm_wino_f32_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return pfk_launch_status();
+}
+
+}  // extern "C"

@@ -33,6 +33,33 @@ def pack_conv_weight(weight: torch.Tensor, segments: Sequence[Tuple[int, int, in
     return torch.cat(parts, dim=1).contiguous()
 
 
+# Winograd F(2x2,3x3) weight transform (Lavin & Gray 2016): U = G g G^T
+WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def wino_slot(nl: torch.Tensor, cc: torch.Tensor) -> torch.Tensor:
+    """LDS slot of channel ``cc`` (0..7 of a K-step) in row ``nl`` of `pfk_conv2d_wino_f32`'s operand images (include/pfk.h)."""
+    return ((cc & 3) * 2 + (cc >> 2)) ^ (((nl >> 2) & 3) * 2)
+
+
+def pack_wino_weight(weight: torch.Tensor) -> torch.Tensor:
+    """``[cout, cin, 3, 3]`` -> the flat transformed weight of ``pfk_conv2d_wino_f32``: U = G g G^T in float64 on the host,
+    rounded to fp32 once, laid out ``[ceil(cout/64)][cin/8][16][64][8]`` (column block, K-step, component 4*row + col, column,
+    slot — include/pfk.h), pad columns zero.  Returned on ``weight``'s device."""
+    cout, cin, kh, kw = weight.shape
+    assert kh == 3 and kw == 3 and cin % 32 == 0
+    G = torch.tensor(WINO_G, dtype=torch.float64)
+    g = weight.detach().to(device="cpu", dtype=torch.float64)
+    U = torch.einsum("au,ocuv,bv->aboc", G, g, G).reshape(16, cout, cin).to(torch.float32)   # [xi][co][c]
+    ncb = (cout + 63) // 64
+    U = F.pad(U, (0, 0, 0, ncb * 64 - cout)).reshape(16, ncb, 64, cin // 8, 8)           # [xi][cb][nl][ks][cc]
+    nl = torch.arange(64).view(64, 1)
+    cc = torch.arange(8).view(1, 8)
+    slot = wino_slot(nl, cc).view(1, 1, 64, 1, 8).expand_as(U)
+    out = torch.empty_like(U).scatter_(4, slot, U)
+    return out.permute(1, 3, 0, 2, 4).contiguous().reshape(-1).to(weight.device)
+
+
 def split_bf16_planes(packed: torch.Tensor, nsplit: int) -> torch.Tensor:
     """fp32 ``[cout, ktot]`` -> bf16 ``[nsplit, cout, ktot]`` with plane 0 = bf16(w), plane 1 = bf16(w - plane 0), ...
     (round to nearest even; every residual is exact in fp32) — the weight operand of ``pfk_conv2d_bf16s``."""

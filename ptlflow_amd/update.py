@@ -33,7 +33,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import load_native
-from .packing import permute_mask_head, pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, round_up, split_bf16_planes
+from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino_weight, permute_mask_head, round_up,
+                      split_bf16_planes)
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 
@@ -100,6 +101,17 @@ def small_spec(corr_levels: int = 4, corr_radius: int = 3) -> UpdateSpec:
                       ((3, 3, ""),), 128, False)
 
 
+# Winograd rule (`_use_wino`): B*H*W x ceil(cout / 64) >= WINO_MIN_WORK, i.e. about 4 x 32 x the Winograd kernel's blocks (32 2x2
+# tiles x 64 channels each; two resident per CU on 256 CUs).  In isolation at 55x128 (scripts/wino_bench.py, MI355X, the direct
+# kernel with the engine's stream-K workspace, profiles/r07_a_winograd.md):
+#   batch 1 (7040 px):  fm (x 8 = 56320) 90.8 -> 56.2 us;  c2 (x 3 = 21120) 69.7 -> 65.1 us;  cv (x 2 = 14080) 51.0 -> 63.4 us
+#   batch 2 (14080 px): fm 162.2 -> 106.3 us;  c2 (42240) 117.2 -> 93.0 us;  cv (28160) 90.4 -> 68.8 us
+#   batch 8: fm 555.7 -> 337.8 us, c2 417.2 -> 268.7 us, cv 276.4 -> 181.5 us
+# Below 28160 the grid leaves most CUs idle and the direct kernel's stream-K schedule wins or ties (c2 at batch 1 gains 7 %, inside
+# what one box to the next moves, so the line is drawn above it).  The full launch's cout decides (a
+# `cout_active` launch takes the same kernel as its full form).
+WINO_MIN_WORK = 28160
+
 # conv_precision -> number of bf16 planes per operand (0 = the fp32 matrix-core path, the default and the parity path)
 CONV_PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}
 
@@ -143,6 +155,9 @@ class UpdateEngine:
         self.profile: Optional[Dict[str, list]] = None
         self.flops: Dict[str, float] = {}
         self.bytes: Dict[str, float] = {}
+        # fp32 engine: `fm`, `c2` and `cv` (3x3, one source) run as Winograd F(2x2,3x3) (`pfk_conv2d_wino_f32`, see _use_wino);
+        # False = every convolution on `pfk_conv2d_f32` (same-build A/B, tests)
+        self.winograd = True
         self.pack(params)
 
     # ------------------------------------------------------------------ weights
@@ -242,6 +257,15 @@ class UpdateEngine:
         if "flow_head.conv2.weight" in P:     # (SEA-RAFT's 6-channel flow head conv2 is packed by its own engine, sea_update.py)
             w["fh2.w"] = pack_flow_head_weight(g("flow_head.conv2.weight"))
             w["fh2.b"] = g("flow_head.conv2.bias").contiguous()
+        if self.nsplit == 0 and not self.b16:
+            # Winograd-transformed twins of the update block's 3x3 stride-1 single-source convolutions (U = G g G^T, once per pack)
+            fm = torch.cat([g("flow_head.conv1.weight"), g("mask.0.weight")], 0) if s.has_mask else g("flow_head.conv1.weight")
+            wino = {"cv": g("encoder.conv.weight"), "fm": fm}
+            if s.c2:
+                wino["c2"] = g("encoder.convc2.weight")
+            for key, wt in wino.items():
+                if wt.shape[1] % 32 == 0 and tuple(wt.shape[2:]) == (3, 3):
+                    w[key + ".ww"] = pack_wino_weight(wt)
         self.w = w
 
     # ------------------------------------------------------------------ buffers
@@ -482,7 +506,9 @@ class UpdateEngine:
         # a stream-K workspace belongs to ONE stream: `workspace` = True (the main chain's), a branch's own tensor, or False
         # (none: plain tile grid)
         ws = self.workspace if workspace is True else (workspace if isinstance(workspace, torch.Tensor) else None)
-        if self.b16:
+        if self._use_wino(key, B * H * W, cout):
+            self.ops.conv2d_wino(srcs[0], B, H, W, self.w[key + ".ww"], self.w.get(key + ".b"), cout, relu, scale, out, cout_active)
+        elif self.b16:
             # K8b: z|r reads h from the bf16 twin (r * h is rounded to bf16 anyway), q updates the fp32 h and mirrors it
             hb = self.hxb[:, : self.spec.hidden] if epi != EPI_LINEAR else None
             self.ops.conv2d_b16(srcs, B, H, W, kh, kw, self.w[key + ".w"], self.w.get(key + ".b"), cout, epi, relu, scale,
@@ -500,6 +526,12 @@ class UpdateEngine:
             self.flops[key] = 2.0 * B * H * W * cout * kh * kw * self._real_cin[key]
             # algorithmic HBM bytes: every input channel read once, every output written once, the weight once (fp32)
             self.bytes[key] = (2.0 if self.b16 else 4.0) * (B * H * W * (self._real_cin[key] + cout) + cout * kh * kw * self._real_cin[key])
+
+    def _use_wino(self, key: str, pixels: int, cout: int) -> bool:
+        """`pfk_conv2d_wino_f32` for `fm`, `c2`, `cv` (their transformed weights exist on the fp32 engine only, see pack) where
+        pixels x ceil(cout / 64) >= WINO_MIN_WORK.  The rule reads the key and the launch shape only — never the schedule mode — so
+        serial, forked, captured, grouped and dead-work-skip forwards launch the same kernel for each of them and agree bit for bit."""
+        return self.winograd and pixels * ((cout + 63) // 64) >= WINO_MIN_WORK and (key + ".ww") in self.w
 
     def motion(self, corr_pm: torch.Tensor) -> None:
         """BasicMotionEncoder / SmallMotionEncoder (update.py:104-112 / :85-91) into its hx slice; `flow` must already be in hx."""
