@@ -30,6 +30,7 @@
  *   pfk_convex_upsample_f32  ptlflow/models/raft/raft.py:112-123 RAFT.upsample_flow
  *   pfk_dwconv_layernorm_f32  ptlflow/models/sea_raft/layer.py:54-58,71-75 (ConvNextBlock dwconv + norm)
  *   pfk_convex_upsample_info_pm_f32  ptlflow/models/sea_raft/sea_raft.py:147-163 SEARAFT.upsample_data
+ *   pfk_dwconv_layernorm_b16 / pfk_conv2d_gelu_b16 / pfk_convex_upsample_info_pm_b16  the same on the bf16 (K8b) path
  *   pfk_altcorr_forward_f32  ptlflow/utils/external/alt_cuda_corr/correlation_kernel.cu:258-285 (alt_cuda_corr.forward)
  *   pfk_corr_lookup_bwd_f32 / pfk_corr_volume_bwd_f32 / pfk_convex_upsample_bwd_f32
  *                         what torch.autograd runs for corr.py:29-64 and raft.py:112-123 in a training step (train.py;
@@ -203,8 +204,8 @@ enum pfk_epilogue {
   PFK_EPI_LINEAR_GELU = 3  /* (added in ABI 7) LINEAR with the exact GELU in place of relu: v = (acc+bias) ;
                               v = 0.5*v*(1 + erf(v/sqrt(2))) ; v *= scale ; [v = residual + v] ; out = v.  `relu` must be 0;
                               `relu_after_residual` as LINEAR.  sea_raft/layer.py:60-62,74-75 (pwconv1 + nn.GELU()).
-                              pfk_conv2d_f32 only (tile grid and stream-K, no cout_active / cout_split): pfk_conv2d_group_f32,
-                              pfk_conv2d_bf16s and pfk_conv2d_b16 return PFK_ERR_UNSUPPORTED for it */
+                              pfk_conv2d_f32 (tile grid and stream-K, no cout_active / cout_split) and pfk_conv2d_gelu_b16:
+                              pfk_conv2d_group_f32, pfk_conv2d_bf16s and pfk_conv2d_b16 return PFK_ERR_UNSUPPORTED for it */
 };
 
 typedef struct {
@@ -362,6 +363,11 @@ typedef struct {
 } pfk_conv_b16_desc;
 int pfk_conv_ktot_b16(const pfk_conv_b16_desc* d);
 int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream);
+/* pfk_conv2d_gelu_b16 (ABI 7): K8b's LINEAR epilogue with the exact GELU where relu would be applied — sea_raft/layer.py:60-62,74-75
+ * (pwconv1 + nn.GELU()) on bf16 operands: v = (acc+bias) ; v = 0.5*v*(1 + erf(v/sqrt(2))) ; v *= scale ; [v = residual + v] ; out.
+ * d->epilogue must be PFK_EPI_LINEAR_GELU and d->relu 0 (PFK_ERR_BAD_ARG otherwise); everything else as pfk_conv2d_b16's LINEAR
+ * (bf16 or fp32 out, fp32 bias, optional residual; no batched GEMM).  pfk_conv2d_b16 itself keeps refusing PFK_EPI_LINEAR_GELU. */
+int pfk_conv2d_gelu_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream);
 int pfk_debug_set_b16(int cfg);            /* K8b tile configuration: 0 = heuristic, 1..5 (pfk_gemm_b16.hip::launch_b16) */
 
 /* ---- small direct kernels ------------------------------------------------------------------- */
@@ -447,6 +453,15 @@ int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight,
                              const float* ln_bias, float eps, float* out, int out_ld, int B, int H, int W, int C, int k,
                              pfk_stream_t stream);
 
+/* pfk_dwconv_layernorm_b16: the same on bf16 rows (ABI 7): in_bf16[p*in_ld + c] -> out_bf16[p*out_ld + c]; dw_weight / dw_bias /
+ * ln_weight / ln_bias fp32 as above.  fp32 accumulation, LayerNorm statistics in fp32 (mean, then the biased variance about it),
+ * one rounding to bf16 at the store.  C % 8 == 0, 8 <= C <= 512, k odd <= 7; in / out 16-byte aligned, in_ld % 8 == 0,
+ * out_ld % 8 == 0 (e.g. the update engine's bf16 [net | context | motion | flow] rows); out must not overlap the input rows.  No
+ * workspace; one HBM read of every input row. */
+int pfk_dwconv_layernorm_b16(const void* in_bf16, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                             const float* ln_bias, float eps, void* out_bf16, int out_ld, int B, int H, int W, int C, int k,
+                             pfk_stream_t stream);
+
 /* pfk_convex_upsample_info_pm_f32: SEARAFT.upsample_data (sea_raft/sea_raft.py:147-163).  flow_pm [M][flow_ld] (channels 0..1),
  * info_pm [M][info_ld] (channels 0..n-1, 1 <= n <= 8), mask [M][mask_ld] fp32 logits with channel c = k*64 + sy*8 + sx, already
  * multiplied by 0.25 (16-byte aligned rows, mask_ld % 4 == 0, mask_ld >= 576).  Softmax over the nine taps; convex combination of
@@ -454,6 +469,12 @@ int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight,
  * (both NCHW, contiguous, 16-byte aligned).  flow_out is bit-identical to pfk_convex_upsample_pm_f32 on the same flow and mask. */
 int pfk_convex_upsample_info_pm_f32(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
                                     const float* mask, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
+                                    pfk_stream_t stream);
+/* same with bf16 mask logits (ABI 7): mask_bf16 [M][mask_ld] in the plain channel order, already x 0.25, 16-byte aligned rows,
+ * mask_ld % 8 == 0; flow / info rows and both outputs fp32 as above.  flow_out is bit-identical to pfk_convex_upsample_pm_b16 on
+ * the same flow and mask. */
+int pfk_convex_upsample_info_pm_b16(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
+                                    const void* mask_bf16, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
                                     pfk_stream_t stream);
 
 /* ---- on-demand correlation behind the reference's alt_cuda_corr ABI --------------------------------

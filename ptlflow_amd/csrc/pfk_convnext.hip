@@ -130,6 +130,144 @@ int launch_dwconv_ln(const float* in, int in_ld, const float* dw_w, const float*
   return pfk_launch_status();
 }
 
+// ---- the bf16 twin (pfk_dwconv_layernorm_b16): bf16 rows in and out, fp32 arithmetic -------------------------------------------
+// A block owns a BT_TY x BT_TX = 4 x 8 tile and all its channels.  Per 64-channel chunk the halo (bf16, 128 B per pixel) and the chunk's
+// k*k weights (fp32) are staged in LDS; thread (strip s, pair j) then forms a strip of BT_PX = 4 consecutive output pixels of one tile
+// row for channels 2j, 2j+1 as a sliding window: per filter row it reads BT_PX + k - 1 halo pairs and k weight pairs once and does
+// BT_PX * k pair-FMAs with them (the fp32 kernel reads one halo value and one weight per FMA).  The pre-norm values stay in registers
+// (acc[chunk][pixel]: at most 8 chunks x 4 pixels x 2 channels = 64 floats): the 32 lanes of a half-wave share a strip, so the
+// LayerNorm's two reductions (mean, then the biased variance about it) are xor-shuffles inside the half-wave — no output tile in LDS.
+constexpr int BT_TY = 4, BT_TX = 8, BT_PX = 4;
+constexpr int BT_CC = 64;                 // channels per staged chunk: 32 pairs
+constexpr int BT_NCH = DW_MAX_C / BT_CC;  // 8
+constexpr int BT_THREADS = 256;           // 8 strips (2 per tile row) x 32 pairs
+static_assert((BT_TY * BT_TX / BT_PX) * (BT_CC / 2) == BT_THREADS, "one (strip, channel pair) item per thread and chunk");
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ f32x2 bf16x2_widen(unsigned w) {     // two bf16 -> fp32, exact
+  f32x2 v;
+  v.x = __builtin_bit_cast(float, w << 16);
+  v.y = __builtin_bit_cast(float, w & 0xffff0000u);
+  return v;
+}
+
+__device__ __forceinline__ float half_wave_sum(float v) {      // over the 32 lanes of this lane's half-wave
+#pragma unroll
+  for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+template <int K>
+__global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16* __restrict__ in, int in_ld, const float* __restrict__ dw_w,
+                                                                   const float* __restrict__ dw_b, const float* __restrict__ ln_w,
+                                                                   const float* __restrict__ ln_b, float eps, __bf16* __restrict__ out,
+                                                                   int out_ld, int H, int W, int C) {
+  constexpr int R = K / 2, HY = BT_TY + K - 1, HX = BT_TX + K - 1, KK = K * K, WIN = BT_PX + K - 1;
+  __shared__ __attribute__((aligned(16))) __bf16 halo[HY * HX * BT_CC];   // [halo pixel][64 channels]: 17.5 KB at k = 7
+  __shared__ __attribute__((aligned(16))) float wts[KK * BT_CC];          // [tap][64 channels]: 12.25 KB at k = 7
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int j = lane & 31;                                   // channel pair of the chunk
+  const int s = (tid >> 6) * 2 + (lane >> 5);                // strip: tile row s / 2, columns (s % 2) * 4 .. + 3
+  const int ry = s >> 1, rx = (s & 1) * BT_PX;
+  const int x0 = blockIdx.x * BT_TX, y0 = blockIdx.y * BT_TY;
+  const long long img = (long long)blockIdx.z * H * W;
+  const unsigned* hw32 = reinterpret_cast<const unsigned*>(halo);
+  f32x2 acc[BT_NCH][BT_PX];
+#pragma unroll
+  for (int ch = 0; ch < BT_NCH; ++ch) {
+    const int c0 = ch * BT_CC;
+    if (c0 < C) {                                            // block-uniform
+      const int cn = (C - c0) < BT_CC ? (C - c0) : BT_CC;    // a multiple of 8
+      __syncthreads();                                       // the previous chunk's LDS reads are done
+      for (int i = tid; i < HY * HX * (BT_CC / 8); i += BT_THREADS) {
+        const int hp = i >> 3, g = i & 7;
+        const int hy = hp / HX, hx = hp - hy * HX;
+        const int yy = y0 + hy - R, xx = x0 + hx - R;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};                        // 16 bytes = eight bf16 zeros
+        if (g * 8 < cn && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+          v = *reinterpret_cast<const f32x4*>(in + (img + (long long)yy * W + xx) * in_ld + c0 + g * 8);
+        *reinterpret_cast<f32x4*>(halo + hp * BT_CC + g * 8) = v;
+      }
+      for (int i = tid; i < KK * BT_CC; i += BT_THREADS) {    // coalesced global reads: [channel][tap] -> [tap][channel]
+        const int c = i / KK, t = i - c * KK;
+        wts[t * BT_CC + c] = c < cn ? dw_w[(long long)c0 * KK + i] : 0.f;
+      }
+      __syncthreads();
+      f32x2 b = {0.f, 0.f};
+      if (dw_b != nullptr && 2 * j < cn) b = f32x2{dw_b[c0 + 2 * j], dw_b[c0 + 2 * j + 1]};
+#pragma unroll
+      for (int o = 0; o < BT_PX; ++o) acc[ch][o] = b;
+      if (2 * j < cn) {
+#pragma unroll 1
+        for (int ky = 0; ky < K; ++ky) {
+          f32x2 w[K];
+#pragma unroll
+          for (int kx = 0; kx < K; ++kx) w[kx] = *reinterpret_cast<const f32x2*>(wts + (ky * K + kx) * BT_CC + 2 * j);
+          const unsigned* hrow = hw32 + ((ry + ky) * HX + rx) * (BT_CC / 2) + j;
+#pragma unroll
+          for (int i = 0; i < WIN; ++i) {
+            const f32x2 h = bf16x2_widen(hrow[i * (BT_CC / 2)]);
+#pragma unroll
+            for (int o = 0; o < BT_PX; ++o) {
+              const int kx = i - o;
+              if (kx >= 0 && kx < K) acc[ch][o] += h * w[kx];
+            }
+          }
+        }
+      }
+    }
+  }
+  // LayerNorm of the strip's pixels: this thread's channels, then the half-wave; two passes over the registers
+  const float inv_c = 1.0f / (float)C;
+  float mean[BT_PX], rstd[BT_PX];
+#pragma unroll
+  for (int o = 0; o < BT_PX; ++o) {
+    float sum = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < BT_NCH; ++ch)
+      if (ch * BT_CC + 2 * j < C) sum += acc[ch][o].x + acc[ch][o].y;
+    mean[o] = half_wave_sum(sum) * inv_c;
+  }
+#pragma unroll
+  for (int o = 0; o < BT_PX; ++o) {
+    float s2 = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < BT_NCH; ++ch) {
+      if (ch * BT_CC + 2 * j < C) {
+        const float dx = acc[ch][o].x - mean[o], dy = acc[ch][o].y - mean[o];
+        s2 += dx * dx + dy * dy;
+      }
+    }
+    rstd[o] = 1.0f / sqrtf(half_wave_sum(s2) * inv_c + eps);
+  }
+  const int y = y0 + ry;
+  if (y >= H) return;
+#pragma unroll
+  for (int ch = 0; ch < BT_NCH; ++ch) {
+    const int c = ch * BT_CC + 2 * j;
+    if (c >= C) continue;
+    const float w0 = ln_w[c], w1 = ln_w[c + 1], b0 = ln_b[c], b1 = ln_b[c + 1];
+#pragma unroll
+    for (int o = 0; o < BT_PX; ++o) {
+      const int x = x0 + rx + o;
+      if (x >= W) continue;
+      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+      bf16x2 v;
+      v[0] = (__bf16)((acc[ch][o].x - mean[o]) * rstd[o] * w0 + b0);
+      v[1] = (__bf16)((acc[ch][o].y - mean[o]) * rstd[o] * w1 + b1);
+      *reinterpret_cast<bf16x2*>(out + (img + (long long)y * W + x) * out_ld + c) = v;
+    }
+  }
+}
+
+template <int K>
+int launch_dwconv_ln_b16(const __bf16* in, int in_ld, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float eps,
+                         __bf16* out, int out_ld, int B, int H, int W, int C, hipStream_t st) {
+  dim3 grid((unsigned)((W + BT_TX - 1) / BT_TX), (unsigned)((H + BT_TY - 1) / BT_TY), (unsigned)B);
+  hipLaunchKernelGGL(dwconv_ln_b16_kernel<K>, grid, dim3(BT_THREADS), 0, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C);
+  return pfk_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -156,6 +294,33 @@ int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight,
     case 3: return launch_dwconv_ln<3>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     case 5: return launch_dwconv_ln<5>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     default: return launch_dwconv_ln<7>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+  }
+}
+
+int pfk_dwconv_layernorm_b16(const void* in_bf16, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                             const float* ln_bias, float eps, void* out_bf16, int out_ld, int B, int H, int W, int C, int k,
+                             pfk_stream_t stream) {
+  if (!in_bf16 || !dw_weight || !ln_weight || !ln_bias || !out_bf16 || B <= 0 || H <= 0 || W <= 0 || C < 8 || in_ld < C || out_ld < C)
+    return PFK_ERR_BAD_ARG;
+  if (k < 1 || !(k & 1) || k > 7) return PFK_ERR_BAD_ARG;
+  if (C > DW_MAX_C || B > 65535 || (H + BT_TY - 1) / BT_TY > 65535) return PFK_ERR_UNSUPPORTED;
+  if ((C & 7) || (in_ld & 7) || (out_ld & 7) || !pfk_aligned16(in_bf16) || !pfk_aligned16(out_bf16)) return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  const __bf16* in = static_cast<const __bf16*>(in_bf16);
+  __bf16* out = static_cast<__bf16*>(out_bf16);
+  // `out` must not overlap the input rows (other blocks still read the halo of pixels this block has written)
+  const char* ib = reinterpret_cast<const char*>(in);
+  const char* ie = reinterpret_cast<const char*>(in + (M - 1) * in_ld + C);
+  const char* ob = reinterpret_cast<const char*>(out);
+  const char* oe = reinterpret_cast<const char*>(out + (M - 1) * out_ld + C);
+  if (ob < ie && ib < oe) return PFK_ERR_BAD_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k) {
+    case 1: return launch_dwconv_ln_b16<1>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    case 3: return launch_dwconv_ln_b16<3>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    case 5: return launch_dwconv_ln_b16<5>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+    default: return launch_dwconv_ln_b16<7>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
   }
 }
 

@@ -212,7 +212,9 @@ __device__ __forceinline__ u32x2 pack_bf16x4(const f32x4 v) {
 // in the same in-order vmcnt queue as loads: a load issued behind a store waits for that store's completion).
 template <int MT, int NT, int EPI>
 struct Epilogue16 {
-  static constexpr bool LIN = EPI == PFK_EPI_LINEAR, ZR = EPI == PFK_EPI_GRU_ZR, Q = EPI == PFK_EPI_GRU_Q;
+  static constexpr bool LIN = EPI == PFK_EPI_LINEAR || EPI == PFK_EPI_LINEAR_GELU, ZR = EPI == PFK_EPI_GRU_ZR, Q = EPI == PFK_EPI_GRU_Q;
+  // PFK_EPI_LINEAR_GELU (pfk_conv2d_gelu_b16 only): LINEAR with the exact GELU where relu would be applied
+  static constexpr bool GELU = EPI == PFK_EPI_LINEAR_GELU;
   // columns per lane of the row-wise pass: 4 (LINEAR: fp32 rows / residuals; its bf16 rows without a residual take the 8-column branch of
   // band()), 8 for the GRU epilogues — every bf16 side operand (context term, h twin, z) and every bf16 result (z, r * h, the h twin) is ONE
   // 16-byte access per lane and pass, the fp32 h two; half the passes and half the store instructions of the 4-column form
@@ -321,7 +323,10 @@ struct Epilogue16 {
           f32x4 v0 = *reinterpret_cast<const f32x4*>(reg + row * CW + c8), v1 = *reinterpret_cast<const f32x4*>(reg + row * CW + c8 + 4);
           const long long p = m_base + MTI * 32 + row;
           if (p >= a.M || n8 >= a.b_rows) continue;
-          if (a.relu) {
+          if constexpr (GELU) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v0[e] = gelu_erf(v0[e]); v1[e] = gelu_erf(v1[e]); }
+          } else if (a.relu) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v0[e] = (v0[e] < 0.f) ? 0.f : v0[e]; v1[e] = (v1[e] < 0.f) ? 0.f : v1[e]; }
           }
@@ -356,7 +361,10 @@ struct Epilogue16 {
       const long long p = m_base + MTI * 32 + row;
       if (p >= a.M || !any) continue;
       if constexpr (LIN) {
-        if (a.relu) {
+        if constexpr (GELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
+        } else if (a.relu) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];   // NaN-propagating like torch.relu
         }
@@ -613,6 +621,7 @@ int launch_b16_epi(const B16Args& a, int epi, hipStream_t st) {
     case PFK_EPI_LINEAR: return launch_b16_one<PFK_EPI_LINEAR, BM, BN, WM, WN, NST>(a, st);
     case PFK_EPI_GRU_ZR: return launch_b16_one<PFK_EPI_GRU_ZR, BM, BN, WM, WN, NST>(a, st);
     case PFK_EPI_GRU_Q:  return launch_b16_one<PFK_EPI_GRU_Q, BM, BN, WM, WN, NST>(a, st);
+    case PFK_EPI_LINEAR_GELU: return launch_b16_one<PFK_EPI_LINEAR_GELU, BM, BN, WM, WN, NST>(a, st);
     default: return PFK_ERR_BAD_ARG;
   }
 }
@@ -642,7 +651,7 @@ int launch_b16(const B16Args& a0, int epi, hipStream_t st) {
     // 16 x 55 x 128: 50.6 -> 48.6) and for every short-K LINEAR launch (1x1 128 -> 256: 34.4 -> 28.8; mask conv2 50.2 -> 44.0) —
     // gpurun_out/r6y_l1.log, r6z_l1.log, r6z2.log.  The update block's batch-8 grids (220 row tiles) keep their tiles (convf2 16.9 vs
     // 17.8, conv 39.1 vs 40.0, q 38 vs 49 us).
-    const bool lin = epi == PFK_EPI_LINEAR;
+    const bool lin = epi == PFK_EPI_LINEAR || epi == PFK_EPI_LINEAR_GELU;
     if (tm * (pad128 / 128) < 200) cfg = 4;
     else if (pad64 < pad128 && a.b_rows < 192) cfg = (lin && tm >= 512) ? 9 : 3;
     else if (lin && a.steps <= 4) cfg = 8;
@@ -693,6 +702,7 @@ int launch_b16(const B16Args& a0, int epi, hipStream_t st) {
     case 6:       // (no q epilogue on this tile: its 128-row wave tile has four bands of fp32 h / z / context operands — spills; q has cout = Ch <= 128 anyway)
       if (epi == PFK_EPI_LINEAR) return launch_b16_one<PFK_EPI_LINEAR, 256, 256, 2, 4, 2>(a, st);
       if (epi == PFK_EPI_GRU_ZR) return launch_b16_one<PFK_EPI_GRU_ZR, 256, 256, 2, 4, 2>(a, st);
+      if (epi == PFK_EPI_LINEAR_GELU) return launch_b16_one<PFK_EPI_LINEAR_GELU, 256, 256, 2, 4, 2>(a, st);
       return PFK_ERR_BAD_ARG;
     default: return PFK_ERR_BAD_ARG;
   }
@@ -893,8 +903,12 @@ int pfk_mask_upsample_b16(const void* x_bf16, int x_ld, int cin, const void* wei
   return pfk_launch_status();
 }
 
-int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
-  if (d && d->epilogue == PFK_EPI_LINEAR_GELU) return PFK_ERR_UNSUPPORTED;       // pfk_conv2d_f32 only (pfk.h)
+}  // extern "C"
+
+namespace {
+
+// pfk_conv2d_b16 / pfk_conv2d_gelu_b16: argument checks and the launch (PFK_EPI_LINEAR_GELU takes LINEAR's path)
+int conv2d_b16_impl(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
   if (!d || !d->weight || d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
   if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return PFK_ERR_BAD_ARG;
   if (d->kh <= 0 || d->kw <= 0 || !(d->kh & 1) || !(d->kw & 1) || d->kh * d->kw > 32) return PFK_ERR_BAD_ARG;
@@ -922,11 +936,12 @@ int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
   fastdiv_make((unsigned)a.Ho, a.ho_mul, a.ho_sh);
   if (d->residual) {      // LINEAR: fp32 rows (bf16 with residual_bf16); GRU epilogues: bf16 rows
     if (d->residual_ld < d->cout) return PFK_ERR_BAD_ARG;
-    const bool r16 = d->epilogue != PFK_EPI_LINEAR || d->residual_bf16;
-    const bool gru = d->epilogue != PFK_EPI_LINEAR;      // the GRU epilogues read the term as 16-byte pieces
+    const bool lin = d->epilogue == PFK_EPI_LINEAR || d->epilogue == PFK_EPI_LINEAR_GELU;
+    const bool r16 = !lin || d->residual_bf16;
+    const bool gru = !lin;                                 // the GRU epilogues read the term as 16-byte pieces
     if ((reinterpret_cast<uintptr_t>(d->residual) & ((r16 && !gru) ? 7u : 15u)) || (d->residual_ld & (gru ? 7 : 3)) || (r16 && (d->cout & 3)))
       return PFK_ERR_ALIGNMENT;
-    a.residual = d->residual; a.residual_ld = d->residual_ld; a.residual_bf16 = d->epilogue == PFK_EPI_LINEAR && d->residual_bf16;
+    a.residual = d->residual; a.residual_ld = d->residual_ld; a.residual_bf16 = lin && d->residual_bf16;
   }
   if (d->batches > 1) {
     // batched GEMM: `batches` independent problems of the same shape in one grid (blockIdx.y) — GMA's attn @ v per frame pair
@@ -939,6 +954,7 @@ int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
   }
   switch (d->epilogue) {
     case PFK_EPI_LINEAR:
+    case PFK_EPI_LINEAR_GELU:
       if (!d->out || d->out_ld < d->out_coff + d->cout) return PFK_ERR_BAD_ARG;
       if ((d->out_ld & 3) || (d->out_coff & 3) || (reinterpret_cast<uintptr_t>(d->out) & (d->out_bf16 ? 7u : 15u))) return PFK_ERR_ALIGNMENT;
       a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff; a.out_bf16 = d->out_bf16;
@@ -962,6 +978,20 @@ int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
       return PFK_ERR_BAD_ARG;
   }
   return launch_b16(a, d->epilogue, static_cast<hipStream_t>(stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfk_conv2d_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
+  if (d && d->epilogue == PFK_EPI_LINEAR_GELU) return PFK_ERR_UNSUPPORTED;       // pfk_conv2d_gelu_b16 (pfk.h)
+  return conv2d_b16_impl(d, stream);
+}
+
+int pfk_conv2d_gelu_b16(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
+  if (!d || d->epilogue != PFK_EPI_LINEAR_GELU || d->relu) return PFK_ERR_BAD_ARG;
+  return conv2d_b16_impl(d, stream);
 }
 
 }  // extern "C"

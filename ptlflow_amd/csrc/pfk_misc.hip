@@ -473,10 +473,12 @@ __global__ __launch_bounds__(256) void convex_upsample4_kernel(const float* __re
 
 // SEARAFT.upsample_data (sea_raft.py:147-163): convex_upsample4_kernel's flow, operation for operation (same bits), plus the
 // same convex combination of the zero-padded 3x3 neighbourhood of `n` info channels (no factor 8) -> info_out [B][n][8H][8W].
+// TM = __bf16: the mask as the K8b mask head writes it; the flow is then convex_upsample4_kernel<__bf16>'s, bit for bit.
 constexpr int UP_MAX_INFO = 8;
+template <typename TM = float>
 __global__ __launch_bounds__(256) void convex_upsample_info4_kernel(const float* __restrict__ flow, int flow_ld,
                                                                     const float* __restrict__ info, int info_ld, int n_info,
-                                                                    const float* __restrict__ mask, int mask_ld,
+                                                                    const TM* __restrict__ mask, int mask_ld,
                                                                     float* __restrict__ out, float* __restrict__ info_out,
                                                                     long long M, int H, int W) {
   const int lane = threadIdx.x & 63;
@@ -487,7 +489,7 @@ __global__ __launch_bounds__(256) void convex_upsample_info4_kernel(const float*
   const long long b = p / hw;
   const int pix = (int)(p - b * hw);
   const int y = pix / W, x = pix - y * W;
-  const float* mrow = mask + p * mask_ld + idx * 4;
+  const TM* mrow = mask + p * mask_ld + idx * 4;
   f32x4 m[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) m[k] = load4_widen(mrow + k * 64);
@@ -856,8 +858,23 @@ int pfk_convex_upsample_info_pm_f32(const float* flow_pm, int flow_ld, const flo
   const long long M = (long long)B * H * W;
   const long long blocks = (M + 15) / 16;
   if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(convex_upsample_info4_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
+  hipLaunchKernelGGL(convex_upsample_info4_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
                      flow_ld, info_pm, info_ld, n_info, mask, mask_ld, flow_out, info_out, M, H, W);
+  return pfk_launch_status();
+}
+
+int pfk_convex_upsample_info_pm_b16(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
+                                    const void* mask_bf16, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
+                                    pfk_stream_t stream) {
+  if (!flow_pm || !info_pm || !mask_bf16 || !flow_out || !info_out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0)
+    return PFK_ERR_BAD_ARG;
+  if (n_info < 1 || n_info > UP_MAX_INFO || info_ld < n_info) return PFK_ERR_BAD_ARG;
+  if (!pfk_aligned16(mask_bf16) || (mask_ld & 7) || !pfk_aligned16(flow_out) || !pfk_aligned16(info_out)) return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  const long long blocks = (M + 15) / 16;
+  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(convex_upsample_info4_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
+                     flow_ld, info_pm, info_ld, n_info, static_cast<const __bf16*>(mask_bf16), mask_ld, flow_out, info_out, M, H, W);
   return pfk_launch_status();
 }
 

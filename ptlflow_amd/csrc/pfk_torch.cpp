@@ -273,13 +273,15 @@ void conv2d_group(at::TensorList srcs, int64_t B, int64_t H, int64_t W, at::IntA
   check_ok(pfk_conv2d_group_f32(d, (int)n, cur_stream()), "conv2d_group");
 }
 
-// K8b: bf16 sources / weight (pfk_conv2d_b16); `out` may be bf16 or fp32, h / aux_z / residual fp32, aux_rh / h_b16 bf16
-void conv2d_b16(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, const Tensor& weight,
-                const c10::optional<Tensor>& bias, int64_t cout, int64_t epilogue, bool relu, double scale,
-                const c10::optional<Tensor>& out, const c10::optional<Tensor>& h, const c10::optional<Tensor>& h_b16,
-                const c10::optional<Tensor>& aux_z, const c10::optional<Tensor>& aux_rh, const c10::optional<Tensor>& residual,
-                int64_t stride, bool relu_after_residual) {
+// K8b: bf16 sources / weight (pfk_conv2d_b16); `out` may be bf16 or fp32, h / aux_z / residual fp32, aux_rh / h_b16 bf16.
+// `gelu_entry`: the descriptor goes to pfk_conv2d_gelu_b16 instead (torch.ops.pfk.conv2d_gelu_b16)
+void conv2d_b16_run(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, const Tensor& weight,
+                    const c10::optional<Tensor>& bias, int64_t cout, int64_t epilogue, bool relu, double scale,
+                    const c10::optional<Tensor>& out, const c10::optional<Tensor>& h, const c10::optional<Tensor>& h_b16,
+                    const c10::optional<Tensor>& aux_z, const c10::optional<Tensor>& aux_rh, const c10::optional<Tensor>& residual,
+                    int64_t stride, bool relu_after_residual, bool gelu_entry) {
   OpScope scope(weight);
+  const bool lin = epilogue == PFK_EPI_LINEAR || (gelu_entry && epilogue == PFK_EPI_LINEAR_GELU);
   if (weight.dim() == 3) {
     // batched GEMM (pfk_conv_b16_desc.batches): src [Bt, M, K] bf16, weight [Bt, cout, K] bf16, out [Bt, M, cout], residual [Bt, M, cout]
     TORCH_CHECK(srcs.size() == 1 && srcs[0].dim() == 3 && kh == 1 && kw == 1 && epilogue == PFK_EPI_LINEAR && out.has_value() && out->dim() == 3,
@@ -351,11 +353,33 @@ void conv2d_b16(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh
   }
   if (residual.has_value()) {
     const bool r16 = check_pm_any(*residual, "residual");
-    TORCH_CHECK(epilogue == PFK_EPI_LINEAR || r16, "conv2d_b16: the GRU epilogues take a bfloat16 residual (the context term)");
+    TORCH_CHECK(lin || r16, "conv2d_b16: the GRU epilogues take a bfloat16 residual (the context term)");
     TORCH_CHECK(residual->size(0) == M && residual->size(1) == cout, "conv2d_b16: residual must be a [M, cout] view");
-    d.residual = residual->data_ptr(); d.residual_ld = residual->stride(0); d.residual_bf16 = r16 && epilogue == PFK_EPI_LINEAR;
+    d.residual = residual->data_ptr(); d.residual_ld = residual->stride(0); d.residual_bf16 = r16 && lin;
+  }
+  if (gelu_entry) {
+    check_ok(pfk_conv2d_gelu_b16(&d, cur_stream()), "conv2d_gelu_b16");
+    return;
   }
   check_ok(pfk_conv2d_b16(&d, cur_stream()), "conv2d_b16");
+}
+
+void conv2d_b16(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, const Tensor& weight,
+                const c10::optional<Tensor>& bias, int64_t cout, int64_t epilogue, bool relu, double scale,
+                const c10::optional<Tensor>& out, const c10::optional<Tensor>& h, const c10::optional<Tensor>& h_b16,
+                const c10::optional<Tensor>& aux_z, const c10::optional<Tensor>& aux_rh, const c10::optional<Tensor>& residual,
+                int64_t stride, bool relu_after_residual) {
+  conv2d_b16_run(srcs, B, H, W, kh, kw, weight, bias, cout, epilogue, relu, scale, out, h, h_b16, aux_z, aux_rh, residual, stride,
+                 relu_after_residual, false);
+}
+
+// K8b + exact GELU (pfk_conv2d_gelu_b16): SEA-RAFT's pwconv1 + nn.GELU() on bf16 rows; `out` bf16 or fp32, residual as LINEAR
+void conv2d_gelu_b16(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, const Tensor& weight,
+                     const c10::optional<Tensor>& bias, int64_t cout, double scale, const Tensor& out,
+                     const c10::optional<Tensor>& residual) {
+  TORCH_CHECK(weight.dim() == 2, "conv2d_gelu_b16: bf16 packed weight [cout, ktot] (no batched form)");
+  conv2d_b16_run(srcs, B, H, W, kh, kw, weight, bias, cout, PFK_EPI_LINEAR_GELU, false, scale, out, c10::nullopt, c10::nullopt,
+                 c10::nullopt, c10::nullopt, residual, 1, false, true);
 }
 
 void debug_set_b16(int64_t cfg) { check_ok(pfk_debug_set_b16((int)cfg), "debug_set_b16"); }
@@ -466,6 +490,46 @@ void convex_upsample_info_pm(const Tensor& flow_pm, const Tensor& info_pm, const
   check_ok(pfk_convex_upsample_info_pm_f32(fptr(flow_pm), flow_pm.stride(0), fptr(info_pm), info_pm.stride(0), n, fptr(mask),
                                            mask.stride(0), fptr(flow_out), fptr(info_out), B, H, W, cur_stream()),
            "convex_upsample_info_pm");
+}
+
+// the same with a bf16 mask [M, 576] view (pfk_convex_upsample_info_pm_b16)
+void convex_upsample_info_pm_b16(const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask, Tensor flow_out, Tensor info_out) {
+  OpScope scope(flow_pm);
+  check_pm(flow_pm, "flow_pm"); check_pm(info_pm, "info_pm"); check_pm_b16(mask, "mask");
+  check_dev_f32(flow_out, "flow_out"); check_dev_f32(info_out, "info_out");
+  TORCH_CHECK(flow_out.dim() == 4 && flow_out.size(1) == 2 && flow_out.is_contiguous() && flow_out.size(2) % 8 == 0 && flow_out.size(3) % 8 == 0,
+              "convex_upsample_info_pm_b16: flow_out [B, 2, 8H, 8W] contiguous");
+  const int B = flow_out.size(0), H = flow_out.size(2) / 8, W = flow_out.size(3) / 8;
+  const int n = info_out.dim() == 4 ? (int)info_out.size(1) : 0;
+  TORCH_CHECK(info_out.dim() == 4 && info_out.is_contiguous() && info_out.size(0) == B && info_out.size(2) == 8 * H && info_out.size(3) == 8 * W,
+              "convex_upsample_info_pm_b16: info_out [B, n, 8H, 8W] contiguous");
+  const int64_t M = (int64_t)B * H * W;
+  TORCH_CHECK(mask.size(0) == M && mask.size(1) == 576 && flow_pm.size(0) == M && flow_pm.size(1) >= 2 && info_pm.size(0) == M &&
+              info_pm.size(1) >= n, "convex_upsample_info_pm_b16: row counts / widths");
+  check_ok(pfk_convex_upsample_info_pm_b16(fptr(flow_pm), flow_pm.stride(0), fptr(info_pm), info_pm.stride(0), n, mask.data_ptr(),
+                                           mask.stride(0), fptr(flow_out), fptr(info_out), B, H, W, cur_stream()),
+           "convex_upsample_info_pm_b16");
+}
+
+// ConvNextBlock dwconv + LayerNorm on bf16 rows (pfk_dwconv_layernorm_b16): in / out bf16 [B*H*W, >= C] views, weights fp32 as below
+void dwconv_layernorm_b16(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                          const Tensor& ln_bias, double eps, Tensor out, int64_t B, int64_t H, int64_t W, int64_t k) {
+  OpScope scope(in);
+  check_pm_b16(in, "in"); check_pm_b16(out, "out");
+  check_dev_f32(dw_weight, "dw_weight"); check_dev_f32(ln_weight, "ln_weight"); check_dev_f32(ln_bias, "ln_bias");
+  const int64_t C = in.size(1);
+  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == in.size(0) && out.size(1) >= C, "dwconv_layernorm_b16: in / out rows");
+  TORCH_CHECK(dw_weight.is_contiguous() && dw_weight.numel() == C * k * k, "dwconv_layernorm_b16: dw_weight [C, k*k] contiguous");
+  TORCH_CHECK(ln_weight.is_contiguous() && ln_weight.numel() == C && ln_bias.is_contiguous() && ln_bias.numel() == C,
+              "dwconv_layernorm_b16: LayerNorm weight / bias [C]");
+  const float* db = nullptr;
+  if (dw_bias.has_value()) {
+    check_dev_f32(*dw_bias, "dw_bias");
+    TORCH_CHECK(dw_bias->is_contiguous() && dw_bias->numel() == C, "dwconv_layernorm_b16: dw_bias [C]");
+    db = fptr(*dw_bias);
+  }
+  check_ok(pfk_dwconv_layernorm_b16(in.data_ptr(), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps,
+                                    out.data_ptr(), out.stride(0), B, H, W, C, k, cur_stream()), "dwconv_layernorm_b16");
 }
 
 // ConvNextBlock dwconv + LayerNorm: in [B*H*W, C] view (e.g. a slice of the update engine's hx), dw_weight [C, 1, k, k] or [C, k*k]
@@ -1009,6 +1073,11 @@ TORCH_LIBRARY(pfk, m) {
   m.def("convex_upsample_info_pm(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor(a!) flow_out, Tensor(b!) info_out) -> ()");
   m.def("dwconv_layernorm(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, Tensor(a!) out, "
         "int B, int H, int W, int k) -> ()");
+  m.def("dwconv_layernorm_b16(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
+        "Tensor(a!) out, int B, int H, int W, int k) -> ()");
+  m.def("conv2d_gelu_b16(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, float scale, "
+        "Tensor(a!) out, Tensor? residual=None) -> ()");
+  m.def("convex_upsample_info_pm_b16(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor(a!) flow_out, Tensor(b!) info_out) -> ()");
   m.def("mask_upsample(Tensor x, Tensor weight_perm, Tensor? bias_perm, float scale, Tensor flow_pm, Tensor(a!) out) -> ()");
   m.def("upflow8(Tensor coords0, Tensor coords1, Tensor(a!) out) -> ()");
   m.def("altcorr_forward(Tensor fmap1, Tensor fmap2, Tensor coords, int radius) -> Tensor");
@@ -1042,6 +1111,9 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("mask_upsample", &mask_upsample);
   m.impl("convex_upsample_info_pm", &convex_upsample_info_pm);
   m.impl("dwconv_layernorm", &dwconv_layernorm);
+  m.impl("dwconv_layernorm_b16", &dwconv_layernorm_b16);
+  m.impl("conv2d_gelu_b16", &conv2d_gelu_b16);
+  m.impl("convex_upsample_info_pm_b16", &convex_upsample_info_pm_b16);
   m.impl("upflow8", &upflow8);
   m.impl("altcorr_forward", &altcorr_forward);
   m.impl("altcorr_backward", &altcorr_backward);

@@ -109,22 +109,38 @@ def match_sea_raft(model: torch.nn.Module) -> Optional[Tuple[int, int]]:
     return int(w[1]), nb
 
 
-def _install_sea_raft(model: torch.nn.Module) -> bool:
-    """SEA-RAFT's update block, heads and `upsample_data` (sea_update.py); True when installed (or already there)."""
+def _sea_precision(sea_raft_update) -> Optional[str]:
+    """`accelerate`'s `sea_raft_update` -> the SEA seams' precision, None = not installed"""
+    if sea_raft_update is False or sea_raft_update is None:
+        return None
+    if sea_raft_update is True or sea_raft_update == "fp32":
+        return "fp32"
+    if sea_raft_update == "bf16":
+        return "bf16"
+    raise ValueError(f"sea_raft_update must be False, True, 'fp32' or 'bf16', got {sea_raft_update!r}")
+
+
+def _install_sea_raft(model: torch.nn.Module, precision: str = "fp32") -> bool:
+    """SEA-RAFT's update block, heads and `upsample_data` (sea_update.py); True when installed (or already there).  Installed seams
+    of another precision are switched to this one (the block's engine is rebuilt on its next call)."""
     from .sea_update import PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam
     if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):
+        model.update_block.set_precision(precision)
+        seam = model.__dict__.get("upsample_data")
+        if isinstance(seam, _UpsampleDataSeam):
+            seam.precision = precision
         return True
     m = match_sea_raft(model)
     if m is None:
         return False
-    block = PfkSeaRaftUpdateBlock(model.update_block, num_blocks=m[1], corr_channels=m[0])
+    block = PfkSeaRaftUpdateBlock(model.update_block, num_blocks=m[1], corr_channels=m[0], precision=precision)
     block._heads = {"flow_head": model.flow_head, "upsample_weight": model.upsample_weight}
     model.update_block = block
     model.flow_head = _SeaHeadSeam(model.flow_head, block, "flow_head")
     model.upsample_weight = _SeaHeadSeam(model.upsample_weight, block, "upsample_weight")
     if callable(getattr(model, "upsample_data", None)) and _SEA_UPSAMPLE not in model.__dict__:
         model.__dict__[_SEA_UPSAMPLE] = model.upsample_data
-        model.__dict__["upsample_data"] = _UpsampleDataSeam(model.upsample_data)
+        model.__dict__["upsample_data"] = _UpsampleDataSeam(model.upsample_data, precision)
     return True
 
 
@@ -556,7 +572,7 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
-               sea_raft_update: bool = False) -> torch.nn.Module:
+               sea_raft_update=False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -572,7 +588,12 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     forward: train mode, a gradient graph, a half / bf16 model or a changed `iters` are honoured (`_DeadWorkSkip`).
     ``sea_raft_update`` (default False): on a SEA-RAFT model, also replace its update block (motion encoder + ConvNeXt blocks), its
     `flow_head` / `upsample_weight` heads and its `upsample_data` by the kernels of sea_update.py (fp32 inference; anything else
-    keeps the model's modules).  Off by default: plain `accelerate(model)` leaves SEA-RAFT's block to torch as before."""
+    keeps the model's modules).  Off by default: plain `accelerate(model)` leaves SEA-RAFT's block to torch as before.
+    ``sea_raft_update="bf16"``: the same seams on the bf16 matrix-core path (K8b, bf16 activation rows): they serve fp32 and bf16
+    GPU tensors with autocast off or cuda autocast to bfloat16 (an autocast loop gets bf16 `net` / mask views back, an fp32 loop
+    fp32 ones; `flow_head` returns fp32).  ``True`` and ``"fp32"`` are today's fp32 path; any other value raises ValueError.  A
+    second call with another value switches the installed seams.  ``conv_precision`` is not read by the SEA seams."""
+    sea_precision = _sea_precision(sea_raft_update)
     load_native()
     mod_name = type(model).__module__
     # registered classes (`class raft(RAFT)`) live in the same module as the implementation
@@ -584,7 +605,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
         spec = match_update_block(model.update_block)
         if spec is not None:
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
-    sea = bool(sea_raft_update) and _install_sea_raft(model)
+    sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
     hook = getattr(mod, "get_corr_block", None)
     if corr and hasattr(mod, _ORIG) and hasattr(hook, "channels_last"):      # (default for callers that are not a model's forward)
         hook.channels_last = sea or isinstance(getattr(model, "update_block", None), PfkUpdateBlock)

@@ -18,6 +18,18 @@ iteration, after the caller's lookup:
 
 Layer scale: `gamma * (x @ W2^T + b2)` is computed as `x @ (gamma W2)^T + gamma b2`, one rounding moved.
 
+`precision="bf16"` runs the same chain on the K8b path (`UpdateEngine`'s `b16`: bf16 activation rows, bf16 weights in 64-channel K
+chunks, fp32 accumulation): the motion encoder writes the bf16 twin `hxb`, and per block
+
+      dwconv 7x7 + LayerNorm             pfk_dwconv_layernorm_b16  (hxb)         -> ln   bf16 [M, 384]
+      pwconv1 + GELU                     pfk_conv2d_gelu_b16                     -> mid  bf16 [M, 512]
+      gamma * pwconv2 + input            pfk_conv2d_b16, LINEAR + residual hxb   -> res  bf16 [M, 384]
+      final 1x1 384 -> 128               pfk_conv2d_b16                          -> hxb[:, :128]
+
+The net state lives in hxb only (bf16, as the `final` convolution's output under autocast).  The heads read hxb; `fo` stays fp32
+[M, 8], the mask logits are bf16 [M, 576] in the plain channel order, upsampled by pfk_convex_upsample_info_pm_b16.  gamma is folded
+into W2 in fp32 and rounded to bf16 once: `bf16(gamma W2)` against autocast's `gamma * bf16(x W2^T)`, one weight rounding apart.
+
 The seams (`accelerate(model, sea_raft_update=True)`, patch.py) hand the model's own loop (sea_raft.py:217-236) views of these
 buffers, the way `PfkUpdateBlock` does for RAFT: `update_block(net, context, corr, flow) -> net` is the engine's h slice, and
 `flow_head(net)` / `upsample_weight(net)` recognise that very object and run the heads from it.  Everything the kernels do not
@@ -31,6 +43,8 @@ import torch
 
 from .packing import pack_conv_weight
 from .update import EPI_LINEAR, UpdateEngine, UpdateSpec
+
+SEA_PRECISIONS = ("fp32", "bf16")
 
 EPI_LINEAR_GELU = 3        # enum pfk_epilogue (include/pfk.h)
 LN_EPS = 1e-6              # sea_raft/layer.py:57 (LayerNorm(dim, eps=1e-6))
@@ -78,11 +92,16 @@ HEAD_SHAPES = {
 
 class SeaUpdateEngine(UpdateEngine):
     """Packed weights and pixel-major buffers of SEA-RAFT's refinement (module docstring).  `params`: the update block's parameters
-    (`encoder.*`, `refine.{i}.*`) and the heads' as `flow_head.{0,2}.*`, `upsample_weight.{0,2}.*`.  fp32 only."""
+    (`encoder.*`, `refine.{i}.*`) and the heads' as `flow_head.{0,2}.*`, `upsample_weight.{0,2}.*`.
+    `precision`: "fp32" or "bf16" (the K8b path, module docstring)."""
 
-    def __init__(self, params: Dict[str, torch.Tensor], spec: UpdateSpec, device: torch.device, num_blocks: int = 2):
+    def __init__(self, params: Dict[str, torch.Tensor], spec: UpdateSpec, device: torch.device, num_blocks: int = 2,
+                 precision: str = "fp32"):
+        if precision not in SEA_PRECISIONS:
+            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
         self.num_blocks = int(num_blocks)
-        super().__init__(params, spec, device, "fp32")
+        self.precision = precision
+        super().__init__(params, spec, device, precision)
 
     # ------------------------------------------------------------------ weights
     def pack(self, P: Dict[str, torch.Tensor]) -> None:
@@ -99,6 +118,11 @@ class SeaUpdateEngine(UpdateEngine):
         def g(name):
             return P[name].detach().to(device=dev, dtype=torch.float32)
 
+        def pk(weight, segments):
+            if self.b16:      # K8b: bf16 [cout, ktot], 64-channel K chunks, rounded once from the fp32 (gamma-folded) weight
+                return pack_conv_weight(weight, segments, kpad=64).to(torch.bfloat16).contiguous()
+            return pack_conv_weight(weight, segments)
+
         C = self.spec.hx_channels
         w = self.w
         for i in range(self.num_blocks):
@@ -108,16 +132,16 @@ class SeaUpdateEngine(UpdateEngine):
             w[f"ln{i}.w"] = g(p + "norm.weight").contiguous()
             w[f"ln{i}.b"] = g(p + "norm.bias").contiguous()
             w1 = g(p + "pwconv1.weight")
-            w[f"p1{i}.w"] = pack_conv_weight(w1[:, :, None, None], [(0, C, C)])
+            w[f"p1{i}.w"] = pk(w1[:, :, None, None], [(0, C, C)])
             w[f"p1{i}.b"] = g(p + "pwconv1.bias").contiguous()
             gamma = g(p + "gamma") if (p + "gamma") in P else torch.ones(C, device=dev)
             w2 = g(p + "pwconv2.weight")
-            w[f"p2{i}.w"] = pack_conv_weight((gamma[:, None] * w2)[:, :, None, None], [(0, w2.shape[1], w2.shape[1])])
+            w[f"p2{i}.w"] = pk((gamma[:, None] * w2)[:, :, None, None], [(0, w2.shape[1], w2.shape[1])])
             w[f"p2{i}.b"] = (gamma * g(p + "pwconv2.bias")).contiguous()
-            w[f"fi{i}.w"] = pack_conv_weight(g(p + "final.weight"), [(0, C, C)])
+            w[f"fi{i}.w"] = pk(g(p + "final.weight"), [(0, C, C)])
             w[f"fi{i}.b"] = g(p + "final.bias").contiguous()
             self._real_cin.update({f"p1{i}": C, f"p2{i}": w2.shape[1], f"fi{i}": C})
-        w["fo.w"] = pack_conv_weight(g("flow_head.2.weight"), [(0, self.spec.fh_hidden, self.spec.fh_hidden)])
+        w["fo.w"] = pk(g("flow_head.2.weight"), [(0, self.spec.fh_hidden, self.spec.fh_hidden)])
         w["fo.b"] = g("flow_head.2.bias").contiguous()
         self._real_cin["fo"] = self.spec.fh_hidden
         self.mid_channels = int(P["refine.0.pwconv1.weight"].shape[0]) if self.num_blocks else 0
@@ -129,9 +153,10 @@ class SeaUpdateEngine(UpdateEngine):
         super().bind(B, H, W)
         M, dev = B * H * W, self.device
         C = self.spec.hx_channels
-        self.ln = torch.zeros(M, C, device=dev, dtype=torch.float32)
-        self.mid = torch.zeros(M, self.mid_channels, device=dev, dtype=torch.float32)
-        self.res = torch.zeros(M, C, device=dev, dtype=torch.float32)
+        dt = torch.bfloat16 if self.b16 else torch.float32
+        self.ln = torch.zeros(M, C, device=dev, dtype=dt)
+        self.mid = torch.zeros(M, self.mid_channels, device=dev, dtype=dt)
+        self.res = torch.zeros(M, C, device=dev, dtype=dt)
         self.fo = torch.zeros(M, 8, device=dev, dtype=torch.float32)      # flow_head output: delta (2) | info (4) | pad
 
     # ------------------------------------------------------------------ one iteration
@@ -140,6 +165,15 @@ class SeaUpdateEngine(UpdateEngine):
         into hx[:, :128], which the next block (and the heads) read."""
         B, H, W = self._shape
         C = self.spec.hx_channels
+        if self.b16:
+            for i in range(self.num_blocks):
+                self.ops.dwconv_layernorm_b16(self.hxb, self.w[f"dw{i}.w"], self.w[f"dw{i}.b"], self.w[f"ln{i}.w"], self.w[f"ln{i}.b"],
+                                              LN_EPS, self.ln, B, H, W, 7)
+                self.ops.conv2d_gelu_b16([self.ln], B, H, W, 1, 1, self.w[f"p1{i}.w"], self.w[f"p1{i}.b"], self.mid_channels, 1.0,
+                                         self.mid)
+                self._conv([self.mid], 1, 1, f"p2{i}", C, relu=False, out=self.res, residual=self.hxb)
+                self._conv([self.res], 1, 1, f"fi{i}", self.spec.hidden, relu=False, out=self.hxb[:, : self.spec.hidden])
+            return
         for i in range(self.num_blocks):
             self.ops.dwconv_layernorm(self.hx, self.w[f"dw{i}.w"], self.w[f"dw{i}.b"], self.w[f"ln{i}.w"], self.w[f"ln{i}.b"], LN_EPS,
                                       self.ln, B, H, W, 7)
@@ -174,6 +208,18 @@ class SeaUpdateEngine(UpdateEngine):
         B, H, W = self._shape
         return self.fo[:, :6].unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
 
+    def net_nchw(self) -> torch.Tensor:
+        """the net state as NCHW with channels-last strides: a view of hx's h slice, or of hxb's on the bf16 path"""
+        if not self.b16:
+            return super().net_nchw()
+        B, H, W = self._shape
+        return self.hxb[:, : self.spec.hidden].unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
+
+    def mask_nchw_raw(self) -> torch.Tensor:
+        """the mask logits as NCHW with channels-last strides, in the buffer's own dtype (bf16 on the bf16 path)"""
+        B, H, W = self._shape
+        return self.mask.view(B, H, W, self.spec.mask_channels).permute(0, 3, 1, 2)
+
 
 def _fp32_eligible(*tensors) -> bool:
     """GPU fp32 tensors, no gradient graph, no autocast region: what the kernels implement"""
@@ -186,14 +232,44 @@ def _fp32_eligible(*tensors) -> bool:
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
 
+def _b16_eligible(*tensors) -> bool:
+    """The bf16 path's calls: GPU tensors of fp32 or bf16, no gradient graph, autocast off or cuda autocast to bfloat16"""
+    t0 = tensors[0]
+    if not t0.is_cuda:
+        return False
+    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    for t in tensors:
+        if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.bfloat16) or t.device != t0.device:
+            return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+
+
+def _eligible(precision: str, tensors, params) -> bool:
+    """what the engine of `precision` implements: the activations as above, the parameters fp32 on the same device"""
+    if precision == "fp32":
+        return _fp32_eligible(*tensors, *params)
+    return _b16_eligible(*tensors) and all(p.dtype == torch.float32 and p.device == tensors[0].device for p in params) and \
+        not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+
+
+def _copy_nchw_rows(src: torch.Tensor, dst: torch.Tensor) -> None:
+    """NCHW [B, C, H, W] of any float dtype -> the [B*H*W, C] rows `dst` (a view), converting the dtype"""
+    B, C, H, W = src.shape
+    dst.unflatten(0, (B, H, W)).copy_(src.permute(0, 2, 3, 1))
+
+
 class PfkSeaRaftUpdateBlock(torch.nn.Module):
     """Drop-in for SEA-RAFT's ``model.update_block``: ``forward(net, inp, corr, flow) -> net`` NCHW (sea_raft/update.py:49-54), a
     view of the engine's h slice with channels-last strides, overwritten by the next call (the reference loop rebinds `net` every
     iteration, sea_raft.py:223).  Keeps the wrapped sub-modules (`encoder`, `refine`): state_dict keys, checkpoints and optimizers
     are unchanged.  The heads' parameters are read through `_heads` (not registered here: they stay the model's own children)."""
 
-    def __init__(self, ref_block: torch.nn.Module, num_blocks: int, corr_channels: int):
+    def __init__(self, ref_block: torch.nn.Module, num_blocks: int, corr_channels: int, precision: str = "fp32"):
         super().__init__()
+        if precision not in SEA_PRECISIONS:
+            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
+        self.precision = precision
         for name, child in ref_block.named_children():
             self.add_module(name, child)
         self._ref = [ref_block]
@@ -206,6 +282,7 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
         self._inp_ref, self._inp_version = None, -1
         self._last_out, self._last_version = None, -1
         self._fm_for = None        # the `net` object whose flow_head[0] | upsample_weight[0] activation `fm` holds
+        self._out_b16 = False      # bf16 path: the handed-out net is a bf16 view (an autocast loop), else an fp32 copy
         self.calls = 0             # kernel-path calls (tests count them)
 
     def _all_params(self) -> Dict[str, torch.nn.Parameter]:
@@ -217,8 +294,8 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
     def _get_engine(self, device) -> SeaUpdateEngine:
         P = self._all_params()
         v = tuple((p.data_ptr(), p._version) for p in P.values())
-        if self._engine is None or self._engine.device != device:
-            self._engine = SeaUpdateEngine(P, self.spec, device, self.num_blocks)
+        if self._engine is None or self._engine.device != device or self._engine.precision != self.precision:
+            self._engine = SeaUpdateEngine(P, self.spec, device, self.num_blocks, self.precision)
             self._versions = v
         elif v != self._versions:
             self._engine.pack(P)
@@ -240,8 +317,23 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
             return cpm.reshape(M, corr.shape[1])
         return None
 
+    def set_precision(self, precision: str) -> None:
+        """switch the kernel path (a second `accelerate` with another `sea_raft_update`): the engine is rebuilt on the next call"""
+        if precision not in SEA_PRECISIONS:
+            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
+        if precision != self.precision:
+            self.precision = precision
+            self._engine, self._versions = None, None
+            self._inp_ref, self._inp_version = None, -1
+            self._last_out, self._last_version, self._fm_for = None, -1, None
+
+    def _params(self):
+        return list(self.parameters()) + [p for m in self._heads.values() for p in m.parameters()]
+
     def forward(self, net, inp, corr, flow):
-        params = list(self.parameters()) + [p for m in self._heads.values() for p in m.parameters()]
+        if self.precision == "bf16":
+            return self._forward_b16(net, inp, corr, flow)
+        params = self._params()
         ok = (torch.is_tensor(corr) and _fp32_eligible(net, inp, corr, flow, *params) and net.dim() == 4
               and corr.shape[1] == self.spec.corr_channels and net.shape[1] == self.spec.hidden and inp.shape[1] == self.spec.context)
         B, _, H, W = net.shape if net.dim() == 4 else (0, 0, 0, 0)
@@ -265,6 +357,50 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
             ops.nchw_to_pm(flow.contiguous(), eng.flow_view)
             eng.update(corr_pm)
             out = eng.net_nchw()
+        self.calls += 1
+        self._last_out, self._last_version, self._fm_for = out, out._version, None
+        return out
+
+    def _forward_b16(self, net, inp, corr, flow):
+        """the bf16 path: the state in hxb, the lookup rows copied into corr16 (as PfkUpdateBlock does for RAFT's K8b engine)"""
+        ok = (torch.is_tensor(corr) and net.dim() == 4 and corr.dim() == 4 and _eligible("bf16", (net, inp, corr, flow), self._params())
+              and corr.shape[1] == self.spec.corr_channels and net.shape[1] == self.spec.hidden and inp.shape[1] == self.spec.context
+              and flow.dim() == 4 and flow.shape[1] == 2 and inp.shape[0] == net.shape[0] and inp.shape[2:] == net.shape[2:]
+              and corr.shape[0] == net.shape[0] and corr.shape[2:] == net.shape[2:] and flow.shape[0] == net.shape[0]
+              and flow.shape[2:] == net.shape[2:])
+        if not ok:
+            self._last_out, self._fm_for = None, None
+            return self._ref[0](net, inp, corr.contiguous() if torch.is_tensor(corr) else corr, flow)
+        B, _, H, W = net.shape
+        M = B * H * W
+        s = self.spec
+        with torch.no_grad():
+            eng = self._get_engine(net.device)
+            eng.bind(B, H, W)
+            new_forward = not self.owns(net)
+            if new_forward:
+                eng.watch_faults()
+                _copy_nchw_rows(net, eng.hxb[:, : s.hidden])
+            if new_forward or inp is not self._inp_ref or inp._version != self._inp_version:
+                _copy_nchw_rows(inp, eng.hxb[:, s.hidden: s.hidden + s.context])
+                self._inp_ref, self._inp_version = inp, inp._version
+            if flow.dtype == torch.float32:
+                eng.ops.nchw_to_pm(flow.contiguous(), eng.flow_view)
+            else:
+                _copy_nchw_rows(flow, eng.flow_view)
+            eng.flow_changed()           # the fp32 flow (convf1's input) mirrored into hxb (the ConvNeXt blocks' input)
+            C = s.corr_channels
+            corr_pm = self._corr_pm(corr, M)
+            if corr_pm is not None:
+                eng.corr16[:, :C].copy_(corr_pm[:, :C])
+            else:
+                _copy_nchw_rows(corr, eng.corr16[:, :C])
+            eng.update(eng.corr16)
+            out = eng.net_nchw()
+            # bf16 out where the model's own block would return bf16: a bf16 net, or any net inside cuda bf16 autocast
+            self._out_b16 = net.dtype == torch.bfloat16 or torch.is_autocast_enabled("cuda")
+            if not self._out_b16:
+                out = out.float()
         self.calls += 1
         self._last_out, self._last_version, self._fm_for = out, out._version, None
         return out
@@ -302,16 +438,19 @@ class _SeaHeadSeam(torch.nn.Module):
 
     def forward(self, x):
         blk = self._block[0]
-        if not (torch.is_tensor(x) and blk.owns(x) and _fp32_eligible(x, *self.parameters())):
+        if not (torch.is_tensor(x) and blk.owns(x) and _eligible(blk.precision, (x,), list(self.parameters()))):
             return self._ref[0](x)
         eng = blk.heads_fm(x)
         with torch.no_grad():
             if self.kind == "flow_head":
                 eng.flow_head_out()
-                out = eng.fo_nchw()
+                out = eng.fo_nchw()            # fp32 on both paths
             else:
                 eng.mask_logits(1.0)
-                out = eng.mask_nchw()
+                if eng.b16:                    # bf16 logits: a view for an autocast loop, an fp32 copy for an fp32 one
+                    out = eng.mask_nchw_raw() if blk._out_b16 else eng.mask_nchw()
+                else:
+                    out = eng.mask_nchw()
         self.calls += 1
         return out
 
@@ -322,9 +461,11 @@ class _UpsampleDataSeam:
     input and the kernel is used only if they agree to 1e-5.  Pixel-major rows are read without a copy where the strides allow
     (the channels-last `0.25 * upsample_weight(net)` and the info slice of `flow_head(net)`)."""
 
-    def __init__(self, original):
+    def __init__(self, original, precision: str = "fp32"):
         self.original = original
+        self.precision = precision     # "bf16": also bf16 tensors and cuda bf16 autocast; bf16 masks on their own kernel
         self.ok = None
+        self.ok16 = None               # the probe of the bf16-mask kernel
         self.calls = 0
 
     @staticmethod
@@ -336,23 +477,38 @@ class _UpsampleDataSeam:
             r = r.clone(memory_format=torch.contiguous_format)
         return r
 
+    @staticmethod
+    def _rows_b16(t: torch.Tensor) -> torch.Tensor:
+        """bf16 [B, C, H, W] -> [B*H*W, C] rows with 16-byte rows (a view where the strides allow, else one copy)"""
+        B, C, H, W = t.shape
+        r = t.permute(0, 2, 3, 1).reshape(B * H * W, C)
+        if r.stride(1) != 1 or r.data_ptr() % 16 or r.stride(0) % 8:
+            r = r.clone(memory_format=torch.contiguous_format)
+        return r
+
     @classmethod
     def _kernel(cls, flow, info, mask):
         B, _, H, W = flow.shape
         n = info.shape[1]
         flow_up = torch.empty(B, 2, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
         info_up = torch.empty(B, n, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
-        torch.ops.pfk.convex_upsample_info_pm(cls._rows(flow), cls._rows(info), cls._rows(mask, aligned=True), flow_up, info_up)
+        flow, info = flow.float(), info.float()        # (bf16 flow / info of an autocast loop: fp32 rows, exact)
+        if mask.dtype == torch.bfloat16:
+            torch.ops.pfk.convex_upsample_info_pm_b16(cls._rows(flow), cls._rows(info), cls._rows_b16(mask), flow_up, info_up)
+        else:
+            torch.ops.pfk.convex_upsample_info_pm(cls._rows(flow), cls._rows(info), cls._rows(mask, aligned=True), flow_up, info_up)
         return flow_up, info_up
 
-    def _probe(self, device) -> bool:
+    def _probe(self, device, mask_dtype=torch.float32) -> bool:
+        """the kernel against the model's own method on a small random input; a bf16 mask is given to the method as its exact
+        fp32 value (the kernel's softmax runs in fp32)"""
         g = torch.Generator().manual_seed(7)
         flow = (torch.randn(2, 2, 5, 7, generator=g) * 3).to(device)
         info = torch.randn(2, 4, 5, 7, generator=g).to(device)
-        mask = torch.randn(2, 576, 5, 7, generator=g).to(device)
+        mask = torch.randn(2, 576, 5, 7, generator=g).to(device=device, dtype=mask_dtype)
         try:
-            with torch.no_grad():
-                want = self.original(flow, info, mask)
+            with torch.no_grad(), torch.autocast("cuda", enabled=False):
+                want = self.original(flow, info, mask.float())
             got = self._kernel(flow, info, mask)
             ok = len(want) == 2 and all(tuple(a.shape) == tuple(b.shape) and
                                         float((a.float() - b).abs().max()) <= 1e-5 * max(1.0, float(a.float().abs().max()))
@@ -369,17 +525,18 @@ class _UpsampleDataSeam:
         if kwargs or len(args) != 3 or not all(torch.is_tensor(a) for a in args):
             return self.original(*args, **kwargs)
         flow, info, mask = args
-        eligible = (_fp32_eligible(flow, info, mask) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
+        eligible = (_eligible(self.precision, (flow, info, mask), ()) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
                     and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
                     and info.shape[0] == flow.shape[0] == mask.shape[0]
                     and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
         if not eligible:
             return self.original(flow, info, mask)
-        if self.ok is None:
+        attr = "ok16" if mask.dtype == torch.bfloat16 else "ok"
+        if getattr(self, attr) is None:
             if torch.cuda.is_current_stream_capturing():
                 return self.original(flow, info, mask)
-            self.ok = self._probe(flow.device)
-        if not self.ok:
+            setattr(self, attr, self._probe(flow.device, mask.dtype))
+        if not getattr(self, attr):
             return self.original(flow, info, mask)
         self.calls += 1
         return self._kernel(flow, info, mask)

@@ -14,6 +14,12 @@ the kernels are checked on large grids by their own tests):
     up_flow, up_info = upsample_data(flow_8x, info_8x, weight_update)  sea_raft.py:147-163
 
 Inputs and outputs are stored, weights are not (tests/test_gpu_sea_raft.py regenerates them from the seed).
+
+    python scripts/make_sea_raft_golden.py --autocast
+
+runs the same step under torch.autocast("cpu", dtype=torch.bfloat16) and writes tests/golden/sea_raft_update_autocast.pt: the
+reference's own reduced-precision semantics (bf16 convolutions / Linear layers, fp32 LayerNorm, the dtype promotions of its cats and
+sums), which tests/test_sea_raft_bf16.py pins the torch restatement to.
 """
 from __future__ import annotations
 
@@ -32,9 +38,10 @@ from sea_seam_model import seeded_params  # noqa: E402
 SEED = 2024
 B, H, W = 1, 7, 8
 OUT = os.path.join(ROOT, "tests", "golden", "sea_raft_update.pt")
+OUT_AUTOCAST = os.path.join(ROOT, "tests", "golden", "sea_raft_update_autocast.pt")
 
 
-def main() -> None:
+def main(autocast: bool = False) -> None:
     mod = ref_loader.ref_module("ptlflow.models.sea_raft.sea_raft")
     torch.manual_seed(0)
     model = mod.SEARAFT(block_dims=[64, 128, 256], iters=4).eval()
@@ -46,7 +53,7 @@ def main() -> None:
     inp = torch.relu(torch.randn(B, 128, H, W, generator=g))
     corr = torch.randn(B, 324, H, W, generator=g)
     flow = torch.randn(B, 2, H, W, generator=g) * 2
-    with torch.no_grad():
+    with torch.no_grad(), torch.autocast("cpu", dtype=torch.bfloat16, enabled=autocast):
         net_out = model.update_block(net, inp, corr, flow)
         flow_update = model.flow_head(net_out)
         weight_update = 0.25 * model.upsample_weight(net_out)
@@ -57,9 +64,12 @@ def main() -> None:
             "weight_update": weight_update, "flow_8x": flow_8x, "info_8x": info_8x.contiguous(), "up_flow": up_flow,
             "up_info": up_info}
     data = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in data.items()}
-    torch.save(data, OUT)
-    print(f"wrote {OUT} ({os.path.getsize(OUT) / 1e6:.2f} MB)")
+    out = OUT_AUTOCAST if autocast else OUT
+    if autocast:
+        data["autocast"] = "cpu/bfloat16"
+    torch.save(data, out)
+    print(f"wrote {out} ({os.path.getsize(out) / 1e6:.2f} MB)")
 
 
 if __name__ == "__main__":
-    main()
+    main("--autocast" in sys.argv[1:])

@@ -2,6 +2,8 @@
 
     python scripts/sea_raft_loop_bench.py [--out sea_loop.json]
     rocprofv3 --kernel-trace --stats -d <dir> -o run -- python scripts/sea_raft_loop_bench.py --trace   # kernel times
+    python scripts/sea_raft_loop_bench.py --precision bf16 [--out sea_loop_bf16.json]
+    rocprofv3 --kernel-trace --stats -d <dir> -o run -- python scripts/sea_raft_loop_bench.py --precision bf16 --trace
 
 Times the loop body of sea_raft.py:217-236 without the lookup — update block, flow_head, 0.25 * upsample_weight, the flow update
 and upsample_data — on a 55 x 128 grid (436 x 1024 frames) with a fixed correlation input, at B = 1 and 8 and 4 and 12 iterations.
@@ -9,6 +11,10 @@ Device events, warm-up, stock and accelerated runs alternating in one process; r
 The accelerated runs also time the engine's GEMM launches with events (`UpdateEngine.profile`): pwconv1 / pwconv2 / final as
 shares of the fp32 MFMA peak.  dwconv + LayerNorm's time comes from the separate `--trace` run (kernel `dwconv_ln_kernel`), its
 share of the HBM roof is computed from it by hand (2 x M x 384 x 4 bytes per launch).
+
+`--precision bf16` times three loops, alternating in one process: the stock loop under torch.autocast("cuda", bfloat16),
+`accelerate(model, sea_raft_update="bf16")` run as that same autocast loop, and the fp32 kernel loop (`sea_raft_update=True`);
+`--trace` then runs the bf16 kernel loop only (kernel `dwconv_ln_b16_kernel`: 2 x M x 384 x 2 bytes per launch).
 """
 from __future__ import annotations
 
@@ -64,7 +70,11 @@ def main() -> None:
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace", action="store_true", help="accelerated loop only, B = 1 and 8, 12 iterations (for rocprofv3)")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
+                    help="bf16: stock autocast loop vs the bf16 kernel loop vs the fp32 kernel loop")
     args = ap.parse_args()
+    if args.precision == "bf16":
+        return main_bf16(args)
     import ptlflow_amd
     from ptlflow_amd import patch
     from sea_seam_model import SeaRaftLoop, load_seeded
@@ -107,6 +117,56 @@ def main() -> None:
                         per[key] = {"us": round(ms * 1e3, 2), "mfma_share": round(fl / (ms * 1e-3) / PEAK_FP32_MFMA, 3) if fl else None}
                     eng.profile = None
                     row["launches"] = per
+                res["runs"].append(row)
+                print(json.dumps(row), flush=True)
+    if args.out and not args.trace:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def main_bf16(args) -> None:
+    import ptlflow_amd
+    from ptlflow_amd import patch
+    from sea_seam_model import SeaRaftLoop, load_seeded
+    ptlflow_amd.load_native()
+    dev = torch.device("cuda:0")
+    stock = load_seeded(SeaRaftLoop(), 11).eval().to(dev)
+    k16 = load_seeded(SeaRaftLoop(), 11).eval().to(dev)
+    k32 = load_seeded(SeaRaftLoop(), 11).eval().to(dev)
+    patch.accelerate(k16, sea_raft_update="bf16")
+    patch.accelerate(k32, sea_raft_update=True)
+    res = {"grid": [H8, W8], "precision": "bf16", "runs": []}
+
+    def autocast_loop(model, *a):
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return _loop(model, *a)
+
+    with torch.no_grad():
+        for B in (1, 8):
+            net, ctx, corr, flow = _inputs(B, dev)
+            corr_cl = corr.contiguous(memory_format=torch.channels_last)    # the channel view the B1 hook hands out
+            for iters in (4, 12):
+                run_16 = lambda: autocast_loop(k16, net, ctx, corr_cl, flow, iters)       # noqa: E731
+                if args.trace:
+                    run_16()
+                    torch.cuda.synchronize()
+                    continue
+                run_s = lambda: autocast_loop(stock, net, ctx, corr, flow, iters)        # noqa: E731
+                run_32 = lambda: _loop(k32, net, ctx, corr_cl, flow, iters)             # noqa: E731
+                for f in (run_s, run_16, run_32) * 2:                                   # warm-up (MIOpen find, packing, probes)
+                    f()
+                torch.cuda.synchronize()
+                c0 = k16.update_block.calls
+                ts, t16, t32 = [], [], []
+                for _ in range(args.reps):                                              # alternating
+                    ts += _time(run_s, 1)
+                    t16 += _time(run_16, 1)
+                    t32 += _time(run_32, 1)
+                assert k16.update_block.calls - c0 == args.reps * iters, "the bf16 loop left the kernels"
+                ms_s, ms_16, ms_32 = (statistics.median(t) / iters for t in (ts, t16, t32))
+                row = {"B": B, "iters": iters, "stock_autocast_ms_per_iter": round(ms_s, 4), "pfk_bf16_ms_per_iter": round(ms_16, 4),
+                       "pfk_fp32_ms_per_iter": round(ms_32, 4), "speedup_vs_stock_autocast": round(ms_s / ms_16, 3),
+                       "speedup_vs_pfk_fp32": round(ms_32 / ms_16, 3)}
                 res["runs"].append(row)
                 print(json.dumps(row), flush=True)
     if args.out and not args.trace:
