@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --dump-outputs DIR           # also write the last timed step's outputs as DIR/<name>.npy (float32)
+    python bench.py --full                       # also every leg listed below (a few minutes more)
 
 A *step* is one forward of `ptlflow_amd.RAFT` (both encoders, correlation volume + pyramid + 32 x {lookup, update block,
 coordinate update, convex upsample} — every kernel libpfk's, no MIOpen / rocBLAS call in the forward) over one batch of
@@ -12,7 +13,8 @@ synthetic 436x1024 frame pairs already resident in HBM.  One process per GPU, fr
 nothing (no data-path collective; RCCL is used only for the barrier and the max-over-ranks of the elapsed time): weak
 scaling, `value` = all pairs of all ranks / max time (ptlflow_amd.shard.timed_steps).
 
-Besides the driver's contract fields the JSON line carries
+A plain run sets up, warms up, times the steps, dumps the outputs if asked and prints the driver's contract fields.  With
+`--full` the JSON line also carries the following legs, each run after the timed steps (the `--no-*` switches thin them out):
   roofline      dominant kernel (largest summed time among the MFMA conv launches), HIP events around every
                 launch of it during one separate instrumented forward; bound = fp32 MFMA peak 157.3 TFLOP/s
   cpu_baseline  the CPU oracle (`oracle/raft_oracle.raft_forward`, a port of the reference forward on torch
@@ -81,6 +83,10 @@ def parse():
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=32)
     ap.add_argument("--model", default="raft", choices=["raft", "raft_small", "gma"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs beside it: batch1 / batch16, roofline, CPU baseline and EPE, the "
+                         "split-bf16, dead-work-skip and single-chain forwards, and at the default configuration the reference-protocol, "
+                         "dropin, config 3 / 4 and training legs (off: the line carries the headline fields only)")
     ap.add_argument("--skip-dead-upsample", action="store_true",
                     help="skip mask head + upsampling on non-final iterations (output-identical dead work)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -588,7 +594,7 @@ def main():
     if os.environ.get("PFK_FUSE_MASK") == "1":        # experiment knob: K13 (fused mask conv2 + softmax + upsampling) instead of the pair
         model.fuse_mask_upsample = True
     model.load_synthetic(1234).eval()
-    cpu_state = {k: v.clone() for k, v in model.state_dict().items()}
+    cpu_state = {k: v.clone() for k, v in model.state_dict().items()} if args.full else None     # the --full legs' weights
     model = model.to(dev)
     if os.environ.get("PFK_CHANNELS_LAST") == "1":        # experiment knob: NHWC encoders
         model.fnet = model.fnet.to(memory_format=torch.channels_last)
@@ -644,7 +650,7 @@ def main():
     if shared:
         result["config"]["shared_device"] = "all ranks on cuda:0 over gloo (N > 1 code-path smoke on a one-GPU box, not a scaling number)"
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if args.batch > 1 and not args.no_batch1:
             one = {"images": inputs["images"][:1].contiguous()}
             for _ in range(2):
@@ -919,6 +925,7 @@ def main():
                 result["train"] = train_leg(dev)
             except Exception as e:
                 result["train"] = {"error": repr(e)[:300]}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()

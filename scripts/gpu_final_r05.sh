@@ -6,7 +6,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 [ -n "$SKIP_PYTEST" ] || { timeout 1800 python -m pytest tests -m gpu -q --tb=line 2>&1 | tail -8 > $O/z_pytest.log; cat $O/z_pytest.log | cut -c1-200; }
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/z_bench.log 2>&1; tail -n 1 $O/z_bench.log | cut -c1-400
+timeout 1200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/z_bench.log 2>&1; tail -n 1 $O/z_bench.log | cut -c1-400
 timeout 200 python scripts/corr_bench.py > $O/z_corr.log 2>&1
 timeout 300 python scripts/lookup_blocked_bench.py > $O/z_lookup_blocked.log 2>&1
 timeout 200 python scripts/maskup_bench.py > $O/z_maskup.log 2>&1

@@ -7,7 +7,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 [ -n "$SKIP_PYTEST" ] || { timeout 1800 python -m pytest tests -m gpu -q --tb=line --durations=15 2>&1 | tail -30 > $O/z6_pytest.log; tail -3 $O/z6_pytest.log | cut -c1-200; }
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/z6_bench.log 2>&1; tail -n 1 $O/z6_bench.log | cut -c1-300
+timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/z6_bench.log 2>&1; tail -n 1 $O/z6_bench.log | cut -c1-300
 timeout 200 python scripts/corr_bench.py > $O/z6_corr.log 2>&1
 timeout 300 python scripts/lookup_blocked_bench.py > $O/z6_lookup_blocked.log 2>&1
 timeout 200 python scripts/maskup_bench.py > $O/z6_maskup.log 2>&1

@@ -88,3 +88,13 @@ def test_dump_outputs_writes_float32_arrays_within_budget(bench, tmp_path):
         a, b = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
         assert a.dtype == np.float32 and a.size > 0 and np.array_equal(a, b)
         assert np.isin(a, big[f[:-4]].numpy().reshape(-1)).all()
+
+
+def test_full_is_off_by_default(bench, monkeypatch):
+    """A plain run times the headline only; the legs beside it (roofline, CPU baseline, other precisions, sizes and models) run
+    with `--full`, which every switch that thins them out leaves alone."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extra-legs", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_extra_legs and a.no_cpu_baseline
