@@ -21,6 +21,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import load_native
+from ._seam import WrappedModule, eligible
 from .packing import pack_conv_weight, split_bf16_planes
 from .update import CONV_PRECISIONS, EPI_LINEAR
 
@@ -191,7 +192,7 @@ class EncoderEngine:
         return y.view(B, h, w, self.out_dim).permute(0, 3, 1, 2)
 
 
-class PfkEncoder(torch.nn.Module):
+class PfkEncoder(WrappedModule):
     """Drop-in for ``model.fnet`` / ``model.cnet`` of a live ptlflow model (``BasicEncoder``, raft/extractor.py:122-194):
     same ``forward(x)`` contract (a tensor, or a list of two images that is batched and split again, :172-193), same
     parameters — the reference sub-modules are re-registered under their own names, so state_dict keys, checkpoints and
@@ -199,32 +200,22 @@ class PfkEncoder(torch.nn.Module):
     GroupNorm stay on the reference's own code."""
 
     def __init__(self, ref: torch.nn.Module, conv_precision: str = "fp32", small: bool = False):
-        super().__init__()
+        super().__init__(ref)
         self.small = small
-        for name, child in ref.named_children():
-            self.add_module(name, child)
-        self._ref = [ref]   # in a list: not registered twice in the module tree
-        self.training = ref.training
         self.norm_fn = ref.norm_fn
         self.conv_precision = conv_precision
-        self._engine: Optional[EncoderEngine] = None
-        self._versions = None
 
     def _get_engine(self, device) -> EncoderEngine:
         ref = self._ref[0]
-        v = tuple((t.data_ptr(), t._version) for t in list(ref.parameters()) + list(ref.buffers()))
-        if self._engine is None or self._engine.device != device or v != self._versions:
-            self._engine = EncoderEngine(ref.state_dict(), self.norm_fn, device, self.conv_precision, self.small)
-            self._versions = v
-        return self._engine
+        return self._engine_for(device, [*ref.parameters(), *ref.buffers()],
+                                lambda: EncoderEngine(ref.state_dict(), self.norm_fn, device, self.conv_precision, self.small))
 
     def forward(self, x):
         ref = self._ref[0]
         is_list = isinstance(x, (tuple, list))
         probe = x[0] if is_list else x
-        needs_graph = torch.is_grad_enabled() and (probe.requires_grad or any(p.requires_grad for p in ref.parameters()))
         ref.training = self.training   # .train() / .eval() reach this wrapper and the shared children, not `ref` itself
-        if self.training or needs_graph or not probe.is_cuda or self.norm_fn not in ("instance", "batch", "none"):
+        if self.training or not eligible((probe,), ref.parameters()) or self.norm_fn not in ("instance", "batch", "none"):
             return ref(x)
         if is_list:
             batch_dim = x[0].shape[0]

@@ -36,7 +36,10 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import load_native
+from ._seam import ProbedMethodSeam, WrappedModule, eligible
 from .corr import get_corr_block as _pfk_get_corr_block
+from .encoder import PfkEncoder
+from .sea_update import HEAD_SHAPES, PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam, sea_block_shapes
 from .update import PfkUpdateBlock, UpdateSpec, basic_spec, ccmr_spec, gma_spec, ms_raft_plus_spec, small_spec
 
 _ORIG = "_pfk_original_get_corr_block"
@@ -78,7 +81,6 @@ _PYRAMID = {"ptlflow.models.sea_raft.sea_raft": "bilinear_f2"}
 # `forward(net, inp, corr, flow) -> net`); installed only with `accelerate(model, sea_raft_update=True)` (extendable with
 # `register_sea_raft_update_block`), and only when the state_dict names / shapes are exactly sea_update.sea_block_shapes
 _SEA_UPDATE_BLOCKS = {("ptlflow.models.sea_raft.update", "BasicUpdateBlock")}
-_SEA_UPSAMPLE = "_pfk_original_upsample_data"
 
 
 def register_sea_raft_update_block(module: str, cls: str = "BasicUpdateBlock") -> None:
@@ -89,7 +91,6 @@ def register_sea_raft_update_block(module: str, cls: str = "BasicUpdateBlock") -
 def match_sea_raft(model: torch.nn.Module) -> Optional[Tuple[int, int]]:
     """(corr_channels, num_blocks) when `model.update_block`, `model.flow_head` and `model.upsample_weight` are provably SEA-RAFT's
     (sea_raft/update.py:39-54, sea_raft.py:114-126 at dim = 128), else None."""
-    from .sea_update import HEAD_SHAPES, sea_block_shapes
     block = getattr(model, "update_block", None)
     if block is None or (type(block).__module__, type(block).__name__) not in _SEA_UPDATE_BLOCKS:
         return None
@@ -123,7 +124,6 @@ def _sea_precision(sea_raft_update) -> Optional[str]:
 def _install_sea_raft(model: torch.nn.Module, precision: str = "fp32") -> bool:
     """SEA-RAFT's update block, heads and `upsample_data` (sea_update.py); True when installed (or already there).  Installed seams
     of another precision are switched to this one (the block's engine is rebuilt on its next call)."""
-    from .sea_update import PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam
     if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):
         model.update_block.set_precision(precision)
         seam = model.__dict__.get("upsample_data")
@@ -138,24 +138,23 @@ def _install_sea_raft(model: torch.nn.Module, precision: str = "fp32") -> bool:
     model.update_block = block
     model.flow_head = _SeaHeadSeam(model.flow_head, block, "flow_head")
     model.upsample_weight = _SeaHeadSeam(model.upsample_weight, block, "upsample_weight")
-    if callable(getattr(model, "upsample_data", None)) and _SEA_UPSAMPLE not in model.__dict__:
-        model.__dict__[_SEA_UPSAMPLE] = model.upsample_data
-        model.__dict__["upsample_data"] = _UpsampleDataSeam(model.upsample_data, precision)
+    if callable(getattr(model, "upsample_data", None)) and not isinstance(model.__dict__.get("upsample_data"), _UpsampleDataSeam):
+        _shadow(model, upsample_data=_UpsampleDataSeam(model.upsample_data, precision))
     return True
 
 
-def _restore_sea_raft(model: torch.nn.Module) -> None:
-    from .sea_update import PfkSeaRaftUpdateBlock, _SeaHeadSeam
-    if _SEA_UPSAMPLE in model.__dict__:
-        del model.__dict__[_SEA_UPSAMPLE]
-        model.__dict__.pop("upsample_data", None)
-    for attr in ("flow_head", "upsample_weight"):
-        head = getattr(model, attr, None)
-        if isinstance(head, _SeaHeadSeam):
-            setattr(model, attr, head._ref[0])
-    ub = getattr(model, "update_block", None)
-    if isinstance(ub, PfkSeaRaftUpdateBlock):
-        model.update_block = ub._ref[0]
+def _shadow(obj, **seams) -> None:
+    """Shadow methods of the instance `obj`: an instance attribute wins over the class's method (nn.Module's `__call__` looks
+    `forward` up on the instance too).  Each seam keeps the method it replaces."""
+    obj.__dict__.update(seams)
+
+
+def _unshadow(obj, kind: type, name: str, *also: str) -> None:
+    """Undo `_shadow` where `obj.name` is a `kind` seam: drop it and the names shadowed together with it."""
+    d = getattr(obj, "__dict__", {})
+    if isinstance(d.get(name), kind):
+        for n in (name, *also):
+            d.pop(n, None)
 
 
 def _with_corr_channels(spec: UpdateSpec, corr_channels: int) -> UpdateSpec:
@@ -313,22 +312,17 @@ def _make_corr_hook(module_name: str, original):
     return get_corr_block
 
 
-_UPSAMPLE = "_pfk_original_upsample_flow"
-
-
-class _UpsampleSeam:
+class _UpsampleSeam(ProbedMethodSeam):
     """Seam B5 — `model.upsample_flow(flow, mask)` (raft.py:112-123; the same method in gma.py:130-141, ccmr.py:128-139):
     8x convex upsampling, called once per iteration by the reference's loop, in the reference five torch kernels over a
-    [B, 576, h, w] mask (softmax, unfold, multiply, sum, permute-copy).  The replacement is `pfk_convex_upsample_f32`.
+    [B, 576, h, w] mask (softmax, unfold, multiply, sum, permute-copy).  The replacement is `pfk_convex_upsample_f32`, behind
+    the behaviour probe of `ProbedMethodSeam` (a family whose `upsample_flow` does something else — another scale, a different
+    neighbourhood — keeps its own code).  Gradient graphs, CPU tensors, other mask widths and dtypes always take the original."""
 
-    Dispatch by BEHAVIOUR, not by name: on the first GPU call the model's own method and the kernel are run on a small random
-    input; the kernel is used from then on only if they agree to 1e-5 (so a family whose `upsample_flow` does something else —
-    another scale, a different neighbourhood — keeps its own code).  Gradient graphs, CPU tensors, other mask widths and
-    dtypes always take the original."""
+    refusal = "ptlflow_amd: this model's upsample_flow is not RAFT's 8x convex upsampling; seam B5 keeps the model's own method"
 
     def __init__(self, original):
-        self.original = original
-        self.ok = None          # None: not probed yet; True / False: the probe's verdict
+        super().__init__(original)
         self.skip = None        # `_DeadWorkSkip` shared with seam B3 (accelerate(..., skip_dead_upsample=True)), else None
 
     @staticmethod
@@ -340,23 +334,11 @@ class _UpsampleSeam:
         torch.ops.pfk.convex_upsample(flow.contiguous(), pm, out)
         return out
 
-    def _probe(self, device) -> bool:
+    def _probe_args(self, device):
         g = torch.Generator().manual_seed(5)
         flow = (torch.randn(2, 2, 5, 7, generator=g) * 3).to(device)
         mask = torch.randn(2, 576, 5, 7, generator=g).to(device)
-        try:
-            with torch.no_grad():
-                want = self.original(flow, mask)
-            got = self._kernel(flow, mask)
-            ok = tuple(want.shape) == tuple(got.shape) and \
-                float((want.float() - got).abs().max()) <= 1e-5 * max(1.0, float(want.float().abs().max()))
-        except Exception:
-            ok = False
-        if not ok:
-            import warnings
-            warnings.warn("ptlflow_amd: this model's upsample_flow is not RAFT's 8x convex upsampling; seam B5 keeps the "
-                          "model's own method", RuntimeWarning, stacklevel=3)
-        return ok
+        return (flow, mask), (flow, mask)
 
     def __call__(self, *args, **kwargs):
         # Other families give `upsample_flow` more arguments — ccmr.py:213 / ms_raft_plus.py:199 pass `scale=`, dip a `rate`,
@@ -365,17 +347,10 @@ class _UpsampleSeam:
         if kwargs or len(args) != 2 or not (torch.is_tensor(args[0]) and torch.is_tensor(args[1])):
             return self.original(*args, **kwargs)
         flow, mask = args
-        eligible = (flow.is_cuda and flow.dtype == torch.float32 and mask.dtype == torch.float32 and mask.dim() == 4 and
-                    mask.shape[1] == 576 and flow.dim() == 4 and flow.shape[1] == 2 and
-                    not (torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad)))
-        if not eligible:
+        if not (eligible(args, dtypes=(torch.float32,)) and mask.dim() == 4 and mask.shape[1] == 576 and flow.dim() == 4
+                and flow.shape[1] == 2 and self._verdict("ok", flow.device)):
             return self.original(flow, mask)
-        if self.ok is None:
-            if torch.cuda.is_current_stream_capturing():     # the probe copies host data: illegal inside a graph capture
-                return self.original(flow, mask)
-            self.ok = self._probe(flow.device)
-        if not self.ok:
-            return self.original(flow, mask)
+        self.calls += 1
         if self.skip is not None:
             if self.skip.upsample_is_dead():
                 return self.skip.scratch(flow)      # a non-final iteration's prediction: eval drops it (raft/raft.py:186-192)
@@ -612,24 +587,18 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
         _bracket_forward_with_layout(model, hook.channels_last)
     cb = getattr(model, "corr_block", None)
     if corr and isinstance(cb, torch.nn.Module) and (type(cb).__module__, type(cb).__name__) in _BILINEAR_VOLUMES \
-            and _VOLUME_SEAM not in cb.__dict__:
+            and not isinstance(cb.__dict__.get(_VOLUME_SEAM), _LearnableVolumeSeam):
         seam = _LearnableVolumeSeam(cb)
         seam.channels_last = isinstance(getattr(model, "update_block", None), PfkUpdateBlock)
-        # instance attributes shadow the class's methods (nn.Module.__call__ looks `forward` up on the instance)
-        cb.__dict__[_VOLUME_SEAM] = seam
-        cb.__dict__["compute_cost_volume"] = seam.compute_cost_volume
-        cb.__dict__["forward"] = seam.forward
+        _shadow(cb, **{_VOLUME_SEAM: seam, "compute_cost_volume": seam.compute_cost_volume, "forward": seam.forward})
     if encoders:
         # seam B4: the BasicEncoder feature / context networks (raft, gma: `self.fnet`, `self.cnet`)
-        from .encoder import PfkEncoder
         for attr in ("fnet", "cnet"):
             enc = getattr(model, attr, None)
             if enc is not None and not isinstance(enc, PfkEncoder) and match_encoder(enc):
                 setattr(model, attr, PfkEncoder(enc, conv_precision, small=type(enc).__name__ == "SmallEncoder"))
-    if upsample and callable(getattr(model, "upsample_flow", None)) and _UPSAMPLE not in model.__dict__:
-        # an instance attribute shadows the class's method; nn.Module.__setattr__ stores plain callables in __dict__
-        model.__dict__[_UPSAMPLE] = model.upsample_flow
-        model.__dict__["upsample_flow"] = _UpsampleSeam(model.upsample_flow)
+    if upsample and callable(getattr(model, "upsample_flow", None)) and not isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam):
+        _shadow(model, upsample_flow=_UpsampleSeam(model.upsample_flow))
     both = isinstance(getattr(model, "update_block", None), PfkUpdateBlock) and isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam)
     if _SKIP not in model.__dict__ and (skip_dead_upsample is True or both) \
             and not (skip_dead_upsample is False and fuse_mask_upsample is False):
@@ -643,7 +612,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
 
 
 def restore(model: torch.nn.Module) -> torch.nn.Module:
-    _restore_sea_raft(model)
+    _unshadow(model, _UpsampleDataSeam, "upsample_data")
     state = model.__dict__.pop(_LAYOUT_HOOKS, None)
     if state is not None:
         for h in state["handles"]:
@@ -652,23 +621,13 @@ def restore(model: torch.nn.Module) -> torch.nn.Module:
         del model.__dict__[_SKIP]
         if isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
             model.update_block._skip = None
-    if _UPSAMPLE in model.__dict__:
-        del model.__dict__[_UPSAMPLE]
-        model.__dict__.pop("upsample_flow", None)
+    _unshadow(model, _UpsampleSeam, "upsample_flow")
     mod = sys.modules.get(type(model).__module__)
     if mod is not None and hasattr(mod, _ORIG):
         mod.get_corr_block = getattr(mod, _ORIG)
         delattr(mod, _ORIG)
-    cb = getattr(model, "corr_block", None)
-    if cb is not None and _VOLUME_SEAM in getattr(cb, "__dict__", {}):
-        for name in (_VOLUME_SEAM, "compute_cost_volume", "forward"):
-            cb.__dict__.pop(name, None)
-    ub = getattr(model, "update_block", None)
-    if isinstance(ub, PfkUpdateBlock):
-        model.update_block = ub._ref[0]
-    from .encoder import PfkEncoder
-    for attr in ("fnet", "cnet"):
-        enc = getattr(model, attr, None)
-        if isinstance(enc, PfkEncoder):
-            setattr(model, attr, enc._ref[0])
+    _unshadow(getattr(model, "corr_block", None), _LearnableVolumeSeam, _VOLUME_SEAM, "compute_cost_volume", "forward")
+    for name, child in list(model._modules.items()):      # update_block, fnet / cnet, SEA-RAFT's heads
+        if isinstance(child, WrappedModule):
+            setattr(model, name, child._ref[0])
     return model

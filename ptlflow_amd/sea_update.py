@@ -41,8 +41,9 @@ from typing import Dict, Optional
 
 import torch
 
+from ._seam import ProbedMethodSeam, WrappedModule, eligible, pixel_rows
 from .packing import pack_conv_weight
-from .update import EPI_LINEAR, UpdateEngine, UpdateSpec
+from .update import EPI_LINEAR, UpdateEngine, UpdateSpec, corr_rows
 
 SEA_PRECISIONS = ("fp32", "bf16")
 
@@ -190,6 +191,31 @@ class SeaUpdateEngine(UpdateEngine):
             self.motion(corr_pm)
         self.refine()
 
+    def stage(self, net: Optional[torch.Tensor], inp: Optional[torch.Tensor], flow: torch.Tensor, corr: torch.Tensor) -> torch.Tensor:
+        """The block's NCHW inputs into the state: `net` and `inp` (None: staged already) into their slices of hx, or of hxb on the
+        bf16 path, `flow` into hx's flow slice (mirrored into hxb).  `corr`: the lookup's fp32 rows on the fp32 path, read as
+        they are; NCHW on the bf16 path, copied into corr16.  Returns the rows `update` reads."""
+        s = self.spec
+        if self.b16:
+            def put(src, dst):         # any float NCHW -> the [M, C] rows `dst`, converting the dtype
+                self.nchw_view(dst).copy_(src.permute(0, 2, 3, 1))
+        else:
+            def put(src, dst):
+                self.ops.nchw_to_pm(src.contiguous(), dst)
+        if net is not None:
+            put(net, self.act[:, : s.hidden])
+        if inp is not None:
+            put(inp, self.act[:, s.hidden: s.hidden + s.context])
+        if flow.dtype == torch.float32:
+            self.ops.nchw_to_pm(flow.contiguous(), self.flow_view)
+        else:
+            put(flow, self.flow_view)
+        self.flow_changed()            # bf16: the fp32 flow (convf1's input) mirrored into hxb (the ConvNeXt blocks' input)
+        if not self.b16:
+            return corr
+        put(corr, self.corr16[:, : s.corr_channels])
+        return self.corr16
+
     def flow_head_out(self) -> None:
         """flow_head[2] (3x3, 256 -> 6) on the flow-head half of fm -> fo[:, :6]: delta flow (2) | info (4)"""
         self._conv([self.fm[:, : self.spec.fh_hidden]], 3, 3, "fo", 6, relu=False, out=self.fo[:, :6])
@@ -221,64 +247,24 @@ class SeaUpdateEngine(UpdateEngine):
         return self.mask.view(B, H, W, self.spec.mask_channels).permute(0, 3, 1, 2)
 
 
-def _fp32_eligible(*tensors) -> bool:
-    """GPU fp32 tensors, no gradient graph, no autocast region: what the kernels implement"""
-    t0 = tensors[0]
-    if not t0.is_cuda or torch.is_autocast_enabled("cuda"):
-        return False
-    for t in tensors:
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != t0.device:
-            return False
-    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+# precision -> (activation dtypes, cuda autocast) the seams serve: the kernels' inputs (`_seam.eligible`)
+SEA_ACCEPTS = {"fp32": ((torch.float32,), False), "bf16": ((torch.float32, torch.bfloat16), torch.bfloat16)}
 
 
-def _b16_eligible(*tensors) -> bool:
-    """The bf16 path's calls: GPU tensors of fp32 or bf16, no gradient graph, autocast off or cuda autocast to bfloat16"""
-    t0 = tensors[0]
-    if not t0.is_cuda:
-        return False
-    if torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") != torch.bfloat16:
-        return False
-    for t in tensors:
-        if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.bfloat16) or t.device != t0.device:
-            return False
-    return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
-
-
-def _eligible(precision: str, tensors, params) -> bool:
-    """what the engine of `precision` implements: the activations as above, the parameters fp32 on the same device"""
-    if precision == "fp32":
-        return _fp32_eligible(*tensors, *params)
-    return _b16_eligible(*tensors) and all(p.dtype == torch.float32 and p.device == tensors[0].device for p in params) and \
-        not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
-
-
-def _copy_nchw_rows(src: torch.Tensor, dst: torch.Tensor) -> None:
-    """NCHW [B, C, H, W] of any float dtype -> the [B*H*W, C] rows `dst` (a view), converting the dtype"""
-    B, C, H, W = src.shape
-    dst.unflatten(0, (B, H, W)).copy_(src.permute(0, 2, 3, 1))
-
-
-class PfkSeaRaftUpdateBlock(torch.nn.Module):
+class PfkSeaRaftUpdateBlock(WrappedModule):
     """Drop-in for SEA-RAFT's ``model.update_block``: ``forward(net, inp, corr, flow) -> net`` NCHW (sea_raft/update.py:49-54), a
     view of the engine's h slice with channels-last strides, overwritten by the next call (the reference loop rebinds `net` every
     iteration, sea_raft.py:223).  Keeps the wrapped sub-modules (`encoder`, `refine`): state_dict keys, checkpoints and optimizers
     are unchanged.  The heads' parameters are read through `_heads` (not registered here: they stay the model's own children)."""
 
     def __init__(self, ref_block: torch.nn.Module, num_blocks: int, corr_channels: int, precision: str = "fp32"):
-        super().__init__()
+        super().__init__(ref_block)
         if precision not in SEA_PRECISIONS:
             raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
         self.precision = precision
-        for name, child in ref_block.named_children():
-            self.add_module(name, child)
-        self._ref = [ref_block]
-        self.training = ref_block.training
         self.spec = sea_spec(corr_channels)
         self.num_blocks = num_blocks
         self._heads: Dict[str, torch.nn.Module] = {}   # "flow_head" / "upsample_weight" -> the model's modules (set by patch)
-        self._engine: Optional[SeaUpdateEngine] = None
-        self._versions = None
         self._inp_ref, self._inp_version = None, -1
         self._last_out, self._last_version = None, -1
         self._fm_for = None        # the `net` object whose flow_head[0] | upsample_weight[0] activation `fm` holds
@@ -292,30 +278,20 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
         return P
 
     def _get_engine(self, device) -> SeaUpdateEngine:
+        if self._engine is not None and self._engine.precision != self.precision:
+            self._engine = None
         P = self._all_params()
-        v = tuple((p.data_ptr(), p._version) for p in P.values())
-        if self._engine is None or self._engine.device != device or self._engine.precision != self.precision:
-            self._engine = SeaUpdateEngine(P, self.spec, device, self.num_blocks, self.precision)
-            self._versions = v
-        elif v != self._versions:
-            self._engine.pack(P)
-            self._versions = v
-        return self._engine
+        return self._engine_for(device, P.values(), lambda: SeaUpdateEngine(P, self.spec, device, self.num_blocks, self.precision),
+                                lambda eng: eng.pack(P))
 
     def owns(self, x: torch.Tensor) -> bool:
         """`x` is the net this block handed out last, untouched since"""
         return x is self._last_out and x._version == self._last_version
 
-    @staticmethod
-    def _corr_pm(corr: torch.Tensor, M: int) -> Optional[torch.Tensor]:
-        """the [M, C] rows behind a channel view of the lookup (what ptlflow_amd.CorrBlock hands out), or None"""
-        padded = getattr(corr, "_pfk_padded_pm", None)
-        if padded is not None and padded.shape[0] == M and padded.dtype == torch.float32:
-            return padded
-        cpm = corr.permute(0, 2, 3, 1)
-        if corr.dtype == torch.float32 and cpm.is_contiguous() and corr.shape[1] % 4 == 0 and corr.data_ptr() % 16 == 0:
-            return cpm.reshape(M, corr.shape[1])
-        return None
+    def accepts(self, tensors, params) -> bool:
+        """the engine of this precision implements a call on `tensors` (SEA_ACCEPTS), with `params` fp32 on the same device"""
+        return eligible(tensors, params, *SEA_ACCEPTS[self.precision]) and \
+            all(p.dtype == torch.float32 and p.device == tensors[0].device for p in params)
 
     def set_precision(self, precision: str) -> None:
         """switch the kernel path (a second `accelerate` with another `sea_raft_update`): the engine is rebuilt on the next call"""
@@ -331,76 +307,40 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
         return list(self.parameters()) + [p for m in self._heads.values() for p in m.parameters()]
 
     def forward(self, net, inp, corr, flow):
-        if self.precision == "bf16":
-            return self._forward_b16(net, inp, corr, flow)
-        params = self._params()
-        ok = (torch.is_tensor(corr) and _fp32_eligible(net, inp, corr, flow, *params) and net.dim() == 4
-              and corr.shape[1] == self.spec.corr_channels and net.shape[1] == self.spec.hidden and inp.shape[1] == self.spec.context)
-        B, _, H, W = net.shape if net.dim() == 4 else (0, 0, 0, 0)
-        corr_pm = self._corr_pm(corr, B * H * W) if ok else None
-        if corr_pm is None:
+        s = self.spec
+        ok = (torch.is_tensor(corr) and net.dim() == 4 and corr.dim() == 4 and self.accepts((net, inp, corr, flow), self._params())
+              and corr.shape[1] == s.corr_channels and net.shape[1] == s.hidden and inp.shape[1] == s.context)
+        if self.precision == "fp32":
+            # the fp32 engine reads the lookup's own rows (what ptlflow_amd.CorrBlock hands out); anything else is the module's
+            corr_pm = corr_rows(corr) if ok else None
+            ok = corr_pm is not None
+        else:
+            # the bf16 engine copies the lookup into its bf16 rows: any NCHW layout of the block's shapes
+            corr_pm = corr
+            ok = ok and flow.dim() == 4 and flow.shape[1] == 2 and \
+                all(t.shape[0] == net.shape[0] and t.shape[2:] == net.shape[2:] for t in (inp, corr, flow))
+        if not ok:
             # the wrapped module, on the NCHW tensor the family's own correlation block would have handed it (the B1 hook's
             # channel view holds the same values; a dense copy keeps the module's convolutions on their usual layout)
             self._last_out, self._fm_for = None, None
             return self._ref[0](net, inp, corr.contiguous() if torch.is_tensor(corr) else corr, flow)
-        with torch.no_grad():
-            eng = self._get_engine(net.device)
-            eng.bind(B, H, W)
-            ops = eng.ops
-            new_forward = not self.owns(net)
-            if new_forward:
-                eng.watch_faults()
-                ops.nchw_to_pm(net.contiguous(), eng.h_view)
-            if new_forward or inp is not self._inp_ref or inp._version != self._inp_version:
-                ops.nchw_to_pm(inp.contiguous(), eng.inp_view)
-                self._inp_ref, self._inp_version = inp, inp._version
-            ops.nchw_to_pm(flow.contiguous(), eng.flow_view)
-            eng.update(corr_pm)
-            out = eng.net_nchw()
-        self.calls += 1
-        self._last_out, self._last_version, self._fm_for = out, out._version, None
-        return out
-
-    def _forward_b16(self, net, inp, corr, flow):
-        """the bf16 path: the state in hxb, the lookup rows copied into corr16 (as PfkUpdateBlock does for RAFT's K8b engine)"""
-        ok = (torch.is_tensor(corr) and net.dim() == 4 and corr.dim() == 4 and _eligible("bf16", (net, inp, corr, flow), self._params())
-              and corr.shape[1] == self.spec.corr_channels and net.shape[1] == self.spec.hidden and inp.shape[1] == self.spec.context
-              and flow.dim() == 4 and flow.shape[1] == 2 and inp.shape[0] == net.shape[0] and inp.shape[2:] == net.shape[2:]
-              and corr.shape[0] == net.shape[0] and corr.shape[2:] == net.shape[2:] and flow.shape[0] == net.shape[0]
-              and flow.shape[2:] == net.shape[2:])
-        if not ok:
-            self._last_out, self._fm_for = None, None
-            return self._ref[0](net, inp, corr.contiguous() if torch.is_tensor(corr) else corr, flow)
         B, _, H, W = net.shape
-        M = B * H * W
-        s = self.spec
         with torch.no_grad():
             eng = self._get_engine(net.device)
             eng.bind(B, H, W)
             new_forward = not self.owns(net)
             if new_forward:
                 eng.watch_faults()
-                _copy_nchw_rows(net, eng.hxb[:, : s.hidden])
-            if new_forward or inp is not self._inp_ref or inp._version != self._inp_version:
-                _copy_nchw_rows(inp, eng.hxb[:, s.hidden: s.hidden + s.context])
+            new_inp = new_forward or inp is not self._inp_ref or inp._version != self._inp_version
+            if new_inp:
                 self._inp_ref, self._inp_version = inp, inp._version
-            if flow.dtype == torch.float32:
-                eng.ops.nchw_to_pm(flow.contiguous(), eng.flow_view)
-            else:
-                _copy_nchw_rows(flow, eng.flow_view)
-            eng.flow_changed()           # the fp32 flow (convf1's input) mirrored into hxb (the ConvNeXt blocks' input)
-            C = s.corr_channels
-            corr_pm = self._corr_pm(corr, M)
-            if corr_pm is not None:
-                eng.corr16[:, :C].copy_(corr_pm[:, :C])
-            else:
-                _copy_nchw_rows(corr, eng.corr16[:, :C])
-            eng.update(eng.corr16)
+            eng.update(eng.stage(net if new_forward else None, inp if new_inp else None, flow, corr_pm))
             out = eng.net_nchw()
-            # bf16 out where the model's own block would return bf16: a bf16 net, or any net inside cuda bf16 autocast
-            self._out_b16 = net.dtype == torch.bfloat16 or torch.is_autocast_enabled("cuda")
-            if not self._out_b16:
-                out = out.float()
+            if eng.b16:
+                # bf16 out where the model's own block would return bf16: a bf16 net, or any net inside cuda bf16 autocast
+                self._out_b16 = net.dtype == torch.bfloat16 or torch.is_autocast_enabled("cuda")
+                if not self._out_b16:
+                    out = out.float()
         self.calls += 1
         self._last_out, self._last_version, self._fm_for = out, out._version, None
         return out
@@ -415,19 +355,15 @@ class PfkSeaRaftUpdateBlock(torch.nn.Module):
         return eng
 
 
-class _SeaHeadSeam(torch.nn.Module):
+class _SeaHeadSeam(WrappedModule):
     """Wraps ``model.flow_head`` / ``model.upsample_weight`` (sea_raft.py:114-126), keeping their children 0 / 1 / 2.  Called with the
     net view the update block just handed out, it runs from the engine's pixel-major state; any other input (the `init_conv` split
     before the loop, sea_raft.py:191-197, CPU, half, autocast, gradient graphs) goes to the original module."""
 
     def __init__(self, ref: torch.nn.Module, block: PfkSeaRaftUpdateBlock, kind: str):
-        super().__init__()
-        for name, child in ref.named_children():
-            self.add_module(name, child)
-        self._ref = [ref]
+        super().__init__(ref)
         self._block = [block]
         self.kind = kind
-        self.training = ref.training
         self.calls = 0
 
     def __getitem__(self, i):          # model.flow_head[0] etc. keep working (nn.Sequential indexing)
@@ -438,7 +374,7 @@ class _SeaHeadSeam(torch.nn.Module):
 
     def forward(self, x):
         blk = self._block[0]
-        if not (torch.is_tensor(x) and blk.owns(x) and _eligible(blk.precision, (x,), list(self.parameters()))):
+        if not (torch.is_tensor(x) and blk.owns(x) and blk.accepts((x,), list(self.parameters()))):
             return self._ref[0](x)
         eng = blk.heads_fm(x)
         with torch.no_grad():
@@ -447,96 +383,65 @@ class _SeaHeadSeam(torch.nn.Module):
                 out = eng.fo_nchw()            # fp32 on both paths
             else:
                 eng.mask_logits(1.0)
-                if eng.b16:                    # bf16 logits: a view for an autocast loop, an fp32 copy for an fp32 one
-                    out = eng.mask_nchw_raw() if blk._out_b16 else eng.mask_nchw()
-                else:
-                    out = eng.mask_nchw()
+                # bf16 logits: a view for an autocast loop, an fp32 copy for an fp32 one
+                out = eng.mask_nchw_raw() if eng.b16 and blk._out_b16 else eng.mask_nchw()
         self.calls += 1
         return out
 
 
-class _UpsampleDataSeam:
-    """`model.upsample_data(flow, info, mask)` (sea_raft.py:147-163) shadowed on the instance by `pfk_convex_upsample_info_pm_f32`,
-    behind a behaviour probe like seam B5's: on the first eligible call the model's own method and the kernel run on a small random
-    input and the kernel is used only if they agree to 1e-5.  Pixel-major rows are read without a copy where the strides allow
-    (the channels-last `0.25 * upsample_weight(net)` and the info slice of `flow_head(net)`)."""
+def _rows(t: torch.Tensor, dtype: torch.dtype, align: int = 1) -> torch.Tensor:
+    """`pixel_rows` of `t`, else one contiguous copy of them"""
+    r = pixel_rows(t, dtype, align)
+    return r if r is not None else t.permute(0, 2, 3, 1).clone(memory_format=torch.contiguous_format).view(-1, t.shape[1])
+
+
+class _UpsampleDataSeam(ProbedMethodSeam):
+    """`model.upsample_data(flow, info, mask)` (sea_raft.py:147-163) shadowed on the instance by `pfk_convex_upsample_info_pm_f32`
+    behind the behaviour probe (`ProbedMethodSeam`, like seam B5's; a bf16 mask has a probe of its own, `ok16`).  Pixel-major rows
+    are read without a copy where the strides allow (the channels-last `0.25 * upsample_weight(net)` and the info slice of
+    `flow_head(net)`)."""
+
+    refusal = "ptlflow_amd: this model's upsample_data is not SEA-RAFT's; it keeps the model's own method"
 
     def __init__(self, original, precision: str = "fp32"):
-        self.original = original
+        super().__init__(original)
         self.precision = precision     # "bf16": also bf16 tensors and cuda bf16 autocast; bf16 masks on their own kernel
-        self.ok = None
         self.ok16 = None               # the probe of the bf16-mask kernel
-        self.calls = 0
 
     @staticmethod
-    def _rows(t: torch.Tensor, aligned: bool = False) -> torch.Tensor:
-        """[B, C, H, W] -> its [B*H*W, C] pixel-major rows: a view where the strides allow, else one copy.  `aligned`: 16-byte rows"""
-        B, C, H, W = t.shape
-        r = t.permute(0, 2, 3, 1).reshape(B * H * W, C)
-        if r.stride(1) != 1 or (aligned and (r.data_ptr() % 16 or r.stride(0) % 4)):
-            r = r.clone(memory_format=torch.contiguous_format)
-        return r
-
-    @staticmethod
-    def _rows_b16(t: torch.Tensor) -> torch.Tensor:
-        """bf16 [B, C, H, W] -> [B*H*W, C] rows with 16-byte rows (a view where the strides allow, else one copy)"""
-        B, C, H, W = t.shape
-        r = t.permute(0, 2, 3, 1).reshape(B * H * W, C)
-        if r.stride(1) != 1 or r.data_ptr() % 16 or r.stride(0) % 8:
-            r = r.clone(memory_format=torch.contiguous_format)
-        return r
-
-    @classmethod
-    def _kernel(cls, flow, info, mask):
+    def _kernel(flow, info, mask):
         B, _, H, W = flow.shape
         n = info.shape[1]
         flow_up = torch.empty(B, 2, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
         info_up = torch.empty(B, n, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
         flow, info = flow.float(), info.float()        # (bf16 flow / info of an autocast loop: fp32 rows, exact)
+        f32 = torch.float32
         if mask.dtype == torch.bfloat16:
-            torch.ops.pfk.convex_upsample_info_pm_b16(cls._rows(flow), cls._rows(info), cls._rows_b16(mask), flow_up, info_up)
+            torch.ops.pfk.convex_upsample_info_pm_b16(_rows(flow, f32), _rows(info, f32), _rows(mask, torch.bfloat16, 8), flow_up, info_up)
         else:
-            torch.ops.pfk.convex_upsample_info_pm(cls._rows(flow), cls._rows(info), cls._rows(mask, aligned=True), flow_up, info_up)
+            torch.ops.pfk.convex_upsample_info_pm(_rows(flow, f32), _rows(info, f32), _rows(mask, f32, 4), flow_up, info_up)
         return flow_up, info_up
 
-    def _probe(self, device, mask_dtype=torch.float32) -> bool:
-        """the kernel against the model's own method on a small random input; a bf16 mask is given to the method as its exact
-        fp32 value (the kernel's softmax runs in fp32)"""
+    def _probe_args(self, device, mask_dtype):
+        """a small random input; a bf16 mask is given to the method as its exact fp32 value (the kernel's softmax runs in fp32)"""
         g = torch.Generator().manual_seed(7)
         flow = (torch.randn(2, 2, 5, 7, generator=g) * 3).to(device)
         info = torch.randn(2, 4, 5, 7, generator=g).to(device)
         mask = torch.randn(2, 576, 5, 7, generator=g).to(device=device, dtype=mask_dtype)
-        try:
-            with torch.no_grad(), torch.autocast("cuda", enabled=False):
-                want = self.original(flow, info, mask.float())
-            got = self._kernel(flow, info, mask)
-            ok = len(want) == 2 and all(tuple(a.shape) == tuple(b.shape) and
-                                        float((a.float() - b).abs().max()) <= 1e-5 * max(1.0, float(a.float().abs().max()))
-                                        for a, b in zip(want, got))
-        except Exception:
-            ok = False
-        if not ok:
-            import warnings
-            warnings.warn("ptlflow_amd: this model's upsample_data is not SEA-RAFT's; it keeps the model's own method",
-                          RuntimeWarning, stacklevel=3)
-        return ok
+        return (flow, info, mask.float()), (flow, info, mask)
+
+    def _probe_context(self):
+        return torch.autocast("cuda", enabled=False)
 
     def __call__(self, *args, **kwargs):
         if kwargs or len(args) != 3 or not all(torch.is_tensor(a) for a in args):
             return self.original(*args, **kwargs)
         flow, info, mask = args
-        eligible = (_eligible(self.precision, (flow, info, mask), ()) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
-                    and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
-                    and info.shape[0] == flow.shape[0] == mask.shape[0]
-                    and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
-        if not eligible:
-            return self.original(flow, info, mask)
-        attr = "ok16" if mask.dtype == torch.bfloat16 else "ok"
-        if getattr(self, attr) is None:
-            if torch.cuda.is_current_stream_capturing():
-                return self.original(flow, info, mask)
-            setattr(self, attr, self._probe(flow.device, mask.dtype))
-        if not getattr(self, attr):
+        ok = (eligible(args, (), *SEA_ACCEPTS[self.precision]) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
+              and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
+              and info.shape[0] == flow.shape[0] == mask.shape[0]
+              and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
+        if not (ok and self._verdict("ok16" if mask.dtype == torch.bfloat16 else "ok", flow.device, mask.dtype)):
             return self.original(flow, info, mask)
         self.calls += 1
         return self._kernel(flow, info, mask)

@@ -33,6 +33,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import load_native
+from ._seam import WrappedModule, pixel_rows
 from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino_weight, permute_mask_head, round_up,
                       split_bf16_planes)
 
@@ -738,7 +739,17 @@ class UpdateEngine:
         return self.mask.float().view(B, H, W, self.spec.mask_channels).permute(0, 3, 1, 2)
 
 
-class PfkUpdateBlock(torch.nn.Module):
+def corr_rows(corr: torch.Tensor) -> Optional[torch.Tensor]:
+    """The pixel-major rows behind a lookup result, or None: the zero-padded [M, round_up(C, 4)] buffer behind the channel view
+    ptlflow_amd.CorrBlock hands out, else the [M, C] rows of a dense, aligned fp32 channels-last tensor."""
+    B, _, H, W = corr.shape
+    padded = getattr(corr, "_pfk_padded_pm", None)
+    if padded is not None and padded.shape[0] == B * H * W:
+        return padded
+    return pixel_rows(corr, torch.float32, align=4, dense=True)
+
+
+class PfkUpdateBlock(WrappedModule):
     """Drop-in for ``model.update_block`` (seam B3): same ``forward(net, inp, corr, flow)`` ->
     ``(net, mask, delta_flow)`` contract as raft/update.py:144-153 / :122-128, same parameters.
 
@@ -746,35 +757,20 @@ class PfkUpdateBlock(torch.nn.Module):
     overwritten by the next call, which is how the reference loop uses them (raft.py:169-187)."""
 
     def __init__(self, ref_block: torch.nn.Module, spec: UpdateSpec, conv_precision: str = "fp32"):
-        super().__init__()
+        super().__init__(ref_block)
         self.conv_precision = conv_precision
-        # keep the reference sub-modules so state_dict keys/checkpoints/optimizers are unchanged
-        for name, child in ref_block.named_children():
-            self.add_module(name, child)
-        self._ref = [ref_block]  # in a list: not registered twice in the module tree
-        self.training = ref_block.training
         self.native_backward = True   # False: calls that need a gradient graph go to the wrapped reference module
         self._train_cache: dict = {}  # packed weights of the training path, keyed by parameter versions
         self.spec = spec
-        self._engine: Optional[UpdateEngine] = None
-        self._versions = None
         self._inp_ref, self._inp_version = None, -1      # strong references: the address cannot be recycled while cached
         self._attn_ref, self._attn_version = None, -1
         self._skip = None      # patch._DeadWorkSkip when `accelerate(model)` found the loop's dead work provably dead (patch.py)
         self._last_out = None  # the `net` tensor handed back by the previous call: the same OBJECT coming in marks the next iteration
 
-    def _param_versions(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
     def _get_engine(self, device) -> UpdateEngine:
-        v = self._param_versions()
-        if self._engine is None or self._engine.device != device:
-            self._engine = UpdateEngine(dict(self.named_parameters()), self.spec, device, self.conv_precision)
-            self._versions = v
-        elif v != self._versions:
-            self._engine.pack(dict(self.named_parameters()))
-            self._versions = v
-        return self._engine
+        return self._engine_for(device, self.parameters(),
+                                lambda: UpdateEngine(dict(self.named_parameters()), self.spec, device, self.conv_precision),
+                                lambda eng: eng.pack(dict(self.named_parameters())))
 
     def forward(self, net, inp, corr, flow, *extra, **kw):
         """raft: (net, inp, corr, flow); gma: + attention (gma/update.py:148); ccmr: + global_context, level_index
@@ -831,15 +827,10 @@ class PfkUpdateBlock(torch.nn.Module):
             self._inp_ref, self._inp_version = inp, inp._version
             eng.state_changed()
             eng.prepare_context()      # the loop-invariant part of the GRU pre-activations, once per (forward, scale)
-        # corr: a channels-last view of a [M, C] buffer (what ptlflow_amd.CorrBlock returns) is used as is
-        cpm = corr.permute(0, 2, 3, 1)
+        # corr: the rows behind a channels-last view of a [M, C] buffer (what ptlflow_amd.CorrBlock returns) are used as they are
         C = corr.shape[1]
-        padded = getattr(corr, "_pfk_padded_pm", None)
-        if padded is not None and padded.shape[0] == B * H * W:
-            corr_pm = padded                                   # [M, round_up(C, 4)], pad columns zero (CorrBlock's own buffer)
-        elif corr.dtype == torch.float32 and cpm.is_contiguous() and C % 4 == 0:
-            corr_pm = cpm.reshape(B * H * W, C)
-        else:
+        corr_pm = corr_rows(corr)
+        if corr_pm is None:
             corr_pm = torch.zeros(B * H * W, round_up(C, 4), device=net.device, dtype=torch.float32)
             ops.nchw_to_pm(corr.float().contiguous(), corr_pm[:, :C])
         ops.nchw_to_pm(flow.float().contiguous(), eng.flow_view)
