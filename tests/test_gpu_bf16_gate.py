@@ -51,6 +51,45 @@ def test_gma_bf16_gate_headline(gpu):
     _gate("gma", 436, 1024, 32, gpu, 1234)
 
 
+def _gate_batch(kind, batch, gpu, H=436, W=1024, iters=32, seed=1234):
+    """BASELINE config 3's batch (bench.py's bf16 legs): pair 0 is the headline pair and is held to the headline gate — the same CPU
+    forwards, under the same _cpu_cache key; the batch in reverse order gives every pair's flow bit for bit (no kernel's per-element
+    K order depends on where a pixel sits in the batch)."""
+    from ptlflow_amd.raft import GMA, RAFT
+    make = (lambda **kw: GMA(iters=iters, **kw)) if kind == "gma" else (lambda **kw: RAFT(iters=iters, **kw))
+    base = make().load_synthetic(seed).eval()
+    P = {k: v.clone() for k, v in base.state_dict().items()}
+    x = O.smooth_pair(batch, H, W, seed)
+    x1 = O.smooth_pair(1, H, W, seed)
+    assert torch.equal(x[:1], x1), "pair 0 of the batch is not the headline pair"
+    from _cpu_cache import cpu_forward
+    key = ("synthetic", seed, "smooth", seed)
+    ref32 = cpu_forward(kind, P, x1, iters, key=key)["flows"][:, 0]
+    ref_ac = cpu_forward(kind, P, x1, iters, autocast=True, key=key)["flows"][:, 0].float()
+    gap, _ = O.epe(ref_ac, ref32)
+    m = make(conv_precision="bf16").eval()
+    m.load_state_dict(P)
+    m = m.to(gpu)
+    out = m({"images": x.to(gpu)})["flows"][:, 0].float().cpu()
+    rev = m({"images": x.flip(0).to(gpu)})["flows"][:, 0].float().cpu().flip(0)
+    mean, mx = O.epe(out[:1], ref32)
+    print(f"{kind} {H}x{W} {iters} it, batch {batch}: pair 0 GPU bf16 EPE mean {mean:.3e} max {mx:.3e} (autocast-CPU gap {gap:.3e})")
+    assert gap > 0
+    assert mean <= 2 * gap, f"pair 0 of the batch: GPU bf16 EPE {mean:.3e} exceeds 2x the autocast-CPU gap {gap:.3e}"
+    differ = [i for i in range(batch) if not torch.equal(out[i], rev[i])]
+    assert not differ, f"pairs {differ} change bits when the batch is reversed"
+
+
+def test_raft_bf16_gate_batch8(gpu):
+    """raft, 436x1024, 32 iterations, batch 8 (config 3's raft_bf16 leg)."""
+    _gate_batch("raft", 8, gpu)
+
+
+def test_gma_bf16_gate_batch4(gpu):
+    """gma, 436x1024, 32 iterations, batch 4 (config 3's gma_bf16 leg)."""
+    _gate_batch("gma", 4, gpu)
+
+
 def test_bf16_pyramid_and_lookup(gpu):
     """`pfk_corr_volume_bf16` + `pfk_corr_pool2x2_bf16` + `pfk_corr_lookup_bf16` against the oracle's pyramid built from bf16
     operands the way autocast builds it (bmm in bf16, / sqrt(D) in bf16, avg_pool2d in bf16): volume within one bf16 ulp,

@@ -287,21 +287,38 @@ def test_conv_all_tile_configs(gpu, tile):
     close(unpm(out, B, H, W), ref)
 
 
+def _stream_k_launch(ws, launch):
+    """`launch()` forced onto the stream-K schedule (cfg 9) with the partials of `ws` set to 0xFF bytes (NaN: a partial read before
+    it is written poisons its tile); returns whether partials were written.  The flag region and the fault word must be zero after."""
+    flags = ws.numel() - 768 * 64       # 768 partial tiles of 64x64 fp32, then the flag region (pfk_gemm.hip SK_WS_BYTES)
+    ws[:flags].fill_(0xFF)
+    torch.ops.pfk.debug_set_tile(9)
+    try:
+        launch()
+    finally:
+        torch.ops.pfk.debug_set_tile(-1)
+    off = torch.ops.pfk.conv_workspace_fault_offset()
+    assert int(ws[off: off + 4].view(torch.int32).item()) == 0, "a stream-K fix-up timed out"
+    assert not bool(ws[flags:].any()), "the stream-K flags are not zero after the launch"
+    return bool((ws[:flags] != 0xFF).any())
+
+
 @pytest.mark.parametrize("B,H,W,segs,cout,kh,kw", [
     (1, 12, 20, [64], 96, 3, 3),          # 8 tiles x 18 steps over 24 blocks: every tile split across 3 blocks
-    (1, 55, 128, [128, 256], 128, 1, 5),  # the q conv of the headline config (220 tiles, 60 steps, 512 blocks)
-    (2, 9, 7, [324], 256, 1, 1),          # short K (11 steps), partial channel chunk
-    (1, 23, 31, [96, 148, 32], 160, 3, 3),
-    (1, 5, 6, [32], 40, 1, 1),            # one K-step, one tile
+    (1, 55, 128, [128, 256], 128, 1, 5),  # q conv of the headline config without the context hoist (220 tiles x 60 steps, 512 blocks)
+    (2, 9, 7, [324], 256, 1, 1),          # short K (8 tiles x 11 steps over 14 blocks), partial channel chunk
+    (1, 23, 31, [96, 148, 32], 160, 3, 3),  # 36 tiles x 81 steps over 486 blocks, three sources
+    (1, 5, 6, [32], 40, 1, 1),            # one K-step, one tile: nothing to split
 ])
 def test_conv_stream_k(gpu, B, H, W, segs, cout, kh, kw):
-    """Stream-K schedule (workspace given) vs the tile-grid schedule vs the CPU reference; and run-to-run determinism."""
+    """Stream-K schedule (forced, workspace given) vs the tile-grid schedule vs an fp64 reference; run-to-run determinism.  The
+    heuristic gives none of these shapes to stream-K, so the workspace runs force it."""
     torch.manual_seed(13)
     cin = sum(segs)
     xs = [torch.randn(B, c, H, W) for c in segs]
     wt = torch.randn(cout, cin, kh, kw) / math.sqrt(cin * kh * kw)
     bias = torch.randn(cout)
-    ref = F.conv2d(torch.cat(xs, 1), wt, bias, padding=(kh // 2, kw // 2))
+    ref = F.conv2d(torch.cat(xs, 1).double(), wt.double(), bias.double(), padding=(kh // 2, kw // 2))
     offs, o = [], 0
     for c in segs:
         offs.append((o, c, c)); o += c
@@ -309,14 +326,64 @@ def test_conv_stream_k(gpu, B, H, W, segs, cout, kh, kw):
     srcs = [pm(x) for x in xs]
     M = B * H * W
     ws = torch.zeros(torch.ops.pfk.conv_workspace_bytes(), device=gpu, dtype=torch.uint8)
-    outs = []
+    outs, split = [], []
     for w in (ws, ws, None):
         out = torch.zeros(M, cout, device=gpu)
-        torch.ops.pfk.conv2d(srcs, B, H, W, kh, kw, packed, bias.cuda(), cout, EPI_LINEAR, False, 1.0, out, None, None, None, w)
+        launch = lambda: torch.ops.pfk.conv2d(srcs, B, H, W, kh, kw, packed, bias.cuda(), cout, EPI_LINEAR, False, 1.0,  # noqa: E731
+                                              out, None, None, None, w)
+        if w is None:
+            launch()
+        else:
+            split.append(_stream_k_launch(ws, launch))
         outs.append(out)
     close(unpm(outs[0], B, H, W), ref)
     close(unpm(outs[2], B, H, W), ref)
     assert torch.equal(outs[0], outs[1]), "stream-K result is not deterministic"
+    steps = sum(kh * kw * ((c + 31) // 32) for c in segs)
+    if steps > 1:
+        assert all(split), "no partial tile was written: the forced stream-K launch split no tile"
+
+
+@pytest.mark.parametrize("epi", [EPI_GRU_ZR, EPI_GRU_Q], ids=["zr", "q"])
+def test_conv_stream_k_gru(gpu, epi):
+    """The gate epilogues with the context term (`residual`) on the forced stream-K schedule (SepConvGRU widths at 23x31: 48 / 24
+    tiles x 40 K-steps over 320 / 160 blocks, every tile split): against fp64, deterministic, h's neighbouring columns untouched."""
+    torch.manual_seed(14)
+    B, H, W, Ch = 1, 23, 31, 128
+    M = B * H * W
+    K = 2 * Ch
+    cout = 2 * Ch if epi == EPI_GRU_ZR else Ch
+    wt = torch.randn(cout, K, 1, 5) / math.sqrt(K * 5)
+    bias = torch.randn(cout) * 0.1
+    hx = torch.randn(M, 3 * Ch)                    # [h | context | motion]: h and the motion channels are the sources
+    hx[:, :Ch] = torch.tanh(hx[:, :Ch])
+    zin = torch.rand(M, Ch)                        # q: the z a z|r launch stored
+    rhin = torch.randn(M, Ch) * 0.5                # q: its r * h, the first source
+    res = torch.randn(M, cout) * 0.5
+    src0 = hx[:, :Ch] if epi == EPI_GRU_ZR else rhin
+    x = torch.cat([src0, hx[:, 2 * Ch:]], 1).double().view(B, H, W, K).permute(0, 3, 1, 2)
+    v = F.conv2d(x, wt.double(), padding=(0, 2)).permute(0, 2, 3, 1).reshape(M, cout) + bias.double() + res.double()
+    packed = _packed(wt, [(0, Ch, Ch), (Ch, Ch, Ch)])
+    ws = torch.zeros(torch.ops.pfk.conv_workspace_bytes(), device=gpu, dtype=torch.uint8)
+    results = []
+    for _ in range(2):
+        hxg = hx.cuda()
+        z = zin.cuda() if epi == EPI_GRU_Q else torch.zeros(M, Ch, device=gpu)
+        rh = rhin.cuda() if epi == EPI_GRU_Q else torch.zeros(M, Ch, device=gpu)
+        srcs = [hxg[:, :Ch] if epi == EPI_GRU_ZR else rh, hxg[:, 2 * Ch:]]
+        assert _stream_k_launch(ws, lambda: torch.ops.pfk.conv2d(srcs, B, H, W, 1, 5, packed, bias.cuda(), cout, epi, False, 1.0, None,
+                                                                 hxg[:, :Ch], z, rh if epi == EPI_GRU_ZR else None, ws, res.cuda())), \
+            "no partial tile was written: the forced stream-K launch split no tile"
+        assert torch.equal(hxg[:, Ch:].cpu(), hx[:, Ch:]), "wrote outside h"
+        results.append((hxg, z, rh))
+    if epi == EPI_GRU_ZR:
+        close(results[0][1], torch.sigmoid(v[:, :Ch]), rtol=2e-5, atol=3e-5)
+        close(results[0][2], torch.sigmoid(v[:, Ch:]) * hx[:, :Ch].double(), rtol=2e-5, atol=3e-5)
+        assert torch.equal(results[0][1], results[1][1]) and torch.equal(results[0][2], results[1][2]), "stream-K z|r is not deterministic"
+    else:
+        zd = zin.double()
+        close(results[0][0][:, :Ch], (1 - zd) * hx[:, :Ch].double() + zd * torch.tanh(v), rtol=2e-5, atol=3e-5)
+        assert torch.equal(results[0][0], results[1][0]), "stream-K q is not deterministic"
 
 
 def test_conv_multi_source(gpu):
