@@ -291,6 +291,12 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
 long long pfk_conv_wino_weight_floats(int cin, int cout);   /* < 0 (PFK_ERR_BAD_ARG) unless cin % 32 == 0, cin, cout > 0 */
 int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream);
 
+/* The same kernel with the residual-block epilogue (sea_raft/layer.py:144-150, `relu(x + relu(bn2(conv2(y))))`):
+ * v = relu?(acc + bias) * scale; v = residual[p*residual_ld + co] + v; relu_after_residual?.  `residual` is required (fp32 rows,
+ * residual_ld >= cout; PFK_ERR_BAD_ARG otherwise), `cout_active` is not supported; everything else as pfk_conv2d_wino_f32, which
+ * keeps refusing a residual. */
+int pfk_conv2d_wino_res_f32(const pfk_conv_desc* d, pfk_stream_t stream);
+
 /* Same convolution on the bf16 matrix cores with split operands (fp32 in HBM, fp32 accumulate, fp32 epilogue).
  * Every fp32 operand x is replaced by the sum of its first `nsplit` bf16 planes x0 = bf16(x), x1 = bf16(x - x0),
  * x2 = bf16(x - x0 - x1); a product keeps the terms a_i*b_j with i + j < nsplit:
@@ -566,6 +572,17 @@ int pfk_conv_stem_f32(const float* img, const float* weight, const float* bias, 
 int pfk_conv_stem_b16(const float* img, const float* weight, const float* bias, void* out_bf16, int out_ld, int B,
                       int H, int W, int cout, int relu, pfk_stream_t stream);
 int pfk_debug_set_stem_valu(int on);       /* 1 = pfk_conv_stem_f32 always takes the VALU kernel (A/B timing) */
+/* The same stem for ONE or TWO 3-channel images summed into one output (sea_raft/extractor.py:35-37: ResNetFPN's
+ * Conv2d(input_dim, 64, 7, stride=2, padding=3) with input_dim 3 (`fnet`) or 6 (`cnet`, on cat([image1, image2], 1))):
+ * img_a, img_b NCHW 3-channel planes, image n of each at `img + n * bstride` floats (bstride >= 3*H*W: 6*H*W for the two halves
+ * of a [B][6][H][W] tensor, img_b = img_a + 3*H*W); img_b may be NULL, then cin must be 3, else cin must be 6.  weight packed
+ * [49][cin][cout] (channels 0..2 of a tap are img_a's, 3..5 img_b's), 16-byte aligned.  cout must be 64 (PFK_ERR_UNSUPPORTED
+ * otherwise).  Rows of `cout` values at out_ld; nothing beyond column cout is written.  fp32 matrix cores, fp32 accumulation. */
+int pfk_conv_stem2_f32(const float* img_a, long long bstride_a, const float* img_b, long long bstride_b, const float* weight,
+                       const float* bias, float* out, int out_ld, int B, int H, int W, int cin, int cout, int relu, pfk_stream_t stream);
+int pfk_conv_stem2_b16(const float* img_a, long long bstride_a, const float* img_b, long long bstride_b, const float* weight,
+                       const float* bias, void* out_bf16, int out_ld, int B, int H, int W, int cin, int cout, int relu,
+                       pfk_stream_t stream);
 
 /* InstanceNorm2d statistics (extractor.py:136-140; affine=False, biased variance, eps inside the sqrt) over
  * pixel-major x[B*HW][ld], channels [0, C): mean[b*C+c], rstd[b*C+c].  One pass over x, deterministic chunked reduction of sum(x) and

@@ -510,6 +510,182 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Stem for one or two 3-channel images, cout = 64 (SEA-RAFT's ResNetFPN: `fnet` reads one image, `cnet` the 6-channel pair,
+// sea_raft/extractor.py:35-37).  Conv2d(6, 64, 7, 2, 3) on cat([a, b], 1) is the 3-channel stem of `a` plus the 3-channel stem of
+// `b` into the same accumulators: the kernel keeps the 3-channel patch layout and the K-step code of conv_stem_mfma_kernel above and
+// makes one pass per image over the accumulators (pass 0: the weight rows of channels 0..2, pass 1: those of channels 3..5), so the
+// two halves of the model's [B, 6, H, W] tensor (or two separate images) are read in place, each with its own batch stride.
+// Both weight halves stay resident in LDS ([2][148][64] fp32 = 74 KB, re-ordered while staging from the packed [49][cin][64]), so a
+// CU holds one workgroup.  To keep two waves per SIMD that workgroup has G = 2 groups of four waves; a group is what a workgroup
+// of the 3-channel kernel is (its own tile stream, its own pair of patch buffers: 34 KB), the groups only share the weight and the
+// barriers: 142 KB of the CU's 160.  With one image a group alternates its two buffers per tile; with two, buffer 0 holds image a's
+// patch and buffer 1 image b's: b's is requested before a's MFMA pass and parked behind it, the next tile's a-patch before b's pass.
+// Measured at 440 x 1024 (scripts/stem2_bench.py): one group per CU (110 KB, one wave per SIMD) is 1.15-1.4x
+// slower than two, so only G = 2 is built.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int S2_WHALF = 2 * SM_KSTEPS * 64;       // one image's [148][64] weight rows
+constexpr int S2_PATCH = (SM_PATCH + 3) & ~3;      // 4348 floats: every buffer 16-byte aligned
+
+constexpr size_t stem2_smem_bytes(int G) { return (size_t)(2 * S2_WHALF + G * 2 * S2_PATCH) * sizeof(float); }
+
+template <int G, int NIMG, typename TO>
+__global__ __launch_bounds__(256 * G, 1) void conv_stem2_mfma_kernel(const float* __restrict__ img_a, const float* __restrict__ img_b,
+                                                                      long long bstride_a, long long bstride_b,
+                                                                      const float* __restrict__ wgt, const float* __restrict__ bias,
+                                                                      TO* __restrict__ out, int out_ld, int H, int W, int Ho, int Wo,
+                                                                      int tiles_x, int tiles_y, int ntiles, int relu) {
+  extern __shared__ __attribute__((aligned(16))) float s2_smem[];
+  constexpr int CIN = 3 * NIMG;
+  const int tid = threadIdx.x & 255;
+  const int grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform
+  const int lane = tid & 63;
+  const int px = lane & 31, hl = lane >> 5;
+  float* s_in = s2_smem + grp * 2 * S2_PATCH;         // the patches in front: their ds offsets stay immediates
+  float* s_w = s2_smem + G * 2 * S2_PATCH;
+  int poff[SM_PT];
+  short pyy[SM_PT], pxx[SM_PT];
+#pragma unroll
+  for (int j = 0; j < SM_PT; ++j) {
+    const int e = tid + 256 * j;
+    const int ci = e / (SM_PR * SM_PC);
+    const int r = e - ci * (SM_PR * SM_PC);
+    const int yy = r / SM_PC, xx = r - yy * SM_PC;
+    pyy[j] = (short)yy; pxx[j] = (short)xx;
+    poff[j] = (ci * H + yy) * W + xx;
+  }
+  float pv[SM_PT];
+  // a group without a tile in the workgroup's last iteration (tile >= ntiles) stages zeros and stores nothing
+  auto fetch = [&](int tile, const float* img, long long bstride) {
+#pragma unroll
+    for (int j = 0; j < SM_PT; ++j) pv[j] = 0.f;
+    if (tile >= ntiles) return;
+    const int tx = tile % tiles_x, t1 = tile / tiles_x;
+    const int ty = t1 % tiles_y, b = t1 / tiles_y;
+    const int iy0 = 2 * ty * SM_ROWS - STEM_R, ix0 = 2 * tx * SM_COLS - STEM_R;
+    const float* src = img + (long long)b * bstride + (long long)iy0 * W + ix0;
+#pragma unroll
+    for (int j = 0; j < SM_PT; ++j) {
+      const int gy = iy0 + pyy[j], gx = ix0 + pxx[j];
+      if (tid + 256 * j < SM_PATCH && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) pv[j] = src[poff[j]];
+    }
+  };
+  auto park = [&](float* dst) {
+#pragma unroll
+    for (int j = 0; j < SM_PT; ++j)
+      if (tid + 256 * j < SM_PATCH) dst[tid + 256 * j] = pv[j];
+  };
+
+  // the workgroup walks tile groups base, base + G * gridDim.x, ...; group `grp` takes tile base + grp (host: ntiles + 2 * G * grid < 2^31)
+  const int step = G * (int)gridDim.x;
+  int base = G * (int)blockIdx.x;
+  if (base >= ntiles) return;
+  fetch(base + grp, img_a, bstride_a);
+  // s_w[pass][k][c], k = tap * 3 + ci, from wgt[tap][CIN][64] channel 3 pass + ci; row 147 of each half zero
+  for (int e = threadIdx.x; e < NIMG * S2_WHALF / 4; e += 256 * G) {
+    const int pass = e / (S2_WHALF / 4), r = e - pass * (S2_WHALF / 4);
+    const int k = r >> 4, c4 = r & 15;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (k < SM_KTOT) v = *reinterpret_cast<const f32x4*>(wgt + ((k / 3) * CIN + 3 * pass + k % 3) * 64 + c4 * 4);
+    *reinterpret_cast<f32x4*>(s_w + e * 4) = v;
+  }
+  park(s_in);
+  __syncthreads();
+  float b0[2];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt) b0[nt] = bias ? bias[nt * 32 + px] : 0.f;
+  int abase[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) abase[mt] = (2 * (2 * wid + mt)) * SM_PC + 2 * px;
+
+  // buffer parity: NIMG = 1 alternates per tile; NIMG = 2 uses buffer 0 for image a and buffer 1 for image b of every tile
+  for (int buf = 0; base < ntiles; base += step) {
+    const int tile = base + grp;
+    const bool more = base + step < ntiles;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+    if constexpr (NIMG == 2) {
+      fetch(tile, img_b, bstride_b);
+      StemSteps<2, 0>::run(acc, s_in, s_w, abase, hl, px);
+      park(s_in + S2_PATCH);
+      __syncthreads();
+      if (more) fetch(tile + step, img_a, bstride_a);
+      StemSteps<2, 0>::run(acc, s_in + S2_PATCH, s_w + S2_WHALF, abase, hl, px);
+    } else {
+      if (more) fetch(tile + step, img_a, bstride_a);
+      StemSteps<2, 0>::run(acc, s_in + buf * S2_PATCH, s_w, abase, hl, px);
+      buf ^= 1;
+    }
+    if (tile < ntiles) {
+      const int tx = tile % tiles_x, t1 = tile / tiles_x;
+      const int ty = t1 % tiles_y, b = t1 / tiles_y;
+      const int yo0 = ty * SM_ROWS, xo0 = tx * SM_COLS;
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int c = nt * 32 + px;
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          const int yo = yo0 + 2 * wid + mt;
+          if (yo >= Ho) continue;
+          const long long row0 = ((long long)b * Ho + yo) * Wo;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int xo = xo0 + (r & 3) + 8 * (r >> 2) + 4 * hl;
+            if (xo >= Wo) continue;
+            float v = acc[mt][nt][r] + b0[nt];
+            if (relu) v = (v < 0.f) ? 0.f : v;
+            out[(row0 + xo) * out_ld + c] = (TO)v;
+          }
+        }
+      }
+    }
+    if (more) park(s_in + (NIMG == 2 ? 0 : buf) * S2_PATCH);
+    __syncthreads();      // the next patch is complete, and every wave is done reading the one that is overwritten after it
+  }
+}
+
+template <int G, typename TO>
+int stem2_launch_g(const float* img_a, long long sa, const float* img_b, long long sb, const float* weight, const float* bias, TO* out,
+                   int out_ld, int H, int W, int Ho, int Wo, int tiles_x, int tiles_y, int tiles, int relu, hipStream_t st) {
+  const int wgs = (tiles + G - 1) / G;
+  const unsigned grid = (unsigned)(wgs < 256 ? wgs : 256);                   // one workgroup per CU, persistent over the tile list
+  constexpr size_t smem = stem2_smem_bytes(G);
+  static pfk_device_once once[2];
+  if (img_b) {
+    auto kern = conv_stem2_mfma_kernel<G, 2, TO>;
+    once[1].run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out, out_ld, H, W, Ho, Wo, tiles_x,
+                       tiles_y, tiles, relu);
+    return pfk_launch_status();
+  }
+  auto kern = conv_stem2_mfma_kernel<G, 1, TO>;
+  once[0].run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out, out_ld, H, W, Ho, Wo, tiles_x,
+                     tiles_y, tiles, relu);
+  return pfk_launch_status();
+}
+
+template <typename TO>
+int stem2_launch(const float* img_a, long long sa, const float* img_b, long long sb, const float* weight, const float* bias, TO* out,
+                 int out_ld, int B, int H, int W, int cin, int cout, int relu, hipStream_t st) {
+  if (!img_a || !weight || !out || B <= 0 || H <= 0 || W <= 0 || cout <= 0 || out_ld < cout) return PFK_ERR_BAD_ARG;
+  if (cin != (img_b ? 6 : 3)) return PFK_ERR_BAD_ARG;
+  if ((long long)3 * H * W >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;     // 32-bit offsets inside one image
+  if (sa < (long long)3 * H * W || (img_b && sb < (long long)3 * H * W)) return PFK_ERR_BAD_ARG;
+  if (cout != 64) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_aligned16(weight)) return PFK_ERR_ALIGNMENT;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int tiles_x = (Wo + SM_COLS - 1) / SM_COLS, tiles_y = (Ho + SM_ROWS - 1) / SM_ROWS;
+  const long long tiles = (long long)B * tiles_x * tiles_y;
+  if (tiles > 0x3fffffffLL) return PFK_ERR_UNSUPPORTED;
+  return stem2_launch_g<2, TO>(img_a, sa, img_b, sb, weight, bias, out, out_ld, H, W, Ho, Wo, tiles_x, tiles_y, (int)tiles, relu, st);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Weight (and bias) gradient of the stem: dW[ky][kx][ci][c] = sum_p dY[p][c] * img[ci][2yo + ky - 3][2xo + kx - 3].
 // Same tiling as the forward kernel (32 consecutive output pixels of one output row per tile, thread = channel x 8 pixels,
 // the 3 x 7 x 69 input patch staged in LDS), but PERSISTENT: a block walks tiles bid, bid + G, ... and keeps its 147 (+1 bias)
@@ -619,6 +795,20 @@ int pfk_conv_stem_b16(const float* img, const float* weight, const float* bias, 
   if (!img || !weight || !out_bf16 || B <= 0 || H <= 0 || W <= 0 || cout <= 0 || out_ld < cout) return PFK_ERR_BAD_ARG;
   if (!pfk_aligned16(weight) || (reinterpret_cast<uintptr_t>(out_bf16) & 1u)) return PFK_ERR_ALIGNMENT;
   return stem_launch<__bf16>(img, weight, bias, static_cast<__bf16*>(out_bf16), out_ld, B, H, W, cout, relu, static_cast<hipStream_t>(stream));
+}
+
+int pfk_conv_stem2_f32(const float* img_a, long long bstride_a, const float* img_b, long long bstride_b, const float* weight,
+                       const float* bias, float* out, int out_ld, int B, int H, int W, int cin, int cout, int relu, pfk_stream_t stream) {
+  return stem2_launch<float>(img_a, bstride_a, img_b, bstride_b, weight, bias, out, out_ld, B, H, W, cin, cout, relu,
+                             static_cast<hipStream_t>(stream));
+}
+
+int pfk_conv_stem2_b16(const float* img_a, long long bstride_a, const float* img_b, long long bstride_b, const float* weight,
+                       const float* bias, void* out_bf16, int out_ld, int B, int H, int W, int cin, int cout, int relu,
+                       pfk_stream_t stream) {
+  if (reinterpret_cast<uintptr_t>(out_bf16) & 1u) return PFK_ERR_ALIGNMENT;
+  return stem2_launch<__bf16>(img_a, bstride_a, img_b, bstride_b, weight, bias, static_cast<__bf16*>(out_bf16), out_ld, B, H, W, cin,
+                              cout, relu, static_cast<hipStream_t>(stream));
 }
 
 int pfk_debug_set_stem_valu(int on) {

@@ -209,10 +209,26 @@ void conv2d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, in
   else check_ok(pfk_conv2d_f32(&d, cur_stream()), "conv2d");
 }
 
+void conv2d_wino_impl(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                      int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active, const Tensor* residual,
+                      bool relu_after_residual);
+
 // Winograd F(2x2,3x3) 3x3 convolution (pfk_conv2d_wino_f32): one fp32 source [B*H*W, cin] view, the transformed weight of
 // packing.pack_wino_weight (flat, pfk_conv_wino_weight_floats(cin, cout) floats), LINEAR epilogue into an [M, cout] view
 void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
                  int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active) {
+  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, cout_active, nullptr, false);
+}
+
+// the same with the residual-block epilogue (pfk_conv2d_wino_res_f32): out = relu2?(residual + relu?(conv + bias) * scale)
+void conv2d_wino_res(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                     int64_t cout, bool relu, double scale, const Tensor& out, const Tensor& residual, bool relu_after_residual) {
+  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, 0, &residual, relu_after_residual);
+}
+
+void conv2d_wino_impl(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                      int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active, const Tensor* residual,
+                      bool relu_after_residual) {
   OpScope scope(weight);
   check_pm(src, "src");
   TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, "conv2d_wino: sizes");
@@ -233,6 +249,13 @@ void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tenso
   check_pm(out, "out");
   TORCH_CHECK(out.size(0) == B * H * W && out.size(1) == cout, "conv2d_wino: out must be a [M, cout] view");
   d.out = fptr(out); d.out_ld = out.stride(0); d.out_coff = 0;
+  if (residual) {
+    check_pm(*residual, "residual");
+    TORCH_CHECK(residual->size(0) == B * H * W && residual->size(1) == cout, "conv2d_wino_res: residual must be a [M, cout] view");
+    d.residual = fptr(*residual); d.residual_ld = residual->stride(0); d.relu_after_residual = relu_after_residual;
+    check_ok(pfk_conv2d_wino_res_f32(&d, cur_stream()), "conv2d_wino_res");
+    return;
+  }
   check_ok(pfk_conv2d_wino_f32(&d, cur_stream()), "conv2d_wino");
 }
 
@@ -809,6 +832,39 @@ void conv_stem(const Tensor& img, const Tensor& weight, const c10::optional<Tens
   check_ok(pfk_conv_stem_f32(fptr(img), fptr(weight), b, fptr(out), out.stride(0), B, H, W, cout, relu, cur_stream()), "conv_stem");
 }
 
+// the stem for one or two 3-channel images (SEA-RAFT's ResNetFPN): img_a / img_b are [B,3,H,W] views whose three planes are dense
+// (any batch stride >= 3*H*W: the channel halves of a [B,6,H,W] tensor are read in place); weight [49,cin,cout], cin = 3 or 6
+void conv_stem2(const Tensor& img_a, const c10::optional<Tensor>& img_b, const Tensor& weight, const c10::optional<Tensor>& bias,
+                Tensor out, bool relu) {
+  OpScope scope(img_a);
+  check_dev_f32(img_a, "img_a"); check_dev_f32(weight, "weight");
+  const bool out_b16 = check_pm_any(out, "out");
+  TORCH_CHECK(img_a.dim() == 4 && img_a.size(1) == 3, "conv_stem2: img_a [B,3,H,W]");
+  const int B = img_a.size(0), H = img_a.size(2), W = img_a.size(3), cout = out.size(1);
+  auto planes = [&](const Tensor& t, const char* what) {
+    TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == 3 && t.size(2) == H && t.size(3) == W, "conv_stem2: ", what, " [B,3,H,W]");
+    TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == W && t.stride(1) == (int64_t)H * W && (B == 1 || t.stride(0) >= (int64_t)3 * H * W),
+                "conv_stem2: ", what, " needs dense channel planes");
+    return B == 1 ? (long long)3 * H * W : (long long)t.stride(0);
+  };
+  const long long sa = planes(img_a, "img_a");
+  const float* pb = nullptr;
+  long long sb = 0;
+  if (img_b.has_value()) { check_dev_f32(*img_b, "img_b"); sb = planes(*img_b, "img_b"); pb = fptr(*img_b); }
+  const int cin = pb ? 6 : 3;
+  TORCH_CHECK(weight.is_contiguous() && weight.numel() == (int64_t)49 * cin * cout, "conv_stem2: weight [49,cin,cout]");
+  TORCH_CHECK(out.size(0) == (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), "conv_stem2: out rows");
+  const float* b = nullptr;
+  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); b = fptr(*bias); }
+  if (out_b16) {
+    check_ok(pfk_conv_stem2_b16(fptr(img_a), sa, pb, sb, fptr(weight), b, out.data_ptr(), out.stride(0), B, H, W, cin, cout, relu, cur_stream()),
+             "conv_stem2 (bf16 out)");
+    return;
+  }
+  check_ok(pfk_conv_stem2_f32(fptr(img_a), sa, pb, sb, fptr(weight), b, fptr(out), out.stride(0), B, H, W, cin, cout, relu, cur_stream()),
+           "conv_stem2");
+}
+
 // weight / bias gradient in PyTorch's layouts: dw [cout, sum(reals), kh, kw], db [cout] (optional); dy [B*Ho*Wo, cout4]
 void conv_wgrad_unpacked(at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, Tensor dw,
                          const c10::optional<Tensor>& db, at::IntArrayRef reals, int64_t stride, bool accumulate) {
@@ -1034,6 +1090,7 @@ TORCH_LIBRARY(pfk, m) {
   m.def("conv_stem_wgrad(Tensor img, Tensor dy, Tensor(a!) dw, Tensor(b!) db) -> ()");
   m.def("instnorm_workspace_bytes(int B, int C) -> int", &instnorm_workspace_bytes);
   m.def("conv_stem(Tensor img, Tensor weight, Tensor? bias, Tensor(a!) out, bool relu) -> ()");
+  m.def("conv_stem2(Tensor img_a, Tensor? img_b, Tensor weight, Tensor? bias, Tensor(a!) out, bool relu) -> ()");
   m.def("instnorm_stats(Tensor x, int B, int HW, float eps, Tensor(a!) mean, Tensor(b!) rstd, Tensor(c!) workspace) -> ()");
   m.def("norm_apply(Tensor x, Tensor mean, Tensor rstd, Tensor? residual, Tensor(a!) out, int B, int HW, bool relu, "
         "bool relu_after_residual) -> ()");
@@ -1055,6 +1112,8 @@ TORCH_LIBRARY(pfk, m) {
         "Tensor(e!)? workspace=None, Tensor? residual=None, int stride=1, bool relu_after_residual=False, int cout_active=0, int cout_split=0) -> ()");
   m.def("conv2d_wino(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
         "int cout_active=0) -> ()");
+  m.def("conv2d_wino_res(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
+        "Tensor residual, bool relu_after_residual) -> ()");
   m.def("conv2d_group(Tensor[] srcs, int B, int H, int W, int[] k, Tensor[] weights, Tensor[] biases, int[] relu, float[] scale, Tensor(a!)[] outs, Tensor[] residuals) -> ()");
   m.def("conv2d_b16(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, int epilogue, bool relu, "
         "float scale, Tensor(a!)? out, Tensor(b!)? h=None, Tensor(c!)? h_b16=None, Tensor(d!)? aux_z=None, Tensor(e!)? aux_rh=None, "
@@ -1103,6 +1162,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv2d_b16", &conv2d_b16);
   m.impl("conv2d_group", &conv2d_group);
   m.impl("conv2d_wino", &conv2d_wino);
+  m.impl("conv2d_wino_res", &conv2d_wino_res);
   m.impl("conv_cin2", &conv_cin2);
   m.impl("flow_delta", &flow_delta);
   m.impl("flow_from_coords", &flow_from_coords);
@@ -1124,6 +1184,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("pm_to_nchw", &pm_to_nchw);
   m.impl("pm_to_cm", &pm_to_cm);
   m.impl("conv_stem", &conv_stem);
+  m.impl("conv_stem2", &conv_stem2);
   m.impl("gru_gates_zr", &gru_gates_zr);
   m.impl("gru_gates_q", &gru_gates_q);
   m.impl("gru_backward_q", &gru_backward_q);

@@ -49,6 +49,8 @@ struct WinoArgs {
   int ncb;                       // column blocks launched
   int relu; float scale;
   float* out; int out_ld, out_coff;
+  const float* res; int res_ld;  // residual rows [pixel][res_ld], column n (conv_gemm_wino_f32_kernel<true> only)
+  int relu2;                     // relu after the residual add
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned bytes) {
@@ -67,6 +69,9 @@ __device__ __forceinline__ void wino_load(__amdgpu_buffer_rsrc_t rs, __amdgpu_bu
     wr[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wk + j * 4096u, 0));
 }
 
+// RES: the residual-block epilogue of pfk_conv2d_wino_res_f32 (v = residual + v, then the block's last relu); the instantiation
+// without it is pfk_conv2d_wino_f32's kernel, unchanged.
+template <bool RES>
 __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoArgs a) {
   __shared__ __attribute__((aligned(16))) float sV[16 * WT * WK];   // [xi][tile][slot]      16 KB
   __shared__ __attribute__((aligned(16))) float sU[16 * WN * WK];   // [xi][column][slot]    32 KB
@@ -196,6 +201,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
         if (a.relu) v = (v < 0.f) ? 0.f : v;   // NaN-propagating like torch.relu
         v *= a.scale;
         const long long p = ((long long)b * a.H + oy) * a.W + ox;
+        if constexpr (RES) {
+          v = a.res[p * a.res_ld + n] + v;
+          if (a.relu2) v = (v < 0.f) ? 0.f : v;
+        }
         outp[p * a.out_ld + a.out_coff + n] = v;
       }
     }
@@ -211,11 +220,13 @@ long long pfk_conv_wino_weight_floats(int cin, int cout) {
   return 16LL * cin * ((cout + WN - 1) / WN * WN);
 }
 
-int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
+// `res`: pfk_conv2d_wino_res_f32 (a residual is required and relu_after_residual honoured); else pfk_conv2d_wino_f32 (both refused)
+static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   if (!d) return PFK_ERR_BAD_ARG;
-  if (d->num_src != 1 || d->kh != 3 || d->kw != 3 || d->stride > 1 || d->epilogue != PFK_EPI_LINEAR || d->residual ||
-      d->relu_after_residual)
+  if (d->num_src != 1 || d->kh != 3 || d->kw != 3 || d->stride > 1 || d->epilogue != PFK_EPI_LINEAR)
     return PFK_ERR_UNSUPPORTED;
+  if (!res && (d->residual || d->relu_after_residual)) return PFK_ERR_UNSUPPORTED;
+  if (res && (!d->residual || d->residual_ld < d->cout || (reinterpret_cast<uintptr_t>(d->residual) & 3u))) return PFK_ERR_BAD_ARG;
   const pfk_conv_src& s = d->src[0];
   if (!s.ptr || !d->weight || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || s.channels <= 0 ||
       s.ld < s.channels || d->out_coff < 0 || d->out_ld < d->out_coff + d->cout)
@@ -248,8 +259,20 @@ int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
   a.ncb = ncb;
   a.relu = d->relu ? 1 : 0; a.scale = d->scale;
   a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
-  hipLaunchKernelGGL(conv_gemm_wino_f32_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  if (res) {
+    if (d->cout_active > 0 && d->cout_active < d->cout) return PFK_ERR_UNSUPPORTED;
+    a.res = d->residual; a.res_ld = d->residual_ld; a.relu2 = d->relu_after_residual ? 1 : 0;
+    hipLaunchKernelGGL(conv_gemm_wino_f32_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  } else {
+    hipLaunchKernelGGL(conv_gemm_wino_f32_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  }
   return pfk_launch_status();
 }
+
+int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) { return wino_launch(d, false, stream); }
+
+int pfk_conv2d_wino_res_f32(const pfk_conv_desc* d, pfk_stream_t stream) { return wino_launch(d, true, stream); }
+
+
 
 }  // extern "C"

@@ -12,6 +12,8 @@ What gets replaced:
 * seam B3 — ``model.update_block`` is wrapped by `PfkUpdateBlock`, which keeps the original sub-modules
   (state_dict keys, checkpoints and optimizers are untouched) and only overrides ``forward``;
 * seam B4 — ``model.fnet`` / ``model.cnet`` (`BasicEncoder`) are wrapped by `PfkEncoder` the same way;
+* SEA-RAFT only, opt-in — ``accelerate(model, sea_raft_update=...)`` (update block, heads, ``upsample_data``; sea_update.py) and
+  ``accelerate(model, sea_raft_encoders=...)`` (``ResNetFPN`` ``fnet`` / ``cnet`` and ``init_conv``; sea_encoder.py);
 * seam B5 — ``model.upsample_flow`` (raft.py:112-123, a method the loop calls every iteration) is shadowed on the instance by
   the convex-upsampling kernel after a behaviour probe (`_UpsampleSeam`).
 
@@ -39,6 +41,7 @@ from . import load_native
 from ._seam import ProbedMethodSeam, WrappedModule, eligible
 from .corr import get_corr_block as _pfk_get_corr_block
 from .encoder import PfkEncoder
+from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
 from .sea_update import HEAD_SHAPES, PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam, sea_block_shapes
 from .update import PfkUpdateBlock, UpdateSpec, basic_spec, ccmr_spec, gma_spec, ms_raft_plus_spec, small_spec
 
@@ -110,15 +113,46 @@ def match_sea_raft(model: torch.nn.Module) -> Optional[Tuple[int, int]]:
     return int(w[1]), nb
 
 
-def _sea_precision(sea_raft_update) -> Optional[str]:
-    """`accelerate`'s `sea_raft_update` -> the SEA seams' precision, None = not installed"""
+def _sea_precision(sea_raft_update, option: str = "sea_raft_update") -> Optional[str]:
+    """`accelerate`'s `sea_raft_update` / `sea_raft_encoders` -> the SEA seams' precision, None = not installed"""
     if sea_raft_update is False or sea_raft_update is None:
         return None
     if sea_raft_update is True or sea_raft_update == "fp32":
         return "fp32"
     if sea_raft_update == "bf16":
         return "bf16"
-    raise ValueError(f"sea_raft_update must be False, True, 'fp32' or 'bf16', got {sea_raft_update!r}")
+    raise ValueError(f"{option} must be False, True, 'fp32' or 'bf16', got {sea_raft_update!r}")
+
+
+# (module of the class, class name) of SEA-RAFT's ResNet encoders (sea_raft/extractor.py:6-116); wrapped only with
+# `accelerate(model, sea_raft_encoders=...)` and only when the state_dict is exactly sea_encoder.resnet_fpn_shapes
+_RESNET_ENCODERS = {("ptlflow.models.sea_raft.extractor", "ResNetFPN")}
+
+
+def register_resnet_encoder(module: str, cls: str = "ResNetFPN") -> None:
+    """Declare another module's class to be SEA-RAFT's ResNetFPN (the state_dict check still applies)."""
+    _RESNET_ENCODERS.add((module, cls))
+
+
+def match_resnet_encoder(enc: torch.nn.Module) -> bool:
+    return (type(enc).__module__, type(enc).__name__) in _RESNET_ENCODERS and match_resnet_fpn(enc)
+
+
+def _install_sea_encoders(model: torch.nn.Module, precision: str) -> bool:
+    """SEA-RAFT's `fnet` / `cnet` (ResNetFPN) and, behind a wrapped `cnet`, `init_conv` (sea_encoder.py); True when any is installed.
+    Installed wrappers of another precision are switched to this one (their engines are rebuilt on the next call)."""
+    for attr in ("fnet", "cnet"):
+        enc = getattr(model, attr, None)
+        if isinstance(enc, PfkResNetEncoder):
+            enc.set_precision(precision)
+        elif enc is not None and match_resnet_encoder(enc):
+            setattr(model, attr, PfkResNetEncoder(enc, precision))
+    cnet, conv = getattr(model, "cnet", None), getattr(model, "init_conv", None)
+    if isinstance(conv, PfkInitConv):
+        conv.set_precision(precision)
+    elif isinstance(cnet, PfkResNetEncoder) and conv is not None and match_init_conv(conv, cnet.final_conv.out_channels):
+        model.init_conv = PfkInitConv(conv, cnet, precision)
+    return any(isinstance(getattr(model, a, None), PfkResNetEncoder) for a in ("fnet", "cnet"))
 
 
 def _install_sea_raft(model: torch.nn.Module, precision: str = "fp32") -> bool:
@@ -547,7 +581,7 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
-               sea_raft_update=False) -> torch.nn.Module:
+               sea_raft_update=False, sea_raft_encoders=False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -567,8 +601,12 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     ``sea_raft_update="bf16"``: the same seams on the bf16 matrix-core path (K8b, bf16 activation rows): they serve fp32 and bf16
     GPU tensors with autocast off or cuda autocast to bfloat16 (an autocast loop gets bf16 `net` / mask views back, an fp32 loop
     fp32 ones; `flow_head` returns fp32).  ``True`` and ``"fp32"`` are today's fp32 path; any other value raises ValueError.  A
-    second call with another value switches the installed seams.  ``conv_precision`` is not read by the SEA seams."""
+    second call with another value switches the installed seams.  ``conv_precision`` is not read by the SEA seams.
+    ``sea_raft_encoders`` (default False; the same values and switching rules): on a SEA-RAFT model, replace its ``ResNetFPN`` encoders
+    `fnet` / `cnet` (BatchNorm folded, stem for the 3- and the 6-channel input) and `init_conv` by the kernels of sea_encoder.py.
+    They serve eval-mode fp32 GPU inference ("bf16": also inside cuda autocast to bfloat16); anything else keeps the model's modules."""
     sea_precision = _sea_precision(sea_raft_update)
+    sea_enc_precision = _sea_precision(sea_raft_encoders, "sea_raft_encoders")
     load_native()
     mod_name = type(model).__module__
     # registered classes (`class raft(RAFT)`) live in the same module as the implementation
@@ -581,6 +619,11 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
         if spec is not None:
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
+    if sea_enc_precision is not None:
+        _install_sea_encoders(model, sea_enc_precision)
+    if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):
+        # with both options the heads serve the iteration-0 prediction too (the split of `init_conv`'s output, sea_raft.py:189-197)
+        model.update_block.adopt_first_net = isinstance(getattr(model, "init_conv", None), PfkInitConv)
     hook = getattr(mod, "get_corr_block", None)
     if corr and hasattr(mod, _ORIG) and hasattr(hook, "channels_last"):      # (default for callers that are not a model's forward)
         hook.channels_last = sea or isinstance(getattr(model, "update_block", None), PfkUpdateBlock)

@@ -203,7 +203,7 @@ class SeaUpdateEngine(UpdateEngine):
             def put(src, dst):
                 self.ops.nchw_to_pm(src.contiguous(), dst)
         if net is not None:
-            put(net, self.act[:, : s.hidden])
+            self.stage_net(net)
         if inp is not None:
             put(inp, self.act[:, s.hidden: s.hidden + s.context])
         if flow.dtype == torch.float32:
@@ -215,6 +215,14 @@ class SeaUpdateEngine(UpdateEngine):
             return corr
         put(corr, self.corr16[:, : s.corr_channels])
         return self.corr16
+
+    def stage_net(self, net: torch.Tensor) -> None:
+        """`net` (any float NCHW) into the h slice of hx, or of hxb on the bf16 path"""
+        dst = self.act[:, : self.spec.hidden]
+        if self.b16:
+            self.nchw_view(dst).copy_(net.permute(0, 2, 3, 1))
+        else:
+            self.ops.nchw_to_pm(net.contiguous(), dst)
 
     def flow_head_out(self) -> None:
         """flow_head[2] (3x3, 256 -> 6) on the flow-head half of fm -> fo[:, :6]: delta flow (2) | info (4)"""
@@ -270,6 +278,8 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
         self._fm_for = None        # the `net` object whose flow_head[0] | upsample_weight[0] activation `fm` holds
         self._out_b16 = False      # bf16 path: the handed-out net is a bf16 view (an autocast loop), else an fp32 copy
         self.calls = 0             # kernel-path calls (tests count them)
+        self._adopted = None           # the net `adopt` staged last
+        self.adopt_first_net = False   # the heads also serve the iteration-0 net (`adopt`); set with `accelerate(sea_raft_encoders=)`
 
     def _all_params(self) -> Dict[str, torch.nn.Parameter]:
         P = dict(self.named_parameters())
@@ -305,6 +315,25 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
 
     def _params(self):
         return list(self.parameters()) + [p for m in self._heads.values() for p in m.parameters()]
+
+    def adopt(self, net: torch.Tensor) -> bool:
+        """Iteration 0 (sea_raft.py:189-197): the heads run on `net` before the block was ever called — the split of `init_conv`'s
+        output.  Stage it into the engine and treat it as handed out by this block, so the heads serve it from the engine's state and
+        the loop's first `forward(net, ...)` finds it staged already.  Only with `adopt_first_net` (`accelerate(sea_raft_encoders=)`)."""
+        s = self.spec
+        if not (self.adopt_first_net and net.dim() == 4 and net.shape[1] == s.hidden
+                and self.accepts((net,), self._params())):
+            return False
+        B, _, H, W = net.shape
+        with torch.no_grad():
+            eng = self._get_engine(net.device)
+            eng.bind(B, H, W)
+            eng.watch_faults()
+            eng.stage_net(net)
+        self._out_b16 = eng.b16 and (net.dtype == torch.bfloat16 or torch.is_autocast_enabled("cuda"))
+        self._last_out, self._last_version, self._fm_for = net, net._version, None
+        self._adopted = net
+        return True
 
     def forward(self, net, inp, corr, flow):
         s = self.spec
@@ -374,13 +403,17 @@ class _SeaHeadSeam(WrappedModule):
 
     def forward(self, x):
         blk = self._block[0]
-        if not (torch.is_tensor(x) and blk.owns(x) and blk.accepts((x,), list(self.parameters()))):
+        if not (torch.is_tensor(x) and (blk.owns(x) or blk.adopt(x)) and blk.accepts((x,), list(self.parameters()))):
             return self._ref[0](x)
         eng = blk.heads_fm(x)
         with torch.no_grad():
             if self.kind == "flow_head":
                 eng.flow_head_out()
                 out = eng.fo_nchw()            # fp32 on both paths
+                if blk._adopted is x:
+                    # iteration 0: the loop keeps this flow (`flow_8x = flow_update[:, :2]`, sea_raft.py:193) across the next
+                    # flow_head call, which overwrites the engine's buffer; later iterations add it to a tensor of their own
+                    out = out.clone()
             else:
                 eng.mask_logits(1.0)
                 # bf16 logits: a view for an autocast loop, an fp32 copy for an fp32 one

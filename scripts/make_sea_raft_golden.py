@@ -20,6 +20,13 @@ Inputs and outputs are stored, weights are not (tests/test_gpu_sea_raft.py regen
 runs the same step under torch.autocast("cpu", dtype=torch.bfloat16) and writes tests/golden/sea_raft_update_autocast.pt: the
 reference's own reduced-precision semantics (bf16 convolutions / Linear layers, fp32 LayerNorm, the dtype promotions of its cats and
 sums), which tests/test_sea_raft_bf16.py pins the torch restatement to.
+
+    python scripts/make_sea_raft_golden.py --encoder
+
+writes tests/golden/sea_raft_encoder.pt from the reference's own `ResNetFPN` (sea_raft/extractor.py): `resnet18` with 3 and with 6 input
+channels and `resnet34` with 3, parameters and running statistics from tests/sea_full_model.py `seeded_encoder_params` (seed
+ENC_SEED + variant index), one 3-channel and one 6-channel 64 x 96 input, each output in fp32 and under
+torch.autocast("cpu", dtype=torch.bfloat16).  Inputs and outputs only; the tests regenerate the weights from the seed.
 """
 from __future__ import annotations
 
@@ -39,6 +46,9 @@ SEED = 2024
 B, H, W = 1, 7, 8
 OUT = os.path.join(ROOT, "tests", "golden", "sea_raft_update.pt")
 OUT_AUTOCAST = os.path.join(ROOT, "tests", "golden", "sea_raft_update_autocast.pt")
+OUT_ENCODER = os.path.join(ROOT, "tests", "golden", "sea_raft_encoder.pt")
+ENC_SEED = 4100
+ENC_VARIANTS = (("resnet18", 3), ("resnet18", 6), ("resnet34", 3))       # (pretrain, input_dim); seed = ENC_SEED + index
 
 
 def main(autocast: bool = False) -> None:
@@ -71,5 +81,26 @@ def main(autocast: bool = False) -> None:
     print(f"wrote {out} ({os.path.getsize(out) / 1e6:.2f} MB)")
 
 
+def encoder() -> None:
+    from sea_full_model import seeded_encoder_params
+    ext = ref_loader.ref_module("ptlflow.models.sea_raft.extractor")
+    g = torch.Generator().manual_seed(ENC_SEED - 1)
+    data = {"seed": ENC_SEED, "variants": [list(v) for v in ENC_VARIANTS], "x3": torch.rand(1, 3, 64, 96, generator=g) * 2 - 1,
+            "x6": torch.rand(1, 6, 64, 96, generator=g) * 2 - 1}
+    for i, (pretrain, cin) in enumerate(ENC_VARIANTS):
+        enc = ext.ResNetFPN(block_dims=[64, 128, 256], initial_dim=64, pretrain=pretrain, input_dim=cin, output_dim=256).eval()
+        enc.load_state_dict(seeded_encoder_params({k: tuple(v.shape) for k, v in enc.state_dict().items()}, ENC_SEED + i), strict=True)
+        x = data[f"x{cin}"]
+        with torch.no_grad():
+            data[f"{pretrain}_{cin}"] = enc(x).contiguous()
+            with torch.autocast("cpu", dtype=torch.bfloat16):
+                data[f"{pretrain}_{cin}_autocast"] = enc(x).contiguous()     # bf16, as the module returns it
+    torch.save(data, OUT_ENCODER)
+    print(f"wrote {OUT_ENCODER} ({os.path.getsize(OUT_ENCODER) / 1e6:.2f} MB)")
+
+
 if __name__ == "__main__":
-    main("--autocast" in sys.argv[1:])
+    if "--encoder" in sys.argv[1:]:
+        encoder()
+    else:
+        main("--autocast" in sys.argv[1:])
