@@ -7,19 +7,23 @@
 // 16 * 2 * tiles * cin * cout flops instead of the direct form's 2 * 4 * tiles * 9 * cin * cout: 2.25x fewer fp32 products.
 //
 // U = G g G^T is made once per weight on the host (packing.pack_wino_weight: fp64, rounded to fp32 once).  Its layout is the LDS
-// image of one (64-channel column block, 8-channel K-step), 32 KB contiguous, so a block copies it with b128 loads:
+// image of one (64-channel column block, 8-channel K-step), 32 KB contiguous, so a block copies it as it is:
 //   weight[cb][ks][xi][nl (64)][slot (8)],  co = 64*cb + nl,  c = 8*ks + cc,
 //   slot = ((cc & 3) * 2 + (cc >> 2)) ^ (((nl >> 2) & 3) * 2)
 // (pad columns co >= cout are zero).  The slot order gives the MFMA lane (k = lane >> 4 of sub-step s = cc >> 2) both sub-steps'
 // values in one 8-byte read; the XOR with bits 2-3 of the row spreads the 16 rows a lane group reads over all banks, for both forms
-// the compiler emits (ds_read_b64: 32-lane groups, 64 banks; ds_read2st64_b64: 16-lane groups, 32 banks).  V in LDS uses the
-// same slot order with the tile as the row.
+// the compiler emits (ds_read_b64: 32-lane groups, 64 banks; ds_read2st64_b64: 16-lane groups, 32 banks; the main loop keeps the
+// two U reads of a component apart, as ds_read_b64).  V in LDS uses the same slot order with the tile as the row.
 //
 // Block = 32 consecutive 2x2 tiles (row-major over batch, tile row, tile column) x 64 output channels, 4 waves, each wave
 // 16 tiles x 32 channels with ALL 16 components in registers (16 x 2 accumulators of 16x16: 128 per lane).  K-step = 8 input
 // channels: each thread transforms one (tile, channel) — 16 dword buffer loads (out-of-image taps read zero through an
-// out-of-range offset: that zero is the padding), B^T d B on the VALU, 16 ds_write_b32 — and copies 128 B of U; the next
-// K-step's loads are in flight during the MFMAs.  48 KB LDS, <= 256 registers: two blocks per CU.
+// out-of-range offset: that zero is the padding), B^T d B on the VALU, 16 ds_write_b32.  U never passes through registers: the
+// packed image is copied by LDS-DMA (buffer_load ... lds, 8 pieces of 1 KB per wave and K-step) into one of two 32 KB buffers, so
+// the copy of K-step k + 1 lands while the MFMAs of k run.  Both the DMA pieces and the tap loads of k + 1 are issued BETWEEN the
+// MFMAs of k, one piece or two taps per component.  The barriers are raw s_barrier with explicit counted waits (a
+// __syncthreads() would drain the LDS-DMA in flight): vmcnt(0) + barrier before a buffer is read, lgkmcnt(0) + barrier before
+// sV and the other buffer are written again.  80 KB LDS, 188 registers: two blocks per CU, which fill its LDS.
 //
 // Epilogue: an MFMA 16x16 accumulator gives a lane four rows (tiles) of one column, at the same place in every component, so
 // A^T m A is lane-local; then PFK_EPI_LINEAR's bias, NaN-propagating relu, scale.  A column's K order and transforms do not
@@ -33,8 +37,11 @@ namespace {
 constexpr int WT = 32;   // 2x2 output tiles per block
 constexpr int WN = 64;   // output channels per block
 constexpr int WK = 8;    // input channels per K-step
+constexpr int UIMG = 16 * WN * WK;   // floats of one K-step of one column block's U: the LDS image, 32 KB
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) float lfloat;   // LDS pointers keep their address space (ds_ instructions, 32-bit)
+typedef __attribute__((address_space(3))) f32x2 lf32x2;
 
 struct WinoArgs {
   const float* src; int ld;      // pixel-major source, row stride in floats
@@ -57,26 +64,67 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }
 
-// One K-step's operands into registers: 16 input taps of this thread's (tile, channel), 128 B of the block's U image.
-// (a plain function rather than a lambda: by-reference captures can put register state in scratch, see pfk_gemm.hip)
-__device__ __forceinline__ void wino_load(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rw, const unsigned (&voff)[16],
-                                          unsigned wvoff, unsigned wk, int ks, float (&d)[16], f32x4 (&wr)[8]) {
+// Two of the 16 input taps of this thread's (tile, channel) of K-step ks into registers.
+// (plain functions rather than lambdas: by-reference captures can put register state in scratch, see pfk_gemm.hip)
+__device__ __forceinline__ void wino_load_v2(__amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[16], int ks, int q, float (&d)[16]) {
+  d[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff[q], ks * WK * 4, 0));
+  d[q + 1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff[q + 1], ks * WK * 4, 0));
+}
+
+// One of the 8 LDS-DMA pieces a wave copies of a K-step of the block's U (32 KB, already the LDS image) straight into LDS: 64 lanes x
+// 16 B to `dst` (wave-uniform) + 16 * lane.  No staging registers and no ds_write; the data is in LDS for every wave once each
+// wave's vmcnt has retired its pieces and a barrier has passed.
+__device__ __forceinline__ void wino_dma_u(__amdgpu_buffer_rsrc_t rw, lfloat* dst, unsigned wvoff, unsigned wk, int j) {
+#if defined(__HIP_DEVICE_COMPILE__)       // (the host pass of hipcc does not know the LDS-DMA builtin)
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, wvoff, wk + j * 4096u, 0, 0);
+#endif
+}
+
+// One K-step (8 channels) of the wave's 16 tiles x 32 columns, all 16 components.  aU1 = aU + 16 * WK through a register the
+// compiler cannot relate to aU: two ds_read_b64 (2 LDS cycles each) instead of one ds_read2st64_b64 (8).
+// `more`: the next K-step's operands are requested BETWEEN the MFMAs, where their issue cycles hide under the matrix pipe (in front of
+// the first MFMA, 8 LDS-DMA pieces and 16 loads are several hundred cycles in which this wave feeds it nothing): one U piece beside
+// each of the components 0-7, two taps beside each of 8-15.
+__device__ __forceinline__ void wino_mfma(const lfloat* aV, const lfloat* aU, const lfloat* aU1, f32x4 (&acc)[16][2], bool more,
+                                          __amdgpu_buffer_rsrc_t rw, lfloat* udst, unsigned wvoff, unsigned wk,
+                                          __amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[16], int ks, float (&d)[16]) {
+  // operands of component x + 1 are read while the MFMAs of x run (the LDS latency hides under the matrix pipe)
+  f32x2 va[2], u0[2], u1[2];
+  va[0] = *(const lf32x2*)(aV);
+  u0[0] = *(const lf32x2*)(aU);
+  u1[0] = *(const lf32x2*)(aU1);
+  __builtin_amdgcn_sched_barrier(0);   // (else the reads of component 0 are merged with component 1's into ds_read2st64_b64)
 #pragma unroll
-  for (int q = 0; q < 16; ++q)
-    d[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff[q], ks * WK * 4, 0));
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    wr[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wvoff, wk + j * 4096u, 0));
+  for (int x = 0; x < 16; ++x) {
+    const int c = x & 1, n = c ^ 1;
+    if (x + 1 < 16) {
+      va[n] = *(const lf32x2*)(aV + (x + 1) * WT * WK);
+      u0[n] = *(const lf32x2*)(aU + (x + 1) * WN * WK);
+      u1[n] = *(const lf32x2*)(aU1 + (x + 1) * WN * WK);
+    }
+    if (more) {
+      if (x < 8) wino_dma_u(rw, udst, wvoff, wk, x);
+      else wino_load_v2(rs, voff, ks, 2 * (x - 8), d);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc hoists the reads of x + 1 behind the MFMAs of x again)
+    acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u0[c][0], acc[x][0], 0, 0, 0);
+    acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u1[c][0], acc[x][1], 0, 0, 0);
+    acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u0[c][1], acc[x][0], 0, 0, 0);
+    acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u1[c][1], acc[x][1], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // RES: the residual-block epilogue of pfk_conv2d_wino_res_f32 (v = residual + v, then the block's last relu); the instantiation
 // without it is pfk_conv2d_wino_f32's kernel, unchanged.
 template <bool RES>
 __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoArgs a) {
-  __shared__ __attribute__((aligned(16))) float sV[16 * WT * WK];   // [xi][tile][slot]      16 KB
-  __shared__ __attribute__((aligned(16))) float sU[16 * WN * WK];   // [xi][column][slot]    32 KB
+  // (one array, U first) 2 x 32 KB of U + 16 KB of V: two blocks fill a CU's LDS
+  __shared__ __attribute__((aligned(16))) float smem[2 * UIMG + 16 * WT * WK];
+  lfloat* const sU = (lfloat*)smem;    // [buffer][xi][column][slot]
+  lfloat* const sV = sU + 2 * UIMG;    // [xi][tile][slot]
 
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int cb = blockIdx.x % a.ncb;
   const int t0 = (blockIdx.x / a.ncb) * WT;
 
@@ -101,17 +149,19 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
       }
   }
   const int vslot = ((cc & 3) * 2 + (cc >> 2)) ^ (((lt >> 2) & 3) * 2);
-  float* const vdst = sV + lt * WK + vslot;
-  const unsigned wvoff = (unsigned)tid * 16u;
-  const unsigned wbase = (unsigned)cb * (unsigned)a.nks * (16u * WN * WK * 4u);   // this column block's U
+  lfloat* const vdst = sV + lt * WK + vslot;
+  const unsigned wvoff = (unsigned)lane * 16u;
+  const unsigned wbase = (unsigned)cb * (unsigned)a.nks * (UIMG * 4u) + (unsigned)wid * 1024u;   // this column block's U, this wave's KB
+  lfloat* const udst = sU + wid * 256;                                                          // of each 4 KB component pair
 
   float d[16];
-  f32x4 wr[8];
   // ---- MFMA role: wave tile rows wt*16.., columns wc*32..
   const int wt = wid & 1, wc = wid >> 1;
   const int rl = lane & 15, kq = lane >> 4;
-  const float* const aV = sV + (wt * 16 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
-  const float* const aU = sU + (wc * 32 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
+  const lfloat* const aV = sV + (wt * 16 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
+  const lfloat* const aU = sU + (wc * 32 + rl) * WK + ((kq * 2) ^ (((rl >> 2) & 3) * 2));
+  const lfloat* aU1 = aU + 16 * WK;
+  asm volatile("" : "+v"(aU1));
 
   f32x4 acc[16][2];
 #pragma unroll
@@ -119,8 +169,11 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
 #pragma unroll
     for (int c = 0; c < 2; ++c) acc[x][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  constexpr unsigned KSTEP_BYTES = 16u * WN * WK * 4u;   // one K-step of one column block's U
-  wino_load(rs, rw, voff, wvoff, wbase, 0, d, wr);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    wino_dma_u(rw, udst, wvoff, wbase, j);
+    wino_load_v2(rs, voff, 0, 2 * j, d);
+  }
   for (int ks = 0; ks < a.nks; ++ks) {
     // V = B^T d B (rows, then columns), one channel of one tile
     float t[16];
@@ -138,31 +191,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
       vdst[(i * 4 + 2) * WT * WK] = t[i * 4 + 2] - t[i * 4 + 1];
       vdst[(i * 4 + 3) * WT * WK] = t[i * 4 + 1] - t[i * 4 + 3];
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(sU + j * 1024 + tid * 4) = wr[j];
-    __syncthreads();
-    if (ks + 1 < a.nks) wino_load(rs, rw, voff, wvoff, wbase + (unsigned)(ks + 1) * KSTEP_BYTES, ks + 1, d, wr);
-    // operands of component x + 1 are read while the MFMAs of x run (the LDS latency hides under the matrix pipe)
-    f32x2 va[2], u0[2], u1[2];
-    va[0] = *reinterpret_cast<const f32x2*>(aV);
-    u0[0] = *reinterpret_cast<const f32x2*>(aU);
-    u1[0] = *reinterpret_cast<const f32x2*>(aU + 16 * WK);
-#pragma unroll
-    for (int x = 0; x < 16; ++x) {
-      const int c = x & 1, n = c ^ 1;
-      if (x + 1 < 16) {
-        va[n] = *reinterpret_cast<const f32x2*>(aV + (x + 1) * WT * WK);
-        u0[n] = *reinterpret_cast<const f32x2*>(aU + (x + 1) * WN * WK);
-        u1[n] = *reinterpret_cast<const f32x2*>(aU + (x + 1) * WN * WK + 16 * WK);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc hoists the reads of x + 1 behind the MFMAs of x again)
-      acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u0[c][0], acc[x][0], 0, 0, 0);
-      acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u1[c][0], acc[x][1], 0, 0, 0);
-      acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u0[c][1], acc[x][0], 0, 0, 0);
-      acc[x][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][1], u1[c][1], acc[x][1], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
+    // this wave's U pieces of this K-step have landed and its V is written; the barrier extends both to every wave
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const int ub = (ks & 1) * UIMG;
+    // the next K-step's U goes to the other buffer, last read before the previous K-step's last barrier
+    wino_mfma(aV, aU + ub, aU1 + ub, acc, ks + 1 < a.nks, rw, udst + (UIMG - ub), wvoff, wbase + (unsigned)(ks + 1) * (UIMG * 4u), rs,
+              voff, ks + 1, d);
+    // a raw barrier: __syncthreads() would wait for the LDS-DMA in flight.  Every wave is done reading sV and this U buffer
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
 
   // ---- epilogue: lane holds tiles 4*kq + r (r = 0..3) of column rl in every component

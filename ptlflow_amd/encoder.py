@@ -8,6 +8,8 @@ RAFT descendants reuse it) and :197-267 (``SmallEncoder`` of raft_small: the sam
 * stem                     -> ``pfk_conv_stem_f32`` (reads the NCHW image)
 * 3x3 / 1x1, stride 1 / 2  -> ``pfk_conv2d_f32`` or ``pfk_conv2d_bf16s`` (implicit GEMM; bias, relu, residual add and the
   block's final relu fused in the epilogue)
+* fp32, 3x3 stride 1, large launches of BasicEncoder -> Winograd F(2x2,3x3): ``pfk_conv2d_wino_f32`` (in front of an instance
+  norm, and a folded-BatchNorm block's conv1) and ``pfk_conv2d_wino_res_f32`` (its conv2: + residual, relu), by ``WINO_MIN_PIXELS``
 * InstanceNorm             -> ``pfk_instnorm_stats_f32`` + ``pfk_norm_apply_f32`` (norm + relu + residual + relu)
 * BatchNorm (eval)         -> folded into the convolution's weights and bias at pack time (no kernel)
 
@@ -22,7 +24,7 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, eligible
-from .packing import pack_conv_weight, split_bf16_planes
+from .packing import pack_conv_weight, pack_wino_weight, split_bf16_planes
 from .update import CONV_PRECISIONS, EPI_LINEAR
 
 # (name, cin, cout, stride) of the six residual blocks, extractor.py:150-153
@@ -32,6 +34,10 @@ _BLOCKS = (("layer1.0", 64, 64, 1), ("layer1.1", 64, 64, 1), ("layer2.0", 64, 96
 _SMALL_BLOCKS = (("layer1.0", 32, 32, 1), ("layer1.1", 32, 32, 1), ("layer2.0", 32, 64, 2), ("layer2.1", 64, 64, 1),
                  ("layer3.0", 64, 96, 2), ("layer3.1", 96, 96, 1))
 EPS = 1e-5
+# Winograd rule of the fp32 BasicEncoder engine: width -> the fewest pixels (B * H * W of the launch) at which `pfk_conv2d_wino_f32` /
+# `pfk_conv2d_wino_res_f32` measured faster than `pfk_conv2d_f32` in both forms (scripts/wino_res_bench.py --encoder raft, table in
+# DESIGN.md §3 K9–K11, profiles/r08_a_winograd_lds_dma.md); a width or a size that was not measured keeps the direct kernel
+WINO_MIN_PIXELS: Dict[int, int] = {64: 218 * 512, 96: 109 * 256, 128: 2 * 55 * 128}     # 436 x 1024 frames: all it was measured on
 
 
 def _out(n: int, s: int) -> int:
@@ -56,6 +62,7 @@ class EncoderEngine:
         # included (statistics and normalisation in fp32 arithmetic on the bf16 rows, as F.instance_norm under autocast)
         self.b16 = conv_precision == "bf16"
         self._ws: Optional[torch.Tensor] = None
+        self.winograd = True       # False: the direct kernel everywhere (A/B timing, tests)
         self.max_matrix_bytes = 2 ** 31 - 1   # 32-bit byte offsets in the convolution kernels
         self.pack(params)
 
@@ -91,6 +98,11 @@ class EncoderEngine:
             for conv, nrm in convs:
                 w, b = self._fold(P, f"{name}.{conv}", f"{name}.{nrm}")
                 W[f"{name}.{conv}.w"], W[f"{name}.{conv}.b"] = self._pk(w), b
+                # fp32 BasicEncoder: the transformed weight of the Winograd kernels for the stride-1 3x3 convolutions `_use_wino` may
+                # select (after the BatchNorm fold)
+                if self.nsplit == 0 and not self.b16 and not self.small and (conv == "conv2" or stride == 1) \
+                        and w.shape[1] == cout and cout in WINO_MIN_PIXELS:
+                    W[f"{name}.{conv}.ww"] = pack_wino_weight(w.cpu()).to(self.device)
             if stride != 1:
                 w, b = self._fold(P, f"{name}.downsample.0", f"{name}.downsample.1")
                 W[f"{name}.ds.w"], W[f"{name}.ds.b"] = self._pk(w), b
@@ -114,6 +126,24 @@ class EncoderEngine:
         out = torch.empty(M, cout, device=self.device, dtype=torch.float32)
         self.ops.conv2d([x], B, H, W, k, k, self.w[key + ".w"], self.w[key + ".b"], cout, EPI_LINEAR, relu, 1.0, out,
                         None, None, None, None, residual, stride, relu2)
+        return out
+
+    def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
+        """Winograd F(2x2,3x3) for this stride-1 3x3 convolution: its transformed weight exists (fp32 BasicEncoder) and the launch is at
+        least as large as the smallest one measured faster than `pfk_conv2d_f32` at this width.  Launch shape only: B * H * W of
+        the launch.  A chunked forward (`max_matrix_bytes`) therefore has the whole-batch forward's bits only where every chunk falls
+        on the same side of the threshold as the whole batch (one image at 55 x 128 and width 128 is below it, two are not)."""
+        return self.winograd and (key + ".ww") in self.w and pixels >= WINO_MIN_PIXELS[cout]
+
+    def _conv3(self, x, B, H, W, key, cout, relu=False, residual=None):
+        """a block's stride-1 3x3 convolution: plain (in front of an instance norm), + relu (conv1), or + relu, + residual, relu (conv2)"""
+        if not self._use_wino(key, cout, B * H * W):
+            return self._conv(x, B, H, W, 3, key, cout, relu=relu, residual=residual, relu2=residual is not None)
+        out = torch.empty(B * H * W, cout, device=self.device, dtype=torch.float32)
+        if residual is None:
+            self.ops.conv2d_wino(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, relu, 1.0, out, 0)
+        else:
+            self.ops.conv2d_wino_res(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, relu, 1.0, out, residual, True)
         return out
 
     def _inorm(self, x, B, HW, relu, residual=None, relu2=False):
@@ -152,16 +182,19 @@ class EncoderEngine:
             return self._bottleneck(x, B, H, W, name, cout, stride)
         Ho, Wo = _out(H, stride), _out(W, stride)
         if self.norm == "instance":
-            y = self._inorm(self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride), B, Ho * Wo, relu=True)
-            y = self._conv(y, B, Ho, Wo, 3, f"{name}.conv2", cout)
+            y = self._conv3(x, B, H, W, f"{name}.conv1", cout) if stride == 1 else self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride)
+            y = self._inorm(y, B, Ho * Wo, relu=True)
+            y = self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout)
             if stride != 1:
                 x = self._inorm(self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride), B, Ho * Wo, relu=False)
             return self._inorm(y, B, Ho * Wo, relu=True, residual=x, relu2=True)
         act = True   # "batch" (folded) and "none": relu straight in the epilogue
-        y = self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride, relu=act)
-        if stride != 1:
+        if stride == 1:
+            y = self._conv3(x, B, H, W, f"{name}.conv1", cout, relu=act)
+        else:
+            y = self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride, relu=act)
             x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
-        return self._conv(y, B, Ho, Wo, 3, f"{name}.conv2", cout, relu=act, residual=x, relu2=True)
+        return self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout, relu=act, residual=x)
 
     @torch.no_grad()
     def __call__(self, img: torch.Tensor) -> torch.Tensor:

@@ -104,13 +104,13 @@ def small_spec(corr_levels: int = 4, corr_radius: int = 3) -> UpdateSpec:
 
 # Winograd rule (`_use_wino`): B*H*W x ceil(cout / 64) >= WINO_MIN_WORK, i.e. about 4 x 32 x the Winograd kernel's blocks (32 2x2
 # tiles x 64 channels each; two resident per CU on 256 CUs).  In isolation at 55x128 (scripts/wino_bench.py, MI355X, the direct
-# kernel with the engine's stream-K workspace, profiles/r07_a_winograd.md):
-#   batch 1 (7040 px):  fm (x 8 = 56320) 90.8 -> 56.2 us;  c2 (x 3 = 21120) 69.7 -> 65.1 us;  cv (x 2 = 14080) 51.0 -> 63.4 us
-#   batch 2 (14080 px): fm 162.2 -> 106.3 us;  c2 (42240) 117.2 -> 93.0 us;  cv (28160) 90.4 -> 68.8 us
-#   batch 8: fm 555.7 -> 337.8 us, c2 417.2 -> 268.7 us, cv 276.4 -> 181.5 us
-# Below 28160 the grid leaves most CUs idle and the direct kernel's stream-K schedule wins or ties (c2 at batch 1 gains 7 %, inside
-# what one box to the next moves, so the line is drawn above it).  The full launch's cout decides (a
-# `cout_active` launch takes the same kernel as its full form).
+# kernel with the engine's stream-K workspace, profiles/r08_a_winograd_lds_dma.md):
+#   batch 1 (7040 px):  fm (x 8 = 56320) 89.1 -> 51.2 us;  c2 (x 3 = 21120) 70.2 -> 54.6 us;  cv (x 2 = 14080) 50.6 -> 52.6 us
+#   batch 2 (14080 px): fm 161.8 -> 95.7 us;  c2 (42240) 120.4 -> 84.6 us;  cv (28160) 88.9 -> 58.3 us
+#   batch 8: fm 540.2 -> 292.7 us, c2 404.6 -> 231.4 us, cv 267.1 -> 157.5 us
+# Below 28160 the grid leaves most CUs idle: cv at batch 1 ties with the direct kernel's stream-K schedule, c2 at batch 1 gains 1.29x,
+# but at 21120 it sits on the lower bound that the engine test keeps for this value, so the line stays above both.  The full launch's
+# cout decides (a `cout_active` launch takes the same kernel as its full form).
 WINO_MIN_WORK = 28160
 
 # conv_precision -> number of bf16 planes per operand (0 = the fp32 matrix-core path, the default and the parity path)

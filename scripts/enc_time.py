@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Un-profiled wall time of the two encoders of the mirror (fnet on both frames, cnet on frame 1) at 436x1024, batch 1 and 8 (GPU box).
-(scripts/enc_prof.py gives the per-launch timeline through torch.profiler, whose clocks run lower.)"""
+(scripts/enc_prof.py gives the per-launch timeline through torch.profiler, whose clocks run lower.)
+
+    python scripts/enc_time.py [rounds]      # each round times the engines' Winograd rule on, then off (`EncoderEngine.winograd`)
+"""
 import os
 import sys
 import torch
@@ -9,6 +12,7 @@ from ptlflow_amd.raft import RAFT  # noqa: E402
 from ptlflow_amd.synth import smooth_pair  # noqa: E402
 
 dev = torch.device("cuda")
+rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 m = RAFT().load_synthetic(1234).eval().to(dev)
 
 
@@ -30,5 +34,9 @@ with torch.no_grad():
         i1, i2 = xp[:, 0].contiguous(), xp[:, 1].contiguous()
         both = torch.cat([i1, i2], 0)
         fnet, cnet = m.encoders(dev)
-        tf, tc = timeit(lambda: fnet(both)), timeit(lambda: cnet(i1))
-        print(f"encoders batch {B}: fnet ({2 * B} images) {tf:.3f} ms, cnet ({B} images) {tc:.3f} ms, together {tf + tc:.3f} ms", flush=True)
+        for rnd in range(rounds):
+            for wino in (True, False):
+                fnet.winograd = cnet.winograd = wino
+                tf, tc = timeit(lambda: fnet(both)), timeit(lambda: cnet(i1))
+                print(f"encoders batch {B} round {rnd + 1} winograd={wino}: fnet ({2 * B} images) {tf:.3f} ms, cnet ({B} images) {tc:.3f} ms, "
+                      f"together {tf + tc:.3f} ms", flush=True)

@@ -3,6 +3,8 @@ implicit GEMM (`pfk_conv2d_f32`) on ResNetFPN's shapes.
 
     python scripts/wino_res_bench.py [--out wino_res.json]
 
+    python scripts/wino_res_bench.py --encoder raft      # RAFT's BasicEncoder: 64 at 218 x 512, 96 at 109 x 256, 128 at 55 x 128
+
 Shapes: cin = cout = 64 at 220 x 512, 128 at 110 x 256, 256 at 55 x 128 (440 x 1024 frames), 1, 2, 8 and 16 images (one pair is one
 6-channel `cnet` pass of B images and two `fnet` passes of B images each).  Two forms per shape, as ResNetFPNEngine launches them: a
 block's conv1 (bias + relu) and its conv2 (bias + relu, + residual, relu).  Alternating in one process, median of `--reps` timings of 10
@@ -23,6 +25,8 @@ sys.path.insert(0, ROOT)
 
 LAUNCHES = 10
 SHAPES = ((64, 220, 512), (128, 110, 256), (256, 55, 128))
+# BasicEncoder (ptlflow_amd/encoder.py) on 436 x 1024 frames; 96 columns are padded to 128 by the Winograd kernel
+RAFT_SHAPES = ((64, 218, 512), (96, 109, 256), (128, 55, 128))
 
 
 def _time(fn):
@@ -39,6 +43,7 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--encoder", choices=("sea", "raft"), default="sea", help="whose shapes: ResNetFPN's or BasicEncoder's")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("wino_res_bench.py measures on the GPU; there is none")
@@ -49,7 +54,7 @@ def main() -> None:
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     rows = []
-    for C, H, W in SHAPES:
+    for C, H, W in (RAFT_SHAPES if args.encoder == "raft" else SHAPES):
         wt = torch.randn(C, C, 3, 3, generator=g) / (9 * C) ** 0.5
         wd = pack_conv_weight(wt, [(0, C, C)]).to(dev)
         ww = pack_wino_weight(wt).to(dev)
