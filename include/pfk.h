@@ -536,6 +536,21 @@ long long pfk_conv_wgrad_unpacked_workspace_bytes(const pfk_conv_desc* d, int wi
 int pfk_conv_wgrad_unpacked_f32(const pfk_conv_desc* d, const int* real_channels, const float* dy, int dy_ld, int cout_real,
                                 float* dw, float* db, int accumulate, void* workspace, long long workspace_bytes, pfk_stream_t stream);
 
+/* K12b — the same weight gradient on bf16 operands (v_mfma_f32_32x32x16_bf16, fp32 accumulation): the training form of
+ * pfk_conv2d_b16.  `d` describes the forward convolution (src / num_src / B / H / W / kh / kw / cout / stride; everything else is
+ * ignored): bf16 pixel-major sources as pfk_conv_src_b16 (ld and channels multiples of 8, 16-byte aligned); dy is bf16
+ * [B*H*W][dy_ld], dy_ld % 8 == 0, d->cout (dy's channel count) % 8 == 0, 8 <= d->cout.  Stride 1 only (d->stride 0 or 1) and
+ * kernels 1x1, 3x3, 1x5, 5x1: anything else is PFK_ERR_BAD_ARG, as are a NULL dw / workspace, a workspace that is too small and
+ * a row stride that is no multiple of 8.  Outputs are FP32, in PyTorch's layouts, exactly as pfk_conv_wgrad_unpacked_f32's:
+ * dw [cout_real][sum real_channels][kh][kw], db [cout_real] or NULL; `accumulate` adds into them.  The pixel range is cut into
+ * slices that are added in a fixed order (deterministic, no atomics) through `workspace`
+ * (pfk_conv_wgrad_unpacked_b16_workspace_bytes(d, db != NULL) bytes, 16-byte aligned, always required).  Byte offsets >= 2^31
+ * are refused (PFK_ERR_UNSUPPORTED). */
+long long pfk_conv_wgrad_unpacked_b16_workspace_bytes(const pfk_conv_b16_desc* d, int with_bias);
+int pfk_conv_wgrad_unpacked_b16(const pfk_conv_b16_desc* d, const int* real_channels, const void* dy, int dy_ld, int cout_real,
+                                float* dw, float* db, int accumulate, void* workspace, long long workspace_bytes, pfk_stream_t stream);
+int pfk_debug_set_wgrad_b16(int splits);   /* pixel slices of pfk_conv_wgrad_unpacked_b16: 0 = by occupancy, n > 0 = n slices (at most one per K-step, at most 64) */
+
 /* Gate arithmetic of one ConvGRU / SepConvGRU pass for the training path (raft/update.py:24-32, 58-73), pixel-major
  * [M][C] tensors, C % 4 == 0; z, r, rh, q, h_new, da_q, dh are contiguous [M][C], a_zr / da_zr contiguous [M][2C]
  * (z half first), h / dh_new have their own row stride.

@@ -44,6 +44,7 @@ HIP_SOURCES = [
     ("pfk_altcorr.hip", []),
     ("pfk_encoder.hip", []),
     ("pfk_wgrad.hip", []),
+    ("pfk_wgrad_b16.hip", []),                # K12b: weight gradient on bf16 operands, transposed LDS reads
     ("pfk_corr_bf16.hip", []),
     ("pfk_bwd.hip", ["-ffp-contract=off"]),   # same coordinate arithmetic as pfk_corr.hip (pfk_lookup.h)
     ("pfk_convnext.hip", []),                 # SEA-RAFT: depthwise conv + LayerNorm of the ConvNeXt block
@@ -117,7 +118,7 @@ def _run(cmd) -> None:
 
 def build_libpfk(force: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h"]
+    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h", CSRC / "pfk_wgrad_reduce.h"]
     tree = source_hash()
     objs, jobs = [], []
     for src, extra in HIP_SOURCES:

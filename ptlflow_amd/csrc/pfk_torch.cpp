@@ -901,6 +901,43 @@ void conv_wgrad_unpacked(at::TensorList srcs, const Tensor& dy, int64_t B, int64
                                        ws.data_ptr(), need, cur_stream()), "conv_wgrad_unpacked");
 }
 
+// K12b: the same on bf16 sources and a bf16 dy (pfk_conv_wgrad_unpacked_b16); dw / db stay fp32
+void conv_wgrad_unpacked_b16(at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, Tensor dw,
+                             const c10::optional<Tensor>& db, at::IntArrayRef reals, bool accumulate) {
+  OpScope scope(dy);
+  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3 && reals.size() == srcs.size(), "conv_wgrad_unpacked_b16: 1..3 sources, one real count each");
+  check_pm_b16(dy, "dy"); check_dev_f32(dw, "dw");
+  pfk_conv_b16_desc d{};
+  const int64_t M = B * H * W;
+  int real[3] = {0, 0, 0};
+  int64_t cin = 0;
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    check_pm_b16(srcs[i], "src");
+    TORCH_CHECK(srcs[i].size(0) == M, "conv_wgrad_unpacked_b16: src rows != B*H*W");
+    TORCH_CHECK(srcs[i].size(1) % 8 == 0 && srcs[i].stride(0) % 8 == 0, "conv_wgrad_unpacked_b16: src channels and row stride must be multiples of 8");
+    d.src[i].ptr = srcs[i].data_ptr(); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
+    real[i] = (int)reals[i];
+    cin += reals[i];
+  }
+  d.num_src = srcs.size();
+  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = dy.size(1); d.stride = 1;
+  TORCH_CHECK(dy.size(0) == M, "conv_wgrad_unpacked_b16: dy rows != B*H*W");
+  TORCH_CHECK(dy.size(1) % 8 == 0 && dy.stride(0) % 8 == 0, "conv_wgrad_unpacked_b16: dy channels and row stride must be multiples of 8");
+  TORCH_CHECK(dw.is_contiguous() && dw.dim() == 4 && dw.size(0) <= d.cout && dw.size(1) == cin && dw.size(2) == kh && dw.size(3) == kw,
+              "conv_wgrad_unpacked_b16: dw [cout, sum(reals), kh, kw] contiguous");
+  float* dbp = nullptr;
+  if (db.has_value()) {
+    check_dev_f32(*db, "db");
+    TORCH_CHECK(db->is_contiguous() && db->numel() == dw.size(0), "conv_wgrad_unpacked_b16: db [cout]");
+    dbp = fptr(*db);
+  }
+  const long long need = pfk_conv_wgrad_unpacked_b16_workspace_bytes(&d, dbp != nullptr);
+  TORCH_CHECK(need > 0, "conv_wgrad_unpacked_b16: unsupported shape (stride 1; 1x1, 3x3, 1x5, 5x1)");
+  Tensor ws = at::empty({(int64_t)need}, dy.options().dtype(at::kByte));
+  check_ok(pfk_conv_wgrad_unpacked_b16(&d, real, dy.data_ptr(), dy.stride(0), (int)dw.size(0), fptr(dw), dbp, accumulate ? 1 : 0,
+                                       ws.data_ptr(), need, cur_stream()), "conv_wgrad_unpacked_b16");
+}
+
 int64_t instnorm_workspace_bytes(int64_t B, int64_t C) { return pfk_instnorm_workspace_bytes((int)B, (int)C); }
 
 void instnorm_stats(const Tensor& x, int64_t B, int64_t HW, double eps, Tensor mean, Tensor rstd, Tensor workspace) {
@@ -1065,6 +1102,7 @@ int64_t conv_workspace_fault_offset() { return pfk_conv_workspace_fault_offset()
 void debug_set_tile(int64_t cfg) { check_ok(pfk_debug_set_tile((int)cfg), "debug_set_tile"); }
 void debug_set_lookup_pix(int64_t pix) { check_ok(pfk_debug_set_lookup_pix((int)pix), "debug_set_lookup_pix"); }
 void debug_set_wgrad(int64_t v) { check_ok(pfk_debug_set_wgrad((int)v), "debug_set_wgrad"); }
+void debug_set_wgrad_b16(int64_t v) { check_ok(pfk_debug_set_wgrad_b16((int)v), "debug_set_wgrad_b16"); }
 void debug_set_altcorr(int64_t v) { check_ok(pfk_debug_set_altcorr((int)v), "debug_set_altcorr"); }
 #ifndef PFK_SOURCE_HASH
 #define PFK_SOURCE_HASH "unstamped"
@@ -1084,6 +1122,7 @@ TORCH_LIBRARY(pfk, m) {
   m.def("gru_backward_zr(Tensor d_rh, Tensor h, Tensor r, Tensor(a!) da_zr, Tensor(b!) dh) -> ()");
   m.def("conv_wgrad(Tensor[] srcs, Tensor dy, int B, int H, int W, int kh, int kw, Tensor(a!) out, bool with_bias=False, int stride=1) -> ()");
   m.def("conv_wgrad_unpacked(Tensor[] srcs, Tensor dy, int B, int H, int W, int kh, int kw, Tensor(a!) dw, Tensor(b!)? db, int[] reals, int stride=1, bool accumulate=False) -> ()");
+  m.def("conv_wgrad_unpacked_b16(Tensor[] srcs, Tensor dy, int B, int H, int W, int kh, int kw, Tensor(a!) dw, Tensor(b!)? db, int[] reals, bool accumulate=False) -> ()");
   m.def("forward_interpolate(Tensor flow, Tensor(a!) out) -> ()");
   m.def("softmax_rows(Tensor(a!) x) -> ()");
   m.def("norm_bwd(Tensor x, Tensor dy, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) sum_g, Tensor(c!) sum_gxhat, int B, int HW, bool relu) -> ()");
@@ -1097,6 +1136,7 @@ TORCH_LIBRARY(pfk, m) {
   m.def("debug_set_tile(int cfg) -> ()", &debug_set_tile);
   m.def("debug_set_lookup_pix(int pix) -> ()", &debug_set_lookup_pix);
   m.def("debug_set_wgrad(int variant) -> ()", &debug_set_wgrad);
+  m.def("debug_set_wgrad_b16(int splits) -> ()", &debug_set_wgrad_b16);
   m.def("debug_set_altcorr(int mode) -> ()", &debug_set_altcorr);
   m.def("corr_volume(Tensor f1, Tensor f2, float scale, Tensor(a!) out) -> ()");
   m.def("corr_pool2x2(Tensor inp, Tensor(a!) out) -> ()");
@@ -1191,6 +1231,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("gru_backward_zr", &gru_backward_zr);
   m.impl("conv_wgrad", &conv_wgrad);
   m.impl("conv_wgrad_unpacked", &conv_wgrad_unpacked);
+  m.impl("conv_wgrad_unpacked_b16", &conv_wgrad_unpacked_b16);
   m.impl("forward_interpolate", &forward_interpolate);
   m.impl("softmax_rows", &softmax_rows);
   m.impl("norm_bwd", &norm_bwd);

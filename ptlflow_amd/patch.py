@@ -581,7 +581,7 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
-               sea_raft_update=False, sea_raft_encoders=False) -> torch.nn.Module:
+               sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32") -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -604,7 +604,14 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     second call with another value switches the installed seams.  ``conv_precision`` is not read by the SEA seams.
     ``sea_raft_encoders`` (default False; the same values and switching rules): on a SEA-RAFT model, replace its ``ResNetFPN`` encoders
     `fnet` / `cnet` (BatchNorm folded, stem for the 3- and the 6-channel input) and `init_conv` by the kernels of sea_encoder.py.
-    They serve eval-mode fp32 GPU inference ("bf16": also inside cuda autocast to bfloat16); anything else keeps the model's modules."""
+    They serve eval-mode fp32 GPU inference ("bf16": also inside cuda autocast to bfloat16); anything else keeps the model's modules.
+    ``train_precision`` ("fp32" default | "bf16"; anything else raises ValueError): precision of the update block's NATIVE TRAINING
+    path, the calls that carry a gradient graph (`PfkUpdateBlock.train_precision`).  "bf16" runs its convolutions — forward, data
+    and weight gradients — on the bf16 matrix cores (ptlflow_amd/train.py), as the reference does under
+    torch.autocast(bfloat16); hidden state, flow and parameter gradients stay fp32.  The conditions of the fp32 training path
+    apply unchanged (no GMA aggregate, 576 mask channels).  A second call with another value switches it."""
+    from .train import check_precision
+    check_precision(train_precision, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     sea_enc_precision = _sea_precision(sea_raft_encoders, "sea_raft_encoders")
     load_native()
@@ -618,6 +625,8 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
         spec = match_update_block(model.update_block)
         if spec is not None:
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
+    if update_block and isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
+        model.update_block.train_precision = train_precision
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
     if sea_enc_precision is not None:
         _install_sea_encoders(model, sea_enc_precision)

@@ -123,9 +123,16 @@ class RAFT(nn.Module):
     def __init__(self, corr_levels: int = 4, corr_radius: Optional[int] = None, iters: int = 32, small: bool = False,
                  upsample_every_iter: bool = True, conv_precision: str = "fp32", native_encoders: bool = True,
                  alternate_corr: bool = False, use_graph: bool = False, overlap_mask_head: bool = True,
-                 fork_branches: Optional[bool] = None, hoist_context: bool = True, fuse_mask_upsample: Optional[bool] = None):
+                 fork_branches: Optional[bool] = None, hoist_context: bool = True, fuse_mask_upsample: Optional[bool] = None,
+                 train_precision: str = "fp32"):
         super().__init__()
         self.small = small
+        # "fp32" (default) | "bf16": precision of the update block's convolutions in `_forward_train` — "bf16" is what the reference
+        # trains under torch.autocast(bfloat16): forward, data and weight gradients on the bf16 matrix cores (ptlflow_amd/train.py,
+        # DESIGN.md K12b); encoders, volume, lookup, upsampling, the hidden state and every parameter gradient stay fp32.
+        # (`conv_precision` below is about inference only.)
+        from .train import check_precision
+        self.train_precision = check_precision(train_precision, "train_precision")
         # The mask head's second convolution, the softmax over its nine taps and the convex upsampling (raft/update.py:152,
         # raft/raft.py:112-123) as ONE kernel that never writes the [M, 576] mask (`pfk_mask_upsample_f32`); bit-identical
         # to the two separate launches.  None: where it pays — fp32 convolutions from 28 160 pixels up (batch 8: 196 us against
@@ -304,7 +311,7 @@ class RAFT(nn.Module):
             fpm = (coords1 - coords0).permute(0, 2, 3, 1).reshape(M, 2)
             hpm, mask_pm, delta_pm = update_block_train_pm(P, self.spec, hpm, ipm, corr_pm, fpm, B, h, w, cache,
                                                            accumulate_wgrad=True,      # `cache` lives for this step only
-                                                           attention=attention)
+                                                           attention=attention, precision=self.train_precision)
             coords1 = coords1 + delta_pm.view(B, h, w, 2).permute(0, 3, 1, 2)
             flow = coords1 - coords0
             if mask_pm is not None:

@@ -16,6 +16,24 @@ arithmetic and its derivatives in four small kernels, ``pfk_gru_*``):
 
 Every MIOpen convolution of the update block's forward and backward is gone; the encoders, the correlation volume and
 the lookup keep the reference's autograd in training (their backward kernels are later rows).
+
+``precision="bf16"`` (K12b) — what the reference trains under ``torch.autocast(bfloat16)``: the same two nodes on the
+bf16 matrix cores.
+
+* forward   ``pfk_conv2d_b16`` LINEAR (relu fused), bf16 rows out; the saved activations are those bf16 rows
+* dgrad     ``pfk_conv2d_b16`` of the bf16-rounded gradient with the flipped, transposed weight slice (64-channel K chunks, bf16)
+* wgrad     ``pfk_conv_wgrad_unpacked_b16``: transposed LDS reads (``ds_read_b64_tr_b16``) feeding ``v_mfma_f32_32x32x16_bf16``;
+  fp32 dW / db in PyTorch's layouts, same step-scoped accumulation (`ConvPacks.acc`, `_Flush`)
+* GRU pass  pre-activations come out of ``pfk_conv2d_b16`` as fp32 rows, the gate arithmetic and its derivatives stay on the fp32
+  ``pfk_gru_*`` kernels, ``h`` stays fp32 with a bf16 copy as the convolutions' operand, ``r * h`` is rounded to bf16.
+
+Hidden state, coordinates, flow, loss, every parameter, every parameter gradient and every accumulator stay fp32.  Layers outside
+``pfk_conv2d_b16``'s envelope keep the fp32 node, with a cast at their boundary:
+
+* ``encoder.convf1`` (7x7 = 49 taps; K8b takes at most 32).
+
+No other layer of the basic / small update block is refused.  GMA's aggregate branch is not covered (``ValueError``), nor is a
+strided convolution (the update block has none).
 """
 from __future__ import annotations
 
@@ -39,11 +57,12 @@ def _segments(srcs: Sequence[torch.Tensor], real: Sequence[int]) -> List[Tuple[i
 
 
 class _Geometry:
-    """Input grid (B, H, W), kernel and stride of one convolution; the output grid is (Ho, Wo) = ((H-1)//stride + 1, ...)."""
-    __slots__ = ("B", "H", "W", "kh", "kw", "stride")
+    """Input grid (B, H, W), kernel and stride of one convolution; the output grid is (Ho, Wo) = ((H-1)//stride + 1, ...).
+    ``precision``: "fp32" | "bf16" | "bf16-f32out" — which kernels the `_ConvPM` node of this convolution runs on."""
+    __slots__ = ("B", "H", "W", "kh", "kw", "stride", "precision")
 
-    def __init__(self, B, H, W, kh, kw, stride=1):
-        self.B, self.H, self.W, self.kh, self.kw, self.stride = B, H, W, kh, kw, stride
+    def __init__(self, B, H, W, kh, kw, stride=1, precision="fp32"):
+        self.B, self.H, self.W, self.kh, self.kw, self.stride, self.precision = B, H, W, kh, kw, stride, precision
 
     @property
     def Ho(self):
@@ -140,6 +159,8 @@ class _ConvPM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight, bias, g: _Geometry, relu: bool, real: Tuple[int, ...], packs: ConvPacks, *srcs):
         ops = torch.ops.pfk
+        if g.precision != "fp32":
+            return _conv_forward_b16(ctx, weight, bias, g, relu, real, packs, g.precision, srcs)
         srcs = [s.contiguous() if s.stride(1) != 1 else s for s in srcs]
         cout = weight.shape[0]
         out = torch.empty(g.B * g.Ho * g.Wo, cout, device=srcs[0].device, dtype=torch.float32)
@@ -152,6 +173,8 @@ class _ConvPM(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         ops = torch.ops.pfk
+        if ctx.g.precision != "fp32":
+            return _conv_backward_b16(ctx, dY)
         weight, out, *srcs = ctx.saved_tensors
         g, real, packs = ctx.g, ctx.real, ctx.packs
         cout = weight.shape[0]
@@ -221,6 +244,122 @@ def _dgrad_pack(packs: ConvPacks, i: int, weight: torch.Tensor, seg, dy_channels
     return packs.dgrad[i]
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# precision="bf16": the same node on pfk_conv2d_b16 (forward, dgrad) and pfk_conv_wgrad_unpacked_b16 (wgrad)
+# --------------------------------------------------------------------------------------------------------------------
+PRECISIONS = ("fp32", "bf16")
+BF16 = torch.bfloat16
+
+
+def check_precision(precision: str, what: str = "precision") -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"{what} must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
+def _fwd_pack_b16(packs: ConvPacks, weight: torch.Tensor, segs, cout_buf: int) -> torch.Tensor:
+    """K8b's forward weight: bf16 [cout_buf, ktot], 64-channel K chunks; rows past cout (a 2-channel head padded to 8) are zero."""
+    if "fwd16" not in packs.extra:
+        w = weight.detach().float()
+        if cout_buf > w.shape[0]:
+            w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, cout_buf - w.shape[0]))
+        packs.extra["fwd16"] = pack_conv_weight(w, segs, kpad=64).to(BF16).contiguous()
+    return packs.extra["fwd16"]
+
+
+def dgrad_weight_b16(weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
+    """K8b weight of the data-gradient convolution w.r.t. one source: W[:, seg] with in / out swapped and the taps flipped,
+    bf16 [n_buf, taps * round_up(dy_channels, 64)] in K8b's K order (tap major, then dY's channels)."""
+    first, n, n_buf = seg
+    cout = weight.shape[0]
+    wt = weight.detach().float()[:, first:first + n].permute(1, 0, 2, 3).flip(2, 3)        # [n, cout, kh, kw]
+    if n_buf > n:
+        wt = F.pad(wt, (0, 0, 0, 0, 0, 0, 0, n_buf - n))                                   # padded channels: zero gradient
+    return pack_conv_weight(wt.contiguous(), [(0, cout, dy_channels)], kpad=64).to(BF16).contiguous()
+
+
+def _dgrad_pack_b16(packs: ConvPacks, i: int, weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
+    key = ("b16", i)
+    if key not in packs.dgrad:
+        packs.dgrad[key] = dgrad_weight_b16(weight, seg, dy_channels)
+    return packs.dgrad[key]
+
+
+def _rows_b16(s: torch.Tensor) -> torch.Tensor:
+    """bf16 rows with unit channel stride and a row stride that is a multiple of 8 (what the b16 kernels read)."""
+    s = s if s.dtype == BF16 else s.to(BF16)
+    if s.stride(1) != 1 or s.stride(0) % 8 or s.data_ptr() % 16:
+        s = s.contiguous()
+    return s
+
+
+def _conv_forward_b16(ctx, weight, bias, g, relu, real, packs, precision, srcs):
+    """sources: bf16 or fp32 rows [M, C_i], C_i % 8 == 0 (fp32 ones are rounded here: the cast at an fp32 layer's boundary);
+    out: bf16 rows (``precision == "bf16"``) or the fp32 accumulators as they are (``"bf16-f32out"``, the heads' last layers)."""
+    ops = torch.ops.pfk
+    if g.stride != 1:
+        raise ValueError("conv_pm(precision='bf16') covers stride 1 only")
+    if g.kh * g.kw > 32:
+        raise ValueError("conv_pm(precision='bf16'): pfk_conv2d_b16 takes at most 32 taps; keep this layer on precision='fp32'")
+    ctx.src_dtypes = tuple(s.dtype for s in srcs)
+    srcs = [_rows_b16(s) for s in srcs]
+    assert all(s.shape[1] % 8 == 0 for s in srcs), "bf16 sources need channel counts that are multiples of 8"
+    cout = weight.shape[0]
+    cout_buf = round_up(cout, 8)
+    out_dtype = torch.float32 if precision == "bf16-f32out" else BF16
+    buf = torch.empty(g.B * g.H * g.W, cout_buf, device=srcs[0].device, dtype=out_dtype)
+    b = None
+    if bias is not None:
+        b = bias.detach().float().contiguous()
+        b = b if cout_buf == cout else F.pad(b, (0, cout_buf - cout))
+    ops.conv2d_b16(list(srcs), g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(packs, weight, _segments(srcs, real), cout_buf), b, cout_buf,
+                   EPI_LINEAR, relu, 1.0, buf, None, None, None, None, None)
+    out = buf if cout_buf == cout else buf[:, :cout]
+    ctx.g, ctx.relu, ctx.real, ctx.has_bias, ctx.packs = g, relu, real, bias is not None, packs
+    ctx.save_for_backward(weight, out if relu else None, *srcs)
+    return out
+
+
+def _conv_backward_b16(ctx, dY):
+    ops = torch.ops.pfk
+    weight, out, *srcs = ctx.saved_tensors
+    g, real, packs = ctx.g, ctx.real, ctx.packs
+    cout = weight.shape[0]
+    M = g.B * g.H * g.W
+    dY = dY.to(BF16)          # what autocast's backward hands the convolution: the gradient of a 16-bit output
+    if ctx.relu:
+        dY = torch.ops.aten.threshold_backward(dY, out.to(BF16), 0.0)
+    dY = _rows_b16(dY if cout % 8 == 0 else F.pad(dY, (0, round_up(cout, 8) - cout)))
+    need = ctx.needs_input_grad      # (weight, bias, g, relu, real, packs, *srcs)
+    dW = db = None
+    dsrcs: List[Optional[torch.Tensor]] = [None] * len(srcs)
+    segs = _segments(srcs, real)
+    for i, seg in enumerate(segs):
+        if not need[6 + i]:
+            continue
+        dx = torch.empty(M, seg[2], device=dY.device, dtype=ctx.src_dtypes[i])     # fp32 for an fp32 source, bf16 rows otherwise
+        ops.conv2d_b16([dY], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack_b16(packs, i, weight, seg, dY.shape[1]), None, seg[2],
+                       EPI_LINEAR, False, 1.0, dx, None, None, None, None, None)
+        dsrcs[i] = dx
+    want_b = ctx.has_bias and need[1]
+    reals = [n for _, n, _ in segs]
+    if need[0] and packs.accumulate and packs.alias is not None:
+        first = packs.acc is None
+        if first:
+            packs.acc = {0: torch.empty(weight.shape, device=dY.device, dtype=torch.float32)}
+            if want_b:
+                packs.acc[1] = torch.empty(cout, device=dY.device, dtype=torch.float32)
+        ops.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, packs.acc[0], packs.acc.get(1), reals, not first)
+    elif need[0]:
+        dW = torch.empty(weight.shape, device=dY.device, dtype=torch.float32)
+        db = torch.empty(cout, device=dY.device, dtype=torch.float32) if want_b else None
+        ops.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, False)
+        dW = dW.to(weight.dtype)
+    elif want_b:
+        db = dY[:, :cout].float().sum(0)
+    return (dW, db, None, None, None, None, *dsrcs)
+
+
 def _unpack_wgrad(packed: torch.Tensor, weight_shape, segs, g: _Geometry) -> torch.Tensor:
     """packed [cout(+pad), ktot] (the forward weight's layout) -> PyTorch layout [cout, cin, kh, kw]."""
     cout = weight_shape[0]
@@ -244,11 +383,17 @@ class _GruPass(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, x, wz, wr, wq, bz, br, bq, g: _Geometry, x_real: int, pk_zr: ConvPacks, pk_q: ConvPacks,
-                pzr: Optional[torch.Tensor] = None, pq: Optional[torch.Tensor] = None):
+                pzr: Optional[torch.Tensor] = None, pq: Optional[torch.Tensor] = None, precision: str = "fp32"):
         """``pzr`` [M, 2C] / ``pq`` [M, C]: additive terms of the z|r and q pre-activations — the loop-invariant context part of
         the gate convolutions, computed once per step by the caller (`update_block_train_pm`); ``x`` / the weights then cover
-        the remaining input channels only.  Their gradient is the pre-activation gradient itself."""
+        the remaining input channels only.  Their gradient is the pre-activation gradient itself.
+
+        ``precision="bf16"``: ``x`` is bf16 rows (``Cx % 8 == 0``), ``h`` fp32; the four convolutions and the two weight
+        gradients run on bf16 operands, everything between them in fp32 (module docstring)."""
         ops = torch.ops.pfk
+        ctx.precision = precision
+        if precision != "fp32":
+            return _gru_forward_b16(ctx, h, x, wz, wr, wq, bz, br, bq, g, x_real, pk_zr, pk_q, pzr, pq)
         h = h.float().contiguous()
         x = x.float().contiguous()
         M, C = h.shape
@@ -277,6 +422,8 @@ class _GruPass(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dhn):
         ops = torch.ops.pfk
+        if ctx.precision != "fp32":
+            return _gru_backward_b16(ctx, dhn)
         h, x, z, r, q, rh, wq = ctx.saved_tensors
         g, x_real, pk_zr, pk_q, wzr = ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr
         M, C = h.shape
@@ -316,26 +463,118 @@ class _GruPass(torch.autograd.Function):
             ops.conv_wgrad_unpacked([rh, x], da_q, g.B, g.H, g.W, g.kh, g.kw, pk_q.acc[0], pk_q.acc[1], reals, 1, not first)
             ops.conv_wgrad_unpacked([h, x], da_zr, g.B, g.H, g.W, g.kh, g.kw, pk_zr.extra["dwzr"], pk_zr.extra["dbzr"], reals, 1, not first)
             return (dh, dx, None, None, None, None, None, None, None, None, None, None,
-                    da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None)
+                    da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None, None)
         dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
         ops.conv_wgrad_unpacked([rh, x], da_q, g.B, g.H, g.W, g.kh, g.kw, dwq, dbq, reals, 1)
         dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
         ops.conv_wgrad_unpacked([h, x], da_zr, g.B, g.H, g.W, g.kh, g.kw, dwzr, dbzr, reals, 1)
         return (dh, dx, dwzr[:C], dwzr[C:], dwq, dbzr[:C], dbzr[C:], dbq, None, None, None, None,
-                da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None)
+                da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None, None)
+
+
+def _gru_forward_b16(ctx, h, x, wz, wr, wq, bz, br, bq, g, x_real, pk_zr, pk_q, pzr, pq):
+    ops = torch.ops.pfk
+    h = h.float().contiguous()
+    x = _rows_b16(x)
+    M, C = h.shape
+    dev = h.device
+    assert C % 8 == 0 and x.shape[1] % 8 == 0
+    if "wzr" not in pk_zr.extra:      # once per (parameter version): the z and r convolutions run as one
+        pk_zr.extra["wzr"] = torch.cat([wz.detach(), wr.detach()], 0).float()
+        pk_zr.extra["bzr"] = torch.cat([bz.detach(), br.detach()], 0).float().contiguous()
+    wzr, bzr = pk_zr.extra["wzr"], pk_zr.extra["bzr"]
+    segs = [(0, C, C), (C, x_real, x.shape[1])]
+    hb = h.to(BF16)                    # the convolutions' operand; the state itself stays fp32
+
+    def res(p):
+        return None if p is None else (p.detach() if p.dtype == BF16 else p.detach().float()).contiguous()
+
+    a_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)       # fp32 pre-activations: the accumulators, unrounded
+    ops.conv2d_b16([hb, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(pk_zr, wzr, segs, 2 * C), bzr, 2 * C, EPI_LINEAR, False, 1.0,
+                   a_zr, None, None, None, None, res(pzr))
+    z, r, rh = (torch.empty(M, C, device=dev, dtype=torch.float32) for _ in range(3))
+    ops.gru_gates_zr(a_zr, h, z, r, rh)
+    rhb = rh.to(BF16)
+    a_q = torch.empty(M, C, device=dev, dtype=torch.float32)
+    ops.conv2d_b16([rhb, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(pk_q, wq, segs, C), bq.detach().float().contiguous(), C,
+                   EPI_LINEAR, False, 1.0, a_q, None, None, None, None, res(pq))
+    q, hn = torch.empty_like(a_q), torch.empty_like(a_q)
+    ops.gru_gates_q(a_q, z, h, q, hn)
+    ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr = g, x_real, pk_zr, pk_q, wzr
+    ctx.has_p = (pzr is not None, pq is not None)
+    ctx.p_dtypes = (None if pzr is None else pzr.dtype, None if pq is None else pq.dtype)
+    ctx.save_for_backward(h, x, z, r, q, rhb, wq)
+    return hn
+
+
+def _gru_backward_b16(ctx, dhn):
+    ops = torch.ops.pfk
+    h, x, z, r, q, rhb, wq = ctx.saved_tensors
+    g, x_real, pk_zr, pk_q, wzr = ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr
+    M, C = h.shape
+    Cx = x.shape[1]
+    dev = h.device
+    segs = [(0, C, C), (C, x_real, Cx)]
+    dhn = dhn.float()
+    if dhn.stride(1) != 1:
+        dhn = dhn.contiguous()
+    da_q = torch.empty(M, C, device=dev, dtype=torch.float32)
+    da_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)
+    dh = torch.empty(M, C, device=dev, dtype=torch.float32)
+    ops.gru_backward_q(dhn, z, q, h, da_q, da_zr, dh)
+
+    def dgrad(dy, packs, weight, i, n_out, residual=None):
+        out = torch.empty(M, n_out, device=dev, dtype=torch.float32)
+        ops.conv2d_b16([dy], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack_b16(packs, i, weight, segs[i], dy.shape[1]), None, n_out,
+                       EPI_LINEAR, False, 1.0, out, None, None, None, None, residual)
+        return out
+
+    da_qb = da_q.to(BF16)
+    d_rh = dgrad(da_qb, pk_q, wq, 0, C)
+    dx = dgrad(da_qb, pk_q, wq, 1, Cx)
+    ops.gru_backward_zr(d_rh, h, r, da_zr, dh)
+    da_zrb = da_zr.to(BF16)
+    dh = dgrad(da_zrb, pk_zr, wzr, 0, C, residual=dh)          # + dh through the epilogue's fp32 residual input
+    dx = dgrad(da_zrb, pk_zr, wzr, 1, Cx, residual=dx).to(x.dtype)
+    hb = h.to(BF16)
+    reals = [n for _, n, _ in segs]
+    gp = (None if not ctx.has_p[0] else da_zr.to(ctx.p_dtypes[0]), None if not ctx.has_p[1] else da_q.to(ctx.p_dtypes[1]))
+    if pk_zr.accumulate and pk_zr.alias is not None and pk_q.alias is not None:
+        first = pk_q.acc is None
+        if first:
+            dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+            dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
+            pk_q.acc = {0: dwq, 1: dbq}
+            pk_zr.extra["dwzr"], pk_zr.extra["dbzr"] = dwzr, dbzr
+            pk_zr.acc = {0: dwzr[:C], 1: dwzr[C:], 2: dbzr[:C], 3: dbzr[C:]}      # (wz, wr, bz, br) as given to _Flush
+        ops.conv_wgrad_unpacked_b16([rhb, x], da_qb, g.B, g.H, g.W, g.kh, g.kw, pk_q.acc[0], pk_q.acc[1], reals, not first)
+        ops.conv_wgrad_unpacked_b16([hb, x], da_zrb, g.B, g.H, g.W, g.kh, g.kw, pk_zr.extra["dwzr"], pk_zr.extra["dbzr"], reals, not first)
+        return (dh, dx, None, None, None, None, None, None, None, None, None, None, gp[0], gp[1], None)
+    dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
+    ops.conv_wgrad_unpacked_b16([rhb, x], da_qb, g.B, g.H, g.W, g.kh, g.kw, dwq, dbq, reals, False)
+    dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
+    ops.conv_wgrad_unpacked_b16([hb, x], da_zrb, g.B, g.H, g.W, g.kh, g.kw, dwzr, dbzr, reals, False)
+    return (dh, dx, dwzr[:C], dwzr[C:], dwq, dbzr[:C], dbzr[C:], dbq, None, None, None, None, gp[0], gp[1], None)
 
 
 def conv_pm(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, H: int, W: int,
             relu: bool = False, real: Optional[Sequence[int]] = None, packs: Optional[ConvPacks] = None,
-            stride: int = 1) -> torch.Tensor:
+            stride: int = 1, precision: str = "fp32", out_fp32: bool = False) -> torch.Tensor:
     """Differentiable convolution (odd kernel, padding k//2, stride s: PyTorch's Conv2d(k, stride=s, padding=k//2)) of the
     channel-concatenation of ``srcs`` (pixel-major ``[B*H*W, C_i]``, ``C_i % 4 == 0``) with a PyTorch-layout weight
     ``[cout, sum(real), kh, kw]``; returns ``[B*Ho*Wo, cout]``.  ``packs``: a ``ConvPacks`` from ``packs_for`` to reuse the
-    packed weights across calls."""
+    packed weights across calls.
+
+    ``precision="bf16"``: the node on the bf16 matrix cores (module docstring) — stride 1, at most 32 taps, ``C_i % 8 == 0``;
+    sources may be bf16 or fp32 rows (their gradient comes back in their dtype), the result is bf16 rows, or with ``out_fp32``
+    the fp32 accumulators unrounded (the incoming gradient is rounded to bf16 either way); weight / bias gradients are fp32."""
     load_native()
+    check_precision(precision)
     real = tuple(int(s.shape[1]) for s in srcs) if real is None else tuple(real)
     assert sum(real) == weight.shape[1], (real, tuple(weight.shape))
-    g = _Geometry(B, H, W, weight.shape[2], weight.shape[3], int(stride))
+    if precision == "bf16" and out_fp32:
+        precision = "bf16-f32out"
+    g = _Geometry(B, H, W, weight.shape[2], weight.shape[3], int(stride), precision)
     packs = packs if packs is not None else ConvPacks()
     weight, bias = step_params(packs, weight, bias)
     return _ConvPM.apply(weight, bias, g, relu, real, packs, *srcs)
@@ -358,8 +597,13 @@ def _pad4(x: torch.Tensor) -> torch.Tensor:
     return x if c % 4 == 0 else F.pad(x, (0, round_up(c, 4) - c))
 
 
+def _pad8(x: torch.Tensor) -> torch.Tensor:
+    c = x.shape[1]
+    return x if c % 8 == 0 else F.pad(x, (0, round_up(c, 8) - c))
+
+
 def _context_terms(P: Dict[str, torch.Tensor], spec, i: torch.Tensor, B: int, H: int, W: int, cache: dict, owner: torch.Tensor,
-                   acc: bool):
+                   acc: bool, precision: str = "fp32"):
     """The loop-invariant part of the GRU (raft/update.py:60-71 / :27-30): the gate convolutions run over cat([h, inp, motion])
     and `inp` — the context features — is the same tensor in every iteration, so conv(W[:, inp slice], inp) is computed ONCE per
     training step (forward, data and weight gradient alike: autograd sums the twelve pre-activation gradients and runs one
@@ -377,8 +621,9 @@ def _context_terms(P: Dict[str, torch.Tensor], spec, i: torch.Tensor, B: int, H:
         rest = [torch.cat([w[:, :Ch], w[:, Ch + Ci:]], 1).contiguous() for w in ws]       # autograd routes the gradients back
         wc = [w[:, Ch:Ch + Ci].contiguous() for w in ws]
         wzr_c = torch.cat([wc[0], wc[1]], 0)
-        pzr = conv_pm([i], wzr_c, None, B, H, W, False, None, packs_for(cache, "zrc" + sfx, [wzr_c], acc))
-        pq = conv_pm([i], wc[2], None, B, H, W, False, None, packs_for(cache, "qc" + sfx, [wc[2]], acc))
+        # (bf16: the terms stay fp32 — they are added to the fp32 pre-activations through the epilogue's residual input)
+        pzr = conv_pm([i], wzr_c, None, B, H, W, False, None, packs_for(cache, "zrc" + sfx, [wzr_c], acc), 1, precision, True)
+        pq = conv_pm([i], wc[2], None, B, H, W, False, None, packs_for(cache, "qc" + sfx, [wc[2]], acc), 1, precision, True)
         out[sfx] = (rest[0], rest[1], rest[2], pzr, pq)
     cache["ctx"] = (weakref.ref(owner), owner._version, out)
     return out
@@ -386,23 +631,28 @@ def _context_terms(P: Dict[str, torch.Tensor], spec, i: torch.Tensor, B: int, H:
 
 def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, H: int, W: int, cache: Optional[dict] = None,
                           accumulate_wgrad: bool = False, attention: Optional[torch.Tensor] = None, hoist_context: bool = True,
-                          context_owner: Optional[torch.Tensor] = None):
+                          context_owner: Optional[torch.Tensor] = None, precision: str = "fp32"):
     """BasicUpdateBlock.forward / SmallUpdateBlock.forward (update.py:144-153 / :122-128) with every convolution on
     ``conv_pm``, on pixel-major tensors: ``h`` [M, Ch], ``i`` [M, Ci], ``c`` [M, corr channels], ``f`` [M, 2] ->
     ``(h', mask [M, 576] | None, delta [M, 2])``.  ``P``: the block's named parameters; ``cache``: a dict that keeps the packed
     weights between the recurrent calls of one training step.  ``accumulate_wgrad`` (only with a ``cache`` that is created per
-    step): the recurrent calls add their weight gradients into one buffer per parameter (`ConvPacks.acc`, `_Flush`)."""
+    step): the recurrent calls add their weight gradients into one buffer per parameter (`ConvPacks.acc`, `_Flush`).
+    ``precision="bf16"``: the convolutions on the bf16 matrix cores (module docstring); inputs and outputs stay fp32 rows."""
     acc = accumulate_wgrad and cache is not None
+    b16 = check_precision(precision) == "bf16"
+    if b16 and spec.aggregate:
+        raise ValueError("update_block_train_pm(precision='bf16') does not cover GMA's aggregate branch")
+    pad = _pad8 if b16 else _pad4
 
-    def conv(srcs, name, relu=False, real=None):
+    def conv(srcs, name, relu=False, real=None, prec=precision, out_fp32=False):
         w = P[name + ".weight"]
-        return conv_pm(srcs, w, P.get(name + ".bias"), B, H, W, relu, real, packs_for(cache, name, [w], acc))
+        return conv_pm(srcs, w, P.get(name + ".bias"), B, H, W, relu, real, packs_for(cache, name, [w], acc), 1, prec, out_fp32)
 
     # motion encoder (update.py:104-112 / :85-91)
-    cor = conv([_pad4(c)], "encoder.convc1", True, [c.shape[1]])
+    cor = conv([pad(c)], "encoder.convc1", True, [c.shape[1]])
     if spec.c2:
         cor = conv([cor], "encoder.convc2", True)
-    flo = conv([_pad4(f)], "encoder.convf1", True, [2])
+    flo = conv([_pad4(f)], "encoder.convf1", True, [2], "fp32")      # 7x7: outside pfk_conv2d_b16's 32 taps, fp32 in either mode
     flo = conv([flo], "encoder.convf2", True)
     out = conv([cor, flo], "encoder.conv", True)
     # x = [inp | motion features (encoder out | flow) | zero pad to a multiple of 4] in ONE concatenation (update.py:112 + :146);
@@ -410,7 +660,8 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
     # (step-scoped caches only — `accumulate_wgrad`, the mirror's training forward: a cache that outlives the step would hand the
     #  next forward derived tensors whose autograd graph the previous backward has already freed)
     hoist = hoist_context and acc
-    ctx_terms = _context_terms(P, spec, i, B, H, W, cache, i if context_owner is None else context_owner, acc) if hoist else None
+    ctx_terms = (_context_terms(P, spec, i, B, H, W, cache, i if context_owner is None else context_owner, acc, precision)
+                 if hoist else None)
     x_real = spec.x_channels - (spec.context if hoist else 0)
     parts = [out, f] if hoist else [i, out, f]
     if spec.aggregate:
@@ -419,15 +670,16 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
         N = H * W
         agg = torch.bmm(attention.reshape(B, N, N).float(), v.view(B, N, v.shape[1])).reshape(B * N, v.shape[1])
         parts = [mf, mf + P["aggregator.gamma"] * agg] if hoist else [i, mf, mf + P["aggregator.gamma"] * agg]
-    if x_real % 4:
-        zkey = ("zpad", i.shape[0], round_up(x_real, 4) - x_real, i.device)
+    xq = 8 if b16 else 4
+    if x_real % xq:
+        zkey = ("zpad", i.shape[0], round_up(x_real, xq) - x_real, i.device)
         z = cache.get(zkey) if cache is not None else None
         if z is None:
-            z = torch.zeros(i.shape[0], round_up(x_real, 4) - x_real, device=i.device, dtype=torch.float32)
+            z = torch.zeros(i.shape[0], round_up(x_real, xq) - x_real, device=i.device, dtype=torch.float32)
             if cache is not None:
                 cache[zkey] = z
         parts.append(z)
-    x = torch.cat(parts, 1)
+    x = torch.cat([t.to(BF16) for t in parts], 1) if b16 else torch.cat(parts, 1)
     # GRU passes (update.py:58-73 / :24-32): one fused autograd node per pass (z and r share a convolution)
     for kh, kw, sfx in spec.gru_passes:
         names = [f"gru.conv{k}{sfx}" for k in "zrq"]
@@ -440,20 +692,22 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
         pk_q = packs_for(cache, "q" + sfx, [wq], acc)
         wz, wr, bz, br = step_params(pk_zr, wz, wr, bz, br)
         wq, bq = step_params(pk_q, wq, bq)
-        h = _GruPass.apply(h, x, wz, wr, wq, bz, br, bq, _Geometry(B, H, W, kh, kw), x_real, pk_zr, pk_q, pzr, pq)
-    # heads (update.py:6-14, 138-142, 152)
-    delta = conv([conv([h], "flow_head.conv1", True)], "flow_head.conv2")
+        h = _GruPass.apply(h, x, wz, wr, wq, bz, br, bq, _Geometry(B, H, W, kh, kw), x_real, pk_zr, pk_q, pzr, pq, precision)
+    # heads (update.py:6-14, 138-142, 152); bf16: the last layers hand their fp32 accumulators on (flow and mask stay fp32)
+    delta = conv([conv([h], "flow_head.conv1", True)], "flow_head.conv2", out_fp32=b16)
     mask = None
     if spec.has_mask:
-        mask = 0.25 * conv([conv([h], "mask.0", True)], "mask.2")
+        mask = 0.25 * conv([conv([h], "mask.0", True)], "mask.2", out_fp32=b16)
     return h, mask, delta
 
 
-def update_block_train(P: Dict[str, torch.Tensor], spec, net, inp, corr, flow, cache: Optional[dict] = None):
+def update_block_train(P: Dict[str, torch.Tensor], spec, net, inp, corr, flow, cache: Optional[dict] = None,
+                       precision: str = "fp32"):
     """NCHW face of `update_block_train_pm` (what `PfkUpdateBlock` calls from the reference's loop):
     NCHW in, NCHW out: ``(net, mask | None, delta_flow)``."""
     B, _, H, W = net.shape
-    h, mask, delta = update_block_train_pm(P, spec, _pm(net), _pm(inp), _pm(corr), _pm(flow), B, H, W, cache, context_owner=inp)
+    h, mask, delta = update_block_train_pm(P, spec, _pm(net), _pm(inp), _pm(corr), _pm(flow), B, H, W, cache, context_owner=inp,
+                                           precision=precision)
     return _nchw(h, B, H, W), (None if mask is None else _nchw(mask, B, H, W)), _nchw(delta, B, H, W)
 
 

@@ -760,6 +760,8 @@ class PfkUpdateBlock(WrappedModule):
         super().__init__(ref_block)
         self.conv_precision = conv_precision
         self.native_backward = True   # False: calls that need a gradient graph go to the wrapped reference module
+        # "fp32" | "bf16": precision of the native training path's convolutions (ptlflow_amd/train.py; `accelerate(train_precision=)`)
+        self.train_precision = "fp32"
         self._train_cache: dict = {}  # packed weights of the training path, keyed by parameter versions
         self.spec = spec
         self._inp_ref, self._inp_version = None, -1      # strong references: the address cannot be recycled while cached
@@ -790,11 +792,13 @@ class PfkUpdateBlock(WrappedModule):
         if torch.is_grad_enabled() and (net.requires_grad or any(p.requires_grad for p in self.parameters())):
             # training graph: every convolution forward / dgrad / wgrad on the MFMA kernel through the
             # differentiable composition of ptlflow_amd/train.py; GMA's aggregate branch, CPU tensors and split-bf16
-            # modes keep the reference module's own autograd
-            if (self.native_backward and net.is_cuda and not self.spec.aggregate and self.conv_precision == "fp32"
-                    and self.spec.mask_channels == 576):
+            # modes keep the reference module's own autograd.  train_precision "bf16" puts the composition on the bf16 matrix
+            # cores whatever the inference precision is.
+            if (self.native_backward and net.is_cuda and not self.spec.aggregate and self.spec.mask_channels == 576
+                    and (self.conv_precision == "fp32" or self.train_precision == "bf16")):
                 from .train import update_block_train
-                h, mask, delta = update_block_train(dict(self.named_parameters()), self.spec, net, inp, corr, flow, self._train_cache)
+                h, mask, delta = update_block_train(dict(self.named_parameters()), self.spec, net, inp, corr, flow, self._train_cache,
+                                                    self.train_precision)
                 return h.to(net.dtype), (None if mask is None else mask.to(net.dtype)), delta.to(net.dtype)
             return self._ref[0](net, inp, corr, flow, *extra, **kw)
         with torch.no_grad():
