@@ -628,6 +628,28 @@ int pfk_instnorm_stats_b16(const void* x_bf16, int ld, int B, int HW, int C, flo
  * `sim.softmax(dim=-1)`, once per forward; the similarity itself is pfk_corr_volume_f32 of the q / k maps). */
 int pfk_softmax_rows_f32(float* x, long long rows, int cols, long long ld, pfk_stream_t stream);
 
+/* ---- training of GMA's attention (K12c, ABI 7 additions) ----------------------------------------------------------
+ * Backward of pfk_softmax_rows_f32: p fp32 [rows][ld_p] (the softmax OUTPUT, cols entries used), dp [rows][ld_dp] fp32 or bf16 ->
+ *   ds[r][j] = p[r][j] * (dp[r][j] - sum_k dp[r][k] * p[r][k])    j < cols,      ds[r][j] = 0    cols <= j < ld_out
+ * fp32 rows [rows][ld_out]: with ld_out % 4 == 0 a legal dC operand of pfk_corr_volume_bwd_f32.  One block per row, the row sum
+ * in fp32 in a fixed order (deterministic).  _f32: ds may be dp itself (then ld_out == ld_dp).  _bf16: dp_bf16 16-byte aligned,
+ * ld_dp % 8 == 0 (PFK_ERR_ALIGNMENT otherwise).  Every ld >= cols (PFK_ERR_BAD_ARG otherwise).  Aliasing: only ds == dp exactly is
+ * recognised (and refused unless fp32 with ld_out == ld_dp); ds overlapping dp in any other way, or overlapping p, is the caller's
+ * error and is NOT detected. */
+int pfk_softmax_rows_bwd_f32(const float* p, long long ld_p, const float* dp, long long ld_dp, float* ds, long long ld_out,
+                             long long rows, int cols, pfk_stream_t stream);
+int pfk_softmax_rows_bwd_bf16(const float* p, long long ld_p, const void* dp_bf16, long long ld_dp, float* ds, long long ld_out,
+                              long long rows, int cols, pfk_stream_t stream);
+/* Batched square map in [B][N][ld_in] fp32 -> outT [B][N][ld_out] with outT[b][j][i] = in[b][i][j] and, when `out` != NULL, in the
+ * same pass out[b][i][j] = in[b][i][j] at the same row stride; columns [N, ld_out) of both are written as zero.  _f32 copies the
+ * bits, _b16 rounds to bf16 (nearest even; outputs 16-byte aligned, ld_out % 8 == 0, PFK_ERR_ALIGNMENT otherwise).  64 x 64 tiles
+ * through LDS: reads and writes are both along rows.  The operands of GMA's aggregate in training: out = the A operand of
+ * attn @ v, outT = the A operand of dV = attn^T @ dAgg (pfk_conv2d_f32 / the batched pfk_conv2d_b16). */
+int pfk_transpose_pack_f32(const float* in, long long ld_in, float* outT, float* out, long long ld_out, int B, int N,
+                           pfk_stream_t stream);
+int pfk_transpose_pack_b16(const float* in, long long ld_in, void* outT_bf16, void* out_bf16, long long ld_out, int B, int N,
+                           pfk_stream_t stream);
+
 /* ---- encoder backward (training, BASELINE config 5) ---------------------------------------------------------------
  * Backward of y = relu?((x - mean) * rstd) with per-(image, channel) statistics (pfk_instnorm_stats_f32): instance norm,
  * and batch norm in training mode when called with B = 1 and HW = all pixels of the batch (torch.autograd of

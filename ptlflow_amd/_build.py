@@ -41,6 +41,7 @@ HIP_SOURCES = [
     ("pfk_wino.hip", []),                     # Winograd F(2x2,3x3) for the update block's 3x3 convolutions
     ("pfk_corr.hip", ["-ffp-contract=off"]),  # index-exact coordinate arithmetic
     ("pfk_misc.hip", ["-ffp-contract=off"]),
+    ("pfk_attn.hip", ["-ffp-contract=off"]),  # K12c: softmax backward, transposed packs of GMA's attention map
     ("pfk_altcorr.hip", []),
     ("pfk_encoder.hip", []),
     ("pfk_wgrad.hip", []),

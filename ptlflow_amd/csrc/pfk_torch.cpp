@@ -1029,6 +1029,47 @@ void softmax_rows(Tensor x) {
   check_ok(pfk_softmax_rows_f32(fptr(x), rows, (int)cols, cols, cur_stream()), "softmax_rows");
 }
 
+// backward of softmax_rows: p, dp [rows, cols] views with contiguous columns (dp float32 or bfloat16), ds [rows, ld_out] contiguous
+// float32 (columns >= cols come out zero); ds may be the buffer dp is a view of (float32, same row stride)
+void softmax_rows_bwd(const Tensor& p, const Tensor& dp, Tensor ds) {
+  OpScope scope(p);
+  check_pm(p, "p"); check_dev_f32(ds, "ds");
+  const bool b16 = check_pm_any(dp, "dp");
+  TORCH_CHECK(ds.dim() == 2 && ds.is_contiguous(), "softmax_rows_bwd: ds must be contiguous [rows, ld_out]");
+  const int64_t rows = p.size(0), cols = p.size(1);
+  TORCH_CHECK(rows > 0 && cols > 0 && dp.size(0) == rows && dp.size(1) == cols && ds.size(0) == rows && ds.size(1) >= cols,
+              "softmax_rows_bwd: p, dp [rows, cols], ds [rows, ld_out >= cols]");
+  if (b16) check_ok(pfk_softmax_rows_bwd_bf16(fptr(p), p.stride(0), dp.data_ptr(), dp.stride(0), fptr(ds), ds.size(1), rows, (int)cols, cur_stream()),
+                    "softmax_rows_bwd (bf16)");
+  else check_ok(pfk_softmax_rows_bwd_f32(fptr(p), p.stride(0), fptr(dp), dp.stride(0), fptr(ds), ds.size(1), rows, (int)cols, cur_stream()),
+                "softmax_rows_bwd");
+}
+
+// inp [B, N, N] float32 (row stride inp.stride(1), batches N rows apart) -> outT [B, N, ld_out] = its transpose, out (optional, same
+// shape) = its copy; float32 or bfloat16, contiguous, pad columns zero
+void transpose_pack(const Tensor& inp, Tensor outT, const c10::optional<Tensor>& out) {
+  OpScope scope(inp);
+  check_dev_f32(inp, "inp"); check_dev(outT, "outT");
+  TORCH_CHECK(inp.dim() == 3 && inp.size(1) == inp.size(2) && inp.stride(2) == 1 && inp.stride(0) == inp.size(1) * inp.stride(1),
+              "transpose_pack: inp [B, N, N] with contiguous columns and batches N rows apart");
+  const int64_t B = inp.size(0), N = inp.size(1);
+  const bool b16 = outT.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(b16 || outT.scalar_type() == at::kFloat, "transpose_pack: outT must be float32 or bfloat16");
+  TORCH_CHECK(outT.dim() == 3 && outT.is_contiguous() && outT.size(0) == B && outT.size(1) == N && outT.size(2) >= N,
+              "transpose_pack: outT [B, N, ld_out >= N] contiguous");
+  void* o = nullptr;
+  if (out.has_value()) {
+    check_dev(*out, "out");
+    TORCH_CHECK(out->scalar_type() == outT.scalar_type() && out->is_contiguous() && out->sizes() == outT.sizes(),
+                "transpose_pack: out must match outT");
+    o = out->data_ptr();
+  }
+  if (b16) check_ok(pfk_transpose_pack_b16(fptr(inp), inp.stride(1), outT.data_ptr(), o, outT.size(2), (int)B, (int)N, cur_stream()),
+                    "transpose_pack (bf16)");
+  else check_ok(pfk_transpose_pack_f32(fptr(inp), inp.stride(1), fptr(outT), static_cast<float*>(o), outT.size(2), (int)B, (int)N, cur_stream()),
+                "transpose_pack");
+}
+
 void forward_interpolate(const Tensor& flow, Tensor out) {
   OpScope scope(flow);
   check_dev_f32(flow, "flow"); check_dev_f32(out, "out");
@@ -1125,6 +1166,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("conv_wgrad_unpacked_b16(Tensor[] srcs, Tensor dy, int B, int H, int W, int kh, int kw, Tensor(a!) dw, Tensor(b!)? db, int[] reals, bool accumulate=False) -> ()");
   m.def("forward_interpolate(Tensor flow, Tensor(a!) out) -> ()");
   m.def("softmax_rows(Tensor(a!) x) -> ()");
+  m.def("softmax_rows_bwd(Tensor p, Tensor dp, Tensor(a!) ds) -> ()");
+  m.def("transpose_pack(Tensor inp, Tensor(a!) outT, Tensor(b!)? out) -> ()");
   m.def("norm_bwd(Tensor x, Tensor dy, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) sum_g, Tensor(c!) sum_gxhat, int B, int HW, bool relu) -> ()");
   m.def("conv_stem_wgrad(Tensor img, Tensor dy, Tensor(a!) dw, Tensor(b!) db) -> ()");
   m.def("instnorm_workspace_bytes(int B, int C) -> int", &instnorm_workspace_bytes);
@@ -1234,6 +1277,8 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv_wgrad_unpacked_b16", &conv_wgrad_unpacked_b16);
   m.impl("forward_interpolate", &forward_interpolate);
   m.impl("softmax_rows", &softmax_rows);
+  m.impl("softmax_rows_bwd", &softmax_rows_bwd);
+  m.impl("transpose_pack", &transpose_pack);
   m.impl("norm_bwd", &norm_bwd);
   m.impl("conv_stem_wgrad", &conv_stem_wgrad);
   m.impl("instnorm_stats", &instnorm_stats);

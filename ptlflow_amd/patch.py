@@ -609,7 +609,9 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     path, the calls that carry a gradient graph (`PfkUpdateBlock.train_precision`).  "bf16" runs its convolutions — forward, data
     and weight gradients — on the bf16 matrix cores (ptlflow_amd/train.py), as the reference does under
     torch.autocast(bfloat16); hidden state, flow and parameter gradients stay fp32.  The conditions of the fp32 training path
-    apply unchanged (no GMA aggregate, 576 mask channels).  A second call with another value switches it."""
+    apply unchanged (576 mask channels, no external aggregate).  GMA's update block trains natively in both precisions: its
+    `attention` argument goes through to `train._AttnMatmul` and its gradient flows back to the caller's map.
+    A second call with another value switches it."""
     from .train import check_precision
     check_precision(train_precision, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)

@@ -268,7 +268,7 @@ class RAFT(nn.Module):
         (forward and backward) and both encoders (ptlflow_amd/train_encoder.py; BatchNorm of `cnet` with batch statistics, as
         `model.train()` implies) run on libpfk through autograd nodes (ptlflow_amd/corr.py, ptlflow_amd/train.py);
         `native_encoders=False` keeps the encoders on the torch modules."""
-        from .train import convex_upsample, update_block_train_pm
+        from .train import attention_map_train, convex_upsample, update_block_train_pm
         from .train_encoder import encoder_train
         load_native()
         images = inputs["images"]
@@ -300,10 +300,16 @@ class RAFT(nn.Module):
             coords1 = coords1 + fwd
         P = dict(self.update_block.named_parameters())
         cache: dict = {}
-        # GMA (gma.py:176-177): the attention map of the context features, torch ops under autograd (`_Attention.forward`)
-        attention = self.att(inp) if self.spec.aggregate else None
         hpm = net.permute(0, 2, 3, 1).reshape(M, self.hidden_dim)
         ipm = inp.permute(0, 2, 3, 1).reshape(M, self.context_dim)
+        # GMA (gma.py:176-177): the attention map of the context features, once per step — `to_qk`, K1, the row softmax and their
+        # backward on libpfk (`train.attention_map_train`); several heads or a width off the 32-grid keep `_Attention.forward`
+        attention = None
+        if self.spec.aggregate:
+            if self.att.heads == 1 and self.context_dim % 32 == 0:
+                attention = attention_map_train(ipm, self.att.to_qk.weight, B, h, w, self.att.scale)
+            else:
+                attention = self.att(inp)
         preds = []
         for _ in range(self.iters):
             coords1 = coords1.detach()
@@ -600,9 +606,9 @@ class GMA(RAFT):
     the same MFMA GEMM kernel as the convolutions, with the residual `fmap + gamma * out` fused in its epilogue."""
 
     def __init__(self, corr_levels: int = 4, corr_radius: int = 4, iters: int = 32, upsample_every_iter: bool = True,
-                 conv_precision: str = "fp32"):
+                 conv_precision: str = "fp32", train_precision: str = "fp32"):
         super().__init__(corr_levels=corr_levels, corr_radius=corr_radius, iters=iters, small=False,
-                         upsample_every_iter=upsample_every_iter, conv_precision=conv_precision)
+                         upsample_every_iter=upsample_every_iter, conv_precision=conv_precision, train_precision=train_precision)
         self.att = _Attention(dim=self.context_dim, heads=1, dim_head=self.context_dim, max_pos_size=160)
 
     def _basic_spec(self, corr_levels: int, corr_radius: int) -> UpdateSpec:

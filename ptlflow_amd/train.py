@@ -15,7 +15,7 @@ arithmetic and its derivatives in four small kernels, ``pfk_gru_*``):
 * dbias     column sums (torch).
 
 Every MIOpen convolution of the update block's forward and backward is gone; the encoders, the correlation volume and
-the lookup keep the reference's autograd in training (their backward kernels are later rows).
+the lookup have their own nodes (train_encoder.py, corr.py).
 
 ``precision="bf16"`` (K12b) — what the reference trains under ``torch.autocast(bfloat16)``: the same two nodes on the
 bf16 matrix cores.
@@ -32,8 +32,16 @@ Hidden state, coordinates, flow, loss, every parameter, every parameter gradient
 
 * ``encoder.convf1`` (7x7 = 49 taps; K8b takes at most 32).
 
-No other layer of the basic / small update block is refused.  GMA's aggregate branch is not covered (``ValueError``), nor is a
-strided convolution (the update block has none).
+No other layer of the basic / small / GMA update block is refused; a strided convolution is (the update block has none).
+
+GMA (K12c) — the attention map and its per-iteration use, in both precisions, with no torch matmul or softmax:
+
+* ``_AttentionMap``   once per step, fp32: ``to_qk`` as a ``conv_pm``, ``P = softmax_rows(scale q k^T)`` on K1 (``pfk_corr_volume_f32``) +
+  ``pfk_softmax_rows_f32``; backward ``pfk_softmax_rows_bwd_f32`` then ``pfk_corr_volume_bwd_f32`` per pair for dq, dk
+* ``pack_attention``  once per step: P and P^T as zero-padded GEMM operands, fp32 or bf16, one pass of ``pfk_transpose_pack_*``
+* ``_AttnMatmul``     once per iteration: ``agg = P v`` and ``dV = P^T dAgg`` on the convolution GEMMs (``pfk_conv2d_f32`` per pair /
+  one batched ``pfk_conv2d_b16``) with ``v^T`` / ``dAgg^T`` as the K-contiguous weight; the map's gradient ``dAgg v^T`` is K1 with scale 1 —
+  per use, or with a step sink (``_AttnFlush``) ONE product over the concatenated K = T*C of all uses of the step.
 """
 from __future__ import annotations
 
@@ -581,6 +589,198 @@ def conv_pm(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias: Optional[t
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# GMA (K12c): the attention map and its per-iteration use `attn @ v` (gma_utils.py:50-78, 100-113)
+# --------------------------------------------------------------------------------------------------------------------
+class AttnState:
+    """The attention map of one forward, packed for the GEMMs of `_AttnMatmul` (built once per step by `pack_attention`):
+
+    ``P``  [B][N][ld]  the map, the A operand of ``agg = P @ v``       — fp32 (ld = N rounded up to 4) or bf16 (to 8)
+    ``PT`` [B][N][ld]  its transpose, the A operand of ``dV = P^T @ dAgg``
+    both with zero pad columns, written in one pass by `pfk_transpose_pack_*`.  ``map``: with a step sink, the map's alias behind
+    an `_AttnFlush` node — what the uses of the step hang on in the autograd graph; None otherwise: the state holds no reference to
+    the caller's tensor (a cache that outlives the step must not keep the map and its graph alive), the uses take it directly."""
+    __slots__ = ("map", "B", "H", "W", "N", "ld", "b16", "P", "PT", "wt", "sink", "uses", "dcat", "vcat", "__weakref__")
+
+    @property
+    def dtype(self):
+        return BF16 if self.b16 else torch.float32
+
+    def target(self, attention: torch.Tensor) -> torch.Tensor:
+        """The tensor a use passes to `_AttnMatmul` as the receiver of the map's gradient."""
+        return self.map if self.sink and self.map is not None else attention
+
+
+def pack_attention(attention: torch.Tensor, B: int, H: int, W: int, precision: str = "fp32", sink: bool = False) -> AttnState:
+    """``attention`` [B, 1, N, N] (one head) -> `AttnState`.  ``sink`` (a step-scoped caller only, like ``accumulate_wgrad``): the
+    uses of this step leave their part of the map's gradient in two [B][N][T*C] buffers and an `_AttnFlush` node between the
+    map and all its uses writes the N x N gradient once."""
+    N = H * W
+    if attention.dim() != 4 or tuple(attention.shape) != (B, 1, N, N):
+        raise ValueError(f"attention must be [B, 1, N, N] = {(B, 1, N, N)} (one head), got {tuple(attention.shape)}")
+    load_native()
+    st = AttnState()
+    st.B, st.H, st.W, st.N, st.b16 = B, H, W, N, check_precision(precision) == "bf16"
+    st.ld = round_up(N, 8 if st.b16 else 4)
+    a = attention.detach().float().reshape(B, N, N)
+    if a.stride(2) != 1 or a.stride(0) != N * a.stride(1):
+        a = a.contiguous()
+    st.PT = torch.empty(B, N, st.ld, device=a.device, dtype=st.dtype)
+    if not st.b16 and st.ld == N and a.is_contiguous():
+        st.P = a                                  # already a legal operand: only the transpose is written
+        torch.ops.pfk.transpose_pack(a, st.PT, None)
+    else:
+        st.P = torch.empty_like(st.PT)
+        torch.ops.pfk.transpose_pack(a, st.PT, st.P)
+    st.wt, st.uses, st.dcat, st.vcat = {}, 0, None, None
+    st.sink = bool(sink) and attention.requires_grad and torch.is_grad_enabled()
+    st.map = _AttnFlush.apply(st, attention) if st.sink else None
+    return st
+
+
+def _attn_gemm(st: AttnState, A: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> None:
+    """out[b] = A[b] @ x[b] for A = st.P or st.PT ([B][N][ld]), x / out pixel-major rows [B*N, C]: the 1x1 "convolution" of
+    `UpdateEngine._aggregate` with x[b]^T as its K-contiguous weight — fp32 on pfk_conv2d_f32 (grouped over the pairs), bf16
+    as ONE batched pfk_conv2d_b16."""
+    ops = torch.ops.pfk
+    B, N, C = st.B, st.N, x.shape[1]
+    wt = st.wt.get(C)
+    if wt is None:       # pad columns stay zero; the columns below N are rewritten by every use (same stream: no hazard)
+        wt = st.wt[C] = torch.zeros(B, C, round_up(st.ld, 64 if st.b16 else 32), device=x.device, dtype=st.dtype)
+    if st.b16:
+        wt[:, :, :N].copy_(x.view(B, N, C).transpose(1, 2))
+        ops.conv2d_b16([A], 1, st.H, st.W, 1, 1, wt, None, C, EPI_LINEAR, False, 1.0, out.view(B, N, C), None, None, None, None, None)
+        return
+    ops.pm_to_cm(x, wt)
+    if B == 1:
+        ops.conv2d([A[0]], 1, st.H, st.W, 1, 1, wt[0], None, C, EPI_LINEAR, False, 1.0, out, None, None, None, _workspace(x.device))
+        return
+    none = x.new_empty(0)
+    for b0 in range(0, B, 4):      # up to four pairs' tiles resident together (`UpdateEngine._aggregate`)
+        bs = range(b0, min(B, b0 + 4))
+        ops.conv2d_group([A[b] for b in bs], 1, st.H, st.W, [1] * len(bs), [wt[b] for b in bs], [none] * len(bs), [0] * len(bs),
+                         [1.0] * len(bs), [out[b * N:(b + 1) * N] for b in bs], [])
+
+
+def _outer_k1(a: torch.Tensor, b: torch.Tensor, B: int, N: int) -> torch.Tensor:
+    """K1 with scale 1 on pixel-major rows [B*N, D]: [B, 1, N, N] fp32 = a[b] @ b[b]^T (bf16 rows: the bf16 K1, then widened)."""
+    D = a.shape[1]
+    out = torch.empty(B, N, N, device=a.device, dtype=a.dtype)
+    (torch.ops.pfk.corr_volume_bf16 if a.dtype == BF16 else torch.ops.pfk.corr_volume)(a.view(B, N, D), b.view(B, N, D), 1.0, out)
+    return out.float().view(B, 1, N, N)
+
+
+class _AttnFlush(torch.autograd.Function):
+    """Identity on the attention map, between the map and ALL its uses of one step (the `_Flush` pattern): the uses return no
+    gradient for the map but leave dAgg_t and v_t in slot t of ``st.dcat`` / ``st.vcat`` [B][N][T*C]; the engine runs this node after
+    the last of them and ONE K1 with K = T*C writes  dP = sum_t dAgg_t v_t^T.  A use that never ran backward left its slot zero.
+    The node holds the state WEAKLY (the uses and the step's cache hold it): AttnState -> map (this node's output) -> grad_fn -> ctx
+    is then no cycle, and a forward whose backward never runs frees P and P^T with the step like any other tensor."""
+
+    @staticmethod
+    def forward(ctx, st, amap):
+        import weakref
+        ctx.set_materialize_grads(False)
+        ctx.st = weakref.ref(st)
+        return amap.view_as(amap)
+
+    @staticmethod
+    def backward(ctx, g):
+        st = ctx.st()
+        if st is None:       # no use is alive: nothing was left in the sink
+            return None, g
+        dcat, vcat, st.dcat, st.vcat = st.dcat, st.vcat, None, None
+        st.map = None        # the sink is closed: a later backward through the same graph gets its gradients the ordinary way
+        if dcat is not None:
+            total = _outer_k1(dcat.view(st.B * st.N, -1), vcat.view(st.B * st.N, -1), st.B, st.N)
+            g = total if g is None else total + g
+        return None, g
+
+
+class _AttnMatmul(torch.autograd.Function):
+    """agg [M, C] fp32 = P[b] @ v[b] per pair (gma_utils.py:108, `torch.einsum('b h i j, b h j d -> b h i d')` with one head).
+    ``amap``: the tensor the map's gradient goes to (`AttnState.target`); ``v`` [M, C] fp32 or bf16 rows, C % 32 == 0.
+    bf16: P, P^T, v and the incoming gradient are bf16 operands (what autocast hands a 16-bit matmul), accumulation fp32."""
+
+    @staticmethod
+    def forward(ctx, amap, v, st: AttnState):
+        if v.shape[1] % 32:
+            raise ValueError(f"_AttnMatmul: the value width must be a multiple of 32, got {v.shape[1]}")
+        v = _rows_b16(v) if st.b16 else v.float().contiguous()
+        out = torch.empty(v.shape[0], v.shape[1], device=v.device, dtype=torch.float32)
+        _attn_gemm(st, st.P, v, out)
+        ctx.st, ctx.slot = st, st.uses
+        st.uses += 1
+        ctx.save_for_backward(v)
+        return out
+
+    @staticmethod
+    def backward(ctx, dAgg):
+        (v,), st = ctx.saved_tensors, ctx.st
+        M, C = v.shape
+        d = _rows_b16(dAgg.to(BF16)) if st.b16 else dAgg.float().contiguous()
+        dV = None
+        if ctx.needs_input_grad[1]:
+            dV = torch.empty(M, C, device=v.device, dtype=v.dtype)
+            _attn_gemm(st, st.PT, d, dV)
+        gmap = None
+        if ctx.needs_input_grad[0]:
+            if st.sink and st.map is not None and st.dcat is None:      # first use to run backward: every use of the step is known
+                st.dcat = torch.zeros(M, st.uses * C, device=v.device, dtype=v.dtype)
+                st.vcat = torch.zeros(M, st.uses * C, device=v.device, dtype=v.dtype)
+            if st.dcat is not None and (ctx.slot + 1) * C <= st.dcat.shape[1]:
+                st.dcat[:, ctx.slot * C:(ctx.slot + 1) * C] = d
+                st.vcat[:, ctx.slot * C:(ctx.slot + 1) * C] = v
+            else:
+                gmap = _outer_k1(d, v, st.B, st.N)
+        return gmap, dV, None
+
+
+class _AttentionMap(torch.autograd.Function):
+    """GMA's attention map, content only, one head (gma_utils.py:55-78): P [B, 1, N, N] = softmax_rows(scale * q k^T) from
+    ``qk`` [B*N, 2d] pixel-major (q | k: `to_qk` as a `conv_pm`, whose own node gives the weight and input gradients).
+    Forward: K1 + `pfk_softmax_rows_f32`; backward: `pfk_softmax_rows_bwd_f32` into rows padded to 4 floats (zero pad columns),
+    then `pfk_corr_volume_bwd_f32` per pair for dq and dk.  fp32 in either training precision."""
+
+    @staticmethod
+    def forward(ctx, qk, B: int, N: int, scale: float):
+        ops = torch.ops.pfk
+        d = qk.shape[1] // 2
+        q, k = qk[:, :d].float().contiguous(), qk[:, d:].float().contiguous()
+        attn = torch.empty(B, N, N, device=qk.device, dtype=torch.float32)
+        ops.corr_volume(q.view(B, N, d), k.view(B, N, d), float(scale), attn)
+        ops.softmax_rows(attn)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(q, k, attn)
+        return attn.view(B, 1, N, N)
+
+    @staticmethod
+    def backward(ctx, dP):
+        ops = torch.ops.pfk
+        q, k, attn = ctx.saved_tensors
+        B, N, _ = attn.shape
+        d = q.shape[1]
+        ldc = round_up(N, 4)
+        dS = torch.empty(B * N, ldc, device=q.device, dtype=torch.float32)
+        ops.softmax_rows_bwd(attn.view(B * N, N), dP.float().reshape(B * N, N), dS)
+        kcm = torch.zeros(B, d, round_up(ldc, 32), device=q.device, dtype=torch.float32)
+        ops.pm_to_cm(k, kcm)
+        dq = torch.empty(B, N, d, device=q.device, dtype=torch.float32)
+        dk = torch.empty(B, ldc, round_up(d, 32), device=q.device, dtype=torch.float32)
+        ops.corr_volume_bwd(dS.view(B, N, ldc), N, q.view(B, N, d), kcm, ctx.scale, dq, False, dk)
+        return torch.cat([dq.view(B * N, d), dk[:, :N, :d].reshape(B * N, d)], 1), None, None, None
+
+
+def attention_map_train(inp_pm: torch.Tensor, to_qk_weight: torch.Tensor, B: int, H: int, W: int, scale: float,
+                        packs: Optional[ConvPacks] = None) -> torch.Tensor:
+    """`Attention.forward` for one head on the kernels, differentiable: ``inp_pm`` [B*H*W, C] fp32 rows (C % 32 == 0),
+    ``to_qk_weight`` [2d, C, 1, 1] -> [B, 1, N, N]."""
+    if to_qk_weight.shape[0] % 64 or inp_pm.shape[1] % 32:
+        raise ValueError("attention_map_train covers one head with widths that are multiples of 32")
+    qk = conv_pm([inp_pm], to_qk_weight, None, B, H, W, False, None, packs)
+    return _AttentionMap.apply(qk, B, H * W, scale)
+
+
+# --------------------------------------------------------------------------------------------------------------------
 # The update block as a differentiable composition (raft/update.py:94-153)
 # --------------------------------------------------------------------------------------------------------------------
 def _pm(x: torch.Tensor) -> torch.Tensor:
@@ -629,6 +829,30 @@ def _context_terms(P: Dict[str, torch.Tensor], spec, i: torch.Tensor, B: int, H:
     return out
 
 
+def _attention_state(attention: torch.Tensor, B: int, H: int, W: int, cache: Optional[dict], acc: bool, precision: str) -> AttnState:
+    """The packed attention map of this step: built once and kept in `cache` for as long as `attention` is the same object at
+    the same version (`_context_terms`' rule).  A step-scoped cache (`acc`) also gets the step sink for the map's gradient.
+    A cache that outlives the step (the seam's) must not pin a step's N x N buffers: without a sink the state holds no reference to
+    the map, the entry goes when the caller's tensor dies, and a stale entry is dropped BEFORE the new pack allocates.  (The
+    autograd nodes of a step still hold their state until that step's graph is freed.)"""
+    import weakref
+    if cache is None:
+        return pack_attention(attention, B, H, W, precision, sink=False)
+    ent = cache.get("attn")
+    if ent is not None and ent[0]() is attention and ent[1] == attention._version and ent[2] == precision:
+        return ent[3]
+    cache.pop("attn", None)
+    del ent
+
+    def gone(ref, cache=cache):
+        if cache.get("attn", (None,))[0] is ref:
+            del cache["attn"]
+
+    st = pack_attention(attention, B, H, W, precision, sink=acc)
+    cache["attn"] = (weakref.ref(attention, gone), attention._version, precision, st)
+    return st
+
+
 def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, H: int, W: int, cache: Optional[dict] = None,
                           accumulate_wgrad: bool = False, attention: Optional[torch.Tensor] = None, hoist_context: bool = True,
                           context_owner: Optional[torch.Tensor] = None, precision: str = "fp32"):
@@ -637,11 +861,12 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
     ``(h', mask [M, 576] | None, delta [M, 2])``.  ``P``: the block's named parameters; ``cache``: a dict that keeps the packed
     weights between the recurrent calls of one training step.  ``accumulate_wgrad`` (only with a ``cache`` that is created per
     step): the recurrent calls add their weight gradients into one buffer per parameter (`ConvPacks.acc`, `_Flush`).
-    ``precision="bf16"``: the convolutions on the bf16 matrix cores (module docstring); inputs and outputs stay fp32 rows."""
+    ``precision="bf16"``: the convolutions on the bf16 matrix cores (module docstring); inputs and outputs stay fp32 rows.
+    ``attention`` (GMA, `spec.aggregate`): the map [B, 1, N, N] of this forward, fp32; its gradient flows back to it."""
     acc = accumulate_wgrad and cache is not None
     b16 = check_precision(precision) == "bf16"
-    if b16 and spec.aggregate:
-        raise ValueError("update_block_train_pm(precision='bf16') does not cover GMA's aggregate branch")
+    if spec.aggregate and attention is None:
+        raise ValueError("update_block_train_pm: a block with GMA's aggregate branch needs the attention map [B, 1, N, N]")
     pad = _pad8 if b16 else _pad4
 
     def conv(srcs, name, relu=False, real=None, prec=precision, out_fp32=False):
@@ -667,8 +892,8 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
     if spec.aggregate:
         mf = torch.cat([out, f], 1)
         v = conv([mf], "aggregator.to_v")                                        # 1x1, no bias
-        N = H * W
-        agg = torch.bmm(attention.reshape(B, N, N).float(), v.view(B, N, v.shape[1])).reshape(B * N, v.shape[1])
+        att = _attention_state(attention, B, H, W, cache, acc, precision)       # packed once per step (P and P^T, fp32 or bf16)
+        agg = _AttnMatmul.apply(att.target(attention), v, att)                                 # fp32 rows in either precision
         parts = [mf, mf + P["aggregator.gamma"] * agg] if hoist else [i, mf, mf + P["aggregator.gamma"] * agg]
     xq = 8 if b16 else 4
     if x_real % xq:
@@ -702,12 +927,12 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
 
 
 def update_block_train(P: Dict[str, torch.Tensor], spec, net, inp, corr, flow, cache: Optional[dict] = None,
-                       precision: str = "fp32"):
+                       precision: str = "fp32", attention: Optional[torch.Tensor] = None):
     """NCHW face of `update_block_train_pm` (what `PfkUpdateBlock` calls from the reference's loop):
-    NCHW in, NCHW out: ``(net, mask | None, delta_flow)``."""
+    NCHW in, NCHW out: ``(net, mask | None, delta_flow)``; ``attention``: GMA's map [B, 1, N, N]."""
     B, _, H, W = net.shape
     h, mask, delta = update_block_train_pm(P, spec, _pm(net), _pm(inp), _pm(corr), _pm(flow), B, H, W, cache, context_owner=inp,
-                                           precision=precision)
+                                           precision=precision, attention=attention)
     return _nchw(h, B, H, W), (None if mask is None else _nchw(mask, B, H, W)), _nchw(delta, B, H, W)
 
 

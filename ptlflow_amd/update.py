@@ -791,14 +791,16 @@ class PfkUpdateBlock(WrappedModule):
         attention = args.get("attention")
         if torch.is_grad_enabled() and (net.requires_grad or any(p.requires_grad for p in self.parameters())):
             # training graph: every convolution forward / dgrad / wgrad on the MFMA kernel through the
-            # differentiable composition of ptlflow_amd/train.py; GMA's aggregate branch, CPU tensors and split-bf16
-            # modes keep the reference module's own autograd.  train_precision "bf16" puts the composition on the bf16 matrix
-            # cores whatever the inference precision is.
-            if (self.native_backward and net.is_cuda and not self.spec.aggregate and self.spec.mask_channels == 576
+            # differentiable composition of ptlflow_amd/train.py — GMA's block included: `attention` goes through, the aggregate
+            # runs on `train._AttnMatmul` and the map's gradient flows back to the caller's tensor; CCMR's external aggregate, CPU
+            # tensors and split-bf16 modes keep the reference module's own autograd.  train_precision "bf16" puts the composition
+            # on the bf16 matrix cores whatever the inference precision is.
+            if (self.native_backward and net.is_cuda and not self.spec.external_aggregate and self.spec.mask_channels == 576
+                    and (attention is not None or not self.spec.aggregate)
                     and (self.conv_precision == "fp32" or self.train_precision == "bf16")):
                 from .train import update_block_train
                 h, mask, delta = update_block_train(dict(self.named_parameters()), self.spec, net, inp, corr, flow, self._train_cache,
-                                                    self.train_precision)
+                                                    self.train_precision, attention)
                 return h.to(net.dtype), (None if mask is None else mask.to(net.dtype)), delta.to(net.dtype)
             return self._ref[0](net, inp, corr, flow, *extra, **kw)
         with torch.no_grad():
