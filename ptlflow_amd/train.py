@@ -3,32 +3,29 @@
 The inference path fuses gates and concatenations into convolution epilogues and keeps its state in place, which autograd
 cannot see.  For training the update block (ptlflow/models/raft/update.py:6-153) is re-composed from ONE differentiable
 primitive, ``conv_pm`` — a "same" convolution over pixel-major ``[B*H*W, C]`` tensors whose forward, data gradient and weight
-gradient all run on fp32-MFMA implicit-GEMM kernels — plus one fused autograd node per GRU pass (``_GruPass``: gate
-arithmetic and its derivatives in four small kernels, ``pfk_gru_*``):
+gradient all run on matrix-core implicit-GEMM kernels — plus one fused autograd node per GRU pass (``_GruPass``: gate
+arithmetic and its derivatives in four small fp32 kernels, ``pfk_gru_*``).  Both nodes are written once, against a `_Kernels`
+object per precision: ``"fp32"``, or ``"bf16"`` (K12b) — what the reference trains under ``torch.autocast(bfloat16)``.
 
-* forward   ``out = conv(srcs, W) + b`` (relu fused)                              -> ``pfk_conv2d_f32``
-* dgrad     ``dX_s = conv(dY, flip(W_s)^T)``  — a convolution again                -> ``pfk_conv2d_f32`` (re-packed weight)
-* wgrad     ``dW[:, c, ky, kx] = sum_p dY[p, :] * X[p + tap, c]``  -> ``pfk_conv_wgrad_f32``: the transposed product with the
-  PIXEL as reduction index on the same matrix cores, read straight from the pixel-major tensors (tap padding by
-  out-of-range buffer offsets, operands fetched from LDS "transposed" with conflict-free ``ds_read_b32``), pixel range cut
-  into slices that are summed in a fixed order (deterministic), result in the forward weight's packed layout.
-* dbias     column sums (torch).
+* forward   ``out = conv(srcs, W) + b`` (relu fused)               -> ``pfk_conv2d_f32`` | ``pfk_conv2d_b16`` LINEAR, bf16 rows out
+  (the saved activations are the operand rows: bf16 ones in bf16)
+* dgrad     ``dX_s = conv(dY, flip(W_s)^T)``  — a convolution again -> the forward's kernel with a re-packed weight slice
+  (K chunks of 32 fp32 | 64 bf16 channels); bf16 rounds the gradient to bf16 first
+* wgrad     ``dW[:, c, ky, kx] = sum_p dY[p, :] * X[p + tap, c]``  -> ``pfk_conv_wgrad_unpacked_f32`` | ``_b16``: the transposed
+  product with the PIXEL as reduction index on the same matrix cores, read straight from the pixel-major tensors (tap
+  padding by out-of-range buffer offsets, operands fetched from LDS "transposed": conflict-free ``ds_read_b32`` |
+  ``ds_read_b64_tr_b16`` feeding ``v_mfma_f32_32x32x16_bf16``), pixel range cut into slices that are summed in a fixed order
+  (deterministic); fp32 dW / db in PyTorch's layouts, the bias gradient being one more K chunk; step-scoped accumulation
+  (`ConvPacks.acc`, `_Flush`) in both
+* dbias     without a weight gradient: column sums (torch).
+* GRU pass  the pre-activations are fp32 rows and the gate arithmetic is fp32 in both; bf16: ``h`` stays fp32 with a bf16 copy as
+  the convolutions' operand, ``r * h`` is rounded to bf16.
 
 Every MIOpen convolution of the update block's forward and backward is gone; the encoders, the correlation volume and
 the lookup have their own nodes (train_encoder.py, corr.py).
 
-``precision="bf16"`` (K12b) — what the reference trains under ``torch.autocast(bfloat16)``: the same two nodes on the
-bf16 matrix cores.
-
-* forward   ``pfk_conv2d_b16`` LINEAR (relu fused), bf16 rows out; the saved activations are those bf16 rows
-* dgrad     ``pfk_conv2d_b16`` of the bf16-rounded gradient with the flipped, transposed weight slice (64-channel K chunks, bf16)
-* wgrad     ``pfk_conv_wgrad_unpacked_b16``: transposed LDS reads (``ds_read_b64_tr_b16``) feeding ``v_mfma_f32_32x32x16_bf16``;
-  fp32 dW / db in PyTorch's layouts, same step-scoped accumulation (`ConvPacks.acc`, `_Flush`)
-* GRU pass  pre-activations come out of ``pfk_conv2d_b16`` as fp32 rows, the gate arithmetic and its derivatives stay on the fp32
-  ``pfk_gru_*`` kernels, ``h`` stays fp32 with a bf16 copy as the convolutions' operand, ``r * h`` is rounded to bf16.
-
-Hidden state, coordinates, flow, loss, every parameter, every parameter gradient and every accumulator stay fp32.  Layers outside
-``pfk_conv2d_b16``'s envelope keep the fp32 node, with a cast at their boundary:
+Hidden state, coordinates, flow, loss, every parameter, every parameter gradient and every accumulator stay fp32 in either
+precision.  Layers outside ``pfk_conv2d_b16``'s envelope keep the fp32 kernels, with a cast at their boundary:
 
 * ``encoder.convf1`` (7x7 = 49 taps; K8b takes at most 32).
 
@@ -93,17 +90,18 @@ _workspace.cache = {}
 
 
 class ConvPacks:
-    """Packed forms of one convolution weight (forward and per-source dgrad), built lazily and reused for as long as the
-    parameter versions in ``key`` do not change — i.e. for all recurrent iterations of a training step.
+    """Packed forms of one convolution weight, built lazily and reused for as long as the parameter versions in ``key`` do
+    not change — i.e. for all recurrent iterations of a training step.  ``packed``: {(precision, "fwd") | (precision, "dgrad",
+    source): operand}, so an entry used under both precisions keeps both forms apart.
 
     ``acc``: gradient accumulators of a step-scoped entry (`packs_for(..., accumulate=True)`): the weight-gradient launches of
     all recurrent uses add into ONE buffer per parameter (`pfk_conv_wgrad_unpacked_f32(accumulate=1)`) and a `_Flush` node
     hands the total to autograd once — instead of every use returning its own gradient and the engine adding them (eleven
     small additions per parameter and step at 12 iterations)."""
-    __slots__ = ("key", "fwd", "dgrad", "accumulate", "acc", "alias", "extra")
+    __slots__ = ("key", "packed", "accumulate", "acc", "alias", "extra")
 
     def __init__(self, key=None, accumulate=False):
-        self.key, self.fwd, self.dgrad = key, None, {}
+        self.key, self.packed = key, {}
         self.accumulate = accumulate
         self.acc = None          # {position among the parameters given to _Flush: accumulator}, None before the first use
         self.alias = None        # the parameters as seen by the uses of this step (outputs of _Flush)
@@ -160,101 +158,6 @@ def step_params(packs: ConvPacks, *params):
     return packs.alias
 
 
-class _ConvPM(torch.autograd.Function):
-    """out[M, cout] = relu?(conv(cat(srcs), weight) + bias) on pixel-major tensors; srcs[i] is [M, C_i] with C_i % 4 == 0
-    (``real[i]`` <= C_i real channels, the rest zero padding)."""
-
-    @staticmethod
-    def forward(ctx, weight, bias, g: _Geometry, relu: bool, real: Tuple[int, ...], packs: ConvPacks, *srcs):
-        ops = torch.ops.pfk
-        if g.precision != "fp32":
-            return _conv_forward_b16(ctx, weight, bias, g, relu, real, packs, g.precision, srcs)
-        srcs = [s.contiguous() if s.stride(1) != 1 else s for s in srcs]
-        cout = weight.shape[0]
-        out = torch.empty(g.B * g.Ho * g.Wo, cout, device=srcs[0].device, dtype=torch.float32)
-        ops.conv2d(list(srcs), g.B, g.H, g.W, g.kh, g.kw, _fwd_pack(packs, weight, _segments(srcs, real)), None if bias is None else bias.detach().float().contiguous(),
-                   cout, EPI_LINEAR, relu, 1.0, out, None, None, None, _workspace(out.device), None, g.stride)
-        ctx.g, ctx.relu, ctx.real, ctx.has_bias, ctx.packs = g, relu, real, bias is not None, packs
-        ctx.save_for_backward(weight, out if relu else None, *srcs)
-        return out
-
-    @staticmethod
-    def backward(ctx, dY):
-        ops = torch.ops.pfk
-        if ctx.g.precision != "fp32":
-            return _conv_backward_b16(ctx, dY)
-        weight, out, *srcs = ctx.saved_tensors
-        g, real, packs = ctx.g, ctx.real, ctx.packs
-        cout = weight.shape[0]
-        M = g.B * g.H * g.W
-        dY = dY.float().contiguous()
-        if ctx.relu:
-            dY = torch.ops.aten.threshold_backward(dY, out, 0.0)     # dY * (out > 0) in one kernel (what torch's relu backward runs)
-        ws = _workspace(dY.device)
-        need = ctx.needs_input_grad      # (weight, bias, g, relu, real, packs, *srcs)
-        dW = db = None
-        dsrcs: List[Optional[torch.Tensor]] = [None] * len(srcs)
-        # channels of dY padded to a multiple of 4 for its role as a convolution source (flow head: cout = 2)
-        dY_src = dY if cout % 4 == 0 else F.pad(dY, (0, round_up(cout, 4) - cout))
-        segs = _segments(srcs, real)
-        # ---- dgrad: dX_s = conv(dY, W_s^T flipped); for a strided convolution the gradient is first spread over the input grid
-        # (zeros between the samples: the transposed convolution written as a stride-1 one)
-        dY_in = dY_src
-        if g.stride != 1 and any(need[6:]):
-            dY_in = torch.zeros(g.B, g.H, g.W, dY_src.shape[1], device=dY.device, dtype=torch.float32)
-            dY_in[:, ::g.stride, ::g.stride] = dY_src.view(g.B, g.Ho, g.Wo, -1)
-            dY_in = dY_in.view(M, -1)
-        for i, (first, n, n_buf) in enumerate(segs):
-            if not need[6 + i]:
-                continue
-            dx = torch.empty(M, n_buf, device=dY.device, dtype=torch.float32)
-            ops.conv2d([dY_in], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack(packs, i, weight, (first, n, n_buf), dY_src.shape[1]), None, n_buf,
-                       EPI_LINEAR, False, 1.0, dx, None, None, None, ws)
-            dsrcs[i] = dx
-        # ---- wgrad: one launch + a deterministic slice reduction straight from the pixel-major tensors; the reduction writes
-        # PyTorch's [cout, cin, kh, kw] / [cout] layouts directly (pfk_conv_wgrad_unpacked_f32), the bias gradient being one more
-        # K chunk whose A operand is a column of ones
-        want_b = ctx.has_bias and need[1]
-        if need[0] and packs.accumulate and packs.alias is not None:
-            # step-scoped entry: add into the parameter's accumulators; `_Flush` returns the totals once (weight, [bias])
-            first = packs.acc is None
-            if first:
-                packs.acc = {0: torch.empty(weight.shape, device=dY.device, dtype=torch.float32)}
-                if want_b:
-                    packs.acc[1] = torch.empty(cout, device=dY.device, dtype=torch.float32)
-            ops.conv_wgrad_unpacked(list(srcs), dY_src, g.B, g.H, g.W, g.kh, g.kw, packs.acc[0], packs.acc.get(1),
-                                    [n for _, n, _ in segs], g.stride, not first)
-        elif need[0]:
-            dW = torch.empty(weight.shape, device=dY.device, dtype=torch.float32)
-            db = torch.empty(cout, device=dY.device, dtype=torch.float32) if want_b else None
-            ops.conv_wgrad_unpacked(list(srcs), dY_src, g.B, g.H, g.W, g.kh, g.kw, dW, db, [n for _, n, _ in segs], g.stride)
-            dW = dW.to(weight.dtype)
-        elif want_b:
-            db = dY.sum(0)
-        return (dW, db, None, None, None, None, *dsrcs)
-
-
-def _fwd_pack(packs: ConvPacks, weight: torch.Tensor, segs) -> torch.Tensor:
-    if packs.fwd is None:
-        packs.fwd = pack_conv_weight(weight.detach().float(), segs)
-    return packs.fwd
-
-
-def _dgrad_pack(packs: ConvPacks, i: int, weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
-    """Packed weight of the data-gradient convolution w.r.t. source i: W[:, seg] with in/out swapped and taps flipped."""
-    if i not in packs.dgrad:
-        first, n, n_buf = seg
-        cout = weight.shape[0]
-        wt = weight.detach().float()[:, first:first + n].permute(1, 0, 2, 3).flip(2, 3)        # [n, cout, kh, kw]
-        if n_buf > n:
-            wt = F.pad(wt, (0, 0, 0, 0, 0, 0, 0, n_buf - n))                                   # padded channels: zero gradient
-        packs.dgrad[i] = pack_conv_weight(wt.contiguous(), [(0, cout, dy_channels)])
-    return packs.dgrad[i]
-
-
-# --------------------------------------------------------------------------------------------------------------------
-# precision="bf16": the same node on pfk_conv2d_b16 (forward, dgrad) and pfk_conv_wgrad_unpacked_b16 (wgrad)
-# --------------------------------------------------------------------------------------------------------------------
 PRECISIONS = ("fp32", "bf16")
 BF16 = torch.bfloat16
 
@@ -265,34 +168,6 @@ def check_precision(precision: str, what: str = "precision") -> str:
     return precision
 
 
-def _fwd_pack_b16(packs: ConvPacks, weight: torch.Tensor, segs, cout_buf: int) -> torch.Tensor:
-    """K8b's forward weight: bf16 [cout_buf, ktot], 64-channel K chunks; rows past cout (a 2-channel head padded to 8) are zero."""
-    if "fwd16" not in packs.extra:
-        w = weight.detach().float()
-        if cout_buf > w.shape[0]:
-            w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, cout_buf - w.shape[0]))
-        packs.extra["fwd16"] = pack_conv_weight(w, segs, kpad=64).to(BF16).contiguous()
-    return packs.extra["fwd16"]
-
-
-def dgrad_weight_b16(weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
-    """K8b weight of the data-gradient convolution w.r.t. one source: W[:, seg] with in / out swapped and the taps flipped,
-    bf16 [n_buf, taps * round_up(dy_channels, 64)] in K8b's K order (tap major, then dY's channels)."""
-    first, n, n_buf = seg
-    cout = weight.shape[0]
-    wt = weight.detach().float()[:, first:first + n].permute(1, 0, 2, 3).flip(2, 3)        # [n, cout, kh, kw]
-    if n_buf > n:
-        wt = F.pad(wt, (0, 0, 0, 0, 0, 0, 0, n_buf - n))                                   # padded channels: zero gradient
-    return pack_conv_weight(wt.contiguous(), [(0, cout, dy_channels)], kpad=64).to(BF16).contiguous()
-
-
-def _dgrad_pack_b16(packs: ConvPacks, i: int, weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
-    key = ("b16", i)
-    if key not in packs.dgrad:
-        packs.dgrad[key] = dgrad_weight_b16(weight, seg, dy_channels)
-    return packs.dgrad[key]
-
-
 def _rows_b16(s: torch.Tensor) -> torch.Tensor:
     """bf16 rows with unit channel stride and a row stride that is a multiple of 8 (what the b16 kernels read)."""
     s = s if s.dtype == BF16 else s.to(BF16)
@@ -301,71 +176,186 @@ def _rows_b16(s: torch.Tensor) -> torch.Tensor:
     return s
 
 
-def _conv_forward_b16(ctx, weight, bias, g, relu, real, packs, precision, srcs):
-    """sources: bf16 or fp32 rows [M, C_i], C_i % 8 == 0 (fp32 ones are rounded here: the cast at an fp32 layer's boundary);
-    out: bf16 rows (``precision == "bf16"``) or the fp32 accumulators as they are (``"bf16-f32out"``, the heads' last layers)."""
-    ops = torch.ops.pfk
-    if g.stride != 1:
-        raise ValueError("conv_pm(precision='bf16') covers stride 1 only")
-    if g.kh * g.kw > 32:
-        raise ValueError("conv_pm(precision='bf16'): pfk_conv2d_b16 takes at most 32 taps; keep this layer on precision='fp32'")
-    ctx.src_dtypes = tuple(s.dtype for s in srcs)
-    srcs = [_rows_b16(s) for s in srcs]
-    assert all(s.shape[1] % 8 == 0 for s in srcs), "bf16 sources need channel counts that are multiples of 8"
-    cout = weight.shape[0]
-    cout_buf = round_up(cout, 8)
-    out_dtype = torch.float32 if precision == "bf16-f32out" else BF16
-    buf = torch.empty(g.B * g.H * g.W, cout_buf, device=srcs[0].device, dtype=out_dtype)
-    b = None
-    if bias is not None:
-        b = bias.detach().float().contiguous()
-        b = b if cout_buf == cout else F.pad(b, (0, cout_buf - cout))
-    ops.conv2d_b16(list(srcs), g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(packs, weight, _segments(srcs, real), cout_buf), b, cout_buf,
-                   EPI_LINEAR, relu, 1.0, buf, None, None, None, None, None)
-    out = buf if cout_buf == cout else buf[:, :cout]
-    ctx.g, ctx.relu, ctx.real, ctx.has_bias, ctx.packs = g, relu, real, bias is not None, packs
-    ctx.save_for_backward(weight, out if relu else None, *srcs)
-    return out
+class _Kernels:
+    """What the two training precisions differ in — everything else of `_ConvPM` and `_GruPass` is written once.  This is the
+    fp32 instance: fp32 operands, channel counts in multiples of 4, packed weights in K chunks of 32 channels, outputs as wide
+    as the weight, any odd kernel and stride."""
+    name, dtype, quantum, kpad, pads_cout = "fp32", torch.float32, 4, 32, False
+
+    def check(self, g: _Geometry, srcs) -> None:
+        """Refuses what the kernels do not cover."""
+
+    def rows(self, t: torch.Tensor) -> torch.Tensor:
+        """``t`` (of the operand dtype already, or any dtype in bf16) in the layout the kernels read."""
+        return t.contiguous() if t.stride(1) != 1 else t
+
+    def operand(self, t: torch.Tensor) -> torch.Tensor:
+        """``t`` in the operand dtype: ``t`` itself where it is contiguous fp32 | its rounding to bf16."""
+        return t.float().contiguous()
+
+    def pad(self, x: torch.Tensor) -> torch.Tensor:
+        """Channels zero-padded to the quantum."""
+        c = x.shape[1]
+        return x if c % self.quantum == 0 else F.pad(x, (0, round_up(c, self.quantum) - c))
+
+    def cout_buf(self, cout: int) -> int:
+        """Width of the output rows (and of the bias and the forward weight's rows) the forward kernel is given."""
+        return round_up(cout, self.quantum) if self.pads_cout else cout
+
+    def pack(self, w: torch.Tensor, segs) -> torch.Tensor:
+        return pack_conv_weight(w, segs, kpad=self.kpad).to(self.dtype).contiguous()
+
+    def conv(self, srcs, g: _Geometry, wpack, bias, cout: int, relu: bool, out, residual=None, stride: int = 1) -> None:
+        torch.ops.pfk.conv2d(list(srcs), g.B, g.H, g.W, g.kh, g.kw, wpack, bias, cout, EPI_LINEAR, relu, 1.0, out, None, None, None,
+                             _workspace(out.device), residual, stride)
+
+    def wgrad(self, srcs, dY, g: _Geometry, dW, db, reals, accumulate: bool) -> None:
+        torch.ops.pfk.conv_wgrad_unpacked(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, g.stride, accumulate)
 
 
-def _conv_backward_b16(ctx, dY):
-    ops = torch.ops.pfk
-    weight, out, *srcs = ctx.saved_tensors
-    g, real, packs = ctx.g, ctx.real, ctx.packs
+class _KernelsB16(_Kernels):
+    """bf16 operands on ``pfk_conv2d_b16`` / ``pfk_conv_wgrad_unpacked_b16``: channel counts in multiples of 8, K chunks of 64
+    channels, output rows padded to 8 channels (a 2-channel head); stride 1 and at most 32 taps."""
+    name, dtype, quantum, kpad, pads_cout = "bf16", BF16, 8, 64, True
+    rows = staticmethod(_rows_b16)
+
+    def check(self, g, srcs):
+        if g.stride != 1:
+            raise ValueError("conv_pm(precision='bf16') covers stride 1 only")
+        if g.kh * g.kw > 32:
+            raise ValueError("conv_pm(precision='bf16'): pfk_conv2d_b16 takes at most 32 taps; keep this layer on precision='fp32'")
+        assert all(s.shape[1] % 8 == 0 for s in srcs), "bf16 sources need channel counts that are multiples of 8"
+
+    def operand(self, t):
+        return t.to(BF16)
+
+    def conv(self, srcs, g, wpack, bias, cout, relu, out, residual=None, stride=1):
+        torch.ops.pfk.conv2d_b16(list(srcs), g.B, g.H, g.W, g.kh, g.kw, wpack, bias, cout, EPI_LINEAR, relu, 1.0, out, None, None, None,
+                                 None, residual)
+
+    def wgrad(self, srcs, dY, g, dW, db, reals, accumulate):
+        torch.ops.pfk.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, accumulate)
+
+
+_KERNELS = {"fp32": _Kernels(), "bf16": _KernelsB16()}
+# `_Geometry.precision` -> (kernels, dtype of the forward's output rows); "bf16-f32out": the fp32 accumulators as they are
+_NODE = {"fp32": (_KERNELS["fp32"], torch.float32), "bf16": (_KERNELS["bf16"], BF16), "bf16-f32out": (_KERNELS["bf16"], torch.float32)}
+
+
+def _fwd_pack(packs: ConvPacks, k: _Kernels, weight: torch.Tensor, segs) -> torch.Tensor:
+    """The forward kernel's weight [cout_buf, ktot]; rows past cout (a 2-channel head padded to 8) are zero."""
+    key = (k.name, "fwd")
+    if key not in packs.packed:
+        w = weight.detach().float()
+        extra = k.cout_buf(w.shape[0]) - w.shape[0]
+        if extra:
+            w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, extra))
+        packs.packed[key] = k.pack(w, segs)
+    return packs.packed[key]
+
+
+def _dgrad_weight(k: _Kernels, weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
+    """Packed weight of the data-gradient convolution w.r.t. one source: W[:, seg] with in / out swapped and the taps flipped,
+    [n_buf, taps * round_up(dy_channels, kpad)] in the forward kernel's K order (tap major, then dY's channels)."""
+    first, n, n_buf = seg
     cout = weight.shape[0]
-    M = g.B * g.H * g.W
-    dY = dY.to(BF16)          # what autocast's backward hands the convolution: the gradient of a 16-bit output
-    if ctx.relu:
-        dY = torch.ops.aten.threshold_backward(dY, out.to(BF16), 0.0)
-    dY = _rows_b16(dY if cout % 8 == 0 else F.pad(dY, (0, round_up(cout, 8) - cout)))
-    need = ctx.needs_input_grad      # (weight, bias, g, relu, real, packs, *srcs)
-    dW = db = None
-    dsrcs: List[Optional[torch.Tensor]] = [None] * len(srcs)
-    segs = _segments(srcs, real)
-    for i, seg in enumerate(segs):
-        if not need[6 + i]:
-            continue
-        dx = torch.empty(M, seg[2], device=dY.device, dtype=ctx.src_dtypes[i])     # fp32 for an fp32 source, bf16 rows otherwise
-        ops.conv2d_b16([dY], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack_b16(packs, i, weight, seg, dY.shape[1]), None, seg[2],
-                       EPI_LINEAR, False, 1.0, dx, None, None, None, None, None)
-        dsrcs[i] = dx
-    want_b = ctx.has_bias and need[1]
-    reals = [n for _, n, _ in segs]
-    if need[0] and packs.accumulate and packs.alias is not None:
-        first = packs.acc is None
-        if first:
-            packs.acc = {0: torch.empty(weight.shape, device=dY.device, dtype=torch.float32)}
-            if want_b:
-                packs.acc[1] = torch.empty(cout, device=dY.device, dtype=torch.float32)
-        ops.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, packs.acc[0], packs.acc.get(1), reals, not first)
-    elif need[0]:
-        dW = torch.empty(weight.shape, device=dY.device, dtype=torch.float32)
-        db = torch.empty(cout, device=dY.device, dtype=torch.float32) if want_b else None
-        ops.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, False)
-        dW = dW.to(weight.dtype)
-    elif want_b:
-        db = dY[:, :cout].float().sum(0)
-    return (dW, db, None, None, None, None, *dsrcs)
+    wt = weight.detach().float()[:, first:first + n].permute(1, 0, 2, 3).flip(2, 3)        # [n, cout, kh, kw]
+    if n_buf > n:
+        wt = F.pad(wt, (0, 0, 0, 0, 0, 0, 0, n_buf - n))                                   # padded channels: zero gradient
+    return k.pack(wt.contiguous(), [(0, cout, dy_channels)])
+
+
+def dgrad_weight_b16(weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
+    """`_dgrad_weight` for K8b: bf16 [n_buf, taps * round_up(dy_channels, 64)]."""
+    return _dgrad_weight(_KERNELS["bf16"], weight, seg, dy_channels)
+
+
+def _dgrad_pack(packs: ConvPacks, k: _Kernels, i: int, weight: torch.Tensor, seg, dy_channels: int) -> torch.Tensor:
+    key = (k.name, "dgrad", i)
+    if key not in packs.packed:
+        packs.packed[key] = _dgrad_weight(k, weight, seg, dy_channels)
+    return packs.packed[key]
+
+
+class _ConvPM(torch.autograd.Function):
+    """out[M, cout] = relu?(conv(cat(srcs), weight) + bias) on pixel-major tensors; srcs[i] is [M, C_i] with C_i % 4 == 0
+    (bf16: % 8; ``real[i]`` <= C_i real channels, the rest zero padding).  ``g.precision``:
+
+    "fp32"         fp32 sources (taken as they are), fp32 out
+    "bf16"         bf16 or fp32 sources (fp32 ones are rounded here: the cast at an fp32 layer's boundary), bf16 rows out
+    "bf16-f32out"  the same with the fp32 accumulators as they are (the heads' last layers)"""
+
+    @staticmethod
+    def forward(ctx, weight, bias, g: _Geometry, relu: bool, real: Tuple[int, ...], packs: ConvPacks, *srcs):
+        k, out_dtype = _NODE[g.precision]
+        k.check(g, srcs)
+        ctx.src_dtypes = tuple(s.dtype for s in srcs)
+        srcs = [k.rows(s) for s in srcs]
+        cout = weight.shape[0]
+        cout_buf = k.cout_buf(cout)
+        buf = torch.empty(g.B * g.Ho * g.Wo, cout_buf, device=srcs[0].device, dtype=out_dtype)
+        b = None
+        if bias is not None:
+            b = bias.detach().float().contiguous()
+            b = b if cout_buf == cout else F.pad(b, (0, cout_buf - cout))
+        k.conv(srcs, g, _fwd_pack(packs, k, weight, _segments(srcs, real)), b, cout_buf, relu, buf, stride=g.stride)
+        out = buf if cout_buf == cout else buf[:, :cout]
+        ctx.g, ctx.relu, ctx.real, ctx.has_bias, ctx.packs = g, relu, real, bias is not None, packs
+        ctx.save_for_backward(weight, out if relu else None, *srcs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dY):
+        weight, out, *srcs = ctx.saved_tensors
+        g, real, packs = ctx.g, ctx.real, ctx.packs
+        k = _NODE[g.precision][0]
+        cout = weight.shape[0]
+        M = g.B * g.H * g.W
+        dev = dY.device
+        dY = k.operand(dY)          # bf16: what autocast's backward hands the convolution, the gradient of a 16-bit output
+        if ctx.relu:
+            dY = torch.ops.aten.threshold_backward(dY, out.to(k.dtype), 0.0)     # dY * (out > 0) in one kernel (what torch's relu backward runs)
+        need = ctx.needs_input_grad      # (weight, bias, g, relu, real, packs, *srcs)
+        dW = db = None
+        dsrcs: List[Optional[torch.Tensor]] = [None] * len(srcs)
+        # channels of dY padded to the quantum for its role as a convolution source (flow head: cout = 2)
+        dY_src = k.rows(k.pad(dY))
+        segs = _segments(srcs, real)
+        # ---- dgrad: dX_s = conv(dY, W_s^T flipped); for a strided convolution the gradient is first spread over the input grid
+        # (zeros between the samples: the transposed convolution written as a stride-1 one)
+        dY_in = dY_src
+        if g.stride != 1 and any(need[6:]):
+            dY_in = torch.zeros(g.B, g.H, g.W, dY_src.shape[1], device=dev, dtype=dY_src.dtype)
+            dY_in[:, ::g.stride, ::g.stride] = dY_src.view(g.B, g.Ho, g.Wo, -1)
+            dY_in = dY_in.view(M, -1)
+        for i, seg in enumerate(segs):
+            if not need[6 + i]:
+                continue
+            dx = torch.empty(M, seg[2], device=dev, dtype=ctx.src_dtypes[i])     # the source's dtype: fp32, or in bf16 also bf16 rows
+            k.conv([dY_in], g, _dgrad_pack(packs, k, i, weight, seg, dY_src.shape[1]), None, seg[2], False, dx)
+            dsrcs[i] = dx
+        # ---- wgrad: one launch + a deterministic slice reduction straight from the pixel-major tensors; the reduction writes
+        # PyTorch's [cout, cin, kh, kw] / [cout] layouts directly, the bias gradient being one more K chunk whose A operand is
+        # a column of ones
+        want_b = ctx.has_bias and need[1]
+        if need[0]:
+            # a step-scoped entry adds into the parameter's accumulators (allocated by the first use) and `_Flush` returns the
+            # totals once (weight, [bias]); any other returns its own
+            accumulate = packs.accumulate and packs.alias is not None
+            first = not accumulate or packs.acc is None
+            bufs = packs.acc
+            if first:
+                bufs = {0: torch.empty(weight.shape, device=dev, dtype=torch.float32)}
+                if want_b:
+                    bufs[1] = torch.empty(cout, device=dev, dtype=torch.float32)
+                if accumulate:
+                    packs.acc = bufs
+            k.wgrad(srcs, dY_src, g, bufs[0], bufs.get(1), [n for _, n, _ in segs], not first)
+            if not accumulate:
+                dW, db = bufs[0].to(weight.dtype), bufs.get(1)
+        elif want_b:
+            db = dY.float().sum(0)          # the unpadded gradient's column sums, in fp32
+        return (dW, db, None, None, None, None, *dsrcs)
 
 
 def _unpack_wgrad(packed: torch.Tensor, weight_shape, segs, g: _Geometry) -> torch.Tensor:
@@ -400,44 +390,45 @@ class _GruPass(torch.autograd.Function):
         gradients run on bf16 operands, everything between them in fp32 (module docstring)."""
         ops = torch.ops.pfk
         ctx.precision = precision
-        if precision != "fp32":
-            return _gru_forward_b16(ctx, h, x, wz, wr, wq, bz, br, bq, g, x_real, pk_zr, pk_q, pzr, pq)
+        k = _KERNELS[precision]
+        k.check(g, [h, x])
         h = h.float().contiguous()
-        x = x.float().contiguous()
+        x = k.rows(k.operand(x))
         M, C = h.shape
         dev = h.device
-        ws = _workspace(dev)
         if "wzr" not in pk_zr.extra:      # once per (parameter version): the z and r convolutions run as one
             pk_zr.extra["wzr"] = torch.cat([wz.detach(), wr.detach()], 0).float()
             pk_zr.extra["bzr"] = torch.cat([bz.detach(), br.detach()], 0).float().contiguous()
         wzr, bzr = pk_zr.extra["wzr"], pk_zr.extra["bzr"]
         segs = [(0, C, C), (C, x_real, x.shape[1])]
-        a_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)
-        ops.conv2d([h, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack(pk_zr, wzr, segs), bzr, 2 * C, EPI_LINEAR, False, 1.0, a_zr,
-                   None, None, None, ws, None if pzr is None else pzr.detach().float().contiguous())
+        hb = k.operand(h)                  # the convolutions' operand; the state itself stays fp32
+
+        def res(p):                        # the epilogue's residual input takes the operand dtype or fp32
+            return None if p is None else (p.detach() if p.dtype == k.dtype else p.detach().float()).contiguous()
+
+        a_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)       # fp32 pre-activations: the accumulators, unrounded
+        k.conv([hb, x], g, _fwd_pack(pk_zr, k, wzr, segs), bzr, 2 * C, False, a_zr, res(pzr))
         z, r, rh = (torch.empty(M, C, device=dev, dtype=torch.float32) for _ in range(3))
         ops.gru_gates_zr(a_zr, h, z, r, rh)
+        rh = k.operand(rh)
         a_q = torch.empty(M, C, device=dev, dtype=torch.float32)
-        ops.conv2d([rh, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack(pk_q, wq, segs), bq.detach().float().contiguous(), C, EPI_LINEAR,
-                   False, 1.0, a_q, None, None, None, ws, None if pq is None else pq.detach().float().contiguous())
+        k.conv([rh, x], g, _fwd_pack(pk_q, k, wq, segs), bq.detach().float().contiguous(), C, False, a_q, res(pq))
         q, hn = torch.empty_like(a_q), torch.empty_like(a_q)
         ops.gru_gates_q(a_q, z, h, q, hn)
         ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr = g, x_real, pk_zr, pk_q, wzr
         ctx.has_p = (pzr is not None, pq is not None)
-        ctx.save_for_backward(h, x, z, r, q, rh, wq)
+        ctx.p_dtypes = (None if pzr is None else pzr.dtype, None if pq is None else pq.dtype)
+        ctx.save_for_backward(h, x, z, r, q, rh, wq)      # r*h as the operand it was; h's operand form is derived again in backward
         return hn
 
     @staticmethod
     def backward(ctx, dhn):
         ops = torch.ops.pfk
-        if ctx.precision != "fp32":
-            return _gru_backward_b16(ctx, dhn)
         h, x, z, r, q, rh, wq = ctx.saved_tensors
-        g, x_real, pk_zr, pk_q, wzr = ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr
+        k, g, x_real, pk_zr, pk_q, wzr = _KERNELS[ctx.precision], ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr
         M, C = h.shape
         Cx = x.shape[1]
         dev = h.device
-        ws = _workspace(dev)
         segs = [(0, C, C), (C, x_real, Cx)]
         dhn = dhn.float()
         if dhn.stride(1) != 1:
@@ -449,120 +440,36 @@ class _GruPass(torch.autograd.Function):
 
         def dgrad(dy, packs, weight, i, n_out, residual=None):
             out = torch.empty(M, n_out, device=dev, dtype=torch.float32)
-            ops.conv2d([dy], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack(packs, i, weight, segs[i], dy.shape[1]), None, n_out, EPI_LINEAR,
-                       False, 1.0, out, None, None, None, ws, residual)
+            k.conv([dy], g, _dgrad_pack(packs, k, i, weight, segs[i], dy.shape[1]), None, n_out, False, out, residual)
             return out
 
-        d_rh = dgrad(da_q, pk_q, wq, 0, C)
-        dx = dgrad(da_q, pk_q, wq, 1, Cx)
+        dy_q = k.operand(da_q)             # each pre-activation gradient in operand form once: both dgrads and the wgrad read it
+        d_rh = dgrad(dy_q, pk_q, wq, 0, C)
+        dx = dgrad(dy_q, pk_q, wq, 1, Cx)
         ops.gru_backward_zr(d_rh, h, r, da_zr, dh)
-        dh = dgrad(da_zr, pk_zr, wzr, 0, C, residual=dh)          # + dh through the epilogue
-        dx = dgrad(da_zr, pk_zr, wzr, 1, Cx, residual=dx)
+        dy_zr = k.operand(da_zr)
+        dh = dgrad(dy_zr, pk_zr, wzr, 0, C, residual=dh)          # + dh through the epilogue's fp32 residual input
+        dx = dgrad(dy_zr, pk_zr, wzr, 1, Cx, residual=dx).to(x.dtype)
+        hb = k.operand(h)
         reals = [n for _, n, _ in segs]
-        if pk_zr.accumulate and pk_zr.alias is not None and pk_q.alias is not None:
-            # step-scoped entries: every pass of every iteration adds into one buffer per parameter; `_Flush` returns the totals
-            first = pk_q.acc is None
-            if first:
-                dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
-                dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
-                pk_q.acc = {0: dwq, 1: dbq}
-                pk_zr.extra["dwzr"], pk_zr.extra["dbzr"] = dwzr, dbzr
-                pk_zr.acc = {0: dwzr[:C], 1: dwzr[C:], 2: dbzr[:C], 3: dbzr[C:]}      # (wz, wr, bz, br) as given to _Flush
-            ops.conv_wgrad_unpacked([rh, x], da_q, g.B, g.H, g.W, g.kh, g.kw, pk_q.acc[0], pk_q.acc[1], reals, 1, not first)
-            ops.conv_wgrad_unpacked([h, x], da_zr, g.B, g.H, g.W, g.kh, g.kw, pk_zr.extra["dwzr"], pk_zr.extra["dbzr"], reals, 1, not first)
-            return (dh, dx, None, None, None, None, None, None, None, None, None, None,
-                    da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None, None)
-        dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
-        ops.conv_wgrad_unpacked([rh, x], da_q, g.B, g.H, g.W, g.kh, g.kw, dwq, dbq, reals, 1)
-        dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
-        ops.conv_wgrad_unpacked([h, x], da_zr, g.B, g.H, g.W, g.kh, g.kw, dwzr, dbzr, reals, 1)
-        return (dh, dx, dwzr[:C], dwzr[C:], dwq, dbzr[:C], dbzr[C:], dbq, None, None, None, None,
-                da_zr if ctx.has_p[0] else None, da_q if ctx.has_p[1] else None, None)
-
-
-def _gru_forward_b16(ctx, h, x, wz, wr, wq, bz, br, bq, g, x_real, pk_zr, pk_q, pzr, pq):
-    ops = torch.ops.pfk
-    h = h.float().contiguous()
-    x = _rows_b16(x)
-    M, C = h.shape
-    dev = h.device
-    assert C % 8 == 0 and x.shape[1] % 8 == 0
-    if "wzr" not in pk_zr.extra:      # once per (parameter version): the z and r convolutions run as one
-        pk_zr.extra["wzr"] = torch.cat([wz.detach(), wr.detach()], 0).float()
-        pk_zr.extra["bzr"] = torch.cat([bz.detach(), br.detach()], 0).float().contiguous()
-    wzr, bzr = pk_zr.extra["wzr"], pk_zr.extra["bzr"]
-    segs = [(0, C, C), (C, x_real, x.shape[1])]
-    hb = h.to(BF16)                    # the convolutions' operand; the state itself stays fp32
-
-    def res(p):
-        return None if p is None else (p.detach() if p.dtype == BF16 else p.detach().float()).contiguous()
-
-    a_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)       # fp32 pre-activations: the accumulators, unrounded
-    ops.conv2d_b16([hb, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(pk_zr, wzr, segs, 2 * C), bzr, 2 * C, EPI_LINEAR, False, 1.0,
-                   a_zr, None, None, None, None, res(pzr))
-    z, r, rh = (torch.empty(M, C, device=dev, dtype=torch.float32) for _ in range(3))
-    ops.gru_gates_zr(a_zr, h, z, r, rh)
-    rhb = rh.to(BF16)
-    a_q = torch.empty(M, C, device=dev, dtype=torch.float32)
-    ops.conv2d_b16([rhb, x], g.B, g.H, g.W, g.kh, g.kw, _fwd_pack_b16(pk_q, wq, segs, C), bq.detach().float().contiguous(), C,
-                   EPI_LINEAR, False, 1.0, a_q, None, None, None, None, res(pq))
-    q, hn = torch.empty_like(a_q), torch.empty_like(a_q)
-    ops.gru_gates_q(a_q, z, h, q, hn)
-    ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr = g, x_real, pk_zr, pk_q, wzr
-    ctx.has_p = (pzr is not None, pq is not None)
-    ctx.p_dtypes = (None if pzr is None else pzr.dtype, None if pq is None else pq.dtype)
-    ctx.save_for_backward(h, x, z, r, q, rhb, wq)
-    return hn
-
-
-def _gru_backward_b16(ctx, dhn):
-    ops = torch.ops.pfk
-    h, x, z, r, q, rhb, wq = ctx.saved_tensors
-    g, x_real, pk_zr, pk_q, wzr = ctx.g, ctx.x_real, ctx.pk_zr, ctx.pk_q, ctx.wzr
-    M, C = h.shape
-    Cx = x.shape[1]
-    dev = h.device
-    segs = [(0, C, C), (C, x_real, Cx)]
-    dhn = dhn.float()
-    if dhn.stride(1) != 1:
-        dhn = dhn.contiguous()
-    da_q = torch.empty(M, C, device=dev, dtype=torch.float32)
-    da_zr = torch.empty(M, 2 * C, device=dev, dtype=torch.float32)
-    dh = torch.empty(M, C, device=dev, dtype=torch.float32)
-    ops.gru_backward_q(dhn, z, q, h, da_q, da_zr, dh)
-
-    def dgrad(dy, packs, weight, i, n_out, residual=None):
-        out = torch.empty(M, n_out, device=dev, dtype=torch.float32)
-        ops.conv2d_b16([dy], g.B, g.H, g.W, g.kh, g.kw, _dgrad_pack_b16(packs, i, weight, segs[i], dy.shape[1]), None, n_out,
-                       EPI_LINEAR, False, 1.0, out, None, None, None, None, residual)
-        return out
-
-    da_qb = da_q.to(BF16)
-    d_rh = dgrad(da_qb, pk_q, wq, 0, C)
-    dx = dgrad(da_qb, pk_q, wq, 1, Cx)
-    ops.gru_backward_zr(d_rh, h, r, da_zr, dh)
-    da_zrb = da_zr.to(BF16)
-    dh = dgrad(da_zrb, pk_zr, wzr, 0, C, residual=dh)          # + dh through the epilogue's fp32 residual input
-    dx = dgrad(da_zrb, pk_zr, wzr, 1, Cx, residual=dx).to(x.dtype)
-    hb = h.to(BF16)
-    reals = [n for _, n, _ in segs]
-    gp = (None if not ctx.has_p[0] else da_zr.to(ctx.p_dtypes[0]), None if not ctx.has_p[1] else da_q.to(ctx.p_dtypes[1]))
-    if pk_zr.accumulate and pk_zr.alias is not None and pk_q.alias is not None:
-        first = pk_q.acc is None
+        gp = (None if not ctx.has_p[0] else da_zr.to(ctx.p_dtypes[0]), None if not ctx.has_p[1] else da_q.to(ctx.p_dtypes[1]))
+        # step-scoped entries: every pass of every iteration adds into one buffer per parameter (allocated by the first) and
+        # `_Flush` returns the totals; any other returns its own
+        accumulate = pk_zr.accumulate and pk_zr.alias is not None and pk_q.alias is not None
+        first = not accumulate or pk_q.acc is None
         if first:
             dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
             dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
-            pk_q.acc = {0: dwq, 1: dbq}
-            pk_zr.extra["dwzr"], pk_zr.extra["dbzr"] = dwzr, dbzr
-            pk_zr.acc = {0: dwzr[:C], 1: dwzr[C:], 2: dbzr[:C], 3: dbzr[C:]}      # (wz, wr, bz, br) as given to _Flush
-        ops.conv_wgrad_unpacked_b16([rhb, x], da_qb, g.B, g.H, g.W, g.kh, g.kw, pk_q.acc[0], pk_q.acc[1], reals, not first)
-        ops.conv_wgrad_unpacked_b16([hb, x], da_zrb, g.B, g.H, g.W, g.kh, g.kw, pk_zr.extra["dwzr"], pk_zr.extra["dbzr"], reals, not first)
-        return (dh, dx, None, None, None, None, None, None, None, None, None, None, gp[0], gp[1], None)
-    dwq, dbq = torch.empty(wq.shape, device=dev, dtype=torch.float32), torch.empty(C, device=dev, dtype=torch.float32)
-    ops.conv_wgrad_unpacked_b16([rhb, x], da_qb, g.B, g.H, g.W, g.kh, g.kw, dwq, dbq, reals, False)
-    dwzr, dbzr = torch.empty(wzr.shape, device=dev, dtype=torch.float32), torch.empty(2 * C, device=dev, dtype=torch.float32)
-    ops.conv_wgrad_unpacked_b16([hb, x], da_zrb, g.B, g.H, g.W, g.kh, g.kw, dwzr, dbzr, reals, False)
-    return (dh, dx, dwzr[:C], dwzr[C:], dwq, dbzr[:C], dbzr[C:], dbq, None, None, None, None, gp[0], gp[1], None)
+            if accumulate:
+                pk_q.acc = {0: dwq, 1: dbq}
+                pk_zr.extra["dwzr"], pk_zr.extra["dbzr"] = dwzr, dbzr
+                pk_zr.acc = {0: dwzr[:C], 1: dwzr[C:], 2: dbzr[:C], 3: dbzr[C:]}      # (wz, wr, bz, br) as given to _Flush
+        else:
+            dwq, dbq, dwzr, dbzr = pk_q.acc[0], pk_q.acc[1], pk_zr.extra["dwzr"], pk_zr.extra["dbzr"]
+        k.wgrad([rh, x], dy_q, g, dwq, dbq, reals, not first)
+        k.wgrad([hb, x], dy_zr, g, dwzr, dbzr, reals, not first)
+        gw = (None,) * 6 if accumulate else (dwzr[:C], dwzr[C:], dwq, dbzr[:C], dbzr[C:], dbq)
+        return (dh, dx, *gw, None, None, None, None, gp[0], gp[1], None)
 
 
 def conv_pm(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, H: int, W: int,
@@ -792,16 +699,6 @@ def _nchw(x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
     return x.view(B, H, W, x.shape[1]).permute(0, 3, 1, 2)
 
 
-def _pad4(x: torch.Tensor) -> torch.Tensor:
-    c = x.shape[1]
-    return x if c % 4 == 0 else F.pad(x, (0, round_up(c, 4) - c))
-
-
-def _pad8(x: torch.Tensor) -> torch.Tensor:
-    c = x.shape[1]
-    return x if c % 8 == 0 else F.pad(x, (0, round_up(c, 8) - c))
-
-
 def _context_terms(P: Dict[str, torch.Tensor], spec, i: torch.Tensor, B: int, H: int, W: int, cache: dict, owner: torch.Tensor,
                    acc: bool, precision: str = "fp32"):
     """The loop-invariant part of the GRU (raft/update.py:60-71 / :27-30): the gate convolutions run over cat([h, inp, motion])
@@ -864,20 +761,20 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
     ``precision="bf16"``: the convolutions on the bf16 matrix cores (module docstring); inputs and outputs stay fp32 rows.
     ``attention`` (GMA, `spec.aggregate`): the map [B, 1, N, N] of this forward, fp32; its gradient flows back to it."""
     acc = accumulate_wgrad and cache is not None
-    b16 = check_precision(precision) == "bf16"
+    k = _KERNELS[check_precision(precision)]
+    b16 = k.dtype == BF16
     if spec.aggregate and attention is None:
         raise ValueError("update_block_train_pm: a block with GMA's aggregate branch needs the attention map [B, 1, N, N]")
-    pad = _pad8 if b16 else _pad4
 
     def conv(srcs, name, relu=False, real=None, prec=precision, out_fp32=False):
         w = P[name + ".weight"]
         return conv_pm(srcs, w, P.get(name + ".bias"), B, H, W, relu, real, packs_for(cache, name, [w], acc), 1, prec, out_fp32)
 
     # motion encoder (update.py:104-112 / :85-91)
-    cor = conv([pad(c)], "encoder.convc1", True, [c.shape[1]])
+    cor = conv([k.pad(c)], "encoder.convc1", True, [c.shape[1]])
     if spec.c2:
         cor = conv([cor], "encoder.convc2", True)
-    flo = conv([_pad4(f)], "encoder.convf1", True, [2], "fp32")      # 7x7: outside pfk_conv2d_b16's 32 taps, fp32 in either mode
+    flo = conv([_KERNELS["fp32"].pad(f)], "encoder.convf1", True, [2], "fp32")      # 7x7: outside pfk_conv2d_b16's 32 taps, fp32 in either mode
     flo = conv([flo], "encoder.convf2", True)
     out = conv([cor, flo], "encoder.conv", True)
     # x = [inp | motion features (encoder out | flow) | zero pad to a multiple of 4] in ONE concatenation (update.py:112 + :146);
@@ -895,16 +792,15 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
         att = _attention_state(attention, B, H, W, cache, acc, precision)       # packed once per step (P and P^T, fp32 or bf16)
         agg = _AttnMatmul.apply(att.target(attention), v, att)                                 # fp32 rows in either precision
         parts = [mf, mf + P["aggregator.gamma"] * agg] if hoist else [i, mf, mf + P["aggregator.gamma"] * agg]
-    xq = 8 if b16 else 4
-    if x_real % xq:
-        zkey = ("zpad", i.shape[0], round_up(x_real, xq) - x_real, i.device)
+    if x_real % k.quantum:
+        zkey = ("zpad", i.shape[0], round_up(x_real, k.quantum) - x_real, i.device)
         z = cache.get(zkey) if cache is not None else None
         if z is None:
-            z = torch.zeros(i.shape[0], round_up(x_real, xq) - x_real, device=i.device, dtype=torch.float32)
+            z = torch.zeros(i.shape[0], round_up(x_real, k.quantum) - x_real, device=i.device, dtype=torch.float32)
             if cache is not None:
                 cache[zkey] = z
         parts.append(z)
-    x = torch.cat([t.to(BF16) for t in parts], 1) if b16 else torch.cat(parts, 1)
+    x = torch.cat([t.to(k.dtype) for t in parts], 1)
     # GRU passes (update.py:58-73 / :24-32): one fused autograd node per pass (z and r share a convolution)
     for kh, kw, sfx in spec.gru_passes:
         names = [f"gru.conv{k}{sfx}" for k in "zrq"]

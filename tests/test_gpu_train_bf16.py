@@ -219,3 +219,32 @@ def test_bf16_accumulating_and_plain_paths_agree(gpu):
     (gw0, gb0), (gw1, gb1) = grads(False), grads(True)
     assert float(gw0.abs().max()) > 0
     assert float((gw1 - gw0).abs().max()) <= 1e-6 * float(gw0.abs().max()) and float((gb1 - gb0).abs().max()) <= 1e-6 * float(gb0.abs().max())
+
+
+# ------------------------------------------------------------------------------------------------------------------ (e)
+def test_one_conv_packs_under_both_precisions(gpu):
+    """One `ConvPacks` entry used under fp32, then bf16, then fp32 again keeps each precision's packed weights (forward and data
+    gradient) apart: every output and gradient is bit-identical to the same call with a `ConvPacks` of its own — the node that
+    tests (a) and (d) above hold against float64 and CPU autocast."""
+    from ptlflow_amd.train import ConvPacks, conv_pm
+    g = torch.Generator().manual_seed(23)
+    B, H, W, cin, cout = 1, 8, 12, 40, 48
+    M = B * H * W
+    w = (torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(9 * cin)).to(gpu)
+    b = (torch.randn(cout, generator=g) * 0.1).to(gpu)
+    x = torch.randn(M, cin, generator=g).to(gpu)               # fp32 rows: the bf16 node casts them
+    gout = torch.randn(M, cout, generator=g).to(gpu)
+
+    def run(precision, packs):
+        wp, bp, xp = (t.clone().requires_grad_() for t in (w, b, x))
+        out = conv_pm([xp], wp, bp, B, H, W, relu=True, packs=packs, precision=precision)
+        out.backward(gout.to(out.dtype))
+        return {"out": out.detach(), "dW": wp.grad, "db": bp.grad, "dx": xp.grad}
+
+    shared = ConvPacks()
+    for precision in ("fp32", "bf16", "fp32"):
+        got, want = run(precision, shared), run(precision, ConvPacks())
+        for name, t in want.items():
+            assert t is not None and bool(t.isfinite().all()) and float(t.float().abs().max()) > 0, (precision, name)
+            assert got[name].dtype == t.dtype and torch.equal(got[name], t), f"{precision}: {name} differs with the shared ConvPacks"
+    assert {k[0] for k in shared.packed} == {"fp32", "bf16"}
