@@ -468,6 +468,47 @@ int pfk_dwconv_layernorm_b16(const void* in_bf16, int in_ld, const float* dw_wei
                              const float* ln_bias, float eps, void* out_bf16, int out_ld, int B, int H, int W, int C, int k,
                              pfk_stream_t stream);
 
+/* ---- training the ConvNeXt block (K12d; additions, ABI 7) ---------------------------------------------------------------------
+ * All fp32, pixel-major rows [M = B*H*W][ld] of which only the C real columns are read or written (ld may be larger), C % 4 == 0,
+ * 4 <= C <= 512, rows 16-byte aligned with ld % 4 == 0, k odd <= 7.  Deterministic: no atomics, sums over pixels in an order that
+ * depends on the shape only.  Arguments are validated before the device is touched: PFK_ERR_BAD_ARG / PFK_ERR_ALIGNMENT.
+ *
+ * pfk_dwconv_layernorm_train_f32: pfk_dwconv_layernorm_f32 with `out` bit-identical to that entry on the same inputs, and in
+ * addition xhat[p*xhat_ld + c] = (u - mean) * rstd, the normalised value before weight and bias, and rstd[p].  No output may
+ * overlap the input rows or another output. */
+int pfk_dwconv_layernorm_train_f32(const float* in, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                                   const float* ln_bias, float eps, float* out, int out_ld, float* xhat, int xhat_ld, float* rstd,
+                                   int B, int H, int W, int C, int k, pfk_stream_t stream);
+
+/* pfk_layernorm_bwd_f32: backward of the LayerNorm from what the train forward saved.  With g = dy * ln_weight per pixel:
+ *   du[p][c] = rstd[p] * (g[c] - mean_c(g) - xhat[p][c] * mean_c(g * xhat)),  dgamma[c] = sum_p dy[p][c] * xhat[p][c],
+ *   dbeta[c] = sum_p dy[p][c].
+ * du must not overlap dy or xhat.  workspace: pfk_layernorm_bwd_workspace_bytes(M, C) bytes, 16-byte aligned (per-block partial
+ * column sums, reduced in a fixed order). */
+long long pfk_layernorm_bwd_workspace_bytes(long long M, int C);
+int pfk_layernorm_bwd_f32(const float* xhat, int xhat_ld, const float* rstd, const float* ln_weight, const float* dy, int dy_ld,
+                          float* du, int du_ld, float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M,
+                          int C, pfk_stream_t stream);
+
+/* pfk_dwconv_bwd_f32: backward of the depthwise k x k "same" convolution (R = k/2): `in` the forward's input rows, `du` the gradient
+ * of its output, dw_weight [C][k*k]:
+ *   dx[p][c]            = sum_{ky,kx} dw_weight[c][ky*k+kx] * du[(y-ky+R, x-kx+R)][c]    (zero outside the image, never across images)
+ *   dweight[c][ky*k+kx] = sum_p du[p][c] * in[(y+ky-R, x+kx-R)][c]
+ *   dbias[c]            = sum_p du[p][c]                                                  (dbias may be NULL)
+ * dx must not overlap du or in.  workspace: pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k) bytes, 16-byte aligned: one partial
+ * [C][k*k + 1] per block slice of tiles (at most 64), summed in slice order. */
+long long pfk_dwconv_bwd_workspace_bytes(int B, int H, int W, int C, int k);
+int pfk_dwconv_bwd_f32(const float* in, int in_ld, const float* du, int du_ld, const float* dw_weight, float* dx, int dx_ld,
+                       float* dweight, float* dbias, void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k,
+                       pfk_stream_t stream);
+
+/* pfk_gelu_f32 / pfk_gelu_bwd_f32: nn.GELU() (approximate='none') on rows, PFK_EPI_LINEAR_GELU's formula, and its derivative:
+ *   y = 0.5 x (1 + erf(x / sqrt 2)),   dx = dy (0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi))
+ * (large |x|: 0 or dy, never NaN).  Any C % 4 == 0, C >= 4; out of place. */
+int pfk_gelu_f32(const float* x, long long x_ld, float* y, long long y_ld, long long M, int C, pfk_stream_t stream);
+int pfk_gelu_bwd_f32(const float* x, long long x_ld, const float* dy, long long dy_ld, float* dx, long long dx_ld, long long M, int C,
+                     pfk_stream_t stream);
+
 /* pfk_convex_upsample_info_pm_f32: SEARAFT.upsample_data (sea_raft/sea_raft.py:147-163).  flow_pm [M][flow_ld] (channels 0..1),
  * info_pm [M][info_ld] (channels 0..n-1, 1 <= n <= 8), mask [M][mask_ld] fp32 logits with channel c = k*64 + sy*8 + sx, already
  * multiplied by 0.25 (16-byte aligned rows, mask_ld % 4 == 0, mask_ld >= 576).  Softmax over the nine taps; convex combination of

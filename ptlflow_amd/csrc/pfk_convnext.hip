@@ -27,11 +27,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <int K>
+// TRAIN (pfk_dwconv_layernorm_train_f32): the same arithmetic in the same order — `out` has the same bits — and the normalised value
+// (u - mean) * rstd goes to `xhat`, the pixel's rstd to `rstd_out`: what pfk_layernorm_bwd_f32 reads.
+template <int K, bool TRAIN = false>
 __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_kernel(const float* __restrict__ in, int in_ld, const float* __restrict__ dw_w,
                                                                const float* __restrict__ dw_b, const float* __restrict__ ln_w,
                                                                const float* __restrict__ ln_b, float eps, float* __restrict__ out,
-                                                               int out_ld, int H, int W, int C) {
+                                                               int out_ld, int H, int W, int C, float* __restrict__ xhat = nullptr,
+                                                               int xhat_ld = 0, float* __restrict__ rstd_out = nullptr) {
   constexpr int R = K / 2, HY = DW_TY + K - 1, HX = DW_TX + K - 1;
   __shared__ f32x4 halo[HY * HX * DW_G];          // [halo pixel][group]: 17.5 KB at k = 7
   __shared__ f32x4 wts[K * K * DW_G];             // [tap][group]
@@ -107,26 +110,42 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_kernel(const float* __re
     }
     const float rstd = 1.0f / sqrtf(wave_sum(s2) * inv_c + eps);
     float* orow = out + (img + (long long)y * W + x) * out_ld;
+    if constexpr (TRAIN) {
+      float* xrow = xhat + (img + (long long)y * W + x) * xhat_ld;
+      if (lane == 0) rstd_out[img + (long long)y * W + x] = rstd;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int c = lane + 64 * t;
-      if (c < C) orow[c] = (v[t] - mean) * rstd * ln_w[c] + ln_b[c];
+      for (int t = 0; t < NT; ++t) {
+        const int c = lane + 64 * t;
+        if (c < C) {
+          const float xh = (v[t] - mean) * rstd;
+          xrow[c] = xh;
+          orow[c] = xh * ln_w[c] + ln_b[c];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int c = lane + 64 * t;
+        if (c < C) orow[c] = (v[t] - mean) * rstd * ln_w[c] + ln_b[c];
+      }
     }
   }
 }
 
-template <int K>
+template <int K, bool TRAIN = false>
 int launch_dwconv_ln(const float* in, int in_ld, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float eps,
-                     float* out, int out_ld, int B, int H, int W, int C, hipStream_t st) {
+                     float* out, int out_ld, int B, int H, int W, int C, hipStream_t st, float* xhat = nullptr, int xhat_ld = 0,
+                     float* rstd = nullptr) {
   const size_t smem = (size_t)DW_PIX * (C + 4) * sizeof(float);
-  auto kern = dwconv_ln_kernel<K>;
+  auto kern = dwconv_ln_kernel<K, TRAIN>;
   static pfk_device_once attr_once;
   attr_once.run([&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)((size_t)DW_PIX * (DW_MAX_C + 4) * sizeof(float)));
   });
   dim3 grid((unsigned)((W + DW_TX - 1) / DW_TX), (unsigned)((H + DW_TY - 1) / DW_TY), (unsigned)B);
-  hipLaunchKernelGGL(kern, grid, dim3(DW_THREADS), smem, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C);
+  hipLaunchKernelGGL(kern, grid, dim3(DW_THREADS), smem, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C, xhat, xhat_ld,
+                     rstd);
   return pfk_launch_status();
 }
 
@@ -294,6 +313,34 @@ int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight,
     case 3: return launch_dwconv_ln<3>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     case 5: return launch_dwconv_ln<5>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     default: return launch_dwconv_ln<7>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+  }
+}
+
+int pfk_dwconv_layernorm_train_f32(const float* in, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                                   const float* ln_bias, float eps, float* out, int out_ld, float* xhat, int xhat_ld, float* rstd,
+                                   int B, int H, int W, int C, int k, pfk_stream_t stream) {
+  if (!in || !dw_weight || !ln_weight || !ln_bias || !out || !xhat || !rstd || B <= 0 || H <= 0 || W <= 0 || C < 4 || in_ld < C ||
+      out_ld < C || xhat_ld < C)
+    return PFK_ERR_BAD_ARG;
+  if (k < 1 || !(k & 1) || k > 7 || C > DW_MAX_C) return PFK_ERR_BAD_ARG;
+  if (B > 65535 || (H + DW_TY - 1) / DW_TY > 65535) return PFK_ERR_UNSUPPORTED;
+  if ((C & 3) || (in_ld & 3) || !pfk_aligned16(in)) return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  // neither output may overlap the input rows (other blocks still read the halo of pixels this block has written)
+  const char* ib = reinterpret_cast<const char*>(in);
+  const char* ie = reinterpret_cast<const char*>(in + (M - 1) * in_ld + C);
+  const char* ob = reinterpret_cast<const char*>(out);
+  const char* oe = reinterpret_cast<const char*>(out + (M - 1) * out_ld + C);
+  const char* xb = reinterpret_cast<const char*>(xhat);
+  const char* xe = reinterpret_cast<const char*>(xhat + (M - 1) * xhat_ld + C);
+  if ((ob < ie && ib < oe) || (xb < ie && ib < xe) || (xb < oe && ob < xe)) return PFK_ERR_BAD_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k) {
+    case 1: return launch_dwconv_ln<1, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    case 3: return launch_dwconv_ln<3, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    case 5: return launch_dwconv_ln<5, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    default: return launch_dwconv_ln<7, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
   }
 }
 

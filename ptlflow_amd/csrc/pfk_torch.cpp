@@ -577,6 +577,76 @@ void dwconv_layernorm(const Tensor& in, const Tensor& dw_weight, const c10::opti
                                     out.stride(0), B, H, W, C, k, cur_stream()), "dwconv_layernorm");
 }
 
+// ---- K12d: training the ConvNeXt block (pfk_convnext_bwd.hip).  Row views [M, C] of wider buffers are fine; only C columns are touched.
+namespace {
+void check_vec(const Tensor& t, int64_t n, const char* name) {
+  check_dev_f32(t, name);
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n, name, " must be contiguous with ", n, " elements");
+}
+}  // namespace
+
+// dwconv_layernorm that also saves xhat [M, >= C] and rstd [M] for the backward; `out` has dwconv_layernorm's bits
+void dwconv_layernorm_train(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                            const Tensor& ln_bias, double eps, Tensor out, Tensor xhat, Tensor rstd, int64_t B, int64_t H, int64_t W,
+                            int64_t k) {
+  OpScope scope(in);
+  check_pm(in, "in"); check_pm(out, "out"); check_pm(xhat, "xhat");
+  const int64_t C = in.size(1), M = B * H * W;
+  TORCH_CHECK(in.size(0) == M && out.size(0) == M && xhat.size(0) == M && out.size(1) == C && xhat.size(1) == C,
+              "dwconv_layernorm_train: in / out / xhat [B*H*W, C]");
+  check_vec(dw_weight, C * k * k, "dw_weight"); check_vec(ln_weight, C, "ln_weight"); check_vec(ln_bias, C, "ln_bias");
+  check_vec(rstd, M, "rstd");
+  const float* db = nullptr;
+  if (dw_bias.has_value()) { check_vec(*dw_bias, C, "dw_bias"); db = fptr(*dw_bias); }
+  check_ok(pfk_dwconv_layernorm_train_f32(fptr(in), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps,
+                                          fptr(out), out.stride(0), fptr(xhat), xhat.stride(0), fptr(rstd), B, H, W, C, k, cur_stream()),
+           "dwconv_layernorm_train");
+}
+
+void layernorm_bwd(const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy, Tensor du, Tensor dgamma,
+                   Tensor dbeta) {
+  OpScope scope(xhat);
+  check_pm(xhat, "xhat"); check_pm(dy, "dy"); check_pm(du, "du");
+  const int64_t M = xhat.size(0), C = xhat.size(1);
+  TORCH_CHECK(dy.size(0) == M && dy.size(1) == C && du.size(0) == M && du.size(1) == C, "layernorm_bwd: xhat / dy / du [M, C]");
+  check_vec(rstd, M, "rstd"); check_vec(ln_weight, C, "ln_weight"); check_vec(dgamma, C, "dgamma"); check_vec(dbeta, C, "dbeta");
+  const long long need = pfk_layernorm_bwd_workspace_bytes(M, C);
+  Tensor ws = at::empty({(int64_t)need}, xhat.options().dtype(at::kByte));
+  check_ok(pfk_layernorm_bwd_f32(fptr(xhat), xhat.stride(0), fptr(rstd), fptr(ln_weight), fptr(dy), dy.stride(0), fptr(du), du.stride(0),
+                                 fptr(dgamma), fptr(dbeta), ws.data_ptr(), need, M, C, cur_stream()), "layernorm_bwd");
+}
+
+void dwconv_bwd(const Tensor& in, const Tensor& du, const Tensor& dw_weight, Tensor dx, Tensor dweight, const c10::optional<Tensor>& dbias,
+                int64_t B, int64_t H, int64_t W, int64_t k) {
+  OpScope scope(in);
+  check_pm(in, "in"); check_pm(du, "du"); check_pm(dx, "dx");
+  const int64_t C = in.size(1), M = B * H * W;
+  TORCH_CHECK(in.size(0) == M && du.size(0) == M && dx.size(0) == M && du.size(1) == C && dx.size(1) == C, "dwconv_bwd: in / du / dx [B*H*W, C]");
+  check_vec(dw_weight, C * k * k, "dw_weight"); check_vec(dweight, C * k * k, "dweight");
+  float* db = nullptr;
+  if (dbias.has_value()) { check_vec(*dbias, C, "dbias"); db = fptr(*dbias); }
+  const long long need = pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k);
+  Tensor ws = at::empty({(int64_t)need}, in.options().dtype(at::kByte));
+  check_ok(pfk_dwconv_bwd_f32(fptr(in), in.stride(0), fptr(du), du.stride(0), fptr(dw_weight), fptr(dx), dx.stride(0), fptr(dweight), db,
+                              ws.data_ptr(), need, B, H, W, C, k, cur_stream()), "dwconv_bwd");
+}
+
+void gelu_rows(const Tensor& x, Tensor y) {
+  OpScope scope(x);
+  check_pm(x, "x"); check_pm(y, "y");
+  TORCH_CHECK(y.size(0) == x.size(0) && y.size(1) == x.size(1), "gelu: x / y [M, C]");
+  check_ok(pfk_gelu_f32(fptr(x), x.stride(0), fptr(y), y.stride(0), x.size(0), x.size(1), cur_stream()), "gelu");
+}
+
+void gelu_rows_bwd(const Tensor& x, const Tensor& dy, Tensor dx) {
+  OpScope scope(x);
+  check_pm(x, "x"); check_pm(dy, "dy"); check_pm(dx, "dx");
+  TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(1) == x.size(1) && dx.size(0) == x.size(0) && dx.size(1) == x.size(1),
+              "gelu_bwd: x / dy / dx [M, C]");
+  check_ok(pfk_gelu_bwd_f32(fptr(x), x.stride(0), fptr(dy), dy.stride(0), fptr(dx), dx.stride(0), x.size(0), x.size(1), cur_stream()),
+           "gelu_bwd");
+}
+
 // fused mask conv2 + softmax + convex upsampling: x [M, cin] (a view of the fh|mask hidden buffer), weight / bias row-permuted (pfk.h)
 void mask_upsample(const Tensor& x, const Tensor& weight_perm, const c10::optional<Tensor>& bias_perm, double scale,
                    const Tensor& flow_pm, Tensor out) {
@@ -1215,6 +1285,13 @@ TORCH_LIBRARY(pfk, m) {
   m.def("convex_upsample_info_pm(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor(a!) flow_out, Tensor(b!) info_out) -> ()");
   m.def("dwconv_layernorm(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, Tensor(a!) out, "
         "int B, int H, int W, int k) -> ()");
+  m.def("dwconv_layernorm_train(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
+        "Tensor(a!) out, Tensor(b!) xhat, Tensor(c!) rstd, int B, int H, int W, int k) -> ()");
+  m.def("layernorm_bwd(Tensor xhat, Tensor rstd, Tensor ln_weight, Tensor dy, Tensor(a!) du, Tensor(b!) dgamma, Tensor(c!) dbeta) -> ()");
+  m.def("dwconv_bwd(Tensor inp, Tensor du, Tensor dw_weight, Tensor(a!) dx, Tensor(b!) dweight, Tensor(c!)? dbias, int B, int H, int W, "
+        "int k) -> ()");
+  m.def("gelu(Tensor x, Tensor(a!) y) -> ()");
+  m.def("gelu_bwd(Tensor x, Tensor dy, Tensor(a!) dx) -> ()");
   m.def("dwconv_layernorm_b16(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
         "Tensor(a!) out, int B, int H, int W, int k) -> ()");
   m.def("conv2d_gelu_b16(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, float scale, "
@@ -1255,6 +1332,11 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("convex_upsample_info_pm", &convex_upsample_info_pm);
   m.impl("dwconv_layernorm", &dwconv_layernorm);
   m.impl("dwconv_layernorm_b16", &dwconv_layernorm_b16);
+  m.impl("dwconv_layernorm_train", &dwconv_layernorm_train);
+  m.impl("layernorm_bwd", &layernorm_bwd);
+  m.impl("dwconv_bwd", &dwconv_bwd);
+  m.impl("gelu", &gelu_rows);
+  m.impl("gelu_bwd", &gelu_rows_bwd);
   m.impl("conv2d_gelu_b16", &conv2d_gelu_b16);
   m.impl("convex_upsample_info_pm_b16", &convex_upsample_info_pm_b16);
   m.impl("upflow8", &upflow8);

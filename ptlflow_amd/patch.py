@@ -581,7 +581,8 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
-               sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32") -> torch.nn.Module:
+               sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
+               sea_raft_train: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -611,10 +612,18 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     torch.autocast(bfloat16); hidden state, flow and parameter gradients stay fp32.  The conditions of the fp32 training path
     apply unchanged (576 mask channels, no external aggregate).  GMA's update block trains natively in both precisions: its
     `attention` argument goes through to `train._AttnMatmul` and its gradient flows back to the caller's map.
-    A second call with another value switches it."""
+    A second call with another value switches it.
+    ``sea_raft_train`` (default False; needs ``sea_raft_update=True`` or ``"fp32"``, anything else raises ValueError): the SEA-RAFT
+    seams also serve the calls that carry a gradient graph — CUDA fp32 tensors, grad mode on, an input or a parameter that requires
+    grad, outside autocast — on the native training path of ptlflow_amd/train_sea.py: the update block (motion
+    encoder and ConvNeXt blocks) and the `flow_head` / `upsample_weight` heads on any such ``[B, 128, H, W]`` input, forward and
+    backward, counted in each wrapper's ``train_calls``.  `upsample_data` in a gradient graph stays the model's own method.  Off:
+    such calls reach the model's own modules, as before."""
     from .train import check_precision
     check_precision(train_precision, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
+    if sea_raft_train and sea_precision != "fp32":
+        raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path is fp32), got {sea_raft_update!r}")
     sea_enc_precision = _sea_precision(sea_raft_encoders, "sea_raft_encoders")
     load_native()
     mod_name = type(model).__module__
@@ -630,6 +639,8 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     if update_block and isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
         model.update_block.train_precision = train_precision
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
+    if sea:
+        model.update_block.sea_train = bool(sea_raft_train)
     if sea_enc_precision is not None:
         _install_sea_encoders(model, sea_enc_precision)
     if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):

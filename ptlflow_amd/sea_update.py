@@ -34,6 +34,10 @@ The seams (`accelerate(model, sea_raft_update=True)`, patch.py) hand the model's
 buffers, the way `PfkUpdateBlock` does for RAFT: `update_block(net, context, corr, flow) -> net` is the engine's h slice, and
 `flow_head(net)` / `upsample_weight(net)` recognise that very object and run the heads from it.  Everything the kernels do not
 implement — CPU tensors, gradient graphs, other dtypes, autocast — is passed to the wrapped modules unchanged.
+
+`accelerate(model, sea_raft_update=True, sea_raft_train=True)` (opt-in, fp32): calls that carry a gradient graph — CUDA fp32, grad mode
+on, an input or a parameter that requires grad, no autocast — run on the differentiable composition of train_sea.py (K12d) instead
+of the wrapped modules, and are counted in `train_calls`.
 """
 from __future__ import annotations
 
@@ -280,6 +284,21 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
         self.calls = 0             # kernel-path calls (tests count them)
         self._adopted = None           # the net `adopt` staged last
         self.adopt_first_net = False   # the heads also serve the iteration-0 net (`adopt`); set with `accelerate(sea_raft_encoders=)`
+        self.sea_train = False         # `accelerate(sea_raft_train=True)`: gradient-graph calls run on train_sea.py (fp32 only)
+        self.train_calls = 0           # calls served by the training path
+        self._train_cache: dict = {}   # its packed weights, keyed by parameter versions (`PfkUpdateBlock._train_cache`'s rules)
+
+    def trains(self, tensors, params) -> bool:
+        """the training path (train_sea.py) serves a call on `tensors`: opted in, CUDA fp32 throughout, grad mode on with something
+        that requires grad, outside autocast"""
+        if not (self.sea_train and self.precision == "fp32" and torch.is_grad_enabled() and not torch.is_autocast_enabled("cuda")):
+            return False
+        t0 = tensors[0]
+        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == t0.device for t in tensors):
+            return False
+        if not all(p.dtype == torch.float32 and p.device == t0.device for p in params):
+            return False
+        return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)
 
     def _all_params(self) -> Dict[str, torch.nn.Parameter]:
         P = dict(self.named_parameters())
@@ -337,6 +356,14 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
 
     def forward(self, net, inp, corr, flow):
         s = self.spec
+        if (self.sea_train and all(torch.is_tensor(t) and t.dim() == 4 for t in (net, inp, corr, flow))
+                and corr.shape[1] == s.corr_channels and net.shape[1] == s.hidden and inp.shape[1] == s.context and flow.shape[1] == 2
+                and all(t.shape[0] == net.shape[0] and t.shape[2:] == net.shape[2:] for t in (inp, corr, flow))
+                and self.trains((net, inp, corr, flow), list(self.parameters()))):
+            from .train_sea import sea_update_block_train
+            self._last_out, self._fm_for = None, None
+            self.train_calls += 1
+            return sea_update_block_train(dict(self.named_parameters()), s, net, inp, corr, flow, self.num_blocks, self._train_cache)
         ok = (torch.is_tensor(corr) and net.dim() == 4 and corr.dim() == 4 and self.accepts((net, inp, corr, flow), self._params())
               and corr.shape[1] == s.corr_channels and net.shape[1] == s.hidden and inp.shape[1] == s.context)
         if self.precision == "fp32":
@@ -394,6 +421,7 @@ class _SeaHeadSeam(WrappedModule):
         self._block = [block]
         self.kind = kind
         self.calls = 0
+        self.train_calls = 0           # calls served by the training path (`accelerate(sea_raft_train=True)`)
 
     def __getitem__(self, i):          # model.flow_head[0] etc. keep working (nn.Sequential indexing)
         return list(self._modules.values())[i]
@@ -403,6 +431,13 @@ class _SeaHeadSeam(WrappedModule):
 
     def forward(self, x):
         blk = self._block[0]
+        if (blk.sea_train and torch.is_tensor(x) and x.dim() == 4 and x.shape[1] == blk.spec.hidden
+                and blk.trains((x,), list(self.parameters()))):
+            # any [B, 128, H, W] net with a gradient graph, the iteration-0 split of `init_conv` included
+            from .train_sea import sea_head_train
+            self.train_calls += 1
+            P = {f"{self.kind}.{k}": v for k, v in self.named_parameters()}
+            return sea_head_train(P, self.kind, x, blk._train_cache)
         if not (torch.is_tensor(x) and (blk.owns(x) or blk.adopt(x)) and blk.accepts((x,), list(self.parameters()))):
             return self._ref[0](x)
         eng = blk.heads_fm(x)
