@@ -151,7 +151,9 @@ int pfk_corr_lookup_blocked_bf16(const pfk_lookup_desc* d, pfk_stream_t stream);
  * volume, one [lvl_h][lvl_w] map per source pixel at row stride lvl_ld[l] floats (>= lvl_h*lvl_w; a stride padded to a
  * multiple of 4 makes the buffer a legal operand of pfk_corr_volume_bwd_f32).  ACCUMULATES (+=): the caller zeroes the
  * buffers once per training step and every recurrent iteration's lookup adds into them.  Deterministic (no atomics).
- * Taps that fell outside the map in the forward (zero padding) receive nothing. */
+ * Taps that fell outside the map in the forward (zero padding) receive nothing.  Non-finite coordinates (NaN, +-inf), coordinates
+ * too large for the map and every tap of a 1-pixel-high or -wide level (whose round trip divides by zero: the forward returns NaN
+ * there) add exactly 0, as grid_sample's backward does: a finite grad_out never puts a NaN into grad_levels. */
 typedef struct {
   float* grad_levels[PFK_MAX_LEVELS];
   int lvl_h[PFK_MAX_LEVELS];

@@ -87,10 +87,14 @@ __global__ __launch_bounds__(256) void lookup_bwd_kernel(const LookupBwdArgs a) 
           const float iy = roundtrip(cy + off, (float)(Hl - 1), (float)(Hl - 1) * 0.5f);
           const float x0 = floorf(ix), y0 = floorf(iy);
           const float dxf = x0 - xb, dyf = y0 - yb;
-          s_rx[wid][q][lane] = (dxf >= 0.f && dxf <= (float)(PATCH - 2)) ? (int)dxf : 0;
-          s_ry[wid][q][lane] = (dyf >= 0.f && dyf <= (float)(PATCH - 2)) ? (int)dyf : 0;
-          s_wx[wid][q][lane] = ix - x0;
-          s_wy[wid][q][lane] = iy - y0;
+          // A tap whose round-trip coordinate is not finite (NaN / inf coordinates, every tap of a 1-pixel level: 0/0 or
+          // x/0 in the round trip) lies in no cell: grid_sample's backward gives the volume exactly 0 there.  Index -2
+          // matches no patch column (the indices are only ever compared), weight 0 keeps the NaN out of the sums.
+          const bool fin_x = fabsf(ix) <= 3.402823466e38f, fin_y = fabsf(iy) <= 3.402823466e38f;
+          s_rx[wid][q][lane] = !fin_x ? -2 : ((dxf >= 0.f && dxf <= (float)(PATCH - 2)) ? (int)dxf : 0);
+          s_ry[wid][q][lane] = !fin_y ? -2 : ((dyf >= 0.f && dyf <= (float)(PATCH - 2)) ? (int)dyf : 0);
+          s_wx[wid][q][lane] = fin_x ? ix - x0 : 0.f;
+          s_wy[wid][q][lane] = fin_y ? iy - y0 : 0.f;
         }
         xbi[q] = safe_base(xb); ybi[q] = safe_base(yb);
       }
