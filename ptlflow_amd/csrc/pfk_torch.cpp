@@ -8,145 +8,93 @@
 //
 // Pixel-major activations are passed as 2-D tensors [M, C] whose row stride is the buffer's
 // `ld` — a channel slice of a wider buffer (buf[:, 128:384]) is just a view.
-#include <ATen/ATen.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
+//
+// Tensors become pointers in pfk_torch_views.h only: rows() for pixel-major views, dense() for contiguous tensors,
+// up8() for the upsampled outputs, fill_sources() for a convolution's inputs.
 #include <torch/library.h>
 
+#include <type_traits>
 #include <vector>
 
-#include "pfk.h"
+#include "pfk_torch_views.h"
 
 namespace {
 
-using at::Tensor;
-
-void check_ok(int status, const char* what) {
-  TORCH_CHECK(status == PFK_OK, "pfk::", what, " failed: ", pfk_status_string(status), " (", status, ")");
-}
-
-// Every op opens an OpScope on one of its tensors: the HIP device becomes that tensor's device for the duration of the
-// op (kernels, torch's current stream and any at::empty are then on the GPU that owns the data, whatever the caller's
-// current device is — model.to("cuda:1") with device 0 current), and every tensor checked afterwards must live there too.
-thread_local const c10::Device* tl_op_device = nullptr;
-struct OpScope {
-  c10::Device dev;
-  c10::DeviceGuard guard;   // generic guard: resolves to the (CUDA-masquerading) HIP implementation registered for the tensor's device type
-  explicit OpScope(const Tensor& t) : dev(t.device()), guard(t.device()) {
-    TORCH_CHECK(t.is_cuda(), "pfk ops need GPU tensors");
-    tl_op_device = &dev;
-  }
-  ~OpScope() { tl_op_device = nullptr; }
-};
-
-pfk_stream_t cur_stream() { return static_cast<pfk_stream_t>(c10::hip::getCurrentHIPStream().stream()); }
-
-void check_dev(const Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(tl_op_device == nullptr || t.device() == *tl_op_device, name, " is on ", t.device(), " but the op runs on ", *tl_op_device);
-}
-
-void check_dev_f32(const Tensor& t, const char* name) {
-  check_dev(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-}
-
-// 2-D row-strided view [M, C] with unit channel stride.
-void check_pm(const Tensor& t, const char* name) {
-  check_dev_f32(t, name);
-  TORCH_CHECK(t.dim() == 2 && (t.size(1) == 1 || t.stride(1) == 1), name,
-              " must be a [pixels, channels] view with contiguous channels");
-}
-
-float* fptr(const Tensor& t) { return t.data_ptr<float>(); }
-
-// [pixels, channels] view of fp32 or bf16 elements; returns true for bf16
-bool check_pm_any(const Tensor& t, const char* name) {
-  check_dev(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16, name, " must be float32 or bfloat16");
-  TORCH_CHECK(t.dim() == 2 && (t.size(1) == 1 || t.stride(1) == 1), name, " must be a [pixels, channels] view with contiguous channels");
-  return t.scalar_type() == at::kBFloat16;
-}
-
-void check_pm_b16(const Tensor& t, const char* name) {
-  check_dev(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bfloat16");
-  TORCH_CHECK(t.dim() == 2 && (t.size(1) == 1 || t.stride(1) == 1), name, " must be a [pixels, channels] view with contiguous channels");
-}
-
-
-// out[b,i,j] = scale * <f1[b,i,:], f2[b,j,:]>
-void corr_volume(const Tensor& f1, const Tensor& f2, double scale, Tensor out) {
+// out[b,i,j] = scale * <f1[b,i,:], f2[b,j,:]>: fp32 [B,N,D] inputs -> fp32 [B,N1,N2] out (corr_volume), or all three bf16 (corr_volume_bf16)
+void corr_volume_impl(const char* op, Elem e, const Tensor& f1, const Tensor& f2, double scale, const Tensor& out) {
   OpScope scope(f1);
-  check_dev_f32(f1, "f1"); check_dev_f32(f2, "f2"); check_dev_f32(out, "out");
-  TORCH_CHECK(f1.dim() == 3 && f2.dim() == 3 && out.dim() == 3, "corr_volume: [B,N,D] inputs, [B,N1,N2] out");
-  TORCH_CHECK(f1.is_contiguous() && f2.is_contiguous() && out.is_contiguous(), "corr_volume: contiguous tensors");
+  const Ptr a = dense(op, f1, "f1", e), b = dense(op, f2, "f2", e), o = dense(op, out, "out", e);
+  TORCH_CHECK(f1.dim() == 3 && f2.dim() == 3 && out.dim() == 3, op, ": [B,N,D] inputs, [B,N1,N2] out");
   const int B = f1.size(0), N1 = f1.size(1), D = f1.size(2), N2 = f2.size(1);
-  TORCH_CHECK(f2.size(0) == B && f2.size(2) == D && out.size(0) == B && out.size(1) == N1 && out.size(2) == N2,
-              "corr_volume: shape mismatch");
-  check_ok(pfk_corr_volume_f32(fptr(f1), D, fptr(f2), D, fptr(out), B, N1, N2, D, (float)scale, cur_stream()),
-           "corr_volume");
+  TORCH_CHECK(f2.size(0) == B && f2.size(2) == D && out.size(0) == B && out.size(1) == N1 && out.size(2) == N2, op, ": shape mismatch");
+  if (e == B16) check_ok(pfk_corr_volume_bf16(a.raw(), D, b.raw(), D, o.raw(), B, N1, N2, D, (float)scale, cur_stream()), op);
+  else check_ok(pfk_corr_volume_f32(a.f32(), D, b.f32(), D, o.f32(), B, N1, N2, D, (float)scale, cur_stream()), op);
 }
+void corr_volume(const Tensor& f1, const Tensor& f2, double scale, Tensor out) { corr_volume_impl("corr_volume", F32, f1, f2, scale, out); }
+void corr_volume_bf16(const Tensor& f1, const Tensor& f2, double scale, Tensor out) { corr_volume_impl("corr_volume_bf16", B16, f1, f2, scale, out); }
 
 void corr_pool2x2(const Tensor& in, Tensor out) {
   OpScope scope(in);
-  check_dev(in, "in"); check_dev(out, "out");
-  TORCH_CHECK(in.scalar_type() == out.scalar_type() && (in.scalar_type() == at::kFloat || in.scalar_type() == at::kBFloat16),
-              "corr_pool2x2: float32 or bfloat16 maps");
-  TORCH_CHECK(in.dim() == 3 && in.is_contiguous() && out.is_contiguous(), "corr_pool2x2: [M,H,W] contiguous");
+  const Ptr i = dense("corr_pool2x2", in, "inp", Any);
+  TORCH_CHECK(in.dim() == 3, "corr_pool2x2: inp must be [M,H,W] contiguous");
   const int64_t M = in.size(0); const int H = in.size(1), W = in.size(2);
-  TORCH_CHECK(out.numel() == M * (H / 2) * (W / 2), "corr_pool2x2: out has wrong size");
+  const Ptr o = dense("corr_pool2x2", out, "out", i.b16 ? B16 : F32, M * (H / 2) * (W / 2));
   if (out.numel() == 0) return;
-  if (in.scalar_type() == at::kFloat) check_ok(pfk_corr_pool2x2_f32(fptr(in), fptr(out), M, H, W, cur_stream()), "corr_pool2x2");
-  else check_ok(pfk_corr_pool2x2_bf16(in.data_ptr(), out.data_ptr(), M, H, W, cur_stream()), "corr_pool2x2 (bf16)");
-}
-
-// bf16 volume: f1, f2 bf16 [B,N,D] -> out bf16 [B,N1,N2]
-void corr_volume_bf16(const Tensor& f1, const Tensor& f2, double scale, Tensor out) {
-  OpScope scope(f1);
-  check_dev(f1, "f1"); check_dev(f2, "f2"); check_dev(out, "out");
-  TORCH_CHECK(f1.scalar_type() == at::kBFloat16 && f2.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
-              "corr_volume_bf16: f1, f2 and out must be bfloat16");
-  TORCH_CHECK(f1.dim() == 3 && f2.dim() == 3 && out.dim() == 3 && f1.is_contiguous() && f2.is_contiguous() && out.is_contiguous(),
-              "corr_volume_bf16: contiguous [B,N,D] inputs, [B,N1,N2] out");
-  const int B = f1.size(0), N1 = f1.size(1), D = f1.size(2), N2 = f2.size(1);
-  TORCH_CHECK(f2.size(0) == B && f2.size(2) == D && out.size(0) == B && out.size(1) == N1 && out.size(2) == N2, "corr_volume_bf16: shape mismatch");
-  check_ok(pfk_corr_volume_bf16(f1.data_ptr(), D, f2.data_ptr(), D, out.data_ptr(), B, N1, N2, D, (float)scale, cur_stream()), "corr_volume_bf16");
+  if (i.b16) check_ok(pfk_corr_pool2x2_bf16(i.raw(), o.raw(), M, H, W, cur_stream()), "corr_pool2x2 (bf16)");
+  else check_ok(pfk_corr_pool2x2_f32(i.f32(), o.f32(), M, H, W, cur_stream()), "corr_pool2x2");
 }
 
 // pixel-major feature map [B*H*W, C] -> [B*(H/2)*(W/2), C]: 2x2 average == bilinear x0.5 (align_corners=False)
 void fmap_pool2x2(const Tensor& in, Tensor out, int64_t B, int64_t H, int64_t W) {
   OpScope scope(in);
-  check_pm(in, "in"); check_pm(out, "out");
-  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == B * (H / 2) * (W / 2) && out.size(1) == in.size(1), "fmap_pool2x2: shapes");
+  const Rows i = rows("fmap_pool2x2", in, "inp", F32).expect(B * H * W, AtLeast{0});
+  const Rows o = rows("fmap_pool2x2", out, "out", F32).expect(B * (H / 2) * (W / 2), i.cols);
   if (out.numel() == 0) return;
-  check_ok(pfk_fmap_pool2x2_f32(fptr(in), in.stride(0), fptr(out), out.stride(0), (int)B, (int)H, (int)W, (int)in.size(1), cur_stream()),
-           "fmap_pool2x2");
+  check_ok(pfk_fmap_pool2x2_f32(i.f32(), i.ld, o.f32(), o.ld, (int)B, (int)H, (int)W, (int)i.cols, cur_stream()), "fmap_pool2x2");
 }
 
-void corr_lookup(at::TensorList levels, const Tensor& coords, int64_t radius, Tensor out) {
+// corr_lookup: levels are [B*N, h_l, w_l] maps, which carry their sizes.  corr_lookup_blocked (include/pfk.h "K1-K3 on the BLOCKED
+// volume layout"): levels are [B*N, pfk_blocked_map_elems(h_l, w_l)] and the map sizes come in lvl_h / lvl_w
+void corr_lookup_impl(const char* op, bool blocked, at::TensorList levels, at::IntArrayRef lvl_h, at::IntArrayRef lvl_w, const Tensor& coords,
+                      int64_t radius, const Tensor& out) {
   OpScope scope(coords);
-  check_dev_f32(coords, "coords");
-  const bool out_b16 = check_pm_any(out, "out");
-  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2 && coords.is_contiguous(), "corr_lookup: coords [B,2,h,w] contiguous");
-  TORCH_CHECK(levels.size() >= 1 && levels.size() <= PFK_MAX_LEVELS, "corr_lookup: 1..8 levels");
+  const Ptr c = dense(op, coords, "coords", F32);
+  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2, op, ": coords [B,2,h,w] contiguous");
+  TORCH_CHECK(levels.size() >= 1 && levels.size() <= PFK_MAX_LEVELS, op, ": 1..8 levels");
+  TORCH_CHECK(!blocked || (lvl_h.size() == levels.size() && lvl_w.size() == levels.size()), op, ": one map size per level");
   pfk_lookup_desc d{};
   d.B = coords.size(0); d.h = coords.size(2); d.w = coords.size(3);
   const int64_t M = (int64_t)d.B * d.h * d.w;
-  const bool bf = levels[0].scalar_type() == at::kBFloat16;
+  const bool bf = levels[0].scalar_type() == at::kBFloat16;      // levels must all be float32 or all bfloat16
   for (size_t l = 0; l < levels.size(); ++l) {
     const Tensor& v = levels[l];
-    check_dev(v, "level");
-    TORCH_CHECK(v.scalar_type() == (bf ? at::kBFloat16 : at::kFloat), "corr_lookup: levels must all be float32 or all bfloat16");
-    TORCH_CHECK(v.dim() == 3 && v.is_contiguous() && v.size(0) == M, "corr_lookup: level must be [B*N,h_l,w_l] contiguous");
-    d.levels[l] = v.data_ptr(); d.lvl_h[l] = v.size(1); d.lvl_w[l] = v.size(2);
+    d.levels[l] = dense(op, v, "level", bf ? B16 : F32).raw();
+    if (blocked) {
+      TORCH_CHECK(lvl_h[l] > 0 && lvl_w[l] > 0 && v.dim() == 2 && v.size(0) == M && v.size(1) == pfk_blocked_map_elems((int)lvl_h[l], (int)lvl_w[l]),
+                  op, ": level must be [B*N, blocked_map_elems(h_l, w_l)] contiguous");
+      d.lvl_h[l] = (int)lvl_h[l]; d.lvl_w[l] = (int)lvl_w[l];
+    } else {
+      TORCH_CHECK(v.dim() == 3 && v.size(0) == M, op, ": level must be [B*N,h_l,w_l] contiguous");
+      d.lvl_h[l] = v.size(1); d.lvl_w[l] = v.size(2);
+    }
   }
   d.num_levels = levels.size(); d.radius = radius;
-  d.coords = fptr(coords); d.out = out.data_ptr(); d.out_ld = out.stride(0); d.out_bf16 = out_b16;
-  TORCH_CHECK(out.size(0) == M, "corr_lookup: out rows");
   const int n = 2 * radius + 1;
-  TORCH_CHECK(out.size(1) >= d.num_levels * n * n, "corr_lookup: out channels");
-  check_ok(bf ? pfk_corr_lookup_bf16(&d, cur_stream()) : pfk_corr_lookup_f32(&d, cur_stream()), "corr_lookup");
+  const Rows o = rows(op, out, "out", Any).expect(M, AtLeast{(int64_t)d.num_levels * n * n});
+  d.coords = c.f32(); d.out = o.raw(); d.out_ld = o.ld; d.out_bf16 = o.b16;
+  if (blocked) check_ok(bf ? pfk_corr_lookup_blocked_bf16(&d, cur_stream()) : pfk_corr_lookup_blocked_f32(&d, cur_stream()), op);
+  else check_ok(bf ? pfk_corr_lookup_bf16(&d, cur_stream()) : pfk_corr_lookup_f32(&d, cur_stream()), op);
+}
+void corr_lookup(at::TensorList levels, const Tensor& coords, int64_t radius, Tensor out) {
+  corr_lookup_impl("corr_lookup", false, levels, {}, {}, coords, radius, out);
+}
+void corr_lookup_blocked(at::TensorList levels, at::IntArrayRef lvl_h, at::IntArrayRef lvl_w, const Tensor& coords, int64_t radius, Tensor out) {
+  corr_lookup_impl("corr_lookup_blocked", true, levels, lvl_h, lvl_w, coords, radius, out);
+}
+
+// hidden width of the GRU epilogues (include/pfk.h): cout = 2*Ch for PFK_EPI_GRU_ZR, Ch for PFK_EPI_GRU_Q; h / aux_z / aux_rh are [M][Ch]
+int64_t gru_hidden(int64_t epilogue, int64_t cout) {
+  return epilogue == PFK_EPI_GRU_ZR ? cout / 2 : epilogue == PFK_EPI_GRU_Q ? cout : 0;
 }
 
 void conv2d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw,
@@ -156,107 +104,80 @@ void conv2d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, in
             const c10::optional<Tensor>& workspace, const c10::optional<Tensor>& residual, int64_t stride,
             bool relu_after_residual, int64_t cout_active, int64_t cout_split) {
   OpScope scope(weight);
-  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3, "conv2d: 1..3 sources");
   TORCH_CHECK(stride >= 1, "conv2d: stride");
   pfk_conv_desc d{};
   d.stride = (int)stride;
   d.cout_active = (int)cout_active;
   d.cout_split = (int)cout_split;
   d.relu_after_residual = relu_after_residual;
-  const int64_t M = B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);   // output rows
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    check_pm(srcs[i], "src");
-    TORCH_CHECK(srcs[i].size(0) == B * H * W, "conv2d: src rows != B*H*W");
-    d.src[i].ptr = fptr(srcs[i]); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
-  }
-  d.num_src = srcs.size();
+  const int64_t M = out_rows(B, H, W, stride), Ch = gru_hidden(epilogue, cout);
+  fill_sources(d, srcs, B * H * W, F32, "conv2d");
   d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = cout;
   d.epilogue = epilogue; d.relu = relu; d.scale = (float)scale;
   // fp32 packed weight [cout, ktot] -> fp32 MFMA path; bf16 planes [nsplit, cout, ktot64] -> split-bf16 path
   const bool split = weight.scalar_type() == at::kBFloat16;
+  const Ptr wp = dense("conv2d", weight, "weight", split ? B16 : F32);
   if (split) {
-    check_dev(weight, "weight");
-    TORCH_CHECK(weight.is_contiguous() && weight.dim() == 3 && weight.size(1) == cout &&
-                weight.size(0) >= 1 && weight.size(0) <= 3, "conv2d: bf16 weight planes [nsplit, cout, ktot]");
+    TORCH_CHECK(weight.dim() == 3 && weight.size(1) == cout && weight.size(0) >= 1 && weight.size(0) <= 3,
+                "conv2d: bf16 weight planes [nsplit, cout, ktot]");
     TORCH_CHECK(weight.size(2) == pfk_conv_ktot_bf16(&d), "conv2d: bf16 weight planes have ktot ", weight.size(2),
                 ", expected ", pfk_conv_ktot_bf16(&d));
   } else {
-    check_dev_f32(weight, "weight");
-    TORCH_CHECK(weight.is_contiguous() && weight.dim() == 2 && weight.size(0) == cout, "conv2d: packed weight [cout, ktot]");
+    TORCH_CHECK(weight.dim() == 2 && weight.size(0) == cout, "conv2d: packed weight [cout, ktot]");
     TORCH_CHECK(weight.size(1) == pfk_conv_ktot(&d), "conv2d: packed weight has ktot ", weight.size(1), ", expected ", pfk_conv_ktot(&d));
-    d.weight = fptr(weight);
+    d.weight = wp.f32();
   }
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); d.bias = fptr(*bias); }
+  d.bias = dense("conv2d", bias, "bias", F32, cout).f32();
   if (out.has_value()) {
-    check_pm(*out, "out");
-    TORCH_CHECK(out->size(0) == M && out->size(1) == cout, "conv2d: out must be a [M, cout] view");
-    d.out = fptr(*out); d.out_ld = out->stride(0); d.out_coff = 0;
+    const Rows o = rows("conv2d", *out, "out", F32).expect(M, cout);
+    d.out = o.f32(); d.out_ld = o.ld; d.out_coff = 0;
   }
-  if (h.has_value()) { check_pm(*h, "h"); TORCH_CHECK(h->size(0) == M); d.h = fptr(*h); d.h_ld = h->stride(0); }
-  if (aux_z.has_value()) { check_dev_f32(*aux_z, "aux_z"); TORCH_CHECK(aux_z->is_contiguous()); d.aux_z = fptr(*aux_z); }
-  if (aux_rh.has_value()) { check_dev_f32(*aux_rh, "aux_rh"); TORCH_CHECK(aux_rh->is_contiguous()); d.aux_rh = fptr(*aux_rh); }
+  if (h.has_value()) { const Rows v = rows("conv2d", *h, "h", F32).expect(M, AtLeast{Ch}); d.h = v.f32(); d.h_ld = v.ld; }
+  d.aux_z = dense("conv2d", aux_z, "aux_z", F32, AtLeast{M * Ch}).f32();
+  d.aux_rh = dense("conv2d", aux_rh, "aux_rh", F32, AtLeast{M * Ch}).f32();
   if (residual.has_value()) {
-    check_pm(*residual, "residual");
-    TORCH_CHECK(residual->size(0) == M && residual->size(1) == cout, "conv2d: residual must be a [M, cout] view");
-    d.residual = fptr(*residual); d.residual_ld = residual->stride(0);
+    const Rows r = rows("conv2d", *residual, "residual", F32).expect(M, cout);
+    d.residual = r.f32(); d.residual_ld = r.ld;
   }
-  if (workspace.has_value()) {
-    check_dev(*workspace, "workspace");
-    TORCH_CHECK(workspace->is_contiguous(), "conv2d: workspace must be a contiguous GPU tensor");
-    d.workspace = workspace->data_ptr(); d.workspace_bytes = (long long)workspace->nbytes();
-  }
-  if (split) check_ok(pfk_conv2d_bf16s(&d, weight.data_ptr(), (int)weight.size(0), cur_stream()), "conv2d (split bf16)");
+  if (workspace.has_value()) { d.workspace = dense("conv2d", *workspace, "workspace", Raw).raw(); d.workspace_bytes = (long long)workspace->nbytes(); }
+  if (split) check_ok(pfk_conv2d_bf16s(&d, wp.raw(), (int)weight.size(0), cur_stream()), "conv2d (split bf16)");
   else check_ok(pfk_conv2d_f32(&d, cur_stream()), "conv2d");
 }
 
-void conv2d_wino_impl(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
-                      int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active, const Tensor* residual,
-                      bool relu_after_residual);
-
 // Winograd F(2x2,3x3) 3x3 convolution (pfk_conv2d_wino_f32): one fp32 source [B*H*W, cin] view, the transformed weight of
-// packing.pack_wino_weight (flat, pfk_conv_wino_weight_floats(cin, cout) floats), LINEAR epilogue into an [M, cout] view
-void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
-                 int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active) {
-  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, cout_active, nullptr, false);
-}
-
-// the same with the residual-block epilogue (pfk_conv2d_wino_res_f32): out = relu2?(residual + relu?(conv + bias) * scale)
-void conv2d_wino_res(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
-                     int64_t cout, bool relu, double scale, const Tensor& out, const Tensor& residual, bool relu_after_residual) {
-  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, 0, &residual, relu_after_residual);
-}
-
+// packing.pack_wino_weight (flat, pfk_conv_wino_weight_floats(cin, cout) floats), LINEAR epilogue into an [M, cout] view;
+// with `residual` the residual-block epilogue (pfk_conv2d_wino_res_f32): out = relu2?(residual + relu?(conv + bias) * scale)
 void conv2d_wino_impl(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
                       int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active, const Tensor* residual,
                       bool relu_after_residual) {
   OpScope scope(weight);
-  check_pm(src, "src");
   TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, "conv2d_wino: sizes");
-  TORCH_CHECK(src.size(0) == B * H * W, "conv2d_wino: src rows != B*H*W");
-  TORCH_CHECK(src.size(1) % 32 == 0, "conv2d_wino: input channels must be a multiple of 32, got ", src.size(1));
   pfk_conv_desc d{};
-  d.src[0].ptr = fptr(src); d.src[0].ld = src.stride(0); d.src[0].channels = src.size(1);
-  d.num_src = 1;
+  fill_sources(d, {src}, B * H * W, F32, "conv2d_wino");
+  const int cin = d.src[0].channels;
+  TORCH_CHECK(cin % 32 == 0, "conv2d_wino: input channels must be a multiple of 32, got ", cin);
   d.B = B; d.H = H; d.W = W; d.kh = 3; d.kw = 3; d.stride = 1; d.cout = cout;
   d.epilogue = PFK_EPI_LINEAR; d.relu = relu; d.scale = (float)scale;
   d.cout_active = (int)cout_active;
-  check_dev_f32(weight, "weight");
-  const long long wn = pfk_conv_wino_weight_floats((int)src.size(1), (int)cout);
-  TORCH_CHECK(weight.is_contiguous() && weight.numel() == wn, "conv2d_wino: transformed weight must be contiguous with ", wn,
-              " elements, got ", weight.numel());
-  d.weight = fptr(weight);
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); d.bias = fptr(*bias); }
-  check_pm(out, "out");
-  TORCH_CHECK(out.size(0) == B * H * W && out.size(1) == cout, "conv2d_wino: out must be a [M, cout] view");
-  d.out = fptr(out); d.out_ld = out.stride(0); d.out_coff = 0;
+  d.weight = dense("conv2d_wino", weight, "weight (transformed)", F32, pfk_conv_wino_weight_floats(cin, (int)cout)).f32();
+  d.bias = dense("conv2d_wino", bias, "bias", F32, cout).f32();
+  const Rows o = rows("conv2d_wino", out, "out", F32).expect(B * H * W, cout);
+  d.out = o.f32(); d.out_ld = o.ld; d.out_coff = 0;
   if (residual) {
-    check_pm(*residual, "residual");
-    TORCH_CHECK(residual->size(0) == B * H * W && residual->size(1) == cout, "conv2d_wino_res: residual must be a [M, cout] view");
-    d.residual = fptr(*residual); d.residual_ld = residual->stride(0); d.relu_after_residual = relu_after_residual;
+    const Rows r = rows("conv2d_wino_res", *residual, "residual", F32).expect(B * H * W, cout);
+    d.residual = r.f32(); d.residual_ld = r.ld; d.relu_after_residual = relu_after_residual;
     check_ok(pfk_conv2d_wino_res_f32(&d, cur_stream()), "conv2d_wino_res");
     return;
   }
   check_ok(pfk_conv2d_wino_f32(&d, cur_stream()), "conv2d_wino");
+}
+void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                 int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active) {
+  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, cout_active, nullptr, false);
+}
+void conv2d_wino_res(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                     int64_t cout, bool relu, double scale, const Tensor& out, const Tensor& residual, bool relu_after_residual) {
+  conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, 0, &residual, relu_after_residual);
 }
 
 // Grouped launch (pfk_conv2d_group_f32): problem i = one fp32 source srcs[i] ([B*H*W, cin_i] view), k[i] x k[i] taps, stride 1, packed
@@ -271,26 +192,19 @@ void conv2d_group(at::TensorList srcs, int64_t B, int64_t H, int64_t W, at::IntA
   OpScope scope(srcs[0]);
   pfk_conv_desc d[PFK_CONV_GROUP_MAX] = {};
   for (size_t i = 0; i < n; ++i) {
-    check_pm(srcs[i], "src"); check_pm(outs[i], "out"); check_dev_f32(weights[i], "weight");
-    TORCH_CHECK(srcs[i].size(0) == B * H * W && outs[i].size(0) == B * H * W, "conv2d_group: rows != B*H*W");
-    const int cout = outs[i].size(1);
-    d[i].num_src = 1;
-    d[i].src[0].ptr = fptr(srcs[i]); d[i].src[0].ld = srcs[i].stride(0); d[i].src[0].channels = srcs[i].size(1);
+    fill_sources(d[i], {srcs[i]}, B * H * W, F32, "conv2d_group");
+    const Rows o = rows("conv2d_group", outs[i], "out", F32).expect(B * H * W, AtLeast{0});
+    const int cout = o.cols;
     d[i].B = B; d[i].H = H; d[i].W = W; d[i].kh = k[i]; d[i].kw = k[i]; d[i].cout = cout; d[i].stride = 1;
     d[i].epilogue = PFK_EPI_LINEAR; d[i].relu = relu[i] != 0; d[i].scale = (float)scale[i];
-    TORCH_CHECK(weights[i].is_contiguous() && weights[i].dim() == 2 && weights[i].size(0) == cout && weights[i].size(1) == pfk_conv_ktot(&d[i]),
+    d[i].weight = dense("conv2d_group", weights[i], "weight", F32).f32();
+    TORCH_CHECK(weights[i].dim() == 2 && weights[i].size(0) == cout && weights[i].size(1) == pfk_conv_ktot(&d[i]),
                 "conv2d_group: packed weight [cout, ktot] of problem ", i);
-    d[i].weight = fptr(weights[i]);
-    if (biases[i].numel() > 0) {
-      check_dev_f32(biases[i], "bias");
-      TORCH_CHECK(biases[i].numel() == cout && biases[i].is_contiguous(), "conv2d_group: bias [cout]");
-      d[i].bias = fptr(biases[i]);
-    }
-    d[i].out = fptr(outs[i]); d[i].out_ld = outs[i].stride(0); d[i].out_coff = 0;
+    if (biases[i].numel() > 0) d[i].bias = dense("conv2d_group", biases[i], "bias", F32, cout).f32();
+    d[i].out = o.f32(); d[i].out_ld = o.ld; d[i].out_coff = 0;
     if (residuals.size() == n && residuals[i].numel() > 0) {      // out = residual + scale * relu?(conv + bias)  (an empty tensor = none)
-      check_pm(residuals[i], "residual");
-      TORCH_CHECK(residuals[i].size(0) == B * H * W && residuals[i].size(1) == cout, "conv2d_group: residual must be a [M, cout] view");
-      d[i].residual = fptr(residuals[i]); d[i].residual_ld = residuals[i].stride(0);
+      const Rows r = rows("conv2d_group", residuals[i], "residual", F32).expect(B * H * W, cout);
+      d[i].residual = r.f32(); d[i].residual_ld = r.ld;
     }
   }
   check_ok(pfk_conv2d_group_f32(d, (int)n, cur_stream()), "conv2d_group");
@@ -304,81 +218,55 @@ void conv2d_b16_run(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_
                     const c10::optional<Tensor>& aux_z, const c10::optional<Tensor>& aux_rh, const c10::optional<Tensor>& residual,
                     int64_t stride, bool relu_after_residual, bool gelu_entry) {
   OpScope scope(weight);
+  const char* op = gelu_entry ? "conv2d_gelu_b16" : "conv2d_b16";
   const bool lin = epilogue == PFK_EPI_LINEAR || (gelu_entry && epilogue == PFK_EPI_LINEAR_GELU);
+  pfk_conv_b16_desc d{};
+  d.weight = dense(op, weight, "weight", B16).raw();
+  d.bias = dense(op, bias, "bias", F32, cout).f32();
   if (weight.dim() == 3) {
     // batched GEMM (pfk_conv_b16_desc.batches): src [Bt, M, K] bf16, weight [Bt, cout, K] bf16, out [Bt, M, cout], residual [Bt, M, cout]
-    TORCH_CHECK(srcs.size() == 1 && srcs[0].dim() == 3 && kh == 1 && kw == 1 && epilogue == PFK_EPI_LINEAR && out.has_value() && out->dim() == 3,
-                "conv2d_b16 (batched): one [Bt, M, K] source, [Bt, cout, K] weight, [Bt, M, cout] out, 1x1, linear epilogue");
+    TORCH_CHECK(srcs.size() == 1 && srcs[0].dim() == 3 && srcs[0].size(0) >= 1 && kh == 1 && kw == 1 && epilogue == PFK_EPI_LINEAR &&
+                out.has_value() && out->dim() == 3 && (!residual.has_value() || residual->dim() == 3),
+                "conv2d_b16 (batched): one [Bt, M, K] source, [Bt, cout, K] weight, [Bt, M, cout] out / residual, 1x1, linear epilogue");
     const Tensor& a = srcs[0];
-    check_dev(a, "src"); check_dev(weight, "weight"); check_dev(*out, "out");
     const int64_t Bt = a.size(0), M = a.size(1), K = a.size(2);
-    TORCH_CHECK(a.scalar_type() == at::kBFloat16 && weight.scalar_type() == at::kBFloat16 && a.stride(2) == 1 && weight.is_contiguous() &&
-                weight.size(0) == Bt && weight.size(1) == cout && weight.size(2) == (K + 63) / 64 * 64 && B == 1 && H * W == M &&
-                out->size(0) == Bt && out->size(1) == M && out->size(2) == cout && out->stride(2) == 1, "conv2d_b16 (batched): shapes");
-    pfk_conv_b16_desc d{};
-    d.src[0].ptr = a.data_ptr(); d.src[0].ld = a.stride(1); d.src[0].channels = K; d.num_src = 1;
+    TORCH_CHECK(weight.size(0) == Bt && weight.size(1) == cout && weight.size(2) == (K + 63) / 64 * 64 && B == 1 && H * W == M &&
+                out->size(0) == Bt && (!residual.has_value() || residual->size(0) == Bt), "conv2d_b16 (batched): shapes");
+    // batch 0 of each operand as a row view (the batch strides go to the descriptor; every batch lies inside its own tensor)
+    fill_sources(d, {a.select(0, 0)}, M, B16, "conv2d_b16 (batched)");
     d.B = 1; d.H = H; d.W = W; d.kh = 1; d.kw = 1; d.cout = cout; d.epilogue = PFK_EPI_LINEAR; d.relu = relu; d.scale = (float)scale;
-    d.weight = weight.data_ptr();
-    d.out = out->data_ptr(); d.out_ld = out->stride(1); d.out_bf16 = out->scalar_type() == at::kBFloat16;
-    TORCH_CHECK(d.out_bf16 || out->scalar_type() == at::kFloat, "conv2d_b16: out must be bfloat16 or float32");
+    const Rows o = rows("conv2d_b16 (batched)", out->select(0, 0), "out", Any).expect(M, cout);
+    d.out = o.raw(); d.out_ld = o.ld; d.out_bf16 = o.b16;
     d.batches = Bt; d.src_batch_stride = a.stride(0); d.weight_batch_stride = weight.stride(0); d.out_batch_stride = out->stride(0);
-    if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); d.bias = fptr(*bias); }
     if (residual.has_value()) {
-      check_dev(*residual, "residual");
-      TORCH_CHECK(residual->dim() == 3 && residual->size(0) == Bt && residual->size(1) == M && residual->size(2) == cout && residual->stride(2) == 1,
-                  "conv2d_b16 (batched): residual [Bt, M, cout]");
-      d.residual_bf16 = residual->scalar_type() == at::kBFloat16;
-      TORCH_CHECK(d.residual_bf16 || residual->scalar_type() == at::kFloat, "conv2d_b16: residual must be bfloat16 or float32");
-      d.residual = residual->data_ptr(); d.residual_ld = residual->stride(1); d.residual_batch_stride = residual->stride(0);
+      const Rows r = rows("conv2d_b16 (batched)", residual->select(0, 0), "residual", Any).expect(M, cout);
+      d.residual = r.raw(); d.residual_ld = r.ld; d.residual_bf16 = r.b16; d.residual_batch_stride = residual->stride(0);
     }
     check_ok(pfk_conv2d_b16(&d, cur_stream()), "conv2d_b16 (batched)");
     return;
   }
-  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3, "conv2d_b16: 1..3 sources");
   TORCH_CHECK(stride >= 1, "conv2d_b16: stride");
-  pfk_conv_b16_desc d{};
   d.stride = (int)stride;
   d.relu_after_residual = relu_after_residual;
-  const int64_t M = B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    check_pm_b16(srcs[i], "src");
-    TORCH_CHECK(srcs[i].size(0) == B * H * W, "conv2d_b16: src rows != B*H*W");
-    d.src[i].ptr = srcs[i].data_ptr(); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
-  }
-  d.num_src = srcs.size();
+  const int64_t M = out_rows(B, H, W, stride), Ch = gru_hidden(epilogue, cout);
+  fill_sources(d, srcs, B * H * W, B16, op);
   d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = cout;
   d.epilogue = epilogue; d.relu = relu; d.scale = (float)scale;
-  check_dev(weight, "weight");
-  TORCH_CHECK(weight.scalar_type() == at::kBFloat16 && weight.is_contiguous() && weight.dim() == 2 && weight.size(0) == cout,
-              "conv2d_b16: bf16 packed weight [cout, ktot]");
+  TORCH_CHECK(weight.dim() == 2 && weight.size(0) == cout, "conv2d_b16: bf16 packed weight [cout, ktot]");
   TORCH_CHECK(weight.size(1) == pfk_conv_ktot_b16(&d), "conv2d_b16: packed weight has ktot ", weight.size(1), ", expected ",
               pfk_conv_ktot_b16(&d));
-  d.weight = weight.data_ptr();
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); d.bias = fptr(*bias); }
   if (out.has_value()) {
-    check_dev(*out, "out");
-    TORCH_CHECK(out->dim() == 2 && (out->size(1) == 1 || out->stride(1) == 1) && out->size(0) == M && out->size(1) == cout,
-                "conv2d_b16: out must be a [M, cout] view");
-    TORCH_CHECK(out->scalar_type() == at::kBFloat16 || out->scalar_type() == at::kFloat, "conv2d_b16: out must be bfloat16 or float32");
-    d.out = out->data_ptr(); d.out_ld = out->stride(0); d.out_coff = 0; d.out_bf16 = out->scalar_type() == at::kBFloat16;
+    const Rows o = rows(op, *out, "out", Any).expect(M, cout);
+    d.out = o.raw(); d.out_ld = o.ld; d.out_coff = 0; d.out_bf16 = o.b16;
   }
-  if (h.has_value()) { check_pm(*h, "h"); TORCH_CHECK(h->size(0) == M); d.h = fptr(*h); d.h_ld = h->stride(0); }
-  if (h_b16.has_value()) { check_pm_b16(*h_b16, "h_b16"); TORCH_CHECK(h_b16->size(0) == M); d.h_b16 = h_b16->data_ptr(); d.h_b16_ld = h_b16->stride(0); }
-  if (aux_z.has_value()) {
-    check_dev(*aux_z, "aux_z");
-    TORCH_CHECK(aux_z->scalar_type() == at::kBFloat16 && aux_z->is_contiguous(), "conv2d_b16: aux_z must be contiguous bfloat16");
-    d.aux_z = aux_z->data_ptr();
-  }
-  if (aux_rh.has_value()) {
-    check_dev(*aux_rh, "aux_rh");
-    TORCH_CHECK(aux_rh->scalar_type() == at::kBFloat16 && aux_rh->is_contiguous(), "conv2d_b16: aux_rh must be contiguous bfloat16");
-    d.aux_rh = aux_rh->data_ptr();
-  }
+  if (h.has_value()) { const Rows v = rows(op, *h, "h", F32).expect(M, AtLeast{Ch}); d.h = v.f32(); d.h_ld = v.ld; }
+  if (h_b16.has_value()) { const Rows v = rows(op, *h_b16, "h_b16", B16).expect(M, AtLeast{Ch}); d.h_b16 = v.raw(); d.h_b16_ld = v.ld; }
+  d.aux_z = dense(op, aux_z, "aux_z", B16, AtLeast{M * Ch}).raw();
+  d.aux_rh = dense(op, aux_rh, "aux_rh", B16, AtLeast{M * Ch}).raw();
   if (residual.has_value()) {
-    const bool r16 = check_pm_any(*residual, "residual");
-    TORCH_CHECK(lin || r16, "conv2d_b16: the GRU epilogues take a bfloat16 residual (the context term)");
-    TORCH_CHECK(residual->size(0) == M && residual->size(1) == cout, "conv2d_b16: residual must be a [M, cout] view");
-    d.residual = residual->data_ptr(); d.residual_ld = residual->stride(0); d.residual_bf16 = r16 && lin;
+    const Rows r = rows(op, *residual, "residual", Any).expect(M, cout);
+    TORCH_CHECK(lin || r.b16, "conv2d_b16: the GRU epilogues take a bfloat16 residual (the context term)");
+    d.residual = r.raw(); d.residual_ld = r.ld; d.residual_bf16 = r.b16 && lin;
   }
   if (gelu_entry) {
     check_ok(pfk_conv2d_gelu_b16(&d, cur_stream()), "conv2d_gelu_b16");
@@ -412,295 +300,252 @@ void debug_set_cin2_valu(int64_t on) { check_ok(pfk_debug_set_cin2_valu((int)on)
 void conv_cin2(const Tensor& in, const Tensor& weight, const c10::optional<Tensor>& bias, Tensor out,
                int64_t B, int64_t H, int64_t W, int64_t k, bool relu) {
   OpScope scope(in);
-  check_pm(in, "in"); check_dev_f32(weight, "weight");
-  const bool out_b16 = check_pm_any(out, "out");
-  const int cout = out.size(1);
-  TORCH_CHECK(weight.is_contiguous() && weight.numel() == k * k * 2 * cout, "conv_cin2: weight [k*k,2,cout]");
-  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == B * H * W && in.size(1) >= 2);
-  const float* bp = nullptr;
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); bp = fptr(*bias); }
-  if (out_b16) check_ok(pfk_conv_cin2_b16(fptr(in), in.stride(0), fptr(weight), bp, out.data_ptr(), out.stride(0), 0, B, H, W, k,
-                                          cout, relu, cur_stream()), "conv_cin2 (bf16 out)");
-  else check_ok(pfk_conv_cin2_f32(fptr(in), in.stride(0), fptr(weight), bp, fptr(out), out.stride(0), 0, B, H, W, k,
-                                  cout, relu, cur_stream()), "conv_cin2");
+  const Rows i = rows("conv_cin2", in, "inp", F32).expect(B * H * W, AtLeast{2});
+  const Rows o = rows("conv_cin2", out, "out", Any).expect(B * H * W, AtLeast{0});
+  const int cout = o.cols;
+  const float* wp = dense("conv_cin2", weight, "weight [k*k,2,cout]", F32, k * k * 2 * cout).f32();
+  const float* bp = dense("conv_cin2", bias, "bias", F32, AtLeast{cout}).f32();
+  if (o.b16) check_ok(pfk_conv_cin2_b16(i.f32(), i.ld, wp, bp, o.raw(), o.ld, 0, B, H, W, k, cout, relu, cur_stream()), "conv_cin2 (bf16 out)");
+  else check_ok(pfk_conv_cin2_f32(i.f32(), i.ld, wp, bp, o.f32(), o.ld, 0, B, H, W, k, cout, relu, cur_stream()), "conv_cin2");
 }
 
 void flow_delta(const Tensor& in, const Tensor& weight, const c10::optional<Tensor>& bias, const Tensor& coords0,
                 Tensor coords1, const c10::optional<Tensor>& delta_out, const c10::optional<Tensor>& flow_out,
                 const c10::optional<Tensor>& flow_out_b16) {
   OpScope scope(in);
-  const bool in_b16 = check_pm_any(in, "in");
-  check_dev_f32(weight, "weight"); check_dev_f32(coords0, "coords0"); check_dev_f32(coords1, "coords1");
-  TORCH_CHECK(coords0.dim() == 4 && coords0.size(1) == 2 && coords0.is_contiguous() && coords1.is_contiguous() &&
-              coords1.sizes() == coords0.sizes(), "flow_delta: coords [B,2,h,w] contiguous");
-  const int B = coords0.size(0), H = coords0.size(2), W = coords0.size(3), cin = in.size(1);
-  TORCH_CHECK(in.size(0) == (int64_t)B * H * W && weight.is_contiguous() && weight.numel() == 9 * 2 * cin);
-  const float* bp = nullptr; float* dp = nullptr; float* fp = nullptr; int fld = 0;
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); bp = fptr(*bias); }
-  if (delta_out.has_value()) { check_dev_f32(*delta_out, "delta"); TORCH_CHECK(delta_out->is_contiguous() && delta_out->sizes() == coords0.sizes()); dp = fptr(*delta_out); }
-  if (flow_out.has_value()) { check_pm(*flow_out, "flow_out"); TORCH_CHECK(flow_out->size(1) >= 2); fp = fptr(*flow_out); fld = flow_out->stride(0); }
-  if (in_b16) {
+  const float* c0 = dense("flow_delta", coords0, "coords0", F32).f32();
+  TORCH_CHECK(coords0.dim() == 4 && coords0.size(1) == 2, "flow_delta: coords0 must be [B,2,h,w] contiguous");
+  const int B = coords0.size(0), H = coords0.size(2), W = coords0.size(3);
+  const int64_t M = (int64_t)B * H * W;
+  float* c1 = dense("flow_delta", coords1, "coords1", F32, 2 * M).f32();
+  const Rows i = rows("flow_delta", in, "inp", Any).expect(M, AtLeast{0});
+  const int cin = i.cols;
+  const float* wp = dense("flow_delta", weight, "weight", F32, 9 * 2 * cin).f32();
+  const float* bp = dense("flow_delta", bias, "bias", F32, AtLeast{2}).f32();
+  float* dp = dense("flow_delta", delta_out, "delta_out", F32, 2 * M).f32();
+  TORCH_CHECK(coords1.sizes() == coords0.sizes() && (!delta_out.has_value() || delta_out->sizes() == coords0.sizes()),
+              "flow_delta: coords1 and delta_out must have coords0's shape");
+  float* fp = nullptr; int fld = 0;
+  if (flow_out.has_value()) { const Rows f = rows("flow_delta", *flow_out, "flow_out", F32).expect(M, AtLeast{2}); fp = f.f32(); fld = f.ld; }
+  if (i.b16) {
     void* fb = nullptr; int fbld = 0;
-    if (flow_out_b16.has_value()) { check_pm_b16(*flow_out_b16, "flow_out_b16"); TORCH_CHECK(flow_out_b16->size(1) >= 2); fb = flow_out_b16->data_ptr(); fbld = flow_out_b16->stride(0); }
-    check_ok(pfk_flow_delta_b16(in.data_ptr(), in.stride(0), cin, fptr(weight), bp, fptr(coords0), fptr(coords1), dp, fp, fld, fb, fbld,
-                                B, H, W, cur_stream()), "flow_delta (bf16 in)");
+    if (flow_out_b16.has_value()) {
+      const Rows f = rows("flow_delta", *flow_out_b16, "flow_out_b16", B16).expect(M, AtLeast{2});
+      fb = f.raw(); fbld = f.ld;
+    }
+    check_ok(pfk_flow_delta_b16(i.raw(), i.ld, cin, wp, bp, c0, c1, dp, fp, fld, fb, fbld, B, H, W, cur_stream()), "flow_delta (bf16 in)");
     return;
   }
   TORCH_CHECK(!flow_out_b16.has_value(), "flow_delta: flow_out_b16 goes with a bfloat16 input");
-  check_ok(pfk_flow_delta_f32(fptr(in), in.stride(0), cin, fptr(weight), bp, fptr(coords0), fptr(coords1), dp, fp,
-                              fld, B, H, W, cur_stream()), "flow_delta");
+  check_ok(pfk_flow_delta_f32(i.f32(), i.ld, cin, wp, bp, c0, c1, dp, fp, fld, B, H, W, cur_stream()), "flow_delta");
 }
 
 void flow_from_coords(const Tensor& coords0, const Tensor& coords1, Tensor flow_out) {
   OpScope scope(coords0);
-  check_dev_f32(coords0, "coords0"); check_dev_f32(coords1, "coords1"); check_pm(flow_out, "flow_out");
-  TORCH_CHECK(coords0.dim() == 4 && coords0.is_contiguous() && coords1.is_contiguous() && coords1.sizes() == coords0.sizes());
-  check_ok(pfk_flow_from_coords_f32(fptr(coords0), fptr(coords1), fptr(flow_out), flow_out.stride(0), coords0.size(0),
-                                    coords0.size(2), coords0.size(3), cur_stream()), "flow_from_coords");
+  const float* c0 = dense("flow_from_coords", coords0, "coords0", F32).f32();
+  TORCH_CHECK(coords0.dim() == 4 && coords0.size(1) == 2, "flow_from_coords: coords0 must be [B,2,h,w] contiguous");
+  const float* c1 = dense("flow_from_coords", coords1, "coords1", F32, coords0.numel()).f32();
+  TORCH_CHECK(coords1.sizes() == coords0.sizes(), "flow_from_coords: coords1 must have coords0's shape");
+  const int64_t B = coords0.size(0), H = coords0.size(2), W = coords0.size(3);
+  const Rows f = rows("flow_from_coords", flow_out, "flow_out", F32).expect(B * H * W, AtLeast{2});
+  check_ok(pfk_flow_from_coords_f32(c0, c1, f.f32(), f.ld, B, H, W, cur_stream()), "flow_from_coords");
 }
 
 void convex_upsample(const Tensor& flow, const Tensor& mask, Tensor out) {
   OpScope scope(flow);
-  check_dev_f32(flow, "flow"); check_pm(mask, "mask"); check_dev_f32(out, "out");
-  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2 && flow.is_contiguous() && out.is_contiguous());
+  const float* fp = dense("convex_upsample", flow, "flow", F32).f32();
+  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2, "convex_upsample: flow must be [B,2,H,W] contiguous");
   const int B = flow.size(0), H = flow.size(2), W = flow.size(3);
-  TORCH_CHECK(mask.size(0) == (int64_t)B * H * W && mask.size(1) == 576 && out.numel() == (int64_t)B * 2 * 64 * H * W);
-  check_ok(pfk_convex_upsample_f32(fptr(flow), fptr(mask), mask.stride(0), fptr(out), B, H, W, cur_stream()),
-           "convex_upsample");
+  const int64_t M = (int64_t)B * H * W;
+  const Rows m = rows("convex_upsample", mask, "mask", F32).expect(M, 576);
+  float* dst = dense("convex_upsample", out, "out [B,2,8H,8W]", F32, M * 2 * 64).f32();
+  check_ok(pfk_convex_upsample_f32(fp, m.f32(), m.ld, dst, B, H, W, cur_stream()), "convex_upsample");
 }
 
 void upflow8(const Tensor& coords0, const Tensor& coords1, Tensor out) {
   OpScope scope(coords0);
-  check_dev_f32(coords0, "coords0"); check_dev_f32(coords1, "coords1"); check_dev_f32(out, "out");
-  TORCH_CHECK(coords0.dim() == 4 && coords0.size(1) == 2 && coords0.is_contiguous() && coords1.is_contiguous() &&
-              coords1.sizes() == coords0.sizes(), "upflow8: coords [B, 2, H, W] contiguous");
-  const int64_t B = coords0.size(0), H = coords0.size(2), W = coords0.size(3);
-  TORCH_CHECK(out.is_contiguous() && out.dim() == 4 && out.size(0) == B && out.size(1) == 2 && out.size(2) == 8 * H && out.size(3) == 8 * W,
-              "upflow8: out [B, 2, 8H, 8W] contiguous");
-  check_ok(pfk_upflow8_f32(fptr(coords0), fptr(coords1), fptr(out), (int)B, (int)H, (int)W, cur_stream()), "upflow8");
+  const Up8 o = up8("upflow8", out, "out");
+  const float* c0 = dense("upflow8", coords0, "coords0", F32, 2 * o.rows()).f32();
+  const float* c1 = dense("upflow8", coords1, "coords1", F32, 2 * o.rows()).f32();
+  TORCH_CHECK(coords0.dim() == 4 && coords0.size(0) == o.B && coords0.size(1) == 2 && coords0.size(2) == o.H && coords0.size(3) == o.W &&
+              coords1.sizes() == coords0.sizes(), "upflow8: coords [B, 2, H, W] contiguous, out [B, 2, 8H, 8W]");
+  check_ok(pfk_upflow8_f32(c0, c1, o.ptr, o.B, o.H, o.W, cur_stream()), "upflow8");
 }
 
 void convex_upsample_pm(const Tensor& flow_pm, const Tensor& mask, Tensor out) {
   OpScope scope(flow_pm);
-  check_pm(flow_pm, "flow_pm"); check_dev_f32(out, "out");
-  const bool mask_b16 = check_pm_any(mask, "mask");
-  TORCH_CHECK(out.dim() == 4 && out.size(1) == 2 && out.is_contiguous() && out.size(2) % 8 == 0 && out.size(3) % 8 == 0);
-  const int B = out.size(0), H = out.size(2) / 8, W = out.size(3) / 8;
-  TORCH_CHECK(mask.size(0) == (int64_t)B * H * W && mask.size(1) == 576 && flow_pm.size(0) == mask.size(0) && flow_pm.size(1) >= 2);
-  if (mask_b16) {
-    check_ok(pfk_convex_upsample_pm_b16(fptr(flow_pm), flow_pm.stride(0), mask.data_ptr(), mask.stride(0), fptr(out), B, H, W, cur_stream()),
-             "convex_upsample_pm (bf16 mask)");
+  const Up8 o = up8("convex_upsample_pm", out, "out");
+  const Rows f = rows("convex_upsample_pm", flow_pm, "flow_pm", F32).expect(o.rows(), AtLeast{2});
+  const Rows m = rows("convex_upsample_pm", mask, "mask", Any).expect(o.rows(), 576);
+  if (m.b16) {
+    check_ok(pfk_convex_upsample_pm_b16(f.f32(), f.ld, m.raw(), m.ld, o.ptr, o.B, o.H, o.W, cur_stream()), "convex_upsample_pm (bf16 mask)");
     return;
   }
-  check_ok(pfk_convex_upsample_pm_f32(fptr(flow_pm), flow_pm.stride(0), fptr(mask), mask.stride(0), fptr(out), B, H, W,
-                                      cur_stream()), "convex_upsample_pm");
+  check_ok(pfk_convex_upsample_pm_f32(f.f32(), f.ld, m.f32(), m.ld, o.ptr, o.B, o.H, o.W, cur_stream()), "convex_upsample_pm");
 }
 
-// SEARAFT.upsample_data: flow_pm [M, >=2] / info_pm [M, >=n] / mask [M, 576] views, flow_out [B, 2, 8H, 8W], info_out [B, n, 8H, 8W]
+// SEARAFT.upsample_data: flow_pm [M, >=2] / info_pm [M, >=n] / mask [M, 576] views, flow_out [B, 2, 8H, 8W], info_out [B, n, 8H, 8W];
+// the mask fp32 (convex_upsample_info_pm) or bf16 (convex_upsample_info_pm_b16)
+void convex_upsample_info_pm_impl(const char* op, Elem mask_elem, const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask,
+                                  const Tensor& flow_out, const Tensor& info_out) {
+  OpScope scope(flow_pm);
+  const Up8 o = up8(op, flow_out, "flow_out");
+  float* io = dense(op, info_out, "info_out", F32).f32();
+  TORCH_CHECK(info_out.dim() == 4 && info_out.size(0) == o.B && info_out.size(2) == 8 * o.H && info_out.size(3) == 8 * o.W,
+              op, ": info_out [B, n, 8H, 8W] contiguous");
+  const int n = info_out.size(1);
+  const Rows f = rows(op, flow_pm, "flow_pm", F32).expect(o.rows(), AtLeast{2});
+  const Rows i = rows(op, info_pm, "info_pm", F32).expect(o.rows(), AtLeast{n});
+  const Rows m = rows(op, mask, "mask", mask_elem).expect(o.rows(), 576);
+  if (m.b16) check_ok(pfk_convex_upsample_info_pm_b16(f.f32(), f.ld, i.f32(), i.ld, n, m.raw(), m.ld, o.ptr, io, o.B, o.H, o.W, cur_stream()), op);
+  else check_ok(pfk_convex_upsample_info_pm_f32(f.f32(), f.ld, i.f32(), i.ld, n, m.f32(), m.ld, o.ptr, io, o.B, o.H, o.W, cur_stream()), op);
+}
 void convex_upsample_info_pm(const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask, Tensor flow_out, Tensor info_out) {
-  OpScope scope(flow_pm);
-  check_pm(flow_pm, "flow_pm"); check_pm(info_pm, "info_pm"); check_pm(mask, "mask");
-  check_dev_f32(flow_out, "flow_out"); check_dev_f32(info_out, "info_out");
-  TORCH_CHECK(flow_out.dim() == 4 && flow_out.size(1) == 2 && flow_out.is_contiguous() && flow_out.size(2) % 8 == 0 && flow_out.size(3) % 8 == 0,
-              "convex_upsample_info_pm: flow_out [B, 2, 8H, 8W] contiguous");
-  const int B = flow_out.size(0), H = flow_out.size(2) / 8, W = flow_out.size(3) / 8;
-  const int n = info_out.dim() == 4 ? (int)info_out.size(1) : 0;
-  TORCH_CHECK(info_out.dim() == 4 && info_out.is_contiguous() && info_out.size(0) == B && info_out.size(2) == 8 * H && info_out.size(3) == 8 * W,
-              "convex_upsample_info_pm: info_out [B, n, 8H, 8W] contiguous");
-  const int64_t M = (int64_t)B * H * W;
-  TORCH_CHECK(mask.size(0) == M && mask.size(1) == 576 && flow_pm.size(0) == M && flow_pm.size(1) >= 2 && info_pm.size(0) == M &&
-              info_pm.size(1) >= n, "convex_upsample_info_pm: row counts / widths");
-  check_ok(pfk_convex_upsample_info_pm_f32(fptr(flow_pm), flow_pm.stride(0), fptr(info_pm), info_pm.stride(0), n, fptr(mask),
-                                           mask.stride(0), fptr(flow_out), fptr(info_out), B, H, W, cur_stream()),
-           "convex_upsample_info_pm");
+  convex_upsample_info_pm_impl("convex_upsample_info_pm", F32, flow_pm, info_pm, mask, flow_out, info_out);
 }
-
-// the same with a bf16 mask [M, 576] view (pfk_convex_upsample_info_pm_b16)
 void convex_upsample_info_pm_b16(const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask, Tensor flow_out, Tensor info_out) {
-  OpScope scope(flow_pm);
-  check_pm(flow_pm, "flow_pm"); check_pm(info_pm, "info_pm"); check_pm_b16(mask, "mask");
-  check_dev_f32(flow_out, "flow_out"); check_dev_f32(info_out, "info_out");
-  TORCH_CHECK(flow_out.dim() == 4 && flow_out.size(1) == 2 && flow_out.is_contiguous() && flow_out.size(2) % 8 == 0 && flow_out.size(3) % 8 == 0,
-              "convex_upsample_info_pm_b16: flow_out [B, 2, 8H, 8W] contiguous");
-  const int B = flow_out.size(0), H = flow_out.size(2) / 8, W = flow_out.size(3) / 8;
-  const int n = info_out.dim() == 4 ? (int)info_out.size(1) : 0;
-  TORCH_CHECK(info_out.dim() == 4 && info_out.is_contiguous() && info_out.size(0) == B && info_out.size(2) == 8 * H && info_out.size(3) == 8 * W,
-              "convex_upsample_info_pm_b16: info_out [B, n, 8H, 8W] contiguous");
-  const int64_t M = (int64_t)B * H * W;
-  TORCH_CHECK(mask.size(0) == M && mask.size(1) == 576 && flow_pm.size(0) == M && flow_pm.size(1) >= 2 && info_pm.size(0) == M &&
-              info_pm.size(1) >= n, "convex_upsample_info_pm_b16: row counts / widths");
-  check_ok(pfk_convex_upsample_info_pm_b16(fptr(flow_pm), flow_pm.stride(0), fptr(info_pm), info_pm.stride(0), n, mask.data_ptr(),
-                                           mask.stride(0), fptr(flow_out), fptr(info_out), B, H, W, cur_stream()),
-           "convex_upsample_info_pm_b16");
-}
-
-// ConvNextBlock dwconv + LayerNorm on bf16 rows (pfk_dwconv_layernorm_b16): in / out bf16 [B*H*W, >= C] views, weights fp32 as below
-void dwconv_layernorm_b16(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
-                          const Tensor& ln_bias, double eps, Tensor out, int64_t B, int64_t H, int64_t W, int64_t k) {
-  OpScope scope(in);
-  check_pm_b16(in, "in"); check_pm_b16(out, "out");
-  check_dev_f32(dw_weight, "dw_weight"); check_dev_f32(ln_weight, "ln_weight"); check_dev_f32(ln_bias, "ln_bias");
-  const int64_t C = in.size(1);
-  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == in.size(0) && out.size(1) >= C, "dwconv_layernorm_b16: in / out rows");
-  TORCH_CHECK(dw_weight.is_contiguous() && dw_weight.numel() == C * k * k, "dwconv_layernorm_b16: dw_weight [C, k*k] contiguous");
-  TORCH_CHECK(ln_weight.is_contiguous() && ln_weight.numel() == C && ln_bias.is_contiguous() && ln_bias.numel() == C,
-              "dwconv_layernorm_b16: LayerNorm weight / bias [C]");
-  const float* db = nullptr;
-  if (dw_bias.has_value()) {
-    check_dev_f32(*dw_bias, "dw_bias");
-    TORCH_CHECK(dw_bias->is_contiguous() && dw_bias->numel() == C, "dwconv_layernorm_b16: dw_bias [C]");
-    db = fptr(*dw_bias);
-  }
-  check_ok(pfk_dwconv_layernorm_b16(in.data_ptr(), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps,
-                                    out.data_ptr(), out.stride(0), B, H, W, C, k, cur_stream()), "dwconv_layernorm_b16");
+  convex_upsample_info_pm_impl("convex_upsample_info_pm_b16", B16, flow_pm, info_pm, mask, flow_out, info_out);
 }
 
 // ConvNextBlock dwconv + LayerNorm: in [B*H*W, C] view (e.g. a slice of the update engine's hx), dw_weight [C, 1, k, k] or [C, k*k]
-// contiguous, out [B*H*W, >= C] view
+// contiguous, out [B*H*W, >= C] view; weights fp32.  Rows fp32 (dwconv_layernorm) or bf16 (pfk_dwconv_layernorm_b16)
+void dwconv_layernorm_impl(const char* op, Elem e, const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias,
+                           const Tensor& ln_weight, const Tensor& ln_bias, double eps, const Tensor& out, int64_t B, int64_t H, int64_t W,
+                           int64_t k) {
+  OpScope scope(in);
+  const Rows i = rows(op, in, "inp", e).expect(B * H * W, AtLeast{0});
+  const int64_t C = i.cols;
+  const Rows o = rows(op, out, "out", e).expect(B * H * W, AtLeast{C});
+  const float* dw = dense(op, dw_weight, "dw_weight [C, k*k]", F32, C * k * k).f32();
+  const float* db = dense(op, dw_bias, "dw_bias", F32, C).f32();
+  const float* lw = dense(op, ln_weight, "ln_weight", F32, C).f32();
+  const float* lb = dense(op, ln_bias, "ln_bias", F32, C).f32();
+  if (e == B16) check_ok(pfk_dwconv_layernorm_b16(i.raw(), i.ld, dw, db, lw, lb, (float)eps, o.raw(), o.ld, B, H, W, C, k, cur_stream()), op);
+  else check_ok(pfk_dwconv_layernorm_f32(i.f32(), i.ld, dw, db, lw, lb, (float)eps, o.f32(), o.ld, B, H, W, C, k, cur_stream()), op);
+}
 void dwconv_layernorm(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
                       const Tensor& ln_bias, double eps, Tensor out, int64_t B, int64_t H, int64_t W, int64_t k) {
-  OpScope scope(in);
-  check_pm(in, "in"); check_pm(out, "out");
-  check_dev_f32(dw_weight, "dw_weight"); check_dev_f32(ln_weight, "ln_weight"); check_dev_f32(ln_bias, "ln_bias");
-  const int64_t C = in.size(1);
-  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == in.size(0) && out.size(1) >= C, "dwconv_layernorm: in / out rows");
-  TORCH_CHECK(dw_weight.is_contiguous() && dw_weight.numel() == C * k * k, "dwconv_layernorm: dw_weight [C, k*k] contiguous");
-  TORCH_CHECK(ln_weight.is_contiguous() && ln_weight.numel() == C && ln_bias.is_contiguous() && ln_bias.numel() == C,
-              "dwconv_layernorm: LayerNorm weight / bias [C]");
-  const float* db = nullptr;
-  if (dw_bias.has_value()) {
-    check_dev_f32(*dw_bias, "dw_bias");
-    TORCH_CHECK(dw_bias->is_contiguous() && dw_bias->numel() == C, "dwconv_layernorm: dw_bias [C]");
-    db = fptr(*dw_bias);
-  }
-  check_ok(pfk_dwconv_layernorm_f32(fptr(in), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps, fptr(out),
-                                    out.stride(0), B, H, W, C, k, cur_stream()), "dwconv_layernorm");
+  dwconv_layernorm_impl("dwconv_layernorm", F32, in, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, B, H, W, k);
+}
+void dwconv_layernorm_b16(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                          const Tensor& ln_bias, double eps, Tensor out, int64_t B, int64_t H, int64_t W, int64_t k) {
+  dwconv_layernorm_impl("dwconv_layernorm_b16", B16, in, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, B, H, W, k);
 }
 
 // ---- K12d: training the ConvNeXt block (pfk_convnext_bwd.hip).  Row views [M, C] of wider buffers are fine; only C columns are touched.
-namespace {
-void check_vec(const Tensor& t, int64_t n, const char* name) {
-  check_dev_f32(t, name);
-  TORCH_CHECK(t.is_contiguous() && t.numel() == n, name, " must be contiguous with ", n, " elements");
-}
-}  // namespace
 
 // dwconv_layernorm that also saves xhat [M, >= C] and rstd [M] for the backward; `out` has dwconv_layernorm's bits
 void dwconv_layernorm_train(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
                             const Tensor& ln_bias, double eps, Tensor out, Tensor xhat, Tensor rstd, int64_t B, int64_t H, int64_t W,
                             int64_t k) {
   OpScope scope(in);
-  check_pm(in, "in"); check_pm(out, "out"); check_pm(xhat, "xhat");
-  const int64_t C = in.size(1), M = B * H * W;
-  TORCH_CHECK(in.size(0) == M && out.size(0) == M && xhat.size(0) == M && out.size(1) == C && xhat.size(1) == C,
-              "dwconv_layernorm_train: in / out / xhat [B*H*W, C]");
-  check_vec(dw_weight, C * k * k, "dw_weight"); check_vec(ln_weight, C, "ln_weight"); check_vec(ln_bias, C, "ln_bias");
-  check_vec(rstd, M, "rstd");
-  const float* db = nullptr;
-  if (dw_bias.has_value()) { check_vec(*dw_bias, C, "dw_bias"); db = fptr(*dw_bias); }
-  check_ok(pfk_dwconv_layernorm_train_f32(fptr(in), in.stride(0), fptr(dw_weight), db, fptr(ln_weight), fptr(ln_bias), (float)eps,
-                                          fptr(out), out.stride(0), fptr(xhat), xhat.stride(0), fptr(rstd), B, H, W, C, k, cur_stream()),
-           "dwconv_layernorm_train");
+  const char* op = "dwconv_layernorm_train";
+  const int64_t M = B * H * W;
+  const Rows i = rows(op, in, "inp", F32).expect(M, AtLeast{0});
+  const int64_t C = i.cols;
+  const Rows o = rows(op, out, "out", F32).expect(M, C), x = rows(op, xhat, "xhat", F32).expect(M, C);
+  const float* dw = dense(op, dw_weight, "dw_weight", F32, C * k * k).f32();
+  const float* db = dense(op, dw_bias, "dw_bias", F32, C).f32();
+  const float* lw = dense(op, ln_weight, "ln_weight", F32, C).f32();
+  const float* lb = dense(op, ln_bias, "ln_bias", F32, C).f32();
+  float* rs = dense(op, rstd, "rstd", F32, M).f32();
+  check_ok(pfk_dwconv_layernorm_train_f32(i.f32(), i.ld, dw, db, lw, lb, (float)eps, o.f32(), o.ld, x.f32(), x.ld, rs, B, H, W, C, k,
+                                          cur_stream()), op);
 }
 
 void layernorm_bwd(const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy, Tensor du, Tensor dgamma,
                    Tensor dbeta) {
   OpScope scope(xhat);
-  check_pm(xhat, "xhat"); check_pm(dy, "dy"); check_pm(du, "du");
-  const int64_t M = xhat.size(0), C = xhat.size(1);
-  TORCH_CHECK(dy.size(0) == M && dy.size(1) == C && du.size(0) == M && du.size(1) == C, "layernorm_bwd: xhat / dy / du [M, C]");
-  check_vec(rstd, M, "rstd"); check_vec(ln_weight, C, "ln_weight"); check_vec(dgamma, C, "dgamma"); check_vec(dbeta, C, "dbeta");
+  const char* op = "layernorm_bwd";
+  const Rows x = rows(op, xhat, "xhat", F32);
+  const int64_t M = x.rows, C = x.cols;
+  const Rows g = rows(op, dy, "dy", F32).expect(M, C), u = rows(op, du, "du", F32).expect(M, C);
+  const float* rs = dense(op, rstd, "rstd", F32, M).f32();
+  const float* lw = dense(op, ln_weight, "ln_weight", F32, C).f32();
+  float* dg = dense(op, dgamma, "dgamma", F32, C).f32();
+  float* dbt = dense(op, dbeta, "dbeta", F32, C).f32();
   const long long need = pfk_layernorm_bwd_workspace_bytes(M, C);
-  Tensor ws = at::empty({(int64_t)need}, xhat.options().dtype(at::kByte));
-  check_ok(pfk_layernorm_bwd_f32(fptr(xhat), xhat.stride(0), fptr(rstd), fptr(ln_weight), fptr(dy), dy.stride(0), fptr(du), du.stride(0),
-                                 fptr(dgamma), fptr(dbeta), ws.data_ptr(), need, M, C, cur_stream()), "layernorm_bwd");
+  const auto ws = byte_workspace(need, xhat);
+  check_ok(pfk_layernorm_bwd_f32(x.f32(), x.ld, rs, lw, g.f32(), g.ld, u.f32(), u.ld, dg, dbt, ws.second, need, M, C, cur_stream()), op);
 }
 
 void dwconv_bwd(const Tensor& in, const Tensor& du, const Tensor& dw_weight, Tensor dx, Tensor dweight, const c10::optional<Tensor>& dbias,
                 int64_t B, int64_t H, int64_t W, int64_t k) {
   OpScope scope(in);
-  check_pm(in, "in"); check_pm(du, "du"); check_pm(dx, "dx");
-  const int64_t C = in.size(1), M = B * H * W;
-  TORCH_CHECK(in.size(0) == M && du.size(0) == M && dx.size(0) == M && du.size(1) == C && dx.size(1) == C, "dwconv_bwd: in / du / dx [B*H*W, C]");
-  check_vec(dw_weight, C * k * k, "dw_weight"); check_vec(dweight, C * k * k, "dweight");
-  float* db = nullptr;
-  if (dbias.has_value()) { check_vec(*dbias, C, "dbias"); db = fptr(*dbias); }
+  const char* op = "dwconv_bwd";
+  const int64_t M = B * H * W;
+  const Rows i = rows(op, in, "inp", F32).expect(M, AtLeast{0});
+  const int64_t C = i.cols;
+  const Rows u = rows(op, du, "du", F32).expect(M, C), x = rows(op, dx, "dx", F32).expect(M, C);
+  const float* w = dense(op, dw_weight, "dw_weight", F32, C * k * k).f32();
+  float* dw = dense(op, dweight, "dweight", F32, C * k * k).f32();
+  float* db = dense(op, dbias, "dbias", F32, C).f32();
   const long long need = pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k);
-  Tensor ws = at::empty({(int64_t)need}, in.options().dtype(at::kByte));
-  check_ok(pfk_dwconv_bwd_f32(fptr(in), in.stride(0), fptr(du), du.stride(0), fptr(dw_weight), fptr(dx), dx.stride(0), fptr(dweight), db,
-                              ws.data_ptr(), need, B, H, W, C, k, cur_stream()), "dwconv_bwd");
+  const auto ws = byte_workspace(need, in);
+  check_ok(pfk_dwconv_bwd_f32(i.f32(), i.ld, u.f32(), u.ld, w, x.f32(), x.ld, dw, db, ws.second, need, B, H, W, C, k, cur_stream()), op);
 }
 
 void gelu_rows(const Tensor& x, Tensor y) {
   OpScope scope(x);
-  check_pm(x, "x"); check_pm(y, "y");
-  TORCH_CHECK(y.size(0) == x.size(0) && y.size(1) == x.size(1), "gelu: x / y [M, C]");
-  check_ok(pfk_gelu_f32(fptr(x), x.stride(0), fptr(y), y.stride(0), x.size(0), x.size(1), cur_stream()), "gelu");
+  const Rows a = rows("gelu", x, "x", F32), b = rows("gelu", y, "y", F32).expect(a.rows, a.cols);
+  check_ok(pfk_gelu_f32(a.f32(), a.ld, b.f32(), b.ld, a.rows, a.cols, cur_stream()), "gelu");
 }
 
 void gelu_rows_bwd(const Tensor& x, const Tensor& dy, Tensor dx) {
   OpScope scope(x);
-  check_pm(x, "x"); check_pm(dy, "dy"); check_pm(dx, "dx");
-  TORCH_CHECK(dy.size(0) == x.size(0) && dy.size(1) == x.size(1) && dx.size(0) == x.size(0) && dx.size(1) == x.size(1),
-              "gelu_bwd: x / dy / dx [M, C]");
-  check_ok(pfk_gelu_bwd_f32(fptr(x), x.stride(0), fptr(dy), dy.stride(0), fptr(dx), dx.stride(0), x.size(0), x.size(1), cur_stream()),
-           "gelu_bwd");
+  const Rows a = rows("gelu_bwd", x, "x", F32), g = rows("gelu_bwd", dy, "dy", F32).expect(a.rows, a.cols);
+  const Rows d = rows("gelu_bwd", dx, "dx", F32).expect(a.rows, a.cols);
+  check_ok(pfk_gelu_bwd_f32(a.f32(), a.ld, g.f32(), g.ld, d.f32(), d.ld, a.rows, a.cols, cur_stream()), "gelu_bwd");
 }
 
 // fused mask conv2 + softmax + convex upsampling: x [M, cin] (a view of the fh|mask hidden buffer), weight / bias row-permuted (pfk.h)
 void mask_upsample(const Tensor& x, const Tensor& weight_perm, const c10::optional<Tensor>& bias_perm, double scale,
                    const Tensor& flow_pm, Tensor out) {
   OpScope scope(x);
-  const bool b16 = check_pm_any(x, "x");
-  check_pm(flow_pm, "flow_pm"); check_dev_f32(out, "out");
-  if (b16) check_dev(weight_perm, "weight"); else check_dev_f32(weight_perm, "weight");
-  TORCH_CHECK(!b16 || weight_perm.scalar_type() == at::kBFloat16, "mask_upsample: a bf16 activation needs the bf16 permuted weight");
-  TORCH_CHECK(out.dim() == 4 && out.size(1) == 2 && out.is_contiguous() && out.size(2) % 8 == 0 && out.size(3) % 8 == 0, "mask_upsample: out [B,2,8H,8W]");
-  const int B = out.size(0), H = out.size(2) / 8, W = out.size(3) / 8;
-  const int cin = x.size(1);
-  TORCH_CHECK(x.size(0) == (int64_t)B * H * W && flow_pm.size(0) == x.size(0) && flow_pm.size(1) >= 2, "mask_upsample: rows");
-  TORCH_CHECK(weight_perm.is_contiguous() && weight_perm.dim() == 2 && weight_perm.size(0) == 640 && weight_perm.size(1) == cin, "mask_upsample: weight [640, cin] (packing.permute_mask_head)");
-  const float* bp = nullptr;
-  if (bias_perm.has_value()) { check_dev_f32(*bias_perm, "bias"); TORCH_CHECK(bias_perm->numel() == 640 && bias_perm->is_contiguous()); bp = fptr(*bias_perm); }
-  if (b16) {
-    check_ok(pfk_mask_upsample_b16(x.data_ptr(), x.stride(0), cin, weight_perm.data_ptr(), bp, (float)scale, fptr(flow_pm), flow_pm.stride(0),
-                                   fptr(out), B, H, W, cur_stream()), "mask_upsample (bf16)");
+  const Up8 o = up8("mask_upsample", out, "out");
+  const Rows a = rows("mask_upsample", x, "x", Any).expect(o.rows(), AtLeast{0});
+  const Rows f = rows("mask_upsample", flow_pm, "flow_pm", F32).expect(o.rows(), AtLeast{2});
+  const int cin = a.cols;
+  // a bf16 activation needs the bf16 permuted weight
+  const Ptr w = dense("mask_upsample", weight_perm, "weight_perm", a.b16 ? B16 : F32, 640 * (int64_t)cin);
+  TORCH_CHECK(weight_perm.dim() == 2 && weight_perm.size(0) == 640, "mask_upsample: weight_perm [640, cin] (packing.permute_mask_head)");
+  const float* bp = dense("mask_upsample", bias_perm, "bias_perm", F32, 640).f32();
+  if (a.b16) {
+    check_ok(pfk_mask_upsample_b16(a.raw(), a.ld, cin, w.raw(), bp, (float)scale, f.f32(), f.ld, o.ptr, o.B, o.H, o.W, cur_stream()),
+             "mask_upsample (bf16)");
     return;
   }
-  check_ok(pfk_mask_upsample_f32(fptr(x), x.stride(0), cin, fptr(weight_perm), bp, (float)scale, fptr(flow_pm), flow_pm.stride(0),
-                                 fptr(out), B, H, W, cur_stream()), "mask_upsample");
+  check_ok(pfk_mask_upsample_f32(a.f32(), a.ld, cin, w.f32(), bp, (float)scale, f.f32(), f.ld, o.ptr, o.B, o.H, o.W, cur_stream()),
+           "mask_upsample");
 }
 
 // alt_cuda_corr.forward semantics (correlation.cpp:23-37): returns [B, N, (2r+1)^2, H1, W1], unscaled
 Tensor altcorr_forward(const Tensor& fmap1, const Tensor& fmap2, const Tensor& coords, int64_t radius) {
   OpScope scope(fmap1);
+  const char* op = "altcorr_forward";
   // fp32 maps (the reference extension's only type, correlation_kernel.cu:275) or bf16 maps (pfk_altcorr_forward_bf16: exact widening,
   // fp32 products and accumulation; the result is fp32 either way — coords stay fp32)
-  const bool bf = fmap1.scalar_type() == at::kBFloat16;
-  if (bf) {
-    TORCH_CHECK(fmap1.is_cuda() && fmap2.is_cuda() && fmap2.scalar_type() == at::kBFloat16, "altcorr_forward: both feature maps bf16 on the GPU");
-  } else {
-    check_dev_f32(fmap1, "fmap1"); check_dev_f32(fmap2, "fmap2");
-  }
-  check_dev_f32(coords, "coords");
+  const Ptr f1 = dense(op, fmap1, "fmap1", Any), f2 = dense(op, fmap2, "fmap2", f1.b16 ? B16 : F32);    // CHECK_CONTIGUOUS in the reference
+  dense(op, coords, "coords", F32);
   TORCH_CHECK(fmap1.dim() == 4 && fmap2.dim() == 4 && coords.dim() == 5 && coords.size(4) == 2, "altcorr_forward: fmap [B,H,W,C], coords [B,N,H1,W1,2]");
-  TORCH_CHECK(fmap1.is_contiguous() && fmap2.is_contiguous() && coords.is_contiguous(), "altcorr_forward: contiguous inputs");  // CHECK_CONTIGUOUS in the reference
   const int B = fmap1.size(0), H1 = fmap1.size(1), W1 = fmap1.size(2), C = fmap1.size(3);
   const int H2 = fmap2.size(1), W2 = fmap2.size(2), N = coords.size(1);
-  TORCH_CHECK(fmap2.size(0) == B && fmap2.size(3) == C && coords.size(0) == B && coords.size(2) == H1 && coords.size(3) == W1);
+  TORCH_CHECK(fmap2.size(0) == B && fmap2.size(3) == C && coords.size(0) == B && coords.size(2) == H1 && coords.size(3) == W1,
+              "altcorr_forward: fmap2 / coords do not match fmap1's [B,H1,W1,C]");
   const int rd = 2 * radius + 1;
   Tensor out = at::empty({B, N, rd * rd, H1, W1}, coords.options());
   // the launch-wide gate's per-block counts (pfk.h): a few hundred bytes from the caching allocator, written before they are read
   Tensor ws = at::empty({std::max<int64_t>(1, pfk_altcorr_workspace_bytes(B, H1, W1) / 4)}, coords.options().dtype(at::kInt));
+  void* wsp = dense(op, ws, "workspace", Raw).raw();
   for (int n = 0; n < N; ++n) {
     Tensor cn = coords.select(1, n).contiguous();
     Tensor on = N == 1 ? out.view({B, rd * rd, H1, W1}) : at::empty({B, rd * rd, H1, W1}, coords.options());
-    if (bf)
-      check_ok(pfk_altcorr_forward_bf16(fmap1.data_ptr(), fmap2.data_ptr(), fptr(cn), fptr(on), B, H1, W1, H2, W2, C, radius, ws.data_ptr(), cur_stream()),
-               "altcorr_forward (bf16 maps)");
+    const float* cp = dense(op, cn, "coords", F32, (int64_t)B * H1 * W1 * 2).f32();
+    float* dst = dense(op, on, "out", F32, (int64_t)B * rd * rd * H1 * W1).f32();
+    if (f1.b16)
+      check_ok(pfk_altcorr_forward_bf16(f1.raw(), f2.raw(), cp, dst, B, H1, W1, H2, W2, C, radius, wsp, cur_stream()), "altcorr_forward (bf16 maps)");
     else
-      check_ok(pfk_altcorr_forward_f32(fptr(fmap1), fptr(fmap2), fptr(cn), fptr(on), B, H1, W1, H2, W2, C, radius, ws.data_ptr(), cur_stream()),
-               "altcorr_forward");
+      check_ok(pfk_altcorr_forward_f32(f1.f32(), f2.f32(), cp, dst, B, H1, W1, H2, W2, C, radius, wsp, cur_stream()), "altcorr_forward");
     if (N != 1) out.select(1, n).copy_(on);
   }
   return out;
@@ -710,10 +555,12 @@ Tensor altcorr_forward(const Tensor& fmap1, const Tensor& fmap2, const Tensor& c
 std::vector<Tensor> altcorr_backward(const Tensor& fmap1, const Tensor& fmap2, const Tensor& coords, const Tensor& corr_grad,
                                      int64_t radius) {
   OpScope scope(fmap1);
-  check_dev_f32(fmap1, "fmap1"); check_dev_f32(fmap2, "fmap2"); check_dev_f32(coords, "coords"); check_dev_f32(corr_grad, "corr_grad");
-  TORCH_CHECK(fmap1.is_contiguous() && fmap2.is_contiguous() && coords.is_contiguous() && corr_grad.is_contiguous(),
-              "altcorr_backward: contiguous inputs");
-  TORCH_CHECK(fmap1.dim() == 4 && fmap2.dim() == 4 && coords.dim() == 5 && corr_grad.dim() == 5);
+  const char* op = "altcorr_backward";
+  const float* f1 = dense(op, fmap1, "fmap1", F32).f32();
+  const float* f2 = dense(op, fmap2, "fmap2", F32).f32();
+  dense(op, coords, "coords", F32); dense(op, corr_grad, "corr_grad", F32);
+  TORCH_CHECK(fmap1.dim() == 4 && fmap2.dim() == 4 && coords.dim() == 5 && corr_grad.dim() == 5,
+              "altcorr_backward: fmap [B,H,W,C], coords [B,N,H1,W1,2], corr_grad [B,N,(2r+1)^2,H1,W1]");
   const int B = fmap1.size(0), H1 = fmap1.size(1), W1 = fmap1.size(2), C = fmap1.size(3);
   const int H2 = fmap2.size(1), W2 = fmap2.size(2), N = coords.size(1);
   const int rd = 2 * radius + 1;
@@ -725,8 +572,9 @@ std::vector<Tensor> altcorr_backward(const Tensor& fmap1, const Tensor& fmap2, c
     Tensor cn = N == 1 ? coords.view({B, H1, W1, 2}) : coords.select(1, n).contiguous();
     Tensor gn = N == 1 ? corr_grad.view({B, rd * rd, H1, W1}) : corr_grad.select(1, n).contiguous();
     Tensor t1 = n == 0 ? g1 : at::empty_like(fmap1), t2 = n == 0 ? g2 : at::empty_like(fmap2);
-    check_ok(pfk_altcorr_backward_f32(fptr(fmap1), fptr(fmap2), fptr(cn), fptr(gn), fptr(t1), fptr(t2), B, H1, W1, H2, W2, C, radius,
-                                      cur_stream()), "altcorr_backward");
+    check_ok(pfk_altcorr_backward_f32(f1, f2, dense(op, cn, "coords", F32).f32(), dense(op, gn, "corr_grad", F32).f32(),
+                                      dense(op, t1, "fmap1_grad", F32, fmap1.numel()).f32(), dense(op, t2, "fmap2_grad", F32, fmap2.numel()).f32(),
+                                      B, H1, W1, H2, W2, C, radius, cur_stream()), op);
     if (n) { g1.add_(t1); g2.add_(t2); }
   }
   return {g1, g2, gc};
@@ -735,53 +583,21 @@ std::vector<Tensor> altcorr_backward(const Tensor& fmap1, const Tensor& fmap2, c
 // ---- blocked volume layout (include/pfk.h "K1-K3 on the BLOCKED volume layout"): levels are [M, pfk_blocked_map_elems(h_l, w_l)]
 void fmap_to_blocked(const Tensor& in, Tensor out, int64_t B, int64_t H, int64_t W) {
   OpScope scope(in);
-  check_pm(in, "in"); check_pm(out, "out");
-  TORCH_CHECK(in.size(0) == B * H * W && out.size(0) == B * pfk_blocked_map_elems((int)H, (int)W) && out.size(1) == in.size(1),
-              "fmap_to_blocked: in [B*H*W, C], out [B*blocked_map_elems(H, W), C]");
-  check_ok(pfk_fmap_to_blocked_f32(fptr(in), in.stride(0), fptr(out), out.stride(0), (int)B, (int)H, (int)W, (int)in.size(1), cur_stream()),
-           "fmap_to_blocked");
+  const Rows i = rows("fmap_to_blocked", in, "inp", F32).expect(B * H * W, AtLeast{0});
+  const Rows o = rows("fmap_to_blocked", out, "out [B*blocked_map_elems(H, W), C]", F32).expect(B * pfk_blocked_map_elems((int)H, (int)W), i.cols);
+  check_ok(pfk_fmap_to_blocked_f32(i.f32(), i.ld, o.f32(), o.ld, (int)B, (int)H, (int)W, (int)i.cols, cur_stream()), "fmap_to_blocked");
 }
 
 void corr_pool2x2_blocked(const Tensor& in, Tensor out, int64_t H, int64_t W) {
   OpScope scope(in);
-  check_dev(in, "in"); check_dev(out, "out");
-  TORCH_CHECK(in.scalar_type() == out.scalar_type() && (in.scalar_type() == at::kFloat || in.scalar_type() == at::kBFloat16),
-              "corr_pool2x2_blocked: float32 or bfloat16 maps");
-  TORCH_CHECK(in.dim() == 2 && out.dim() == 2 && in.is_contiguous() && out.is_contiguous() && in.size(0) == out.size(0),
-              "corr_pool2x2_blocked: [M, elems] contiguous");
+  const char* op = "corr_pool2x2_blocked";
+  const Ptr i = dense(op, in, "inp", Any), o = dense(op, out, "out", i.b16 ? B16 : F32);
+  TORCH_CHECK(in.dim() == 2 && out.dim() == 2 && in.size(0) == out.size(0), "corr_pool2x2_blocked: [M, elems] contiguous");
   TORCH_CHECK(in.size(1) == pfk_blocked_map_elems((int)H, (int)W) && out.size(1) == pfk_blocked_map_elems((int)(H / 2), (int)(W / 2)),
               "corr_pool2x2_blocked: map sizes");
   if (out.numel() == 0) return;
-  if (in.scalar_type() == at::kFloat) check_ok(pfk_corr_pool2x2_blocked_f32(fptr(in), fptr(out), in.size(0), (int)H, (int)W, cur_stream()), "corr_pool2x2_blocked");
-  else check_ok(pfk_corr_pool2x2_blocked_bf16(in.data_ptr(), out.data_ptr(), in.size(0), (int)H, (int)W, cur_stream()), "corr_pool2x2_blocked (bf16)");
-}
-
-void corr_lookup_blocked(at::TensorList levels, at::IntArrayRef lvl_h, at::IntArrayRef lvl_w, const Tensor& coords, int64_t radius, Tensor out) {
-  OpScope scope(coords);
-  check_dev_f32(coords, "coords");
-  const bool out_b16 = check_pm_any(out, "out");
-  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2 && coords.is_contiguous(), "corr_lookup_blocked: coords [B,2,h,w] contiguous");
-  TORCH_CHECK(levels.size() >= 1 && levels.size() <= PFK_MAX_LEVELS && lvl_h.size() == levels.size() && lvl_w.size() == levels.size(),
-              "corr_lookup_blocked: 1..8 levels with their map sizes");
-  pfk_lookup_desc d{};
-  d.B = coords.size(0); d.h = coords.size(2); d.w = coords.size(3);
-  const int64_t M = (int64_t)d.B * d.h * d.w;
-  const bool bf = levels[0].scalar_type() == at::kBFloat16;
-  for (size_t l = 0; l < levels.size(); ++l) {
-    const Tensor& v = levels[l];
-    check_dev(v, "level");
-    TORCH_CHECK(v.scalar_type() == (bf ? at::kBFloat16 : at::kFloat), "corr_lookup_blocked: levels must all be float32 or all bfloat16");
-    TORCH_CHECK(lvl_h[l] > 0 && lvl_w[l] > 0 && v.dim() == 2 && v.is_contiguous() && v.size(0) == M &&
-                v.size(1) == pfk_blocked_map_elems((int)lvl_h[l], (int)lvl_w[l]),
-                "corr_lookup_blocked: level must be [B*N, blocked_map_elems(h_l, w_l)] contiguous");
-    d.levels[l] = v.data_ptr(); d.lvl_h[l] = (int)lvl_h[l]; d.lvl_w[l] = (int)lvl_w[l];
-  }
-  d.num_levels = levels.size(); d.radius = radius;
-  d.coords = fptr(coords); d.out = out.data_ptr(); d.out_ld = out.stride(0); d.out_bf16 = out_b16;
-  TORCH_CHECK(out.size(0) == M, "corr_lookup_blocked: out rows");
-  const int n = 2 * radius + 1;
-  TORCH_CHECK(out.size(1) >= d.num_levels * n * n, "corr_lookup_blocked: out channels");
-  check_ok(bf ? pfk_corr_lookup_blocked_bf16(&d, cur_stream()) : pfk_corr_lookup_blocked_f32(&d, cur_stream()), "corr_lookup_blocked");
+  if (i.b16) check_ok(pfk_corr_pool2x2_blocked_bf16(i.raw(), o.raw(), in.size(0), (int)H, (int)W, cur_stream()), "corr_pool2x2_blocked (bf16)");
+  else check_ok(pfk_corr_pool2x2_blocked_f32(i.f32(), o.f32(), in.size(0), (int)H, (int)W, cur_stream()), op);
 }
 
 int64_t blocked_map_elems(int64_t H, int64_t W) { return pfk_blocked_map_elems((int)H, (int)W); }
@@ -790,24 +606,23 @@ int64_t blocked_map_elems(int64_t H, int64_t W) { return pfk_blocked_map_elems((
 void corr_lookup_bwd(at::TensorList grad_levels, at::IntArrayRef lvl_h, at::IntArrayRef lvl_w, const Tensor& coords,
                      int64_t radius, const Tensor& grad_out) {
   OpScope scope(coords);
-  check_dev_f32(coords, "coords"); check_pm(grad_out, "grad_out");
-  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2 && coords.is_contiguous(), "corr_lookup_bwd: coords [B,2,h,w] contiguous");
+  const char* op = "corr_lookup_bwd";
   TORCH_CHECK(grad_levels.size() >= 1 && grad_levels.size() <= PFK_MAX_LEVELS && lvl_h.size() == grad_levels.size() &&
               lvl_w.size() == grad_levels.size(), "corr_lookup_bwd: 1..8 levels with their map sizes");
   pfk_lookup_bwd_desc d{};
+  d.coords = dense(op, coords, "coords", F32).f32();
+  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2, "corr_lookup_bwd: coords [B,2,h,w] contiguous");
   d.B = coords.size(0); d.h = coords.size(2); d.w = coords.size(3);
   const int64_t M = (int64_t)d.B * d.h * d.w;
   for (size_t l = 0; l < grad_levels.size(); ++l) {
-    const Tensor& v = grad_levels[l];
-    check_pm(v, "grad_level");
-    TORCH_CHECK(v.size(0) == M && v.size(1) >= lvl_h[l] * lvl_w[l], "corr_lookup_bwd: grad level must be [B*N, >= h_l*w_l]");
-    d.grad_levels[l] = fptr(v); d.lvl_h[l] = lvl_h[l]; d.lvl_w[l] = lvl_w[l]; d.lvl_ld[l] = v.stride(0);
+    const Rows v = rows(op, grad_levels[l], "grad_level", F32).expect(M, AtLeast{lvl_h[l] * lvl_w[l]});
+    d.grad_levels[l] = v.f32(); d.lvl_h[l] = lvl_h[l]; d.lvl_w[l] = lvl_w[l]; d.lvl_ld[l] = v.ld;
   }
   d.num_levels = grad_levels.size(); d.radius = radius;
-  d.coords = fptr(coords); d.grad_out = fptr(grad_out); d.grad_out_ld = grad_out.stride(0);
   const int n = 2 * radius + 1;
-  TORCH_CHECK(grad_out.size(0) == M && grad_out.size(1) >= d.num_levels * n * n, "corr_lookup_bwd: grad_out shape");
-  check_ok(pfk_corr_lookup_bwd_f32(&d, cur_stream()), "corr_lookup_bwd");
+  const Rows g = rows(op, grad_out, "grad_out", F32).expect(M, AtLeast{(int64_t)d.num_levels * n * n});
+  d.grad_out = g.f32(); d.grad_out_ld = g.ld;
+  check_ok(pfk_corr_lookup_bwd_f32(&d, cur_stream()), op);
 }
 
 // backward of corr_volume for one pyramid level, all batch elements: dC [B,N1,ldc] (columns >= N2 zero), f1 [B,N1,D],
@@ -815,91 +630,89 @@ void corr_lookup_bwd(at::TensorList grad_levels, at::IntArrayRef lvl_h, at::IntA
 void corr_volume_bwd(const Tensor& dC, int64_t N2, const Tensor& f1, const Tensor& f2cm, double scale, Tensor df1, bool accumulate,
                      Tensor df2) {
   OpScope scope(dC);
-  check_dev_f32(dC, "dC"); check_dev_f32(f1, "f1"); check_dev_f32(f2cm, "f2cm"); check_dev_f32(df1, "df1"); check_dev_f32(df2, "df2");
+  const char* op = "corr_volume_bwd";
+  const float* dc = dense(op, dC, "dC", F32).f32();
+  const float* a = dense(op, f1, "f1", F32).f32();
+  const float* b = dense(op, f2cm, "f2cm", F32).f32();
+  float* da = dense(op, df1, "df1", F32).f32();
+  float* db = dense(op, df2, "df2", F32).f32();
   TORCH_CHECK(dC.dim() == 3 && f1.dim() == 3 && f2cm.dim() == 3 && df1.dim() == 3 && df2.dim() == 3, "corr_volume_bwd: 3-D tensors");
-  TORCH_CHECK(dC.is_contiguous() && f1.is_contiguous() && f2cm.is_contiguous() && df1.is_contiguous() && df2.is_contiguous(),
-              "corr_volume_bwd: contiguous tensors");
   const int B = dC.size(0), N1 = dC.size(1), ldc = dC.size(2), D = f1.size(2), ld2cm = f2cm.size(2);
   TORCH_CHECK(f1.size(0) == B && f1.size(1) == N1 && f2cm.size(0) == B && f2cm.size(1) == D && df1.sizes() == f1.sizes() &&
               df2.size(0) == B && df2.size(1) == ldc && df2.size(2) == (D + 31) / 32 * 32, "corr_volume_bwd: shape mismatch");
   const long long need = pfk_corr_volume_bwd_workspace_bytes(N1, ldc, D);
-  Tensor ws;
-  void* wsp = nullptr;
-  if (need > 0) { ws = at::empty({(int64_t)need}, dC.options().dtype(at::kByte)); wsp = ws.data_ptr(); }
-  for (int b = 0; b < B; ++b)
-    check_ok(pfk_corr_volume_bwd_f32(fptr(dC) + (int64_t)b * N1 * ldc, ldc, N1, (int)N2, fptr(f1) + (int64_t)b * N1 * D, D,
-                                     fptr(f2cm) + (int64_t)b * D * ld2cm, ld2cm, D, (float)scale, fptr(df1) + (int64_t)b * N1 * D, D,
-                                     accumulate, fptr(df2) + (int64_t)b * ldc * df2.size(2), wsp, need, cur_stream()),
-             "corr_volume_bwd");
+  const auto ws = byte_workspace(need, dC);
+  for (int i = 0; i < B; ++i)
+    check_ok(pfk_corr_volume_bwd_f32(dc + (int64_t)i * N1 * ldc, ldc, N1, (int)N2, a + (int64_t)i * N1 * D, D,
+                                     b + (int64_t)i * D * ld2cm, ld2cm, D, (float)scale, da + (int64_t)i * N1 * D, D,
+                                     accumulate, db + (int64_t)i * ldc * df2.size(2), ws.second, need, cur_stream()),
+             op);
 }
 
 // backward of convex_upsample(_pm): flow NCHW [B,2,H,W] or pixel-major [M, >=2]
 void convex_upsample_bwd(const Tensor& flow, const Tensor& mask, const Tensor& grad_out, Tensor grad_mask, Tensor grad_flow) {
   OpScope scope(mask);
-  check_dev_f32(flow, "flow"); check_pm(mask, "mask"); check_dev_f32(grad_out, "grad_out"); check_pm(grad_mask, "grad_mask");
-  check_dev_f32(grad_flow, "grad_flow");
-  TORCH_CHECK(grad_out.dim() == 4 && grad_out.size(1) == 2 && grad_out.is_contiguous() && grad_out.size(2) % 8 == 0 &&
-              grad_out.size(3) % 8 == 0, "convex_upsample_bwd: grad_out [B,2,8H,8W] contiguous");
-  const int B = grad_out.size(0), H = grad_out.size(2) / 8, W = grad_out.size(3) / 8;
-  const int64_t M = (int64_t)B * H * W;
-  int flow_ld = 0;
-  if (flow.dim() == 2) { check_pm(flow, "flow"); TORCH_CHECK(flow.size(0) == M && flow.size(1) >= 2); flow_ld = flow.stride(0); }
-  else TORCH_CHECK(flow.dim() == 4 && flow.is_contiguous() && flow.size(0) == B && flow.size(1) == 2 && flow.size(2) == H && flow.size(3) == W,
-                   "convex_upsample_bwd: flow [B,2,H,W] contiguous or pixel-major [M,2+]");
-  TORCH_CHECK(mask.size(0) == M && mask.size(1) == 576 && grad_mask.size(0) == M && grad_mask.size(1) == 576, "convex_upsample_bwd: mask shapes");
-  TORCH_CHECK(grad_flow.is_contiguous() && grad_flow.numel() == M * 2, "convex_upsample_bwd: grad_flow [B,2,H,W]");
-  const long long need = pfk_convex_upsample_bwd_workspace_bytes(B, H, W);
-  Tensor ws = at::empty({(int64_t)need}, mask.options().dtype(at::kByte));
-  check_ok(pfk_convex_upsample_bwd_f32(fptr(flow), flow_ld, fptr(mask), mask.stride(0), fptr(grad_out), fptr(grad_mask),
-                                       grad_mask.stride(0), fptr(grad_flow), ws.data_ptr(), need, B, H, W, cur_stream()),
-           "convex_upsample_bwd");
+  const char* op = "convex_upsample_bwd";
+  const Up8 g = up8(op, grad_out, "grad_out");
+  const int64_t M = g.rows();
+  const float* fp; int flow_ld = 0;
+  if (flow.dim() == 2) { const Rows f = rows(op, flow, "flow", F32).expect(M, AtLeast{2}); fp = f.f32(); flow_ld = f.ld; }
+  else {
+    fp = dense(op, flow, "flow", F32, 2 * M).f32();
+    TORCH_CHECK(flow.dim() == 4 && flow.size(0) == g.B && flow.size(1) == 2 && flow.size(2) == g.H && flow.size(3) == g.W,
+                "convex_upsample_bwd: flow [B,2,H,W] contiguous or pixel-major [M,2+]");
+  }
+  const Rows m = rows(op, mask, "mask", F32).expect(M, 576), gm = rows(op, grad_mask, "grad_mask", F32).expect(M, 576);
+  float* gf = dense(op, grad_flow, "grad_flow [B,2,H,W]", F32, 2 * M).f32();
+  const long long need = pfk_convex_upsample_bwd_workspace_bytes(g.B, g.H, g.W);
+  const auto ws = byte_workspace(need, mask);
+  check_ok(pfk_convex_upsample_bwd_f32(fp, flow_ld, m.f32(), m.ld, g.ptr, gm.f32(), gm.ld, gf, ws.second, need, g.B, g.H, g.W, cur_stream()), op);
 }
 
 void nchw_to_pm(const Tensor& in, Tensor out) {
   OpScope scope(in);
-  check_dev_f32(in, "in"); check_pm(out, "out");
-  TORCH_CHECK(in.dim() == 4 && in.is_contiguous());
+  const float* ip = dense("nchw_to_pm", in, "inp", F32).f32();
+  TORCH_CHECK(in.dim() == 4, "nchw_to_pm: inp must be [B,C,H,W] contiguous");
   const int B = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
-  TORCH_CHECK(out.size(0) == (int64_t)B * H * W && out.size(1) == C);
-  check_ok(pfk_nchw_to_pm_f32(fptr(in), fptr(out), out.stride(0), 0, B, C, H, W, cur_stream()), "nchw_to_pm");
+  const Rows o = rows("nchw_to_pm", out, "out", F32).expect((int64_t)B * H * W, C);
+  check_ok(pfk_nchw_to_pm_f32(ip, o.f32(), o.ld, 0, B, C, H, W, cur_stream()), "nchw_to_pm");
 }
 
 void pm_to_nchw(const Tensor& in, Tensor out) {
   OpScope scope(in);
-  check_pm(in, "in"); check_dev_f32(out, "out");
-  TORCH_CHECK(out.dim() == 4 && out.is_contiguous());
+  float* dst = dense("pm_to_nchw", out, "out", F32).f32();
+  TORCH_CHECK(out.dim() == 4, "pm_to_nchw: out must be [B,C,H,W] contiguous");
   const int B = out.size(0), C = out.size(1), H = out.size(2), W = out.size(3);
-  TORCH_CHECK(in.size(0) == (int64_t)B * H * W && in.size(1) == C);
-  check_ok(pfk_pm_to_nchw_f32(fptr(in), in.stride(0), 0, fptr(out), B, C, H, W, cur_stream()), "pm_to_nchw");
+  const Rows i = rows("pm_to_nchw", in, "inp", F32).expect((int64_t)B * H * W, C);
+  check_ok(pfk_pm_to_nchw_f32(i.f32(), i.ld, 0, dst, B, C, H, W, cur_stream()), "pm_to_nchw");
 }
 
 // in [B*N, C] pixel-major view -> out [B, C, Npad] channel-major (row stride = out.stride(1))
 void pm_to_cm(const Tensor& in, Tensor out) {
   OpScope scope(in);
-  check_pm(in, "in"); check_dev_f32(out, "out");
-  TORCH_CHECK(out.dim() == 3 && out.stride(2) == 1 && out.stride(0) == out.size(1) * out.stride(1), "pm_to_cm: out [B,C,Npad]");
+  TORCH_CHECK(out.dim() == 3 && out.size(0) >= 1 && out.stride(2) == 1 && out.stride(0) == out.size(1) * out.stride(1), "pm_to_cm: out [B,C,Npad]");
   const int B = out.size(0), C = out.size(1);
-  TORCH_CHECK(in.size(1) == C && in.size(0) % B == 0);
-  const int N = in.size(0) / B;
-  TORCH_CHECK(out.stride(1) >= N);
-  check_ok(pfk_pm_to_cm_f32(fptr(in), in.stride(0), fptr(out), out.stride(1), B, C, N, cur_stream()), "pm_to_cm");
+  const Rows i = rows("pm_to_cm", in, "inp", F32);
+  TORCH_CHECK(i.cols == C && i.rows % B == 0, "pm_to_cm: inp must be [B*N, C] for out [B,C,Npad], got [", i.rows, ", ", i.cols, "]");
+  const int N = i.rows / B;
+  const Rows o = rows("pm_to_cm", out.view({(int64_t)B * C, out.size(2)}), "out", F32).expect((int64_t)B * C, AtLeast{N});      // the B*C channel rows
+  check_ok(pfk_pm_to_cm_f32(i.f32(), i.ld, o.f32(), o.ld, B, C, N, cur_stream()), "pm_to_cm");
 }
 
 void conv_stem(const Tensor& img, const Tensor& weight, const c10::optional<Tensor>& bias, Tensor out, bool relu) {
   OpScope scope(img);
-  check_dev_f32(img, "img"); check_dev_f32(weight, "weight");
-  const bool out_b16 = check_pm_any(out, "out");
-  TORCH_CHECK(img.dim() == 4 && img.size(1) == 3 && img.is_contiguous(), "conv_stem: img [B,3,H,W] contiguous");
-  const int B = img.size(0), H = img.size(2), W = img.size(3), cout = out.size(1);
-  TORCH_CHECK(weight.is_contiguous() && weight.numel() == 49 * 3 * cout, "conv_stem: weight [49,3,cout]");
-  TORCH_CHECK(out.size(0) == (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), "conv_stem: out rows");
-  const float* b = nullptr;
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); b = fptr(*bias); }
-  if (out_b16) {
-    check_ok(pfk_conv_stem_b16(fptr(img), fptr(weight), b, out.data_ptr(), out.stride(0), B, H, W, cout, relu, cur_stream()), "conv_stem (bf16 out)");
+  const float* ip = dense("conv_stem", img, "img", F32).f32();
+  TORCH_CHECK(img.dim() == 4 && img.size(1) == 3, "conv_stem: img [B,3,H,W] contiguous");
+  const int B = img.size(0), H = img.size(2), W = img.size(3);
+  const Rows o = rows("conv_stem", out, "out", Any).expect(out_rows(B, H, W, 2), AtLeast{0});
+  const int cout = o.cols;
+  const float* wp = dense("conv_stem", weight, "weight [49,3,cout]", F32, 49 * 3 * cout).f32();
+  const float* b = dense("conv_stem", bias, "bias", F32, cout).f32();
+  if (o.b16) {
+    check_ok(pfk_conv_stem_b16(ip, wp, b, o.raw(), o.ld, B, H, W, cout, relu, cur_stream()), "conv_stem (bf16 out)");
     return;
   }
-  check_ok(pfk_conv_stem_f32(fptr(img), fptr(weight), b, fptr(out), out.stride(0), B, H, W, cout, relu, cur_stream()), "conv_stem");
+  check_ok(pfk_conv_stem_f32(ip, wp, b, o.f32(), o.ld, B, H, W, cout, relu, cur_stream()), "conv_stem");
 }
 
 // the stem for one or two 3-channel images (SEA-RAFT's ResNetFPN): img_a / img_b are [B,3,H,W] views whose three planes are dense
@@ -907,156 +720,111 @@ void conv_stem(const Tensor& img, const Tensor& weight, const c10::optional<Tens
 void conv_stem2(const Tensor& img_a, const c10::optional<Tensor>& img_b, const Tensor& weight, const c10::optional<Tensor>& bias,
                 Tensor out, bool relu) {
   OpScope scope(img_a);
-  check_dev_f32(img_a, "img_a"); check_dev_f32(weight, "weight");
-  const bool out_b16 = check_pm_any(out, "out");
-  TORCH_CHECK(img_a.dim() == 4 && img_a.size(1) == 3, "conv_stem2: img_a [B,3,H,W]");
-  const int B = img_a.size(0), H = img_a.size(2), W = img_a.size(3), cout = out.size(1);
-  auto planes = [&](const Tensor& t, const char* what) {
+  TORCH_CHECK(img_a.dim() == 4 && img_a.size(0) >= 1 && img_a.size(1) == 3, "conv_stem2: img_a [B,3,H,W]");
+  const int B = img_a.size(0), H = img_a.size(2), W = img_a.size(3);
+  // one image's three planes are a dense tensor; the batch stride goes to the kernel
+  auto planes = [&](const Tensor& t, const char* what, long long* batch_stride) {
     TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == 3 && t.size(2) == H && t.size(3) == W, "conv_stem2: ", what, " [B,3,H,W]");
     TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == W && t.stride(1) == (int64_t)H * W && (B == 1 || t.stride(0) >= (int64_t)3 * H * W),
                 "conv_stem2: ", what, " needs dense channel planes");
-    return B == 1 ? (long long)3 * H * W : (long long)t.stride(0);
+    *batch_stride = B == 1 ? (long long)3 * H * W : (long long)t.stride(0);
+    return dense("conv_stem2", t.select(0, 0), what, F32, (int64_t)3 * H * W).f32();
   };
-  const long long sa = planes(img_a, "img_a");
-  const float* pb = nullptr;
-  long long sb = 0;
-  if (img_b.has_value()) { check_dev_f32(*img_b, "img_b"); sb = planes(*img_b, "img_b"); pb = fptr(*img_b); }
+  long long sa = 0, sb = 0;
+  const float* pa = planes(img_a, "img_a", &sa);
+  const float* pb = img_b.has_value() ? planes(*img_b, "img_b", &sb) : nullptr;
   const int cin = pb ? 6 : 3;
-  TORCH_CHECK(weight.is_contiguous() && weight.numel() == (int64_t)49 * cin * cout, "conv_stem2: weight [49,cin,cout]");
-  TORCH_CHECK(out.size(0) == (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), "conv_stem2: out rows");
-  const float* b = nullptr;
-  if (bias.has_value()) { check_dev_f32(*bias, "bias"); TORCH_CHECK(bias->numel() == cout && bias->is_contiguous()); b = fptr(*bias); }
-  if (out_b16) {
-    check_ok(pfk_conv_stem2_b16(fptr(img_a), sa, pb, sb, fptr(weight), b, out.data_ptr(), out.stride(0), B, H, W, cin, cout, relu, cur_stream()),
-             "conv_stem2 (bf16 out)");
+  const Rows o = rows("conv_stem2", out, "out", Any).expect(out_rows(B, H, W, 2), AtLeast{0});
+  const int cout = o.cols;
+  const float* wp = dense("conv_stem2", weight, "weight [49,cin,cout]", F32, (int64_t)49 * cin * cout).f32();
+  const float* b = dense("conv_stem2", bias, "bias", F32, cout).f32();
+  if (o.b16) {
+    check_ok(pfk_conv_stem2_b16(pa, sa, pb, sb, wp, b, o.raw(), o.ld, B, H, W, cin, cout, relu, cur_stream()), "conv_stem2 (bf16 out)");
     return;
   }
-  check_ok(pfk_conv_stem2_f32(fptr(img_a), sa, pb, sb, fptr(weight), b, fptr(out), out.stride(0), B, H, W, cin, cout, relu, cur_stream()),
-           "conv_stem2");
+  check_ok(pfk_conv_stem2_f32(pa, sa, pb, sb, wp, b, o.f32(), o.ld, B, H, W, cin, cout, relu, cur_stream()), "conv_stem2");
 }
 
-// weight / bias gradient in PyTorch's layouts: dw [cout, sum(reals), kh, kw], db [cout] (optional); dy [B*Ho*Wo, cout4]
+// weight / bias gradient in PyTorch's layouts: dw [cout, sum(reals), kh, kw], db [cout] (optional); dy [B*Ho*Wo, cout4].
+// K12b (conv_wgrad_unpacked_b16): the same on bf16 sources and a bf16 dy (pfk_conv_wgrad_unpacked_b16), stride 1; dw / db stay fp32
+template <class Desc>
+void conv_wgrad_unpacked_impl(const char* op, at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh,
+                              int64_t kw, const Tensor& dw, const c10::optional<Tensor>& db, at::IntArrayRef reals, int64_t stride,
+                              bool accumulate) {
+  OpScope scope(dy);
+  constexpr bool b16 = std::is_same<Desc, pfk_conv_b16_desc>::value;
+  const Elem e = b16 ? B16 : F32;
+  TORCH_CHECK(stride >= 1, op, ": stride");
+  Desc d{};
+  fill_sources(d, srcs, B * H * W, e, op);
+  TORCH_CHECK(reals.size() == srcs.size(), op, ": one real count per source");
+  int real[3] = {0, 0, 0};
+  int64_t cin = 0;
+  for (size_t i = 0; i < srcs.size(); ++i) { real[i] = (int)reals[i]; cin += reals[i]; }
+  const Rows g = rows(op, dy, "dy", e).expect(out_rows(B, H, W, stride), AtLeast{0});
+  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = g.cols; d.stride = (int)stride;
+  float* dwp = dense(op, dw, "dw", F32).f32();
+  TORCH_CHECK(dw.dim() == 4 && dw.size(0) <= d.cout && dw.size(1) == cin && dw.size(2) == kh && dw.size(3) == kw,
+              op, ": dw [cout, sum(reals), kh, kw] contiguous");
+  float* dbp = dense(op, db, "db [cout]", F32, dw.size(0)).f32();
+  if constexpr (b16) {
+    for (int i = 0; i < d.num_src; ++i)
+      TORCH_CHECK(d.src[i].channels % 8 == 0 && d.src[i].ld % 8 == 0, op, ": src channels and row stride must be multiples of 8");
+    TORCH_CHECK(g.cols % 8 == 0 && g.ld % 8 == 0, op, ": dy channels and row stride must be multiples of 8");
+    const long long need = pfk_conv_wgrad_unpacked_b16_workspace_bytes(&d, dbp != nullptr);
+    TORCH_CHECK(need > 0, op, ": unsupported shape (stride 1; 1x1, 3x3, 1x5, 5x1)");
+    const auto ws = byte_workspace(need, dy);
+    check_ok(pfk_conv_wgrad_unpacked_b16(&d, real, g.raw(), g.ld, (int)dw.size(0), dwp, dbp, accumulate ? 1 : 0, ws.second, need, cur_stream()), op);
+  } else {
+    const long long need = pfk_conv_wgrad_unpacked_workspace_bytes(&d, dbp != nullptr);
+    const auto ws = byte_workspace(need, dy);
+    check_ok(pfk_conv_wgrad_unpacked_f32(&d, real, g.f32(), g.ld, (int)dw.size(0), dwp, dbp, accumulate ? 1 : 0, ws.second, need, cur_stream()), op);
+  }
+}
 void conv_wgrad_unpacked(at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, Tensor dw,
                          const c10::optional<Tensor>& db, at::IntArrayRef reals, int64_t stride, bool accumulate) {
-  OpScope scope(dy);
-  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3 && reals.size() == srcs.size(), "conv_wgrad_unpacked: 1..3 sources, one real count each");
-  check_pm(dy, "dy"); check_dev_f32(dw, "dw");
-  pfk_conv_desc d{};
-  const int64_t M = B * H * W;
-  int real[3] = {0, 0, 0};
-  int64_t cin = 0;
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    check_pm(srcs[i], "src");
-    TORCH_CHECK(srcs[i].size(0) == M, "conv_wgrad_unpacked: src rows != B*H*W");
-    d.src[i].ptr = fptr(srcs[i]); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
-    real[i] = (int)reals[i];
-    cin += reals[i];
-  }
-  d.num_src = srcs.size();
-  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = dy.size(1);
-  TORCH_CHECK(stride >= 1, "conv_wgrad_unpacked: stride");
-  d.stride = (int)stride;
-  TORCH_CHECK(dy.size(0) == B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1), "conv_wgrad_unpacked: dy rows != B*Ho*Wo");
-  TORCH_CHECK(dw.is_contiguous() && dw.dim() == 4 && dw.size(0) <= d.cout && dw.size(1) == cin && dw.size(2) == kh && dw.size(3) == kw,
-              "conv_wgrad_unpacked: dw [cout, sum(reals), kh, kw] contiguous");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_dev_f32(*db, "db");
-    TORCH_CHECK(db->is_contiguous() && db->numel() == dw.size(0), "conv_wgrad_unpacked: db [cout]");
-    dbp = fptr(*db);
-  }
-  const long long need = pfk_conv_wgrad_unpacked_workspace_bytes(&d, dbp != nullptr);
-  Tensor ws = at::empty({(int64_t)need}, dy.options().dtype(at::kByte));
-  check_ok(pfk_conv_wgrad_unpacked_f32(&d, real, fptr(dy), dy.stride(0), (int)dw.size(0), fptr(dw), dbp, accumulate ? 1 : 0,
-                                       ws.data_ptr(), need, cur_stream()), "conv_wgrad_unpacked");
+  conv_wgrad_unpacked_impl<pfk_conv_desc>("conv_wgrad_unpacked", srcs, dy, B, H, W, kh, kw, dw, db, reals, stride, accumulate);
 }
-
-// K12b: the same on bf16 sources and a bf16 dy (pfk_conv_wgrad_unpacked_b16); dw / db stay fp32
 void conv_wgrad_unpacked_b16(at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, Tensor dw,
                              const c10::optional<Tensor>& db, at::IntArrayRef reals, bool accumulate) {
-  OpScope scope(dy);
-  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3 && reals.size() == srcs.size(), "conv_wgrad_unpacked_b16: 1..3 sources, one real count each");
-  check_pm_b16(dy, "dy"); check_dev_f32(dw, "dw");
-  pfk_conv_b16_desc d{};
-  const int64_t M = B * H * W;
-  int real[3] = {0, 0, 0};
-  int64_t cin = 0;
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    check_pm_b16(srcs[i], "src");
-    TORCH_CHECK(srcs[i].size(0) == M, "conv_wgrad_unpacked_b16: src rows != B*H*W");
-    TORCH_CHECK(srcs[i].size(1) % 8 == 0 && srcs[i].stride(0) % 8 == 0, "conv_wgrad_unpacked_b16: src channels and row stride must be multiples of 8");
-    d.src[i].ptr = srcs[i].data_ptr(); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
-    real[i] = (int)reals[i];
-    cin += reals[i];
-  }
-  d.num_src = srcs.size();
-  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = dy.size(1); d.stride = 1;
-  TORCH_CHECK(dy.size(0) == M, "conv_wgrad_unpacked_b16: dy rows != B*H*W");
-  TORCH_CHECK(dy.size(1) % 8 == 0 && dy.stride(0) % 8 == 0, "conv_wgrad_unpacked_b16: dy channels and row stride must be multiples of 8");
-  TORCH_CHECK(dw.is_contiguous() && dw.dim() == 4 && dw.size(0) <= d.cout && dw.size(1) == cin && dw.size(2) == kh && dw.size(3) == kw,
-              "conv_wgrad_unpacked_b16: dw [cout, sum(reals), kh, kw] contiguous");
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    check_dev_f32(*db, "db");
-    TORCH_CHECK(db->is_contiguous() && db->numel() == dw.size(0), "conv_wgrad_unpacked_b16: db [cout]");
-    dbp = fptr(*db);
-  }
-  const long long need = pfk_conv_wgrad_unpacked_b16_workspace_bytes(&d, dbp != nullptr);
-  TORCH_CHECK(need > 0, "conv_wgrad_unpacked_b16: unsupported shape (stride 1; 1x1, 3x3, 1x5, 5x1)");
-  Tensor ws = at::empty({(int64_t)need}, dy.options().dtype(at::kByte));
-  check_ok(pfk_conv_wgrad_unpacked_b16(&d, real, dy.data_ptr(), dy.stride(0), (int)dw.size(0), fptr(dw), dbp, accumulate ? 1 : 0,
-                                       ws.data_ptr(), need, cur_stream()), "conv_wgrad_unpacked_b16");
+  conv_wgrad_unpacked_impl<pfk_conv_b16_desc>("conv_wgrad_unpacked_b16", srcs, dy, B, H, W, kh, kw, dw, db, reals, 1, accumulate);
 }
 
 int64_t instnorm_workspace_bytes(int64_t B, int64_t C) { return pfk_instnorm_workspace_bytes((int)B, (int)C); }
 
 void instnorm_stats(const Tensor& x, int64_t B, int64_t HW, double eps, Tensor mean, Tensor rstd, Tensor workspace) {
   OpScope scope(x);
-  const bool x_b16 = check_pm_any(x, "x");
-  check_dev_f32(mean, "mean"); check_dev_f32(rstd, "rstd");
-  const int C = x.size(1);
-  TORCH_CHECK(x.size(0) == B * HW, "instnorm_stats: rows");
-  TORCH_CHECK(mean.is_contiguous() && rstd.is_contiguous() && mean.numel() == B * C && rstd.numel() == B * C, "instnorm_stats: mean/rstd [B*C]");
-  check_dev(workspace, "workspace");
-  TORCH_CHECK(workspace.is_contiguous(), "instnorm_stats: workspace");
-  if (x_b16) {
-    check_ok(pfk_instnorm_stats_b16(x.data_ptr(), x.stride(0), (int)B, (int)HW, C, (float)eps, fptr(mean), fptr(rstd),
-                                    workspace.data_ptr(), (long long)workspace.nbytes(), cur_stream()), "instnorm_stats (bf16 rows)");
+  const Rows a = rows("instnorm_stats", x, "x", Any).expect(B * HW, AtLeast{0});
+  const int C = a.cols;
+  float* mp = dense("instnorm_stats", mean, "mean [B*C]", F32, B * C).f32();
+  float* rp = dense("instnorm_stats", rstd, "rstd [B*C]", F32, B * C).f32();
+  void* ws = dense("instnorm_stats", workspace, "workspace", Raw).raw();
+  const long long ws_bytes = workspace.nbytes();
+  if (a.b16) {
+    check_ok(pfk_instnorm_stats_b16(a.raw(), a.ld, (int)B, (int)HW, C, (float)eps, mp, rp, ws, ws_bytes, cur_stream()), "instnorm_stats (bf16 rows)");
     return;
   }
-  check_ok(pfk_instnorm_stats_f32(fptr(x), x.stride(0), (int)B, (int)HW, C, (float)eps, fptr(mean), fptr(rstd),
-                                  workspace.data_ptr(), (long long)workspace.nbytes(), cur_stream()), "instnorm_stats");
+  check_ok(pfk_instnorm_stats_f32(a.f32(), a.ld, (int)B, (int)HW, C, (float)eps, mp, rp, ws, ws_bytes, cur_stream()), "instnorm_stats");
 }
 
 void norm_apply(const Tensor& x, const Tensor& mean, const Tensor& rstd, const c10::optional<Tensor>& residual, Tensor out,
                 int64_t B, int64_t HW, bool relu, bool relu_after_residual) {
   OpScope scope(x);
-  const bool x_b16 = check_pm_any(x, "x");
-  check_dev_f32(mean, "mean"); check_dev_f32(rstd, "rstd");
-  const bool out_b16 = check_pm_any(out, "out");
-  TORCH_CHECK(out_b16 || !x_b16, "norm_apply: bf16 rows in need a bf16 output");
-  const int C = x.size(1);
-  TORCH_CHECK(x.size(0) == B * HW && out.size(0) == B * HW && out.size(1) == C, "norm_apply: shapes");
-  TORCH_CHECK(mean.numel() == B * C && rstd.numel() == B * C, "norm_apply: mean/rstd [B*C]");
-  if (out_b16) {      // the K8b encoders: bf16 residual rows (if any), bf16 output
-    const void* r16 = nullptr; int r16_ld = 0;
-    if (residual.has_value()) {
-      check_pm_b16(*residual, "residual");
-      TORCH_CHECK(residual->size(0) == B * HW && residual->size(1) == C, "norm_apply: residual shape");
-      r16 = residual->data_ptr(); r16_ld = residual->stride(0);
-    }
-    check_ok(pfk_norm_apply_b16(x.data_ptr(), x_b16 ? 1 : 0, x.stride(0), fptr(mean), fptr(rstd), r16, r16_ld, out.data_ptr(), out.stride(0), (int)B, (int)HW, C,
-                                relu, relu_after_residual, cur_stream()), "norm_apply (bf16 out)");
+  const Rows a = rows("norm_apply", x, "x", Any).expect(B * HW, AtLeast{0});
+  const int C = a.cols;
+  // the K8b encoders: bf16 rows in need a bf16 output; a bf16 output takes bf16 residual rows (if any)
+  const Rows o = rows("norm_apply", out, "out", a.b16 ? B16 : Any).expect(B * HW, C);
+  const float* mp = dense("norm_apply", mean, "mean [B*C]", F32, B * C).f32();
+  const float* rp = dense("norm_apply", rstd, "rstd [B*C]", F32, B * C).f32();
+  Rows r;
+  if (residual.has_value()) r = rows("norm_apply", *residual, "residual", o.b16 ? B16 : F32).expect(B * HW, C);
+  if (o.b16) {
+    check_ok(pfk_norm_apply_b16(a.raw(), a.b16 ? 1 : 0, a.ld, mp, rp, r.raw(), r.ld, o.raw(), o.ld, (int)B, (int)HW, C, relu, relu_after_residual,
+                                cur_stream()), "norm_apply (bf16 out)");
     return;
   }
-  const float* r = nullptr; int r_ld = 0;
-  if (residual.has_value()) {
-    check_pm(*residual, "residual");
-    TORCH_CHECK(residual->size(0) == B * HW && residual->size(1) == C, "norm_apply: residual shape");
-    r = fptr(*residual); r_ld = residual->stride(0);
-  }
-  check_ok(pfk_norm_apply_f32(fptr(x), x.stride(0), fptr(mean), fptr(rstd), r, r_ld, fptr(out), out.stride(0), (int)B, (int)HW, C,
-                              relu, relu_after_residual, cur_stream()), "norm_apply");
+  check_ok(pfk_norm_apply_f32(a.f32(), a.ld, mp, rp, r.f32(), r.ld, o.f32(), o.ld, (int)B, (int)HW, C, relu, relu_after_residual, cur_stream()),
+           "norm_apply");
 }
 
 int64_t norm_bwd_workspace_bytes(int64_t B, int64_t C) { return pfk_norm_bwd_workspace_bytes((int)B, (int)C); }
@@ -1065,145 +833,142 @@ int64_t norm_bwd_workspace_bytes(int64_t B, int64_t C) { return pfk_norm_bwd_wor
 void norm_bwd(const Tensor& x, const Tensor& dy, const Tensor& mean, const Tensor& rstd, Tensor dx, Tensor sum_g, Tensor sum_gxhat,
               int64_t B, int64_t HW, bool relu) {
   OpScope scope(x);
-  check_pm(x, "x"); check_pm(dy, "dy"); check_pm(dx, "dx"); check_dev_f32(mean, "mean"); check_dev_f32(rstd, "rstd");
-  check_dev_f32(sum_g, "sum_g"); check_dev_f32(sum_gxhat, "sum_gxhat");
-  const int C = x.size(1);
-  TORCH_CHECK(x.size(0) == B * HW && dy.size(0) == B * HW && dx.size(0) == B * HW && dy.size(1) == C && dx.size(1) == C, "norm_bwd: shapes");
-  TORCH_CHECK(mean.numel() == B * C && rstd.numel() == B * C && sum_g.numel() == B * C && sum_gxhat.numel() == B * C &&
-              mean.is_contiguous() && rstd.is_contiguous() && sum_g.is_contiguous() && sum_gxhat.is_contiguous(), "norm_bwd: [B*C] statistics");
+  const char* op = "norm_bwd";
+  const Rows a = rows(op, x, "x", F32).expect(B * HW, AtLeast{0});
+  const int C = a.cols;
+  const Rows g = rows(op, dy, "dy", F32).expect(B * HW, C), d = rows(op, dx, "dx", F32).expect(B * HW, C);
+  const float* mp = dense(op, mean, "mean [B*C]", F32, B * C).f32();
+  const float* rp = dense(op, rstd, "rstd [B*C]", F32, B * C).f32();
+  float* s1 = dense(op, sum_g, "sum_g [B*C]", F32, B * C).f32();
+  float* s2 = dense(op, sum_gxhat, "sum_gxhat [B*C]", F32, B * C).f32();
   const long long need = pfk_norm_bwd_workspace_bytes((int)B, C);
-  Tensor ws = at::empty({(int64_t)need}, x.options().dtype(at::kByte));
-  check_ok(pfk_norm_bwd_f32(fptr(x), x.stride(0), fptr(dy), dy.stride(0), fptr(mean), fptr(rstd), fptr(dx), dx.stride(0), fptr(sum_g),
-                            fptr(sum_gxhat), (int)B, (int)HW, C, relu, ws.data_ptr(), need, cur_stream()), "norm_bwd");
+  const auto ws = byte_workspace(need, x);
+  check_ok(pfk_norm_bwd_f32(a.f32(), a.ld, g.f32(), g.ld, mp, rp, d.f32(), d.ld, s1, s2, (int)B, (int)HW, C, relu, ws.second, need, cur_stream()), op);
 }
 
 // stem weight / bias gradient: img [B,3,H,W], dy pixel-major [B*Ho*Wo, cout] -> dw [49,3,cout], db [cout]
 void conv_stem_wgrad(const Tensor& img, const Tensor& dy, Tensor dw, Tensor db) {
   OpScope scope(img);
-  check_dev_f32(img, "img"); check_pm(dy, "dy"); check_dev_f32(dw, "dw"); check_dev_f32(db, "db");
-  TORCH_CHECK(img.dim() == 4 && img.size(1) == 3 && img.is_contiguous(), "conv_stem_wgrad: img [B,3,H,W] contiguous");
-  const int B = img.size(0), H = img.size(2), W = img.size(3), cout = dy.size(1);
-  TORCH_CHECK(dy.size(0) == (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), "conv_stem_wgrad: dy rows");
-  TORCH_CHECK(dw.is_contiguous() && dw.numel() == 49 * 3 * cout && db.is_contiguous() && db.numel() == cout, "conv_stem_wgrad: dw [49,3,cout], db [cout]");
+  const char* op = "conv_stem_wgrad";
+  const float* ip = dense(op, img, "img", F32).f32();
+  TORCH_CHECK(img.dim() == 4 && img.size(1) == 3, "conv_stem_wgrad: img [B,3,H,W] contiguous");
+  const int B = img.size(0), H = img.size(2), W = img.size(3);
+  const Rows g = rows(op, dy, "dy", F32).expect(out_rows(B, H, W, 2), AtLeast{0});
+  const int cout = g.cols;
+  float* dwp = dense(op, dw, "dw [49,3,cout]", F32, 49 * 3 * cout).f32();
+  float* dbp = dense(op, db, "db [cout]", F32, cout).f32();
   const long long need = pfk_conv_stem_wgrad_workspace_bytes();
-  Tensor ws = at::empty({(int64_t)need}, img.options().dtype(at::kByte));
-  check_ok(pfk_conv_stem_wgrad_f32(fptr(img), fptr(dy), dy.stride(0), fptr(dw), fptr(db), B, H, W, cout, ws.data_ptr(), need, cur_stream()),
-           "conv_stem_wgrad");
+  const auto ws = byte_workspace(need, img);
+  check_ok(pfk_conv_stem_wgrad_f32(ip, g.f32(), g.ld, dwp, dbp, B, H, W, cout, ws.second, need, cur_stream()), op);
 }
 
 void softmax_rows(Tensor x) {
   OpScope scope(x);
-  check_dev_f32(x, "x");
-  TORCH_CHECK(x.dim() >= 2 && x.is_contiguous(), "softmax_rows: contiguous [..., rows, cols]");
-  const int64_t cols = x.size(-1), rows = x.numel() / cols;
-  check_ok(pfk_softmax_rows_f32(fptr(x), rows, (int)cols, cols, cur_stream()), "softmax_rows");
+  float* p = dense("softmax_rows", x, "x", F32).f32();
+  TORCH_CHECK(x.dim() >= 2, "softmax_rows: contiguous [..., rows, cols]");
+  const int64_t cols = x.size(-1), n_rows = x.numel() / cols;
+  check_ok(pfk_softmax_rows_f32(p, n_rows, (int)cols, cols, cur_stream()), "softmax_rows");
 }
 
 // backward of softmax_rows: p, dp [rows, cols] views with contiguous columns (dp float32 or bfloat16), ds [rows, ld_out] contiguous
 // float32 (columns >= cols come out zero); ds may be the buffer dp is a view of (float32, same row stride)
 void softmax_rows_bwd(const Tensor& p, const Tensor& dp, Tensor ds) {
   OpScope scope(p);
-  check_pm(p, "p"); check_dev_f32(ds, "ds");
-  const bool b16 = check_pm_any(dp, "dp");
-  TORCH_CHECK(ds.dim() == 2 && ds.is_contiguous(), "softmax_rows_bwd: ds must be contiguous [rows, ld_out]");
-  const int64_t rows = p.size(0), cols = p.size(1);
-  TORCH_CHECK(rows > 0 && cols > 0 && dp.size(0) == rows && dp.size(1) == cols && ds.size(0) == rows && ds.size(1) >= cols,
-              "softmax_rows_bwd: p, dp [rows, cols], ds [rows, ld_out >= cols]");
-  if (b16) check_ok(pfk_softmax_rows_bwd_bf16(fptr(p), p.stride(0), dp.data_ptr(), dp.stride(0), fptr(ds), ds.size(1), rows, (int)cols, cur_stream()),
-                    "softmax_rows_bwd (bf16)");
-  else check_ok(pfk_softmax_rows_bwd_f32(fptr(p), p.stride(0), fptr(dp), dp.stride(0), fptr(ds), ds.size(1), rows, (int)cols, cur_stream()),
-                "softmax_rows_bwd");
+  const char* op = "softmax_rows_bwd";
+  const Rows a = rows(op, p, "p", F32);
+  TORCH_CHECK(a.rows > 0 && a.cols > 0, "softmax_rows_bwd: p must not be empty");
+  const Rows g = rows(op, dp, "dp", Any).expect(a.rows, a.cols), s = rows(op, ds, "ds", F32).expect(a.rows, AtLeast{a.cols});
+  TORCH_CHECK(ds.is_contiguous(), "softmax_rows_bwd: ds must be contiguous [rows, ld_out]");
+  if (g.b16) check_ok(pfk_softmax_rows_bwd_bf16(a.f32(), a.ld, g.raw(), g.ld, s.f32(), s.cols, a.rows, (int)a.cols, cur_stream()),
+                      "softmax_rows_bwd (bf16)");
+  else check_ok(pfk_softmax_rows_bwd_f32(a.f32(), a.ld, g.f32(), g.ld, s.f32(), s.cols, a.rows, (int)a.cols, cur_stream()), op);
 }
 
 // inp [B, N, N] float32 (row stride inp.stride(1), batches N rows apart) -> outT [B, N, ld_out] = its transpose, out (optional, same
 // shape) = its copy; float32 or bfloat16, contiguous, pad columns zero
 void transpose_pack(const Tensor& inp, Tensor outT, const c10::optional<Tensor>& out) {
   OpScope scope(inp);
-  check_dev_f32(inp, "inp"); check_dev(outT, "outT");
+  const char* op = "transpose_pack";
   TORCH_CHECK(inp.dim() == 3 && inp.size(1) == inp.size(2) && inp.stride(2) == 1 && inp.stride(0) == inp.size(1) * inp.stride(1),
               "transpose_pack: inp [B, N, N] with contiguous columns and batches N rows apart");
   const int64_t B = inp.size(0), N = inp.size(1);
-  const bool b16 = outT.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(b16 || outT.scalar_type() == at::kFloat, "transpose_pack: outT must be float32 or bfloat16");
-  TORCH_CHECK(outT.dim() == 3 && outT.is_contiguous() && outT.size(0) == B && outT.size(1) == N && outT.size(2) >= N,
-              "transpose_pack: outT [B, N, ld_out >= N] contiguous");
-  void* o = nullptr;
-  if (out.has_value()) {
-    check_dev(*out, "out");
-    TORCH_CHECK(out->scalar_type() == outT.scalar_type() && out->is_contiguous() && out->sizes() == outT.sizes(),
-                "transpose_pack: out must match outT");
-    o = out->data_ptr();
-  }
-  if (b16) check_ok(pfk_transpose_pack_b16(fptr(inp), inp.stride(1), outT.data_ptr(), o, outT.size(2), (int)B, (int)N, cur_stream()),
-                    "transpose_pack (bf16)");
-  else check_ok(pfk_transpose_pack_f32(fptr(inp), inp.stride(1), fptr(outT), static_cast<float*>(o), outT.size(2), (int)B, (int)N, cur_stream()),
-                "transpose_pack");
+  const Rows i = rows(op, inp.view({B * N, N}), "inp", F32).expect(B * N, N);      // the B*N rows
+  const Ptr t = dense(op, outT, "outT", Any);
+  TORCH_CHECK(outT.dim() == 3 && outT.size(0) == B && outT.size(1) == N && outT.size(2) >= N, "transpose_pack: outT [B, N, ld_out >= N] contiguous");
+  const Ptr o = dense(op, out, "out", t.b16 ? B16 : F32, outT.numel());
+  TORCH_CHECK(!out.has_value() || out->sizes() == outT.sizes(), "transpose_pack: out must match outT");
+  if (t.b16) check_ok(pfk_transpose_pack_b16(i.f32(), i.ld, t.raw(), o.raw(), outT.size(2), (int)B, (int)N, cur_stream()), "transpose_pack (bf16)");
+  else check_ok(pfk_transpose_pack_f32(i.f32(), i.ld, t.f32(), o.f32(), outT.size(2), (int)B, (int)N, cur_stream()), op);
 }
 
 void forward_interpolate(const Tensor& flow, Tensor out) {
   OpScope scope(flow);
-  check_dev_f32(flow, "flow"); check_dev_f32(out, "out");
-  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2 && flow.is_contiguous() && out.is_contiguous() && out.sizes() == flow.sizes(),
-              "forward_interpolate: flow/out [B,2,H,W] contiguous");
-  check_ok(pfk_forward_interpolate_f32(fptr(flow), fptr(out), flow.size(0), flow.size(2), flow.size(3), cur_stream()), "forward_interpolate");
+  const float* fp = dense("forward_interpolate", flow, "flow", F32).f32();
+  float* dst = dense("forward_interpolate", out, "out", F32, flow.numel()).f32();
+  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2 && out.sizes() == flow.sizes(), "forward_interpolate: flow/out [B,2,H,W] contiguous");
+  check_ok(pfk_forward_interpolate_f32(fp, dst, flow.size(0), flow.size(2), flow.size(3), cur_stream()), "forward_interpolate");
 }
 
 // weight gradient in the packed [cout, ktot] layout; dy [M, cout] (cout % 4 == 0)
 void conv_wgrad(at::TensorList srcs, const Tensor& dy, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, Tensor out,
                 bool with_bias, int64_t stride) {
   OpScope scope(dy);
-  TORCH_CHECK(srcs.size() >= 1 && srcs.size() <= 3, "conv_wgrad: 1..3 sources");
-  check_pm(dy, "dy"); check_dev_f32(out, "out");
-  pfk_conv_desc d{};
-  const int64_t M = B * H * W;
-  for (size_t i = 0; i < srcs.size(); ++i) {
-    check_pm(srcs[i], "src");
-    TORCH_CHECK(srcs[i].size(0) == M, "conv_wgrad: src rows != B*H*W");
-    d.src[i].ptr = fptr(srcs[i]); d.src[i].ld = srcs[i].stride(0); d.src[i].channels = srcs[i].size(1);
-  }
-  d.num_src = srcs.size();
-  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = dy.size(1);
   TORCH_CHECK(stride >= 1, "conv_wgrad: stride");
-  d.stride = (int)stride;
-  TORCH_CHECK(dy.size(0) == B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1), "conv_wgrad: dy rows != B*Ho*Wo");
-  TORCH_CHECK(out.is_contiguous() && out.dim() == 2 && out.size(0) == d.cout && out.size(1) == pfk_conv_ktot(&d) + (with_bias ? 32 : 0),
+  pfk_conv_desc d{};
+  fill_sources(d, srcs, B * H * W, F32, "conv_wgrad");
+  const Rows g = rows("conv_wgrad", dy, "dy", F32).expect(out_rows(B, H, W, stride), AtLeast{0});
+  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.cout = g.cols; d.stride = (int)stride;
+  float* dst = dense("conv_wgrad", out, "out", F32).f32();
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == d.cout && out.size(1) == pfk_conv_ktot(&d) + (with_bias ? 32 : 0),
               "conv_wgrad: out [cout, ktot (+32 with the bias column)]");
   const long long need = pfk_conv_wgrad_workspace_bytes(&d, with_bias);
-  Tensor ws;
-  void* wsp = nullptr;
-  if (need > 0) { ws = at::empty({(int64_t)need}, dy.options().dtype(at::kByte)); wsp = ws.data_ptr(); }
-  check_ok(pfk_conv_wgrad_f32(&d, fptr(dy), dy.stride(0), fptr(out), with_bias, wsp, need, cur_stream()), "conv_wgrad");
+  const auto ws = byte_workspace(need, dy);
+  check_ok(pfk_conv_wgrad_f32(&d, g.f32(), g.ld, dst, with_bias, ws.second, need, cur_stream()), "conv_wgrad");
 }
 
+// The GRU gate kernels (include/pfk.h): h / dh_new are [M, C] row views; every other tensor is dense fp32 with M*C elements
+// (a_zr / da_zr: [M, 2C]), possibly the head of a longer buffer
 void gru_gates_zr(const Tensor& a_zr, const Tensor& h, Tensor z, Tensor r, Tensor rh) {
   OpScope scope(h);
-  check_pm(h, "h"); check_dev_f32(a_zr, "a_zr");
-  const int64_t M = h.size(0); const int C = h.size(1);
-  TORCH_CHECK(a_zr.is_contiguous() && a_zr.size(0) == M && a_zr.size(1) == 2 * C && z.is_contiguous() && r.is_contiguous() && rh.is_contiguous());
-  check_ok(pfk_gru_gates_zr_f32(fptr(a_zr), fptr(h), h.stride(0), fptr(z), fptr(r), fptr(rh), M, C, cur_stream()), "gru_gates_zr");
+  const char* op = "gru_gates_zr";
+  const Rows hv = rows(op, h, "h", F32);
+  const int64_t M = hv.rows, C = hv.cols;
+  const float* a = dense(op, a_zr, "a_zr", F32, AtLeast{M * 2 * C}).f32();
+  TORCH_CHECK(a_zr.dim() == 2 && a_zr.size(0) == M && a_zr.size(1) == 2 * C, "gru_gates_zr: a_zr must be [M, 2C] for h [M, C]");
+  check_ok(pfk_gru_gates_zr_f32(a, hv.f32(), hv.ld, dense(op, z, "z", F32, AtLeast{M * C}).f32(), dense(op, r, "r", F32, AtLeast{M * C}).f32(),
+                                dense(op, rh, "rh", F32, AtLeast{M * C}).f32(), M, (int)C, cur_stream()), op);
 }
 void gru_gates_q(const Tensor& a_q, const Tensor& z, const Tensor& h, Tensor q, Tensor h_new) {
   OpScope scope(h);
-  check_pm(h, "h");
-  const int64_t M = h.size(0); const int C = h.size(1);
-  TORCH_CHECK(a_q.is_contiguous() && a_q.size(0) == M && a_q.size(1) == C && z.is_contiguous() && q.is_contiguous() && h_new.is_contiguous());
-  check_ok(pfk_gru_gates_q_f32(fptr(a_q), fptr(z), fptr(h), h.stride(0), fptr(q), fptr(h_new), M, C, cur_stream()), "gru_gates_q");
+  const char* op = "gru_gates_q";
+  const Rows hv = rows(op, h, "h", F32);
+  const int64_t M = hv.rows, C = hv.cols;
+  const float* a = dense(op, a_q, "a_q", F32, AtLeast{M * C}).f32();
+  TORCH_CHECK(a_q.dim() == 2 && a_q.size(0) == M && a_q.size(1) == C, "gru_gates_q: a_q must be [M, C] like h");
+  check_ok(pfk_gru_gates_q_f32(a, dense(op, z, "z", F32, AtLeast{M * C}).f32(), hv.f32(), hv.ld, dense(op, q, "q", F32, AtLeast{M * C}).f32(),
+                               dense(op, h_new, "h_new", F32, AtLeast{M * C}).f32(), M, (int)C, cur_stream()), op);
 }
 void gru_backward_q(const Tensor& dh_new, const Tensor& z, const Tensor& q, const Tensor& h, Tensor da_q, Tensor da_zr, Tensor dh) {
   OpScope scope(h);
-  check_pm(h, "h"); check_pm(dh_new, "dh_new");
-  const int64_t M = h.size(0); const int C = h.size(1);
-  TORCH_CHECK(z.is_contiguous() && q.is_contiguous() && da_q.is_contiguous() && da_zr.is_contiguous() && dh.is_contiguous() &&
-              da_zr.size(1) == 2 * C && dh_new.size(1) == C);
-  check_ok(pfk_gru_backward_q_f32(fptr(dh_new), dh_new.stride(0), fptr(z), fptr(q), fptr(h), h.stride(0), fptr(da_q), fptr(da_zr),
-                                  fptr(dh), M, C, cur_stream()), "gru_backward_q");
+  const char* op = "gru_backward_q";
+  const Rows hv = rows(op, h, "h", F32);
+  const int64_t M = hv.rows, C = hv.cols;
+  const Rows g = rows(op, dh_new, "dh_new", F32).expect(M, C);
+  float* dzr = dense(op, da_zr, "da_zr", F32, AtLeast{M * 2 * C}).f32();
+  TORCH_CHECK(da_zr.dim() == 2 && da_zr.size(1) == 2 * C, "gru_backward_q: da_zr must be [M, 2C] for h [M, C]");
+  check_ok(pfk_gru_backward_q_f32(g.f32(), g.ld, dense(op, z, "z", F32, AtLeast{M * C}).f32(), dense(op, q, "q", F32, AtLeast{M * C}).f32(),
+                                  hv.f32(), hv.ld, dense(op, da_q, "da_q", F32, AtLeast{M * C}).f32(), dzr,
+                                  dense(op, dh, "dh", F32, AtLeast{M * C}).f32(), M, (int)C, cur_stream()), op);
 }
 void gru_backward_zr(const Tensor& d_rh, const Tensor& h, const Tensor& r, Tensor da_zr, Tensor dh) {
   OpScope scope(h);
-  check_pm(h, "h");
-  const int64_t M = h.size(0); const int C = h.size(1);
-  TORCH_CHECK(d_rh.is_contiguous() && r.is_contiguous() && da_zr.is_contiguous() && dh.is_contiguous() && da_zr.size(1) == 2 * C);
-  check_ok(pfk_gru_backward_zr_f32(fptr(d_rh), fptr(h), h.stride(0), fptr(r), fptr(da_zr), fptr(dh), M, C, cur_stream()), "gru_backward_zr");
+  const char* op = "gru_backward_zr";
+  const Rows hv = rows(op, h, "h", F32);
+  const int64_t M = hv.rows, C = hv.cols;
+  float* dzr = dense(op, da_zr, "da_zr", F32, AtLeast{M * 2 * C}).f32();
+  TORCH_CHECK(da_zr.dim() == 2 && da_zr.size(1) == 2 * C, "gru_backward_zr: da_zr must be [M, 2C] for h [M, C]");
+  check_ok(pfk_gru_backward_zr_f32(dense(op, d_rh, "d_rh", F32, AtLeast{M * C}).f32(), hv.f32(), hv.ld, dense(op, r, "r", F32, AtLeast{M * C}).f32(),
+                                   dzr, dense(op, dh, "dh", F32, AtLeast{M * C}).f32(), M, (int)C, cur_stream()), op);
 }
 
 int64_t abi_version() { return pfk_abi_version(); }

@@ -65,6 +65,17 @@ def test_product_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle", txt, flags=re.M), f"{f} imports the oracle"
 
 
+def test_binding_unwraps_tensors_in_one_place():
+    """pfk_torch.cpp takes every pointer from the checked views of pfk_torch_views.h, and every op it declares without a
+    function has an implementation registered."""
+    txt = open(os.path.join(ROOT, "ptlflow_amd", "csrc", "pfk_torch.cpp")).read()
+    assert "data_ptr" not in txt and "fptr(" not in txt, "pfk_torch.cpp unwraps a tensor itself"
+    defs = txt[txt.index("TORCH_LIBRARY(pfk, m)"): txt.index("TORCH_LIBRARY_IMPL(pfk")]
+    declared = {re.match(r'\s*m\.def\("(\w+)\(', s).group(1) for s in defs.split(";") if "m.def(" in s and "&" not in s}
+    implemented = set(re.findall(r'm\.impl\("(\w+)"', txt))
+    assert declared and declared <= implemented, f"declared without an implementation: {sorted(declared - implemented)}"
+
+
 def test_product_never_touches_the_staged_reference():
     """oracle/_ref (the reference staged for the GPU box) is test infrastructure like the rest of oracle/."""
     pkg = os.path.join(ROOT, "ptlflow_amd")
