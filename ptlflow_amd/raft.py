@@ -18,7 +18,7 @@ On a machine that *has* ptlflow, use `ptlflow_amd.patch.accelerate(model)` on th
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 from . import load_native
 from .corr import AlternateCorrBlock, CorrBlock
-from .update import UpdateEngine, UpdateSpec, basic_spec, gma_spec, small_spec
+from .update import SMALL_GRID_PIXELS, UpdateEngine, UpdateSpec, basic_spec, gma_spec, small_spec
 from .synth import synth_state_dict, update_block_shapes
 
 
@@ -119,6 +119,26 @@ def _param_tree(shapes: Dict[str, tuple]) -> nn.Module:
 
 
 # ----------------------------------------------------------------------------- model
+def loop_schedule(*, pixels: int, has_mask: bool, aggregate: bool, alternate_corr: bool, can_fuse: bool, b16: bool, can_group: bool,
+                  capturing: bool, fork_branches: Optional[bool], fuse_mask_upsample: Optional[bool], overlap_mask_head: bool,
+                  group_launches: Optional[bool]) -> Tuple[str, bool]:
+    """The one rule that picks `RAFT._iterate`'s schedule, from plain values: (which `RAFT._iterate_<loop>` runs — "forked", "side",
+    "grouped" or "serial" —, whether the mask tail is the fused `UpdateEngine.mask_upsample`).  `can_fuse`, `b16`, `can_group` are the
+    engine's, `pixels` = B*H*W (the measured reasons: `SMALL_GRID_PIXELS`), the last four the user attributes (None: the default)."""
+    big = pixels >= SMALL_GRID_PIXELS
+    fork = fork_branches if fork_branches is not None else capturing
+    if fork and not aggregate and not alternate_corr:
+        return "forked", False
+    fuse = has_mask and can_fuse and (fuse_mask_upsample if fuse_mask_upsample is not None else big)
+    # (not with the fused K13b: 55 us of mostly matrix / VALU work per iteration — on the main stream it measured 26.44 ms per
+    #  batch-8 forward against 26.76 on the side stream, where it competes with the HBM-bound bf16 launches beside it)
+    if has_mask and overlap_mask_head and big and not capturing and not (fuse and b16):
+        return "side", fuse
+    if not fuse and can_group and not alternate_corr and (group_launches if group_launches is not None else not big):
+        return "grouped", False
+    return "serial", fuse
+
+
 class RAFT(nn.Module):
     def __init__(self, corr_levels: int = 4, corr_radius: Optional[int] = None, iters: int = 32, small: bool = False,
                  upsample_every_iter: bool = True, conv_precision: str = "fp32", native_encoders: bool = True,
@@ -133,23 +153,16 @@ class RAFT(nn.Module):
         # (`conv_precision` below is about inference only.)
         from .train import check_precision
         self.train_precision = check_precision(train_precision, "train_precision")
-        # The mask head's second convolution, the softmax over its nine taps and the convex upsampling (raft/update.py:152,
-        # raft/raft.py:112-123) as ONE kernel that never writes the [M, 576] mask (`pfk_mask_upsample_f32`); bit-identical
-        # to the two separate launches.  None: where it pays — fp32 convolutions from 28 160 pixels up (batch 8: 196 us against
-        # 173 + 41 for the pair, 254 MB less HBM traffic per iteration; at batch 1 the two forms take the same 34 us);
-        # True / False: always (where the kernel applies) / never.
+        # None: the mask tail as ONE kernel that never writes the [M, 576] mask (`UpdateEngine.mask_upsample`; bit-identical
+        # to the two launches) where it pays, from `SMALL_GRID_PIXELS` up; True / False: always (where the kernel applies) / never.
         self.fuse_mask_upsample = fuse_mask_upsample
         # True (default): the context features' part of the GRU convolutions — loop-invariant, `inp` is the same tensor in every
         # iteration (raft.py:158-160, update.py:60-71) — is computed once per forward instead of once per iteration
         # (UpdateEngine's docstring); False: the single-chain launches (A/B, tests)
         self.hoist_context = hoist_context
-        # True: the mask head's second convolution and the convex upsampling of iteration i — off the recurrent critical path:
-        # nothing of iteration i+1 reads their results — run on a second HIP stream next to iteration i+1's lookup / motion
-        # encoder / GRU, filling the idle CUs of those launches' tails (same kernels, same operands: bit-identical output).
-        # Eager loop only; the hipGraph path keeps one stream.
+        # True: the mask tail on a second HIP stream from `SMALL_GRID_PIXELS` up; eager loop only (`_iterate_side`)
         self.overlap_mask_head = overlap_mask_head
-        # None: fork the independent branches of an iteration (flow branch of the motion encoder; mask conv2 + upsampling) onto
-        # side streams only while the loop is being captured into a hipGraph; True / False: always / never (`_iterate`)
+        # None: the forked schedule (`_iterate_forked`) only while the loop is being captured into a hipGraph; True / False: always / never
         self.fork_branches = fork_branches
         self._side_streams: Dict[tuple, torch.cuda.Stream] = {}
         # True: the 32-iteration loop (lookup, update block, upsampling: ~20 launches per iteration) is captured once per
@@ -161,7 +174,7 @@ class RAFT(nn.Module):
         # inside a graph, and forked graph branches did not run concurrently (19.19 ms); eager forks on real streams gained
         # 0.3 ms only once every block was 48 KB (three per CU), which itself costs 0.5 ms.
         self.use_graph = use_graph
-        self.group_launches = None   # None: grouped launches of the motion encoder below 28 160 pixels (`_iterate`); True / False: forced
+        self.group_launches = None   # None: grouped launches of the motion encoder below `SMALL_GRID_PIXELS` (`_iterate_grouped`); True / False: forced
         self.max_graphs = 4          # recorded shapes kept (oldest dropped first): each holds its loop buffers and pyramid
         self._graphs: Dict[tuple, dict] = {}
         # True: never materialise the N x N volume, compute the lookup windows on demand (raft.py `alternate_corr`,
@@ -254,6 +267,23 @@ class RAFT(nn.Module):
         ht, wd = x.shape[-2:]
         return x[..., pads[2]: ht - pads[3], pads[0]: wd - pads[1]]
 
+    @staticmethod
+    def _coords_grid(B: int, h: int, w: int, device) -> torch.Tensor:
+        """coords_grid (raft/utils.py): [B, 2, h, w] with (x, y) of every feature pixel"""
+        ys, xs = torch.meshgrid(torch.arange(h, device=device, dtype=torch.float32),
+                                torch.arange(w, device=device, dtype=torch.float32), indexing="ij")
+        return torch.stack([xs, ys], 0)[None].repeat(B, 1, 1, 1).contiguous()
+
+    @staticmethod
+    def _warm_start(inputs, coords1: torch.Tensor) -> Optional[torch.Tensor]:
+        """warm start (raft.py:162-167): `prev_preds["flow_small"]` forward-warped on the device (no gradient into it), or None"""
+        prev = inputs.get("prev_preds")
+        if prev is None or prev.get("flow_small") is None:
+            return None
+        fwd = torch.empty_like(coords1)
+        torch.ops.pfk.forward_interpolate(prev["flow_small"].detach().to(device=coords1.device, dtype=torch.float32).contiguous(), fwd)
+        return fwd
+
     # -- forward -----------------------------------------------------------------------------------
     def forward(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         if self.training:
@@ -289,15 +319,11 @@ class RAFT(nn.Module):
         net, inp = torch.tanh(net), torch.relu(inp)
         h, w = image1.shape[-2] // 8, image1.shape[-1] // 8
         M = B * h * w
-        ys, xs = torch.meshgrid(torch.arange(h, device=x.device, dtype=torch.float32),
-                                torch.arange(w, device=x.device, dtype=torch.float32), indexing="ij")
-        coords0 = torch.stack([xs, ys], 0)[None].repeat(B, 1, 1, 1).contiguous()
+        coords0 = self._coords_grid(B, h, w, x.device)
         coords1 = coords0.clone()
-        prev = inputs.get("prev_preds")
-        if prev is not None and prev.get("flow_small") is not None:      # warm start applies in training mode too (raft.py:162-167)
-            fwd = torch.empty_like(coords1)
-            torch.ops.pfk.forward_interpolate(prev["flow_small"].detach().to(device=x.device, dtype=torch.float32).contiguous(), fwd)
-            coords1 = coords1 + fwd
+        fwd = self._warm_start(inputs, coords1)      # applies in training mode too
+        if fwd is not None:
+            coords1 = coords1 + fwd                  # (out of place; `_forward_eval` adds into its graph's fixed buffer)
         P = dict(self.update_block.named_parameters())
         cache: dict = {}
         hpm = net.permute(0, 2, 3, 1).reshape(M, self.hidden_dim)
@@ -329,7 +355,6 @@ class RAFT(nn.Module):
 
     def _forward_eval(self, inputs: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         load_native()
-        ops = torch.ops.pfk
         images = inputs["images"]
         if not images.is_cuda:
             raise RuntimeError("ptlflow_amd.RAFT needs GPU inputs (no CPU fallback)")
@@ -366,9 +391,7 @@ class RAFT(nn.Module):
             else:   # conv_precision "bf16" = BASELINE config 3's precision: bf16 operands everywhere autocast would put them
                 vt = torch.bfloat16 if self.conv_precision == "bf16" else torch.float32
                 corr_fn = CorrBlock(fm[:B], fm[B:], num_levels=self.corr_levels, radius=self.corr_radius, volume_dtype=vt)
-            ys, xs = torch.meshgrid(torch.arange(h, device=x.device, dtype=torch.float32),
-                                    torch.arange(w, device=x.device, dtype=torch.float32), indexing="ij")
-            coords0 = torch.stack([xs, ys], 0)[None].repeat(B, 1, 1, 1).contiguous()
+            coords0 = self._coords_grid(B, h, w, x.device)
             coords1 = coords0.clone()
             flow_up = torch.empty(B, 2, 8 * h, 8 * w, device=x.device, dtype=torch.float32)
         else:
@@ -382,16 +405,14 @@ class RAFT(nn.Module):
         net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
 
-        prev = inputs.get("prev_preds")
-        if prev is not None and prev.get("flow_small") is not None:      # warm start, raft.py:162-167, on the device
-            fwd = torch.empty_like(coords1)
-            ops.forward_interpolate(prev["flow_small"].to(device=x.device, dtype=torch.float32).contiguous(), fwd)
-            coords1.add_(fwd)
+        fwd = self._warm_start(inputs, coords1)
+        if fwd is not None:
+            coords1.add_(fwd)      # in place: a recorded graph reads `coords1` at this address
 
         eng.watch_faults()          # a timed-out stream-K fix-up of an earlier forward raises here (no host sync)
         eng.load_state(net, inp)
         self._after_context(eng, inp)
-        ops.flow_from_coords(coords0, coords1, eng.flow_view)
+        torch.ops.pfk.flow_from_coords(coords0, coords1, eng.flow_view)
         eng.flow_changed()
         if st is not None:
             st["graph"].replay()
@@ -421,144 +442,128 @@ class RAFT(nn.Module):
         return st
 
     def _iterate(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up):
-        """The recurrent loop of raft.py:169-187 on fixed buffers: lookup -> update block -> coordinate update -> upsampling.
+        """The recurrent loop of raft.py:169-187 on fixed buffers (lookup -> update block -> coordinate update -> upsampling into `flow_up`)
+        in one of four schedules of the SAME launches on the same operands (bit-identical results, tests/test_gpu_model.py)."""
+        loop, fused = loop_schedule(
+            pixels=eng.pixels, has_mask=self.spec.has_mask, aggregate=self.spec.aggregate, alternate_corr=self.alternate_corr,
+            can_fuse=eng.can_fuse_mask_upsample, b16=eng.b16, can_group=eng.can_group, capturing=torch.cuda.is_current_stream_capturing(),
+            fork_branches=self.fork_branches, fuse_mask_upsample=self.fuse_mask_upsample, overlap_mask_head=self.overlap_mask_head,
+            group_launches=self.group_launches)
+        if loop == "forked":
+            self._iterate_forked(corr_fn, eng, coords0, coords1, flow_up)
+        elif loop == "grouped":
+            self._iterate_grouped(corr_fn, eng, coords0, coords1, flow_up)
+        elif loop == "side":
+            self._iterate_side(corr_fn, eng, coords0, coords1, flow_up, fused)
+        else:
+            self._iterate_serial(corr_fn, eng, coords0, coords1, flow_up, fused)
+        return flow_up
 
-        Three schedules of the SAME launches on the same operands (bit-identical results, tests/test_gpu_model.py):
-        * serial — everything on the current stream;
-        * mask branch on a side stream (eager, >= 28160 pixels): mask conv2 + convex upsampling of iteration i next to iteration i+1;
-        * forked (`fork_branches`, meant for the captured hipGraph where a fork / join is a graph edge, not a host call): the
-          independent branches of one iteration run concurrently — the motion encoder's flow branch (convf1 -> convf2, reads
-          only the flow slice) next to lookup -> convc1 -> convc2; mask conv2 + upsampling next to the coordinate update and
-          the next iteration — so the 110..440-tile launches of the batch-1 regime fill each other's idle CUs
-          (update.py:104-112: `cor` and `flo` only meet in `conv`; :152: the mask head reads `net` only)."""
-        ops = torch.ops.pfk
-        has_mask = self.spec.has_mask
-        h, w = coords0.shape[-2:]
-        dev = coords0.device
-        capturing = torch.cuda.is_current_stream_capturing()
-        pixels = coords0.shape[0] * h * w
-        fork = self.fork_branches if self.fork_branches is not None else capturing
-        if fork and not self.spec.aggregate and not self.alternate_corr:
-            return self._iterate_forked(corr_fn, eng, coords0, coords1, flow_up)
-        side = None
-        # (measured, one MI355X: +0.9 % at batch 8 of 436x1024; -1.4 % at batch 1, where the loop's launches are short and the extra
-        #  events cost more than the filled tails give back: only for >= 4 x 7040 pixels)
-        fuse = has_mask and eng.can_fuse_mask_upsample and \
-            (self.fuse_mask_upsample if self.fuse_mask_upsample is not None else pixels >= 28160)
-        # (K8b with the fused K13b: 55 us of mostly matrix / VALU work per iteration — on the main stream it measured 26.44 ms per
-        #  batch-8 forward against 26.76 on the side stream, where it competes with the HBM-bound bf16 launches beside it)
-        if has_mask and self.overlap_mask_head and pixels >= 28160 and not capturing and not (fuse and eng.b16):
-            side = self._stream(dev, "mask")
-        main = torch.cuda.current_stream(dev)
-        side_done = None
-        # Small batches (below the side-stream threshold; fp32 tile kernel): convc1 | convf2 | the PREVIOUS iteration's mask conv2 as one
-        # grouped launch (`UpdateEngine.motion_grouped`), the previous iteration's upsampling right behind it — before this
-        # iteration's coordinate update overwrites the flow slice it reads.  Same launches' tiles, same bits.
-        grouped = side is None and not fuse and eng.can_group and not self.alternate_corr and \
-            (self.group_launches if self.group_launches is not None else pixels < 28160)
+    def _lookup(self, corr_fn, eng: UpdateEngine, coords1):
+        """this iteration's lookup (K8b engines take it in bf16, written directly), timed like the engine's own launches"""
+        t0 = eng.tic() if eng.profile is not None else None
+        corr_pm = corr_fn.lookup_pm(coords1, out=eng.lookup_out)
+        if t0 is not None:
+            n = 2 * self.corr_radius + 1
+            # SURVEY §8(d): N L [(2r+2)^2 + (2r+1)^2] 4 + 8 N bytes per pair and lookup (element sizes as stored: bf16 on the K8b path)
+            eng.toc(t0, "lookup", 0.0, float(eng.pixels * (self.corr_levels * ((n + 1) ** 2 * corr_fn.volume_dtype.itemsize
+                                                                              + n * n * corr_pm.element_size()) + 8)))
+        return corr_pm
+
+    def _upsample(self, eng: UpdateEngine, coords0, coords1, flow_up, fused: bool = False) -> None:
+        """This iteration's 8x flow (`flow_delta` left flow = coords1 - coords0 in the engine's hx slice): `fused`, mask conv2 + softmax +
+        convex upsampling as one kernel, no [M, 576] mask in memory; else from `eng.mask`, or raft_small's upflow8 (raft/utils.py:94-96)."""
+        if fused:
+            eng.mask_upsample(flow_up)
+        elif self.spec.has_mask:
+            torch.ops.pfk.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
+        else:
+            torch.ops.pfk.upflow8(coords0, coords1, flow_up)
+
+    def _iterate_serial(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up, fused: bool) -> None:
+        """Everything on the current stream, one launch per convolution."""
+        for it in range(self.iters):
+            do_up = it == self.iters - 1 or self.upsample_every_iter
+            eng.motion_and_gru(self._lookup(corr_fn, eng, coords1))
+            eng.heads(coords0, coords1, None, want_mask=do_up, mask_conv2=not fused)
+            if do_up:
+                self._upsample(eng, coords0, coords1, flow_up, fused)
+
+    def _iterate_grouped(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up) -> None:
+        """Small grids, fp32 tile kernel: the PREVIOUS iteration's mask conv2 rides in the motion encoder's grouped launch (`UpdateEngine.
+        motion_grouped`), its upsampling right behind it — before this iteration's coordinate update overwrites the flow slice it reads."""
         owed = False        # the previous iteration's mask conv2 + upsampling have not run yet
         for it in range(self.iters):
             last = it == self.iters - 1
-            if eng.profile is not None:     # bench.py's instrumented forward: HIP events around the lookup too (the HBM-bound kernel)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                corr_pm = corr_fn.lookup_pm(coords1, out=eng.lookup_out)
-                e1.record()
-                eng.profile.setdefault("lookup", []).append((e0, e1))
-                n = 2 * self.corr_radius + 1
-                eng.flops["lookup"] = 0.0
-                # SURVEY §8(d): N L [(2r+2)^2 + (2r+1)^2] 4 + 8 N bytes per pair and lookup
-                # (element sizes as stored: bf16 maps / bf16 rows on the K8b path)
-                eng.bytes["lookup"] = float(pixels * (self.corr_levels * ((n + 1) ** 2 * corr_fn.volume_dtype.itemsize
-                                                                        + n * n * corr_pm.element_size()) + 8))
-            else:
-                corr_pm = corr_fn.lookup_pm(coords1, out=eng.lookup_out)      # K8b engines take the lookup in bf16, written directly
             do_up = last or self.upsample_every_iter
-            if grouped:
-                eng.motion_and_gru(corr_pm, grouped=True, prev_mask=owed)
-                if owed:         # `eng.mask` = mask(it - 1) now; the flow slice still holds flow(it - 1)
-                    ops.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
-                    owed = False
-                eng.heads(coords0, coords1, None, want_mask=do_up, mask_conv2=last)
-                if do_up:
-                    if not has_mask:
-                        ops.upflow8(coords0, coords1, flow_up)
-                    elif last:
-                        ops.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
-                    else:
-                        owed = True
-                continue
-            if side is None or not do_up:
-                if fuse and do_up:
-                    eng.motion_and_gru(corr_pm)
-                    eng.heads_conv1(True)
-                    eng.flow_delta(coords0, coords1)
-                    eng.mask_upsample(flow_up)       # mask conv2 + softmax + convex upsampling, no [M, 576] mask in memory
-                    continue
-                eng.step(corr_pm, coords0, coords1, want_mask=do_up)
-                if do_up:
-                    if has_mask:   # flow = coords1 - coords0 is already in the engine's hx slice (written by flow_delta)
-                        ops.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
-                    else:          # raft_small: upflow8 (raft/utils.py:94-96)
-                        ops.upflow8(coords0, coords1, flow_up)
-                continue
-            eng.motion_and_gru(corr_pm)
+            eng.motion_and_gru(self._lookup(corr_fn, eng, coords1), grouped=True, prev_mask=owed)
+            if owed:         # `eng.mask` = mask(it - 1) now; the flow slice still holds flow(it - 1)
+                self._upsample(eng, coords0, coords1, flow_up)
+            eng.heads(coords0, coords1, None, want_mask=do_up, mask_conv2=last)
+            owed = do_up and self.spec.has_mask and not last      # this mask's conv2 rides in the next grouped launch
+            if do_up and not owed:
+                self._upsample(eng, coords0, coords1, flow_up)
+
+    def _iterate_side(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up, fused: bool) -> None:
+        """Models with a mask head, eager: mask conv2 + convex upsampling of iteration i — off the recurrent critical path — on a
+        second stream next to iteration i+1, filling the idle CUs of those launches' tails."""
+        main, side = torch.cuda.current_stream(coords0.device), self._stream(coords0.device, "mask")
+        side_done = None
+        for it in range(self.iters):
+            do_up = it == self.iters - 1 or self.upsample_every_iter
+            eng.motion_and_gru(self._lookup(corr_fn, eng, coords1))
             if side_done is not None:      # the previous iteration's mask head / upsampling still read `fm` and the flow slice
                 main.wait_event(side_done)
-            eng.heads_conv1(True)                    # fh | mask conv1 (`fm`): the mask half is consumed on the side stream
-            eng.flow_delta(coords0, coords1)         # flow head conv2 + coordinate update
-            forked = main.record_event()
-            side.wait_event(forked)
-            with torch.cuda.stream(side):
-                if fuse:
-                    eng.mask_upsample(flow_up)
-                else:
-                    eng.mask_head(side_stream=True)
-                    ops.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
-                side_done = side.record_event()
+            # fh | mask conv1 (`fm`: the mask half is consumed on the side stream), flow head conv2 + coordinate update
+            eng.heads(coords0, coords1, None, want_mask=do_up, mask_conv2=False)
+            if do_up:
+                side.wait_event(main.record_event())
+                with torch.cuda.stream(side):
+                    if not fused:
+                        eng.mask_head(side_stream=True)
+                    self._upsample(eng, coords0, coords1, flow_up, fused)
+                    side_done = side.record_event()
         if side_done is not None:
             main.wait_event(side_done)
-        return flow_up
 
-    def _iterate_forked(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up):
-        ops = torch.ops.pfk
-        has_mask = self.spec.has_mask
+    def _iterate_forked(self, corr_fn, eng: UpdateEngine, coords0, coords1, flow_up) -> None:
+        """Meant for the captured hipGraph, where a fork / join is a graph edge, not a host call: the motion encoder's flow branch (convf1
+        -> convf2, reads only the flow slice) next to lookup -> convc1 -> convc2 (update.py:104-112: `cor` and `flo` only meet in `conv`);
+        mask conv2 + upsampling (:152: reads `net` only; always the pair of launches) next to the coordinate update and the next
+        iteration — the 110..440-tile launches of the batch-1 regime fill each other's idle CUs."""
         dev = coords0.device
         main = torch.cuda.current_stream(dev)
         s_flow, s_mask = self._stream(dev, "flow"), self._stream(dev, "mask")
         mask_done = None
         for it in range(self.iters):
-            last = it == self.iters - 1
-            do_up = last or self.upsample_every_iter
+            do_up = it == self.iters - 1 or self.upsample_every_iter
             # fork: the flow branch needs the flow slice of hx (written by the previous coordinate update, on main)
             s_flow.wait_event(main.record_event())
             with torch.cuda.stream(s_flow):
                 eng.motion_flow(branch=True)
                 flow_done = s_flow.record_event()
-            corr_pm = corr_fn.lookup_pm(coords1, out=eng.lookup_out)
-            eng.motion_corr(corr_pm)
+            eng.motion_corr(self._lookup(corr_fn, eng, coords1))
             main.wait_event(flow_done)                                # join: `conv` reads both halves of corflo
             eng.motion_join()
             eng.gru()
             if mask_done is not None:      # the previous mask branch still reads the mask half of `fm` and the flow slice
                 main.wait_event(mask_done)
             eng.heads_conv1(want_mask=do_up)
-            if has_mask and do_up:
+            if self.spec.has_mask and do_up:
                 s_mask.wait_event(main.record_event())
                 with torch.cuda.stream(s_mask):
                     eng.mask_head(side_stream=True)                   # next to the coordinate update
                 eng.flow_delta(coords0, coords1)
                 s_mask.wait_event(main.record_event())                # the upsampling reads the NEW flow slice
                 with torch.cuda.stream(s_mask):
-                    ops.convex_upsample_pm(eng.flow_view, eng.mask, flow_up)
+                    self._upsample(eng, coords0, coords1, flow_up)
                     mask_done = s_mask.record_event()
             else:
                 eng.flow_delta(coords0, coords1)
-                if do_up and not has_mask:
-                    ops.upflow8(coords0, coords1, flow_up)
+                if do_up:
+                    self._upsample(eng, coords0, coords1, flow_up)      # (no mask head here: upflow8)
         if mask_done is not None:
             main.wait_event(mask_done)
-        return flow_up
 
 
 class RAFTSmall(RAFT):

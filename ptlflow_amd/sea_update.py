@@ -188,8 +188,7 @@ class SeaUpdateEngine(UpdateEngine):
 
     def update(self, corr_pm: torch.Tensor) -> None:
         """update.py:49-54: motion encoder into hx, then the ConvNeXt blocks; `flow` must already be in hx."""
-        B, H, W = self._shape
-        if self.can_group and B * H * W < 28160:
+        if self.wants_grouped_motion:
             self.motion_grouped(corr_pm)       # convc1 | convf2 as one grouped launch (same bits as motion())
         else:
             self.motion(corr_pm)

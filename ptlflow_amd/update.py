@@ -106,12 +106,20 @@ def small_spec(corr_levels: int = 4, corr_radius: int = 3) -> UpdateSpec:
 # tiles x 64 channels each; two resident per CU on 256 CUs).  In isolation at 55x128 (scripts/wino_bench.py, MI355X, the direct
 # kernel with the engine's stream-K workspace, profiles/r08_a_winograd_lds_dma.md):
 #   batch 1 (7040 px):  fm (x 8 = 56320) 89.1 -> 51.2 us;  c2 (x 3 = 21120) 70.2 -> 54.6 us;  cv (x 2 = 14080) 50.6 -> 52.6 us
-#   batch 2 (14080 px): fm 161.8 -> 95.7 us;  c2 (42240) 120.4 -> 84.6 us;  cv (28160) 88.9 -> 58.3 us
+#   batch 2 (14080 px): fm 161.8 -> 95.7 us;  c2 (42240) 120.4 -> 84.6 us;  cv (28 160) 88.9 -> 58.3 us
 #   batch 8: fm 540.2 -> 292.7 us, c2 404.6 -> 231.4 us, cv 267.1 -> 157.5 us
-# Below 28160 the grid leaves most CUs idle: cv at batch 1 ties with the direct kernel's stream-K schedule, c2 at batch 1 gains 1.29x,
+# Below 28 160 the grid leaves most CUs idle: cv at batch 1 ties with the direct kernel's stream-K schedule, c2 at batch 1 gains 1.29x,
 # but at 21120 it sits on the lower bound that the engine test keeps for this value, so the line stays above both.  The full launch's
 # cout decides (a `cout_active` launch takes the same kernel as its full form).
 WINO_MIN_WORK = 28160
+
+# The small-grid threshold in PIXELS (B*H*W; batch 4 of 436x1024's 55x128 grid) — not `WINO_MIN_WORK`, which counts pixels x column
+# tiles and merely has the same value.  Below it the update block's launches (110..990 tiles at batch 1 for 256 CUs) each pay their own
+# tail: convc1 | convf2 [| the previous mask conv2] go as ONE grouped launch (`motion_grouped`).  From it up (measured, one MI355X):
+# the mask branch on a side stream (+0.9 % at batch 8 of 436x1024; -1.4 % at batch 1, where the launches are short and the extra events
+# cost more than the filled tails give back); the fused mask tail (`mask_upsample`: batch 8 196 us against 173 + 41 for the pair, batch
+# 1 the same 34 us); the flow-head-only `fh` launch of the kernels without `cout_active` (no launch in the stream-K window there).
+SMALL_GRID_PIXELS = 28160
 
 # conv_precision -> number of bf16 planes per operand (0 = the fp32 matrix-core path, the default and the parity path)
 CONV_PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}
@@ -152,7 +160,7 @@ class UpdateEngine:
         self._shape: Optional[Tuple[int, int, int]] = None
         self._fault_host: Optional[torch.Tensor] = None
         self._fault_event = None
-        # optional per-launch instrumentation: key -> [(start_event, end_event)], and key -> algorithmic FLOPs
+        # optional per-launch instrumentation (`tic` / `toc`; {} arms it, None disarms it): key -> [(start, end) events], key -> FLOPs / bytes
         self.profile: Optional[Dict[str, list]] = None
         self.flops: Dict[str, float] = {}
         self.bytes: Dict[str, float] = {}
@@ -315,7 +323,21 @@ class UpdateEngine:
         self.workspace = torch.zeros(nws, device=dev, dtype=torch.uint8)
         self.workspace_flow = torch.zeros(nws, device=dev, dtype=torch.uint8)
         self.workspace_mask = torch.zeros(nws, device=dev, dtype=torch.uint8)
-        self._shape = (B, H, W)
+        self._shape, self.pixels = (B, H, W), M
+
+    def tic(self):
+        """A timing event recorded on the current stream: the start of a timed launch.  Called while armed only, so that an untimed launch
+        pays one test: ``t0 = self.tic() if self.profile is not None else None`` ... ``if t0 is not None: self.toc(t0, key, flops)``"""
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+
+    def toc(self, t0, key: str, flops: float, nbytes: Optional[float] = None) -> None:
+        """the end of the launch `t0` opened: one more (start, end) pair in `profile[key]`, its algorithmic `flops[key]` [and `bytes[key]`]"""
+        self.profile.setdefault(key, []).append((t0, self.tic()))
+        self.flops[key] = flops
+        if nbytes is not None:
+            self.bytes[key] = nbytes
 
     def faults(self) -> int:
         """Stream-K fix-ups that timed out since the workspace was created (pfk_conv_workspace_fault_offset): 0 means every
@@ -424,16 +446,11 @@ class UpdateEngine:
             hxb = self.hxb.view(B, N, self.hxb.shape[1])
             self._conv([self.hxb[:, o: o + mc]], 1, 1, "tv", mc, relu=False, out=self.vbuf)
             self.vT[:, :, :N].copy_(self.vbuf.view(B, N, mc).transpose(1, 2))
-            prof = self.profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+            t0 = self.tic() if self.profile is not None else None
             self.ops.conv2d_b16([self.attn], 1, H, W, 1, 1, self.vT, None, mc, EPI_LINEAR, False, self.gamma,
                                 hxb[:, :, o + mc: o + 2 * mc], None, None, None, None, hxb[:, :, o: o + mc])
-            if prof is not None:
-                e1.record()
-                prof.setdefault("ag", []).append((e0, e1))
-                self.flops["ag"] = 2.0 * B * N * N * mc
+            if t0 is not None:      # `ag`, here and below: FLOPs only, deliberately — no byte count was ever defined for it (bench.py: None)
+                self.toc(t0, "ag", 2.0 * B * N * N * mc)
             return
         mf = self.hx[:, o: o + mc]
         self._conv([mf], 1, 1, "tv", mc, relu=False, out=self.vbuf)
@@ -445,33 +462,23 @@ class UpdateEngine:
             for b0 in range(0, B, 4):
                 bs = list(range(b0, min(B, b0 + 4)))
                 rows = [slice(b * N, (b + 1) * N) for b in bs]
-                prof = self.profile
-                if prof is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
+                t0 = self.tic() if self.profile is not None else None
                 self.ops.conv2d_group([self.attn[b] for b in bs], 1, H, W, [1] * len(bs), [self.vT[b] for b in bs],
                                       [self._empty] * len(bs), [0] * len(bs), [self.gamma] * len(bs),
                                       [self.hx[r, o + mc: o + 2 * mc] for r in rows], [self.hx[r, o: o + mc] for r in rows])
-                if prof is not None:
-                    e1.record()
-                    prof.setdefault("ag", []).append((e0, e1))
-                    self.flops["ag"] = 2.0 * len(bs) * N * N * mc
+                if t0 is not None:
+                    self.toc(t0, "ag", 2.0 * len(bs) * N * N * mc)
             return
         for b in range(B):
             rows = slice(b * N, (b + 1) * N)
             src = self.attn[b]
-            prof = self.profile
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+            t0 = self.tic() if self.profile is not None else None
             # split modes: V^T changes every iteration, so its bf16 planes are cut here (three tiny elementwise kernels)
             vt = self.vT[b] if self.nsplit == 0 else split_bf16_planes(self.vT[b], self.nsplit)
             self.ops.conv2d([src], 1, H, W, 1, 1, vt, None, mc, EPI_LINEAR, False, self.gamma,
                             self.hx[rows, o + mc: o + 2 * mc], None, None, None, self.workspace, self.hx[rows, o: o + mc])
-            if prof is not None:
-                e1.record()
-                prof.setdefault("ag", []).append((e0, e1))
-                self.flops["ag"] = 2.0 * N * N * mc
+            if t0 is not None:
+                self.toc(t0, "ag", 2.0 * N * N * mc)
 
     def load_state(self, net: torch.Tensor, inp: torch.Tensor) -> None:
         """NCHW ``net`` / ``inp`` -> their hx slices (once per forward), then the loop-invariant context terms."""
@@ -500,10 +507,7 @@ class UpdateEngine:
     def _conv(self, srcs: List[torch.Tensor], kh, kw, key, cout, relu=True, scale=1.0, out=None,
               epi=EPI_LINEAR, h=None, z=None, rh=None, workspace=True, residual=None, cout_active=0, cout_split=0):
         B, H, W = self._shape
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        t0 = self.tic() if self.profile is not None else None
         # a stream-K workspace belongs to ONE stream: `workspace` = True (the main chain's), a branch's own tensor, or False
         # (none: plain tile grid)
         ws = self.workspace if workspace is True else (workspace if isinstance(workspace, torch.Tensor) else None)
@@ -517,16 +521,14 @@ class UpdateEngine:
         else:
             self.ops.conv2d(srcs, B, H, W, kh, kw, self.w[key + ".w"], self.w.get(key + ".b"), cout, epi, relu, scale,
                             out, h, z, rh, ws, residual, 1, False, cout_active, cout_split)
-        if prof is not None:
-            e1.record()
+        if t0 is not None:
+            cin = self._real_cin[key]
             if cout_active:
                 key, cout = key + "_half", cout_active
-                self._real_cin[key] = self._real_cin[key[:-5]]
-            prof.setdefault(key, []).append((e0, e1))
             # algorithmic work: 2 * pixels * cout * taps * real input channels (padding is not work)
-            self.flops[key] = 2.0 * B * H * W * cout * kh * kw * self._real_cin[key]
             # algorithmic HBM bytes: every input channel read once, every output written once, the weight once (fp32)
-            self.bytes[key] = (2.0 if self.b16 else 4.0) * (B * H * W * (self._real_cin[key] + cout) + cout * kh * kw * self._real_cin[key])
+            self.toc(t0, key, 2.0 * B * H * W * cout * kh * kw * cin,
+                     (2.0 if self.b16 else 4.0) * (B * H * W * (cin + cout) + cout * kh * kw * cin))
 
     def _use_wino(self, key: str, pixels: int, cout: int) -> bool:
         """`pfk_conv2d_wino_f32` for `fm`, `c2`, `cv` (their transformed weights exist on the fp32 engine only, see pack) where
@@ -564,6 +566,11 @@ class UpdateEngine:
         """the grouped launch exists for the fp32 tile kernel (`pfk_conv2d_group_f32`)"""
         return self.nsplit == 0 and not self.b16
 
+    @property
+    def wants_grouped_motion(self) -> bool:
+        """for the callers without a schedule of their own (drop-in seam, SEA-RAFT engine): grouped below the small-grid threshold"""
+        return self.can_group and self.pixels < SMALL_GRID_PIXELS
+
     def motion_grouped(self, corr_pm: torch.Tensor, prev_mask: bool = False) -> None:
         """The motion encoder with convc1 | convf2 [| the PREVIOUS iteration's mask conv2] as ONE grouped launch
         (`pfk_conv2d_group_f32`; update.py:105-108: `cor` and `flo` only meet in `conv`; :152: the mask head reads `net` only, i.e. the
@@ -580,20 +587,14 @@ class UpdateEngine:
         outs = [self.cor1 if s.c2 else self.corflo[:, : s.c1], self.corflo[:, cor_c: cor_c + s.f2]]
         if prev_mask:
             srcs.append(self.fm[:, s.fh_hidden:]); ks.append(1); keys.append("mk"); relu.append(0); scale.append(0.25); outs.append(self.mask)
-        prof = self.profile
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        t0 = self.tic() if self.profile is not None else None
         self.ops.conv2d_group(srcs, B, H, W, ks, [self.w[k + ".w"] for k in keys],
                               [self.w[k + ".b"] for k in keys], relu, scale, outs, [])
-        if prof is not None:
-            e1.record()
-            key = "+".join(keys)
-            prof.setdefault(key, []).append((e0, e1))
+        if t0 is not None:
             M = B * H * W
-            self.flops[key] = sum(2.0 * M * o.shape[1] * k * k * self._real_cin[kk] for o, k, kk in zip(outs, ks, keys))
-            self.bytes[key] = sum(4.0 * (M * (self._real_cin[kk] + o.shape[1]) + o.shape[1] * k * k * self._real_cin[kk])
-                                  for o, k, kk in zip(outs, ks, keys))
+            self.toc(t0, "+".join(keys), sum(2.0 * M * o.shape[1] * k * k * self._real_cin[kk] for o, k, kk in zip(outs, ks, keys)),
+                     sum(4.0 * (M * (self._real_cin[kk] + o.shape[1]) + o.shape[1] * k * k * self._real_cin[kk])
+                         for o, k, kk in zip(outs, ks, keys)))
         if s.c2:
             self._conv([self.cor1], 3, 3, "c2", s.c2, out=self.corflo[:, : s.c2])
         self.motion_join()
@@ -672,7 +673,7 @@ class UpdateEngine:
             # launch, so that they share their split points (same bits) and the half launch still balances its blocks
             self._conv([self.h_view], 3, 3, "fm", 2 * s.fh_hidden, out=self.fm, cout_active=0 if want_mask else s.fh_hidden,
                        cout_split=s.fh_hidden)
-        elif s.has_mask and not want_mask and (self.b16 or self._shape[0] * self._shape[1] * self._shape[2] >= 28160):
+        elif s.has_mask and not want_mask and (self.b16 or self.pixels >= SMALL_GRID_PIXELS):
             # split-bf16 / K8b kernels (no `cout_active`): the flow-head-only weights, where no launch is in the stream-K window
             self._conv([self.act[:, : s.hidden]], 3, 3, "fh", s.fh_hidden, out=self.fm[:, : s.fh_hidden])
         else:
@@ -706,19 +707,13 @@ class UpdateEngine:
         reads the mask half of `fm` (written by `heads_conv1`) and the flow slice of hx, writes the 8x flow; the [M, 576] mask is
         never materialised.  Bit-identical to `mask_head()` + `convex_upsample_pm` (tests/test_gpu_kernels.py)."""
         s = self.spec
-        key = "mku"
         x = self.fm[:, s.fh_hidden:]
-        if self.profile is not None:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
+        t0 = self.tic() if self.profile is not None else None
         self.ops.mask_upsample(x, self.w["mku.w"], self.w["mku.b"], 0.25, self.flow_view, flow_up)
-        if self.profile is not None:
-            b.record()
-            self.profile.setdefault(key, []).append((a, b))
+        if t0 is not None:
             M = x.shape[0]
-            self.flops[key] = 2.0 * M * 576 * s.fh_hidden
             eb = 2.0 if self.b16 else 4.0       # activation / weight element size; flow in and 8x flow out are fp32 on both paths
-            self.bytes[key] = eb * (M * s.fh_hidden + 576 * s.fh_hidden) + 4.0 * (2 * M + 2 * 64 * M)
+            self.toc(t0, "mku", 2.0 * M * 576 * s.fh_hidden, eb * (M * s.fh_hidden + 576 * s.fh_hidden) + 4.0 * (2 * M + 2 * 64 * M))
 
     def step(self, corr_pm: torch.Tensor, coords0: torch.Tensor, coords1: torch.Tensor, want_mask: bool = True) -> None:
         """One full RAFT iteration body after the lookup; updates hx (net, flow) and coords1 in place."""
@@ -860,7 +855,7 @@ class PfkUpdateBlock(WrappedModule):
                     eng.set_attention(attention)
                     self._attn_ref, self._attn_version = attention, attention._version
             # small batches: convc1 | convf2 as one grouped launch (`motion_grouped`; same tiles, same bits)
-            eng.motion_and_gru(corr_pm, grouped=eng.can_group and B * H * W < 28160)
+            eng.motion_and_gru(corr_pm, grouped=eng.wants_grouped_motion)
         if new_forward:
             eng._scratch_c1.zero_()     # the kernel's `coords1 += delta` lands here; `delta` itself does not depend on it — once per forward keeps it bounded
         # a live call of an armed forward leaves mask conv2 to seam B5, which runs it fused with the softmax and the upsampling (K13)
