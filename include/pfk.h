@@ -299,6 +299,24 @@ int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream);
  * keeps refusing a residual. */
 int pfk_conv2d_wino_res_f32(const pfk_conv_desc* d, pfk_stream_t stream);
 
+/* 1-D Winograd F(4,5) form of pfk_conv2d_f32 for the 1x5 / 5x1 stride-1 convolutions of the SepConvGRU (raft/update.py:58-73;
+ * fp32 MFMA, fp32 accumulate): 8 GEMMs over the transformed input per 4 outputs along the convolution axis, 2.5x fewer products
+ * than the direct form.  Supported: (kh, kw) = (1, 5) or (5, 1), stride 0 or 1, one or two sources in K order (channels % 8 == 0
+ * each), the epilogues PFK_EPI_LINEAR (bias, relu, scale; no residual), PFK_EPI_GRU_ZR and PFK_EPI_GRU_Q exactly as defined above
+ * (optional `residual` rows added to the pre-activation, h through h_ld, q updates h in place).  `cout_active` below cout,
+ * `relu_after_residual`, any other kernel size, stride, epilogue or source count: PFK_ERR_UNSUPPORTED.  `workspace` and `cout_split`
+ * are ignored (one schedule, no workspace).  Results differ from pfk_conv2d_f32 by fp32 rounding (pre-activation error about 6e-6 at
+ * K = 256 with unit-scale operands, several times the direct form's); the same inputs give the same bits on every launch.
+ * d->weight = the transformed weight, pfk_conv_wino1d_weight_floats(ktot, cout) floats, 16-byte aligned, ktot = the sources'
+ * channels summed:  U = G g per (co, c) over the 5 taps (correlation order), interpolation points 0, +-1, +-2, +-1/2, inf,
+ *   G = [-1 0 0 0 0; -2/9 -2/9 -2/9 -2/9 -2/9; -2/9 2/9 -2/9 2/9 -2/9; 1/90 1/45 2/45 4/45 8/45; 1/90 -1/45 2/45 -4/45 8/45;
+ *        32/45 16/45 8/45 4/45 2/45; 32/45 -16/45 8/45 -4/45 2/45; 0 0 0 0 1],
+ * made in float64 and rounded to fp32 once, laid out [ceil(cout/128)][ktot/8][8 (component)][128 (nl)][8 (slot)] with
+ * co = 128*cb + nl, k = 8*ks + cc, slot as in pfk_conv2d_wino_f32's weight, zeros for co >= cout and for a source's pad channels
+ * (ptlflow_amd/packing.py, pack_wino1d_weight). */
+long long pfk_conv_wino1d_weight_floats(int ktot, int cout);   /* < 0 (PFK_ERR_BAD_ARG) unless ktot % 8 == 0, ktot, cout > 0 */
+int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream);
+
 /* Same convolution on the bf16 matrix cores with split operands (fp32 in HBM, fp32 accumulate, fp32 epilogue).
  * Every fp32 operand x is replaced by the sum of its first `nsplit` bf16 planes x0 = bf16(x), x1 = bf16(x - x0),
  * x2 = bf16(x - x0 - x1); a product keeps the terms a_i*b_j with i + j < nsplit:

@@ -180,6 +180,42 @@ void conv2d_wino_res(const Tensor& src, int64_t B, int64_t H, int64_t W, const T
   conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, 0, &residual, relu_after_residual);
 }
 
+// 1-D Winograd F(4,5) form of a 1x5 / 5x1 convolution (pfk_conv1d_wino_f32): one or two fp32 sources ([B*H*W, channels_i] views,
+// channels % 8 == 0), the transformed weight of packing.pack_wino1d_weight (flat), the LINEAR epilogue into `out` or the GRU gate
+// epilogues with h / aux_z / aux_rh / residual as in conv2d
+void conv2d_wino1d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, int64_t kw, const Tensor& weight,
+                   const c10::optional<Tensor>& bias, int64_t cout, int64_t epilogue, bool relu, double scale,
+                   const c10::optional<Tensor>& out, const c10::optional<Tensor>& h, const c10::optional<Tensor>& aux_z,
+                   const c10::optional<Tensor>& aux_rh, const c10::optional<Tensor>& residual) {
+  OpScope scope(weight);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, "conv2d_wino1d: sizes");
+  TORCH_CHECK(srcs.size() <= 2, "conv2d_wino1d: one or two sources");
+  pfk_conv_desc d{};
+  const int64_t M = B * H * W, Ch = gru_hidden(epilogue, cout);
+  fill_sources(d, srcs, M, F32, "conv2d_wino1d");
+  int64_t ktot = 0;
+  for (int i = 0; i < d.num_src; ++i) {
+    TORCH_CHECK(d.src[i].channels % 8 == 0, "conv2d_wino1d: source channels must be a multiple of 8, got ", d.src[i].channels);
+    ktot += d.src[i].channels;
+  }
+  d.B = B; d.H = H; d.W = W; d.kh = kh; d.kw = kw; d.stride = 1; d.cout = cout;
+  d.epilogue = epilogue; d.relu = relu; d.scale = (float)scale;
+  d.weight = dense("conv2d_wino1d", weight, "weight (transformed)", F32, pfk_conv_wino1d_weight_floats((int)ktot, (int)cout)).f32();
+  d.bias = dense("conv2d_wino1d", bias, "bias", F32, cout).f32();
+  if (out.has_value()) {
+    const Rows o = rows("conv2d_wino1d", *out, "out", F32).expect(M, cout);
+    d.out = o.f32(); d.out_ld = o.ld; d.out_coff = 0;
+  }
+  if (h.has_value()) { const Rows v = rows("conv2d_wino1d", *h, "h", F32).expect(M, AtLeast{Ch}); d.h = v.f32(); d.h_ld = v.ld; }
+  d.aux_z = dense("conv2d_wino1d", aux_z, "aux_z", F32, AtLeast{M * Ch}).f32();
+  d.aux_rh = dense("conv2d_wino1d", aux_rh, "aux_rh", F32, AtLeast{M * Ch}).f32();
+  if (residual.has_value()) {
+    const Rows r = rows("conv2d_wino1d", *residual, "residual", F32).expect(M, cout);
+    d.residual = r.f32(); d.residual_ld = r.ld;
+  }
+  check_ok(pfk_conv1d_wino_f32(&d, cur_stream()), "conv2d_wino1d");
+}
+
 // Grouped launch (pfk_conv2d_group_f32): problem i = one fp32 source srcs[i] ([B*H*W, cin_i] view), k[i] x k[i] taps, stride 1, packed
 // weight weights[i] [cout_i, ktot_i], bias biases[i] (an empty tensor = none), relu[i], scale[i], out = outs[i] ([B*H*W, cout_i] view),
 // residuals[i] (optional; an empty tensor = none): added after relu / scale
@@ -1030,6 +1066,9 @@ TORCH_LIBRARY(pfk, m) {
         "Tensor(e!)? workspace=None, Tensor? residual=None, int stride=1, bool relu_after_residual=False, int cout_active=0, int cout_split=0) -> ()");
   m.def("conv2d_wino(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
         "int cout_active=0) -> ()");
+  m.def("conv2d_wino1d(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, int epilogue, "
+        "bool relu, float scale, Tensor(a!)? out=None, Tensor(b!)? h=None, Tensor(c!)? aux_z=None, Tensor(d!)? aux_rh=None, "
+        "Tensor? residual=None) -> ()");
   m.def("conv2d_wino_res(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
         "Tensor residual, bool relu_after_residual) -> ()");
   m.def("conv2d_group(Tensor[] srcs, int B, int H, int W, int[] k, Tensor[] weights, Tensor[] biases, int[] relu, float[] scale, Tensor(a!)[] outs, Tensor[] residuals) -> ()");
@@ -1088,6 +1127,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv2d_group", &conv2d_group);
   m.impl("conv2d_wino", &conv2d_wino);
   m.impl("conv2d_wino_res", &conv2d_wino_res);
+  m.impl("conv2d_wino1d", &conv2d_wino1d);
   m.impl("conv_cin2", &conv_cin2);
   m.impl("flow_delta", &flow_delta);
   m.impl("flow_from_coords", &flow_from_coords);

@@ -42,6 +42,7 @@ constexpr int UIMG = 16 * WN * WK;   // floats of one K-step of one column block
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lfloat;   // LDS pointers keep their address space (ds_ instructions, 32-bit)
 typedef __attribute__((address_space(3))) f32x2 lf32x2;
+typedef __attribute__((address_space(3))) f32x4 lf32x4;
 
 struct WinoArgs {
   const float* src; int ld;      // pixel-major source, row stride in floats
@@ -247,9 +248,389 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
   }
 }
 
+// ---- K4w1: the SepConvGRU's 1x5 / 5x1 gate convolutions as 1-D Winograd F(4,5) -------------------------------------------------
+// Points 0, +-1, +-2, +-1/2, inf: for 4 consecutive outputs along the convolution axis and the 8 input pixels d that start 2 in
+// front of the first one (correlation form, y_i = sum_k d[i + k] g[k]),  Y = A^T [ sum_c (G g_c) (.) (B^T d_c) ]  with
+//   B^T = [-1 0 21/4 0 -21/4 0 1 0; 0 1 1 -17/4 -17/4 1 1 0; 0 -1 1 17/4 -17/4 -1 1 0; 0 1/2 1/4 -5/2 -5/4 2 1 0;
+//          0 -1/2 1/4 5/2 -5/4 -2 1 0; 0 2 4 -5/2 -5 1/2 1 0; 0 -2 4 5/2 -5 -1/2 1 0; 0 -1 0 21/4 0 -21/4 0 1]
+//   A^T = [1 1 1 1 1 1 1 0; 0 1 -1 2 -2 1/2 -1/2 0; 0 1 1 4 4 1/4 1/4 0; 0 1 -1 8 -8 1/8 -1/8 1]
+// (every entry exact in fp32; rows 1|2, 3|4, 5|6 share their even and odd parts): 8 products per 4 outputs instead of 20.
+// U = G g (packing.pack_wino1d_weight: fp64, rounded once) comes as the LDS image of one (128-channel column block, K-step):
+//   weight[cb][ks][xi (8)][nl (128)][slot (8)], the slot order of the 2-D kernel — again 32 KB, copied by the same 8 LDS-DMA pieces.
+// With 8 components instead of 16 the wave tile doubles its columns: block = 32 tiles x 128 channels, wave = 16 tiles x 64 channels
+// x 8 components = 8 x 4 accumulators of 16x16 (128 per lane), 8 x 8 = 64 MFMAs per K-step as before; V is 8 KB, 72 KB LDS in all.
+// The loop, the raw barriers, the operand requests between the MFMAs (one U piece and one tap beside each component) are the 2-D
+// kernel's.  VERT = false (1x5): tiles run along a row, the block's 32 tiles row-major over (image row, tile x).  VERT = true (5x1):
+// tiles run down a column, the block's tiles are neighbouring x of one tile row.  The K-steps walk source 0, then source 1 (the
+// torch.cat operands of the gate convolutions), each with its own descriptor and tap offsets.  Epilogues after the lane-local A^T m:
+// LINEAR, GRU_ZR, GRU_Q of include/pfk.h with pfk_gemm.h's arithmetic.  Nothing depends on the grid: same input, same bits.
+constexpr int WN1 = 128;                 // output channels per block
+constexpr int VIMG1 = 8 * WT * WK;       // floats of V: 8 components x 32 tiles x 8 channels
+
+struct Wino1dArgs {
+  const float* src0; const float* src1;   // pixel-major sources in K order (src1 = src0 when there is one)
+  int ld0, ld1;
+  unsigned bytes0, bytes1;                // readable bytes from each
+  int nks0, nks;                          // K-steps of source 0, of both
+  int H, W;
+  int L, nt;                              // pixels and tiles along the convolution axis
+  int ntiles;
+  const float* weight; unsigned w_bytes;
+  const float* bias;
+  int cout, ncb;
+  int relu; float scale;
+  float* out; int out_ld, out_coff;
+  const float* res; int res_ld;           // GRU epilogues: added to the pre-activation
+  float* h; int h_ld;
+  float* aux_z; float* aux_rh;
+  int ch;
+};
+
+// tile g -> the pixel of axis coordinate 0 on its line, and its tile index along the axis
+template <bool VERT>
+__device__ __forceinline__ void wino1d_tile(const Wino1dArgs& a, int g, int& base, int& t) {
+  if constexpr (VERT) {
+    const int r = g / a.W, x = g - r * a.W, b = r / a.nt;
+    t = r - b * a.nt;
+    base = b * a.H * a.W + x;
+  } else {
+    const int line = g / a.nt;
+    t = g - line * a.nt;
+    base = line * a.W;
+  }
+}
+
+// tap q of this thread's (tile, channel) of a K-step: `s1` (block-uniform) = the K-step lies in source 1, `soff` = its channel offset there
+__device__ __forceinline__ void wino1d_load_v(__amdgpu_buffer_rsrc_t rs0, __amdgpu_buffer_rsrc_t rs1, const unsigned (&voff0)[8],
+                                              const unsigned (&voff1)[8], bool s1, int soff, int q, float (&d)[8]) {
+  d[q] = s1 ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, voff1[q], soff, 0))
+            : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs0, voff0[q], soff, 0));
+}
+
+// One K-step of the wave's 16 tiles x 64 columns, all 8 components (see wino_mfma).  aU[f] reach the four column fragments through
+// registers the compiler cannot relate: four ds_read_b64 per component.
+__device__ __forceinline__ void wino1d_mfma(const lfloat* aV, const lfloat* aU0, const lfloat* aU1, const lfloat* aU2, const lfloat* aU3,
+                                            f32x4 (&acc)[8][4], bool more, __amdgpu_buffer_rsrc_t rw, lfloat* udst, unsigned wvoff,
+                                            unsigned wk, __amdgpu_buffer_rsrc_t rs0, __amdgpu_buffer_rsrc_t rs1,
+                                            const unsigned (&voff0)[8], const unsigned (&voff1)[8], bool s1, int soff, float (&d)[8]) {
+  f32x2 va[2], u[2][4];
+  va[0] = *(const lf32x2*)(aV);
+  u[0][0] = *(const lf32x2*)(aU0);
+  u[0][1] = *(const lf32x2*)(aU1);
+  u[0][2] = *(const lf32x2*)(aU2);
+  u[0][3] = *(const lf32x2*)(aU3);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int x = 0; x < 8; ++x) {
+    const int c = x & 1, n = c ^ 1;
+    if (x + 1 < 8) {
+      va[n] = *(const lf32x2*)(aV + (x + 1) * WT * WK);
+      u[n][0] = *(const lf32x2*)(aU0 + (x + 1) * WN1 * WK);
+      u[n][1] = *(const lf32x2*)(aU1 + (x + 1) * WN1 * WK);
+      u[n][2] = *(const lf32x2*)(aU2 + (x + 1) * WN1 * WK);
+      u[n][3] = *(const lf32x2*)(aU3 + (x + 1) * WN1 * WK);
+    }
+    if (more) {
+      wino_dma_u(rw, udst, wvoff, wk, x);
+      wino1d_load_v(rs0, rs1, voff0, voff1, s1, soff, x, d);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) acc[x][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][s], u[c][f][s], acc[x][f], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// y = A^T m of fragment f, accumulator row r (one tile of one column)
+__device__ __forceinline__ void wino1d_at(const f32x4 (&acc)[8][4], int f, int r, float (&y)[4]) {
+  const float p12 = acc[1][f][r] + acc[2][f][r], q12 = acc[1][f][r] - acc[2][f][r];
+  const float p34 = acc[3][f][r] + acc[4][f][r], q34 = acc[3][f][r] - acc[4][f][r];
+  const float p56 = acc[5][f][r] + acc[6][f][r], q56 = acc[5][f][r] - acc[6][f][r];
+  y[0] = acc[0][f][r] + p12 + p34 + p56;
+  y[1] = q12 + 2.f * q34 + 0.5f * q56;
+  y[2] = p12 + 4.f * p34 + 0.25f * p56;
+  y[3] = q12 + 8.f * q34 + 0.125f * q56 + acc[7][f][r];
+}
+
+template <bool VERT, int EPI>
+__global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino1dArgs a) {
+  // 2 x 32 KB of U + 8 KB of V
+  __shared__ __attribute__((aligned(16))) float smem[2 * UIMG + VIMG1];
+  lfloat* const sU = (lfloat*)smem;    // [buffer][xi][column][slot]
+  lfloat* const sV = sU + 2 * UIMG;    // [xi][tile][slot]
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cb = blockIdx.x % a.ncb;
+  const int t0 = (blockIdx.x / a.ncb) * WT;
+  const int pstride = VERT ? a.W : 1;
+
+  const __amdgpu_buffer_rsrc_t rs0 = rsrc_n(a.src0, a.bytes0);
+  const __amdgpu_buffer_rsrc_t rs1 = rsrc_n(a.src1, a.bytes1);
+  const __amdgpu_buffer_rsrc_t rw = rsrc_n(a.weight, a.w_bytes);
+
+  // ---- staging role: tile lt, channel cc of the K-step
+  const int lt = tid >> 3, cc = tid & 7;
+  unsigned voff0[8], voff1[8];
+  {
+    const int g = t0 + lt;
+    const bool tok = g < a.ntiles;
+    int base, t;
+    wino1d_tile<VERT>(a, g, base, t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int ax = 4 * t - 2 + j;
+      const bool ok = tok && (unsigned)ax < (unsigned)a.L;
+      const unsigned pix = (unsigned)(base + ax * pstride);
+      voff0[j] = ok ? (pix * (unsigned)a.ld0 + (unsigned)cc) * 4u : OOB;
+      voff1[j] = ok ? (pix * (unsigned)a.ld1 + (unsigned)cc) * 4u : OOB;
+    }
+  }
+  const int vslot = ((cc & 3) * 2 + (cc >> 2)) ^ (((lt >> 2) & 3) * 2);
+  lfloat* const vdst = sV + lt * WK + vslot;
+  const unsigned wvoff = (unsigned)lane * 16u;
+  const unsigned wbase = (unsigned)cb * (unsigned)a.nks * (UIMG * 4u) + (unsigned)wid * 1024u;
+  lfloat* const udst = sU + wid * 256;
+
+  float d[8];
+  // ---- MFMA role: wave tile rows wt*16.., columns wc*64..
+  const int wt = wid & 1, wc = wid >> 1;
+  const int rl = lane & 15, kq = lane >> 4;
+  const int oslot = (kq * 2) ^ (((rl >> 2) & 3) * 2);
+  const lfloat* const aV = sV + (wt * 16 + rl) * WK + oslot;
+  const lfloat* const aU0 = sU + (wc * 64 + rl) * WK + oslot;
+  const lfloat* aU1 = aU0 + 16 * WK;
+  const lfloat* aU2 = aU0 + 32 * WK;
+  const lfloat* aU3 = aU0 + 48 * WK;
+  asm volatile("" : "+v"(aU1));
+  asm volatile("" : "+v"(aU2));
+  asm volatile("" : "+v"(aU3));
+
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int x = 0; x < 8; ++x)
+#pragma unroll
+    for (int f = 0; f < 4; ++f) acc[x][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    wino_dma_u(rw, udst, wvoff, wbase, j);
+    wino1d_load_v(rs0, rs1, voff0, voff1, false, 0, j, d);
+  }
+  for (int ks = 0; ks < a.nks; ++ks) {
+    // V = B^T d, one channel of one tile
+    {
+      const float e12 = d[2] - 4.25f * d[4] + d[6], o12 = d[1] - 4.25f * d[3] + d[5];
+      const float e34 = 0.25f * d[2] - 1.25f * d[4] + d[6], o34 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
+      const float e56 = 4.f * d[2] - 5.f * d[4] + d[6], o56 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
+      vdst[0 * WT * WK] = (d[6] - d[0]) + 5.25f * (d[2] - d[4]);
+      vdst[1 * WT * WK] = e12 + o12;
+      vdst[2 * WT * WK] = e12 - o12;
+      vdst[3 * WT * WK] = e34 + o34;
+      vdst[4 * WT * WK] = e34 - o34;
+      vdst[5 * WT * WK] = e56 + o56;
+      vdst[6 * WT * WK] = e56 - o56;
+      vdst[7 * WT * WK] = (d[7] - d[1]) + 5.25f * (d[3] - d[5]);
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const int ub = (ks & 1) * UIMG;
+    const int kn = ks + 1;
+    const bool s1 = kn >= a.nks0;
+    const int soff = (kn - (s1 ? a.nks0 : 0)) * WK * 4;
+    wino1d_mfma(aV, aU0 + ub, aU1 + ub, aU2 + ub, aU3 + ub, acc, kn < a.nks, rw, udst + (UIMG - ub), wvoff,
+                wbase + (unsigned)kn * (UIMG * 4u), rs0, rs1, voff0, voff1, s1, soff, d);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+
+  // ---- epilogue: lane holds tiles 4*kq + r (r = 0..3) of column rl of each fragment, in every component
+  typedef __attribute__((address_space(1))) float gfloat;
+  if constexpr (EPI == PFK_EPI_LINEAR) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const int n = cb * WN1 + wc * 64 + f * 16 + rl;
+      const bool nok = n < a.cout;
+      const float bias = (a.bias != nullptr && nok) ? a.bias[n] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int g = t0 + wt * 16 + kq * 4 + r;
+        float y[4];
+        wino1d_at(acc, f, r, y);
+        if (!nok || g >= a.ntiles) continue;
+        int base, t;
+        wino1d_tile<VERT>(a, g, base, t);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int ax = 4 * t + e;
+          if (ax >= a.L) continue;
+          const long long p = base + ax * pstride;
+          float v = y[e] + bias;
+          if (a.relu) v = (v < 0.f) ? 0.f : v;   // NaN-propagating like torch.relu
+          v *= a.scale;
+          ((gfloat*)a.out)[p * a.out_ld + a.out_coff + n] = v;
+        }
+      }
+    }
+  } else {
+    // The gate epilogues read two or three rows per output (context term, h, z): from the accumulator layout that is 64-byte pieces,
+    // four at a time, with the memory latency of each batch exposed.  Instead every wave parks its 64 pixels x 64 columns of A^T m in
+    // its own 17 KB of the LDS the loop has finished with (all waves are past the last barrier; rows padded to 68 floats: the float4
+    // reads of four rows fall into different banks) and walks them as rows: a lane takes 4 columns of one pixel, 16 lanes a 256-byte
+    // row piece, and the loads of 8 pixels per lane are requested before the first is used.
+    constexpr int ES = 68;
+    static_assert(4 * 64 * ES <= 2 * UIMG + VIMG1, "the four waves' parking areas must fit into the loop's LDS");
+    lfloat* const sE = (lfloat*)smem + wid * (64 * ES);
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float y[4];
+        wino1d_at(acc, f, r, y);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sE[((kq * 4 + r) * 4 + e) * ES + f * 16 + rl] = y[e];
+      }
+    const int prow = lane >> 4, col4 = (lane & 15) * 4;
+    const int n0 = cb * WN1 + wc * 64 + col4;        // cout % 4 == 0: the lane's four columns are inside or outside together
+    const bool nok = n0 < a.cout;
+    const int nc = nok ? n0 : 0;
+    const int ch = a.ch;
+    f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (a.bias != nullptr) bias4 = f32x4{a.bias[nc], a.bias[nc + 1], a.bias[nc + 2], a.bias[nc + 3]};
+    const bool upper = nc >= ch;                      // GRU_ZR: the r half
+    const int hc = (EPI == PFK_EPI_GRU_ZR) ? (upper ? nc - ch : 0) : nc;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      bool ok[8];
+      long long p[8];
+      f32x4 r4[8], h4[8], z4[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int li = (half * 8 + i) * 4 + prow;     // the wave's pixel: tile li >> 2, output li & 3
+        const int g = t0 + wt * 16 + (li >> 2);
+        int base, t;
+        wino1d_tile<VERT>(a, g, base, t);
+        const int ax = 4 * t + (li & 3);
+        ok[i] = nok && g < a.ntiles && ax < a.L;
+        p[i] = ok[i] ? base + ax * pstride : 0;       // (row 0 for the lanes without an output: every load below is legal)
+        r4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (a.res != nullptr) r4[i] = *(const f32x4*)(a.res + p[i] * a.res_ld + nc);
+        if constexpr (EPI == PFK_EPI_GRU_ZR) {
+          if (upper) h4[i] = *(const f32x4*)(a.h + p[i] * a.h_ld + hc);
+        } else {
+          z4[i] = *(const f32x4*)(a.aux_z + p[i] * ch + nc);
+          h4[i] = *(const f32x4*)(a.h + p[i] * a.h_ld + hc);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int li = (half * 8 + i) * 4 + prow;
+        const f32x4 v = *(const lf32x4*)(sE + li * ES + col4) + bias4 + r4[i];
+        f32x4 o;
+        if constexpr (EPI == PFK_EPI_GRU_ZR) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = sigmoid_f(v[e]);
+          if (!ok[i]) continue;
+          if (upper) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] *= h4[i][e];
+            *(f32x4*)(a.aux_rh + p[i] * ch + hc) = o;
+          } else {
+            *(f32x4*)(a.aux_z + p[i] * ch + nc) = o;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            // (1 - z) * h + z * q, each product rounded (no contraction), as the direct kernel's epilogue
+            const float keep = __fmul_rn(__fsub_rn(1.0f, z4[i][e]), h4[i][e]);
+            const float take = __fmul_rn(z4[i][e], tanhf(v[e]));
+            o[e] = __fadd_rn(keep, take);
+          }
+          if (!ok[i]) continue;
+          *(f32x4*)(a.h + p[i] * a.h_ld + hc) = o;
+        }
+      }
+    }
+  }
+}
+
+template <bool VERT>
+static void wino1d_launch_epi(const Wino1dArgs& a, int epilogue, unsigned nblk, hipStream_t st) {
+  switch (epilogue) {
+    case PFK_EPI_GRU_ZR: hipLaunchKernelGGL((conv_gemm_wino1d_f32_kernel<VERT, PFK_EPI_GRU_ZR>), dim3(nblk), dim3(256), 0, st, a); break;
+    case PFK_EPI_GRU_Q: hipLaunchKernelGGL((conv_gemm_wino1d_f32_kernel<VERT, PFK_EPI_GRU_Q>), dim3(nblk), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((conv_gemm_wino1d_f32_kernel<VERT, PFK_EPI_LINEAR>), dim3(nblk), dim3(256), 0, st, a); break;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+long long pfk_conv_wino1d_weight_floats(int ktot, int cout) {
+  if (ktot <= 0 || cout <= 0 || (ktot & 7)) return PFK_ERR_BAD_ARG;
+  return 8LL * ktot * ((cout + WN1 - 1) / WN1 * WN1);
+}
+
+int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
+  if (!d) return PFK_ERR_BAD_ARG;
+  const bool vert = d->kh == 5 && d->kw == 1;
+  if (!vert && !(d->kh == 1 && d->kw == 5)) return PFK_ERR_UNSUPPORTED;
+  if (d->stride > 1 || d->num_src < 1 || d->num_src > 2 || d->relu_after_residual) return PFK_ERR_UNSUPPORTED;
+  if (d->epilogue != PFK_EPI_LINEAR && d->epilogue != PFK_EPI_GRU_ZR && d->epilogue != PFK_EPI_GRU_Q) return PFK_ERR_UNSUPPORTED;
+  if (d->cout_active > 0 && d->cout_active < d->cout) return PFK_ERR_UNSUPPORTED;
+  if (d->epilogue == PFK_EPI_LINEAR && d->residual) return PFK_ERR_UNSUPPORTED;
+  if (!d->weight || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return PFK_ERR_BAD_ARG;
+  const long long M = (long long)d->B * d->H * d->W;
+  int ktot = 0;
+  for (int i = 0; i < d->num_src; ++i) {
+    const pfk_conv_src& s = d->src[i];
+    if (!s.ptr || s.channels <= 0 || s.ld < s.channels) return PFK_ERR_BAD_ARG;
+    if (s.channels & 7) return PFK_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(s.ptr) & 3u) return PFK_ERR_ALIGNMENT;
+    if (M * s.ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
+    ktot += s.channels;
+  }
+  const int ch = d->epilogue == PFK_EPI_GRU_ZR ? d->cout / 2 : d->cout;
+  if (d->epilogue == PFK_EPI_LINEAR) {
+    if (!d->out || d->out_coff < 0 || d->out_ld < d->out_coff + d->cout) return PFK_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(d->out) & 3u) return PFK_ERR_ALIGNMENT;
+  } else {
+    // the gate epilogues move float4 pieces of rows: hidden width % 4, 16-byte aligned rows
+    if (!d->h || !d->aux_z || d->h_ld < ch || (d->epilogue == PFK_EPI_GRU_ZR && (!d->aux_rh || (d->cout & 1))) || (ch & 3))
+      return PFK_ERR_BAD_ARG;
+    if (d->residual && d->residual_ld < d->cout) return PFK_ERR_BAD_ARG;
+    if (!pfk_aligned16(d->h) || !pfk_aligned16(d->aux_z) || !pfk_aligned16(d->aux_rh) || !pfk_aligned16(d->residual) || (d->h_ld & 3) ||
+        (d->residual && (d->residual_ld & 3)))
+      return PFK_ERR_ALIGNMENT;
+  }
+  if (!pfk_aligned16(d->weight)) return PFK_ERR_ALIGNMENT;
+  const long long wfloats = pfk_conv_wino1d_weight_floats(ktot, d->cout);
+  if (wfloats * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  Wino1dArgs a{};
+  const pfk_conv_src& s0 = d->src[0];
+  const pfk_conv_src& s1 = d->src[d->num_src - 1];
+  a.src0 = s0.ptr; a.ld0 = s0.ld; a.bytes0 = (unsigned)(((M - 1) * s0.ld + s0.channels) * 4);
+  a.src1 = s1.ptr; a.ld1 = s1.ld; a.bytes1 = (unsigned)(((M - 1) * s1.ld + s1.channels) * 4);
+  a.nks0 = s0.channels / WK; a.nks = ktot / WK;
+  a.H = d->H; a.W = d->W;
+  a.L = vert ? d->H : d->W;
+  a.nt = (a.L + 3) / 4;
+  const long long ntiles = (long long)d->B * (vert ? d->W : d->H) * a.nt;
+  a.ncb = (d->cout + WN1 - 1) / WN1;
+  const long long nblk = (ntiles + WT - 1) / WT * a.ncb;
+  if (nblk >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  a.ntiles = (int)ntiles;
+  a.weight = d->weight; a.w_bytes = (unsigned)(wfloats * 4);
+  a.bias = d->bias;
+  a.cout = d->cout;
+  a.relu = d->relu ? 1 : 0; a.scale = d->scale;
+  a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
+  a.res = d->residual; a.res_ld = d->residual_ld;
+  a.h = d->h; a.h_ld = d->h_ld; a.aux_z = d->aux_z; a.aux_rh = d->aux_rh; a.ch = ch;
+  if (vert) wino1d_launch_epi<true>(a, d->epilogue, (unsigned)nblk, static_cast<hipStream_t>(stream));
+  else wino1d_launch_epi<false>(a, d->epilogue, (unsigned)nblk, static_cast<hipStream_t>(stream));
+  return pfk_launch_status();
+}
 
 long long pfk_conv_wino_weight_floats(int cin, int cout) {
   if (cin <= 0 || cout <= 0 || (cin & 31)) return PFK_ERR_BAD_ARG;

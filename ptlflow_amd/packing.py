@@ -60,6 +60,42 @@ def pack_wino_weight(weight: torch.Tensor) -> torch.Tensor:
     return out.permute(1, 3, 0, 2, 4).contiguous().reshape(-1).to(weight.device)
 
 
+# Winograd F(4,5) weight transform, points 0, +-1, +-2, +-1/2, inf (correlation order of the 5 taps): U = G g
+WINO1D_G = ((-1.0, 0.0, 0.0, 0.0, 0.0),
+            (-2 / 9, -2 / 9, -2 / 9, -2 / 9, -2 / 9),
+            (-2 / 9, 2 / 9, -2 / 9, 2 / 9, -2 / 9),
+            (1 / 90, 1 / 45, 2 / 45, 4 / 45, 8 / 45),
+            (1 / 90, -1 / 45, 2 / 45, -4 / 45, 8 / 45),
+            (32 / 45, 16 / 45, 8 / 45, 4 / 45, 2 / 45),
+            (32 / 45, -16 / 45, 8 / 45, -4 / 45, 2 / 45),
+            (0.0, 0.0, 0.0, 0.0, 1.0))
+
+
+def pack_wino1d_weight(weight: torch.Tensor, segments: Sequence[Tuple[int, int, int]], dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``[cout, cin, 1, 5]`` or ``[cout, cin, 5, 1]`` -> the flat transformed weight of ``pfk_conv1d_wino_f32``: U = G g in float64 on
+    the host, rounded to fp32 once.  ``segments`` as in `pack_conv_weight` — one per source of the launch, in K order, with the
+    source's channel count in its buffer (a multiple of 8; pad channels get zero U).  Layout
+    ``[ceil(cout/128)][ktot/8][8][128][8]`` (column block, K-step, component, column, slot — include/pfk.h), pad columns zero.
+    Returned on ``weight``'s device.  ``dtype=torch.float64`` keeps U unrounded (tests of the layout; the kernel reads float32)."""
+    cout, cin, kh, kw = weight.shape
+    assert (kh, kw) in ((1, 5), (5, 1))
+    G = torch.tensor(WINO1D_G, dtype=torch.float64)
+    g = weight.detach().to(device="cpu", dtype=torch.float64).reshape(cout, cin, 5)
+    parts = []
+    for first, n, n_buf in segments:
+        assert first + n <= cin and n_buf >= n and n_buf % 8 == 0
+        parts.append(F.pad(torch.einsum("xk,ock->xoc", G, g[:, first:first + n]), (0, n_buf - n)))
+    U = torch.cat(parts, dim=2).to(dtype)                                                # [xi][co][k]
+    ktot = U.shape[2]
+    ncb = (cout + 127) // 128
+    U = F.pad(U, (0, 0, 0, ncb * 128 - cout)).reshape(8, ncb, 128, ktot // 8, 8)          # [xi][cb][nl][ks][cc]
+    nl = torch.arange(128).view(128, 1)
+    cc = torch.arange(8).view(1, 8)
+    slot = wino_slot(nl, cc).view(1, 1, 128, 1, 8).expand_as(U)
+    out = torch.empty_like(U).scatter_(4, slot, U)
+    return out.permute(1, 3, 0, 2, 4).contiguous().reshape(-1).to(weight.device)
+
+
 def split_bf16_planes(packed: torch.Tensor, nsplit: int) -> torch.Tensor:
     """fp32 ``[cout, ktot]`` -> bf16 ``[nsplit, cout, ktot]`` with plane 0 = bf16(w), plane 1 = bf16(w - plane 0), ...
     (round to nearest even; every residual is exact in fp32) — the weight operand of ``pfk_conv2d_bf16s``."""

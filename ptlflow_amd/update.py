@@ -34,8 +34,8 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, pixel_rows
-from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino_weight, permute_mask_head, round_up,
-                      split_bf16_planes)
+from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight, permute_mask_head,
+                      round_up, split_bf16_planes)
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 
@@ -113,6 +113,22 @@ def small_spec(corr_levels: int = 4, corr_radius: int = 3) -> UpdateSpec:
 # cout decides (a `cout_active` launch takes the same kernel as its full form).
 WINO_MIN_WORK = 28160
 
+# 1-D Winograd rule (`_use_wino1d`): the SepConvGRU's per-iteration z|r and q launches run as F(4,5) (`pfk_conv1d_wino_f32`) where
+# B*H*W >= WINO1D_MIN_PIXELS (and the transformed weights exist: fp32 engine, context hoisted, source widths multiples of 8, see pack).
+# In isolation (scripts/wino1d_bench.py, MI355X, the direct kernel with the engine's stream-K workspace,
+# median of three alternating rounds of 40 launches, us, the direct kernel's max - min in brackets; 1x5 shown, 5x1 agrees to 3 %,
+# profiles/r13_a_wino1d.md §3):
+#   grid (pixels)       raft z|r                 raft q                  gma z|r                  gma q
+#   2x55x128 (14080)     98.5 [ 9.5] ->  60.1     51.5 [ 0.0] ->  57.4   134.7 [17.4] ->  82.0     71.8 [ 1.1] ->  80.5
+#   4x55x128 (28160)    168.0 [21.1] ->  87.9     90.6 [ 1.2] ->  60.3   237.6 [36.9] -> 121.6    126.9 [ 2.8] ->  82.6
+#   8x55x128 (56320)    301.8 [21.2] -> 168.9    166.1 [ 4.5] ->  88.8   436.6 [27.3] -> 238.3    237.6 [14.8] -> 123.2
+#   8x47x156 (58656)    341.0 [ 4.8] -> 169.8    178.5 [ 5.3] ->  88.8   493.0 [27.1] -> 238.8    258.3 [10.0] -> 123.6
+# 28160 is the smallest measured size from which both launches win at both widths, each by more than the direct kernel's spread.  At
+# 14080 z|r (220 blocks of 32 tiles x 128 channels on 512 resident slots) still wins 1.6x but q (110 blocks) loses 0.9x, and at 7040
+# both lose (z|r 0.93x, q 0.56x); 14080 also lies below what tests/test_gpu_gru_schedules.py leaves open (q at 1x128x160 = 20480 pixels must stay
+# stream-K; z|r at 56320 must not touch the workspace).
+WINO1D_MIN_PIXELS = 28160
+
 # The small-grid threshold in PIXELS (B*H*W; batch 4 of 436x1024's 55x128 grid) — not `WINO_MIN_WORK`, which counts pixels x column
 # tiles and merely has the same value.  Below it the update block's launches (110..990 tiles at batch 1 for 256 CUs) each pay their own
 # tail: convc1 | convf2 [| the previous mask conv2] go as ONE grouped launch (`motion_grouped`).  From it up (measured, one MI355X):
@@ -164,7 +180,8 @@ class UpdateEngine:
         self.profile: Optional[Dict[str, list]] = None
         self.flops: Dict[str, float] = {}
         self.bytes: Dict[str, float] = {}
-        # fp32 engine: `fm`, `c2` and `cv` (3x3, one source) run as Winograd F(2x2,3x3) (`pfk_conv2d_wino_f32`, see _use_wino);
+        # fp32 engine: `fm`, `c2` and `cv` (3x3, one source) run as Winograd F(2x2,3x3) (`pfk_conv2d_wino_f32`, see _use_wino), the
+        # SepConvGRU's per-iteration `zr*` / `q*` as 1-D Winograd F(4,5) (`pfk_conv1d_wino_f32`, see _use_wino1d);
         # False = every convolution on `pfk_conv2d_f32` (same-build A/B, tests)
         self.winograd = True
         self.pack(params)
@@ -223,6 +240,10 @@ class UpdateEngine:
                 wzr = torch.cat([wz, wr], 0)
                 w[f"zr{sfx}.w"] = pk(wzr, rest)
                 w[f"q{sfx}.w"] = pk(wq, rest)
+                if self.nsplit == 0 and not self.b16 and (kh, kw) in ((1, 5), (5, 1)) and rest[1][2] % 8 == 0 and Ch % 8 == 0:
+                    # F(4,5)-transformed twins of the per-iteration gate convolutions (U = G g, once per pack; see _use_wino1d)
+                    w[f"zr{sfx}.w1d"] = pack_wino1d_weight(wzr, rest)
+                    w[f"q{sfx}.w1d"] = pack_wino1d_weight(wq, rest)
                 w[f"zrc{sfx}.w"] = pk(wzr, [(Ch, Ci, Ci)])
                 w[f"zrc{sfx}.b"] = torch.cat([bz, br]).contiguous()
                 w[f"qc{sfx}.w"] = pk(wq, [(Ch, Ci, Ci)])
@@ -511,7 +532,10 @@ class UpdateEngine:
         # a stream-K workspace belongs to ONE stream: `workspace` = True (the main chain's), a branch's own tensor, or False
         # (none: plain tile grid)
         ws = self.workspace if workspace is True else (workspace if isinstance(workspace, torch.Tensor) else None)
-        if self._use_wino(key, B * H * W, cout):
+        if self._use_wino1d(key, B * H * W):
+            self.ops.conv2d_wino1d(srcs, B, H, W, kh, kw, self.w[key + ".w1d"], self.w.get(key + ".b"), cout, epi, relu, scale, out,
+                                   h, z, rh, residual)
+        elif self._use_wino(key, B * H * W, cout):
             self.ops.conv2d_wino(srcs[0], B, H, W, self.w[key + ".ww"], self.w.get(key + ".b"), cout, relu, scale, out, cout_active)
         elif self.b16:
             # K8b: z|r reads h from the bf16 twin (r * h is rounded to bf16 anyway), q updates the fp32 h and mirrors it
@@ -535,6 +559,14 @@ class UpdateEngine:
         pixels x ceil(cout / 64) >= WINO_MIN_WORK.  The rule reads the key and the launch shape only — never the schedule mode — so
         serial, forked, captured, grouped and dead-work-skip forwards launch the same kernel for each of them and agree bit for bit."""
         return self.winograd and pixels * ((cout + 63) // 64) >= WINO_MIN_WORK and (key + ".ww") in self.w
+
+    def _use_wino1d(self, key: str, pixels: int) -> bool:
+        """`pfk_conv1d_wino_f32` for the per-iteration `zr*` / `q*` launches of the SepConvGRU (their F(4,5) weights exist on the fp32
+        engine with the context term hoisted only, and only where the hidden width and the motion slice behind the context are
+        multiples of 8 channels, the kernel's K-step — raft, gma, ccmr, ms_raft_plus; any other spec stays on the direct kernel, see
+        pack) from WINO1D_MIN_PIXELS up.  Like `_use_wino` the rule reads the key and
+        the launch shape only, never the schedule."""
+        return self.winograd and pixels >= WINO1D_MIN_PIXELS and (key + ".w1d") in self.w
 
     def motion(self, corr_pm: torch.Tensor) -> None:
         """BasicMotionEncoder / SmallMotionEncoder (update.py:104-112 / :85-91) into its hx slice; `flow` must already be in hx."""
