@@ -283,7 +283,8 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
 /* Winograd F(2x2,3x3) form of pfk_conv2d_f32 for 3x3 stride-1 convolutions (fp32 MFMA, fp32 accumulate): 16 GEMMs over the
  * transformed input, 2.25x fewer products than the direct form.  Supported: one source with channels % 32 == 0, kh = kw = 3,
  * stride 0 or 1, the LINEAR epilogue without residual or relu_after_residual, `cout_active` (0, >= cout, or a multiple of 64:
- * exactly the bits the full launch gives those channels).  Anything else returns PFK_ERR_UNSUPPORTED.  `workspace` and
+ * exactly the bits the full launch gives those channels), source, output (and residual) spans below 2 GB from their pointers
+ * (32-bit byte offsets).  Anything else returns PFK_ERR_UNSUPPORTED.  `workspace` and
  * `cout_split` are ignored (one schedule, no workspace: safe under graph capture).  Results differ from pfk_conv2d_f32 by fp32
  * rounding (other products, other order); the same inputs give the same bits on every run.
  * d->weight = the transformed weight, pfk_conv_wino_weight_floats(cin, cout) floats, 16-byte aligned:

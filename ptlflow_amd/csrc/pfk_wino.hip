@@ -23,10 +23,20 @@
 // the copy of K-step k + 1 lands while the MFMAs of k run.  Both the DMA pieces and the tap loads of k + 1 are issued BETWEEN the
 // MFMAs of k, one piece or two taps per component.  The barriers are raw s_barrier with explicit counted waits (a
 // __syncthreads() would drain the LDS-DMA in flight): vmcnt(0) + barrier before a buffer is read, lgkmcnt(0) + barrier before
-// sV and the other buffer are written again.  80 KB LDS, 188 registers: two blocks per CU, which fill its LDS.
+// sV and the other buffer are written again.  80 KB LDS, 192 registers: two blocks per CU, which fill its LDS.
 //
 // Epilogue: an MFMA 16x16 accumulator gives a lane four rows (tiles) of one column, at the same place in every component, so
-// A^T m A is lane-local; then PFK_EPI_LINEAR's bias, NaN-propagating relu, scale.  A column's K order and transforms do not
+// A^T m A is lane-local.  From that layout a store is a 64-byte piece per 16 lanes and every output needs its own pixel address, so
+// the wave parks its 64 pixels (16 tiles x 4 outputs) x 32 columns of A^T m A in the LDS the loop is done with and walks them as
+// rows: a lane takes 4 consecutive columns of one pixel, 8 lanes a 128-byte row piece, one 16-byte store each; the residual form
+// requests its 8 row pieces per lane before it parks.  Then PFK_EPI_LINEAR's bias, NaN-propagating relu, scale (residual form: one
+// fma onto the residual, second relu), in the order and rounding of the first version: same bits.  Pixel addresses come from a table
+// of byte offsets, 4 per tile, that the staging role writes once per block from the (b, ty, tx) its prologue divided out: no
+// division, no 64-bit multiply and no branch per output.  Predication: stores and residual loads go through buffer descriptors of
+// `out` / `residual` with 32-bit offsets (the launcher refuses spans of 2 GB and more), and a lane without work — a tile past the
+// end, a pixel past H or W, a column from cout on — carries an out-of-range offset, which the hardware drops (loads: zero).
+// Where rows do not take 16-byte pieces (out + out_coff or residual not 16-byte aligned, a row stride % 4 != 0) and in a wave whose
+// 32 columns reach past cout (cout 126), the same walk stores its 4 columns as dwords.  A column's K order and transforms do not
 // depend on which other columns are in the launch: `cout_active` launches fewer column blocks and gives the full launch's bits.
 #include "pfk_gemm.h"
 
@@ -57,9 +67,19 @@ struct WinoArgs {
   int ncb;                       // column blocks launched
   int relu; float scale;
   float* out; int out_ld, out_coff;
+  unsigned out_bytes;            // writable bytes from out (the last pixel's last column)
   const float* res; int res_ld;  // residual rows [pixel][res_ld], column n (conv_gemm_wino_f32_kernel<true> only)
+  unsigned res_bytes;            // readable bytes from res
   int relu2;                     // relu after the residual add
+  int vec;                       // the rows of out (and res) take 16-byte pieces: 16-byte aligned, row strides % 4 == 0
 };
+
+// The epilogue's entry of one of the block's 32 tiles, made once by the staging role: bit 31 the tile exists, bit 30 / 29 its second
+// output row / column lies inside the image, the low bits its first output pixel (B * H * W < 2^24: the launcher's 32-bit byte offsets).
+constexpr unsigned T_OK = 0x80000000u, T_ROW2 = 0x40000000u, T_COL2 = 0x20000000u, T_PIX = 0x1fffffffu;
+// A wave's parking area for A^T m A: 64 pixels (16 tiles x 4 outputs) x 32 columns, 16 floats of padding behind every 16 pixels (the
+// four tile groups kq of the accumulator layout write different banks; the row walk reads 1 KB runs)
+constexpr int ESZ = 64 * 32 + 4 * 16;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
@@ -116,8 +136,75 @@ __device__ __forceinline__ void wino_mfma(const lfloat* aV, const lfloat* aU, co
   }
 }
 
+typedef __attribute__((address_space(3))) unsigned lunsigned;
+typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
+
+// Epilogue, row walk (see the kernel).  The lane's 8 pixels are output e = (lane >> 3) & 3 of the wave's tiles 2 * i + (lane >> 5),
+// i = 0..7, its 4 columns start at n0; tT = the offset table at (e, the wave's tile lane >> 5).  Byte offsets of the 8 row pieces in
+// `out` (OOB and beyond for a pixel that does not exist: the buffer store drops it) and, RES, the residual's 8 pieces, all requested
+// here, before the first is used.  VEC: 16-byte pieces; else the 4 columns one by one, those from cout on read as zero.
+template <bool RES, bool VEC>
+__device__ __forceinline__ void wino_epi_request(const WinoArgs& a, const lunsigned* tT, int n0, unsigned (&oo)[8], f32x4 (&r4)[8]) {
+  unsigned ro[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    oo[i] = tT[2 * i] + (unsigned)(a.out_coff + n0) * 4u;
+    if constexpr (RES) ro[i] = tT[4 * WT + 2 * i] + (unsigned)n0 * 4u;
+  }
+  if constexpr (RES) {
+    const __amdgpu_buffer_rsrc_t rr = rsrc_n(a.res, a.res_bytes);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if constexpr (VEC) {
+        r4[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, ro[i], 0, 0));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          r4[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, n0 + j < a.cout ? ro[i] + 4u * j : OOB, 0, 0));
+      }
+    }
+  }
+}
+
+// Epilogue, row walk: the lane's 8 row pieces from the wave's parking area (rE = the lane's pixel 0 and column there), then the first
+// version's arithmetic in its order and rounding: + bias, NaN-propagating relu, x scale (RES: one fma with the residual as the addend,
+// then the second relu); a relu that is off compares with -inf and keeps every value.
+template <bool RES, bool VEC>
+__device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* rE, int n0, const unsigned (&oo)[8], const f32x4 (&r4)[8]) {
+  const __amdgpu_buffer_rsrc_t ro = rsrc_n(a.out, a.out_bytes);
+  const __amdgpu_buffer_rsrc_t rbias = rsrc_n(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
+  float bias4[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bias4[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, (unsigned)(n0 + j) * 4u, 0, 0));
+  const float lo = a.relu ? 0.f : -__builtin_inff(), lo2 = a.relu2 ? 0.f : -__builtin_inff();
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x4 y = *(const lf32x4*)(rE + i * 256 + (i >> 1) * 16);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float t = y[j] + bias4[j];
+      t = (t < lo) ? lo : t;
+      if constexpr (RES) {
+        t = __builtin_fmaf(t, a.scale, r4[i][j]);
+        t = (t < lo2) ? lo2 : t;
+      } else {
+        t *= a.scale;
+      }
+      v[j] = t;
+    }
+    if constexpr (VEC) {
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, (f32x4{v[0], v[1], v[2], v[3]})), ro, oo[i], 0, 0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[j]), ro, n0 + j < a.cout ? oo[i] + 4u * j : OOB, 0, 0);
+    }
+  }
+}
+
 // RES: the residual-block epilogue of pfk_conv2d_wino_res_f32 (v = residual + v, then the block's last relu); the instantiation
-// without it is pfk_conv2d_wino_f32's kernel, unchanged.
+// without it is pfk_conv2d_wino_f32's kernel.
 template <bool RES>
 __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoArgs a) {
   // (one array, U first) 2 x 32 KB of U + 16 KB of V: two blocks fill a CU's LDS
@@ -135,11 +222,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
   // ---- staging role: tile lt, channel cc of the K-step
   const int lt = tid >> 3, cc = tid & 7;
   unsigned voff[16];
+  unsigned tinfo;   // the tile's entry of the epilogue's table
   {
     const int g = t0 + lt;
     const bool tok = g < a.ntiles;
     const int b = g / a.tpi, r = g - b * a.tpi;
     const int ty = r / a.tw, tx = r - ty * a.tw;
+    tinfo = tok ? (T_OK | (2 * ty + 1 < a.H ? T_ROW2 : 0u) | (2 * tx + 1 < a.W ? T_COL2 : 0u) | (unsigned)((b * a.H + 2 * ty) * a.W + 2 * tx)) : 0u;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -202,50 +291,63 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
 
-  // ---- epilogue: lane holds tiles 4*kq + r (r = 0..3) of column rl in every component
-  typedef __attribute__((address_space(1))) float gfloat;
-  gfloat* const outp = (gfloat*)a.out;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int n = cb * WN + wc * 32 + c * 16 + rl;
-    const bool nok = n < a.cout;
-    const float bias = (a.bias != nullptr && nok) ? a.bias[n] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int g = t0 + wt * 16 + kq * 4 + r;
-      float m[16];
-#pragma unroll
-      for (int x = 0; x < 16; ++x) m[x] = acc[x][c][r];
-      float s0[4], s1[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s0[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
-        s1[j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
-      }
-      float y[4];
-      y[0] = s0[0] + s0[1] + s0[2];
-      y[1] = s0[1] - s0[2] - s0[3];
-      y[2] = s1[0] + s1[1] + s1[2];
-      y[3] = s1[1] - s1[2] - s1[3];
-      if (!nok || g >= a.ntiles) continue;
-      const int b = g / a.tpi, rr = g - b * a.tpi;
-      const int ty = rr / a.tw, tx = rr - ty * a.tw;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int oy = 2 * ty + (e >> 1), ox = 2 * tx + (e & 1);
-        if (oy >= a.H || ox >= a.W) continue;
-        float v = y[e] + bias;
-        if (a.relu) v = (v < 0.f) ? 0.f : v;   // NaN-propagating like torch.relu
-        v *= a.scale;
-        const long long p = ((long long)b * a.H + oy) * a.W + ox;
-        if constexpr (RES) {
-          v = a.res[p * a.res_ld + n] + v;
-          if (a.relu2) v = (v < 0.f) ? 0.f : v;
-        }
-        outp[p * a.out_ld + a.out_coff + n] = v;
-      }
+  // ---- epilogue.  Every wave is past the loop's last barrier: sU and sV are free.
+  // The offset table: for each of the block's 32 tiles and its 4 outputs e = 2 * row + column, the byte offset of that pixel's row in
+  // out (then in the residual), OOB where the tile or the pixel does not exist.  The staging role's threads cc = e of a tile write it
+  // from the entry they kept; one more barrier hands it to the MFMA role's waves.  All divisions were the prologue's.
+  lfloat* const sE = (lfloat*)smem + wid * ESZ;
+  lunsigned* const sT = (lunsigned*)((lfloat*)smem + 4 * ESZ);   // [out, residual][e][tile]
+  static_assert(4 * ESZ + 8 * WT <= 2 * UIMG + 16 * WT * WK, "parking areas and offset table must fit into the loop's LDS");
+  {
+    const unsigned need = T_OK | ((cc & 2) ? T_ROW2 : 0u) | ((cc & 1) ? T_COL2 : 0u);
+    const bool ok = (tinfo & need) == need;
+    const unsigned pix = (tinfo & T_PIX) + (unsigned)(((cc >> 1) & 1) * a.W + (cc & 1));
+    const unsigned po = ok ? pix * (unsigned)a.out_ld * 4u : OOB;
+    const unsigned pr = ok ? pix * (unsigned)a.res_ld * 4u : OOB;
+    if (cc < 4) {
+      sT[cc * WT + lt] = po;
+      if constexpr (RES) sT[(4 + cc) * WT + lt] = pr;
     }
   }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+  // row-walk role: pixel li = 8 * i + prow of the wave's 64 (tile li >> 2, output li & 3), 4 columns from c4
+  const int prow = lane >> 3, c4 = (lane & 7) * 4;
+  const int n0 = cb * WN + wc * 32 + c4;
+  const lunsigned* const tT = sT + (prow & 3) * WT + wt * 16 + (lane >> 5);
+  // (wave-uniform) 16-byte pieces where the launcher found the rows aligned and the wave's 32 columns all exist
+  const bool vec = a.vec && cb * WN + wc * 32 + 32 <= a.cout;
+  unsigned oo[8];
+  f32x4 r4[8];
+  if (vec) wino_epi_request<RES, true>(a, tT, n0, oo, r4);
+  else wino_epi_request<RES, false>(a, tT, n0, oo, r4);
+
+  // MFMA role: the lane holds tiles 4*kq + r (r = 0..3) of columns c*16 + rl in every component; A^T m A is lane-local.  Parked at
+  // [pixel li = (4*kq + r)*4 + e][column] of the wave's own area (no barrier: the wave's own LDS operations stay in order)
+  {
+    lfloat* const pE = sE + kq * (16 * 32 + 16) + rl;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float m[16];
+#pragma unroll
+        for (int x = 0; x < 16; ++x) m[x] = acc[x][c][r];
+        float s0[4], s1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s0[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
+          s1[j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
+        }
+        pE[(r * 4 + 0) * 32 + c * 16] = s0[0] + s0[1] + s0[2];
+        pE[(r * 4 + 1) * 32 + c * 16] = s0[1] - s0[2] - s0[3];
+        pE[(r * 4 + 2) * 32 + c * 16] = s1[0] + s1[1] + s1[2];
+        pE[(r * 4 + 3) * 32 + c * 16] = s1[1] - s1[2] - s1[3];
+      }
+  }
+  const lfloat* const rE = sE + prow * 32 + c4;
+  if (vec) wino_epi_store<RES, true>(a, rE, n0, oo, r4);
+  else wino_epi_store<RES, false>(a, rE, n0, oo, r4);
 }
 
 // ---- K4w1: the SepConvGRU's 1x5 / 5x1 gate convolutions as 1-D Winograd F(4,5) -------------------------------------------------
@@ -655,6 +757,10 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   const long long src_bytes = ((M - 1) * s.ld + s.channels) * 4;
   const long long wfloats = pfk_conv_wino_weight_floats(s.channels, d->cout);
   if (M * s.ld * 4 >= 0x7fffffffLL || wfloats * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
+  // the epilogue stores (and reads the residual) through buffer descriptors with 32-bit byte offsets from `out` (`residual`)
+  const long long out_bytes = ((M - 1) * d->out_ld + d->out_coff + d->cout) * 4;
+  const long long res_bytes = res ? ((M - 1) * d->residual_ld + d->cout) * 4 : 0;
+  if (out_bytes >= 0x7fffffffLL || res_bytes >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
   int ncb = (d->cout + WN - 1) / WN;
   if (d->cout_active > 0 && d->cout_active < d->cout) {
     if (d->cout_active & (WN - 1)) return PFK_ERR_UNSUPPORTED;
@@ -675,10 +781,11 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   a.cout = d->cout;
   a.ncb = ncb;
   a.relu = d->relu ? 1 : 0; a.scale = d->scale;
-  a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
+  a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff; a.out_bytes = (unsigned)out_bytes;
+  a.vec = pfk_aligned16(d->out + d->out_coff) && !(d->out_ld & 3) && (!res || (pfk_aligned16(d->residual) && !(d->residual_ld & 3)));
   if (res) {
     if (d->cout_active > 0 && d->cout_active < d->cout) return PFK_ERR_UNSUPPORTED;
-    a.res = d->residual; a.res_ld = d->residual_ld; a.relu2 = d->relu_after_residual ? 1 : 0;
+    a.res = d->residual; a.res_ld = d->residual_ld; a.res_bytes = (unsigned)res_bytes; a.relu2 = d->relu_after_residual ? 1 : 0;
     hipLaunchKernelGGL(conv_gemm_wino_f32_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   } else {
     hipLaunchKernelGGL(conv_gemm_wino_f32_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), a);

@@ -36,7 +36,9 @@ _SMALL_BLOCKS = (("layer1.0", 32, 32, 1), ("layer1.1", 32, 32, 1), ("layer2.0", 
 EPS = 1e-5
 # Winograd rule of the fp32 BasicEncoder engine: width -> the fewest pixels (B * H * W of the launch) at which `pfk_conv2d_wino_f32` /
 # `pfk_conv2d_wino_res_f32` measured faster than `pfk_conv2d_f32` in both forms (scripts/wino_res_bench.py --encoder raft, table in
-# DESIGN.md §3 K9–K11, profiles/r08_a_winograd_lds_dma.md); a width or a size that was not measured keeps the direct kernel
+# DESIGN.md §3 K9–K11, profiles/r08_a_winograd_lds_dma.md; re-measured with the row-walk epilogue, profiles/r14_a_wino_epilogue.md §2:
+# every entry wins by more — 64 at one image 1.76x / 1.73x, 96 1.98x / 1.99x, 128 at two 1.62x / 1.58x — and 128 at one image, 1.06x,
+# stays below the line); a width or a size that was not measured keeps the direct kernel
 WINO_MIN_PIXELS: Dict[int, int] = {64: 218 * 512, 96: 109 * 256, 128: 2 * 55 * 128}     # 436 x 1024 frames: all it was measured on
 
 

@@ -110,8 +110,20 @@ def small_spec(corr_levels: int = 4, corr_radius: int = 3) -> UpdateSpec:
 #   batch 8: fm 540.2 -> 292.7 us, c2 404.6 -> 231.4 us, cv 267.1 -> 157.5 us
 # Below 28 160 the grid leaves most CUs idle: cv at batch 1 ties with the direct kernel's stream-K schedule, c2 at batch 1 gains 1.29x,
 # but at 21120 it sits on the lower bound that the engine test keeps for this value, so the line stays above both.  The full launch's
-# cout decides (a `cout_active` launch takes the same kernel as its full form).
+# cout decides (a `cout_active` launch takes the same kernel as its full form).  With the row-walk epilogue the batch-8 Winograd
+# figures are fm 275.8, c2 216.4, cv 155.2 us (profiles/r14_a_wino_epilogue.md §2); the smaller batches were not re-measured and the
+# value stands.
 WINO_MIN_WORK = 28160
+
+# `f2` (convf2, 3x3, f1 -> 64: one column block) has a floor of its own, in PIXELS (B*H*W).  In isolation (scripts/wino_bench.py --keys
+# f2 --rounds 3, MI355X, the direct kernel with the engine's stream-K workspace, median of three alternating rounds of 40 launches, us,
+# max - min in brackets: direct, Winograd; profiles/r14_a_wino_epilogue.md §3):
+#   2x55x128 (14080)   26.7 [1.2] -> 25.3 [0.7]      4x55x128 (28160)   45.0 [1.2] -> 28.0 [2.2]
+#   8x55x128 (56320)   79.2 [5.6] -> 42.8 [1.6]      8x47x156 (58656)   89.8 [6.4] -> 46.5 [3.3]
+# 28160 is the smallest measured size that wins clearly (1.61x).  At 14080 (220 blocks on 512 resident slots) the 1.4 us are inside the
+# two kernels' spreads taken together, and grids below SMALL_GRID_PIXELS run `f2` inside the grouped launch, which the isolated
+# direct launch does not stand for: nothing below 28160 takes Winograd.
+WINO_F2_MIN_PIXELS = 28160
 
 # 1-D Winograd rule (`_use_wino1d`): the SepConvGRU's per-iteration z|r and q launches run as F(4,5) (`pfk_conv1d_wino_f32`) where
 # B*H*W >= WINO1D_MIN_PIXELS (and the transformed weights exist: fp32 engine, context hoisted, source widths multiples of 8, see pack).
@@ -290,7 +302,7 @@ class UpdateEngine:
         if self.nsplit == 0 and not self.b16:
             # Winograd-transformed twins of the update block's 3x3 stride-1 single-source convolutions (U = G g G^T, once per pack)
             fm = torch.cat([g("flow_head.conv1.weight"), g("mask.0.weight")], 0) if s.has_mask else g("flow_head.conv1.weight")
-            wino = {"cv": g("encoder.conv.weight"), "fm": fm}
+            wino = {"cv": g("encoder.conv.weight"), "fm": fm, "f2": g("encoder.convf2.weight")}
             if s.c2:
                 wino["c2"] = g("encoder.convc2.weight")
             for key, wt in wino.items():
@@ -556,9 +568,14 @@ class UpdateEngine:
 
     def _use_wino(self, key: str, pixels: int, cout: int) -> bool:
         """`pfk_conv2d_wino_f32` for `fm`, `c2`, `cv` (their transformed weights exist on the fp32 engine only, see pack) where
-        pixels x ceil(cout / 64) >= WINO_MIN_WORK.  The rule reads the key and the launch shape only — never the schedule mode — so
-        serial, forked, captured, grouped and dead-work-skip forwards launch the same kernel for each of them and agree bit for bit."""
-        return self.winograd and pixels * ((cout + 63) // 64) >= WINO_MIN_WORK and (key + ".ww") in self.w
+        pixels x ceil(cout / 64) >= WINO_MIN_WORK, and for `f2` where pixels >= WINO_F2_MIN_PIXELS.  The rule reads the key and the
+        launch shape only — never the schedule mode — so serial, forked, captured, grouped and dead-work-skip forwards launch the same
+        kernel for each of them and agree bit for bit (`motion_grouped` takes `f2` out of its grouped launch where the rule holds)."""
+        if not self.winograd or (key + ".ww") not in self.w:
+            return False
+        if key == "f2":
+            return pixels >= WINO_F2_MIN_PIXELS
+        return pixels * ((cout + 63) // 64) >= WINO_MIN_WORK
 
     def _use_wino1d(self, key: str, pixels: int) -> bool:
         """`pfk_conv1d_wino_f32` for the per-iteration `zr*` / `q*` launches of the SepConvGRU (their F(4,5) weights exist on the fp32
@@ -617,6 +634,10 @@ class UpdateEngine:
         keys = ["c1", "f2"]
         relu, scale = [1, 1], [1.0, 1.0]
         outs = [self.cor1 if s.c2 else self.corflo[:, : s.c1], self.corflo[:, cor_c: cor_c + s.f2]]
+        # where `f2` takes the Winograd kernel it does so in every schedule: it leaves the group and goes through `_conv` below
+        f2_alone = self._use_wino("f2", B * H * W, s.f2)
+        if f2_alone:
+            srcs, ks, keys, relu, scale, outs = srcs[:1], ks[:1], keys[:1], relu[:1], scale[:1], outs[:1]
         if prev_mask:
             srcs.append(self.fm[:, s.fh_hidden:]); ks.append(1); keys.append("mk"); relu.append(0); scale.append(0.25); outs.append(self.mask)
         t0 = self.tic() if self.profile is not None else None
@@ -629,6 +650,8 @@ class UpdateEngine:
                          for o, k, kk in zip(outs, ks, keys)))
         if s.c2:
             self._conv([self.cor1], 3, 3, "c2", s.c2, out=self.corflo[:, : s.c2])
+        if f2_alone:      # (behind c2: the serial schedule's order of launches, which scripts/callsite_stats.py counts by position)
+            self._conv([self.flo1], 3, 3, "f2", s.f2, out=self.corflo[:, cor_c: cor_c + s.f2])
         self.motion_join()
 
     def motion_join(self) -> None:
