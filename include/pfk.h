@@ -35,6 +35,7 @@
  *   pfk_corr_lookup_bwd_f32 / pfk_corr_volume_bwd_f32 / pfk_convex_upsample_bwd_f32
  *                         what torch.autograd runs for corr.py:29-64 and raft.py:112-123 in a training step (train.py;
  *                         gradients reach fmap1 / fmap2 only, `coords` is detached at raft.py:171)
+ *   pfk_convex_upsample_info_bwd_pm_f32  what torch.autograd runs for sea_raft.py:147-163 in a training step (train_sea.py)
  * The native plug-in precedent in the reference is alt_cuda_corr
  * (ptlflow/utils/external/alt_cuda_corr/correlation.cpp:23-54: pybind forward/backward on raw
  * contiguous CUDA tensors); this header is the same kind of boundary, minus torch.
@@ -189,6 +190,21 @@ long long pfk_convex_upsample_bwd_workspace_bytes(int B, int H, int W);
 int pfk_convex_upsample_bwd_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, const float* grad_out,
                                 float* grad_mask, int grad_mask_ld, float* grad_flow, void* workspace, long long workspace_bytes,
                                 int B, int H, int W, pfk_stream_t stream);
+
+/* ---- backward of pfk_convex_upsample_info_pm_f32 (SEARAFT.upsample_data, sea_raft/sea_raft.py:147-163), fp32, pixel-major -----
+ * flow_pm / info_pm / mask as the forward reads them (columns 0..1, 0..n_info-1, 0..575 of their rows; 0 <= n_info <= 8, info_pm
+ * and grad_info_pm may be NULL when n_info == 0); grad_flow_up [B][2][8H][8W], grad_info_up [B][n_info][8H][8W] or NULL (= zero)
+ * -> grad_mask [M][grad_mask_ld] (576 columns written), grad_flow_pm[p*grad_flow_ld + 0..1] and grad_info_pm[p*grad_info_ld +
+ * 0..n_info-1]: rows with their own ld, so both may point into one [M][8] buffer (columns 0..1 and 2..5: the gradient of
+ * flow_head's output).  mask, grad_mask, grad_flow_up, grad_info_up 16-byte aligned, mask_ld % 4 == 0 and grad_mask_ld % 4 == 0
+ * (PFK_ERR_ALIGNMENT otherwise).  workspace: pfk_convex_upsample_info_bwd_workspace_bytes(B, H, W, n_info) bytes
+ * (B*H*W*9*(2 + n_info) floats).  Deterministic: no atomics, fixed summation order. */
+long long pfk_convex_upsample_info_bwd_workspace_bytes(int B, int H, int W, int n_info);
+int pfk_convex_upsample_info_bwd_pm_f32(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
+                                        const float* mask, int mask_ld, const float* grad_flow_up, const float* grad_info_up,
+                                        float* grad_mask, int grad_mask_ld, float* grad_flow_pm, int grad_flow_ld, float* grad_info_pm,
+                                        int grad_info_ld, void* workspace, long long workspace_bytes, int B, int H, int W,
+                                        pfk_stream_t stream);
 
 /* ---- K4-K6: "same"-padded convolution (stride 1, or s for the encoders) as an implicit GEMM on fp32 MFMA ----
  * out[p][co] = epilogue( bias[co] + sum_{s, ky, kx, c} src[s][p + (ky-kh/2)*W + (kx-kw/2)][c]

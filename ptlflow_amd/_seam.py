@@ -49,6 +49,19 @@ def eligible(tensors, params=(), dtypes=None, autocast=None) -> bool:
     return not (torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)))
 
 
+def carries_grad(tensors, params=()) -> bool:
+    """A native fp32 training path may serve a call on `tensors` (the rule of `PfkSeaRaftUpdateBlock.trains`): CUDA fp32 tensors on
+    one device, grad mode on with a tensor or a parameter that requires grad, outside cuda autocast."""
+    if not torch.is_grad_enabled() or torch.is_autocast_enabled("cuda"):
+        return False
+    t0 = tensors[0]
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == t0.device for t in tensors):
+        return False
+    if not all(p.dtype == torch.float32 and p.device == t0.device for p in params):
+        return False
+    return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)
+
+
 def pixel_rows(t: torch.Tensor, dtype: torch.dtype, align: int = 1, dense: bool = False) -> Optional[torch.Tensor]:
     """The [B*H*W, C] pixel-major rows of the NCHW tensor `t` as a view, or None: `t` must be of `dtype`, its pixels one row stride
     apart with unit channel stride (channels-last strides, or a channel slice of such a buffer; `dense`: no slice), and the data

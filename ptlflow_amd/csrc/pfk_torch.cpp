@@ -705,6 +705,33 @@ void convex_upsample_bwd(const Tensor& flow, const Tensor& mask, const Tensor& g
   check_ok(pfk_convex_upsample_bwd_f32(fp, flow_ld, m.f32(), m.ld, g.ptr, gm.f32(), gm.ld, gf, ws.second, need, g.B, g.H, g.W, cur_stream()), op);
 }
 
+// backward of convex_upsample_info_pm (fp32 mask): row views as the forward's, grad_flow_up [B, 2, 8H, 8W], grad_info_up
+// [B, n, 8H, 8W] or None (= zero), n = grad_info_pm's columns; grad_flow_pm [M, 2] / grad_info_pm [M, n] may be slices of one buffer
+void convex_upsample_info_bwd(const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask, const Tensor& grad_flow_up,
+                              const c10::optional<Tensor>& grad_info_up, Tensor grad_mask, Tensor grad_flow_pm, Tensor grad_info_pm) {
+  OpScope scope(mask);
+  const char* op = "convex_upsample_info_bwd";
+  const Up8 g = up8(op, grad_flow_up, "grad_flow_up");
+  const int64_t M = g.rows();
+  const Rows gi = rows(op, grad_info_pm, "grad_info_pm", F32).expect(M, AtLeast{0});
+  const int64_t n = gi.cols;
+  TORCH_CHECK(n <= 8, op, ": at most 8 info channels, grad_info_pm has ", n);
+  const Rows f = rows(op, flow_pm, "flow_pm", F32).expect(M, AtLeast{2});
+  const Rows i = rows(op, info_pm, "info_pm", F32).expect(M, AtLeast{n});
+  const Rows m = rows(op, mask, "mask", F32).expect(M, 576), gm = rows(op, grad_mask, "grad_mask", F32).expect(M, 576);
+  const Rows gf = rows(op, grad_flow_pm, "grad_flow_pm", F32).expect(M, 2);
+  const Ptr gu = dense(op, grad_info_up, "grad_info_up [B, n, 8H, 8W]", F32, n * M * 64);
+  TORCH_CHECK(!grad_info_up.has_value() || (grad_info_up->dim() == 4 && grad_info_up->size(0) == g.B && grad_info_up->size(1) == n &&
+                                            grad_info_up->size(2) == 8 * g.H && grad_info_up->size(3) == 8 * g.W),
+              op, ": grad_info_up must be [B, n, 8H, 8W] contiguous with n = grad_info_pm's columns");
+  const long long need = pfk_convex_upsample_info_bwd_workspace_bytes(g.B, g.H, g.W, (int)n);
+  const auto ws = byte_workspace(need, mask);
+  check_ok(pfk_convex_upsample_info_bwd_pm_f32(f.f32(), f.ld, i.f32(), i.ld, (int)n, m.f32(), m.ld, g.ptr, gu.ptr ? gu.f32() : nullptr,
+                                               gm.f32(), gm.ld, gf.f32(), gf.ld, gi.f32(), gi.ld, ws.second, need, g.B, g.H, g.W,
+                                               cur_stream()),
+           op);
+}
+
 void nchw_to_pm(const Tensor& in, Tensor out) {
   OpScope scope(in);
   const float* ip = dense("nchw_to_pm", in, "inp", F32).f32();
@@ -1108,6 +1135,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("corr_lookup_bwd(Tensor(a!)[] grad_levels, int[] lvl_h, int[] lvl_w, Tensor coords, int radius, Tensor grad_out) -> ()");
   m.def("corr_volume_bwd(Tensor dC, int N2, Tensor f1, Tensor f2cm, float scale, Tensor(a!) df1, bool accumulate, Tensor(b!) df2) -> ()");
   m.def("convex_upsample_bwd(Tensor flow, Tensor mask, Tensor grad_out, Tensor(a!) grad_mask, Tensor(b!) grad_flow) -> ()");
+  m.def("convex_upsample_info_bwd(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor grad_flow_up, Tensor? grad_info_up, "
+        "Tensor(a!) grad_mask, Tensor(b!) grad_flow_pm, Tensor(c!) grad_info_pm) -> ()");
   m.def("nchw_to_pm(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_nchw(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_cm(Tensor inp, Tensor(a!) out) -> ()");
@@ -1150,6 +1179,7 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("corr_lookup_bwd", &corr_lookup_bwd);
   m.impl("corr_volume_bwd", &corr_volume_bwd);
   m.impl("convex_upsample_bwd", &convex_upsample_bwd);
+  m.impl("convex_upsample_info_bwd", &convex_upsample_info_bwd);
   m.impl("nchw_to_pm", &nchw_to_pm);
   m.impl("pm_to_nchw", &pm_to_nchw);
   m.impl("pm_to_cm", &pm_to_cm);

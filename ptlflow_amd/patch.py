@@ -15,7 +15,8 @@ What gets replaced:
 * SEA-RAFT only, opt-in — ``accelerate(model, sea_raft_update=...)`` (update block, heads, ``upsample_data``; sea_update.py) and
   ``accelerate(model, sea_raft_encoders=...)`` (``ResNetFPN`` ``fnet`` / ``cnet`` and ``init_conv``; sea_encoder.py);
 * seam B5 — ``model.upsample_flow`` (raft.py:112-123, a method the loop calls every iteration) is shadowed on the instance by
-  the convex-upsampling kernel after a behaviour probe (`_UpsampleSeam`).
+  the convex-upsampling kernel after a behaviour probe (`_UpsampleSeam`).  ``accelerate(model, train_upsample=True)``: this seam and
+  SEA-RAFT's ``upsample_data`` also serve the calls that carry a gradient graph (forward and backward on the kernels).
 
 Dispatch is by *implementation identity*, never by class name alone: about two dozen ptlflow families call their block
 ``BasicUpdateBlock`` with different layers and ``forward`` signatures (sea_raft/update.py:39-54 is a ConvNeXt stack that
@@ -38,7 +39,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import load_native
-from ._seam import ProbedMethodSeam, WrappedModule, eligible
+from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixel_rows
 from .corr import get_corr_block as _pfk_get_corr_block
 from .encoder import PfkEncoder
 from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
@@ -175,6 +176,16 @@ def _install_sea_raft(model: torch.nn.Module, precision: str = "fp32") -> bool:
     if callable(getattr(model, "upsample_data", None)) and not isinstance(model.__dict__.get("upsample_data"), _UpsampleDataSeam):
         _shadow(model, upsample_data=_UpsampleDataSeam(model.upsample_data, precision))
     return True
+
+
+def _upsample_seam_expected(model: torch.nn.Module, upsample: bool, sea_precision: Optional[str]) -> bool:
+    """an upsampling seam is installed on `model`, or `accelerate` with these options installs one"""
+    d = getattr(model, "__dict__", {})
+    if isinstance(d.get("upsample_flow"), _UpsampleSeam) or isinstance(d.get("upsample_data"), _UpsampleDataSeam):
+        return True
+    if upsample and callable(getattr(model, "upsample_flow", None)):
+        return True
+    return sea_precision is not None and callable(getattr(model, "upsample_data", None)) and match_sea_raft(model) is not None
 
 
 def _shadow(obj, **seams) -> None:
@@ -351,13 +362,18 @@ class _UpsampleSeam(ProbedMethodSeam):
     8x convex upsampling, called once per iteration by the reference's loop, in the reference five torch kernels over a
     [B, 576, h, w] mask (softmax, unfold, multiply, sum, permute-copy).  The replacement is `pfk_convex_upsample_f32`, behind
     the behaviour probe of `ProbedMethodSeam` (a family whose `upsample_flow` does something else — another scale, a different
-    neighbourhood — keeps its own code).  Gradient graphs, CPU tensors, other mask widths and dtypes always take the original."""
+    neighbourhood — keeps its own code).  CPU tensors, other mask widths and dtypes always take the original; so do gradient
+    graphs, unless `train_upsample` is set (`accelerate(model, train_upsample=True)`): then the plain call on two CUDA fp32 tensors
+    with grad mode on, something requiring grad and no autocast runs `train.convex_upsample` (`pfk_convex_upsample_f32` forward,
+    `pfk_convex_upsample_bwd_f32` backward) and is counted in `train_calls`.  The dead-work skip is never active in grad mode."""
 
     refusal = "ptlflow_amd: this model's upsample_flow is not RAFT's 8x convex upsampling; seam B5 keeps the model's own method"
 
     def __init__(self, original):
         super().__init__(original)
         self.skip = None        # `_DeadWorkSkip` shared with seam B3 (accelerate(..., skip_dead_upsample=True)), else None
+        self.train_upsample = False    # `accelerate(train_upsample=True)`: gradient-graph calls run `train.convex_upsample`
+        self.train_calls = 0           # calls served by it
 
     @staticmethod
     def _kernel(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -381,8 +397,16 @@ class _UpsampleSeam(ProbedMethodSeam):
         if kwargs or len(args) != 2 or not (torch.is_tensor(args[0]) and torch.is_tensor(args[1])):
             return self.original(*args, **kwargs)
         flow, mask = args
-        if not (eligible(args, dtypes=(torch.float32,)) and mask.dim() == 4 and mask.shape[1] == 576 and flow.dim() == 4
-                and flow.shape[1] == 2 and self._verdict("ok", flow.device)):
+        shapes = mask.dim() == 4 and mask.shape[1] == 576 and flow.dim() == 4 and flow.shape[1] == 2
+        if self.train_upsample and shapes and flow.shape[0] == mask.shape[0] and flow.shape[2:] == mask.shape[2:] \
+                and carries_grad(args) and self._verdict("ok", flow.device):
+            from .train import convex_upsample
+            self.train_calls += 1
+            rows = pixel_rows(mask, torch.float32)      # PfkUpdateBlock's training mask: a view
+            if rows is None:
+                rows = mask.permute(0, 2, 3, 1).reshape(-1, 576)
+            return convex_upsample(flow, rows)
+        if not (shapes and eligible(args, dtypes=(torch.float32,)) and self._verdict("ok", flow.device)):
             return self.original(flow, mask)
         self.calls += 1
         if self.skip is not None:
@@ -582,7 +606,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
-               sea_raft_train: bool = False) -> torch.nn.Module:
+               sea_raft_train: bool = False, train_upsample: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -617,14 +641,27 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     seams also serve the calls that carry a gradient graph — CUDA fp32 tensors, grad mode on, an input or a parameter that requires
     grad, outside autocast — on the native training path of ptlflow_amd/train_sea.py: the update block (motion
     encoder and ConvNeXt blocks) and the `flow_head` / `upsample_weight` heads on any such ``[B, 128, H, W]`` input, forward and
-    backward, counted in each wrapper's ``train_calls``.  `upsample_data` in a gradient graph stays the model's own method.  Off:
-    such calls reach the model's own modules, as before."""
+    backward, counted in each wrapper's ``train_calls``.  `upsample_data` in a gradient graph stays the model's own method unless
+    ``train_upsample`` is set.  Off: such calls reach the model's own modules, as before.
+    ``train_upsample`` (default False): the upsampling seams — B5 (`upsample_flow`) and SEA-RAFT's `upsample_data` — also serve the
+    plain positional call on CUDA fp32 tensors that carries a gradient graph (grad mode on, something requiring grad, outside
+    autocast, the behaviour probe passed): forward on the inference kernel, backward on `pfk_convex_upsample_bwd_f32` /
+    `pfk_convex_upsample_info_bwd_pm_f32`, counted in the seam's ``train_calls``.  Everything else, and every
+    gradient graph while it is off, goes to the model's own method.  Raises ValueError when the model gets neither seam, and on a
+    SEA-RAFT model unless ``sea_raft_update`` is True or "fp32".  A second call with another value switches the installed seams."""
     from .train import check_precision
     check_precision(train_precision, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
         raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path is fp32), got {sea_raft_update!r}")
     sea_enc_precision = _sea_precision(sea_raft_encoders, "sea_raft_encoders")
+    if train_upsample:
+        if (isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock) or match_sea_raft(model) is not None) \
+                and sea_precision != "fp32":
+            raise ValueError(f"train_upsample=True needs sea_raft_update=True or 'fp32' on a SEA-RAFT model (the training path is fp32), "
+                             f"got {sea_raft_update!r}")
+        if not _upsample_seam_expected(model, upsample, sea_precision):
+            raise ValueError("train_upsample=True: this model gets neither seam B5 (`upsample_flow`) nor SEA-RAFT's `upsample_data` seam")
     load_native()
     mod_name = type(model).__module__
     # registered classes (`class raft(RAFT)`) live in the same module as the implementation
@@ -673,6 +710,9 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
             model.__dict__[_SKIP] = skip
             model.update_block._skip = skip
             model.__dict__["upsample_flow"].skip = skip
+    for name, kind in (("upsample_flow", _UpsampleSeam), ("upsample_data", _UpsampleDataSeam)):
+        if isinstance(model.__dict__.get(name), kind):
+            model.__dict__[name].train_upsample = bool(train_upsample)
     return model
 
 

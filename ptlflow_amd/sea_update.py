@@ -37,7 +37,9 @@ implement — CPU tensors, gradient graphs, other dtypes, autocast — is passed
 
 `accelerate(model, sea_raft_update=True, sea_raft_train=True)` (opt-in, fp32): calls that carry a gradient graph — CUDA fp32, grad mode
 on, an input or a parameter that requires grad, no autocast — run on the differentiable composition of train_sea.py (K12d) instead
-of the wrapped modules, and are counted in `train_calls`.
+of the wrapped modules, and are counted in `train_calls`.  With `train_upsample=True` on top, `upsample_data` in such a graph runs
+`train_sea.upsample_data_train` (the inference kernel forward, `pfk_convex_upsample_info_bwd_pm_f32` backward; K12e) instead of the
+model's own method, counted in the seam's `train_calls`; without it, it stays the model's method.
 """
 from __future__ import annotations
 
@@ -45,7 +47,7 @@ from typing import Dict, Optional
 
 import torch
 
-from ._seam import ProbedMethodSeam, WrappedModule, eligible, pixel_rows
+from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixel_rows
 from .packing import pack_conv_weight
 from .update import EPI_LINEAR, UpdateEngine, UpdateSpec, corr_rows
 
@@ -466,7 +468,9 @@ class _UpsampleDataSeam(ProbedMethodSeam):
     """`model.upsample_data(flow, info, mask)` (sea_raft.py:147-163) shadowed on the instance by `pfk_convex_upsample_info_pm_f32`
     behind the behaviour probe (`ProbedMethodSeam`, like seam B5's; a bf16 mask has a probe of its own, `ok16`).  Pixel-major rows
     are read without a copy where the strides allow (the channels-last `0.25 * upsample_weight(net)` and the info slice of
-    `flow_head(net)`)."""
+    `flow_head(net)`).  A call that carries a gradient graph goes to the model's own method, or — `train_upsample`, fp32 seams only:
+    three CUDA fp32 tensors, grad mode on, something requiring grad, outside autocast, the probe passed — to
+    `train_sea.upsample_data_train` (`train_calls`)."""
 
     refusal = "ptlflow_amd: this model's upsample_data is not SEA-RAFT's; it keeps the model's own method"
 
@@ -474,6 +478,8 @@ class _UpsampleDataSeam(ProbedMethodSeam):
         super().__init__(original)
         self.precision = precision     # "bf16": also bf16 tensors and cuda bf16 autocast; bf16 masks on their own kernel
         self.ok16 = None               # the probe of the bf16-mask kernel
+        self.train_upsample = False    # `accelerate(train_upsample=True)`: gradient-graph calls run `train_sea.upsample_data_train`
+        self.train_calls = 0           # calls served by it
 
     @staticmethod
     def _kernel(flow, info, mask):
@@ -504,10 +510,16 @@ class _UpsampleDataSeam(ProbedMethodSeam):
         if kwargs or len(args) != 3 or not all(torch.is_tensor(a) for a in args):
             return self.original(*args, **kwargs)
         flow, info, mask = args
-        ok = (eligible(args, (), *SEA_ACCEPTS[self.precision]) and flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
-              and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
-              and info.shape[0] == flow.shape[0] == mask.shape[0]
-              and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
+        shapes = (flow.dim() == 4 and flow.shape[1] == 2 and info.dim() == 4
+                  and 1 <= info.shape[1] <= 8 and mask.dim() == 4 and mask.shape[1] == 576
+                  and info.shape[0] == flow.shape[0] == mask.shape[0]
+                  and info.shape[2:] == flow.shape[2:] == mask.shape[2:])
+        if (self.train_upsample and self.precision == "fp32" and shapes and carries_grad(args)
+                and self._verdict("ok", flow.device, torch.float32)):
+            from .train_sea import upsample_data_train
+            self.train_calls += 1
+            return upsample_data_train(flow, info, mask)
+        ok = shapes and eligible(args, (), *SEA_ACCEPTS[self.precision])
         if not (ok and self._verdict("ok16" if mask.dtype == torch.bfloat16 else "ok", flow.device, mask.dtype)):
             return self.original(flow, info, mask)
         self.calls += 1

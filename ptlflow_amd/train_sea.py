@@ -11,7 +11,8 @@ their own:
 its weight (``gamma[:, None] * W2``, ``gamma * b2``: formed in torch on the parameters, so autograd delivers dW2, db2 and dgamma from
 the one weight gradient; the rounding the inference path documents) -> ``+ x`` -> ``final``.
 ``sea_update_block_train_pm`` is sea_raft/update.py:49-54 (RAFT's motion encoder, then the blocks), ``sea_heads_train_pm`` the heads of
-sea_raft.py:106-117.  Saved per block and iteration: x^ [M, 384] and rstd [M] here, the LayerNorm output, the GELU's input and output
+sea_raft.py:106-117, ``upsample_data_train`` the convex upsampling of flow and info (sea_raft.py:147-163: the inference kernel forward,
+``pfk_convex_upsample_info_bwd_pm_f32`` backward; K12e).  Saved per block and iteration: x^ [M, 384] and rstd [M] here, the LayerNorm output, the GELU's input and output
 [M, 512] and the residual sum [M, 384] as the operands of the convolutions that read them (the block input is the concatenation the
 caller holds anyway).
 """
@@ -22,6 +23,7 @@ from typing import Dict, Optional
 import torch
 
 from . import load_native
+from ._seam import pixel_rows
 from .train import _KERNELS, _nchw, _pm, conv_pm, packs_for
 
 LN_EPS = 1e-6              # sea_raft/layer.py:57
@@ -190,3 +192,60 @@ def sea_update_block_train(P: Dict[str, torch.Tensor], spec, net, inp, corr, flo
 def sea_head_train(P: Dict[str, torch.Tensor], name: str, net, cache: Optional[dict] = None):
     B, _, H, W = net.shape
     return _nchw(sea_head_train_pm(P, name, _pm(net), B, H, W, cache), B, H, W)
+
+
+# ---- convex upsampling of flow + info (sea_raft.py:147-163) ----------------------------------------------------------------------------
+def _upsample_rows(t: torch.Tensor, align: int = 1) -> torch.Tensor:
+    """the pixel-major rows of an NCHW fp32 tensor: a view where the strides allow (`pixel_rows`), else one contiguous copy"""
+    r = pixel_rows(t, torch.float32, align)
+    return r if r is not None else t.permute(0, 2, 3, 1).contiguous().view(-1, t.shape[1])
+
+
+class _UpsampleData(torch.autograd.Function):
+    """flow [B, 2, H, W], info [B, n, H, W] (n <= 8), mask [B, 576, H, W] (already x 0.25), fp32 -> (flow_up [B, 2, 8H, 8W], info_up
+    [B, n, 8H, 8W]): `pfk_convex_upsample_info_pm_f32` forward (the inference seam's bits), `pfk_convex_upsample_info_bwd_pm_f32`
+    backward.  The flow and info gradients are the columns 0..1 and 2.. of ONE [M, 2 + n] buffer, handed back as NCHW views of it
+    (what `flow_head`'s backward reads as its channels-last output gradient)."""
+
+    @staticmethod
+    def forward(ctx, flow, info, mask):
+        B, _, H, W = flow.shape
+        n = info.shape[1]
+        f, i, m = _upsample_rows(flow), _upsample_rows(info), _upsample_rows(mask, 4)
+        flow_up = torch.empty(B, 2, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
+        info_up = torch.empty(B, n, 8 * H, 8 * W, device=flow.device, dtype=torch.float32)
+        torch.ops.pfk.convex_upsample_info_pm(f, i, m, flow_up, info_up)
+        ctx.save_for_backward(f, i, m)
+        ctx.geom = (B, H, W, n)
+        ctx.set_materialize_grads(False)      # an output without a gradient arrives as None: the kernel's NULL, not a zero tensor
+        return flow_up, info_up
+
+    @staticmethod
+    def backward(ctx, g_flow, g_info):
+        f, i, m = ctx.saved_tensors
+        B, H, W, n = ctx.geom
+        M, dev = B * H * W, m.device
+        if g_flow is None:
+            g_flow = torch.zeros(B, 2, 8 * H, 8 * W, device=dev, dtype=torch.float32)
+        g_flow = g_flow.float().contiguous()
+        g_info = None if g_info is None else g_info.float().contiguous()
+        gmask = torch.empty(M, 576, device=dev, dtype=torch.float32)
+        gfi = torch.empty(M, 2 + n, device=dev, dtype=torch.float32)
+        torch.ops.pfk.convex_upsample_info_bwd(f, i, m, g_flow, g_info, gmask, gfi[:, :2], gfi[:, 2:])
+        need = ctx.needs_input_grad
+        return (_nchw(gfi[:, :2], B, H, W) if need[0] else None, _nchw(gfi[:, 2:], B, H, W) if need[1] else None,
+                _nchw(gmask, B, H, W) if need[2] else None)
+
+
+def upsample_data_train(flow: torch.Tensor, info: torch.Tensor, mask: torch.Tensor):
+    """SEARAFT.upsample_data (sea_raft.py:147-163), differentiable in all three arguments: NCHW fp32 GPU tensors (channel slices of a
+    channels-last buffer are read in place) -> ``(flow_up, info_up)``.  An output that receives no gradient counts as a zero one."""
+    load_native()
+    if not (flow.dim() == 4 and info.dim() == 4 and mask.dim() == 4 and flow.shape[1] == 2 and 1 <= info.shape[1] <= 8
+            and mask.shape[1] == 576 and info.shape[0] == flow.shape[0] == mask.shape[0]
+            and info.shape[2:] == flow.shape[2:] == mask.shape[2:]):
+        raise ValueError(f"upsample_data_train: flow [B, 2, H, W], info [B, 1..8, H, W], mask [B, 576, H, W], got "
+                         f"{tuple(flow.shape)}, {tuple(info.shape)}, {tuple(mask.shape)}")
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in (flow, info, mask)):
+        raise ValueError("upsample_data_train: fp32 GPU tensors")
+    return _UpsampleData.apply(flow, info, mask)

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """One SEA-RAFT training step of the refinement loop — the torch stand-in of tests/sea_seam_model.py (the reference's module layout,
 no encoders): forward, a fixed linear loss over `flows` / `info` / `flow_small`, `zero_grad`, backward — GPU box.
-    python scripts/sea_raft_train_bench.py [--samples 9] [--batch 8] [--iters 4] [--grids 46x62,55x128]
-Two legs alternating in one process, device events around the whole Python step (so the host's launch overhead is in: a whole-step
+    python scripts/sea_raft_train_bench.py [--samples 9] [--batch 8] [--iters 4] [--grids 46x62,55x128] [--legs native,native_up]
+The legs alternating in one process, device events around the whole Python step (so the host's launch overhead is in: a whole-step
 figure), median of `--samples` with the min-max spread, and each leg's peak memory (torch.cuda.max_memory_allocated over one step).
 
 * ``modules``  `accelerate(model)` as it was: seam B1 only (correlation volume and lookup, their native backward); the motion encoder,
   both ConvNeXt blocks and both heads are the model's own modules: MIOpen / rocBLAS under torch's autograd.
 * ``native``   `accelerate(model, sea_raft_update=True, sea_raft_train=True)`: those calls on ptlflow_amd/train_sea.py (K12d).
-`upsample_data` is the model's own method in both.
+  `upsample_data` is the model's own method in both.
+* ``native_up``  the same with `train_upsample=True`: `upsample_data` on `train_sea.upsample_data_train` (K12e) — ``native`` is its
+  baseline.
 
 `--trace-leg LEG` runs warm-up and then `--samples` steps of ONE leg at the first grid only (for a rocprofv3 --kernel-trace run)."""
 import argparse
@@ -27,7 +29,7 @@ from ptlflow_amd import patch  # noqa: E402
 from sea_seam_model import SeaRaftLoop, load_seeded  # noqa: E402
 
 ptlflow_amd.load_native()
-LEGS = ("modules", "native")
+LEGS = ("modules", "native", "native_up")
 
 
 def timed_ms(f):
@@ -49,7 +51,9 @@ def run(batch, h, w, iters, samples, legs, warmup=2):
          "flow_small": torch.randn(batch, 2, h, w, generator=g).to(dev)}
     # one model per leg, the same weights; seam B1 (a global of the model's module) serves both
     models = {"modules": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train()),
-              "native": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True, sea_raft_train=True)}
+              "native": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True, sea_raft_train=True),
+              "native_up": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True,
+                                            sea_raft_train=True, train_upsample=True)}
 
     def step(leg):
         m = models[leg]
@@ -69,6 +73,8 @@ def run(batch, h, w, iters, samples, legs, warmup=2):
             t[leg].append(timed_ms(lambda: step(leg)))
             peak[leg] = torch.cuda.max_memory_allocated()
     assert "native" not in legs or models["native"].update_block.train_calls > 0 and models["native"].flow_head.train_calls > 0
+    assert "native_up" not in legs or models["native_up"].upsample_data.train_calls == (warmup + samples) * (iters + 1)
+    assert models["native"].upsample_data.train_calls == 0
     for m in models.values():
         patch.restore(m)
     return t, peak
@@ -81,8 +87,10 @@ def main():
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--grids", default="46x62,55x128")
     ap.add_argument("--trace-leg", default="")
+    ap.add_argument("--legs", default=",".join(LEGS))
     args = ap.parse_args()
-    legs = [args.trace_leg] if args.trace_leg else list(LEGS)
+    legs = [args.trace_leg] if args.trace_leg else args.legs.split(",")
+    assert all(k in LEGS for k in legs), f"legs are {LEGS}"
     grids = [tuple(map(int, s.split("x"))) for s in args.grids.split(",")]
     if args.trace_leg:
         grids = grids[:1]
@@ -92,7 +100,7 @@ def main():
               f"torch {torch.__version__}, median of {args.samples}")
         for k in legs:
             v = t[k]
-            print(f"  {k:8s}: median {statistics.median(v):8.2f} ms  (min {min(v):8.2f} - max {max(v):8.2f}), peak memory {peak[k] / 2**20:8.0f} MiB")
+            print(f"  {k:9s}: median {statistics.median(v):8.2f} ms  (min {min(v):8.2f} - max {max(v):8.2f}), peak memory {peak[k] / 2**20:8.0f} MiB")
         print(json.dumps({"batch": args.batch, "grid": [h, w], "iters": args.iters, "median_ms": {k: statistics.median(v) for k, v in t.items()},
                           "min_ms": {k: min(v) for k, v in t.items()}, "max_ms": {k: max(v) for k, v in t.items()}, "peak_bytes": peak}), flush=True)
         torch.cuda.empty_cache()
