@@ -3,7 +3,9 @@
 Reference: ptlflow/models/raft/extractor.py:122-194 (``BasicEncoder``: 7x7/2 stem, three pairs of ``ResidualBlock``s at
 1/2, 1/4, 1/8 resolution, 1x1 output conv; ``norm_fn`` = ``instance`` for fnet, ``batch`` for cnet; gma/ and the other
 RAFT descendants reuse it) and :197-267 (``SmallEncoder`` of raft_small: the same skeleton at widths 32/64/96 with
-``BottleneckBlock``s — 1x1 -> 3x3 (stride) -> 1x1, :62-119).  Activations stay pixel-major ``[B*H*W, C]`` between kernels:
+``BottleneckBlock``s — 1x1 -> 3x3 (stride) -> 1x1, :62-119).  ``EncoderEngine`` is the one engine body of these and of SEA-RAFT's
+ResNetFPN (sea_encoder.py): pack loop, Winograd rule, block and forward are written once; an encoder is its block table, its
+state_dict names, its stem launch and its module's ``WINO_MIN_PIXELS``.  Activations stay pixel-major ``[B*H*W, C]`` between kernels:
 
 * stem                     -> ``pfk_conv_stem_f32`` (reads the NCHW image)
 * 3x3 / 1x1, stride 1 / 2  -> ``pfk_conv2d_f32`` or ``pfk_conv2d_bf16s`` (implicit GEMM; bias, relu, residual add and the
@@ -24,15 +26,18 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, eligible
-from .packing import pack_conv_weight, pack_wino_weight, split_bf16_planes
+from .packing import pack_conv_operand, pack_wino_weight
 from .update import CONV_PRECISIONS, EPI_LINEAR
 
-# (name, cin, cout, stride) of the six residual blocks, extractor.py:150-153
-_BLOCKS = (("layer1.0", 64, 64, 1), ("layer1.1", 64, 64, 1), ("layer2.0", 64, 96, 2), ("layer2.1", 96, 96, 1),
-           ("layer3.0", 96, 128, 2), ("layer3.1", 128, 128, 1))
+# (name, cin, cout, stride, has_downsample) of the six residual blocks, extractor.py:150-153
+_BLOCKS = (("layer1.0", 64, 64, 1, False), ("layer1.1", 64, 64, 1, False), ("layer2.0", 64, 96, 2, True), ("layer2.1", 96, 96, 1, False),
+           ("layer3.0", 96, 128, 2, True), ("layer3.1", 128, 128, 1, False))
 # the six bottleneck blocks of SmallEncoder, extractor.py:216-219
-_SMALL_BLOCKS = (("layer1.0", 32, 32, 1), ("layer1.1", 32, 32, 1), ("layer2.0", 32, 64, 2), ("layer2.1", 64, 64, 1),
-                 ("layer3.0", 64, 96, 2), ("layer3.1", 96, 96, 1))
+_SMALL_BLOCKS = (("layer1.0", 32, 32, 1, False), ("layer1.1", 32, 32, 1, False), ("layer2.0", 32, 64, 2, True), ("layer2.1", 64, 64, 1, False),
+                 ("layer3.0", 64, 96, 2, True), ("layer3.1", 96, 96, 1, False))
+# state_dict names: (the stem's norm, a block's (conv, norm) pairs, the norm of its downsample path, the output convolution)
+_NAMES = ("norm1", (("conv1", "norm1"), ("conv2", "norm2")), "downsample.1", "conv2")
+_SMALL_NAMES = ("norm1", (("conv1", "norm1"), ("conv2", "norm2"), ("conv3", "norm3")), "downsample.1", "conv2")
 EPS = 1e-5
 # Winograd rule of the fp32 BasicEncoder engine: width -> the fewest pixels (B * H * W of the launch) at which `pfk_conv2d_wino_f32` /
 # `pfk_conv2d_wino_res_f32` measured faster than `pfk_conv2d_f32` in both forms (scripts/wino_res_bench.py --encoder raft, table in
@@ -47,11 +52,18 @@ def _out(n: int, s: int) -> int:
 
 
 class EncoderEngine:
+    """Packed weights of one encoder; `engine(img)` maps ``img`` [B, input_dim, H, W] fp32 to [B, out_dim, H/8, W/8] (channels-last).
+    What differs between BasicEncoder, SmallEncoder and SEA-RAFT's ResNetFPN (sea_encoder.py) is data: the block table, the state_dict
+    names, the stem's input channels and the Winograd threshold table — the module's own dict object, read at call time."""
+
     def __init__(self, params: Dict[str, torch.Tensor], norm: str, device: torch.device, conv_precision: str = "fp32",
-                 small: bool = False):
+                 small: bool = False, *, blocks=None, names=None, input_dim: int = 3, wino_min_pixels: Optional[Dict[int, int]] = None):
         load_native()
         self.small = small
-        self.blocks = _SMALL_BLOCKS if small else _BLOCKS
+        self.blocks = blocks if blocks is not None else (_SMALL_BLOCKS if small else _BLOCKS)
+        self.names = names if names is not None else (_SMALL_NAMES if small else _NAMES)
+        self.input_dim = input_dim
+        self.wino_min_pixels = WINO_MIN_PIXELS if wino_min_pixels is None else wino_min_pixels
         if norm not in ("instance", "batch", "none"):
             raise ValueError(norm)
         if conv_precision not in CONV_PRECISIONS:
@@ -64,7 +76,7 @@ class EncoderEngine:
         # included (statistics and normalisation in fp32 arithmetic on the bf16 rows, as F.instance_norm under autocast)
         self.b16 = conv_precision == "bf16"
         self._ws: Optional[torch.Tensor] = None
-        self.winograd = True       # False: the direct kernel everywhere (A/B timing, tests)
+        self.winograd = True       # False: the direct kernel everywhere (A/B timing, tests); "always": Winograd wherever its weight exists
         self.max_matrix_bytes = 2 ** 31 - 1   # 32-bit byte offsets in the convolution kernels
         self.pack(params)
 
@@ -82,34 +94,29 @@ class EncoderEngine:
             b = (b - mean) * scale + beta
         return w, b.contiguous()
 
-    def _pk(self, w: torch.Tensor) -> torch.Tensor:
+    def _put(self, W, key: str, w: torch.Tensor, b: torch.Tensor, wino: bool = False) -> None:
+        """the (folded) convolution under `key`: the direct kernel's operand and the bias; `wino` (a stride-1 3x3 convolution): on the
+        fp32 engine of a non-small encoder, square and of a width in the threshold table, also the transformed weight of the Winograd
+        kernels `_use_wino` may select"""
         cin = w.shape[1]
-        if self.b16:
-            return pack_conv_weight(w, [(0, cin, cin)], kpad=64).to(torch.bfloat16).contiguous()
-        packed = pack_conv_weight(w, [(0, cin, cin)])
-        return packed if self.nsplit == 0 else split_bf16_planes(packed, self.nsplit)
+        W[key + ".w"], W[key + ".b"] = pack_conv_operand(w, [(0, cin, cin)], self.b16, self.nsplit), b
+        if wino and self.nsplit == 0 and not self.b16 and not self.small and cin == w.shape[0] and cin in self.wino_min_pixels:
+            W[key + ".ww"] = pack_wino_weight(w.cpu()).to(self.device)
 
     def pack(self, P: Dict[str, torch.Tensor]) -> None:
         W: Dict[str, torch.Tensor] = {}
-        w, b = self._fold(P, "conv1", "norm1")
-        assert w.shape[1:] == (3, 7, 7), "stem must be Conv2d(3, C, 7, stride=2, padding=3)"
-        W["stem.w"] = w.permute(2, 3, 1, 0).reshape(49, 3, w.shape[0]).contiguous()
+        stem_norm, convs, ds_norm, out_conv = self.names
+        w, b = self._fold(P, "conv1", stem_norm)
+        assert w.shape[1:] == (self.input_dim, 7, 7), "stem must be Conv2d(input_dim, C, 7, stride=2, padding=3)"
+        W["stem.w"] = w.permute(2, 3, 1, 0).reshape(49, self.input_dim, w.shape[0]).contiguous()
         W["stem.b"] = b
-        convs = (("conv1", "norm1"), ("conv2", "norm2"), ("conv3", "norm3")) if self.small else (("conv1", "norm1"), ("conv2", "norm2"))
-        for name, cin, cout, stride in self.blocks:
+        for name, _cin, _cout, stride, ds in self.blocks:
             for conv, nrm in convs:
-                w, b = self._fold(P, f"{name}.{conv}", f"{name}.{nrm}")
-                W[f"{name}.{conv}.w"], W[f"{name}.{conv}.b"] = self._pk(w), b
-                # fp32 BasicEncoder: the transformed weight of the Winograd kernels for the stride-1 3x3 convolutions `_use_wino` may
-                # select (after the BatchNorm fold)
-                if self.nsplit == 0 and not self.b16 and not self.small and (conv == "conv2" or stride == 1) \
-                        and w.shape[1] == cout and cout in WINO_MIN_PIXELS:
-                    W[f"{name}.{conv}.ww"] = pack_wino_weight(w.cpu()).to(self.device)
-            if stride != 1:
-                w, b = self._fold(P, f"{name}.downsample.0", f"{name}.downsample.1")
-                W[f"{name}.ds.w"], W[f"{name}.ds.b"] = self._pk(w), b
-        w, b = self._fold(P, "conv2", None)
-        W["out.w"], W["out.b"] = self._pk(w), b
+                self._put(W, f"{name}.{conv}", *self._fold(P, f"{name}.{conv}", f"{name}.{nrm}"), wino=conv == "conv2" or stride == 1)
+            if ds:
+                self._put(W, f"{name}.ds", *self._fold(P, f"{name}.downsample.0", f"{name}.{ds_norm}"))
+        w, b = self._fold(P, out_conv, None)
+        self._put(W, "out", w, b)
         self.out_dim = w.shape[0]
         self.stem_dim = W["stem.b"].numel()
         self.w = W
@@ -131,16 +138,19 @@ class EncoderEngine:
         return out
 
     def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
-        """Winograd F(2x2,3x3) for this stride-1 3x3 convolution: its transformed weight exists (fp32 BasicEncoder) and the launch is at
-        least as large as the smallest one measured faster than `pfk_conv2d_f32` at this width.  Launch shape only: B * H * W of
-        the launch.  A chunked forward (`max_matrix_bytes`) therefore has the whole-batch forward's bits only where every chunk falls
-        on the same side of the threshold as the whole batch (one image at 55 x 128 and width 128 is below it, two are not)."""
-        return self.winograd and (key + ".ww") in self.w and pixels >= WINO_MIN_PIXELS[cout]
+        """Winograd F(2x2,3x3) for this stride-1 3x3 convolution: its transformed weight exists (`_put`) and the launch is at least as
+        large as the smallest one measured faster than `pfk_conv2d_f32` at this width.  Launch shape only: B * H * W of the launch.
+        A chunked forward (`max_matrix_bytes`) therefore has the whole-batch forward's bits only where every chunk falls on the same
+        side of the threshold as the whole batch (one image at 55 x 128 and width 128 is below it, two are not)."""
+        if not self.winograd or (key + ".ww") not in self.w:
+            return False
+        return self.winograd == "always" or pixels >= self.wino_min_pixels[cout]
 
-    def _conv3(self, x, B, H, W, key, cout, relu=False, residual=None):
-        """a block's stride-1 3x3 convolution: plain (in front of an instance norm), + relu (conv1), or + relu, + residual, relu (conv2)"""
+    def _conv3(self, x, B, H, W, key, cout, relu=False, residual=None, fp32_out=None):
+        """a stride-1 3x3 convolution: plain (in front of an instance norm, `init_conv`), + relu (conv1), or + relu, + residual, relu
+        (conv2)"""
         if not self._use_wino(key, cout, B * H * W):
-            return self._conv(x, B, H, W, 3, key, cout, relu=relu, residual=residual, relu2=residual is not None)
+            return self._conv(x, B, H, W, 3, key, cout, relu=relu, residual=residual, relu2=residual is not None, fp32_out=fp32_out)
         out = torch.empty(B * H * W, cout, device=self.device, dtype=torch.float32)
         if residual is None:
             self.ops.conv2d_wino(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, relu, 1.0, out, 0)
@@ -162,7 +172,7 @@ class EncoderEngine:
         self.ops.norm_apply(x, mean, rstd, residual, out, B, HW, relu, relu2)      # (bf16 rows: in place, like the fp32 path)
         return out
 
-    def _bottleneck(self, x, B, H, W, name, cout, stride):
+    def _bottleneck(self, x, B, H, W, name, cout, stride, ds):
         """BottleneckBlock.forward (extractor.py:110-119): relu(norm(1x1)) -> relu(norm(3x3, stride)) -> relu(norm(1x1)); relu(x + y)."""
         Ho, Wo = _out(H, stride), _out(W, stride)
         mid = cout // 4
@@ -170,58 +180,68 @@ class EncoderEngine:
             y = self._inorm(self._conv(x, B, H, W, 1, f"{name}.conv1", mid), B, H * W, relu=True)
             y = self._inorm(self._conv(y, B, H, W, 3, f"{name}.conv2", mid, stride), B, Ho * Wo, relu=True)
             y = self._conv(y, B, Ho, Wo, 1, f"{name}.conv3", cout)
-            if stride != 1:
+            if ds:
                 x = self._inorm(self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride), B, Ho * Wo, relu=False)
             return self._inorm(y, B, Ho * Wo, relu=True, residual=x, relu2=True)
         y = self._conv(x, B, H, W, 1, f"{name}.conv1", mid, relu=True)
         y = self._conv(y, B, H, W, 3, f"{name}.conv2", mid, stride, relu=True)
-        if stride != 1:
+        if ds:
             x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
         return self._conv(y, B, Ho, Wo, 1, f"{name}.conv3", cout, relu=True, residual=x, relu2=True)
 
-    def _block(self, x, B, H, W, name, cout, stride):
+    def _block(self, x, B, H, W, name, cout, stride, ds):
+        """ResidualBlock.forward (extractor.py:52-59) / SEA-RAFT's BasicBlock.forward (sea_raft/layer.py:144-150): relu(x' + relu(norm2(
+        conv2(relu(norm1(conv1(x))))))) with x' the downsample path where the table has one"""
         if self.small:
-            return self._bottleneck(x, B, H, W, name, cout, stride)
+            return self._bottleneck(x, B, H, W, name, cout, stride, ds)
         Ho, Wo = _out(H, stride), _out(W, stride)
-        if self.norm == "instance":
-            y = self._conv3(x, B, H, W, f"{name}.conv1", cout) if stride == 1 else self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride)
-            y = self._inorm(y, B, Ho * Wo, relu=True)
-            y = self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout)
-            if stride != 1:
-                x = self._inorm(self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride), B, Ho * Wo, relu=False)
-            return self._inorm(y, B, Ho * Wo, relu=True, residual=x, relu2=True)
-        act = True   # "batch" (folded) and "none": relu straight in the epilogue
+        act = self.norm != "instance"   # "batch" (folded) and "none": relu straight in the epilogue
         if stride == 1:
             y = self._conv3(x, B, H, W, f"{name}.conv1", cout, relu=act)
         else:
             y = self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride, relu=act)
-            x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
-        return self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout, relu=act, residual=x)
+        if act:
+            if ds:
+                x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
+            return self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout, relu=True, residual=x)
+        y = self._inorm(y, B, Ho * Wo, relu=True)
+        y = self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout)
+        if ds:
+            x = self._inorm(self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride), B, Ho * Wo, relu=False)
+        return self._inorm(y, B, Ho * Wo, relu=True, residual=x, relu2=True)
+
+    def _max_batch(self, H1: int, W1: int) -> int:
+        """images per pass that keep every activation matrix under `max_matrix_bytes` (32-bit byte offsets in the conv kernels); the
+        widest activation row: 128 floats at half resolution (32 for the small encoder; same bound)"""
+        return max(1, self.max_matrix_bytes // (H1 * W1 * 128 * 4))
+
+    def _stem(self, img: torch.Tensor, x: torch.Tensor) -> None:
+        self.ops.conv_stem(img, self.w["stem.w"], self.w["stem.b"], x, self.norm != "instance")
 
     @torch.no_grad()
     def __call__(self, img: torch.Tensor) -> torch.Tensor:
-        """``img`` [B, 3, H, W] fp32 (already normalised / padded) -> [B, out_dim, H/8, W/8] (channels-last strides)."""
+        """``img`` [B, input_dim, H, W] fp32 (already normalised / padded) -> [B, out_dim, H/8, W/8] (channels-last strides)."""
         if not img.is_cuda:
-            raise RuntimeError("EncoderEngine needs GPU tensors (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs GPU tensors (no CPU fallback)")
+        if img.dim() != 4 or img.shape[1] != self.input_dim:
+            raise ValueError(f"expected [B, {self.input_dim}, H, W], got {tuple(img.shape)}")
         img = img.float().contiguous()
         B, _, H, W = img.shape
         H1, W1 = _out(H, 2), _out(W, 2)
-        # the convolution kernels address a source with 32-bit byte offsets: keep every activation matrix under 2 GiB
-        per_image = H1 * W1 * 128 * 4   # widest activation row: 128 floats (32 at half resolution for the small encoder; same bound)
-        max_b = max(1, self.max_matrix_bytes // per_image)
+        max_b = self._max_batch(H1, W1)
         if B > max_b:
             return torch.cat([self(img[i:i + max_b]) for i in range(0, B, max_b)], 0)
-        # K8b: the MFMA stem kernel rounds to bf16 itself (widths 32 / 64), also in front of an instance norm (`_conv`'s note)
+        # K8b: the MFMA stem kernels round to bf16 themselves (widths 32 / 64), also in front of an instance norm (`_conv`'s note)
         stem_b16 = self.b16 and self.stem_dim in (32, 64)
         x = torch.empty(B * H1 * W1, self.stem_dim, device=self.device, dtype=torch.bfloat16 if stem_b16 else torch.float32)
-        self.ops.conv_stem(img, self.w["stem.w"], self.w["stem.b"], x, self.norm != "instance")
+        self._stem(img, x)
         if self.norm == "instance":
             x = self._inorm(x, B, H1 * W1, relu=True)
         elif self.b16 and not stem_b16:
             x = x.to(torch.bfloat16)
         h, w = H1, W1
-        for name, _cin, cout, stride in self.blocks:
-            x = self._block(x, B, h, w, name, cout, stride)
+        for name, _cin, cout, stride, ds in self.blocks:
+            x = self._block(x, B, h, w, name, cout, stride, ds)
             h, w = _out(h, stride), _out(w, stride)
         y = self._conv(x, B, h, w, 1, "out", self.out_dim, fp32_out=True)
         return y.view(B, h, w, self.out_dim).permute(0, 3, 1, 2)

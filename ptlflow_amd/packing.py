@@ -108,6 +108,16 @@ def split_bf16_planes(packed: torch.Tensor, nsplit: int) -> torch.Tensor:
     return torch.stack(planes, 0).contiguous()
 
 
+def pack_conv_operand(weight: torch.Tensor, segments: Sequence[Tuple[int, int, int]], b16: bool, nsplit: int) -> torch.Tensor:
+    """The weight operand of the direct convolution kernel an engine's precision selects (the tensor's dtype picks the kernel in
+    torch.ops.pfk.conv2d): ``b16`` (K8b, `pfk_conv2d_b16`) one bf16 matrix ``[cout, ktot]`` in 64-channel K chunks, rounded once;
+    else fp32 ``[cout, ktot]`` in 32-channel chunks (`pfk_conv2d_f32`) or, ``nsplit`` > 0, its bf16 planes (`pfk_conv2d_bf16s`)."""
+    if b16:
+        return pack_conv_weight(weight, segments, kpad=64).to(torch.bfloat16).contiguous()
+    packed = pack_conv_weight(weight, segments)
+    return packed if nsplit == 0 else split_bf16_planes(packed, nsplit)
+
+
 def pack_cin2_weight(weight: torch.Tensor) -> torch.Tensor:
     """[cout, 2, k, k] -> [k*k, 2, cout] for pfk_conv_cin2_f32."""
     cout, cin, kh, kw = weight.shape

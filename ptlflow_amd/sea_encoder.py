@@ -5,8 +5,10 @@ Reference: ptlflow/models/sea_raft/extractor.py:6-116 (``ResNetFPN``: 7x7/2 stem
 (``BasicBlock``: ``relu(x' + relu(bn2(conv2(relu(bn1(conv1(x)))))))`` with ``x' = bn3(conv1x1(x))`` when the block changes the stride
 or the width).  ``fnet`` reads one image; ``cnet`` reads ``cat([image1, image2], 1)`` (sea_raft.py:187).
 
-``ResNetFPNEngine`` is an ``EncoderEngine`` with another block table: the eval-mode BatchNorms are folded into the convolutions
-(`EncoderEngine._fold`), activations stay pixel-major between the kernels:
+``ResNetFPNEngine`` is ``EncoderEngine`` (encoder.py: its pack loop, Winograd rule, block and forward) constructed with the block table
+read from the state_dict, ResNetFPN's state_dict names, 3 or 6 input channels and this module's ``WINO_MIN_PIXELS``; its own are the
+stem launch and the per-layer batch bound.  ``ConvEngine`` (`init_conv`) is that engine's one stride-1 3x3 convolution.  The eval-mode
+BatchNorms are folded into the convolutions (`EncoderEngine._fold`), activations stay pixel-major between the kernels:
 
 * stem, 3 or 6 input channels        -> ``pfk_conv_stem2_f32`` / ``_b16`` (reads the two 3-channel halves of the input in place)
 * 3x3 / 1x1, stride 1 / 2            -> ``pfk_conv2d_f32`` or ``pfk_conv2d_b16`` (bias, relu, residual add and the block's last relu
@@ -29,7 +31,6 @@ import torch
 
 from ._seam import WrappedModule, eligible, pixel_rows
 from .encoder import EncoderEngine, _out
-from .packing import pack_wino_weight
 
 SEA_ENCODER_PRECISIONS = ("fp32", "bf16")
 STEM_DIM = 64              # the width pfk_conv_stem2 is built for (every shipped `initial_dim`)
@@ -39,6 +40,8 @@ STEM_DIM = 64              # the width pfk_conv_stem2 is built for (every shippe
 WINO_MIN_PIXELS: Dict[int, int] = {64: 220 * 512, 128: 110 * 256, 256: 55 * 128}     # one 440 x 1024 frame: all it was measured on
 # precision -> (input dtypes, cuda autocast) the encoder seams serve (`_seam.eligible`)
 ACCEPTS = {"fp32": ((torch.float32,), False), "bf16": ((torch.float32,), torch.bfloat16)}
+# state_dict names (`encoder._NAMES`): the stem's norm, a block's (conv, norm) pairs, the norm of its downsample path, the output convolution
+_NAMES = ("bn1", (("conv1", "bn1"), ("conv2", "bn2")), "bn3", "final_conv")
 
 
 def block_table(shapes: Dict[str, tuple]) -> Optional[List[Tuple[str, int, int, int, bool]]]:
@@ -119,66 +122,15 @@ class ResNetFPNEngine(EncoderEngine):
         if precision not in SEA_ENCODER_PRECISIONS:
             raise ValueError(f"precision must be one of {SEA_ENCODER_PRECISIONS}, got {precision!r}")
         self.precision = precision
-        self.winograd = True       # False: the direct kernel everywhere; "always": Winograd wherever its weight exists (tests)
-        super().__init__(params, "batch", device, precision)
-
-    def pack(self, P: Dict[str, torch.Tensor]) -> None:
-        table = block_table({k: tuple(v.shape) for k, v in P.items()})
+        shapes = {k: tuple(v.shape) for k, v in params.items()}
+        table = block_table(shapes)
         if table is None:
             raise ValueError("not a ResNetFPN state_dict")
-        W: Dict[str, torch.Tensor] = {}
-        w, b = self._fold(P, "conv1", "bn1")
-        if w.shape[0] != STEM_DIM or w.shape[1] not in (3, 6) or tuple(w.shape[2:]) != (7, 7):
+        stem = shapes["conv1.weight"]
+        if stem[0] != STEM_DIM or stem[1] not in (3, 6) or stem[2:] != (7, 7):
             raise ValueError("stem must be Conv2d(3 or 6, 64, 7, stride=2, padding=3)")
-        self.input_dim = w.shape[1]
-        W["stem.w"] = w.permute(2, 3, 1, 0).reshape(49, w.shape[1], w.shape[0]).contiguous()
-        W["stem.b"] = b
-        for name, cin, cout, stride, ds in table:
-            for conv, nrm in (("conv1", "bn1"), ("conv2", "bn2")):
-                w, b = self._fold(P, f"{name}.{conv}", f"{name}.{nrm}")
-                W[f"{name}.{conv}.w"], W[f"{name}.{conv}.b"] = self._pk(w), b
-                # fp32: the transformed weight of the Winograd kernels for the stride-1 3x3 convolutions `_use_wino` may select
-                if self.precision == "fp32" and (conv == "conv2" or stride == 1) and WINO_MIN_PIXELS.get(cout) is not None \
-                        and w.shape[1] == cout:
-                    W[f"{name}.{conv}.ww"] = pack_wino_weight(w.cpu()).to(self.device)
-            if ds:
-                w, b = self._fold(P, f"{name}.downsample.0", f"{name}.bn3")
-                W[f"{name}.ds.w"], W[f"{name}.ds.b"] = self._pk(w), b
-        w, b = self._fold(P, "final_conv", None)
-        W["out.w"], W["out.b"] = self._pk(w), b
-        self.out_dim = w.shape[0]
-        self.stem_dim = STEM_DIM
-        self.blocks = table
-        self.w = W
-
-    def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
-        """Winograd F(2x2,3x3) for this stride-1 3x3 convolution: its transformed weight exists (fp32 engine) and the launch is at
-        least as large as the smallest one measured faster than `pfk_conv2d_f32` at this width (WINO_MIN_PIXELS)"""
-        if (key + ".ww") not in self.w or not self.winograd:
-            return False
-        return self.winograd == "always" or pixels >= WINO_MIN_PIXELS[cout]
-
-    def _conv3(self, x, B, H, W, key, cout, residual=None):
-        """a block's stride-1 3x3 convolution + relu (conv1), or + relu, + residual, relu (conv2)"""
-        if not self._use_wino(key, cout, B * H * W):
-            return self._conv(x, B, H, W, 3, key, cout, relu=True, residual=residual, relu2=residual is not None)
-        out = torch.empty(B * H * W, cout, device=self.device, dtype=torch.float32)
-        if residual is None:
-            self.ops.conv2d_wino(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, True, 1.0, out, 0)
-        else:
-            self.ops.conv2d_wino_res(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, True, 1.0, out, residual, True)
-        return out
-
-    def _res_block(self, x, B, H, W, name, cout, stride, ds):
-        """BasicBlock.forward (layer.py:144-150), the norms folded"""
-        Ho, Wo = _out(H, stride), _out(W, stride)
-        if stride == 1:
-            y = self._conv3(x, B, H, W, f"{name}.conv1", cout)
-        else:
-            y = self._conv(x, B, H, W, 3, f"{name}.conv1", cout, stride, relu=True)
-        if ds:
-            x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
-        return self._conv3(y, B, Ho, Wo, f"{name}.conv2", cout, residual=x)
+        super().__init__(params, "batch", device, precision, blocks=table, names=_NAMES, input_dim=stem[1],
+                         wino_min_pixels=WINO_MIN_PIXELS)
 
     def _max_batch(self, H1: int, W1: int) -> int:
         """images per pass that keep every activation matrix under `max_matrix_bytes` (32-bit byte offsets in the conv kernels)"""
@@ -188,53 +140,30 @@ class ResNetFPNEngine(EncoderEngine):
             per_image = max(per_image, h * w * cout * 4)
         return max(1, self.max_matrix_bytes // per_image)
 
-    @torch.no_grad()
-    def __call__(self, img: torch.Tensor) -> torch.Tensor:
-        if not img.is_cuda:
-            raise RuntimeError("ResNetFPNEngine needs GPU tensors (no CPU fallback)")
-        if img.dim() != 4 or img.shape[1] != self.input_dim:
-            raise ValueError(f"expected [B, {self.input_dim}, H, W], got {tuple(img.shape)}")
-        img = img.float().contiguous()
-        B, _, H, W = img.shape
-        H1, W1 = _out(H, 2), _out(W, 2)
-        max_b = self._max_batch(H1, W1)
-        if B > max_b:
-            return torch.cat([self(img[i:i + max_b]) for i in range(0, B, max_b)], 0)
-        x = torch.empty(B * H1 * W1, self.stem_dim, device=self.device, dtype=torch.bfloat16 if self.b16 else torch.float32)
+    def _stem(self, img: torch.Tensor, x: torch.Tensor) -> None:
         # the 6-channel input is read as its two 3-channel halves, in place (batch stride 6 H W)
         self.ops.conv_stem2(img[:, :3], img[:, 3:] if self.input_dim == 6 else None, self.w["stem.w"], self.w["stem.b"], x, True)
-        h, w = H1, W1
-        for name, _cin, cout, stride, ds in self.blocks:
-            x = self._res_block(x, B, h, w, name, cout, stride, ds)
-            h, w = _out(h, stride), _out(w, stride)
-        y = self._conv(x, B, h, w, 1, "out", self.out_dim, fp32_out=True)
-        return y.view(B, h, w, self.out_dim).permute(0, 3, 1, 2)
 
 
 class ConvEngine(EncoderEngine):
     """One bias-only 3x3 stride-1 convolution on pixel-major rows (SEA-RAFT's `init_conv`, sea_raft.py:112), packed and launched as the
-    encoder's own convolutions are."""
+    encoder's own convolutions are (`_put`, `_conv3`: the encoder's Winograd rule and `winograd` switch)."""
 
     def __init__(self, params: Dict[str, torch.Tensor], device: torch.device, precision: str = "fp32"):
         self.precision = precision
-        super().__init__(params, "none", device, precision)
+        super().__init__(params, "none", device, precision, wino_min_pixels=WINO_MIN_PIXELS)
 
     def pack(self, P: Dict[str, torch.Tensor]) -> None:
         w, b = self._fold(P, "conv", None)
         self.out_dim = w.shape[0]
-        self.w = {"conv.w": self._pk(w), "conv.b": b}
-        if self.precision == "fp32" and w.shape[0] == w.shape[1] and WINO_MIN_PIXELS.get(w.shape[0]) is not None:
-            self.w["conv.ww"] = pack_wino_weight(w.cpu()).to(self.device)
+        self.w = {}
+        self._put(self.w, "conv", w, b, wino=True)
 
     @torch.no_grad()
     def __call__(self, rows: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
         if self.b16 and rows.dtype != torch.bfloat16:
             rows = rows.to(torch.bfloat16)        # what autocast does to the convolution's input
-        if "conv.ww" in self.w and B * H * W >= WINO_MIN_PIXELS[self.out_dim]:        # ResNetFPNEngine's Winograd rule
-            y = torch.empty(B * H * W, self.out_dim, device=self.device, dtype=torch.float32)
-            self.ops.conv2d_wino(rows, B, H, W, self.w["conv.ww"], self.w["conv.b"], self.out_dim, False, 1.0, y, 0)
-        else:
-            y = self._conv(rows, B, H, W, 3, "conv", self.out_dim, fp32_out=True)
+        y = self._conv3(rows, B, H, W, "conv", self.out_dim, relu=False, fp32_out=True)
         return y.view(B, H, W, self.out_dim).permute(0, 3, 1, 2)
 
 

@@ -48,7 +48,7 @@ from typing import Dict, Optional
 import torch
 
 from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixel_rows
-from .packing import pack_conv_weight
+from .packing import pack_conv_operand
 from .update import EPI_LINEAR, UpdateEngine, UpdateSpec, corr_rows
 
 SEA_PRECISIONS = ("fp32", "bf16")
@@ -125,10 +125,8 @@ class SeaUpdateEngine(UpdateEngine):
         def g(name):
             return P[name].detach().to(device=dev, dtype=torch.float32)
 
-        def pk(weight, segments):
-            if self.b16:      # K8b: bf16 [cout, ktot], 64-channel K chunks, rounded once from the fp32 (gamma-folded) weight
-                return pack_conv_weight(weight, segments, kpad=64).to(torch.bfloat16).contiguous()
-            return pack_conv_weight(weight, segments)
+        def pk(weight, segments):      # (bf16: rounded once from the fp32, gamma-folded weight)
+            return pack_conv_operand(weight, segments, self.b16, self.nsplit)
 
         C = self.spec.hx_channels
         w = self.w

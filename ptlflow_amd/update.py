@@ -34,8 +34,8 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, pixel_rows
-from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight, permute_mask_head,
-                      round_up, split_bf16_planes)
+from .packing import (pack_cin2_weight, pack_conv_operand, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight,
+                      permute_mask_head, round_up, split_bf16_planes)
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 
@@ -209,12 +209,7 @@ class UpdateEngine:
             return [(0, c, round_up(c, 8 if self.b16 else 4))]
 
         def pk(weight, segments):
-            # the weight tensor's dtype selects the kernel in torch.ops.pfk.conv2d: fp32 [cout, ktot] or bf16 planes
-            if self.b16:      # K8b: one bf16 matrix [cout, ktot], 64-channel K chunks
-                return pack_conv_weight(weight, segments, kpad=64).to(torch.bfloat16).contiguous()
-            if self.nsplit == 0:
-                return pack_conv_weight(weight, segments)
-            return split_bf16_planes(pack_conv_weight(weight, segments), self.nsplit)
+            return pack_conv_operand(weight, segments, self.b16, self.nsplit)
 
         w: Dict[str, torch.Tensor] = {}
         real = s.hidden + s.x_channels
@@ -547,7 +542,7 @@ class UpdateEngine:
         if self._use_wino1d(key, B * H * W):
             self.ops.conv2d_wino1d(srcs, B, H, W, kh, kw, self.w[key + ".w1d"], self.w.get(key + ".b"), cout, epi, relu, scale, out,
                                    h, z, rh, residual)
-        elif self._use_wino(key, B * H * W, cout):
+        elif self._use_wino(key, cout, B * H * W):
             self.ops.conv2d_wino(srcs[0], B, H, W, self.w[key + ".ww"], self.w.get(key + ".b"), cout, relu, scale, out, cout_active)
         elif self.b16:
             # K8b: z|r reads h from the bf16 twin (r * h is rounded to bf16 anyway), q updates the fp32 h and mirrors it
@@ -566,7 +561,7 @@ class UpdateEngine:
             self.toc(t0, key, 2.0 * B * H * W * cout * kh * kw * cin,
                      (2.0 if self.b16 else 4.0) * (B * H * W * (cin + cout) + cout * kh * kw * cin))
 
-    def _use_wino(self, key: str, pixels: int, cout: int) -> bool:
+    def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
         """`pfk_conv2d_wino_f32` for `fm`, `c2`, `cv` (their transformed weights exist on the fp32 engine only, see pack) where
         pixels x ceil(cout / 64) >= WINO_MIN_WORK, and for `f2` where pixels >= WINO_F2_MIN_PIXELS.  The rule reads the key and the
         launch shape only — never the schedule mode — so serial, forked, captured, grouped and dead-work-skip forwards launch the same
@@ -635,7 +630,7 @@ class UpdateEngine:
         relu, scale = [1, 1], [1.0, 1.0]
         outs = [self.cor1 if s.c2 else self.corflo[:, : s.c1], self.corflo[:, cor_c: cor_c + s.f2]]
         # where `f2` takes the Winograd kernel it does so in every schedule: it leaves the group and goes through `_conv` below
-        f2_alone = self._use_wino("f2", B * H * W, s.f2)
+        f2_alone = self._use_wino("f2", s.f2, B * H * W)
         if f2_alone:
             srcs, ks, keys, relu, scale, outs = srcs[:1], ks[:1], keys[:1], relu[:1], scale[:1], outs[:1]
         if prev_mask:

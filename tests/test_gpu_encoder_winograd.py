@@ -73,7 +73,7 @@ def _wino_launches(eng, B, H, W):
     """the stride-1 3x3 convolutions of a B x H x W forward that `_use_wino` sends to Winograd"""
     taken = []
     h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    for name, _cin, cout, stride in eng.blocks:
+    for name, _cin, cout, stride, _ds in eng.blocks:
         if stride == 1 and eng._use_wino(f"{name}.conv1", cout, B * h * w):
             taken.append(f"{name}.conv1")
         h, w = (h - 1) // stride + 1, (w - 1) // stride + 1
