@@ -316,6 +316,24 @@ int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream);
  * keeps refusing a residual. */
 int pfk_conv2d_wino_res_f32(const pfk_conv_desc* d, pfk_stream_t stream);
 
+/* pfk_conv2d_wino_f32 with the instance norm IN FRONT of the convolution folded into its loads: d->src[0] is the raw output of the
+ * previous convolution, in_mean / in_rstd ([B][cin] fp32, e.g. of pfk_instnorm_stats_f32) its statistics, and every tap becomes
+ * in_relu?((x - mean) * rstd) in registers — pfk_norm_apply_f32's arithmetic; the zero padding is applied after the norm.  The
+ * output has the bits of pfk_norm_apply_f32 followed by pfk_conv2d_wino_f32.  Null statistics: PFK_ERR_BAD_ARG; everything else
+ * as pfk_conv2d_wino_f32. */
+int pfk_conv2d_wino_norm_f32(const pfk_conv_desc* d, const float* in_mean, const float* in_rstd, int in_relu, pfk_stream_t stream);
+
+/* pfk_conv2d_wino_f32 that also yields the instance-norm statistics of its OUTPUT (out_mean / out_rstd, [B][cout] fp32): the
+ * epilogue sums what it stores, and its square, in double per (block, column); the blocks of an image are reduced in a fixed order
+ * and finished as pfk_instnorm_stats_f32 finishes (no atomics: the same bits on every run).  The output has pfk_conv2d_wino_f32's
+ * bits; mean / rstd can differ from pfk_instnorm_stats_f32's by the order of a double sum, i.e. only where a double falls on an fp32
+ * rounding boundary.  in_mean / in_rstd: both null, or both given as for pfk_conv2d_wino_norm_f32.  `workspace`: 8-byte aligned,
+ * at least pfk_conv_wino_stats_workspace_bytes(B, H, W, cout) bytes, no need to clear it.  A residual, relu_after_residual, a null
+ * out_mean / out_rstd / workspace or a short workspace: PFK_ERR_BAD_ARG; `cout_active` below cout: PFK_ERR_UNSUPPORTED. */
+long long pfk_conv_wino_stats_workspace_bytes(int B, int H, int W, int cout);   /* < 0 (PFK_ERR_BAD_ARG) unless all > 0 */
+int pfk_conv2d_wino_stats_f32(const pfk_conv_desc* d, const float* in_mean, const float* in_rstd, int in_relu, float eps,
+                              float* out_mean, float* out_rstd, void* workspace, long long workspace_bytes, pfk_stream_t stream);
+
 /* 1-D Winograd F(4,5) form of pfk_conv2d_f32 for the 1x5 / 5x1 stride-1 convolutions of the SepConvGRU (raft/update.py:58-73;
  * fp32 MFMA, fp32 accumulate): 8 GEMMs over the transformed input per 4 outputs along the convolution axis, 2.5x fewer products
  * than the direct form.  Supported: (kh, kw) = (1, 5) or (5, 1), stride 0 or 1, one or two sources in K order (channels % 8 == 0
@@ -690,6 +708,14 @@ int pfk_instnorm_stats_f32(const float* x, int ld, int B, int HW, int C, float e
 int pfk_norm_apply_f32(const float* x, int x_ld, const float* mean, const float* rstd, const float* residual,
                        int residual_ld, float* out, int out_ld, int B, int HW, int C, int relu,
                        int relu_after_residual, pfk_stream_t stream);
+
+/* The same with a residual that is a raw convolution output with statistics of its own (res_mean / res_rstd, [B][C]), normalised
+ * in flight: out = relu?((x - mean) * rstd); out = relu_after?(res_relu?((residual - res_mean) * res_rstd) + out).  The bits are
+ * those of pfk_norm_apply_f32 on the residual (relu = res_relu) followed by pfk_norm_apply_f32 with that result as the residual.
+ * Everything is required (PFK_ERR_BAD_ARG for a null pointer); out may alias x. */
+int pfk_norm_apply_res_f32(const float* x, int x_ld, const float* mean, const float* rstd, const float* residual, int residual_ld,
+                           const float* res_mean, const float* res_rstd, int res_relu, float* out, int out_ld, int B, int HW, int C,
+                           int relu, int relu_after_residual, pfk_stream_t stream);
 
 /* same with bf16 residual rows and a bf16 output (ABI 7; ld in elements, 8-byte aligned rows).  x = the convolution output the
  * statistics were taken from: fp32 rows (x_bf16 = 0), or bf16 rows (x_bf16 = 1; `out_bf16` may be `x` itself: in place) — what

@@ -39,6 +39,11 @@ static inline int pfk_launch_status() {
   return hipGetLastError() == hipSuccess ? PFK_OK : PFK_ERR_LAUNCH;
 }
 
+// pfk_encoder.hip, for the Winograd kernel's statistics epilogue (pfk_wino.hip): part = sums, then sums of squares, each
+// [B][nch][C] doubles, reduced over nch in chunk_reduce_kernel's fixed order and finished as pfk_instnorm_stats_f32 finishes
+// (mean, rstd in double, rounded once).  Arguments are the caller's to check.
+int pfk_instnorm_finish_parts(const double* part, int B, int nch, int C, int HW, float eps, float* mean, float* rstd, hipStream_t st);
+
 // Bijective XCD-aware block remap (8 XCDs, dispatcher places block b on XCD b % 8): gives each
 // XCD one contiguous range of tile ids so tiles that share operand panels share an L2.
 __device__ __forceinline__ int pfk_xcd_remap(int bid, int nblk) {

@@ -420,6 +420,37 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const TX* __restrict__ 
   na_store4(out + p * out_ld + c4, v);
 }
 
+// The same with a residual that is itself a raw convolution output in front of its own instance norm (the stem's output under
+// layer1.0, a downsample path): y = relu?((x - mean) * rstd); y = relu?((res - res_mean) * res_rstd) + y; relu?.  Each step rounded
+// as norm_apply_kernel rounds it, so the result is that of two launches: the residual normalised first, then this block's apply.
+__global__ __launch_bounds__(256) void norm_apply_res_kernel(const float* __restrict__ x, int x_ld, const float* __restrict__ mean,
+                                                             const float* __restrict__ rstd, const float* __restrict__ residual,
+                                                             int res_ld, const float* __restrict__ res_mean,
+                                                             const float* __restrict__ res_rstd, float* __restrict__ out, int out_ld,
+                                                             long long M, int HW, int C, int relu, int res_relu, int relu_after) {
+  const int tpr = C >> 2;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long p = idx / tpr;
+  if (p >= M) return;
+  const int c4 = (int)(idx - p * tpr) * 4;
+  const long long sidx = (p / HW) * C + c4;
+  const f32x4 m = *reinterpret_cast<const f32x4*>(mean + sidx), r = *reinterpret_cast<const f32x4*>(rstd + sidx);
+  const f32x4 rm = *reinterpret_cast<const f32x4*>(res_mean + sidx), rr = *reinterpret_cast<const f32x4*>(res_rstd + sidx);
+  const f32x4 xv = ld4f(x + p * x_ld + c4), rv = ld4f(residual + p * res_ld + c4);
+  const float lo = relu ? 0.f : -__builtin_inff(), rlo = res_relu ? 0.f : -__builtin_inff(), alo = relu_after ? 0.f : -__builtin_inff();
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float y = __fmul_rn(__fsub_rn(xv[e], m[e]), r[e]);
+    y = (y < lo) ? lo : y;
+    float z = __fmul_rn(__fsub_rn(rv[e], rm[e]), rr[e]);
+    z = (z < rlo) ? rlo : z;
+    y = __fadd_rn(z, y);
+    v[e] = (y < alo) ? alo : y;
+  }
+  na_store4(out + p * out_ld + c4, v);
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // Backward of  y = relu?((x - mean) * rstd)  with per-(image, channel) statistics over HW pixels (instance norm; batch norm
@@ -842,6 +873,12 @@ static int instnorm_stats_launch(const TX* x, int ld, int B, int HW, int C, floa
   return pfk_launch_status();
 }
 
+int pfk_instnorm_finish_parts(const double* part, int B, int nch, int C, int HW, float eps, float* mean, float* rstd, hipStream_t st) {
+  const dim3 rgrid((unsigned)((C + 63) / 64), (unsigned)B);
+  hipLaunchKernelGGL(chunk_reduce_kernel<true>, rgrid, dim3(1024), 0, st, part, (long long)B * nch * C, 2, nch, C, static_cast<double*>(nullptr), 0LL, HW, eps, mean, rstd);
+  return pfk_launch_status();
+}
+
 extern "C" {
 
 int pfk_instnorm_stats_f32(const float* x, int ld, int B, int HW, int C, float eps, float* mean, float* rstd,
@@ -921,6 +958,23 @@ int pfk_norm_apply_f32(const float* x, int x_ld, const float* mean, const float*
   if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((norm_apply_kernel<float, float>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_ld,
                      mean, rstd, residual, residual_ld, out, out_ld, M, HW, C, relu, relu_after_residual);
+  return pfk_launch_status();
+}
+
+int pfk_norm_apply_res_f32(const float* x, int x_ld, const float* mean, const float* rstd, const float* residual, int residual_ld,
+                           const float* res_mean, const float* res_rstd, int res_relu, float* out, int out_ld, int B, int HW, int C,
+                           int relu, int relu_after_residual, pfk_stream_t stream) {
+  if (!x || !mean || !rstd || !residual || !res_mean || !res_rstd || !out || B <= 0 || HW <= 0 || C <= 0 || x_ld < C || out_ld < C ||
+      residual_ld < C)
+    return PFK_ERR_BAD_ARG;
+  if ((C & 3) || (x_ld & 3) || (out_ld & 3) || (residual_ld & 3) || !pfk_aligned16(x) || !pfk_aligned16(out) || !pfk_aligned16(residual) ||
+      !pfk_aligned16(mean) || !pfk_aligned16(rstd) || !pfk_aligned16(res_mean) || !pfk_aligned16(res_rstd))
+    return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * HW;
+  const long long blocks = (M * (C >> 2) + 255) / 256;
+  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(norm_apply_res_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_ld, mean, rstd,
+                     residual, residual_ld, res_mean, res_rstd, out, out_ld, M, HW, C, relu, res_relu, relu_after_residual);
   return pfk_launch_status();
 }
 

@@ -147,22 +147,27 @@ void conv2d(at::TensorList srcs, int64_t B, int64_t H, int64_t W, int64_t kh, in
 // Winograd F(2x2,3x3) 3x3 convolution (pfk_conv2d_wino_f32): one fp32 source [B*H*W, cin] view, the transformed weight of
 // packing.pack_wino_weight (flat, pfk_conv_wino_weight_floats(cin, cout) floats), LINEAR epilogue into an [M, cout] view;
 // with `residual` the residual-block epilogue (pfk_conv2d_wino_res_f32): out = relu2?(residual + relu?(conv + bias) * scale)
+pfk_conv_desc wino_desc(const char* op, const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight,
+                        const c10::optional<Tensor>& bias, int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active) {
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, op, ": sizes");
+  pfk_conv_desc d{};
+  fill_sources(d, {src}, B * H * W, F32, op);
+  const int cin = d.src[0].channels;
+  TORCH_CHECK(cin % 32 == 0, op, ": input channels must be a multiple of 32, got ", cin);
+  d.B = B; d.H = H; d.W = W; d.kh = 3; d.kw = 3; d.stride = 1; d.cout = cout;
+  d.epilogue = PFK_EPI_LINEAR; d.relu = relu; d.scale = (float)scale;
+  d.cout_active = (int)cout_active;
+  d.weight = dense(op, weight, "weight (transformed)", F32, pfk_conv_wino_weight_floats(cin, (int)cout)).f32();
+  d.bias = dense(op, bias, "bias", F32, cout).f32();
+  const Rows o = rows(op, out, "out", F32).expect(B * H * W, cout);
+  d.out = o.f32(); d.out_ld = o.ld; d.out_coff = 0;
+  return d;
+}
 void conv2d_wino_impl(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
                       int64_t cout, bool relu, double scale, const Tensor& out, int64_t cout_active, const Tensor* residual,
                       bool relu_after_residual) {
   OpScope scope(weight);
-  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && cout >= 1, "conv2d_wino: sizes");
-  pfk_conv_desc d{};
-  fill_sources(d, {src}, B * H * W, F32, "conv2d_wino");
-  const int cin = d.src[0].channels;
-  TORCH_CHECK(cin % 32 == 0, "conv2d_wino: input channels must be a multiple of 32, got ", cin);
-  d.B = B; d.H = H; d.W = W; d.kh = 3; d.kw = 3; d.stride = 1; d.cout = cout;
-  d.epilogue = PFK_EPI_LINEAR; d.relu = relu; d.scale = (float)scale;
-  d.cout_active = (int)cout_active;
-  d.weight = dense("conv2d_wino", weight, "weight (transformed)", F32, pfk_conv_wino_weight_floats(cin, (int)cout)).f32();
-  d.bias = dense("conv2d_wino", bias, "bias", F32, cout).f32();
-  const Rows o = rows("conv2d_wino", out, "out", F32).expect(B * H * W, cout);
-  d.out = o.f32(); d.out_ld = o.ld; d.out_coff = 0;
+  pfk_conv_desc d = wino_desc("conv2d_wino", src, B, H, W, weight, bias, cout, relu, scale, out, cout_active);
   if (residual) {
     const Rows r = rows("conv2d_wino_res", *residual, "residual", F32).expect(B * H * W, cout);
     d.residual = r.f32(); d.residual_ld = r.ld; d.relu_after_residual = relu_after_residual;
@@ -178,6 +183,39 @@ void conv2d_wino(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tenso
 void conv2d_wino_res(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
                      int64_t cout, bool relu, double scale, const Tensor& out, const Tensor& residual, bool relu_after_residual) {
   conv2d_wino_impl(src, B, H, W, weight, bias, cout, relu, scale, out, 0, &residual, relu_after_residual);
+}
+
+// The instance norm in front of the convolution applied on load (pfk_conv2d_wino_norm_f32): `src` is the raw output of the previous
+// convolution, in_mean / in_rstd [B*cin] its statistics
+void conv2d_wino_norm(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                      int64_t cout, bool relu, double scale, const Tensor& out, const Tensor& in_mean, const Tensor& in_rstd, bool in_relu) {
+  OpScope scope(weight);
+  const pfk_conv_desc d = wino_desc("conv2d_wino_norm", src, B, H, W, weight, bias, cout, relu, scale, out, 0);
+  const int64_t cin = d.src[0].channels;
+  const float* mp = dense("conv2d_wino_norm", in_mean, "in_mean [B*cin]", F32, B * cin).f32();
+  const float* rp = dense("conv2d_wino_norm", in_rstd, "in_rstd [B*cin]", F32, B * cin).f32();
+  check_ok(pfk_conv2d_wino_norm_f32(&d, mp, rp, in_relu, cur_stream()), "conv2d_wino_norm");
+}
+
+// ... and / or the statistics of the instance norm behind it out of the epilogue (pfk_conv2d_wino_stats_f32; bias only: the
+// convolution in front of a norm has no relu and no scale)
+int64_t conv_wino_stats_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t cout) {
+  return pfk_conv_wino_stats_workspace_bytes((int)B, (int)H, (int)W, (int)cout);
+}
+void conv2d_wino_stats(const Tensor& src, int64_t B, int64_t H, int64_t W, const Tensor& weight, const c10::optional<Tensor>& bias,
+                       int64_t cout, const Tensor& out, const c10::optional<Tensor>& in_mean, const c10::optional<Tensor>& in_rstd,
+                       bool in_relu, double eps, Tensor out_mean, Tensor out_rstd, Tensor workspace) {
+  OpScope scope(weight);
+  const pfk_conv_desc d = wino_desc("conv2d_wino_stats", src, B, H, W, weight, bias, cout, false, 1.0, out, 0);
+  const int64_t cin = d.src[0].channels;
+  TORCH_CHECK(in_mean.has_value() == in_rstd.has_value(), "conv2d_wino_stats: in_mean and in_rstd come together");
+  const float* mp = dense("conv2d_wino_stats", in_mean, "in_mean [B*cin]", F32, B * cin).f32();
+  const float* rp = dense("conv2d_wino_stats", in_rstd, "in_rstd [B*cin]", F32, B * cin).f32();
+  float* om = dense("conv2d_wino_stats", out_mean, "out_mean [B*cout]", F32, B * cout).f32();
+  float* orr = dense("conv2d_wino_stats", out_rstd, "out_rstd [B*cout]", F32, B * cout).f32();
+  void* ws = dense("conv2d_wino_stats", workspace, "workspace", Raw).raw();
+  check_ok(pfk_conv2d_wino_stats_f32(&d, mp, rp, in_relu, (float)eps, om, orr, ws, (long long)workspace.nbytes(), cur_stream()),
+           "conv2d_wino_stats");
 }
 
 // 1-D Winograd F(4,5) form of a 1x5 / 5x1 convolution (pfk_conv1d_wino_f32): one or two fp32 sources ([B*H*W, channels_i] views,
@@ -890,6 +928,22 @@ void norm_apply(const Tensor& x, const Tensor& mean, const Tensor& rstd, const c
            "norm_apply");
 }
 
+// norm_apply with a raw residual and its own statistics (pfk_norm_apply_res_f32), fp32 rows
+void norm_apply_res(const Tensor& x, const Tensor& mean, const Tensor& rstd, const Tensor& residual, const Tensor& res_mean,
+                    const Tensor& res_rstd, bool res_relu, Tensor out, int64_t B, int64_t HW, bool relu, bool relu_after_residual) {
+  OpScope scope(x);
+  const Rows a = rows("norm_apply_res", x, "x", F32).expect(B * HW, AtLeast{0});
+  const int C = a.cols;
+  const Rows o = rows("norm_apply_res", out, "out", F32).expect(B * HW, C);
+  const Rows r = rows("norm_apply_res", residual, "residual", F32).expect(B * HW, C);
+  const float* mp = dense("norm_apply_res", mean, "mean [B*C]", F32, B * C).f32();
+  const float* rp = dense("norm_apply_res", rstd, "rstd [B*C]", F32, B * C).f32();
+  const float* rmp = dense("norm_apply_res", res_mean, "res_mean [B*C]", F32, B * C).f32();
+  const float* rrp = dense("norm_apply_res", res_rstd, "res_rstd [B*C]", F32, B * C).f32();
+  check_ok(pfk_norm_apply_res_f32(a.f32(), a.ld, mp, rp, r.f32(), r.ld, rmp, rrp, res_relu, o.f32(), o.ld, (int)B, (int)HW, C, relu,
+                                  relu_after_residual, cur_stream()), "norm_apply_res");
+}
+
 int64_t norm_bwd_workspace_bytes(int64_t B, int64_t C) { return pfk_norm_bwd_workspace_bytes((int)B, (int)C); }
 
 // backward of relu?((x - mean) * rstd): dx, and the two per-(image, channel) sums (d beta / d gamma of an affine batch norm)
@@ -1074,6 +1128,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("instnorm_stats(Tensor x, int B, int HW, float eps, Tensor(a!) mean, Tensor(b!) rstd, Tensor(c!) workspace) -> ()");
   m.def("norm_apply(Tensor x, Tensor mean, Tensor rstd, Tensor? residual, Tensor(a!) out, int B, int HW, bool relu, "
         "bool relu_after_residual) -> ()");
+  m.def("norm_apply_res(Tensor x, Tensor mean, Tensor rstd, Tensor residual, Tensor res_mean, Tensor res_rstd, bool res_relu, "
+        "Tensor(a!) out, int B, int HW, bool relu, bool relu_after_residual) -> ()");
   m.def("debug_set_tile(int cfg) -> ()", &debug_set_tile);
   m.def("debug_set_lookup_pix(int pix) -> ()", &debug_set_lookup_pix);
   m.def("debug_set_wgrad(int variant) -> ()", &debug_set_wgrad);
@@ -1093,6 +1149,11 @@ TORCH_LIBRARY(pfk, m) {
         "Tensor(e!)? workspace=None, Tensor? residual=None, int stride=1, bool relu_after_residual=False, int cout_active=0, int cout_split=0) -> ()");
   m.def("conv2d_wino(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
         "int cout_active=0) -> ()");
+  m.def("conv2d_wino_norm(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, bool relu, float scale, Tensor(a!) out, "
+        "Tensor in_mean, Tensor in_rstd, bool in_relu) -> ()");
+  m.def("conv_wino_stats_workspace_bytes(int B, int H, int W, int cout) -> int", &conv_wino_stats_workspace_bytes);
+  m.def("conv2d_wino_stats(Tensor src, int B, int H, int W, Tensor weight, Tensor? bias, int cout, Tensor(a!) out, Tensor? in_mean, "
+        "Tensor? in_rstd, bool in_relu, float eps, Tensor(b!) out_mean, Tensor(c!) out_rstd, Tensor(d!) workspace) -> ()");
   m.def("conv2d_wino1d(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, int epilogue, "
         "bool relu, float scale, Tensor(a!)? out=None, Tensor(b!)? h=None, Tensor(c!)? aux_z=None, Tensor(d!)? aux_rh=None, "
         "Tensor? residual=None) -> ()");
@@ -1156,6 +1217,8 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv2d_group", &conv2d_group);
   m.impl("conv2d_wino", &conv2d_wino);
   m.impl("conv2d_wino_res", &conv2d_wino_res);
+  m.impl("conv2d_wino_norm", &conv2d_wino_norm);
+  m.impl("conv2d_wino_stats", &conv2d_wino_stats);
   m.impl("conv2d_wino1d", &conv2d_wino1d);
   m.impl("conv_cin2", &conv_cin2);
   m.impl("flow_delta", &flow_delta);
@@ -1200,4 +1263,5 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("conv_stem_wgrad", &conv_stem_wgrad);
   m.impl("instnorm_stats", &instnorm_stats);
   m.impl("norm_apply", &norm_apply);
+  m.impl("norm_apply_res", &norm_apply_res);
 }

@@ -38,6 +38,15 @@
 // Where rows do not take 16-byte pieces (out + out_coff or residual not 16-byte aligned, a row stride % 4 != 0) and in a wave whose
 // 32 columns reach past cout (cout 126), the same walk stores its 4 columns as dwords.  A column's K order and transforms do not
 // depend on which other columns are in the launch: `cout_active` launches fewer column blocks and gives the full launch's bits.
+//
+// Instance norms around the launch (the fp32 feature encoder), two more template switches; the instantiations without them are the
+// code above, instruction for instruction.  NORM: only U comes by LDS-DMA — the 16 taps pass through registers, so the norm in front
+// of the convolution is applied there: the staging thread requests mean and rstd of (its tile's image, its channel) for the next
+// K-step through a sized descriptor, beside the first taps between the MFMAs, and every tap becomes relu?((d - mean) * rstd) before
+// B^T d B — VALU work beside a loop the matrix pipe bounds; a tap whose offset is the out-of-range one stays 0.f (the padding is zero
+// after the norm).  STATS: the row walk adds what it stores to per-column double sums of x and x * x for the norm behind the
+// convolution, reduced per block in a fixed order and written to a workspace [image][block of the image][cout]; for that the tile
+// list is laid out per image, padded to whole blocks (a tile's arithmetic does not depend on its block: same output bits).
 #include "pfk_gemm.h"
 
 using namespace pfkg;
@@ -72,6 +81,14 @@ struct WinoArgs {
   unsigned res_bytes;            // readable bytes from res
   int relu2;                     // relu after the residual add
   int vec;                       // the rows of out (and res) take 16-byte pieces: 16-byte aligned, row strides % 4 == 0
+  // NORM: the source is a raw convolution output in front of an instance norm; a tap becomes relu?((d - mean) * rstd) on its way in
+  const float* in_mean; const float* in_rstd;   // [B][cin]
+  unsigned stat_bytes;           // B * cin * 4
+  int cin, in_relu;
+  // STATS: the tile list is laid out per image, `nbi` blocks of 32 tiles each (the last one padded); every block writes the sums of
+  // x and of x * x over what it stores, per column, into part[sum, sum of squares][image][block of the image][cout]
+  int nbi;
+  double* part; long long astride;
 };
 
 // The epilogue's entry of one of the block's 32 tiles, made once by the staging role: bit 31 the tile exists, bit 30 / 29 its second
@@ -83,6 +100,12 @@ constexpr int ESZ = 64 * 32 + 4 * 16;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+
+// NORM: mean and rstd of this thread's (image, channel) of K-step ks (zero for a tile past the end: its taps are all padding)
+__device__ __forceinline__ void wino_load_stat(__amdgpu_buffer_rsrc_t rm, __amdgpu_buffer_rsrc_t rr, unsigned soff, int ks, float (&mr)[2]) {
+  mr[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, soff, ks * WK * 4, 0));
+  mr[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, soff, ks * WK * 4, 0));
 }
 
 // Two of the 16 input taps of this thread's (tile, channel) of K-step ks into registers.
@@ -106,9 +129,12 @@ __device__ __forceinline__ void wino_dma_u(__amdgpu_buffer_rsrc_t rw, lfloat* ds
 // `more`: the next K-step's operands are requested BETWEEN the MFMAs, where their issue cycles hide under the matrix pipe (in front of
 // the first MFMA, 8 LDS-DMA pieces and 16 loads are several hundred cycles in which this wave feeds it nothing): one U piece beside
 // each of the components 0-7, two taps beside each of 8-15.
+// NORM: the staging thread's mean and rstd of the next K-step's channel (its tile's image) are requested with the first two taps.
+template <bool NORM>
 __device__ __forceinline__ void wino_mfma(const lfloat* aV, const lfloat* aU, const lfloat* aU1, f32x4 (&acc)[16][2], bool more,
                                           __amdgpu_buffer_rsrc_t rw, lfloat* udst, unsigned wvoff, unsigned wk,
-                                          __amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[16], int ks, float (&d)[16]) {
+                                          __amdgpu_buffer_rsrc_t rs, const unsigned (&voff)[16], int ks, float (&d)[16],
+                                          __amdgpu_buffer_rsrc_t rm, __amdgpu_buffer_rsrc_t rr, unsigned soff, float (&mr)[2]) {
   // operands of component x + 1 are read while the MFMAs of x run (the LDS latency hides under the matrix pipe)
   f32x2 va[2], u0[2], u1[2];
   va[0] = *(const lf32x2*)(aV);
@@ -126,6 +152,9 @@ __device__ __forceinline__ void wino_mfma(const lfloat* aV, const lfloat* aU, co
     if (more) {
       if (x < 8) wino_dma_u(rw, udst, wvoff, wk, x);
       else wino_load_v2(rs, voff, ks, 2 * (x - 8), d);
+      if constexpr (NORM) {
+        if (x == 8) wino_load_stat(rm, rr, soff, ks, mr);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc hoists the reads of x + 1 behind the MFMAs of x again)
     acc[x][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[c][0], u0[c][0], acc[x][0], 0, 0, 0);
@@ -169,8 +198,11 @@ __device__ __forceinline__ void wino_epi_request(const WinoArgs& a, const lunsig
 // Epilogue, row walk: the lane's 8 row pieces from the wave's parking area (rE = the lane's pixel 0 and column there), then the first
 // version's arithmetic in its order and rounding: + bias, NaN-propagating relu, x scale (RES: one fma with the residual as the addend,
 // then the second relu); a relu that is off compares with -inf and keeps every value.
-template <bool RES, bool VEC>
-__device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* rE, int n0, const unsigned (&oo)[8], const f32x4 (&r4)[8]) {
+// STATS: the lane also sums what it stores, and its square, per column in double (st[0..3], st[4..7]); a store the hardware drops — a
+// missing tile, a pixel past H or W (its offset is OOB or beyond), a column from cout on — adds an exact zero.
+template <bool RES, bool VEC, bool STATS>
+__device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* rE, int n0, const unsigned (&oo)[8], const f32x4 (&r4)[8],
+                                               double (&st)[8]) {
   const __amdgpu_buffer_rsrc_t ro = rsrc_n(a.out, a.out_bytes);
   const __amdgpu_buffer_rsrc_t rbias = rsrc_n(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
   float bias4[4];
@@ -192,6 +224,11 @@ __device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* 
         t *= a.scale;
       }
       v[j] = t;
+      if constexpr (STATS) {
+        const double dv = (double)((oo[i] < OOB && (VEC || n0 + j < a.cout)) ? t : 0.f);
+        st[j] += dv;
+        st[4 + j] = __builtin_fma(dv, dv, st[4 + j]);
+      }
     }
     if constexpr (VEC) {
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, (f32x4{v[0], v[1], v[2], v[3]})), ro, oo[i], 0, 0);
@@ -205,8 +242,14 @@ __device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* 
 
 // RES: the residual-block epilogue of pfk_conv2d_wino_res_f32 (v = residual + v, then the block's last relu); the instantiation
 // without it is pfk_conv2d_wino_f32's kernel.
-template <bool RES>
+// NORM (pfk_conv2d_wino_norm_f32, pfk_conv2d_wino_stats_f32): the instance norm in front of the convolution is applied to the taps
+// in registers, with norm_apply_kernel's arithmetic (subtract, multiply, compare; each rounded); a padding tap stays 0.f.
+// STATS (pfk_conv2d_wino_stats_f32, plain form): the row walk sums its stores for the instance norm behind the convolution.  A block's
+// 32 tiles are of one image (WinoArgs::nbi); lanes of a column, then the two wave rows are added in a fixed order through LDS — no
+// atomics, the same bits on every run — and chunk_reduce_kernel<true> finishes over the image's blocks.
+template <bool RES, bool NORM = false, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoArgs a) {
+  static_assert(!(RES && STATS), "the residual form is never in front of an instance norm");
   // (one array, U first) 2 x 32 KB of U + 16 KB of V: two blocks fill a CU's LDS
   __shared__ __attribute__((aligned(16))) float smem[2 * UIMG + 16 * WT * WK];
   lfloat* const sU = (lfloat*)smem;    // [buffer][xi][column][slot]
@@ -218,15 +261,30 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
 
   const __amdgpu_buffer_rsrc_t rs = rsrc_n(a.src, a.src_bytes);
   const __amdgpu_buffer_rsrc_t rw = rsrc_n(a.weight, a.w_bytes);
+  const __amdgpu_buffer_rsrc_t rm = rsrc_n(a.in_mean, NORM ? a.stat_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rr = rsrc_n(a.in_rstd, NORM ? a.stat_bytes : 0u);
 
   // ---- staging role: tile lt, channel cc of the K-step
   const int lt = tid >> 3, cc = tid & 7;
   unsigned voff[16];
   unsigned tinfo;   // the tile's entry of the epilogue's table
+  unsigned soff = 0;   // NORM: byte offset of (the tile's image, channel cc) in the statistics
   {
-    const int g = t0 + lt;
-    const bool tok = g < a.ntiles;
-    const int b = g / a.tpi, r = g - b * a.tpi;
+    int g, b, r;
+    bool tok;
+    if constexpr (STATS) {
+      // block (image sb, its block sk): tiles 32 * sk .. of that image
+      const int tb = blockIdx.x / a.ncb;
+      b = tb / a.nbi;
+      r = (tb - b * a.nbi) * WT + lt;
+      tok = r < a.tpi;
+    } else {
+      g = t0 + lt;
+      tok = g < a.ntiles;
+      b = g / a.tpi;
+      r = g - b * a.tpi;
+    }
+    if constexpr (NORM) soff = ((unsigned)b * (unsigned)a.cin + (unsigned)cc) * 4u;
     const int ty = r / a.tw, tx = r - ty * a.tw;
     tinfo = tok ? (T_OK | (2 * ty + 1 < a.H ? T_ROW2 : 0u) | (2 * tx + 1 < a.W ? T_COL2 : 0u) | (unsigned)((b * a.H + 2 * ty) * a.W + 2 * tx)) : 0u;
 #pragma unroll
@@ -245,6 +303,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
   lfloat* const udst = sU + wid * 256;                                                          // of each 4 KB component pair
 
   float d[16];
+  float mr[2] = {0.f, 0.f};   // NORM: mean, rstd of the K-step whose taps are in d
   // ---- MFMA role: wave tile rows wt*16.., columns wc*32..
   const int wt = wid & 1, wc = wid >> 1;
   const int rl = lane & 15, kq = lane >> 4;
@@ -264,7 +323,16 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
     wino_dma_u(rw, udst, wvoff, wbase, j);
     wino_load_v2(rs, voff, 0, 2 * j, d);
   }
-  for (int ks = 0; ks < a.nks; ++ks) {
+  if constexpr (NORM) wino_load_stat(rm, rr, soff, 0, mr);
+  const float nlo = a.in_relu ? 0.f : -__builtin_inff();  for (int ks = 0; ks < a.nks; ++ks) {
+    if constexpr (NORM) {
+      // norm_apply_kernel's y = (x - mean) * rstd, relu (a relu that is off compares with -inf); the padding is zero AFTER the norm
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float y = __fmul_rn(__fsub_rn(d[q], mr[0]), mr[1]);
+        d[q] = voff[q] == OOB ? 0.f : ((y < nlo) ? nlo : y);
+      }
+    }
     // V = B^T d B (rows, then columns), one channel of one tile
     float t[16];
 #pragma unroll
@@ -285,8 +353,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const int ub = (ks & 1) * UIMG;
     // the next K-step's U goes to the other buffer, last read before the previous K-step's last barrier
-    wino_mfma(aV, aU + ub, aU1 + ub, acc, ks + 1 < a.nks, rw, udst + (UIMG - ub), wvoff, wbase + (unsigned)(ks + 1) * (UIMG * 4u), rs,
-              voff, ks + 1, d);
+    wino_mfma<NORM>(aV, aU + ub, aU1 + ub, acc, ks + 1 < a.nks, rw, udst + (UIMG - ub), wvoff, wbase + (unsigned)(ks + 1) * (UIMG * 4u),
+                    rs, voff, ks + 1, d, rm, rr, soff, mr);
     // a raw barrier: __syncthreads() would wait for the LDS-DMA in flight.  Every wave is done reading sV and this U buffer
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
@@ -346,8 +414,36 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
       }
   }
   const lfloat* const rE = sE + prow * 32 + c4;
-  if (vec) wino_epi_store<RES, true>(a, rE, n0, oo, r4);
-  else wino_epi_store<RES, false>(a, rE, n0, oo, r4);
+  double st[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+  if (vec) wino_epi_store<RES, true, STATS>(a, rE, n0, oo, r4, st);
+  else wino_epi_store<RES, false, STATS>(a, rE, n0, oo, r4, st);
+
+  if constexpr (STATS) {
+    // The lane's 8 sums into its wave's parking area (read for the last time above; a wave's LDS operations stay in order), 64 bytes
+    // per lane.  Then thread (sum | sum of squares, column of the block's 64) adds the 8 lanes prow = 0..7 that walked the column in
+    // each wave row, then the two wave rows: a fixed order.
+    typedef __attribute__((address_space(3))) double ldouble;
+    ldouble* const sS = (ldouble*)(sE) + lane * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sS[j] = st[j];
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (tid < 2 * WN) {
+      const int which = tid >> 6, col = tid & 63;
+      const int idx = ((col & 31) >> 2) * 8 + which * 4 + (col & 3);   // lane (prow 0, column group) * 8 + entry
+      double tot[2];
+#pragma unroll
+      for (int w = 0; w < 2; ++w) {
+        const ldouble* const p = (const ldouble*)((lfloat*)smem + ((col >> 5) * 2 + w) * ESZ) + idx;
+        double s = 0.;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += p[k * 64];
+        tot[w] = s;
+      }
+      const int n = cb * WN + col;
+      // (block-uniform) image blockIdx / ncb / nbi, and the block's index there: together blockIdx / ncb
+      if (n < a.cout) a.part[which * a.astride + (long long)(blockIdx.x / a.ncb) * a.cout + n] = tot[0] + tot[1];
+    }
+  }
 }
 
 // ---- K4w1: the SepConvGRU's 1x5 / 5x1 gate convolutions as 1-D Winograd F(4,5) -------------------------------------------------
@@ -739,9 +835,23 @@ long long pfk_conv_wino_weight_floats(int cin, int cout) {
   return 16LL * cin * ((cout + WN - 1) / WN * WN);
 }
 
+// blocks of 32 tiles per image where the tile list is laid out per image (the statistics form)
+static inline long long wino_blocks_per_image(int H, int W) { return ((long long)((H + 1) / 2) * ((W + 1) / 2) + WT - 1) / WT; }
+
+// What the fused forms add to a launch.  norm: the taps are normalised on load with in_mean / in_rstd [B][cin] (+ in_relu).
+// stats: mean / rstd [B][cout] of the output come out of the epilogue's sums (workspace: pfk_conv_wino_stats_workspace_bytes).
+struct WinoFuse {
+  bool norm, stats;
+  const float* in_mean; const float* in_rstd; int in_relu;
+  float eps; float* out_mean; float* out_rstd; void* workspace; long long workspace_bytes;
+};
+
 // `res`: pfk_conv2d_wino_res_f32 (a residual is required and relu_after_residual honoured); else pfk_conv2d_wino_f32 (both refused)
-static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
+static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream, const WinoFuse* f = nullptr) {
   if (!d) return PFK_ERR_BAD_ARG;
+  const bool norm = f && f->norm, stats = f && f->stats;
+  if (norm && (!f->in_mean || !f->in_rstd)) return PFK_ERR_BAD_ARG;
+  if (stats && (!f->out_mean || !f->out_rstd || !f->workspace || d->residual || d->relu_after_residual)) return PFK_ERR_BAD_ARG;
   if (d->num_src != 1 || d->kh != 3 || d->kw != 3 || d->stride > 1 || d->epilogue != PFK_EPI_LINEAR)
     return PFK_ERR_UNSUPPORTED;
   if (!res && (d->residual || d->relu_after_residual)) return PFK_ERR_UNSUPPORTED;
@@ -765,6 +875,12 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   if (d->cout_active > 0 && d->cout_active < d->cout) {
     if (d->cout_active & (WN - 1)) return PFK_ERR_UNSUPPORTED;
     ncb = d->cout_active / WN;
+    if (stats) return PFK_ERR_UNSUPPORTED;   // every column's sums are written
+  }
+  if (norm && ((reinterpret_cast<uintptr_t>(f->in_mean) | reinterpret_cast<uintptr_t>(f->in_rstd)) & 3u)) return PFK_ERR_ALIGNMENT;
+  if (stats) {
+    if (reinterpret_cast<uintptr_t>(f->workspace) & 7u) return PFK_ERR_ALIGNMENT;
+    if (f->workspace_bytes < pfk_conv_wino_stats_workspace_bytes(d->B, d->H, d->W, d->cout)) return PFK_ERR_BAD_ARG;
   }
   WinoArgs a{};
   a.src = s.ptr; a.ld = s.ld; a.src_bytes = (unsigned)src_bytes;
@@ -772,8 +888,9 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   a.tw = (d->W + 1) / 2;
   a.tpi = a.tw * ((d->H + 1) / 2);
   const long long ntiles = (long long)d->B * a.tpi;
-  const long long nblk = (ntiles + WT - 1) / WT * ncb;
-  if (nblk >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  const long long nbi = wino_blocks_per_image(d->H, d->W);
+  const long long nblk = (stats ? d->B * nbi : (ntiles + WT - 1) / WT) * ncb;
+  if (nblk >= 0x7fffffffLL || ntiles >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
   a.ntiles = (int)ntiles;
   a.nks = s.channels / WK;
   a.weight = d->weight; a.w_bytes = (unsigned)(wfloats * 4);
@@ -783,6 +900,24 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream) {
   a.relu = d->relu ? 1 : 0; a.scale = d->scale;
   a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff; a.out_bytes = (unsigned)out_bytes;
   a.vec = pfk_aligned16(d->out + d->out_coff) && !(d->out_ld & 3) && (!res || (pfk_aligned16(d->residual) && !(d->residual_ld & 3)));
+  if (norm) {
+    a.in_mean = f->in_mean; a.in_rstd = f->in_rstd; a.in_relu = f->in_relu ? 1 : 0;
+    a.cin = s.channels; a.stat_bytes = (unsigned)((long long)d->B * s.channels * 4);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (stats) {
+    a.nbi = (int)nbi;
+    a.part = static_cast<double*>(f->workspace);
+    a.astride = (long long)d->B * nbi * d->cout;
+    if (norm) hipLaunchKernelGGL((conv_gemm_wino_f32_kernel<false, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv_gemm_wino_f32_kernel<false, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+    return pfk_instnorm_finish_parts(a.part, d->B, a.nbi, d->cout, d->H * d->W, f->eps, f->out_mean, f->out_rstd, st);
+  }
+  if (norm) {
+    if (res) return PFK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((conv_gemm_wino_f32_kernel<false, true, false>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+    return pfk_launch_status();
+  }
   if (res) {
     if (d->cout_active > 0 && d->cout_active < d->cout) return PFK_ERR_UNSUPPORTED;
     a.res = d->residual; a.res_ld = d->residual_ld; a.res_bytes = (unsigned)res_bytes; a.relu2 = d->relu_after_residual ? 1 : 0;
@@ -797,6 +932,22 @@ int pfk_conv2d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) { return wi
 
 int pfk_conv2d_wino_res_f32(const pfk_conv_desc* d, pfk_stream_t stream) { return wino_launch(d, true, stream); }
 
+int pfk_conv2d_wino_norm_f32(const pfk_conv_desc* d, const float* in_mean, const float* in_rstd, int in_relu, pfk_stream_t stream) {
+  const WinoFuse f{true, false, in_mean, in_rstd, in_relu, 0.f, nullptr, nullptr, nullptr, 0};
+  return wino_launch(d, false, stream, &f);
+}
+
+long long pfk_conv_wino_stats_workspace_bytes(int B, int H, int W, int cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || cout <= 0) return PFK_ERR_BAD_ARG;
+  return 2LL * B * wino_blocks_per_image(H, W) * cout * (long long)sizeof(double);
+}
+
+int pfk_conv2d_wino_stats_f32(const pfk_conv_desc* d, const float* in_mean, const float* in_rstd, int in_relu, float eps,
+                              float* out_mean, float* out_rstd, void* workspace, long long workspace_bytes, pfk_stream_t stream) {
+  if ((in_mean == nullptr) != (in_rstd == nullptr)) return PFK_ERR_BAD_ARG;
+  const WinoFuse f{in_mean != nullptr, true, in_mean, in_rstd, in_relu, eps, out_mean, out_rstd, workspace, workspace_bytes};
+  return wino_launch(d, false, stream, &f);
+}
 
 
 }  // extern "C"

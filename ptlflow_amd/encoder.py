@@ -13,6 +13,10 @@ state_dict names, its stem launch and its module's ``WINO_MIN_PIXELS``.  Activat
 * fp32, 3x3 stride 1, large launches of BasicEncoder -> Winograd F(2x2,3x3): ``pfk_conv2d_wino_f32`` (in front of an instance
   norm, and a folded-BatchNorm block's conv1) and ``pfk_conv2d_wino_res_f32`` (its conv2: + residual, relu), by ``WINO_MIN_PIXELS``
 * InstanceNorm             -> ``pfk_instnorm_stats_f32`` + ``pfk_norm_apply_f32`` (norm + relu + residual + relu)
+* InstanceNorm around a Winograd launch of the fp32 engine (``fuse_norms``) -> no pass of its own: the norm in front of the
+  convolution is applied to its taps on load and the statistics of the norm behind it are summed in its epilogue
+  (``pfk_conv2d_wino_stats_f32``); the block's last apply normalises a raw residual (the stem's output, the downsample path) in
+  flight (``pfk_norm_apply_res_f32``).  Same bits as the separate passes
 * BatchNorm (eval)         -> folded into the convolution's weights and bias at pack time (no kernel)
 
 The tensor handed back is an NCHW-shaped channels-last view of the last pixel-major buffer, which ``CorrBlock`` and
@@ -45,6 +49,12 @@ EPS = 1e-5
 # every entry wins by more — 64 at one image 1.76x / 1.73x, 96 1.98x / 1.99x, 128 at two 1.62x / 1.58x — and 128 at one image, 1.06x,
 # stays below the line); a width or a size that was not measured keeps the direct kernel
 WINO_MIN_PIXELS: Dict[int, int] = {64: 218 * 512, 96: 109 * 256, 128: 2 * 55 * 128}     # 436 x 1024 frames: all it was measured on
+# `fuse_norms`, a Winograd conv1 behind an already normalised input (nothing to fold on load): width -> the fewest pixels at which
+# the statistics out of its epilogue measured faster than the statistics pass behind the plain launch (scripts/enc_norm_fusion_bench.py,
+# profiles/r16_a_encoder_norms.md §2).  The epilogue leaves one partial row per 32 tiles, and at width 64 the fixed-order reduction
+# over an image's 880 rows outweighs the pass at two images (+5.6 us) and not at sixteen (-22.5 us); 96 and 128 win at both.  With
+# a norm to fold on load the fused launch won at every width and size measured.
+STATS_ONLY_MIN_PIXELS: Dict[int, int] = {64: 16 * 218 * 512}
 
 
 def _out(n: int, s: int) -> int:
@@ -77,6 +87,7 @@ class EncoderEngine:
         self.b16 = conv_precision == "bf16"
         self._ws: Optional[torch.Tensor] = None
         self.winograd = True       # False: the direct kernel everywhere (A/B timing, tests); "always": Winograd wherever its weight exists
+        self.fuse_norms = True     # False: every instance norm as its own statistics and apply launches (A/B timing, tests)
         self.max_matrix_bytes = 2 ** 31 - 1   # 32-bit byte offsets in the convolution kernels
         self.pack(params)
 
@@ -158,16 +169,64 @@ class EncoderEngine:
             self.ops.conv2d_wino_res(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, relu, 1.0, out, residual, True)
         return out
 
+    def _workspace(self, need: int) -> torch.Tensor:
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return self._ws
+
+    def _stats(self, x, B, HW):
+        """(mean, rstd) [B*C] of the instance norm over the fp32 pixel-major buffer x, by the statistics pass"""
+        C = x.shape[1]
+        mean = torch.empty(B * C, device=self.device, dtype=torch.float32)
+        rstd = torch.empty(B * C, device=self.device, dtype=torch.float32)
+        self.ops.instnorm_stats(x, B, HW, EPS, mean, rstd, self._workspace(self.ops.instnorm_workspace_bytes(B, C)))
+        return mean, rstd
+
+    def _wino_stats(self, x, xst, B, H, W, key, cout):
+        """a Winograd convolution in front of an instance norm -> (raw output, its (mean, rstd)), the statistics out of the epilogue;
+        `xst` = (mean, rstd, relu): x is the raw output of the convolution before, normalised on load"""
+        out = torch.empty(B * H * W, cout, device=self.device, dtype=torch.float32)
+        mean = torch.empty(B * cout, device=self.device, dtype=torch.float32)
+        rstd = torch.empty(B * cout, device=self.device, dtype=torch.float32)
+        im, ir, irelu = xst if xst is not None else (None, None, False)
+        self.ops.conv2d_wino_stats(x, B, H, W, self.w[key + ".ww"], self.w[key + ".b"], cout, out, im, ir, irelu, EPS, mean, rstd,
+                                   self._workspace(self.ops.conv_wino_stats_workspace_bytes(B, H, W, cout)))
+        return out, (mean, rstd)
+
+    def _block_fused(self, x, xst, B, H, W, name, cout, stride, ds):
+        """`_block` of the fp32 instance-norm engine with the norm passes folded into the Winograd launches around them.  A raw
+        buffer travels with its statistics: `xst` = (mean, rstd, relu) where x is the raw stem output (layer1.0), else None.  A
+        convolution on the direct kernel keeps its separate passes, and every step rounds as they do: `_block`'s bits."""
+        Ho, Wo = _out(H, stride), _out(W, stride)
+        k1, k2 = f"{name}.conv1", f"{name}.conv2"
+        if stride == 1 and self._use_wino(k1, cout, B * H * W) and (xst is not None or B * H * W >= STATS_ONLY_MIN_PIXELS.get(cout, 0)):
+            y, yst = self._wino_stats(x, xst, B, H, W, k1, cout)
+        else:
+            assert xst is None
+            y = self._conv3(x, B, H, W, k1, cout) if stride == 1 else self._conv(x, B, H, W, 3, k1, cout, stride)
+            yst = self._stats(y, B, Ho * Wo)
+        if self._use_wino(k2, cout, B * Ho * Wo):
+            z, zst = self._wino_stats(y, (*yst, True), B, Ho, Wo, k2, cout)
+        else:
+            self.ops.norm_apply(y, *yst, None, y, B, Ho * Wo, True, False)
+            z = self._conv3(y, B, Ho, Wo, k2, cout)
+            zst = self._stats(z, B, Ho * Wo)
+        if ds:
+            x = self._conv(x, B, H, W, 1, f"{name}.ds", cout, stride)
+            xst = (*self._stats(x, B, Ho * Wo), False)
+        if xst is None:
+            self.ops.norm_apply(z, *zst, x, z, B, Ho * Wo, True, True)
+        else:
+            self.ops.norm_apply_res(z, *zst, x, *xst, z, B, Ho * Wo, True, True)
+        return z
+
     def _inorm(self, x, B, HW, relu, residual=None, relu2=False):
         """InstanceNorm2d (+relu, + residual add + relu) in place on the pixel-major buffer x — fp32 rows, or the bf16 rows of the K8b
         path (only the stem, a VALU / fp32-MFMA kernel, hands over fp32 rows there: those are normalised into a fresh bf16 buffer)."""
         C = x.shape[1]
-        need = self.ops.instnorm_workspace_bytes(B, C)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
         mean = torch.empty(B * C, device=self.device, dtype=torch.float32)
         rstd = torch.empty(B * C, device=self.device, dtype=torch.float32)
-        self.ops.instnorm_stats(x, B, HW, EPS, mean, rstd, self._ws)
+        self.ops.instnorm_stats(x, B, HW, EPS, mean, rstd, self._workspace(self.ops.instnorm_workspace_bytes(B, C)))
         out = torch.empty(x.shape[0], C, device=self.device, dtype=torch.bfloat16) if (self.b16 and x.dtype != torch.bfloat16) else x
         self.ops.norm_apply(x, mean, rstd, residual, out, B, HW, relu, relu2)      # (bf16 rows: in place, like the fp32 path)
         return out
@@ -235,13 +294,22 @@ class EncoderEngine:
         stem_b16 = self.b16 and self.stem_dim in (32, 64)
         x = torch.empty(B * H1 * W1, self.stem_dim, device=self.device, dtype=torch.bfloat16 if stem_b16 else torch.float32)
         self._stem(img, x)
-        if self.norm == "instance":
+        # the norm passes folded into the Winograd launches: the fp32 BasicEncoder / ResNet engines with instance norm
+        fused = self.fuse_norms and self.norm == "instance" and self.nsplit == 0 and not self.b16 and not self.small
+        xst = None
+        name0, _, cout0, stride0, _ = self.blocks[0]
+        if fused and stride0 == 1 and self._use_wino(f"{name0}.conv1", cout0, B * H1 * W1):
+            xst = (*self._stats(x, B, H1 * W1), True)      # the stem's output stays raw: the first block normalises it on load
+        elif self.norm == "instance":
             x = self._inorm(x, B, H1 * W1, relu=True)
         elif self.b16 and not stem_b16:
             x = x.to(torch.bfloat16)
         h, w = H1, W1
         for name, _cin, cout, stride, ds in self.blocks:
-            x = self._block(x, B, h, w, name, cout, stride, ds)
+            if fused:
+                x, xst = self._block_fused(x, xst, B, h, w, name, cout, stride, ds), None
+            else:
+                x = self._block(x, B, h, w, name, cout, stride, ds)
             h, w = _out(h, stride), _out(w, stride)
         y = self._conv(x, B, h, w, 1, "out", self.out_dim, fp32_out=True)
         return y.view(B, h, w, self.out_dim).permute(0, 3, 1, 2)
