@@ -41,6 +41,7 @@ HIP_SOURCES = [
     ("pfk_wino.hip", []),                     # Winograd F(2x2,3x3) for the update block's 3x3 convolutions
     ("pfk_corr.hip", ["-ffp-contract=off"]),  # index-exact coordinate arithmetic
     ("pfk_misc.hip", ["-ffp-contract=off"]),
+    ("pfk_upsample.hip", ["-ffp-contract=off"]),  # convex upsampling, forward and backward: the arithmetic of pfk_upsample.h, never contracted
     ("pfk_attn.hip", ["-ffp-contract=off"]),  # K12c: softmax backward, transposed packs of GMA's attention map
     ("pfk_altcorr.hip", []),
     ("pfk_encoder.hip", []),
@@ -120,7 +121,8 @@ def _run(cmd) -> None:
 
 def build_libpfk(force: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h", CSRC / "pfk_wgrad_reduce.h"]
+    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h", CSRC / "pfk_upsample.h",
+               CSRC / "pfk_wgrad_reduce.h"]
     tree = source_hash()
     objs, jobs = [], []
     for src, extra in HIP_SOURCES:

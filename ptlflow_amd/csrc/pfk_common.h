@@ -8,6 +8,16 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+__device__ __forceinline__ f32x4 load4_widen(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 load4_widen(const __bf16* p) {      // four bf16 (8 bytes) -> fp32, exact
+  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  const u32x2 w = *reinterpret_cast<const u32x2*>(p);
+  f32x4 v;
+  v.x = __builtin_bit_cast(float, w[0] << 16); v.y = __builtin_bit_cast(float, w[0] & 0xffff0000u);
+  v.z = __builtin_bit_cast(float, w[1] << 16); v.w = __builtin_bit_cast(float, w[1] & 0xffff0000u);
+  return v;
+}
+
 #define PFK_WAVE 64
 
 static inline bool pfk_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -37,6 +47,23 @@ static inline bool pfk_debug_knobs_enabled() {
 
 static inline int pfk_launch_status() {
   return hipGetLastError() == hipSuccess ? PFK_OK : PFK_ERR_LAUNCH;
+}
+
+// Division of n < 2^31 by a launch-invariant d through a host-made multiplier (Granlund & Montgomery 1994, N = 32):
+//   l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1,  n / d = (mulhi(mul, n) + n) >> l   (no overflow: mulhi(..) <= n < 2^31)
+// three instructions instead of the ~30 of a runtime 32-bit (or ~100 of a 64-bit) division.
+static inline void fastdiv_make(unsigned d, unsigned& mul, int& sh) {
+  int l = 0;
+  while ((1ull << l) < d) ++l;
+  mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1ull);
+  sh = l;
+}
+__host__ __device__ __forceinline__ unsigned fastdiv_u32(unsigned n, unsigned mul, int sh) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (__umulhi(n, mul) + n) >> sh;
+#else
+  return (unsigned)((((unsigned long long)n * mul) >> 32) + n) >> sh;
+#endif
 }
 
 // pfk_encoder.hip, for the Winograd kernel's statistics epilogue (pfk_wino.hip): part = sums, then sums of squares, each

@@ -78,23 +78,6 @@ __device__ __forceinline__ void tile_of(int bid, int tiles_m, int tiles_n, int S
   tile_n = n_base + l2 - (l2 / wb) * wb;
 }
 
-// Division of n < 2^31 by a launch-invariant d through a host-made multiplier (Granlund & Montgomery 1994, N = 32):
-//   l = ceil(log2 d), mul = floor(2^32 (2^l - d) / d) + 1,  n / d = (mulhi(mul, n) + n) >> l   (no overflow: mulhi(..) <= n < 2^31)
-// three instructions instead of the ~30 of a runtime 32-bit (or ~100 of a 64-bit) division.
-static inline void fastdiv_make(unsigned d, unsigned& mul, int& sh) {
-  int l = 0;
-  while ((1ull << l) < d) ++l;
-  mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1ull);
-  sh = l;
-}
-__host__ __device__ __forceinline__ unsigned fastdiv_u32(unsigned n, unsigned mul, int sh) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (__umulhi(n, mul) + n) >> sh;
-#else
-  return (unsigned)((((unsigned long long)n * mul) >> 32) + n) >> sh;
-#endif
-}
-
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // GemmArgs::relu == ACT_GELU: the LINEAR epilogue applies the exact GELU where it would apply relu (PFK_EPI_LINEAR_GELU of
@@ -358,43 +341,5 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[MT][NT]) {
 // pfk_gemm_bf.hip: split-bf16 implicit GEMM (nsplit 1..3)
 extern int g_bf_cfg;
 int launch_bf(const GemmArgs& a, int epi, int nsplit, hipStream_t st);
-
-// One (pixel, sub-pixel) of the fused epilogue: the nine logits -> softmax -> convex combination of the neighbours' flows, with the
-// arithmetic of the unfused pair operation for operation — conv epilogue (pfk_gemm.h, LINEAR): + bias, x scale; convex_upsample_kernel
-// (pfk_misc.hip, compiled with -ffp-contract=off): max, exp, sum in tap order, one reciprocal, multiply then add.  In the unfused
-// pair the mask goes through memory between the two kernels and pfk_misc.hip never contracts, so NOTHING here may be contracted
-// into an FMA either: this translation unit is compiled with contraction on and HIP's __fmul_rn / __fadd_rn are plain operators
-// (they do not stop it), hence the pragma.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void mask_upsample_combine(const float (&m_in)[9], const f32x2* nfp, float& ox, float& oy) {
-#pragma clang fp contract(off)
-  float m[9];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { m[k] = m_in[k]; mx = fmaxf(mx, m[k]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { m[k] = expf(m[k] - mx); sum = sum + m[k]; }
-  const float inv = 1.0f / sum;
-  float ax = 0.f, ay = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const f32x2 f = nfp[k];
-    const float wk = m[k] * inv;
-    const float tx = wk * f[0], ty = wk * f[1];
-    ax = ax + tx;
-    ay = ay + ty;
-  }
-  ox = ax;
-  oy = ay;
-}
-// the conv epilogue's + bias, x scale on one logit, un-contracted
-__device__ __forceinline__ float mask_logit(float acc, float bias, float sc) {
-#pragma clang fp contract(off)
-  float v = acc + bias;
-  v = v * sc;
-  return v;
-}
-
 
 }  // namespace pfkg

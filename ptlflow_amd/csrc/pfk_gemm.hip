@@ -22,6 +22,7 @@
 // bias, relu, scale, sigmoid gates + r*h, tanh + GRU blend, and write straight into channel
 // slices of pixel-major buffers (no torch.cat).
 #include "pfk_gemm.h"
+#include "pfk_upsample.h"
 #ifndef PP_EXP
 #define PP_EXP 0
 #endif
@@ -389,11 +390,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
 // The host permutes the weight / bias rows to [quarter (4)][tile (5)][32] (zero rows for the pad tap), which makes the block's B
 // rows the plain range [quarter*160, quarter*160 + 160) of the 2-stage kernel's stager.  K loop = variant 1's on the swizzled
 // layout (same K order per output element as every other tile shape: the logits are bit-identical to the unfused launch's), 8
-// K-steps of 80 MFMAs per wave for the 256 input channels; LDS 2 x (128 + 160) x 32 floats = 72 KB.  Epilogue arithmetic = the
-// unfused pair's, operation for operation => bit-identical flow.
+// K-steps of 80 MFMAs per wave for the 256 input channels; LDS 2 x (128 + 160) x 32 floats = 72 KB.  The epilogue is
+// mask_upsample_epilogue of pfk_upsample.h, the one copy of the unfused pair's arithmetic => bit-identical flow; the K8b form of this
+// kernel in pfk_gemm_b16.hip calls the same function.
 // -------------------------------------------------------------------------------------------------
-// (mask_upsample_combine / mask_logit — one (pixel, sub-pixel) of the fused epilogue — live in pfk_gemm.h: the K8b form of this kernel
-//  in pfk_gemm_b16.hip shares them)
 template <int MT, int NT, int LD>
 __device__ __forceinline__ void mma_rest_ld(f32x16 (&acc)[MT][NT], Frags<MT, NT>& f, const float* cA, const float* cB,
                                             const int (&ko)[4]) {
@@ -462,68 +462,9 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_kernel(const GemmArgs a)
     __syncthreads();
   }
 
-  // ---- epilogue.  8 * flow of every pixel's 3x3 neighbourhood (zero outside the image: F.unfold's padding) -> LDS
-  f32x2* nf = reinterpret_cast<f32x2*>(smem);     // [BM][9]; every stage read sits behind the loop's final barrier
-  const unsigned H = (unsigned)a.H, W = (unsigned)a.W;
-  for (int e = tid; e < BM * 9; e += 256) {
-    const int pl = e / 9, k = e - pl * 9;
-    const unsigned p = (unsigned)m0 + (unsigned)pl;
-    f32x2 v = {0.f, 0.f};
-    if ((long long)p < a.M) {
-      const unsigned prow = fastdiv_u32(p, a.wo_mul, a.wo_sh);          // b*H + y
-      const unsigned bimg = fastdiv_u32(prow, a.ho_mul, a.ho_sh);
-      const int x = (int)(p - prow * W), y = (int)(prow - bimg * H);
-      const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-      if ((unsigned)yy < H && (unsigned)xx < W) {
-        const float* f = a.mu_flow + ((size_t)(bimg * H + (unsigned)yy) * W + (unsigned)xx) * (size_t)a.mu_flow_ld;
-        v[0] = 8.0f * f[0];      // exact (a power of two)
-        v[1] = 8.0f * f[1];
-      }
-    }
-    nf[e] = v;
-  }
-  __syncthreads();
-
-  const int col = lane & 31;
-  const int odd = col >> 4;                          // this lane's own taps are 2j + odd
-  const int s = quarter * 16 + (col & 15), sy = s >> 3, sx = s & 7;
-  float bias[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) bias[j] = a.bias != nullptr ? a.bias[n0 + j * 32 + col] : 0.f;
-  const float sc = a.scale;
-  const size_t HW8 = (size_t)H * W * 64;
-  // The two lanes of a pair split the ROWS: of every row pair (r, r + 1) the lane with the even taps finishes row r, its partner
-  // row r + 1 — one exchange per tile and row pair serves both (each lane sends the logits of the row the other finishes and
-  // receives those of its own), and each lane runs the softmax (9 expf) for 8 of the wave tile's 16 rows instead of all 16.
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const int rr = r + odd;                          // the row this lane finishes
-    const int row = wm0 + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
-    const unsigned p = (unsigned)m0 + (unsigned)row;
-    float own[NT], oth[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const float l0 = mask_logit(acc[0][j][r], bias[j], sc), l1 = mask_logit(acc[0][j][r + 1], bias[j], sc);
-      own[j] = odd ? l1 : l0;                        // tap 2j + odd of my row
-      oth[j] = __shfl_xor(odd ? l0 : l1, 16, 64);    // send the partner's row, receive tap 2j + (1 - odd) of mine
-    }
-    float m[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int j = k >> 1;
-      m[k] = ((k & 1) == odd) ? own[j] : oth[j];     // (tap 9 — tile 4 of the odd lanes — is the zero pad row: never read)
-    }
-    float ox, oy;
-    mask_upsample_combine(m, nf + row * 9, ox, oy);
-    if ((long long)p < a.M) {
-      const unsigned prow = fastdiv_u32(p, a.wo_mul, a.wo_sh);
-      const unsigned bimg = fastdiv_u32(prow, a.ho_mul, a.ho_sh);
-      const unsigned x = p - prow * W, y = prow - bimg * H;
-      const size_t o = (size_t)(8 * y + (unsigned)sy) * (8 * W) + 8 * x + (unsigned)sx;
-      a.mu_out[((size_t)bimg * 2 + 0) * HW8 + o] = ox;
-      a.mu_out[((size_t)bimg * 2 + 1) * HW8 + o] = oy;
-    }
-  }
+  // ---- epilogue (pfk_upsample.h): the staging LDS becomes the flow neighbourhoods; every stage read sits behind the loop's final barrier
+  mask_upsample_epilogue<false>(acc, reinterpret_cast<f32x2*>(smem), a.bias, a.scale, a.mu_flow, a.mu_flow_ld, a.mu_out, a.H, a.W, a.M,
+                                a.wo_mul, a.wo_sh, a.ho_mul, a.ho_sh, m0, quarter, wm0);
 }
 
 // -------------------------------------------------------------------------------------------------

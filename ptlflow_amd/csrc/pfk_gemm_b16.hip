@@ -17,6 +17,7 @@
 // `s_waitcnt vmcnt(pieces per step)` + a raw `s_barrier` at the end of step j retire step j + 1 while step j + 2 stays in flight
 // (cdna_hip_programming.md §5: LDS-DMA survives a raw barrier, `__syncthreads()` would drain it).
 #include "pfk_gemm.h"
+#include "pfk_upsample.h"
 
 #include <utility>
 
@@ -715,8 +716,8 @@ int launch_b16(const B16Args& a0, int epi, hipStream_t st) {
 // LDS-DMA (64-channel K-steps, two stages of (128 + 160) x 128 B = 72 KB: two blocks per CU), products on v_mfma_f32_32x32x16_bf16.
 // On this path the unfused pair writes 65 MB of bf16 logits per iteration at batch 8 and reads them back on a side stream next to the
 // main stream's HBM-bound launches; here the logits never leave the registers.  Each logit is rounded to bf16 exactly where the unfused
-// launch stores it ((acc + bias) * scale, round to nearest even) and the epilogue is the shared mask_upsample_combine: the 8x flow is
-// bit-identical to pfk_conv2d_b16 (bf16 out) + pfk_convex_upsample_pm_b16.
+// launch stores it ((acc + bias) * scale, round to nearest even) and the epilogue is mask_upsample_epilogue<true> (pfk_upsample.h):
+// the 8x flow is bit-identical to pfk_conv2d_b16 (bf16 out) + pfk_convex_upsample_pm_b16.
 // -------------------------------------------------------------------------------------------------
 struct MuB16Args {
   const void* x; int x_ld, cin;          // bf16 [M][x_ld]
@@ -799,66 +800,9 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_b16_kernel(const MuB16Ar
     __builtin_amdgcn_s_barrier();      // every wave is done with `cur` before the step after next lands in it
   }
 
-  // ---- epilogue (pfk_gemm.hip::mask_upsample_kernel's, with the logits rounded to bf16 as the unfused launch stores them)
-  f32x2* nf = reinterpret_cast<f32x2*>(smem_mu);     // [BM][9]: 8 x flow of every pixel's 3x3 neighbourhood, zero outside the image
-  const unsigned H = (unsigned)a.H, W = (unsigned)a.W;
-  for (int e = tid; e < BM * 9; e += 256) {
-    const int pl = e / 9, k = e - pl * 9;
-    const unsigned p = (unsigned)m0 + (unsigned)pl;
-    f32x2 v = {0.f, 0.f};
-    if ((long long)p < a.M) {
-      const unsigned prow = fastdiv_u32(p, a.wo_mul, a.wo_sh);          // b*H + y
-      const unsigned bimg = fastdiv_u32(prow, a.ho_mul, a.ho_sh);
-      const int x = (int)(p - prow * W), y = (int)(prow - bimg * H);
-      const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-      if ((unsigned)yy < H && (unsigned)xx < W) {
-        const float* f = a.flow + ((size_t)(bimg * H + (unsigned)yy) * W + (unsigned)xx) * (size_t)a.flow_ld;
-        v[0] = 8.0f * f[0];
-        v[1] = 8.0f * f[1];
-      }
-    }
-    nf[e] = v;
-  }
-  __syncthreads();
-
-  const int col = lane & 31;
-  const int odd = col >> 4;                          // this lane's own taps are 2j + odd
-  const int s = quarter * 16 + (col & 15), sy = s >> 3, sx = s & 7;
-  const int wm0 = wid * 32;
-  float bias[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) bias[j] = a.bias != nullptr ? a.bias[n0 + j * 32 + col] : 0.f;
-  const float sc = a.scale;
-  const size_t HW8 = (size_t)H * W * 64;
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    const int rr = r + odd;                          // the row this lane finishes
-    const int row = wm0 + (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
-    const unsigned p = (unsigned)m0 + (unsigned)row;
-    float own[NT], oth[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const float l0 = (float)(__bf16)mask_logit(acc[0][j][r], bias[j], sc), l1 = (float)(__bf16)mask_logit(acc[0][j][r + 1], bias[j], sc);
-      own[j] = odd ? l1 : l0;                        // tap 2j + odd of my row
-      oth[j] = __shfl_xor(odd ? l0 : l1, 16, 64);    // send the partner's row, receive tap 2j + (1 - odd) of mine
-    }
-    float m[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int j = k >> 1;
-      m[k] = ((k & 1) == odd) ? own[j] : oth[j];
-    }
-    float ox, oy;
-    mask_upsample_combine(m, nf + row * 9, ox, oy);
-    if ((long long)p < a.M) {
-      const unsigned prow = fastdiv_u32(p, a.wo_mul, a.wo_sh);
-      const unsigned bimg = fastdiv_u32(prow, a.ho_mul, a.ho_sh);
-      const unsigned x = p - prow * W, y = prow - bimg * H;
-      const size_t o = (size_t)(8 * y + (unsigned)sy) * (8 * W) + 8 * x + (unsigned)sx;
-      a.out[((size_t)bimg * 2 + 0) * HW8 + o] = ox;
-      a.out[((size_t)bimg * 2 + 1) * HW8 + o] = oy;
-    }
-  }
+  // ---- epilogue (pfk_upsample.h): K13's, with the logits rounded to bf16 as the unfused launch stores them
+  mask_upsample_epilogue<true>(acc, reinterpret_cast<f32x2*>(smem_mu), a.bias, a.scale, a.flow, a.flow_ld, a.out, a.H, a.W, a.M, a.wo_mul,
+                               a.wo_sh, a.ho_mul, a.ho_sh, m0, quarter, wid * 32);
 }
 
 int b16_ktot(const pfk_conv_b16_desc* d) {

@@ -1,21 +1,10 @@
 // Small direct (VALU) kernels around the MFMA convolutions: the 2-channel 7x7 flow convolution,
-// the 2-output flow head fused with the coordinate update, convex upsampling, layout changes.
+// the 2-output flow head fused with the coordinate update, bilinear upsampling, layout changes.
 // None of them is GEMM-shaped enough to pay for a matrix-core tile; they are bandwidth/latency
 // bound and written for coalesced 64-lane access.
 #include "pfk_common.h"
 
 namespace {
-
-__device__ __forceinline__ f32x4 load4_widen(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 load4_widen(const __bf16* p) {      // four bf16 (8 bytes) -> fp32, exact
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-  f32x4 v;
-  v.x = __builtin_bit_cast(float, w[0] << 16); v.y = __builtin_bit_cast(float, w[0] & 0xffff0000u);
-  v.z = __builtin_bit_cast(float, w[1] << 16); v.w = __builtin_bit_cast(float, w[1] & 0xffff0000u);
-  return v;
-}
-
 
 // out[p][co] = relu?( bias[co] + sum_{tap} in[p+off][0]*w[tap][0][co] + in[p+off][1]*w[tap][1][co] )
 // raft/update.py:100,107 (convf1).  Thread per (pixel, co); the flow taps are wave-broadcast
@@ -354,213 +343,6 @@ __global__ __launch_bounds__(256) void upflow8_kernel(const float* __restrict__ 
   }
 }
 
-// RAFT.upsample_flow (raft.py:112-123).  One wave per coarse pixel, lane = sy*8 + sx: the nine
-// mask reads are 256-byte coalesced rows, the 3x3 flow neighbourhood is broadcast.
-__global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __restrict__ flow, int flow_ld,
-                                                              const float* __restrict__ mask,
-                                                              int mask_ld, float* __restrict__ out,
-                                                              long long M, int H, int W) {
-  const int lane = threadIdx.x & 63;
-  const long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= M) return;
-  const long long hw = (long long)H * W;
-  const long long b = p / hw;
-  const int pix = (int)(p - b * hw);
-  const int y = pix / W, x = pix - y * W;
-  const float* mrow = mask + p * mask_ld + lane;
-  float m[9];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { m[k] = mrow[k * 64]; mx = fmaxf(mx, m[k]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { m[k] = expf(m[k] - mx); sum += m[k]; }
-  const float inv = 1.0f / sum;
-  float ox = 0.f, oy = 0.f;
-  const float* fx = flow + (b * 2 + 0) * hw;
-  const float* fy = flow + (b * 2 + 1) * hw;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-    float vx = 0.f, vy = 0.f;
-    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-      if (flow_ld > 0) {   // pixel-major: flow[p][0..1] (the update engine's hx slice)
-        const float* f = flow + (b * hw + (long long)yy * W + xx) * flow_ld;
-        vx = 8.0f * f[0];
-        vy = 8.0f * f[1];
-      } else {             // NCHW
-        vx = 8.0f * fx[yy * W + xx];
-        vy = 8.0f * fy[yy * W + xx];
-      }
-    }
-    const float wk = m[k] * inv;
-    ox += wk * vx;
-    oy += wk * vy;
-  }
-  const int sy = lane >> 3, sx = lane & 7;
-  const long long HW8 = hw * 64;
-  const long long o = (long long)(8 * y + sy) * (8 * W) + 8 * x + sx;
-  out[(b * 2 + 0) * HW8 + o] = ox;
-  out[(b * 2 + 1) * HW8 + o] = oy;
-}
-
-// The same arithmetic, four coarse pixels per wave: lane = pixel-in-group * 16 + float4 index inside the 64 mask floats of a tap
-// (sy = idx >> 1, sx = 4 * (idx & 1) .. +3), so a tap is ONE 1 KiB load per wave (9 per 4 pixels instead of 36 of 256 bytes) and an
-// output row piece of the group is 128 contiguous bytes.  Every output element runs the scalar kernel's operation sequence
-// (max, exp, sum, one reciprocal, taps in order): the two kernels produce the same bits.  Needs 16-byte aligned mask rows.
-// TM = __bf16: the mask as the K8b mask head writes it (2-byte logits, widened exactly; half the bytes of this HBM-bound kernel).
-template <typename TM = float>
-__global__ __launch_bounds__(256) void convex_upsample4_kernel(const float* __restrict__ flow, int flow_ld,
-                                                               const TM* __restrict__ mask,
-                                                               int mask_ld, float* __restrict__ out,
-                                                               long long M, int H, int W) {
-  const int lane = threadIdx.x & 63;
-  const long long p = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  if (p >= M) return;
-  const int idx = lane & 15;
-  const long long hw = (long long)H * W;
-  const long long b = p / hw;
-  const int pix = (int)(p - b * hw);
-  const int y = pix / W, x = pix - y * W;
-  const TM* mrow = mask + p * mask_ld + idx * 4;
-  f32x4 m[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) m[k] = load4_widen(mrow + k * 64);
-  float vx[9], vy[9];
-  const float* fx = flow + (b * 2 + 0) * hw;
-  const float* fy = flow + (b * 2 + 1) * hw;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-    vx[k] = 0.f; vy[k] = 0.f;
-    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-      if (flow_ld > 0) {
-        const float* f = flow + (b * hw + (long long)yy * W + xx) * flow_ld;
-        vx[k] = 8.0f * f[0];
-        vy[k] = 8.0f * f[1];
-      } else {
-        vx[k] = 8.0f * fx[yy * W + xx];
-        vy[k] = 8.0f * fy[yy * W + xx];
-      }
-    }
-  }
-  f32x4 ox, oy;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) mx = fmaxf(mx, m[k][c]);
-    float e[9], sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { e[k] = expf(m[k][c] - mx); sum += e[k]; }
-    const float inv = 1.0f / sum;
-    float ax = 0.f, ay = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float wk = e[k] * inv;
-      ax += wk * vx[k];
-      ay += wk * vy[k];
-    }
-    ox[c] = ax;
-    oy[c] = ay;
-  }
-  const int sy = idx >> 1, sx = (idx & 1) * 4;
-  const long long HW8 = hw * 64;
-  const long long o = (long long)(8 * y + sy) * (8 * W) + 8 * x + sx;
-  *reinterpret_cast<f32x4*>(out + (b * 2 + 0) * HW8 + o) = ox;
-  *reinterpret_cast<f32x4*>(out + (b * 2 + 1) * HW8 + o) = oy;
-}
-
-// SEARAFT.upsample_data (sea_raft.py:147-163): convex_upsample4_kernel's flow, operation for operation (same bits), plus the
-// same convex combination of the zero-padded 3x3 neighbourhood of `n` info channels (no factor 8) -> info_out [B][n][8H][8W].
-// TM = __bf16: the mask as the K8b mask head writes it; the flow is then convex_upsample4_kernel<__bf16>'s, bit for bit.
-constexpr int UP_MAX_INFO = 8;
-template <typename TM = float>
-__global__ __launch_bounds__(256) void convex_upsample_info4_kernel(const float* __restrict__ flow, int flow_ld,
-                                                                    const float* __restrict__ info, int info_ld, int n_info,
-                                                                    const TM* __restrict__ mask, int mask_ld,
-                                                                    float* __restrict__ out, float* __restrict__ info_out,
-                                                                    long long M, int H, int W) {
-  const int lane = threadIdx.x & 63;
-  const long long p = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  if (p >= M) return;
-  const int idx = lane & 15;
-  const long long hw = (long long)H * W;
-  const long long b = p / hw;
-  const int pix = (int)(p - b * hw);
-  const int y = pix / W, x = pix - y * W;
-  const TM* mrow = mask + p * mask_ld + idx * 4;
-  f32x4 m[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) m[k] = load4_widen(mrow + k * 64);
-  float vx[9], vy[9], vi[9][UP_MAX_INFO];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-    vx[k] = 0.f; vy[k] = 0.f;
-#pragma unroll
-    for (int c = 0; c < UP_MAX_INFO; ++c) vi[k][c] = 0.f;
-    if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-      const long long q = b * hw + (long long)yy * W + xx;
-      const float* f = flow + q * flow_ld;
-      vx[k] = 8.0f * f[0];
-      vy[k] = 8.0f * f[1];
-      const float* fi = info + q * info_ld;
-#pragma unroll
-      for (int c = 0; c < UP_MAX_INFO; ++c)
-        if (c < n_info) vi[k][c] = fi[c];
-    }
-  }
-  f32x4 ox, oy, oi[UP_MAX_INFO];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) mx = fmaxf(mx, m[k][c]);
-    float e[9], sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { e[k] = expf(m[k][c] - mx); sum += e[k]; }
-    const float inv = 1.0f / sum;
-    float ax = 0.f, ay = 0.f, ai[UP_MAX_INFO];
-#pragma unroll
-    for (int i = 0; i < UP_MAX_INFO; ++i) ai[i] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float wk = e[k] * inv;
-      ax += wk * vx[k];
-      ay += wk * vy[k];
-#pragma unroll
-      for (int i = 0; i < UP_MAX_INFO; ++i) ai[i] += wk * vi[k][i];
-    }
-    ox[c] = ax;
-    oy[c] = ay;
-#pragma unroll
-    for (int i = 0; i < UP_MAX_INFO; ++i) oi[i][c] = ai[i];
-  }
-  const int sy = idx >> 1, sx = (idx & 1) * 4;
-  const long long HW8 = hw * 64;
-  const long long o = (long long)(8 * y + sy) * (8 * W) + 8 * x + sx;
-  *reinterpret_cast<f32x4*>(out + (b * 2 + 0) * HW8 + o) = ox;
-  *reinterpret_cast<f32x4*>(out + (b * 2 + 1) * HW8 + o) = oy;
-#pragma unroll
-  for (int i = 0; i < UP_MAX_INFO; ++i)
-    if (i < n_info) *reinterpret_cast<f32x4*>(info_out + (b * n_info + i) * HW8 + o) = oi[i];
-}
-
-int launch_convex_upsample(const float* flow, int flow_ld, const float* mask, int mask_ld, float* out, long long M, int H, int W,
-                           hipStream_t st) {
-  if (pfk_aligned16(mask) && pfk_aligned16(out) && (mask_ld & 3) == 0) {
-    const long long blocks = (M + 15) / 16;
-    if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(convex_upsample4_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, flow, flow_ld, mask, mask_ld, out, M, H, W);
-  } else {
-    const long long blocks = (M + 3) / 4;
-    if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(convex_upsample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, flow, flow_ld, mask, mask_ld, out, M, H, W);
-  }
-  return pfk_launch_status();
-}
-
 // 32x32 LDS tile transposes between NCHW ([C][HW] per image) and pixel-major ([HW][ld]).
 __global__ __launch_bounds__(256) void nchw_to_pm_kernel(const float* __restrict__ in,
                                                          float* __restrict__ out, int out_ld,
@@ -814,12 +596,6 @@ int pfk_flow_from_coords_f32(const float* coords0, const float* coords1, float* 
   return pfk_launch_status();
 }
 
-int pfk_convex_upsample_f32(const float* flow, const float* mask, int mask_ld, float* out, int B,
-                            int H, int W, pfk_stream_t stream) {
-  if (!flow || !mask || !out || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
-  return launch_convex_upsample(flow, 0, mask, mask_ld, out, (long long)B * H * W, H, W, static_cast<hipStream_t>(stream));
-}
-
 int pfk_upflow8_f32(const float* coords0, const float* coords1, float* out, int B, int H, int W, pfk_stream_t stream) {
   if (!coords0 || !coords1 || !out || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
   const long long n = (long long)B * 64 * H * W;
@@ -827,54 +603,6 @@ int pfk_upflow8_f32(const float* coords0, const float* coords1, float* out, int 
   if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(upflow8_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), coords0, coords1, out,
                      B, H, W);
-  return pfk_launch_status();
-}
-
-int pfk_convex_upsample_pm_b16(const float* flow_pm, int flow_ld, const void* mask_bf16, int mask_ld, float* out,
-                               int B, int H, int W, pfk_stream_t stream) {
-  if (!flow_pm || !mask_bf16 || !out || B <= 0 || H <= 0 || W <= 0 || mask_ld < 576 || flow_ld < 2) return PFK_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(mask_bf16) & 7u) || !pfk_aligned16(out) || (mask_ld & 3)) return PFK_ERR_ALIGNMENT;
-  const long long M = (long long)B * H * W;
-  const long long blocks = (M + 15) / 16;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(convex_upsample4_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm, flow_ld,
-                     static_cast<const __bf16*>(mask_bf16), mask_ld, out, M, H, W);
-  return pfk_launch_status();
-}
-
-int pfk_convex_upsample_pm_f32(const float* flow_pm, int flow_ld, const float* mask, int mask_ld, float* out,
-                               int B, int H, int W, pfk_stream_t stream) {
-  if (!flow_pm || !mask || !out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
-  return launch_convex_upsample(flow_pm, flow_ld, mask, mask_ld, out, (long long)B * H * W, H, W, static_cast<hipStream_t>(stream));
-}
-
-int pfk_convex_upsample_info_pm_f32(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
-                                    const float* mask, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
-                                    pfk_stream_t stream) {
-  if (!flow_pm || !info_pm || !mask || !flow_out || !info_out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0)
-    return PFK_ERR_BAD_ARG;
-  if (n_info < 1 || n_info > UP_MAX_INFO || info_ld < n_info) return PFK_ERR_BAD_ARG;
-  if (!pfk_aligned16(mask) || (mask_ld & 3) || !pfk_aligned16(flow_out) || !pfk_aligned16(info_out)) return PFK_ERR_ALIGNMENT;
-  const long long M = (long long)B * H * W;
-  const long long blocks = (M + 15) / 16;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(convex_upsample_info4_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
-                     flow_ld, info_pm, info_ld, n_info, mask, mask_ld, flow_out, info_out, M, H, W);
-  return pfk_launch_status();
-}
-
-int pfk_convex_upsample_info_pm_b16(const float* flow_pm, int flow_ld, const float* info_pm, int info_ld, int n_info,
-                                    const void* mask_bf16, int mask_ld, float* flow_out, float* info_out, int B, int H, int W,
-                                    pfk_stream_t stream) {
-  if (!flow_pm || !info_pm || !mask_bf16 || !flow_out || !info_out || flow_ld < 2 || mask_ld < 576 || B <= 0 || H <= 0 || W <= 0)
-    return PFK_ERR_BAD_ARG;
-  if (n_info < 1 || n_info > UP_MAX_INFO || info_ld < n_info) return PFK_ERR_BAD_ARG;
-  if (!pfk_aligned16(mask_bf16) || (mask_ld & 7) || !pfk_aligned16(flow_out) || !pfk_aligned16(info_out)) return PFK_ERR_ALIGNMENT;
-  const long long M = (long long)B * H * W;
-  const long long blocks = (M + 15) / 16;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(convex_upsample_info4_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flow_pm,
-                     flow_ld, info_pm, info_ld, n_info, static_cast<const __bf16*>(mask_bf16), mask_ld, flow_out, info_out, M, H, W);
   return pfk_launch_status();
 }
 
