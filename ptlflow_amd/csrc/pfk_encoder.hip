@@ -352,7 +352,7 @@ __global__ __launch_bounds__(1024) void chunk_reduce_kernel(const double* __rest
     if (sl == 0 && c < C) {
       const double m = fin[0] / (double)HW;
       double var = fin[1] / (double)HW - m * m;
-      var = var > 0. ? var : 0.;
+      var = var < 0. ? 0. : var;      // rounding may leave a constant channel's variance below 0; a NaN stays a NaN
       mean[(long long)b * C + c] = (float)m;
       rstd[(long long)b * C + c] = (float)(1.0 / sqrt(var + (double)eps));
     }
@@ -365,7 +365,7 @@ __global__ void instnorm_finish_kernel(const double* __restrict__ sum, const dou
   if (i >= total) return;
   const double m = sum[i] / (double)HW;
   double var = sq[i] / (double)HW - m * m;
-  var = var > 0. ? var : 0.;
+  var = var < 0. ? 0. : var;
   mean[i] = (float)m;
   rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
 }

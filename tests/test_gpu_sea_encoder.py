@@ -39,7 +39,8 @@ def unpm(x, B, H, W):
 @pytest.mark.parametrize("source", ["one", "halves", "two"])
 def test_stem2(gpu, source, B, H, W, relu, out_dtype):
     """Conv2d(3 or 6, 64, 7, stride 2, padding 3): one image pointer, the two channel halves of one [B, 6, H, W] tensor read in place
-    (batch stride 6 H W), two separate images.  9 x 234 x 440: 945 tiles, three rounds of the persistent walk, the last one partial."""
+    (batch stride 6 H W), two separate images.  9 x 234 x 440: 945 tiles, two rounds of the persistent walk (256 workgroups of two
+    groups: 512 tiles a round), the second one partial; tests/test_gpu_encoder_gate.py::test_stem_three_rounds reaches a third."""
     cin = 3 if source == "one" else 6
     torch.manual_seed(B * 1000 + H + cin)
     x = torch.randn(B, cin, H, W)
