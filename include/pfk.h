@@ -339,7 +339,8 @@ int pfk_conv2d_wino_stats_f32(const pfk_conv_desc* d, const float* in_mean, cons
  * than the direct form.  Supported: (kh, kw) = (1, 5) or (5, 1), stride 0 or 1, one or two sources in K order (channels % 8 == 0
  * each), the epilogues PFK_EPI_LINEAR (bias, relu, scale; no residual), PFK_EPI_GRU_ZR and PFK_EPI_GRU_Q exactly as defined above
  * (optional `residual` rows added to the pre-activation, h through h_ld, q updates h in place).  `cout_active` below cout,
- * `relu_after_residual`, any other kernel size, stride, epilogue or source count: PFK_ERR_UNSUPPORTED.  `workspace` and `cout_split`
+ * `relu_after_residual`, any other kernel size, stride, epilogue or source count, a source, and with the gate epilogues `residual`,
+ * h, aux_z or aux_rh, that spans 2 GB or more up to its last pixel's last column: PFK_ERR_UNSUPPORTED.  `workspace` and `cout_split`
  * are ignored (one schedule, no workspace).  Results differ from pfk_conv2d_f32 by fp32 rounding (pre-activation error about 6e-6 at
  * K = 256 with unit-scale operands, several times the direct form's); the same inputs give the same bits on every launch.
  * d->weight = the transformed weight, pfk_conv_wino1d_weight_floats(ktot, cout) floats, 16-byte aligned, ktot = the sources'

@@ -462,6 +462,11 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
 // tiles run down a column, the block's tiles are neighbouring x of one tile row.  The K-steps walk source 0, then source 1 (the
 // torch.cat operands of the gate convolutions), each with its own descriptor and tap offsets.  Epilogues after the lane-local A^T m:
 // LINEAR, GRU_ZR, GRU_Q of include/pfk.h with pfk_gemm.h's arithmetic.  Nothing depends on the grid: same input, same bits.
+// The gate epilogues are the 2-D kernel's row walk with two or three operand rows per pixel: the wave parks A^T m in the LDS the loop
+// has finished with and walks it as rows; pixel addresses come from offset tables that the staging role writes once per block from
+// the (first pixel, outputs inside L) it kept of its tile, and every operand and result passes a sized buffer descriptor, so a lane
+// without work carries an out-of-range offset instead of a test.  The first 8 pixels' operands are requested before the wave parks,
+// the other 8 before the first gate is computed (see the kernel's epilogue).
 constexpr int WN1 = 128;                 // output channels per block
 constexpr int VIMG1 = 8 * WT * WK;       // floats of V: 8 components x 32 tiles x 8 channels
 
@@ -482,7 +487,20 @@ struct Wino1dArgs {
   float* h; int h_ld;
   float* aux_z; float* aux_rh;
   int ch;
+  unsigned res_bytes, h_bytes, z_bytes;   // GRU epilogues: bytes of res (0 without one), h, aux_z / aux_rh up to the last pixel's last column
 };
+
+// The gate epilogues' entry of one of the block's 32 tiles, kept by the staging role: bits 31-29 how many of the tile's 4 outputs lie
+// inside L (0: there is no such tile), the low bits its first output pixel (B * H * W < 2^26: the launcher's 32-bit byte offsets).
+constexpr unsigned T1_PIX = 0x1fffffffu;
+// A wave's parking area for A^T m: 64 pixels (16 tiles x 4 outputs) x 64 columns, 16 floats of padding behind every 16 pixels: the
+// dword stores of a lane half (16 columns of two tile groups kq) then fall into 32 different banks, and a float4 read serves 16 lanes
+// at a time — 4 + 8 + 4 of them from two neighbouring pixels, which together take each 16-byte slot of the 256-byte bank row once
+// when rows are exactly 256 bytes apart (rows of 68 floats made two of those lanes share a slot).  A lane's four outputs of one
+// (fragment, tile) lie 64 floats apart: two ds_write2_b32.
+constexpr int ES1 = 64, ESZ1 = 64 * ES1 + 4 * 16;
+// The gate epilogues' offset tables behind the four parking areas: [context term, h, z | r*h, none][output e][tile], 128 words each
+constexpr int TBL1 = 4 * WT;
 
 // tile g -> the pixel of axis coordinate 0 on its line, and its tile index along the axis
 template <bool VERT>
@@ -552,6 +570,51 @@ __device__ __forceinline__ void wino1d_at(const f32x4 (&acc)[8][4], int f, int r
   y[3] = q12 + 8.f * q34 + 0.125f * q56 + acc[7][f][r];
 }
 
+typedef __attribute__((address_space(3))) u32x4v lu32x4;
+
+// Gate epilogues, row walk.  The lane's 16 pixels are output e = lane >> 4 of the wave's 16 tiles, 8 per half, its 4 columns the
+// same in each.  Byte offsets of one half's 8 row pieces from one table: tP = the table at (e, the half's first tile), `col` the byte
+// offset of the 4 columns in a row.  A pixel that does not exist has OOB in the table and stays out of range; a lane without work
+// reads the table that holds nothing else.
+__device__ __forceinline__ void wino1d_epi_offsets(const lunsigned* tP, unsigned col, unsigned (&o)[8]) {
+  const u32x4v t0 = *(const lu32x4*)tP, t1 = *(const lu32x4*)(tP + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    o[j] = t0[j] + col;
+    o[4 + j] = t1[j] + col;
+  }
+}
+
+// the 8 row pieces of one operand, all requested before the first is used (out of range: zero)
+__device__ __forceinline__ void wino1d_epi_load(__amdgpu_buffer_rsrc_t rs, const unsigned (&o)[8], f32x4 (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o[i], 0, 0));
+}
+
+// One pixel's 4 columns: (parked A^T m + bias) + context term, then the gate with pfk_gemm.h's arithmetic.  GRU_ZR: sigmoid, times h
+// in the r half (`upper`).  GRU_Q: (1 - z) * h + z * tanh, each product rounded (no contraction), as the direct kernel's epilogue.
+template <int EPI>
+__device__ __forceinline__ f32x4 wino1d_gate(f32x4 y, f32x4 bias4, f32x4 r, f32x4 h, f32x4 z, bool upper) {
+  const f32x4 v = y + bias4 + r;
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if constexpr (EPI == PFK_EPI_GRU_ZR) {
+      const float s = sigmoid_f(v[e]);
+      o[e] = upper ? s * h[e] : s;
+    } else {
+      const float keep = __fmul_rn(__fsub_rn(1.0f, z[e]), h[e]);
+      const float take = __fmul_rn(z[e], tanhf(v[e]));
+      o[e] = __fadd_rn(keep, take);
+    }
+  }
+  return o;
+}
+
+__device__ __forceinline__ void wino1d_epi_put(f32x4 o, __amdgpu_buffer_rsrc_t rs, unsigned off) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, o), rs, off, 0, 0);
+}
+
 template <bool VERT, int EPI>
 __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino1dArgs a) {
   // 2 x 32 KB of U + 8 KB of V
@@ -571,11 +634,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
   // ---- staging role: tile lt, channel cc of the K-step
   const int lt = tid >> 3, cc = tid & 7;
   unsigned voff0[8], voff1[8];
+  unsigned tinfo;   // the tile's entry of the gate epilogues' tables
   {
     const int g = t0 + lt;
     const bool tok = g < a.ntiles;
     int base, t;
     wino1d_tile<VERT>(a, g, base, t);
+    const int nout = a.L - 4 * t;
+    tinfo = tok ? ((unsigned)(nout < 4 ? nout : 4) << 29) | (unsigned)(base + 4 * t * pstride) : 0u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int ax = 4 * t - 2 + j;
@@ -672,79 +738,138 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
   } else {
     // The gate epilogues read two or three rows per output (context term, h, z): from the accumulator layout that is 64-byte pieces,
     // four at a time, with the memory latency of each batch exposed.  Instead every wave parks its 64 pixels x 64 columns of A^T m in
-    // its own 17 KB of the LDS the loop has finished with (all waves are past the last barrier; rows padded to 68 floats: the float4
-    // reads of four rows fall into different banks) and walks them as rows: a lane takes 4 columns of one pixel, 16 lanes a 256-byte
-    // row piece, and the loads of 8 pixels per lane are requested before the first is used.
-    constexpr int ES = 68;
-    static_assert(4 * 64 * ES <= 2 * UIMG + VIMG1, "the four waves' parking areas must fit into the loop's LDS");
-    lfloat* const sE = (lfloat*)smem + wid * (64 * ES);
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float y[4];
-        wino1d_at(acc, f, r, y);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sE[((kq * 4 + r) * 4 + e) * ES + f * 16 + rl] = y[e];
-      }
+    // its own 16 KB of the LDS the loop has finished with (all waves are past the last barrier; the layout: ESZ1) and walks them as
+    // rows: a lane takes 4 columns of one pixel, 16 lanes a 256-byte row piece, 16 pixels per lane in two halves of 8.
+    //
+    // Pixel addresses come from tables of byte offsets that the staging role writes once per block from the entry its prologue kept:
+    // per tile and output, the pixel's row in the context term, in h and in z / r*h (one table per row stride), OOB where the tile or
+    // the pixel does not exist, and a fourth table that holds only OOB.  All operands and results go through buffer descriptors sized
+    // to the last pixel's last column (the launcher refuses spans of 2 GB and more): a lane without work — a pixel past L, a tile past
+    // the end, columns from cout on, the z half where h is read — reads the fourth table, so its loads give zero and its stores are
+    // dropped.  No division, no 64-bit multiply and no bounds test per output, and no branch beyond tanhf's own and a wave-uniform
+    // one around the r half's store in a wave whose 64 columns hold both halves (z and r*h are two buffers: the other waves choose
+    // their descriptor once).  The first half's operands are requested before the wave parks, the second half's before the first
+    // half's gates are computed.
+    static_assert(4 * ESZ1 + 4 * TBL1 <= 2 * UIMG + VIMG1, "the four waves' parking areas and the offset tables must fit into the loop's LDS");
+    lfloat* const sE = (lfloat*)smem + wid * ESZ1;
+    lunsigned* const sT = (lunsigned*)((lfloat*)smem + 4 * ESZ1);
+    if (cc < 4) {
+      const bool ok = (unsigned)cc < (tinfo >> 29);
+      const unsigned pix = (tinfo & T1_PIX) + (unsigned)(cc * pstride);
+      sT[0 * TBL1 + cc * WT + lt] = ok ? pix * (unsigned)a.res_ld * 4u : OOB;
+      sT[1 * TBL1 + cc * WT + lt] = ok ? pix * (unsigned)a.h_ld * 4u : OOB;
+      sT[2 * TBL1 + cc * WT + lt] = ok ? pix * (unsigned)a.ch * 4u : OOB;
+      sT[3 * TBL1 + cc * WT + lt] = OOB;
+    }
+    // row-walk role: pixel li = (8 * half + i) * 4 + prow of the wave's 64 (tile li >> 2, output li & 3), 4 columns from col4
     const int prow = lane >> 4, col4 = (lane & 15) * 4;
-    const int n0 = cb * WN1 + wc * 64 + col4;        // cout % 4 == 0: the lane's four columns are inside or outside together
+    const int w0 = cb * WN1 + wc * 64;               // (wave-uniform) the wave's first column
+    const int n0 = w0 + col4;                        // cout % 4 == 0: the lane's four columns are inside or outside together
     const bool nok = n0 < a.cout;
-    const int nc = nok ? n0 : 0;
     const int ch = a.ch;
-    f32x4 bias4 = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (a.bias != nullptr) bias4 = f32x4{a.bias[nc], a.bias[nc + 1], a.bias[nc + 2], a.bias[nc + 3]};
-    const bool upper = nc >= ch;                      // GRU_ZR: the r half
-    const int hc = (EPI == PFK_EPI_GRU_ZR) ? (upper ? nc - ch : 0) : nc;
+    const bool upper = EPI == PFK_EPI_GRU_ZR && n0 >= ch;   // GRU_ZR: the r half
+    const unsigned cn = (unsigned)n0 * 4u, chc = (unsigned)(upper ? n0 - ch : n0) * 4u;
+    const __amdgpu_buffer_rsrc_t rbias = rsrc_n(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
+    f32x4 bias4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bias4[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, cn + 4u * j, 0, 0));
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the tables are written
+
+    const __amdgpu_buffer_rsrc_t rres = rsrc_n(a.res, a.res != nullptr ? a.res_bytes : 0u);   // (no context term: zero)
+    const __amdgpu_buffer_rsrc_t rh = rsrc_n(a.h, a.h_bytes);
+    // (wave-uniform) GRU_ZR: the wave's 64 columns lie in the z half, in the r half, or — hidden widths that are no multiple of 64 — in both
+    const bool wupper = EPI == PFK_EPI_GRU_ZR && w0 >= ch, wh = EPI == PFK_EPI_GRU_ZR && w0 + 64 > ch, wmixed = wh && !wupper;
+    const __amdgpu_buffer_rsrc_t rz = rsrc_n(wupper ? a.aux_rh : a.aux_z, a.z_bytes);   // GRU_ZR: stored; GRU_Q: read
+    const __amdgpu_buffer_rsrc_t rrh = rsrc_n(a.aux_rh, a.z_bytes);                     // GRU_ZR, both halves in the wave: the r half's store
+    const lunsigned* const tN = sT + 3 * TBL1 + prow * WT + wt * 16;   // the lane's place in the table without work
+    const lunsigned* const tR = nok ? tN - 3 * TBL1 : tN;
+    const lunsigned* const tH = (nok && (EPI == PFK_EPI_GRU_Q || upper)) ? tN - 2 * TBL1 : tN;
+    const lunsigned* const tZ = (nok && upper == wupper) ? tN - 1 * TBL1 : tN;
+    const lunsigned* const tZ2 = (nok && upper) ? tN - 1 * TBL1 : tN;
+
+    const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    unsigned oo[2][8];                                // where the results go: GRU_ZR z | r*h, GRU_Q h
+    f32x4 r4[2][8], h4[2][8], z4[2][8];
+    {
+      unsigned o[8];
+      wino1d_epi_offsets(tR, cn, o);
+      wino1d_epi_load(rres, o, r4[0]);
+      if constexpr (EPI == PFK_EPI_GRU_ZR) {
+        wino1d_epi_offsets(tZ, chc, oo[0]);
+        if (wh) {
+          wino1d_epi_offsets(tH, chc, o);
+          wino1d_epi_load(rh, o, h4[0]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) h4[0][i] = zero4;
+        }
+      } else {
+        wino1d_epi_offsets(tZ, cn, o);
+        wino1d_epi_load(rz, o, z4[0]);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // MFMA role: A^T m is lane-local; parked at [pixel li = (4 * kq + r) * 4 + e][column] of the wave's own area (no barrier: a wave's
+    // own LDS operations stay in order)
+    {
+      lfloat* const pE = sE + kq * (16 * ES1 + 16) + rl;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float y[4];
+          wino1d_at(acc, f, r, y);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pE[(r * 4 + e) * ES1 + f * 16] = y[e];
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      unsigned o[8];
+      if constexpr (EPI == PFK_EPI_GRU_Q) {
+        wino1d_epi_offsets(tH, cn, oo[0]);
+        wino1d_epi_load(rh, oo[0], h4[0]);
+        wino1d_epi_offsets(tZ + 8, cn, o);
+        wino1d_epi_load(rz, o, z4[1]);
+      }
+      wino1d_epi_offsets(tR + 8, cn, o);
+      wino1d_epi_load(rres, o, r4[1]);
+      if constexpr (EPI == PFK_EPI_GRU_ZR) {
+        wino1d_epi_offsets(tZ + 8, chc, oo[1]);
+        if (wh) {
+          wino1d_epi_offsets(tH + 8, chc, o);
+          wino1d_epi_load(rh, o, h4[1]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) h4[1][i] = zero4;
+        }
+      } else {
+        wino1d_epi_offsets(tH + 8, cn, oo[1]);
+        wino1d_epi_load(rh, oo[1], h4[1]);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const lfloat* const rE = sE + prow * ES1 + col4;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      bool ok[8];
-      long long p[8];
-      f32x4 r4[8], h4[8], z4[8];
+      unsigned o2[8];
+      if constexpr (EPI == PFK_EPI_GRU_ZR) {
+        if (wmixed) wino1d_epi_offsets(tZ2 + 8 * half, chc, o2);
+      }
+      f32x4 y[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const int li = (half * 8 + i) * 4 + prow;     // the wave's pixel: tile li >> 2, output li & 3
-        const int g = t0 + wt * 16 + (li >> 2);
-        int base, t;
-        wino1d_tile<VERT>(a, g, base, t);
-        const int ax = 4 * t + (li & 3);
-        ok[i] = nok && g < a.ntiles && ax < a.L;
-        p[i] = ok[i] ? base + ax * pstride : 0;       // (row 0 for the lanes without an output: every load below is legal)
-        r4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (a.res != nullptr) r4[i] = *(const f32x4*)(a.res + p[i] * a.res_ld + nc);
-        if constexpr (EPI == PFK_EPI_GRU_ZR) {
-          if (upper) h4[i] = *(const f32x4*)(a.h + p[i] * a.h_ld + hc);
-        } else {
-          z4[i] = *(const f32x4*)(a.aux_z + p[i] * ch + nc);
-          h4[i] = *(const f32x4*)(a.h + p[i] * a.h_ld + hc);
-        }
+        const int li4 = (half * 8 + i) * 4;           // the lane's pixel is li4 + prow
+        y[i] = *(const lf32x4*)(rE + li4 * ES1 + (li4 >> 4) * 16);
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const int li = (half * 8 + i) * 4 + prow;
-        const f32x4 v = *(const lf32x4*)(sE + li * ES + col4) + bias4 + r4[i];
-        f32x4 o;
+        const f32x4 o = wino1d_gate<EPI>(y[i], bias4, r4[half][i], h4[half][i], EPI == PFK_EPI_GRU_Q ? z4[half][i] : zero4, upper);
         if constexpr (EPI == PFK_EPI_GRU_ZR) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = sigmoid_f(v[e]);
-          if (!ok[i]) continue;
-          if (upper) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] *= h4[i][e];
-            *(f32x4*)(a.aux_rh + p[i] * ch + hc) = o;
-          } else {
-            *(f32x4*)(a.aux_z + p[i] * ch + nc) = o;
-          }
+          wino1d_epi_put(o, rz, oo[half][i]);
+          if (wmixed) wino1d_epi_put(o, rrh, o2[i]);
         } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            // (1 - z) * h + z * q, each product rounded (no contraction), as the direct kernel's epilogue
-            const float keep = __fmul_rn(__fsub_rn(1.0f, z4[i][e]), h4[i][e]);
-            const float take = __fmul_rn(z4[i][e], tanhf(v[e]));
-            o[e] = __fadd_rn(keep, take);
-          }
-          if (!ok[i]) continue;
-          *(f32x4*)(a.h + p[i] * a.h_ld + hc) = o;
+          wino1d_epi_put(o, rh, oo[half][i]);
         }
       }
     }
@@ -800,6 +925,10 @@ int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
     if (!pfk_aligned16(d->h) || !pfk_aligned16(d->aux_z) || !pfk_aligned16(d->aux_rh) || !pfk_aligned16(d->residual) || (d->h_ld & 3) ||
         (d->residual && (d->residual_ld & 3)))
       return PFK_ERR_ALIGNMENT;
+    // the row walk's 32-bit byte offsets: the context term, h, z and r*h up to the last pixel's last column
+    if ((d->residual && ((M - 1) * d->residual_ld + d->cout) * 4 >= 0x7fffffffLL) || ((M - 1) * d->h_ld + ch) * 4 >= 0x7fffffffLL ||
+        M * ch * 4 >= 0x7fffffffLL)
+      return PFK_ERR_UNSUPPORTED;
   }
   if (!pfk_aligned16(d->weight)) return PFK_ERR_ALIGNMENT;
   const long long wfloats = pfk_conv_wino1d_weight_floats(ktot, d->cout);
@@ -825,6 +954,11 @@ int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
   a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff;
   a.res = d->residual; a.res_ld = d->residual_ld;
   a.h = d->h; a.h_ld = d->h_ld; a.aux_z = d->aux_z; a.aux_rh = d->aux_rh; a.ch = ch;
+  if (d->epilogue != PFK_EPI_LINEAR) {
+    a.res_bytes = d->residual ? (unsigned)(((M - 1) * d->residual_ld + d->cout) * 4) : 0u;
+    a.h_bytes = (unsigned)(((M - 1) * d->h_ld + ch) * 4);
+    a.z_bytes = (unsigned)(M * ch * 4);
+  }
   if (vert) wino1d_launch_epi<true>(a, d->epilogue, (unsigned)nblk, static_cast<hipStream_t>(stream));
   else wino1d_launch_epi<false>(a, d->epilogue, (unsigned)nblk, static_cast<hipStream_t>(stream));
   return pfk_launch_status();
