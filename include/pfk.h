@@ -565,6 +565,41 @@ int pfk_gelu_f32(const float* x, long long x_ld, float* y, long long y_ld, long 
 int pfk_gelu_bwd_f32(const float* x, long long x_ld, const float* dy, long long dy_ld, float* dx, long long dx_ld, long long M, int C,
                      pfk_stream_t stream);
 
+/* ---- training the ConvNeXt block on bf16 rows (K12f; additions, ABI 7) ----------------------------------------------------------
+ * The five entries above with bf16 activations and activation gradients: what the block saves and moves between its bf16 GEMMs
+ * (pfk_conv2d_b16 / pfk_conv_wgrad_unpacked_b16) at half the bytes.  Every `*_bf16` pointer is bf16 pixel-major rows [M][ld] of
+ * which only the C real columns are read or written: C % 8 == 0, 8 <= C <= 512, 16-byte aligned with ld % 8 == 0 (ld in elements),
+ * k odd <= 7.  Parameters, parameter gradients, rstd and the workspaces are fp32.  A bf16 value is widened exactly when it is read,
+ * all arithmetic and all accumulation is fp32 in the order of the fp32 entry, and each bf16 output is rounded once (to nearest even)
+ * at its store.  Deterministic and validated as the fp32 entries are.
+ *
+ * pfk_dwconv_layernorm_train_b16: pfk_dwconv_layernorm_b16 with `out_bf16` bit-identical to that entry on the same inputs, and in
+ * addition xhat_bf16[p*xhat_ld + c] = bf16((u - mean) * rstd) — the fp32 normalised value rounded once, not derived from the rounded
+ * output — and the fp32 rstd[p] (4-byte aligned, [M]).  No output may overlap the input rows or another output. */
+int pfk_dwconv_layernorm_train_b16(const void* in_bf16, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                                   const float* ln_bias, float eps, void* out_bf16, int out_ld, void* xhat_bf16, int xhat_ld, float* rstd,
+                                   int B, int H, int W, int C, int k, pfk_stream_t stream);
+
+/* pfk_layernorm_bwd_b16: pfk_layernorm_bwd_f32's formulas on bf16 xhat / dy -> bf16 du; rstd, ln_weight, dgamma, dbeta fp32 (the
+ * column sums run over the widened dy and xhat in fp32 and are never rounded to bf16).  du must not overlap dy or xhat.  workspace:
+ * pfk_layernorm_bwd_workspace_bytes(M, C) bytes, 16-byte aligned. */
+int pfk_layernorm_bwd_b16(const void* xhat_bf16, int xhat_ld, const float* rstd, const float* ln_weight, const void* dy_bf16, int dy_ld,
+                          void* du_bf16, int du_ld, float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M,
+                          int C, pfk_stream_t stream);
+
+/* pfk_dwconv_bwd_b16: pfk_dwconv_bwd_f32's formulas (never across images) on bf16 in / du -> bf16 dx; dw_weight, dweight [C][k*k] and
+ * dbias [C] (may be NULL) fp32.  dx must not overlap du or in.  workspace: pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k) bytes,
+ * 16-byte aligned. */
+int pfk_dwconv_bwd_b16(const void* in_bf16, int in_ld, const void* du_bf16, int du_ld, const float* dw_weight, void* dx_bf16, int dx_ld,
+                       float* dweight, float* dbias, void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k,
+                       pfk_stream_t stream);
+
+/* pfk_gelu_b16 / pfk_gelu_bwd_b16: pfk_gelu_f32's formulas evaluated in fp32 on float(x); x, y, dy, dx bf16 rows (large |x|: 0 or dy,
+ * never NaN).  Any C % 8 == 0, C >= 8; out of place. */
+int pfk_gelu_b16(const void* x_bf16, long long x_ld, void* y_bf16, long long y_ld, long long M, int C, pfk_stream_t stream);
+int pfk_gelu_bwd_b16(const void* x_bf16, long long x_ld, const void* dy_bf16, long long dy_ld, void* dx_bf16, long long dx_ld, long long M,
+                     int C, pfk_stream_t stream);
+
 /* pfk_convex_upsample_info_pm_f32: SEARAFT.upsample_data (sea_raft/sea_raft.py:147-163).  flow_pm [M][flow_ld] (channels 0..1),
  * info_pm [M][info_ld] (channels 0..n-1, 1 <= n <= 8), mask [M][mask_ld] fp32 logits with channel c = k*64 + sy*8 + sx, already
  * multiplied by 0.25 (16-byte aligned rows, mask_ld % 4 == 0, mask_ld >= 576).  Softmax over the nine taps; convex combination of

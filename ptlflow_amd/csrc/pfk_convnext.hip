@@ -176,11 +176,14 @@ __device__ __forceinline__ float half_wave_sum(float v) {      // over the 32 la
   return v;
 }
 
-template <int K>
+// TRAIN (pfk_dwconv_layernorm_train_b16): the same arithmetic in the same order — `out` has the same bits — and the fp32 normalised
+// value (u - mean) * rstd goes to `xhat` rounded once, the pixel's fp32 rstd to `rstd_out`: what pfk_layernorm_bwd_b16 reads.
+template <int K, bool TRAIN = false>
 __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16* __restrict__ in, int in_ld, const float* __restrict__ dw_w,
                                                                    const float* __restrict__ dw_b, const float* __restrict__ ln_w,
                                                                    const float* __restrict__ ln_b, float eps, __bf16* __restrict__ out,
-                                                                   int out_ld, int H, int W, int C) {
+                                                                   int out_ld, int H, int W, int C, __bf16* __restrict__ xhat = nullptr,
+                                                                   int xhat_ld = 0, float* __restrict__ rstd_out = nullptr) {
   constexpr int R = K / 2, HY = BT_TY + K - 1, HX = BT_TX + K - 1, KK = K * K, WIN = BT_PX + K - 1;
   __shared__ __attribute__((aligned(16))) __bf16 halo[HY * HX * BT_CC];   // [halo pixel][64 channels]: 17.5 KB at k = 7
   __shared__ __attribute__((aligned(16))) float wts[KK * BT_CC];          // [tap][64 channels]: 12.25 KB at k = 7
@@ -261,6 +264,13 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
   }
   const int y = y0 + ry;
   if (y >= H) return;
+  if constexpr (TRAIN) {
+    if (j == 0) {                                              // one lane per strip
+#pragma unroll
+      for (int o = 0; o < BT_PX; ++o)
+        if (x0 + rx + o < W) rstd_out[img + (long long)y * W + x0 + rx + o] = rstd[o];
+    }
+  }
 #pragma unroll
   for (int ch = 0; ch < BT_NCH; ++ch) {
     const int c = ch * BT_CC + 2 * j;
@@ -271,20 +281,34 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
       const int x = x0 + rx + o;
       if (x >= W) continue;
       typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+      const float xh0 = (acc[ch][o].x - mean[o]) * rstd[o], xh1 = (acc[ch][o].y - mean[o]) * rstd[o];
       bf16x2 v;
-      v[0] = (__bf16)((acc[ch][o].x - mean[o]) * rstd[o] * w0 + b0);
-      v[1] = (__bf16)((acc[ch][o].y - mean[o]) * rstd[o] * w1 + b1);
+      v[0] = (__bf16)(xh0 * w0 + b0);
+      v[1] = (__bf16)(xh1 * w1 + b1);
       *reinterpret_cast<bf16x2*>(out + (img + (long long)y * W + x) * out_ld + c) = v;
+      if constexpr (TRAIN) {
+        bf16x2 n;
+        n[0] = (__bf16)xh0;
+        n[1] = (__bf16)xh1;
+        *reinterpret_cast<bf16x2*>(xhat + (img + (long long)y * W + x) * xhat_ld + c) = n;
+      }
     }
   }
 }
 
-template <int K>
+template <int K, bool TRAIN = false>
 int launch_dwconv_ln_b16(const __bf16* in, int in_ld, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, float eps,
-                         __bf16* out, int out_ld, int B, int H, int W, int C, hipStream_t st) {
+                         __bf16* out, int out_ld, int B, int H, int W, int C, hipStream_t st, __bf16* xhat = nullptr, int xhat_ld = 0,
+                         float* rstd = nullptr) {
   dim3 grid((unsigned)((W + BT_TX - 1) / BT_TX), (unsigned)((H + BT_TY - 1) / BT_TY), (unsigned)B);
-  hipLaunchKernelGGL(dwconv_ln_b16_kernel<K>, grid, dim3(BT_THREADS), 0, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C);
+  hipLaunchKernelGGL((dwconv_ln_b16_kernel<K, TRAIN>), grid, dim3(BT_THREADS), 0, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W,
+                     C, xhat, xhat_ld, rstd);
   return pfk_launch_status();
+}
+
+// [b, e) of two row ranges intersect
+bool ranges_overlap(const void* ab, const void* ae, const void* bb, const void* be) {
+  return static_cast<const char*>(ab) < static_cast<const char*>(be) && static_cast<const char*>(bb) < static_cast<const char*>(ae);
 }
 
 }  // namespace
@@ -368,6 +392,36 @@ int pfk_dwconv_layernorm_b16(const void* in_bf16, int in_ld, const float* dw_wei
     case 3: return launch_dwconv_ln_b16<3>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     case 5: return launch_dwconv_ln_b16<5>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
     default: return launch_dwconv_ln_b16<7>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st);
+  }
+}
+
+int pfk_dwconv_layernorm_train_b16(const void* in_bf16, int in_ld, const float* dw_weight, const float* dw_bias, const float* ln_weight,
+                                   const float* ln_bias, float eps, void* out_bf16, int out_ld, void* xhat_bf16, int xhat_ld, float* rstd,
+                                   int B, int H, int W, int C, int k, pfk_stream_t stream) {
+  if (!in_bf16 || !dw_weight || !ln_weight || !ln_bias || !out_bf16 || !xhat_bf16 || !rstd || B <= 0 || H <= 0 || W <= 0 || C < 8 ||
+      in_ld < C || out_ld < C || xhat_ld < C)
+    return PFK_ERR_BAD_ARG;
+  if (k < 1 || !(k & 1) || k > 7 || C > DW_MAX_C) return PFK_ERR_BAD_ARG;
+  if (B > 65535 || (H + BT_TY - 1) / BT_TY > 65535) return PFK_ERR_UNSUPPORTED;
+  if ((C & 7) || (in_ld & 7) || (out_ld & 7) || (xhat_ld & 7) || !pfk_aligned16(in_bf16) || !pfk_aligned16(out_bf16) ||
+      !pfk_aligned16(xhat_bf16) || (reinterpret_cast<uintptr_t>(rstd) & 3u))
+    return PFK_ERR_ALIGNMENT;
+  const long long M = (long long)B * H * W;
+  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  const __bf16* in = static_cast<const __bf16*>(in_bf16);
+  __bf16* out = static_cast<__bf16*>(out_bf16);
+  __bf16* xhat = static_cast<__bf16*>(xhat_bf16);
+  // no output may overlap the input rows (other blocks still read the halo of pixels this block has written) or another output
+  const void *ie = in + (M - 1) * in_ld + C, *oe = out + (M - 1) * out_ld + C, *xe = xhat + (M - 1) * xhat_ld + C, *re = rstd + M;
+  if (ranges_overlap(out, oe, in, ie) || ranges_overlap(xhat, xe, in, ie) || ranges_overlap(xhat, xe, out, oe) ||
+      ranges_overlap(rstd, re, in, ie) || ranges_overlap(rstd, re, out, oe) || ranges_overlap(rstd, re, xhat, xe))
+    return PFK_ERR_BAD_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k) {
+    case 1: return launch_dwconv_ln_b16<1, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    case 3: return launch_dwconv_ln_b16<3, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    case 5: return launch_dwconv_ln_b16<5, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
+    default: return launch_dwconv_ln_b16<7, true>(in, in_ld, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, out_ld, B, H, W, C, st, xhat, xhat_ld, rstd);
   }
 }
 

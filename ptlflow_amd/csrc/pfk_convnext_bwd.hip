@@ -9,6 +9,12 @@
 //    gradient [32][k*k] stays in registers over all its tiles: a thread owns (four channels, tap) items and walks the tile's 32
 //    pixels out of LDS.  One partial [C][k*k + 1] per slice (the + 1: the bias gradient).
 //  * pfk_gelu_f32 / pfk_gelu_bwd_f32   float4 per thread over [M][C] rows.
+//
+// The bf16 entries (K12f: pfk_layernorm_bwd_b16, pfk_dwconv_bwd_b16, pfk_gelu_b16, pfk_gelu_bwd_b16) are the same kernel bodies on the
+// element type __bf16: rows are widened to fp32 as they are loaded (exact) and rounded once as they are stored, everything between —
+// LDS tiles, sums, partials, the parameter gradients — is the fp32 code.  What differs is how many channels a lane moves at once:
+// 16 bytes of a bf16 row (eight channels) in the LayerNorm and GELU kernels, 8 bytes (the (pixel, four channels) item) in the
+// depthwise one.
 #include "pfk_common.h"
 
 namespace {
@@ -29,53 +35,125 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// N consecutive channels of a row as fp32 (bf16: widened, exact) and back (bf16: one rounding to nearest even); p is N * sizeof(T)
+// aligned
+template <int N>
+__device__ __forceinline__ void load_row(const float* p, float* v) {
+  if constexpr (N == 1) v[0] = *p;
+  else {
+    static_assert(N == 4, "one float or one float4");
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = q[e];
+  }
+}
+template <int N>
+__device__ __forceinline__ void load_row(const __bf16* p, float* v) {
+  static_assert(N == 8, "16 bytes of a bf16 row");
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 w = *reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[2 * e] = __builtin_bit_cast(float, w[e] << 16);
+    v[2 * e + 1] = __builtin_bit_cast(float, w[e] & 0xffff0000u);
+  }
+}
+template <int N>
+__device__ __forceinline__ void store_row(float* p, const float* v) {
+  if constexpr (N == 1) *p = v[0];
+  else {
+    static_assert(N == 4, "one float or one float4");
+    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  }
+}
+template <int N>
+__device__ __forceinline__ void store_row(__bf16* p, const float* v) {
+  typedef __bf16 bf16xN __attribute__((ext_vector_type(N)));
+  bf16xN q;
+#pragma unroll
+  for (int e = 0; e < N; ++e) q[e] = (__bf16)v[e];
+  *reinterpret_cast<bf16xN*>(p) = q;
+}
+__device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void store4(__bf16* p, f32x4 v) {
+  const float a[4] = {v[0], v[1], v[2], v[3]};
+  store_row<4>(p, a);
+}
+
+// channels per 16-byte row access, and the rule the entries check: C and ld in multiples of it
+template <typename T>
+constexpr int QUANTUM = 16 / (int)sizeof(T);
+
 // ---------------------------------------------------------------------------------------------------------------- LayerNorm backward
-__global__ __launch_bounds__(LN_WAVES * 64) void layernorm_bwd_kernel(const float* __restrict__ xhat, int xhat_ld,
+// fp32: lane = channel + 64 t, one float per access (V = 1, NT = 8); bf16: lane l holds channels 8 l .. 8 l + 7, one 16-byte access
+// per row (V = 8, NT = 1: 48 lanes at C = 384).  Channel c = (lane + 64 t) V + e either way.
+template <typename T>
+__global__ __launch_bounds__(LN_WAVES * 64) void layernorm_bwd_kernel(const T* __restrict__ xhat, int xhat_ld,
                                                                       const float* __restrict__ rstd, const float* __restrict__ ln_w,
-                                                                      const float* __restrict__ dy, int dy_ld, float* __restrict__ du,
+                                                                      const T* __restrict__ dy, int dy_ld, T* __restrict__ du,
                                                                       int du_ld, float* __restrict__ part, long long M, int C) {
-  constexpr int NT = CB_MAX_C / 64;
+  constexpr int V = sizeof(T) == 4 ? 1 : 8;
+  constexpr int NT = CB_MAX_C / (64 * V);
   __shared__ float red[LN_WAVES][2][CB_MAX_C];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const float inv_c = 1.0f / (float)C;
-  float gam[NT], dg[NT], db[NT];
+  float gam[NT][V], dg[NT][V], db[NT][V];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    const int c = lane + 64 * t;
-    gam[t] = c < C ? ln_w[c] : 0.f;
-    dg[t] = 0.f;
-    db[t] = 0.f;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = (lane + 64 * t) * V + e;
+      gam[t][e] = c < C ? ln_w[c] : 0.f;
+      dg[t][e] = 0.f;
+      db[t][e] = 0.f;
+    }
   }
   const long long step = (long long)gridDim.x * LN_WAVES;
   for (long long p = (long long)blockIdx.x * LN_WAVES + wv; p < M; p += step) {
-    const float* xr = xhat + p * xhat_ld;
-    const float* dr = dy + p * dy_ld;
-    float xh[NT], g[NT];
+    const T* xr = xhat + p * xhat_ld;
+    const T* dr = dy + p * dy_ld;
+    float xh[NT][V], g[NT][V];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int c = lane + 64 * t;
-      const float d = c < C ? dr[c] : 0.f;
-      xh[t] = c < C ? xr[c] : 0.f;
-      g[t] = d * gam[t];
-      s1 += g[t];
-      s2 += g[t] * xh[t];
-      dg[t] += d * xh[t];
-      db[t] += d;
+      const int c = (lane + 64 * t) * V;               // C % V == 0: the V channels are real or pad together
+      float d[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) d[e] = xh[t][e] = 0.f;
+      if (c < C) {
+        load_row<V>(dr + c, d);
+        load_row<V>(xr + c, xh[t]);
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        g[t][e] = d[e] * gam[t][e];
+        s1 += g[t][e];
+        s2 += g[t][e] * xh[t][e];
+        dg[t][e] += d[e] * xh[t][e];
+        db[t][e] += d[e];
+      }
     }
     const float m1 = wave_sum(s1) * inv_c, m2 = wave_sum(s2) * inv_c;
     const float rs = rstd[p];
-    float* o = du + p * du_ld;
+    T* o = du + p * du_ld;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int c = lane + 64 * t;
-      if (c < C) o[c] = rs * (g[t] - m1 - xh[t] * m2);
+      const int c = (lane + 64 * t) * V;
+      if (c < C) {
+        float u[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) u[e] = rs * (g[t][e] - m1 - xh[t][e] * m2);
+        store_row<V>(o + c, u);
+      }
     }
   }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    red[wv][0][lane + 64 * t] = dg[t];
-    red[wv][1][lane + 64 * t] = db[t];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      red[wv][0][(lane + 64 * t) * V + e] = dg[t][e];
+      red[wv][1][(lane + 64 * t) * V + e] = db[t][e];
+    }
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 2 * C; i += LN_WAVES * 64) {
@@ -117,9 +195,10 @@ int ln_bwd_blocks(long long M) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- depthwise conv backward
-template <int K>
-__global__ __launch_bounds__(CB_THREADS) void dwconv_bwd_kernel(const float* __restrict__ in, int in_ld, const float* __restrict__ du,
-                                                                int du_ld, const float* __restrict__ dw_w, float* __restrict__ dx,
+// T: the element type of in, du and dx; the LDS tiles and every sum are fp32 for both
+template <int K, typename T>
+__global__ __launch_bounds__(CB_THREADS) void dwconv_bwd_kernel(const T* __restrict__ in, int in_ld, const T* __restrict__ du,
+                                                                int du_ld, const float* __restrict__ dw_w, T* __restrict__ dx,
                                                                 int dx_ld, float* __restrict__ part, int H, int W, int C, int tiles_x,
                                                                 int tiles_y, int tiles) {
   constexpr int R = K / 2, HY = CB_TY + K - 1, HX = CB_TX + K - 1, KK = K * K;
@@ -167,8 +246,8 @@ __global__ __launch_bounds__(CB_THREADS) void dwconv_bwd_kernel(const float* __r
       f32x4 a = zero, d = zero;
       if (gg * 4 < cn && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
         const long long p = img + (long long)yy * W + xx;
-        a = *reinterpret_cast<const f32x4*>(in + p * in_ld + c0 + gg * 4);
-        d = *reinterpret_cast<const f32x4*>(du + p * du_ld + c0 + gg * 4);
+        a = load4_widen(in + p * in_ld + c0 + gg * 4);
+        d = load4_widen(du + p * du_ld + c0 + gg * 4);
       }
       hin[i] = a;
       hdu[i] = d;
@@ -183,7 +262,7 @@ __global__ __launch_bounds__(CB_THREADS) void dwconv_bwd_kernel(const float* __r
         for (int kx = 0; kx < K; ++kx)
           s += hdu[((qy + K - 1 - ky) * HX + qx + K - 1 - kx) * CB_G + g] * wts[(ky * K + kx) * CB_G + g];
       }
-      *reinterpret_cast<f32x4*>(dx + (img + (long long)(y0 + qy) * W + x0 + qx) * dx_ld + c0 + g * 4) = s;
+      store4(dx + (img + (long long)(y0 + qy) * W + x0 + qx) * dx_ld + c0 + g * 4, s);
     }
     // dweight[c][ky][kx] += sum over the tile's pixels of du[p] * in[y + ky - R, x + kx - R] (du is zero outside the image)
 #pragma unroll
@@ -241,12 +320,12 @@ int dw_bwd_slices(int B, int H, int W) {
   return (int)(tiles < CB_MAX_SLICES ? tiles : CB_MAX_SLICES);
 }
 
-template <int K>
-int launch_dwconv_bwd(const float* in, int in_ld, const float* du, int du_ld, const float* dw_w, float* dx, int dx_ld, float* dweight,
+template <int K, typename T>
+int launch_dwconv_bwd(const T* in, int in_ld, const T* du, int du_ld, const float* dw_w, T* dx, int dx_ld, float* dweight,
                       float* dbias, float* part, int B, int H, int W, int C, hipStream_t st) {
   const int tiles_x = (W + CB_TX - 1) / CB_TX, tiles_y = (H + CB_TY - 1) / CB_TY;
   const int tiles = B * tiles_x * tiles_y, slices = dw_bwd_slices(B, H, W);
-  hipLaunchKernelGGL(dwconv_bwd_kernel<K>, dim3((unsigned)slices, (unsigned)((C + CB_CC - 1) / CB_CC)), dim3(CB_THREADS), 0, st, in, in_ld,
+  hipLaunchKernelGGL((dwconv_bwd_kernel<K, T>), dim3((unsigned)slices, (unsigned)((C + CB_CC - 1) / CB_CC)), dim3(CB_THREADS), 0, st, in, in_ld,
                      du, du_ld, dw_w, dx, dx_ld, part, H, W, C, tiles_x, tiles_y, tiles);
   const int n = C * (K * K + 1);
   hipLaunchKernelGGL(dwconv_bwd_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, slices, C, K * K, dweight, dbias);
@@ -256,19 +335,24 @@ int launch_dwconv_bwd(const float* in, int in_ld, const float* du, int du_ld, co
 // ---------------------------------------------------------------------------------------------------------------- GELU
 constexpr float INV_SQRT2 = 0.70710678118654752f, INV_SQRT_2PI = 0.39894228040143268f;
 
-template <bool BWD>
-__global__ __launch_bounds__(256) void gelu_rows_kernel(const float* __restrict__ x, long long x_ld, const float* __restrict__ dy,
-                                                        long long dy_ld, float* __restrict__ out, long long out_ld, long long M, int C4) {
+// 16 bytes of a row per thread: four floats | eight bf16 (CV groups per row); the formulas are evaluated on float(x)
+template <bool BWD, typename T>
+__global__ __launch_bounds__(256) void gelu_rows_kernel(const T* __restrict__ x, long long x_ld, const T* __restrict__ dy,
+                                                        long long dy_ld, T* __restrict__ out, long long out_ld, long long M, int CV) {
+  constexpr int V = QUANTUM<T>;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= M * C4) return;
-  const long long r = i / C4;
-  const int c = (int)(i - r * C4) * 4;
-  const f32x4 v = *reinterpret_cast<const f32x4*>(x + r * x_ld + c);
-  f32x4 o;
+  if (i >= M * CV) return;
+  long long r;
+  if (M * CV <= 0xffffffffLL) r = (unsigned)i / (unsigned)CV;      // grid-uniform: a 32-bit division wherever the item count allows one
+  else r = i / CV;
+  const int c = (int)(i - r * CV) * V;
+  float v[V], o[V];
+  load_row<V>(x + r * x_ld + c, v);
   if constexpr (BWD) {
-    const f32x4 d = *reinterpret_cast<const f32x4*>(dy + r * dy_ld + c);
+    float d[V];
+    load_row<V>(dy + r * dy_ld + c, d);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < V; ++e) {
       // Phi(x) + x phi(x); past |x| = 40 the density term is below every fp32 (and x * 0 would be NaN at infinity)
       const float cdf = 0.5f * (1.0f + erff(v[e] * INV_SQRT2));
       const float pdf = fabsf(v[e]) > 40.f ? 0.f : v[e] * expf(-0.5f * v[e] * v[e]) * INV_SQRT_2PI;
@@ -276,14 +360,16 @@ __global__ __launch_bounds__(256) void gelu_rows_kernel(const float* __restrict_
     }
   } else {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = 0.5f * v[e] * (1.0f + erff(v[e] * INV_SQRT2));      // the epilogue's formula (pfk_gemm.h)
+    for (int e = 0; e < V; ++e) o[e] = 0.5f * v[e] * (1.0f + erff(v[e] * INV_SQRT2));      // the epilogue's formula (pfk_gemm.h)
   }
-  *reinterpret_cast<f32x4*>(out + r * out_ld + c) = o;
+  store_row<V>(out + r * out_ld + c, o);
 }
 
-bool rows_ok(const void* p, long long ld) { return pfk_aligned16(p) && !(ld & 3); }
+template <typename T>
+bool rows_ok(const T* p, long long ld) { return pfk_aligned16(p) && !(ld & (QUANTUM<T> - 1)); }
 
-bool overlap(const float* a, long long a_ld, const float* b, long long b_ld, long long M, int C) {
+template <typename T>
+bool overlap(const T* a, long long a_ld, const T* b, long long b_ld, long long M, int C) {
   const char* ab = reinterpret_cast<const char*>(a);
   const char* ae = reinterpret_cast<const char*>(a + (M - 1) * a_ld + C);
   const char* bb = reinterpret_cast<const char*>(b);
@@ -291,19 +377,12 @@ bool overlap(const float* a, long long a_ld, const float* b, long long b_ld, lon
   return ab < be && bb < ae;
 }
 
-}  // namespace
-
-extern "C" {
-
-long long pfk_layernorm_bwd_workspace_bytes(long long M, int C) {
-  if (M <= 0 || C <= 0) return 0;
-  return (long long)ln_bwd_blocks(M) * 2 * C * (long long)sizeof(float);
-}
-
-int pfk_layernorm_bwd_f32(const float* xhat, int xhat_ld, const float* rstd, const float* ln_weight, const float* dy, int dy_ld,
-                          float* du, int du_ld, float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M,
-                          int C, pfk_stream_t stream) {
-  if (!xhat || !rstd || !ln_weight || !dy || !du || !dgamma || !dbeta || !workspace || M <= 0 || C < 4 || C > CB_MAX_C || (C & 3) ||
+// ---------------------------------------------------------------------------------------------------------------- the entries, per T
+template <typename T>
+int layernorm_bwd_entry(const T* xhat, int xhat_ld, const float* rstd, const float* ln_weight, const T* dy, int dy_ld, T* du, int du_ld,
+                        float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M, int C, pfk_stream_t stream) {
+  constexpr int Q = QUANTUM<T>;
+  if (!xhat || !rstd || !ln_weight || !dy || !du || !dgamma || !dbeta || !workspace || M <= 0 || C < Q || C > CB_MAX_C || (C & (Q - 1)) ||
       xhat_ld < C || dy_ld < C || du_ld < C)
     return PFK_ERR_BAD_ARG;
   if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
@@ -313,22 +392,18 @@ int pfk_layernorm_bwd_f32(const float* xhat, int xhat_ld, const float* rstd, con
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int blocks = ln_bwd_blocks(M);
   float* part = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)blocks), dim3(LN_WAVES * 64), 0, st, xhat, xhat_ld, rstd, ln_weight, dy, dy_ld, du,
-                     du_ld, part, M, C);
+  hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3((unsigned)blocks), dim3(LN_WAVES * 64), 0, st, xhat, xhat_ld, rstd, ln_weight, dy, dy_ld,
+                     du, du_ld, part, M, C);
   hipLaunchKernelGGL(column_reduce_kernel, dim3((unsigned)((2 * C + 63) / 64)), dim3(LN_RED_PARTS * 64), 0, st, part, blocks, 2 * C, dgamma,
                      dbeta, C);
   return pfk_launch_status();
 }
 
-long long pfk_dwconv_bwd_workspace_bytes(int B, int H, int W, int C, int k) {
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0) return 0;
-  return (long long)dw_bwd_slices(B, H, W) * C * (k * k + 1) * (long long)sizeof(float);
-}
-
-int pfk_dwconv_bwd_f32(const float* in, int in_ld, const float* du, int du_ld, const float* dw_weight, float* dx, int dx_ld,
-                       float* dweight, float* dbias, void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k,
-                       pfk_stream_t stream) {
-  if (!in || !du || !dw_weight || !dx || !dweight || !workspace || B <= 0 || H <= 0 || W <= 0 || C < 4 || C > CB_MAX_C || (C & 3) ||
+template <typename T>
+int dwconv_bwd_entry(const T* in, int in_ld, const T* du, int du_ld, const float* dw_weight, T* dx, int dx_ld, float* dweight, float* dbias,
+                     void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k, pfk_stream_t stream) {
+  constexpr int Q = QUANTUM<T>;
+  if (!in || !du || !dw_weight || !dx || !dweight || !workspace || B <= 0 || H <= 0 || W <= 0 || C < Q || C > CB_MAX_C || (C & (Q - 1)) ||
       in_ld < C || du_ld < C || dx_ld < C)
     return PFK_ERR_BAD_ARG;
   if (k < 1 || !(k & 1) || k > 7) return PFK_ERR_BAD_ARG;
@@ -348,27 +423,81 @@ int pfk_dwconv_bwd_f32(const float* in, int in_ld, const float* du, int du_ld, c
   }
 }
 
-static int gelu_launch(bool bwd, const float* x, long long x_ld, const float* dy, long long dy_ld, float* out, long long out_ld,
-                       long long M, int C, pfk_stream_t stream) {
-  if (!x || !out || (bwd && !dy) || M <= 0 || C < 4 || (C & 3) || x_ld < C || out_ld < C || (bwd && dy_ld < C)) return PFK_ERR_BAD_ARG;
-  if (M * (C / 4) >= 0x7fffffffLL * 256) return PFK_ERR_UNSUPPORTED;
+template <typename T>
+int gelu_entry(bool bwd, const T* x, long long x_ld, const T* dy, long long dy_ld, T* out, long long out_ld, long long M, int C,
+               pfk_stream_t stream) {
+  constexpr int Q = QUANTUM<T>;
+  if (!x || !out || (bwd && !dy) || M <= 0 || C < Q || (C & (Q - 1)) || x_ld < C || out_ld < C || (bwd && dy_ld < C)) return PFK_ERR_BAD_ARG;
+  if (M * (C / Q) >= 0x7fffffffLL * 256) return PFK_ERR_UNSUPPORTED;
   if (!rows_ok(x, x_ld) || !rows_ok(out, out_ld) || (bwd && !rows_ok(dy, dy_ld))) return PFK_ERR_ALIGNMENT;
   if (overlap(out, out_ld, x, x_ld, M, C) || (bwd && overlap(out, out_ld, dy, dy_ld, M, C))) return PFK_ERR_BAD_ARG;   // out of place only
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long n = M * (C / 4);
+  const long long n = M * (C / Q);
   const dim3 grid((unsigned)((n + 255) / 256));
-  if (bwd) hipLaunchKernelGGL(gelu_rows_kernel<true>, grid, dim3(256), 0, st, x, x_ld, dy, dy_ld, out, out_ld, M, C / 4);
-  else hipLaunchKernelGGL(gelu_rows_kernel<false>, grid, dim3(256), 0, st, x, x_ld, x, x_ld, out, out_ld, M, C / 4);
+  if (bwd) hipLaunchKernelGGL((gelu_rows_kernel<true, T>), grid, dim3(256), 0, st, x, x_ld, dy, dy_ld, out, out_ld, M, C / Q);
+  else hipLaunchKernelGGL((gelu_rows_kernel<false, T>), grid, dim3(256), 0, st, x, x_ld, x, x_ld, out, out_ld, M, C / Q);
   return pfk_launch_status();
 }
 
+const __bf16* b16(const void* p) { return static_cast<const __bf16*>(p); }
+__bf16* b16(void* p) { return static_cast<__bf16*>(p); }
+
+}  // namespace
+
+extern "C" {
+
+long long pfk_layernorm_bwd_workspace_bytes(long long M, int C) {
+  if (M <= 0 || C <= 0) return 0;
+  return (long long)ln_bwd_blocks(M) * 2 * C * (long long)sizeof(float);
+}
+
+int pfk_layernorm_bwd_f32(const float* xhat, int xhat_ld, const float* rstd, const float* ln_weight, const float* dy, int dy_ld,
+                          float* du, int du_ld, float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M,
+                          int C, pfk_stream_t stream) {
+  return layernorm_bwd_entry(xhat, xhat_ld, rstd, ln_weight, dy, dy_ld, du, du_ld, dgamma, dbeta, workspace, workspace_bytes, M, C, stream);
+}
+
+int pfk_layernorm_bwd_b16(const void* xhat_bf16, int xhat_ld, const float* rstd, const float* ln_weight, const void* dy_bf16, int dy_ld,
+                          void* du_bf16, int du_ld, float* dgamma, float* dbeta, void* workspace, long long workspace_bytes, long long M,
+                          int C, pfk_stream_t stream) {
+  return layernorm_bwd_entry(b16(xhat_bf16), xhat_ld, rstd, ln_weight, b16(dy_bf16), dy_ld, b16(du_bf16), du_ld, dgamma, dbeta, workspace,
+                             workspace_bytes, M, C, stream);
+}
+
+long long pfk_dwconv_bwd_workspace_bytes(int B, int H, int W, int C, int k) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0) return 0;
+  return (long long)dw_bwd_slices(B, H, W) * C * (k * k + 1) * (long long)sizeof(float);
+}
+
+int pfk_dwconv_bwd_f32(const float* in, int in_ld, const float* du, int du_ld, const float* dw_weight, float* dx, int dx_ld,
+                       float* dweight, float* dbias, void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k,
+                       pfk_stream_t stream) {
+  return dwconv_bwd_entry(in, in_ld, du, du_ld, dw_weight, dx, dx_ld, dweight, dbias, workspace, workspace_bytes, B, H, W, C, k, stream);
+}
+
+int pfk_dwconv_bwd_b16(const void* in_bf16, int in_ld, const void* du_bf16, int du_ld, const float* dw_weight, void* dx_bf16, int dx_ld,
+                       float* dweight, float* dbias, void* workspace, long long workspace_bytes, int B, int H, int W, int C, int k,
+                       pfk_stream_t stream) {
+  return dwconv_bwd_entry(b16(in_bf16), in_ld, b16(du_bf16), du_ld, dw_weight, b16(dx_bf16), dx_ld, dweight, dbias, workspace,
+                          workspace_bytes, B, H, W, C, k, stream);
+}
+
 int pfk_gelu_f32(const float* x, long long x_ld, float* y, long long y_ld, long long M, int C, pfk_stream_t stream) {
-  return gelu_launch(false, x, x_ld, nullptr, 0, y, y_ld, M, C, stream);
+  return gelu_entry<float>(false, x, x_ld, nullptr, 0, y, y_ld, M, C, stream);
 }
 
 int pfk_gelu_bwd_f32(const float* x, long long x_ld, const float* dy, long long dy_ld, float* dx, long long dx_ld, long long M, int C,
                      pfk_stream_t stream) {
-  return gelu_launch(true, x, x_ld, dy, dy_ld, dx, dx_ld, M, C, stream);
+  return gelu_entry<float>(true, x, x_ld, dy, dy_ld, dx, dx_ld, M, C, stream);
+}
+
+int pfk_gelu_b16(const void* x_bf16, long long x_ld, void* y_bf16, long long y_ld, long long M, int C, pfk_stream_t stream) {
+  return gelu_entry<__bf16>(false, b16(x_bf16), x_ld, nullptr, 0, b16(y_bf16), y_ld, M, C, stream);
+}
+
+int pfk_gelu_bwd_b16(const void* x_bf16, long long x_ld, const void* dy_bf16, long long dy_ld, void* dx_bf16, long long dx_ld, long long M,
+                     int C, pfk_stream_t stream) {
+  return gelu_entry<__bf16>(true, b16(x_bf16), x_ld, b16(dy_bf16), dy_ld, b16(dx_bf16), dx_ld, M, C, stream);
 }
 
 }  // extern "C"

@@ -508,69 +508,104 @@ void dwconv_layernorm_b16(const Tensor& in, const Tensor& dw_weight, const c10::
 
 // ---- K12d: training the ConvNeXt block (pfk_convnext_bwd.hip).  Row views [M, C] of wider buffers are fine; only C columns are touched.
 
-// dwconv_layernorm that also saves xhat [M, >= C] and rstd [M] for the backward; `out` has dwconv_layernorm's bits
-void dwconv_layernorm_train(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
-                            const Tensor& ln_bias, double eps, Tensor out, Tensor xhat, Tensor rstd, int64_t B, int64_t H, int64_t W,
-                            int64_t k) {
+// dwconv_layernorm that also saves xhat [M, >= C] and rstd [M] for the backward; `out` has dwconv_layernorm's bits.  Each op of this
+// block has one body for its fp32 and its bf16 (K12f: `_b16`) form: rows of element type `e`, parameters and their gradients fp32
+void dwconv_layernorm_train_impl(const char* op, Elem e, const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias,
+                                 const Tensor& ln_weight, const Tensor& ln_bias, double eps, const Tensor& out, const Tensor& xhat,
+                                 const Tensor& rstd, int64_t B, int64_t H, int64_t W, int64_t k) {
   OpScope scope(in);
-  const char* op = "dwconv_layernorm_train";
   const int64_t M = B * H * W;
-  const Rows i = rows(op, in, "inp", F32).expect(M, AtLeast{0});
+  const Rows i = rows(op, in, "inp", e).expect(M, AtLeast{0});
   const int64_t C = i.cols;
-  const Rows o = rows(op, out, "out", F32).expect(M, C), x = rows(op, xhat, "xhat", F32).expect(M, C);
+  const Rows o = rows(op, out, "out", e).expect(M, C), x = rows(op, xhat, "xhat", e).expect(M, C);
   const float* dw = dense(op, dw_weight, "dw_weight", F32, C * k * k).f32();
   const float* db = dense(op, dw_bias, "dw_bias", F32, C).f32();
   const float* lw = dense(op, ln_weight, "ln_weight", F32, C).f32();
   const float* lb = dense(op, ln_bias, "ln_bias", F32, C).f32();
   float* rs = dense(op, rstd, "rstd", F32, M).f32();
-  check_ok(pfk_dwconv_layernorm_train_f32(i.f32(), i.ld, dw, db, lw, lb, (float)eps, o.f32(), o.ld, x.f32(), x.ld, rs, B, H, W, C, k,
-                                          cur_stream()), op);
+  if (e == B16)
+    check_ok(pfk_dwconv_layernorm_train_b16(i.raw(), i.ld, dw, db, lw, lb, (float)eps, o.raw(), o.ld, x.raw(), x.ld, rs, B, H, W, C, k,
+                                            cur_stream()), op);
+  else
+    check_ok(pfk_dwconv_layernorm_train_f32(i.f32(), i.ld, dw, db, lw, lb, (float)eps, o.f32(), o.ld, x.f32(), x.ld, rs, B, H, W, C, k,
+                                            cur_stream()), op);
+}
+void dwconv_layernorm_train(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                            const Tensor& ln_bias, double eps, Tensor out, Tensor xhat, Tensor rstd, int64_t B, int64_t H, int64_t W,
+                            int64_t k) {
+  dwconv_layernorm_train_impl("dwconv_layernorm_train", F32, in, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, xhat, rstd, B, H, W, k);
+}
+void dwconv_layernorm_train_b16(const Tensor& in, const Tensor& dw_weight, const c10::optional<Tensor>& dw_bias, const Tensor& ln_weight,
+                                const Tensor& ln_bias, double eps, Tensor out, Tensor xhat, Tensor rstd, int64_t B, int64_t H, int64_t W,
+                                int64_t k) {
+  dwconv_layernorm_train_impl("dwconv_layernorm_train_b16", B16, in, dw_weight, dw_bias, ln_weight, ln_bias, eps, out, xhat, rstd, B, H, W, k);
 }
 
-void layernorm_bwd(const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy, Tensor du, Tensor dgamma,
-                   Tensor dbeta) {
+void layernorm_bwd_impl(const char* op, Elem e, const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy,
+                        const Tensor& du, const Tensor& dgamma, const Tensor& dbeta) {
   OpScope scope(xhat);
-  const char* op = "layernorm_bwd";
-  const Rows x = rows(op, xhat, "xhat", F32);
+  const Rows x = rows(op, xhat, "xhat", e);
   const int64_t M = x.rows, C = x.cols;
-  const Rows g = rows(op, dy, "dy", F32).expect(M, C), u = rows(op, du, "du", F32).expect(M, C);
+  const Rows g = rows(op, dy, "dy", e).expect(M, C), u = rows(op, du, "du", e).expect(M, C);
   const float* rs = dense(op, rstd, "rstd", F32, M).f32();
   const float* lw = dense(op, ln_weight, "ln_weight", F32, C).f32();
   float* dg = dense(op, dgamma, "dgamma", F32, C).f32();
   float* dbt = dense(op, dbeta, "dbeta", F32, C).f32();
   const long long need = pfk_layernorm_bwd_workspace_bytes(M, C);
   const auto ws = byte_workspace(need, xhat);
-  check_ok(pfk_layernorm_bwd_f32(x.f32(), x.ld, rs, lw, g.f32(), g.ld, u.f32(), u.ld, dg, dbt, ws.second, need, M, C, cur_stream()), op);
+  if (e == B16) check_ok(pfk_layernorm_bwd_b16(x.raw(), x.ld, rs, lw, g.raw(), g.ld, u.raw(), u.ld, dg, dbt, ws.second, need, M, C, cur_stream()), op);
+  else check_ok(pfk_layernorm_bwd_f32(x.f32(), x.ld, rs, lw, g.f32(), g.ld, u.f32(), u.ld, dg, dbt, ws.second, need, M, C, cur_stream()), op);
+}
+void layernorm_bwd(const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy, Tensor du, Tensor dgamma,
+                   Tensor dbeta) {
+  layernorm_bwd_impl("layernorm_bwd", F32, xhat, rstd, ln_weight, dy, du, dgamma, dbeta);
+}
+void layernorm_bwd_b16(const Tensor& xhat, const Tensor& rstd, const Tensor& ln_weight, const Tensor& dy, Tensor du, Tensor dgamma,
+                       Tensor dbeta) {
+  layernorm_bwd_impl("layernorm_bwd_b16", B16, xhat, rstd, ln_weight, dy, du, dgamma, dbeta);
 }
 
-void dwconv_bwd(const Tensor& in, const Tensor& du, const Tensor& dw_weight, Tensor dx, Tensor dweight, const c10::optional<Tensor>& dbias,
-                int64_t B, int64_t H, int64_t W, int64_t k) {
+void dwconv_bwd_impl(const char* op, Elem e, const Tensor& in, const Tensor& du, const Tensor& dw_weight, const Tensor& dx,
+                     const Tensor& dweight, const c10::optional<Tensor>& dbias, int64_t B, int64_t H, int64_t W, int64_t k) {
   OpScope scope(in);
-  const char* op = "dwconv_bwd";
   const int64_t M = B * H * W;
-  const Rows i = rows(op, in, "inp", F32).expect(M, AtLeast{0});
+  const Rows i = rows(op, in, "inp", e).expect(M, AtLeast{0});
   const int64_t C = i.cols;
-  const Rows u = rows(op, du, "du", F32).expect(M, C), x = rows(op, dx, "dx", F32).expect(M, C);
+  const Rows u = rows(op, du, "du", e).expect(M, C), x = rows(op, dx, "dx", e).expect(M, C);
   const float* w = dense(op, dw_weight, "dw_weight", F32, C * k * k).f32();
   float* dw = dense(op, dweight, "dweight", F32, C * k * k).f32();
   float* db = dense(op, dbias, "dbias", F32, C).f32();
   const long long need = pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k);
   const auto ws = byte_workspace(need, in);
-  check_ok(pfk_dwconv_bwd_f32(i.f32(), i.ld, u.f32(), u.ld, w, x.f32(), x.ld, dw, db, ws.second, need, B, H, W, C, k, cur_stream()), op);
+  if (e == B16) check_ok(pfk_dwconv_bwd_b16(i.raw(), i.ld, u.raw(), u.ld, w, x.raw(), x.ld, dw, db, ws.second, need, B, H, W, C, k, cur_stream()), op);
+  else check_ok(pfk_dwconv_bwd_f32(i.f32(), i.ld, u.f32(), u.ld, w, x.f32(), x.ld, dw, db, ws.second, need, B, H, W, C, k, cur_stream()), op);
+}
+void dwconv_bwd(const Tensor& in, const Tensor& du, const Tensor& dw_weight, Tensor dx, Tensor dweight, const c10::optional<Tensor>& dbias,
+                int64_t B, int64_t H, int64_t W, int64_t k) {
+  dwconv_bwd_impl("dwconv_bwd", F32, in, du, dw_weight, dx, dweight, dbias, B, H, W, k);
+}
+void dwconv_bwd_b16(const Tensor& in, const Tensor& du, const Tensor& dw_weight, Tensor dx, Tensor dweight, const c10::optional<Tensor>& dbias,
+                    int64_t B, int64_t H, int64_t W, int64_t k) {
+  dwconv_bwd_impl("dwconv_bwd_b16", B16, in, du, dw_weight, dx, dweight, dbias, B, H, W, k);
 }
 
-void gelu_rows(const Tensor& x, Tensor y) {
+// y = gelu(x), or with `dy` the derivative dx = dy * gelu'(x), into `out`
+void gelu_rows_impl(const char* op, Elem e, const Tensor& x, const Tensor* dy, const Tensor& out, const char* out_name) {
   OpScope scope(x);
-  const Rows a = rows("gelu", x, "x", F32), b = rows("gelu", y, "y", F32).expect(a.rows, a.cols);
-  check_ok(pfk_gelu_f32(a.f32(), a.ld, b.f32(), b.ld, a.rows, a.cols, cur_stream()), "gelu");
+  const Rows a = rows(op, x, "x", e), o = rows(op, out, out_name, e).expect(a.rows, a.cols);
+  if (dy == nullptr) {
+    if (e == B16) check_ok(pfk_gelu_b16(a.raw(), a.ld, o.raw(), o.ld, a.rows, a.cols, cur_stream()), op);
+    else check_ok(pfk_gelu_f32(a.f32(), a.ld, o.f32(), o.ld, a.rows, a.cols, cur_stream()), op);
+    return;
+  }
+  const Rows g = rows(op, *dy, "dy", e).expect(a.rows, a.cols);
+  if (e == B16) check_ok(pfk_gelu_bwd_b16(a.raw(), a.ld, g.raw(), g.ld, o.raw(), o.ld, a.rows, a.cols, cur_stream()), op);
+  else check_ok(pfk_gelu_bwd_f32(a.f32(), a.ld, g.f32(), g.ld, o.f32(), o.ld, a.rows, a.cols, cur_stream()), op);
 }
-
-void gelu_rows_bwd(const Tensor& x, const Tensor& dy, Tensor dx) {
-  OpScope scope(x);
-  const Rows a = rows("gelu_bwd", x, "x", F32), g = rows("gelu_bwd", dy, "dy", F32).expect(a.rows, a.cols);
-  const Rows d = rows("gelu_bwd", dx, "dx", F32).expect(a.rows, a.cols);
-  check_ok(pfk_gelu_bwd_f32(a.f32(), a.ld, g.f32(), g.ld, d.f32(), d.ld, a.rows, a.cols, cur_stream()), "gelu_bwd");
-}
+void gelu_rows(const Tensor& x, Tensor y) { gelu_rows_impl("gelu", F32, x, nullptr, y, "y"); }
+void gelu_rows_b16(const Tensor& x, Tensor y) { gelu_rows_impl("gelu_b16", B16, x, nullptr, y, "y"); }
+void gelu_rows_bwd(const Tensor& x, const Tensor& dy, Tensor dx) { gelu_rows_impl("gelu_bwd", F32, x, &dy, dx, "dx"); }
+void gelu_rows_bwd_b16(const Tensor& x, const Tensor& dy, Tensor dx) { gelu_rows_impl("gelu_bwd_b16", B16, x, &dy, dx, "dx"); }
 
 // fused mask conv2 + softmax + convex upsampling: x [M, cin] (a view of the fh|mask hidden buffer), weight / bias row-permuted (pfk.h)
 void mask_upsample(const Tensor& x, const Tensor& weight_perm, const c10::optional<Tensor>& bias_perm, double scale,
@@ -1179,11 +1214,18 @@ TORCH_LIBRARY(pfk, m) {
         "int B, int H, int W, int k) -> ()");
   m.def("dwconv_layernorm_train(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
         "Tensor(a!) out, Tensor(b!) xhat, Tensor(c!) rstd, int B, int H, int W, int k) -> ()");
+  m.def("dwconv_layernorm_train_b16(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
+        "Tensor(a!) out, Tensor(b!) xhat, Tensor(c!) rstd, int B, int H, int W, int k) -> ()");
   m.def("layernorm_bwd(Tensor xhat, Tensor rstd, Tensor ln_weight, Tensor dy, Tensor(a!) du, Tensor(b!) dgamma, Tensor(c!) dbeta) -> ()");
+  m.def("layernorm_bwd_b16(Tensor xhat, Tensor rstd, Tensor ln_weight, Tensor dy, Tensor(a!) du, Tensor(b!) dgamma, Tensor(c!) dbeta) -> ()");
   m.def("dwconv_bwd(Tensor inp, Tensor du, Tensor dw_weight, Tensor(a!) dx, Tensor(b!) dweight, Tensor(c!)? dbias, int B, int H, int W, "
         "int k) -> ()");
+  m.def("dwconv_bwd_b16(Tensor inp, Tensor du, Tensor dw_weight, Tensor(a!) dx, Tensor(b!) dweight, Tensor(c!)? dbias, int B, int H, int W, "
+        "int k) -> ()");
   m.def("gelu(Tensor x, Tensor(a!) y) -> ()");
+  m.def("gelu_b16(Tensor x, Tensor(a!) y) -> ()");
   m.def("gelu_bwd(Tensor x, Tensor dy, Tensor(a!) dx) -> ()");
+  m.def("gelu_bwd_b16(Tensor x, Tensor dy, Tensor(a!) dx) -> ()");
   m.def("dwconv_layernorm_b16(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, "
         "Tensor(a!) out, int B, int H, int W, int k) -> ()");
   m.def("conv2d_gelu_b16(Tensor[] srcs, int B, int H, int W, int kh, int kw, Tensor weight, Tensor? bias, int cout, float scale, "
@@ -1230,10 +1272,15 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("dwconv_layernorm", &dwconv_layernorm);
   m.impl("dwconv_layernorm_b16", &dwconv_layernorm_b16);
   m.impl("dwconv_layernorm_train", &dwconv_layernorm_train);
+  m.impl("dwconv_layernorm_train_b16", &dwconv_layernorm_train_b16);
   m.impl("layernorm_bwd", &layernorm_bwd);
+  m.impl("layernorm_bwd_b16", &layernorm_bwd_b16);
   m.impl("dwconv_bwd", &dwconv_bwd);
+  m.impl("dwconv_bwd_b16", &dwconv_bwd_b16);
   m.impl("gelu", &gelu_rows);
+  m.impl("gelu_b16", &gelu_rows_b16);
   m.impl("gelu_bwd", &gelu_rows_bwd);
+  m.impl("gelu_bwd_b16", &gelu_rows_bwd_b16);
   m.impl("conv2d_gelu_b16", &conv2d_gelu_b16);
   m.impl("convex_upsample_info_pm_b16", &convex_upsample_info_pm_b16);
   m.impl("upflow8", &upflow8);

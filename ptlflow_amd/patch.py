@@ -636,12 +636,18 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     torch.autocast(bfloat16); hidden state, flow and parameter gradients stay fp32.  The conditions of the fp32 training path
     apply unchanged (576 mask channels, no external aggregate).  GMA's update block trains natively in both precisions: its
     `attention` argument goes through to `train._AttnMatmul` and its gradient flows back to the caller's map.
+    On a SEA-RAFT model with ``sea_raft_train=True`` it is the precision of that training path (`PfkSeaRaftUpdateBlock.train_precision`,
+    ptlflow_amd/train_sea.py): "bf16" runs the update block and both heads on bf16 rows — the dense convolutions on the
+    bf16 matrix cores, the depthwise convolution + LayerNorm and the GELU, forward and backward, on the `_b16` row kernels — and hands
+    fp32 `net`, flow / info and mask logits back, so ``train_upsample`` keeps working unchanged.  It is independent of the inference
+    precision: the spelling is ``accelerate(model, sea_raft_update=True, sea_raft_train=True, train_precision="bf16")``.
     A second call with another value switches it.
     ``sea_raft_train`` (default False; needs ``sea_raft_update=True`` or ``"fp32"``, anything else raises ValueError): the SEA-RAFT
     seams also serve the calls that carry a gradient graph — CUDA fp32 tensors, grad mode on, an input or a parameter that requires
     grad, outside autocast — on the native training path of ptlflow_amd/train_sea.py: the update block (motion
     encoder and ConvNeXt blocks) and the `flow_head` / `upsample_weight` heads on any such ``[B, 128, H, W]`` input, forward and
-    backward, counted in each wrapper's ``train_calls``.  `upsample_data` in a gradient graph stays the model's own method unless
+    backward, counted in each wrapper's ``train_calls``, in fp32 or with ``train_precision="bf16"`` on bf16 rows (``sea_raft_update="bf16"``
+    with ``sea_raft_train=True`` stays refused).  `upsample_data` in a gradient graph stays the model's own method unless
     ``train_upsample`` is set.  Off: such calls reach the model's own modules, as before.
     ``train_upsample`` (default False): the upsampling seams — B5 (`upsample_flow`) and SEA-RAFT's `upsample_data` — also serve the
     plain positional call on CUDA fp32 tensors that carries a gradient graph (grad mode on, something requiring grad, outside
@@ -653,7 +659,8 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     check_precision(train_precision, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
-        raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path is fp32), got {sea_raft_update!r}")
+        raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path sits behind the fp32 seams; "
+                         f"its own precision is train_precision), got {sea_raft_update!r}")
     sea_enc_precision = _sea_precision(sea_raft_encoders, "sea_raft_encoders")
     if train_upsample:
         if (isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock) or match_sea_raft(model) is not None) \
@@ -678,6 +685,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
     if sea:
         model.update_block.sea_train = bool(sea_raft_train)
+        model.update_block.train_precision = train_precision
     if sea_enc_precision is not None:
         _install_sea_encoders(model, sea_enc_precision)
     if isinstance(getattr(model, "update_block", None), PfkSeaRaftUpdateBlock):

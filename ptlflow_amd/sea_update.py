@@ -37,7 +37,8 @@ implement — CPU tensors, gradient graphs, other dtypes, autocast — is passed
 
 `accelerate(model, sea_raft_update=True, sea_raft_train=True)` (opt-in, fp32): calls that carry a gradient graph — CUDA fp32, grad mode
 on, an input or a parameter that requires grad, no autocast — run on the differentiable composition of train_sea.py (K12d) instead
-of the wrapped modules, and are counted in `train_calls`.  With `train_upsample=True` on top, `upsample_data` in such a graph runs
+of the wrapped modules, and are counted in `train_calls`.  `train_precision="bf16"` (`PfkSeaRaftUpdateBlock.train_precision`, K12f) runs
+that composition on bf16 rows; the calls it takes and the fp32 tensors it hands back are the same.  With `train_upsample=True` on top, `upsample_data` in such a graph runs
 `train_sea.upsample_data_train` (the inference kernel forward, `pfk_convex_upsample_info_bwd_pm_f32` backward; K12e) instead of the
 model's own method, counted in the seam's `train_calls`; without it, it stays the model's method.
 """
@@ -283,7 +284,9 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
         self.calls = 0             # kernel-path calls (tests count them)
         self._adopted = None           # the net `adopt` staged last
         self.adopt_first_net = False   # the heads also serve the iteration-0 net (`adopt`); set with `accelerate(sea_raft_encoders=)`
-        self.sea_train = False         # `accelerate(sea_raft_train=True)`: gradient-graph calls run on train_sea.py (fp32 only)
+        self.sea_train = False         # `accelerate(sea_raft_train=True)`: gradient-graph calls run on train_sea.py
+        # "fp32" | "bf16": precision of that training path (`accelerate(train_precision=)`), independent of the inference `precision`
+        self.train_precision = "fp32"
         self.train_calls = 0           # calls served by the training path
         self._train_cache: dict = {}   # its packed weights, keyed by parameter versions (`PfkUpdateBlock._train_cache`'s rules)
 
@@ -362,7 +365,8 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
             from .train_sea import sea_update_block_train
             self._last_out, self._fm_for = None, None
             self.train_calls += 1
-            return sea_update_block_train(dict(self.named_parameters()), s, net, inp, corr, flow, self.num_blocks, self._train_cache)
+            return sea_update_block_train(dict(self.named_parameters()), s, net, inp, corr, flow, self.num_blocks, self._train_cache,
+                                          self.train_precision)
         ok = (torch.is_tensor(corr) and net.dim() == 4 and corr.dim() == 4 and self.accepts((net, inp, corr, flow), self._params())
               and corr.shape[1] == s.corr_channels and net.shape[1] == s.hidden and inp.shape[1] == s.context)
         if self.precision == "fp32":
@@ -436,7 +440,7 @@ class _SeaHeadSeam(WrappedModule):
             from .train_sea import sea_head_train
             self.train_calls += 1
             P = {f"{self.kind}.{k}": v for k, v in self.named_parameters()}
-            return sea_head_train(P, self.kind, x, blk._train_cache)
+            return sea_head_train(P, self.kind, x, blk._train_cache, blk.train_precision)
         if not (torch.is_tensor(x) and (blk.owns(x) or blk.adopt(x)) and blk.accepts((x,), list(self.parameters()))):
             return self._ref[0](x)
         eng = blk.heads_fm(x)

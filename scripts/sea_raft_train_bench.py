@@ -11,6 +11,10 @@ figure), median of `--samples` with the min-max spread, and each leg's peak memo
   `upsample_data` is the model's own method in both.
 * ``native_up``  the same with `train_upsample=True`: `upsample_data` on `train_sea.upsample_data_train` (K12e) — ``native`` is its
   baseline.
+* ``native_bf16``  ``native_up`` with `train_precision="bf16"` (K12f): the update block and heads on bf16 rows — the dense convolutions
+  on the bf16 matrix cores, depthwise + LayerNorm and GELU on the `_b16` row kernels; ``native_up`` is its baseline.
+* ``modules_autocast``  ``modules`` with the whole step's forward under `torch.autocast("cuda", bfloat16)`: what the reference trains
+  with, the model's own modules in 16 bits.
 
 `--trace-leg LEG` runs warm-up and then `--samples` steps of ONE leg at the first grid only (for a rocprofv3 --kernel-trace run)."""
 import argparse
@@ -29,7 +33,7 @@ from ptlflow_amd import patch  # noqa: E402
 from sea_seam_model import SeaRaftLoop, load_seeded  # noqa: E402
 
 ptlflow_amd.load_native()
-LEGS = ("modules", "native", "native_up")
+LEGS = ("modules", "native", "native_up", "native_bf16", "modules_autocast")
 
 
 def timed_ms(f):
@@ -53,11 +57,15 @@ def run(batch, h, w, iters, samples, legs, warmup=2):
     models = {"modules": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train()),
               "native": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True, sea_raft_train=True),
               "native_up": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True,
-                                            sea_raft_train=True, train_upsample=True)}
+                                            sea_raft_train=True, train_upsample=True),
+              "native_bf16": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train(), sea_raft_update=True,
+                                              sea_raft_train=True, train_upsample=True, train_precision="bf16"),
+              "modules_autocast": patch.accelerate(load_seeded(SeaRaftLoop(iters=iters), 7).to(dev).train())}
 
     def step(leg):
         m = models[leg]
-        out = m(*x)
+        with torch.autocast("cuda", torch.bfloat16, enabled=leg == "modules_autocast"):
+            out = m(*x)
         loss = sum((out[k] * R[k]).sum() for k in R)
         m.zero_grad(set_to_none=True)
         loss.backward()
@@ -75,6 +83,12 @@ def run(batch, h, w, iters, samples, legs, warmup=2):
     assert "native" not in legs or models["native"].update_block.train_calls > 0 and models["native"].flow_head.train_calls > 0
     assert "native_up" not in legs or models["native_up"].upsample_data.train_calls == (warmup + samples) * (iters + 1)
     assert models["native"].upsample_data.train_calls == 0
+    nb = models["native_bf16"]
+    assert nb.update_block.train_precision == "bf16" and models["native_up"].update_block.train_precision == "fp32"
+    assert "native_bf16" not in legs or (nb.update_block.train_calls == (warmup + samples) * iters
+                                         and nb.flow_head.train_calls == nb.upsample_weight.train_calls == (warmup + samples) * (iters + 1)
+                                         and nb.upsample_data.train_calls == (warmup + samples) * (iters + 1))
+    assert not hasattr(models["modules_autocast"].update_block, "train_calls")      # the model's own modules
     for m in models.values():
         patch.restore(m)
     return t, peak
