@@ -19,14 +19,10 @@ namespace {
 constexpr int MAX_C4 = 8;   // channels <= 16 lanes * 4 floats * MAX_C4 = 512
 
 // Feature-map element: float, or bf16 (pfk_altcorr_forward_bf16: bf16 maps, exact widening, fp32 products and accumulation —
-// half the gather bytes of an L2-bound kernel).  load4: four consecutive channels as floats.
+// half the gather bytes of an L2-bound kernel).
 typedef unsigned short bf16_t;
-typedef unsigned int ac_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 widen4(ac_u32x2 u) {
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
-}
-__device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 load4(const bf16_t* p) { return widen4(*reinterpret_cast<const ac_u32x2*>(p)); }
+using ::load4_widen;   // bf16_t names the kernel instantiations; its rows are the 8 bytes load4_widen(const __bf16*) reads
+__device__ __forceinline__ f32x4 load4_widen(const bf16_t* p) { return widen4(*reinterpret_cast<const u32x2*>(p)); }
 
 template <class T>
 __global__ __launch_bounds__(256) void altcorr_fwd_kernel(const T* __restrict__ f1, const T* __restrict__ f2,
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(256) void altcorr_fwd_kernel(const T* __restrict__ 
 #pragma unroll
   for (int i = 0; i < MAX_C4; ++i) {
     const int c = cl * 4 + i * 64;
-    a[i] = (live && c < C) ? load4(f1 + p * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    a[i] = (live && c < C) ? load4_widen(f1 + p * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   for (int t0 = 0; t0 < ntaps; t0 += 4) {
@@ -75,13 +71,13 @@ __global__ __launch_bounds__(256) void altcorr_fwd_kernel(const T* __restrict__ 
       for (int i = 0; i < MAX_C4; ++i) {
         const int c = cl * 4 + i * 64;
         if (c < C) {
-          const f32x4 v = load4(row + c);
+          const f32x4 v = load4_widen(row + c);
           acc = fmaf(a[i].x, v.x, fmaf(a[i].y, v.y, fmaf(a[i].z, v.z, fmaf(a[i].w, v.w, acc))));
         }
       }
     }
 #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);
+    for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);   // written out: as a wave_sum call the tap loop schedules differently
     if (cl == 0 && t < ntaps) s_tap[wid][t] = acc;
   }
   __syncthreads();
@@ -114,7 +110,6 @@ __global__ __launch_bounds__(256) void altcorr_fwd_kernel(const T* __restrict__ 
 constexpr int WS_NP_MAX = 512;                 // box points per block (16 column blocks of 32)
 constexpr int WS_BK = 16;                      // channels per K step
 constexpr int WS_ROWB = WS_BK * 4;             // 64-byte LDS rows
-typedef unsigned int ws_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned WS_OOB = 0x80000000u;
 
 // per-pixel algorithm of altcorr_fwd_kernel for one pixel per wave (wave-local: no workgroup barrier)
@@ -132,7 +127,7 @@ __device__ __forceinline__ void altcorr_pixel(const T* __restrict__ f1, const T*
 #pragma unroll
   for (int i = 0; i < MAX_C4; ++i) {
     const int c = cl * 4 + i * 64;
-    a[i] = (live && c < C) ? load4(f1 + p * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    a[i] = (live && c < C) ? load4_widen(f1 + p * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int t0 = 0; t0 < ntaps; t0 += 4) {
     const int t = t0 + g;
@@ -146,13 +141,13 @@ __device__ __forceinline__ void altcorr_pixel(const T* __restrict__ f1, const T*
       for (int i = 0; i < MAX_C4; ++i) {
         const int c = cl * 4 + i * 64;
         if (c < C) {
-          const f32x4 v = load4(row + c);
+          const f32x4 v = load4_widen(row + c);
           acc = fmaf(a[i].x, v.x, fmaf(a[i].y, v.y, fmaf(a[i].z, v.z, fmaf(a[i].w, v.w, acc))));
         }
       }
     }
 #pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);
+    for (int off = 8; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 16);   // written out: as a wave_sum call the tap loop schedules differently
     if (cl == 0 && t < ntaps) s_tap_w[t] = acc;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // s_tap_w is this wave's own: in-order LDS, no workgroup barrier
@@ -262,9 +257,7 @@ __device__ __forceinline__ bool gemm_pass_enabled(const int* __restrict__ counts
   if (counts == nullptr) return true;
   int s = 0;
   for (int i = lane; i < nplan; i += 64) s += counts[i];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  return 8LL * s >= 5LL * npatch;
+  return 8LL * wave_sum(s) >= 5LL * npatch;
 }
 
 // The patches the window-sharing kernel skipped: the per-pixel algorithm, one pixel per wave, blocks in the per-pixel kernel's own
@@ -354,8 +347,8 @@ __global__ __launch_bounds__(256, 2) void altcorr_fwd_ws_kernel(const T* __restr
 
   if (NP > 0) {
     // ---- staging plan: thread t owns 16-byte chunk (t & 3) of A row t >> 2 (TP == 64) and of B rows (t >> 2) + 64 i -------------
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(f1), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(f2), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(f1);
+    const __amdgpu_buffer_rsrc_t rs2 = buffer_rsrc(f2);
     constexpr int ES = (int)sizeof(T);                      // bytes per feature-map element
     const int ch = t & 3, r0 = t >> 2;
     const unsigned sw = (unsigned)(((ch ^ ((r0 >> 2) & 3)) << 4));      // swizzled chunk byte offset (rows r0 + 64 i share the key)
@@ -375,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void altcorr_fwd_ws_kernel(const T* __restr
       }
     }
     const int nrow_b = (NCB * 32 + 63) >> 6;               // B passes of 64 rows that hold live column blocks
-    ws_u32x4 ra, rb[WS_NP_MAX / 64];
+    u32x4 ra, rb[WS_NP_MAX / 64];
     auto load = [&](int k0) {
       const bool cok = k0 + ch * 4 < C;                    // C is a multiple of 4
       // four channels per thread: one 16-byte (fp32) or 8-byte (bf16, widened on the way into LDS: the GEMM stays fp32) load
@@ -385,17 +378,17 @@ __global__ __launch_bounds__(256, 2) void altcorr_fwd_ws_kernel(const T* __restr
         for (int i = 0; i < WS_NP_MAX / 64; ++i)
           if (i < nrow_b) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rs2, cok ? boff[i] : WS_OOB, k0 * 4, 0);
       } else {
-        ra = __builtin_bit_cast(ws_u32x4, widen4(__builtin_amdgcn_raw_buffer_load_b64(rs1, (cok && r0 < TP) ? aoff : WS_OOB, k0 * 2, 0)));
+        ra = __builtin_bit_cast(u32x4, widen4(__builtin_amdgcn_raw_buffer_load_b64(rs1, (cok && r0 < TP) ? aoff : WS_OOB, k0 * 2, 0)));
 #pragma unroll
         for (int i = 0; i < WS_NP_MAX / 64; ++i)
-          if (i < nrow_b) rb[i] = __builtin_bit_cast(ws_u32x4, widen4(__builtin_amdgcn_raw_buffer_load_b64(rs2, cok ? boff[i] : WS_OOB, k0 * 2, 0)));
+          if (i < nrow_b) rb[i] = __builtin_bit_cast(u32x4, widen4(__builtin_amdgcn_raw_buffer_load_b64(rs2, cok ? boff[i] : WS_OOB, k0 * 2, 0)));
       }
     };
     auto store = [&](char* stage) {
-      if (r0 < TP) *reinterpret_cast<ws_u32x4*>(stage + r0 * WS_ROWB + sw) = ra;
+      if (r0 < TP) *reinterpret_cast<u32x4*>(stage + r0 * WS_ROWB + sw) = ra;
 #pragma unroll
       for (int i = 0; i < WS_NP_MAX / 64; ++i)
-        if (i < nrow_b) *reinterpret_cast<ws_u32x4*>(stage + (TP + r0 + 64 * i) * WS_ROWB + sw) = rb[i];
+        if (i < nrow_b) *reinterpret_cast<u32x4*>(stage + (TP + r0 + 64 * i) * WS_ROWB + sw) = rb[i];
     };
     // fragment addressing: lane l feeds row l & 31 and the k half l >> 5; per 8 channels one ds_read_b128 (chunk 2 q + (l >> 5))
     const int frow = lane & 31, hl = lane >> 5;
@@ -558,7 +551,7 @@ __global__ __launch_bounds__(256) void altcorr_bwd_kernel(const float* __restric
 #pragma unroll
   for (int i = 0; i < MAX_C4; ++i) {
 #pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
+    for (int off = 16; off <= 32; off <<= 1) {      // across the four 16-lane groups, ascending: not wave_sum's order
       ga[i].x += __shfl_xor(ga[i].x, off, 64); ga[i].y += __shfl_xor(ga[i].y, off, 64);
       ga[i].z += __shfl_xor(ga[i].z, off, 64); ga[i].w += __shfl_xor(ga[i].w, off, 64);
     }

@@ -7,8 +7,7 @@
 
 namespace {
 
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned h) { return __builtin_bit_cast(float, h << 16); }
-
+// An explicit bit rule, not the (__bf16) cast of store_row: its NaN handling is part of the contract.
 // round to nearest even on the bits (what torch's Tensor.to(bfloat16) does); NaN stays a quiet NaN, denormals stay denormals
 __device__ __forceinline__ unsigned f32_to_bf16_bits(float f) {
   const unsigned u = __builtin_bit_cast(unsigned, f);
@@ -32,25 +31,25 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float* p, l
   if constexpr (BF16) {
     const unsigned* drow = reinterpret_cast<const unsigned*>(static_cast<const unsigned short*>(dp_) + (long long)blockIdx.x * ld_dp);
     for (int c = 2 * t; c < cols; c += 512) {
-      const unsigned w = drow[c >> 1];
-      sum += bf16_bits_to_f32(w & 0xffffu) * prow[c];
-      if (c + 1 < cols) sum += bf16_bits_to_f32(w >> 16) * prow[c + 1];
+      const f32x2 d = widen2(drow[c >> 1]);
+      sum += d.x * prow[c];
+      if (c + 1 < cols) sum += d.y * prow[c + 1];
     }
   } else {
     const float* drow = static_cast<const float*>(dp_) + (long long)blockIdx.x * ld_dp;
     for (int c = t; c < cols; c += 256) sum += drow[c] * prow[c];
   }
 #pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s, 64);
+  for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s, 64);      // wave_sum written out: the call moves the LDS address computation
   if (lane == 0) red[wid] = sum;
   __syncthreads();
   sum = (red[0] + red[1]) + (red[2] + red[3]);
   if constexpr (BF16) {
     const unsigned* drow = reinterpret_cast<const unsigned*>(static_cast<const unsigned short*>(dp_) + (long long)blockIdx.x * ld_dp);
     for (int c = 2 * t; c < cols; c += 512) {
-      const unsigned w = drow[c >> 1];
-      orow[c] = prow[c] * (bf16_bits_to_f32(w & 0xffffu) - sum);
-      if (c + 1 < cols) orow[c + 1] = prow[c + 1] * (bf16_bits_to_f32(w >> 16) - sum);
+      const f32x2 d = widen2(drow[c >> 1]);
+      orow[c] = prow[c] * (d.x - sum);
+      if (c + 1 < cols) orow[c + 1] = prow[c + 1] * (d.y - sum);
     }
   } else {
     const float* drow = static_cast<const float*>(dp_) + (long long)blockIdx.x * ld_dp;

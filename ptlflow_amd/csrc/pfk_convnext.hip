@@ -21,12 +21,6 @@ constexpr int DW_THREADS = 256;
 static_assert(DW_PIX * DW_G == DW_THREADS, "one (pixel, float4) item per thread and chunk");
 constexpr int DW_MAX_C = 512;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // TRAIN (pfk_dwconv_layernorm_train_f32): the same arithmetic in the same order — `out` has the same bits — and the normalised value
 // (u - mean) * rstd goes to `xhat`, the pixel's rstd to `rstd_out`: what pfk_layernorm_bwd_f32 reads.
 template <int K, bool TRAIN = false>
@@ -161,21 +155,6 @@ constexpr int BT_CC = 64;                 // channels per staged chunk: 32 pairs
 constexpr int BT_NCH = DW_MAX_C / BT_CC;  // 8
 constexpr int BT_THREADS = 256;           // 8 strips (2 per tile row) x 32 pairs
 static_assert((BT_TY * BT_TX / BT_PX) * (BT_CC / 2) == BT_THREADS, "one (strip, channel pair) item per thread and chunk");
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x2 bf16x2_widen(unsigned w) {     // two bf16 -> fp32, exact
-  f32x2 v;
-  v.x = __builtin_bit_cast(float, w << 16);
-  v.y = __builtin_bit_cast(float, w & 0xffff0000u);
-  return v;
-}
-
-__device__ __forceinline__ float half_wave_sum(float v) {      // over the 32 lanes of this lane's half-wave
-#pragma unroll
-  for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // TRAIN (pfk_dwconv_layernorm_train_b16): the same arithmetic in the same order — `out` has the same bits — and the fp32 normalised
 // value (u - mean) * rstd goes to `xhat` rounded once, the pixel's fp32 rstd to `rstd_out`: what pfk_layernorm_bwd_b16 reads.
 template <int K, bool TRAIN = false>
@@ -228,7 +207,7 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
           const unsigned* hrow = hw32 + ((ry + ky) * HX + rx) * (BT_CC / 2) + j;
 #pragma unroll
           for (int i = 0; i < WIN; ++i) {
-            const f32x2 h = bf16x2_widen(hrow[i * (BT_CC / 2)]);
+            const f32x2 h = widen2(hrow[i * (BT_CC / 2)]);
 #pragma unroll
             for (int o = 0; o < BT_PX; ++o) {
               const int kx = i - o;
@@ -248,7 +227,7 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
 #pragma unroll
     for (int ch = 0; ch < BT_NCH; ++ch)
       if (ch * BT_CC + 2 * j < C) sum += acc[ch][o].x + acc[ch][o].y;
-    mean[o] = half_wave_sum(sum) * inv_c;
+    mean[o] = wave_sum<32>(sum) * inv_c;                      // over the 32 lanes of this lane's half-wave
   }
 #pragma unroll
   for (int o = 0; o < BT_PX; ++o) {
@@ -260,7 +239,7 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
         s2 += dx * dx + dy * dy;
       }
     }
-    rstd[o] = 1.0f / sqrtf(half_wave_sum(s2) * inv_c + eps);
+    rstd[o] = 1.0f / sqrtf(wave_sum<32>(s2) * inv_c + eps);
   }
   const int y = y0 + ry;
   if (y >= H) return;
@@ -280,9 +259,8 @@ __global__ __launch_bounds__(BT_THREADS) void dwconv_ln_b16_kernel(const __bf16*
     for (int o = 0; o < BT_PX; ++o) {
       const int x = x0 + rx + o;
       if (x >= W) continue;
-      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
       const float xh0 = (acc[ch][o].x - mean[o]) * rstd[o], xh1 = (acc[ch][o].y - mean[o]) * rstd[o];
-      bf16x2 v;
+      bf16x2 v;                                                  // store_row<2> written out: through it the whole kernel schedules differently
       v[0] = (__bf16)(xh0 * w0 + b0);
       v[1] = (__bf16)(xh1 * w1 + b1);
       *reinterpret_cast<bf16x2*>(out + (img + (long long)y * W + x) * out_ld + c) = v;

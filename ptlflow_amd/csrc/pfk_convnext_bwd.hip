@@ -29,57 +29,6 @@ constexpr int LN_WAVES = 4;               // waves (= rows in flight) per block
 constexpr int LN_MAX_BLOCKS = 1024;
 constexpr int LN_RED_PARTS = 4;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// N consecutive channels of a row as fp32 (bf16: widened, exact) and back (bf16: one rounding to nearest even); p is N * sizeof(T)
-// aligned
-template <int N>
-__device__ __forceinline__ void load_row(const float* p, float* v) {
-  if constexpr (N == 1) v[0] = *p;
-  else {
-    static_assert(N == 4, "one float or one float4");
-    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = q[e];
-  }
-}
-template <int N>
-__device__ __forceinline__ void load_row(const __bf16* p, float* v) {
-  static_assert(N == 8, "16 bytes of a bf16 row");
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 w = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[2 * e] = __builtin_bit_cast(float, w[e] << 16);
-    v[2 * e + 1] = __builtin_bit_cast(float, w[e] & 0xffff0000u);
-  }
-}
-template <int N>
-__device__ __forceinline__ void store_row(float* p, const float* v) {
-  if constexpr (N == 1) *p = v[0];
-  else {
-    static_assert(N == 4, "one float or one float4");
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  }
-}
-template <int N>
-__device__ __forceinline__ void store_row(__bf16* p, const float* v) {
-  typedef __bf16 bf16xN __attribute__((ext_vector_type(N)));
-  bf16xN q;
-#pragma unroll
-  for (int e = 0; e < N; ++e) q[e] = (__bf16)v[e];
-  *reinterpret_cast<bf16xN*>(p) = q;
-}
-__device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void store4(__bf16* p, f32x4 v) {
-  const float a[4] = {v[0], v[1], v[2], v[3]};
-  store_row<4>(p, a);
-}
-
 // channels per 16-byte row access, and the rule the entries check: C and ld in multiples of it
 template <typename T>
 constexpr int QUANTUM = 16 / (int)sizeof(T);
@@ -360,7 +309,7 @@ __global__ __launch_bounds__(256) void gelu_rows_kernel(const T* __restrict__ x,
     }
   } else {
 #pragma unroll
-    for (int e = 0; e < V; ++e) o[e] = 0.5f * v[e] * (1.0f + erff(v[e] * INV_SQRT2));      // the epilogue's formula (pfk_gemm.h)
+    for (int e = 0; e < V; ++e) o[e] = 0.5f * v[e] * (1.0f + erff(v[e] * INV_SQRT2));      // gelu_erf (pfk_common.h) written out: the call allocates this kernel's registers differently
   }
   store_row<V>(out + r * out_ld + c, o);
 }

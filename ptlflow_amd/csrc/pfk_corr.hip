@@ -206,9 +206,9 @@ __global__ __launch_bounds__(256) void lookup_kernel(const LookupArgs a) {
             const int e = lane + 64 * e2;
             if (e < PATCH * (PW / 2)) {
               const int yy = e / (PW / 2), xp = e - yy * (PW / 2);
-              const unsigned wv = __builtin_bit_cast(unsigned, v[q][e2]);
-              s_patch[wid][q][yy * PLD + 2 * xp] = __builtin_bit_cast(float, wv << 16);            // exact widening of the two halves
-              s_patch[wid][q][yy * PLD + 2 * xp + 1] = __builtin_bit_cast(float, wv & 0xffff0000u);
+              const f32x2 f = widen2(__builtin_bit_cast(unsigned, v[q][e2]));                      // exact widening of the two halves
+              s_patch[wid][q][yy * PLD + 2 * xp] = f.x;
+              s_patch[wid][q][yy * PLD + 2 * xp + 1] = f.y;
             }
           }
       } else {

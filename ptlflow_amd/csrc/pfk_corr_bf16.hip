@@ -16,7 +16,6 @@ using namespace pfkg;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TM = 128, TN = 128, KC = 64;          // tile and K chunk (channels)
 constexpr int ROWB = 64;                            // LDS row: 32 bf16
@@ -41,7 +40,7 @@ __global__ __launch_bounds__(256, 4) void corr_bf16_kernel(const CorrBfArgs g) {
   tile_of(bid, g.tiles_m, g.tiles_n, g.supertile, tile_m, tile_n);
   const int m0 = tile_m * TM, n0 = tile_n * TN;
   const long long batch = blockIdx.y;
-  const __amdgpu_buffer_rsrc_t rsa = make_rsrc(g.a + batch * g.a_bs), rsb = make_rsrc(g.b + batch * g.b_bs);
+  const __amdgpu_buffer_rsrc_t rsa = buffer_rsrc(g.a + batch * g.a_bs), rsb = buffer_rsrc(g.b + batch * g.b_bs);
 
   // staging role: 16-byte piece c16 (of the chunk's 128 B) of rows r0 + 32 * i, both operands
   const int c16 = t & 7, r0 = t >> 3;

@@ -249,25 +249,13 @@ static inline int in_chunks(int B) { int c = 1024 / (B > 0 ? B : 1); return c < 
 // low digits of the variance when the sums carry fp32 accumulation error, and everything downstream of the norm —
 // the normalised activations, their relu masks and, in training, the weight gradients of the layers in front of it — inherits
 // that error (measured on BasicEncoder gradients: 9e-3 with fp32 sums, 1e-6 with double; MIOpen's fp32 kernels 9e-4).
-typedef double f64x4s __attribute__((ext_vector_type(4)));
-
-// four consecutive channels of a pixel-major row as fp32: fp32 rows as they are, bf16 rows widened exactly
-__device__ __forceinline__ f32x4 ld4f(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 ld4f(const __bf16* p) {
-  typedef unsigned int u32x2e __attribute__((ext_vector_type(2)));
-  const u32x2e w = *reinterpret_cast<const u32x2e*>(p);
-  f32x4 v;
-  v[0] = __builtin_bit_cast(float, w[0] << 16); v[1] = __builtin_bit_cast(float, w[0] & 0xffff0000u);
-  v[2] = __builtin_bit_cast(float, w[1] << 16); v[3] = __builtin_bit_cast(float, w[1] & 0xffff0000u);
-  return v;
-}
 
 // part: two arrays [B][nch][C] one after the other (sum, then sum of squares; `astride` doubles apart)
 // TX = __bf16: the statistics of a bf16 convolution output (what F.instance_norm sees under the reference's autocast switch)
 template <typename TX>
 __global__ __launch_bounds__(256) void instnorm_partial_kernel(const TX* __restrict__ x, int ld, int C, int HW,
                                                                double* __restrict__ part, long long astride) {
-  __shared__ f64x4s red[2][256];
+  __shared__ f64x4 red[2][256];
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int tpr = C >> 2;                   // threads per row
   const int rpi = 256 / tpr;                // rows per iteration
@@ -277,16 +265,16 @@ __global__ __launch_bounds__(256) void instnorm_partial_kernel(const TX* __restr
   const int nch = (int)gridDim.x;
   const int rows = (HW + nch - 1) / nch;
   const int r0 = chunk * rows, r1 = min(HW, r0 + rows);
-  f64x4s s0 = {0., 0., 0., 0.}, q0 = {0., 0., 0., 0.};
+  f64x4 s0 = {0., 0., 0., 0.}, q0 = {0., 0., 0., 0.};
   if (active) {
     const TX* base = x + (long long)b * HW * ld + c4;
     // two independent accumulator sets: the fp64 add / fma chain of one set would otherwise serialise the loop (a chunk has
     // only a few hundred rows per thread and, at batch 1, the grid is far from filling the chip)
-    f64x4s s1 = {0., 0., 0., 0.}, q1 = {0., 0., 0., 0.};
+    f64x4 s1 = {0., 0., 0., 0.}, q1 = {0., 0., 0., 0.};
     int r = r0 + rr;
     for (; r + rpi < r1; r += 2 * rpi) {
-      const f32x4 v0 = ld4f(base + (long long)r * ld);
-      const f32x4 v1 = ld4f(base + (long long)(r + rpi) * ld);
+      const f32x4 v0 = load4_widen(base + (long long)r * ld);
+      const f32x4 v1 = load4_widen(base + (long long)(r + rpi) * ld);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const double d0 = (double)v0[e], d1 = (double)v1[e];
@@ -295,7 +283,7 @@ __global__ __launch_bounds__(256) void instnorm_partial_kernel(const TX* __restr
       }
     }
     if (r < r1) {
-      const f32x4 v = ld4f(base + (long long)r * ld);
+      const f32x4 v = load4_widen(base + (long long)r * ld);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const double d = (double)v[e];
@@ -309,9 +297,9 @@ __global__ __launch_bounds__(256) void instnorm_partial_kernel(const TX* __restr
   __syncthreads();
   for (int u = t; u < 2 * tpr; u += 256) {   // [0, tpr): sums; [tpr, 2 tpr): sums of squares
     const int which = u >= tpr, tt = u - which * tpr;
-    f64x4s s = red[which][tt];
+    f64x4 s = red[which][tt];
     for (int k = 1; k < rpi; ++k) s += red[which][tt + k * tpr];
-    *reinterpret_cast<f64x4s*>(part + which * astride + ((long long)b * nch + chunk) * C + tt * 4) = s;
+    *reinterpret_cast<f64x4*>(part + which * astride + ((long long)b * nch + chunk) * C + tt * 4) = s;
   }
 }
 
@@ -373,23 +361,6 @@ __global__ void instnorm_finish_kernel(const double* __restrict__ sum, const dou
 // y = (x - mean) * rstd ; relu? ; [y = residual + y ; relu?]   (float4 per thread)
 // TR / TO = __bf16: the residual rows / the output as the K8b convolutions hold activations (ABI 7): the statistics and the
 // normalisation stay fp32 on the fp32 convolution output, only what the next convolution reads is 16 bits wide.
-__device__ __forceinline__ f32x4 na_load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 na_load4(const __bf16* p) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-  f32x4 v;
-  v[0] = __builtin_bit_cast(float, w[0] << 16); v[1] = __builtin_bit_cast(float, w[0] & 0xffff0000u);
-  v[2] = __builtin_bit_cast(float, w[1] << 16); v[3] = __builtin_bit_cast(float, w[1] & 0xffff0000u);
-  return v;
-}
-__device__ __forceinline__ void na_store4(float* p, const f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void na_store4(__bf16* p, const f32x4 v) {
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  bf16x4 h;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
-  *reinterpret_cast<bf16x4*>(p) = h;
-}
 
 template <typename TR = float, typename TO = float, typename TX = float>
 __global__ __launch_bounds__(256) void norm_apply_kernel(const TX* __restrict__ x, int x_ld, const float* __restrict__ mean,
@@ -404,20 +375,20 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const TX* __restrict__ 
   const long long sidx = (p / HW) * C + c4;
   const f32x4 m = *reinterpret_cast<const f32x4*>(mean + sidx);
   const f32x4 r = *reinterpret_cast<const f32x4*>(rstd + sidx);
-  f32x4 v = ld4f(x + p * x_ld + c4);
+  f32x4 v = load4_widen(x + p * x_ld + c4);
   v = (v - m) * r;
   if (relu) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];
   }
   if (residual != nullptr) {
-    v = na_load4(residual + p * res_ld + c4) + v;
+    v = load4_widen(residual + p * res_ld + c4) + v;
     if (relu_after) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];
     }
   }
-  na_store4(out + p * out_ld + c4, v);
+  store4(out + p * out_ld + c4, v);
 }
 
 // The same with a residual that is itself a raw convolution output in front of its own instance norm (the stem's output under
@@ -436,7 +407,7 @@ __global__ __launch_bounds__(256) void norm_apply_res_kernel(const float* __rest
   const long long sidx = (p / HW) * C + c4;
   const f32x4 m = *reinterpret_cast<const f32x4*>(mean + sidx), r = *reinterpret_cast<const f32x4*>(rstd + sidx);
   const f32x4 rm = *reinterpret_cast<const f32x4*>(res_mean + sidx), rr = *reinterpret_cast<const f32x4*>(res_rstd + sidx);
-  const f32x4 xv = ld4f(x + p * x_ld + c4), rv = ld4f(residual + p * res_ld + c4);
+  const f32x4 xv = load4_widen(x + p * x_ld + c4), rv = load4_widen(residual + p * res_ld + c4);
   const float lo = relu ? 0.f : -__builtin_inff(), rlo = res_relu ? 0.f : -__builtin_inff(), alo = relu_after ? 0.f : -__builtin_inff();
   f32x4 v;
 #pragma unroll
@@ -448,7 +419,7 @@ __global__ __launch_bounds__(256) void norm_apply_res_kernel(const float* __rest
     y = __fadd_rn(z, y);
     v[e] = (y < alo) ? alo : y;
   }
-  na_store4(out + p * out_ld + c4, v);
+  store4(out + p * out_ld + c4, v);
 }
 
 
@@ -465,7 +436,6 @@ __global__ __launch_bounds__(256) void norm_apply_res_kernel(const float* __rest
 // fp32 sums lose 2-3 digits there (measured: 1e-2 relative on encoder weight gradients, for MIOpen's kernels as well); torch's
 // CPU kernels accumulate float tensors in double for the same reason.  MI355X's fp64 vector rate makes this free next to the
 // memory traffic of the pass.
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void norm_bwd_partial_kernel(const float* __restrict__ x, int x_ld, const float* __restrict__ dy,
                                                                int dy_ld, const float* __restrict__ mean,

@@ -78,20 +78,11 @@ __device__ __forceinline__ void tile_of(int bid, int tiles_m, int tiles_n, int S
   tile_n = n_base + l2 - (l2 / wb) * wb;
 }
 
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // GemmArgs::relu == ACT_GELU: the LINEAR epilogue applies the exact GELU where it would apply relu (PFK_EPI_LINEAR_GELU of
 // include/pfk.h; desc_to_args sets it, every other producer of GemmArgs leaves relu at 0 / 1)
 constexpr int ACT_GELU = 2;
-// nn.GELU() (approximate='none'): 0.5 * v * (1 + erf(v / sqrt(2)))
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;  // >= num_records of every descriptor below
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
+constexpr unsigned OOB = 0x80000000u;  // >= num_records of every buffer_rsrc() descriptor
 
 // Epilogue for accumulator registers [R0, R1) of every 32x32 block of the wave tile.
 template <int MT, int NT, int EPI, int R0, int R1>
@@ -162,9 +153,6 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& a, const f32x16 (&a
   const int col_l = lane & 31, row_l = (lane >> 5) * 4;
   const int rrow = lane >> 3, c4 = (lane & 7) * 4;     // read side: 8 rows per pass, 4 columns per lane
   // explicit global address space: with the plain generic pointers hipcc emitted flat_store for the LINEAR branch
-  typedef __attribute__((address_space(1))) float gfloat;
-  typedef __attribute__((address_space(1))) f32x4 gf32x4;
-  typedef __attribute__((address_space(1))) __bf16 gbf16;
   gfloat* outp = (gfloat*)(a.out + batch * a.o_bs);
   // 16-byte accesses need the row stride / offsets to be multiples of 4 floats and the bases 16-byte aligned (pfk.h asks for it;
   // the training path's fresh [M, cout] outputs with cout = 126 or 2 do not comply): wave-uniform fall-back to scalar accesses

@@ -75,8 +75,8 @@ struct Stager {
   __device__ __forceinline__ Stager(const GemmArgs& a, int t, NoTile) {
     H = a.H; W = a.W; kh = a.kh; kw = a.kw; ph = a.kh >> 1; pw = a.kw >> 1; nsrc = a.nsrc;
     ld0 = a.ld0; ld1 = a.ld1; ld2 = a.ld2; ch0 = a.ch0; ch1 = a.ch1; ch2 = a.ch2;
-    rs1 = make_rsrc(a.src1);
-    rs2 = make_rsrc(a.src2);
+    rs1 = buffer_rsrc(a.src1);
+    rs2 = buffer_rsrc(a.src2);
     c4 = (t & 7) * 4;
     r0 = t >> 3;
     // LD == 32: chunk' = chunk ^ ((row >> 1) & 7) — a 16-lane ds_read_b128 group (16 rows, one logical chunk) then
@@ -96,8 +96,8 @@ struct Stager {
   // and the batch-dependent descriptors.  32-bit arithmetic with the host-made multipliers of GemmArgs (M < 2^31 rows is implied
   // by the 32-bit byte offsets the kernels address their sources with; launch() / launch_pp() fill the multipliers).
   __device__ __forceinline__ void retarget(const GemmArgs& a, long long m0, int n0, long long batch) {
-    rs0 = make_rsrc(a.src0 + batch * a.a_bs);
-    rsw = make_rsrc(a.weight + batch * a.b_bs);
+    rs0 = buffer_rsrc(a.src0 + batch * a.a_bs);
+    rsw = buffer_rsrc(a.weight + batch * a.b_bs);
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
       const unsigned p = (unsigned)m0 + (unsigned)(r0 + 32 * i);
@@ -171,7 +171,7 @@ struct Stager {
     const float* const* srcv = &a.src0;
     const float* p = srcv[sg];
     if (sg == 0) p += batch * a.a_bs;
-    rs = make_rsrc(p);
+    rs = buffer_rsrc(p);
     cld = (&a.ld0)[sg];
     cch = (&a.ch0)[sg];
 #pragma unroll

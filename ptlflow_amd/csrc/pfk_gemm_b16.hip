@@ -25,10 +25,6 @@ using namespace pfkg;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK16 = 64;          // channels per K-step
 constexpr int ROW16 = 128;        // bytes per LDS row
 
@@ -86,7 +82,7 @@ struct Stager16 {
   __device__ __forceinline__ Stager16(const B16Args& a, long long m0, int n0, int t) {
     W = a.W; kh = a.kh; kw = a.kw; ph = a.kh >> 1; pw = a.kw >> 1; nsrc = a.nsrc;
     ld0 = a.ld[0]; ld1 = a.ld[1]; ld2 = a.ld[2]; ch0 = a.ch[0]; ch1 = a.ch[1]; ch2 = a.ch[2];
-    rs0 = make_rsrc(a.src[0]); rs1 = make_rsrc(a.src[1]); rs2 = make_rsrc(a.src[2]); rsw = make_rsrc(a.weight);
+    rs0 = buffer_rsrc(a.src[0]); rs1 = buffer_rsrc(a.src[1]); rs2 = buffer_rsrc(a.src[2]); rsw = buffer_rsrc(a.weight);
     total = a.steps;
     const int r0 = t >> 3;
     // rows of one thread differ by multiples of RPP (a multiple of 16): the swizzle key is the same for all of them
@@ -221,12 +217,6 @@ struct Epilogue16 {
   // 16-byte access per lane and pass, the fp32 h two; half the passes and half the store instructions of the 4-column form
   static constexpr int COLS = LIN ? 4 : 8;
   static constexpr int CW = NT * 32, LPR = CW / COLS, RPS = 64 / LPR, PASSES = 32 / RPS;
-  typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(1))) u32x4e gu32x4e;
-  typedef __attribute__((address_space(1))) float gfloat;
-  typedef __attribute__((address_space(1))) f32x4 gf32x4;
-  typedef __attribute__((address_space(1))) u32x2 gu32x2;
-  typedef __attribute__((address_space(1))) __bf16 gbf16;
   long long m_base;
   int n, rrow, c4;
   bool full, any, has_res;
@@ -235,7 +225,7 @@ struct Epilogue16 {
   // epilogue (8 registers per pass) has one: its later bands are requested behind the previous band's stores and wait for them.
   static constexpr int NSETS = Q ? 1 : 2;
   f32x4 res32[LIN ? 2 : 1][LIN ? PASSES : 1];
-  u32x4e res16[LIN ? 1 : NSETS][LIN ? 1 : PASSES], aux16[LIN ? 1 : NSETS][LIN ? 1 : PASSES];      // eight bf16 each
+  u32x4 res16[LIN ? 1 : NSETS][LIN ? 1 : PASSES], aux16[LIN ? 1 : NSETS][LIN ? 1 : PASSES];      // eight bf16 each
   f32x4 h32[1][Q ? PASSES : 1][2];
 
   __device__ __forceinline__ Epilogue16(const B16Args& a, long long m_base_, int n_base, int lane) : m_base(m_base_) {
@@ -245,18 +235,11 @@ struct Epilogue16 {
     has_res = a.residual != nullptr;
   }
 
-  static __device__ __forceinline__ f32x4 widen(const u32x2 w) {      // four bf16 -> fp32 (exact)
-    f32x4 v;
-    v[0] = __builtin_bit_cast(float, w[0] << 16); v[1] = __builtin_bit_cast(float, w[0] & 0xffff0000u);
-    v[2] = __builtin_bit_cast(float, w[1] << 16); v[3] = __builtin_bit_cast(float, w[1] & 0xffff0000u);
-    return v;
-  }
-
-  static __device__ __forceinline__ f32x4 widen_lo(const u32x4e w) { const u32x2 h = {w[0], w[1]}; return widen(h); }
-  static __device__ __forceinline__ f32x4 widen_hi(const u32x4e w) { const u32x2 h = {w[2], w[3]}; return widen(h); }
-  static __device__ __forceinline__ u32x4e pack_bf16x8(const f32x4 a, const f32x4 b) {
+  static __device__ __forceinline__ f32x4 widen_lo(const u32x4 w) { const u32x2 h = {w[0], w[1]}; return widen4(h); }
+  static __device__ __forceinline__ f32x4 widen_hi(const u32x4 w) { const u32x2 h = {w[2], w[3]}; return widen4(h); }
+  static __device__ __forceinline__ u32x4 pack_bf16x8(const f32x4 a, const f32x4 b) {
     const u32x2 lo = pack_bf16x4(a), hi = pack_bf16x4(b);
-    const u32x4e w = {lo[0], lo[1], hi[0], hi[1]};
+    const u32x4 w = {lo[0], lo[1], hi[0], hi[1]};
     return w;
   }
 
@@ -274,7 +257,7 @@ struct Epilogue16 {
       if constexpr (LIN) {
         res32[S][pass] = zero4;
         if (ok && a.residual_bf16) {       // bf16 rows (cout % 4 == 0 on these launches): widened at once
-          res32[S][pass] = widen(*reinterpret_cast<const u32x2*>(reinterpret_cast<const __bf16*>(a.residual) + p * a.residual_ld + n));
+          res32[S][pass] = load4_widen(reinterpret_cast<const __bf16*>(a.residual) + p * a.residual_ld + n);
         } else if (ok) {
           const float* rp = reinterpret_cast<const float*>(a.residual) + p * a.residual_ld + n;
           if (full) res32[S][pass] = *reinterpret_cast<const f32x4*>(rp);
@@ -285,12 +268,12 @@ struct Epilogue16 {
           }
         }
       } else {
-        const u32x4e zero8 = {0u, 0u, 0u, 0u};
-        res16[S][pass] = (ok && has_res) ? *reinterpret_cast<const u32x4e*>(reinterpret_cast<const __bf16*>(a.residual) + p * a.residual_ld + n) : zero8;
+        const u32x4 zero8 = {0u, 0u, 0u, 0u};
+        res16[S][pass] = (ok && has_res) ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(a.residual) + p * a.residual_ld + n) : zero8;
         if constexpr (ZR) {
-          aux16[S][pass] = (ok && n >= ch) ? *reinterpret_cast<const u32x4e*>(reinterpret_cast<const __bf16*>(a.h_b16) + p * a.hb_ld + (n - ch)) : zero8;
+          aux16[S][pass] = (ok && n >= ch) ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(a.h_b16) + p * a.hb_ld + (n - ch)) : zero8;
         } else {
-          aux16[S][pass] = ok ? *reinterpret_cast<const u32x4e*>(reinterpret_cast<const __bf16*>(a.aux_z) + p * ch + n) : zero8;
+          aux16[S][pass] = ok ? *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(a.aux_z) + p * ch + n) : zero8;
           h32[S][pass][0] = ok ? *reinterpret_cast<const f32x4*>(a.h + p * a.h_ld + n) : zero4;
           h32[S][pass][1] = ok ? *reinterpret_cast<const f32x4*>(a.h + p * a.h_ld + n + 4) : zero4;
         }
@@ -339,10 +322,7 @@ struct Epilogue16 {
           }
           __bf16* ob = reinterpret_cast<__bf16*>(a.out) + p * a.out_ld + a.out_coff + n8;
           if (n8 + 7 < a.b_rows) {
-            const u32x2 lo = pack_bf16x4(v0), hi = pack_bf16x4(v1);
-            typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-            const u32x4v w = {lo[0], lo[1], hi[0], hi[1]};
-            *(__attribute__((address_space(1))) u32x4v*)ob = w;
+            *(gu32x4*)ob = pack_bf16x8(v0, v1);
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -401,8 +381,8 @@ struct Epilogue16 {
         f32x4 g0, g1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { g0[e] = fast_sigmoid(v[e]); g1[e] = fast_sigmoid(w[e]); }
-        if (n < ch) *(gu32x4e*)(reinterpret_cast<__bf16*>(a.aux_z) + p * ch + n) = pack_bf16x8(g0, g1);
-        else *(gu32x4e*)(reinterpret_cast<__bf16*>(a.aux_rh) + p * ch + (n - ch)) =
+        if (n < ch) *(gu32x4*)(reinterpret_cast<__bf16*>(a.aux_z) + p * ch + n) = pack_bf16x8(g0, g1);
+        else *(gu32x4*)(reinterpret_cast<__bf16*>(a.aux_rh) + p * ch + (n - ch)) =
             pack_bf16x8(g0 * widen_lo(aux16[S][pass]), g1 * widen_hi(aux16[S][pass]));
       } else {  // PFK_EPI_GRU_Q
         f32x4 w = *reinterpret_cast<const f32x4*>(reg + row * CW + c4 + 4);
@@ -418,7 +398,7 @@ struct Epilogue16 {
         }
         *(gf32x4*)(a.h + p * a.h_ld + n) = o0;
         *(gf32x4*)(a.h + p * a.h_ld + n + 4) = o1;
-        if (a.h_b16 != nullptr) *(gu32x4e*)(reinterpret_cast<__bf16*>(a.h_b16) + p * a.hb_ld + n) = pack_bf16x8(o0, o1);
+        if (a.h_b16 != nullptr) *(gu32x4*)(reinterpret_cast<__bf16*>(a.h_b16) + p * a.hb_ld + n) = pack_bf16x8(o0, o1);
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads are done before the next band overwrites the region
@@ -746,7 +726,7 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_b16_kernel(const MuB16Ar
   const long long m0 = (long long)(bid >> 2) * BM;
   const int n0 = quarter * BN;
 
-  const __amdgpu_buffer_rsrc_t rsx = make_rsrc(a.x), rsw = make_rsrc(a.w);
+  const __amdgpu_buffer_rsrc_t rsx = buffer_rsrc(a.x), rsw = buffer_rsrc(a.w);
   const int r0 = tid >> 3;
   const int lc8 = ((tid & 7) ^ ((r0 >> 1) & 7)) * 8;      // logical chunk of this lane's physical slot (rows of one thread share the key)
   const unsigned wave_off = (unsigned)wid * 1024u;

@@ -25,7 +25,6 @@ using namespace pfkg;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BKB = 32;            // channels per K sub-step (same K order / padding as the fp32 path's packed weight)
 constexpr int ROWB = 64;           // bytes per LDS row: 32 bf16
@@ -65,10 +64,10 @@ struct StagerBF {
   __device__ __forceinline__ StagerBF(const GemmArgs& a, long long m0, int n0, int t) {
     H = a.H; W = a.W; kh = a.kh; kw = a.kw; ph = a.kh >> 1; pw = a.kw >> 1; nsrc = a.nsrc;
     ld0 = a.ld0; ld1 = a.ld1; ld2 = a.ld2; ch0 = a.ch0; ch1 = a.ch1; ch2 = a.ch2;
-    rs0 = make_rsrc(a.src0);
-    rs1 = make_rsrc(a.src1);
-    rs2 = make_rsrc(a.src2);
-    rsw = make_rsrc(a.wbf);
+    rs0 = buffer_rsrc(a.src0);
+    rs1 = buffer_rsrc(a.src1);
+    rs2 = buffer_rsrc(a.src2);
+    rsw = buffer_rsrc(a.wbf);
     plane_bytes = (int)a.wbf_plane_bytes;
     total = a.sk_steps;
     c8 = (t & 3) * 8;
@@ -168,8 +167,6 @@ struct StagerBF {
   f32x4 sr;
   template <int S, int U, int I, int Hf, int PL>
   __device__ __forceinline__ void split_piece() {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     if constexpr (PL == 0) sr = ra[S][U][I][Hf];
     bf16x4 h;
 #pragma unroll

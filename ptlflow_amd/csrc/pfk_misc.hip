@@ -197,12 +197,6 @@ __global__ __launch_bounds__(256, 2) void conv_cin2_mfma_kernel(const float* __r
 
 int g_cin2_valu = 0;           // pfk_debug_set_cin2_valu: 0 = by size, 1 = always the tiled VALU kernel, 2 = the MFMA kernel at every size
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // one reduce-scatter step: of 2 N values a lane keeps the half selected by its bit OFF and adds the partner's copy of it
 template <int N, int OFF>
 __device__ __forceinline__ void rs_step(float* s, int lane) {
@@ -279,11 +273,9 @@ __global__ __launch_bounds__(256) void flow_delta_kernel(
   rs_step<PIX / 2, 16>(s, lane);
   rs_step<PIX / 4, 8>(s, lane);
   if constexpr (PIX == 8) rs_step<1, 4>(s, lane);
-  float tot = s[0];
-#pragma unroll
-  for (int off = (PIX == 8 ? 2 : 4); off >= 1; off >>= 1) tot += __shfl_xor(tot, off, 64);
-  // lane l now holds total j = l >> (PIX == 8 ? 2 : 3) (bit 5 of the lane = most significant bit of j = the component)
   constexpr int REP = PIX == 8 ? 4 : 8;             // lanes per total
+  const float tot = wave_sum<REP>(s[0]);            // the butterfly's last steps, among the REP lanes of a total
+  // lane l now holds total j = l >> (PIX == 8 ? 2 : 3) (bit 5 of the lane = most significant bit of j = the component)
   const int j = lane / REP, o = j / PIX, q = j - o * PIX;
   if ((lane & (REP - 1)) == 0 && x0 + q < W) {
     const long long hw = (long long)H * W;
@@ -436,16 +428,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ x
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   float m = -INFINITY;
   for (int c = t; c < cols; c += 256) m = fmaxf(m, row[c]);
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+  m = wave_max(m);
   if (lane == 0) red[wid] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
   float sum = 0.f;
   for (int c = t; c < cols; c += 256) sum += expf(row[c] - m);
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) sum += __shfl_xor(sum, s, 64);
+  sum = wave_sum(sum);
   if (lane == 0) red[wid] = sum;
   __syncthreads();
   sum = (red[0] + red[1]) + (red[2] + red[3]);

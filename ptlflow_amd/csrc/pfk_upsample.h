@@ -13,8 +13,6 @@
 #pragma once
 #include "pfk_common.h"
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int UP_MAX_INFO = 8;   // info channels of upsample_data the kernels hold in registers
 
 // Nine logits -> nine normalised weights, in place: max in tap order, expf(m - max), sum in tap order, ONE reciprocal, e * inv.

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void convex_upsample_bwd_kernel(const float* _
     grow[k * 64] = m[k] * (dw[k] - dot);
     float cxv = m[k] * gx, cyv = m[k] * gy;
 #pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
+    for (int s = 32; s >= 1; s >>= 1) {      // two wave_sums interleaved step by step: as two calls the kernel schedules differently
       cxv += __shfl_xor(cxv, s, 64);
       cyv += __shfl_xor(cyv, s, 64);
     }

@@ -20,7 +20,6 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned OOB = 0x80000000u;
 
 struct WgradArgs {
@@ -35,10 +34,6 @@ struct WgradArgs {
   int with_bias;               // one extra 32-column chunk whose column 0 is sum_p dY[p][co] (A = a column of ones): the bias gradient
   long long px_per_split; // multiple of 32
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 
 // One (source, tap, 32-channel) entry of the forward kernel's K enumeration.
 struct ChunkRef { const float* src; int ld, cch, c0, dy, dx, bias, live; };
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
   const int split = blockIdx.y;
   const int co0 = tile_m * CO;
 
-  const __amdgpu_buffer_rsrc_t rsy = rsrc_of(a.dy);
+  const __amdgpu_buffer_rsrc_t rsy = buffer_rsrc(a.dy);
   const long long p_begin = (long long)split * a.px_per_split;
   const long long p_end = min(a.M, p_begin + a.px_per_split);
   const int steps = p_end > p_begin ? (int)((p_end - p_begin + 31) >> 5) : 0;
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const ChunkRef c = chunk_ref(a, grp * NCH + i);
-    rsx[i] = rsrc_of(c.src);
+    rsx[i] = buffer_rsrc(c.src);
     tap_off[i] = (c.dy * a.W + c.dx) * c.ld + c.c0 + q * 4;
     cdy[i] = c.dy; cdx[i] = c.dx; cld[i] = c.ld;
     c_ok[i] = c.live && !c.bias && c.c0 + q * 4 < c.cch;
@@ -185,11 +180,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 __device__ __forceinline__ f32x4 sigmoid4(f32x4 v) {
   f32x4 o;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = 1.0f / (1.0f + expf(-v[e]));
+  for (int e = 0; e < 4; ++e) o[e] = sigmoid_f(v[e]);
   return o;
 }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 __global__ __launch_bounds__(256) void gru_f1_kernel(const float* __restrict__ azr, const float* __restrict__ h, int h_ld,
                                                      float* __restrict__ z, float* __restrict__ r, float* __restrict__ rh,
@@ -198,10 +191,10 @@ __global__ __launch_bounds__(256) void gru_f1_kernel(const float* __restrict__ a
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, p = idx / tpr;
   if (p >= M) return;
   const int c = (int)(idx - p * tpr) * 4;
-  const f32x4 zz = sigmoid4(ld4(azr + p * 2 * C + c)), rr = sigmoid4(ld4(azr + p * 2 * C + C + c));
-  st4(z + p * C + c, zz);
-  st4(r + p * C + c, rr);
-  st4(rh + p * C + c, rr * ld4(h + p * h_ld + c));
+  const f32x4 zz = sigmoid4(load4_widen(azr + p * 2 * C + c)), rr = sigmoid4(load4_widen(azr + p * 2 * C + C + c));
+  store4(z + p * C + c, zz);
+  store4(r + p * C + c, rr);
+  store4(rh + p * C + c, rr * load4_widen(h + p * h_ld + c));
 }
 
 __global__ __launch_bounds__(256) void gru_f2_kernel(const float* __restrict__ aq, const float* __restrict__ z,
@@ -211,12 +204,12 @@ __global__ __launch_bounds__(256) void gru_f2_kernel(const float* __restrict__ a
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, p = idx / tpr;
   if (p >= M) return;
   const int c = (int)(idx - p * tpr) * 4;
-  const f32x4 a = ld4(aq + p * C + c), zz = ld4(z + p * C + c), hh = ld4(h + p * h_ld + c);
+  const f32x4 a = load4_widen(aq + p * C + c), zz = load4_widen(z + p * C + c), hh = load4_widen(h + p * h_ld + c);
   f32x4 qq;
 #pragma unroll
   for (int e = 0; e < 4; ++e) qq[e] = tanhf(a[e]);
-  st4(q + p * C + c, qq);
-  st4(hn + p * C + c, (1.0f - zz) * hh + zz * qq);
+  store4(q + p * C + c, qq);
+  store4(hn + p * C + c, (1.0f - zz) * hh + zz * qq);
 }
 
 __global__ __launch_bounds__(256) void gru_b1_kernel(const float* __restrict__ dhn, int dhn_ld, const float* __restrict__ z,
@@ -227,10 +220,10 @@ __global__ __launch_bounds__(256) void gru_b1_kernel(const float* __restrict__ d
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, p = idx / tpr;
   if (p >= M) return;
   const int c = (int)(idx - p * tpr) * 4;
-  const f32x4 g = ld4(dhn + p * dhn_ld + c), zz = ld4(z + p * C + c), qq = ld4(q + p * C + c), hh = ld4(h + p * h_ld + c);
-  st4(daq + p * C + c, g * zz * (1.0f - qq * qq));
-  st4(dazr + p * 2 * C + c, g * (qq - hh) * zz * (1.0f - zz));
-  st4(dh + p * C + c, g * (1.0f - zz));
+  const f32x4 g = load4_widen(dhn + p * dhn_ld + c), zz = load4_widen(z + p * C + c), qq = load4_widen(q + p * C + c), hh = load4_widen(h + p * h_ld + c);
+  store4(daq + p * C + c, g * zz * (1.0f - qq * qq));
+  store4(dazr + p * 2 * C + c, g * (qq - hh) * zz * (1.0f - zz));
+  store4(dh + p * C + c, g * (1.0f - zz));
 }
 
 __global__ __launch_bounds__(256) void gru_b2_kernel(const float* __restrict__ drh, const float* __restrict__ h, int h_ld,
@@ -240,9 +233,9 @@ __global__ __launch_bounds__(256) void gru_b2_kernel(const float* __restrict__ d
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x, p = idx / tpr;
   if (p >= M) return;
   const int c = (int)(idx - p * tpr) * 4;
-  const f32x4 g = ld4(drh + p * C + c), hh = ld4(h + p * h_ld + c), rr = ld4(r + p * C + c);
-  st4(dazr + p * 2 * C + C + c, g * hh * rr * (1.0f - rr));
-  st4(dh + p * C + c, ld4(dh + p * C + c) + g * rr);
+  const f32x4 g = load4_widen(drh + p * C + c), hh = load4_widen(h + p * h_ld + c), rr = load4_widen(r + p * C + c);
+  store4(dazr + p * 2 * C + C + c, g * hh * rr * (1.0f - rr));
+  store4(dh + p * C + c, load4_widen(dh + p * C + c) + g * rr);
 }
 
 int g_wgrad_variant = 0;   // 0: tile height by padding waste (pick_cb); 1 / 2 / 4: forced CB — pfk_debug_set_wgrad

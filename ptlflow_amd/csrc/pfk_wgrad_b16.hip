@@ -24,10 +24,8 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr unsigned OOB = 0x80000000u;
 constexpr int KS = 64;          // pixels per K-step
 
@@ -42,10 +40,6 @@ struct WgradB16Args {
   int with_bias;               // one extra 32-column chunk whose column 0 is sum_p dY[p][co] (A = a column of ones)
   long long px_per_split; // multiple of KS
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 
 // One (source, tap, 32-channel) entry of the K enumeration.
 struct ChunkRef { const void* src; int ld, cch, c0, dy, dx, bias, live; };
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_b16_kernel(const WgradB16Args 
   const int split = blockIdx.y;
   const int co0 = tile_m * 32 * CB;
 
-  const __amdgpu_buffer_rsrc_t rsy = rsrc_of(a.dy);
+  const __amdgpu_buffer_rsrc_t rsy = buffer_rsrc(a.dy);
   const long long p_begin = (long long)split * a.px_per_split;
   const long long p_end = min(a.M, p_begin + a.px_per_split);
   const int steps = p_end > p_begin ? (int)((p_end - p_begin + KS - 1) / KS) : 0;
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_b16_kernel(const WgradB16Args 
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const ChunkRef c = chunk_ref(a, grp * NCH + i);
-    rsx[i] = rsrc_of(c.src);
+    rsx[i] = buffer_rsrc(c.src);
     tap_off[i] = (c.dy * a.W + c.dx) * c.ld + c.c0 + q * 8;
     cdy[i] = c.dy; cdx[i] = c.dx; cld[i] = c.ld;
     c_ok[i] = c.live && !c.bias && c.c0 + q * 8 < c.cch;

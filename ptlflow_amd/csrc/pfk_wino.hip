@@ -58,7 +58,6 @@ constexpr int WN = 64;   // output channels per block
 constexpr int WK = 8;    // input channels per K-step
 constexpr int UIMG = 16 * WN * WK;   // floats of one K-step of one column block's U: the LDS image, 32 KB
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lfloat;   // LDS pointers keep their address space (ds_ instructions, 32-bit)
 typedef __attribute__((address_space(3))) f32x2 lf32x2;
 typedef __attribute__((address_space(3))) f32x4 lf32x4;
@@ -97,10 +96,6 @@ constexpr unsigned T_OK = 0x80000000u, T_ROW2 = 0x40000000u, T_COL2 = 0x20000000
 // A wave's parking area for A^T m A: 64 pixels (16 tiles x 4 outputs) x 32 columns, 16 floats of padding behind every 16 pixels (the
 // four tile groups kq of the accumulator layout write different banks; the row walk reads 1 KB runs)
 constexpr int ESZ = 64 * 32 + 4 * 16;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_n(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // NORM: mean and rstd of this thread's (image, channel) of K-step ks (zero for a tile past the end: its taps are all padding)
 __device__ __forceinline__ void wino_load_stat(__amdgpu_buffer_rsrc_t rm, __amdgpu_buffer_rsrc_t rr, unsigned soff, int ks, float (&mr)[2]) {
@@ -166,7 +161,6 @@ __device__ __forceinline__ void wino_mfma(const lfloat* aV, const lfloat* aU, co
 }
 
 typedef __attribute__((address_space(3))) unsigned lunsigned;
-typedef unsigned int u32x4v __attribute__((__vector_size__(16)));
 
 // Epilogue, row walk (see the kernel).  The lane's 8 pixels are output e = (lane >> 3) & 3 of the wave's tiles 2 * i + (lane >> 5),
 // i = 0..7, its 4 columns start at n0; tT = the offset table at (e, the wave's tile lane >> 5).  Byte offsets of the 8 row pieces in
@@ -181,7 +175,7 @@ __device__ __forceinline__ void wino_epi_request(const WinoArgs& a, const lunsig
     if constexpr (RES) ro[i] = tT[4 * WT + 2 * i] + (unsigned)n0 * 4u;
   }
   if constexpr (RES) {
-    const __amdgpu_buffer_rsrc_t rr = rsrc_n(a.res, a.res_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buffer_rsrc(a.res, a.res_bytes);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       if constexpr (VEC) {
@@ -203,8 +197,8 @@ __device__ __forceinline__ void wino_epi_request(const WinoArgs& a, const lunsig
 template <bool RES, bool VEC, bool STATS>
 __device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* rE, int n0, const unsigned (&oo)[8], const f32x4 (&r4)[8],
                                                double (&st)[8]) {
-  const __amdgpu_buffer_rsrc_t ro = rsrc_n(a.out, a.out_bytes);
-  const __amdgpu_buffer_rsrc_t rbias = rsrc_n(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
+  const __amdgpu_buffer_rsrc_t ro = buffer_rsrc(a.out, a.out_bytes);
+  const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
   float bias4[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) bias4[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, (unsigned)(n0 + j) * 4u, 0, 0));
@@ -231,7 +225,7 @@ __device__ __forceinline__ void wino_epi_store(const WinoArgs& a, const lfloat* 
       }
     }
     if constexpr (VEC) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, (f32x4{v[0], v[1], v[2], v[3]})), ro, oo[i], 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4{v[0], v[1], v[2], v[3]})), ro, oo[i], 0, 0);
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -259,10 +253,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino_f32_kernel(const WinoAr
   const int cb = blockIdx.x % a.ncb;
   const int t0 = (blockIdx.x / a.ncb) * WT;
 
-  const __amdgpu_buffer_rsrc_t rs = rsrc_n(a.src, a.src_bytes);
-  const __amdgpu_buffer_rsrc_t rw = rsrc_n(a.weight, a.w_bytes);
-  const __amdgpu_buffer_rsrc_t rm = rsrc_n(a.in_mean, NORM ? a.stat_bytes : 0u);
-  const __amdgpu_buffer_rsrc_t rr = rsrc_n(a.in_rstd, NORM ? a.stat_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(a.src, a.src_bytes);
+  const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.weight, a.w_bytes);
+  const __amdgpu_buffer_rsrc_t rm = buffer_rsrc(a.in_mean, NORM ? a.stat_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rr = buffer_rsrc(a.in_rstd, NORM ? a.stat_bytes : 0u);
 
   // ---- staging role: tile lt, channel cc of the K-step
   const int lt = tid >> 3, cc = tid & 7;
@@ -570,14 +564,14 @@ __device__ __forceinline__ void wino1d_at(const f32x4 (&acc)[8][4], int f, int r
   y[3] = q12 + 8.f * q34 + 0.125f * q56 + acc[7][f][r];
 }
 
-typedef __attribute__((address_space(3))) u32x4v lu32x4;
+typedef __attribute__((address_space(3))) u32x4 lu32x4;
 
 // Gate epilogues, row walk.  The lane's 16 pixels are output e = lane >> 4 of the wave's 16 tiles, 8 per half, its 4 columns the
 // same in each.  Byte offsets of one half's 8 row pieces from one table: tP = the table at (e, the half's first tile), `col` the byte
 // offset of the 4 columns in a row.  A pixel that does not exist has OOB in the table and stays out of range; a lane without work
 // reads the table that holds nothing else.
 __device__ __forceinline__ void wino1d_epi_offsets(const lunsigned* tP, unsigned col, unsigned (&o)[8]) {
-  const u32x4v t0 = *(const lu32x4*)tP, t1 = *(const lu32x4*)(tP + 4);
+  const u32x4 t0 = *(const lu32x4*)tP, t1 = *(const lu32x4*)(tP + 4);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     o[j] = t0[j] + col;
@@ -612,7 +606,7 @@ __device__ __forceinline__ f32x4 wino1d_gate(f32x4 y, f32x4 bias4, f32x4 r, f32x
 }
 
 __device__ __forceinline__ void wino1d_epi_put(f32x4 o, __amdgpu_buffer_rsrc_t rs, unsigned off) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, o), rs, off, 0, 0);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs, off, 0, 0);
 }
 
 template <bool VERT, int EPI>
@@ -627,9 +621,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
   const int t0 = (blockIdx.x / a.ncb) * WT;
   const int pstride = VERT ? a.W : 1;
 
-  const __amdgpu_buffer_rsrc_t rs0 = rsrc_n(a.src0, a.bytes0);
-  const __amdgpu_buffer_rsrc_t rs1 = rsrc_n(a.src1, a.bytes1);
-  const __amdgpu_buffer_rsrc_t rw = rsrc_n(a.weight, a.w_bytes);
+  const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(a.src0, a.bytes0);
+  const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(a.src1, a.bytes1);
+  const __amdgpu_buffer_rsrc_t rw = buffer_rsrc(a.weight, a.w_bytes);
 
   // ---- staging role: tile lt, channel cc of the K-step
   const int lt = tid >> 3, cc = tid & 7;
@@ -708,7 +702,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
   }
 
   // ---- epilogue: lane holds tiles 4*kq + r (r = 0..3) of column rl of each fragment, in every component
-  typedef __attribute__((address_space(1))) float gfloat;
   if constexpr (EPI == PFK_EPI_LINEAR) {
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
@@ -769,18 +762,18 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
     const int ch = a.ch;
     const bool upper = EPI == PFK_EPI_GRU_ZR && n0 >= ch;   // GRU_ZR: the r half
     const unsigned cn = (unsigned)n0 * 4u, chc = (unsigned)(upper ? n0 - ch : n0) * 4u;
-    const __amdgpu_buffer_rsrc_t rbias = rsrc_n(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
+    const __amdgpu_buffer_rsrc_t rbias = buffer_rsrc(a.bias, a.bias != nullptr ? (unsigned)a.cout * 4u : 0u);   // (no bias, pad columns: zero)
     f32x4 bias4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) bias4[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, cn + 4u * j, 0, 0));
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the tables are written
 
-    const __amdgpu_buffer_rsrc_t rres = rsrc_n(a.res, a.res != nullptr ? a.res_bytes : 0u);   // (no context term: zero)
-    const __amdgpu_buffer_rsrc_t rh = rsrc_n(a.h, a.h_bytes);
+    const __amdgpu_buffer_rsrc_t rres = buffer_rsrc(a.res, a.res != nullptr ? a.res_bytes : 0u);   // (no context term: zero)
+    const __amdgpu_buffer_rsrc_t rh = buffer_rsrc(a.h, a.h_bytes);
     // (wave-uniform) GRU_ZR: the wave's 64 columns lie in the z half, in the r half, or — hidden widths that are no multiple of 64 — in both
     const bool wupper = EPI == PFK_EPI_GRU_ZR && w0 >= ch, wh = EPI == PFK_EPI_GRU_ZR && w0 + 64 > ch, wmixed = wh && !wupper;
-    const __amdgpu_buffer_rsrc_t rz = rsrc_n(wupper ? a.aux_rh : a.aux_z, a.z_bytes);   // GRU_ZR: stored; GRU_Q: read
-    const __amdgpu_buffer_rsrc_t rrh = rsrc_n(a.aux_rh, a.z_bytes);                     // GRU_ZR, both halves in the wave: the r half's store
+    const __amdgpu_buffer_rsrc_t rz = buffer_rsrc(wupper ? a.aux_rh : a.aux_z, a.z_bytes);   // GRU_ZR: stored; GRU_Q: read
+    const __amdgpu_buffer_rsrc_t rrh = buffer_rsrc(a.aux_rh, a.z_bytes);                     // GRU_ZR, both halves in the wave: the r half's store
     const lunsigned* const tN = sT + 3 * TBL1 + prow * WT + wt * 16;   // the lane's place in the table without work
     const lunsigned* const tR = nok ? tN - 3 * TBL1 : tN;
     const lunsigned* const tH = (nok && (EPI == PFK_EPI_GRU_Q || upper)) ? tN - 2 * TBL1 : tN;
