@@ -121,8 +121,8 @@ def _run(cmd) -> None:
 
 def build_libpfk(force: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h", CSRC / "pfk_upsample.h",
-               CSRC / "pfk_wgrad_reduce.h"]
+    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_launch.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h",
+               CSRC / "pfk_upsample.h", CSRC / "pfk_wgrad_reduce.h"]
     tree = source_hash()
     objs, jobs = [], []
     for src, extra in HIP_SOURCES:

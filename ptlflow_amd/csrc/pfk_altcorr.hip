@@ -12,7 +12,7 @@
 // in float4 (one coalesced 256-byte segment of the NHWC fmap2 row per load), a 4-step butterfly finishes the dot
 // product.  fmap1's row lives in registers.  The (2r+2)^2 tap values go through LDS, then the lanes write the
 // (2r+1)^2 interpolated cells.  HBM/L2-bound gather: (2r+2)^2 * C * 4 bytes read per pixel.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -576,7 +576,7 @@ int altcorr_forward_launch(const T* fmap1, const T* fmap2, const float* coords, 
   if (C > 64 * MAX_C4) return PFK_ERR_UNSUPPORTED;
   const long long M = (long long)B * H1 * W1;
   const long long blocks = (M + 3) / 4;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // Window-sharing MFMA kernel on 8 x 4 patches once the patch grid fills the chip (a block lives ~30 us), the per-pixel kernel below that and for maps whose byte offsets do not fit the 32-bit buffer addressing of the staging
   // loads.  MI355X, C = 256, r = 4 (scripts/lookup_bench.py, gpurun_out/r3_altcorr.log): 55x128 batch 8 with a smooth flow field
@@ -586,13 +586,13 @@ int altcorr_forward_launch(const T* fmap1, const T* fmap2, const float* coords, 
   // kernel's row-major block order, 333; the rest is the border patches' GEMMs in front of it).  8 x 8 patches never beat 8 x 4.
   const int tx = (W1 + 7) / 8;
   const long long t8 = (long long)B * ((H1 + 7) / 8) * tx, t4 = (long long)B * ((H1 + 3) / 4) * tx;
-  const bool fits32 = (long long)B * H1 * W1 * C * (long long)sizeof(T) < 0x7fffffffLL && (long long)B * H2 * W2 * C * (long long)sizeof(T) < 0x7fffffffLL;
+  const bool fits32 = pfk_fits32((long long)B * H1 * W1 * C * (long long)sizeof(T)) && pfk_fits32((long long)B * H2 * W2 * C * (long long)sizeof(T));
   const int mode = g_altcorr_mode;
   if (fits32 && mode != 1 && (mode >= 2 || t4 >= 256)) {
     const bool big = mode == 3;
     const int gxn = (W1 + 3) / 4;
     const long long ogrid = (long long)B * H1 * gxn;
-    if (ogrid > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits_int(ogrid)) return PFK_ERR_UNSUPPORTED;
     // launch-wide gate (8 x 4 patches, when the caller lent a workspace): per-block counts of the patches that take the GEMM
     int* counts = (!big && mode == 0) ? static_cast<int*>(workspace) : nullptr;
     const int nplan = (int)((t4 + PLAN_PATCHES - 1) / PLAN_PATCHES);
@@ -601,16 +601,14 @@ int altcorr_forward_launch(const T* fmap1, const T* fmap2, const float* coords, 
                          (H1 + 3) / 4);
     if (big) {
       constexpr size_t smem = 2 * (64 + WS_NP_MAX) * WS_ROWB;
-      static pfk_device_once once;
-      once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(altcorr_fwd_ws_kernel<8, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+      pfk_raise_lds_limit<altcorr_fwd_ws_kernel<8, T>, smem>();
       hipLaunchKernelGGL((altcorr_fwd_ws_kernel<8, T>), dim3((unsigned)t8), dim3(256), smem, st, fmap1, fmap2, coords, out, B, H1, W1, H2, W2, C,
                          radius, tx, (H1 + 7) / 8, (const int*)nullptr, 0);
       hipLaunchKernelGGL((altcorr_fwd_overflow_kernel<8, T>), dim3((unsigned)ogrid), dim3(256), 0, st, fmap1, fmap2, coords, out, H1, W1, H2, W2,
                          C, radius, gxn, 0, (const int*)nullptr, 0, t8);
     } else {
       constexpr size_t smem = 2 * (32 + WS_NP_MAX) * WS_ROWB;
-      static pfk_device_once once;
-      once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(altcorr_fwd_ws_kernel<4, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+      pfk_raise_lds_limit<altcorr_fwd_ws_kernel<4, T>, smem>();
       if (mode != 4)
         hipLaunchKernelGGL((altcorr_fwd_ws_kernel<4, T>), dim3((unsigned)t4), dim3(256), smem, st, fmap1, fmap2, coords, out, B, H1, W1, H2, W2,
                            C, radius, tx, (H1 + 3) / 4, (const int*)counts, nplan);
@@ -639,7 +637,7 @@ int pfk_altcorr_backward_f32(const float* fmap1, const float* fmap2, const float
   if (C > 64 * MAX_C4) return PFK_ERR_UNSUPPORTED;
   const long long M = (long long)B * H1 * W1;
   const long long blocks = (M + 3) / 4;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(fmap2_grad, 0, (size_t)B * H2 * W2 * C * sizeof(float), st) != hipSuccess) return PFK_ERR_LAUNCH;
   hipLaunchKernelGGL(altcorr_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, fmap1, fmap2, coords, corr_grad,

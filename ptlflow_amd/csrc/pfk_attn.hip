@@ -3,7 +3,7 @@
 //  * pfk_transpose_pack_{f32,b16}:    the attention map's transposed copy (the A operand of dV = P^T dAgg) and, in the same pass,
 //                                     its untransposed packed copy, fp32 bits or bf16 (round to nearest even), pad columns zero.
 // Both are bandwidth bound and run once per training step.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -114,8 +114,8 @@ __global__ __launch_bounds__(256) void transpose_pack_kernel(const float* __rest
 
 int softmax_rows_bwd_launch(bool bf16, const float* p, long long ld_p, const void* dp, long long ld_dp, float* ds, long long ld_out,
                             long long rows, int cols, pfk_stream_t stream) {
-  if (!p || !dp || !ds || rows <= 0 || cols <= 0 || rows > 0x7fffffffLL) return PFK_ERR_BAD_ARG;
-  if (ld_p < cols || ld_dp < cols || ld_out < cols || ld_out > 0x7fffffffLL) return PFK_ERR_BAD_ARG;
+  if (!p || !dp || !ds || rows <= 0 || cols <= 0 || !pfk_fits_int(rows)) return PFK_ERR_BAD_ARG;
+  if (ld_p < cols || ld_dp < cols || ld_out < cols || !pfk_fits_int(ld_out)) return PFK_ERR_BAD_ARG;
   if (static_cast<const void*>(ds) == dp && (bf16 || ld_out != ld_dp)) return PFK_ERR_BAD_ARG;      // in place: fp32, same rows
   if (bf16 && (!pfk_aligned16(dp) || (ld_dp & 7))) return PFK_ERR_ALIGNMENT;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -128,7 +128,7 @@ int softmax_rows_bwd_launch(bool bf16, const float* p, long long ld_p, const voi
 
 int transpose_pack_launch(bool bf16, const float* in, long long ld_in, void* outT, void* out, long long ld_out, int B, int N,
                           pfk_stream_t stream) {
-  if (!in || !outT || B <= 0 || N <= 0 || ld_in < N || ld_out < N || ld_out > 0x7fffffffLL) return PFK_ERR_BAD_ARG;
+  if (!in || !outT || B <= 0 || N <= 0 || ld_in < N || ld_out < N || !pfk_fits_int(ld_out)) return PFK_ERR_BAD_ARG;
   if (in == outT || in == out || outT == out) return PFK_ERR_BAD_ARG;
   if (bf16 && (!pfk_aligned16(outT) || (out && !pfk_aligned16(out)) || (ld_out & 7))) return PFK_ERR_ALIGNMENT;
   const long long tiles = (ld_out + TP - 1) / TP;

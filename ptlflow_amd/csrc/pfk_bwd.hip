@@ -11,7 +11,7 @@
 //                       dF2_l     = s * dC_l^T . F1            -> pfk_conv_wgrad_f32 (the transposed product, reduction over rows)
 //                     and the (tiny) chain F2 -> F2_l is left to the caller; no pass over the N x N buffers besides the two GEMMs.
 // (The convex upsampling's backward is in pfk_upsample.hip.)
-#include "pfk_common.h"
+#include "pfk_launch.h"
 #include "pfk_lookup.h"
 
 namespace {
@@ -175,7 +175,7 @@ int pfk_corr_lookup_bwd_f32(const pfk_lookup_bwd_desc* d, pfk_stream_t stream) {
   }
   a.L = d->num_levels; a.r = d->radius; a.B = d->B; a.h = d->h; a.w = d->w;
   a.coords = d->coords; a.gout = d->grad_out; a.gout_ld = d->grad_out_ld;
-  if ((long long)d->B * d->h * d->w >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32((long long)d->B * d->h * d->w)) return PFK_ERR_UNSUPPORTED;
   const long long blocks = ((long long)d->B * d->h * d->w + BPIX - 1) / BPIX;
   const dim3 grid((unsigned)blocks), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -109,33 +109,11 @@ __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf
 // nn.GELU() (approximate='none'): 0.5 * v * (1 + erf(v / sqrt(2)))
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
-static inline bool pfk_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// hipFuncSetAttribute is per DEVICE: a process that drives several GPUs (model.to("cuda:1"), DataParallel) must raise the
-// dynamic-LDS limit of a kernel on each of them.  One flag per (kernel instantiation, device), lock-free after the first call.
-#include <atomic>
-constexpr int PFK_MAX_DEVICES = 64;
-struct pfk_device_once {
-  std::atomic<unsigned char> done[PFK_MAX_DEVICES] = {};
-  template <class F>
-  void run(F&& f) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PFK_MAX_DEVICES) { f(); return; }
-    if (done[dev].load(std::memory_order_acquire)) return;
-    f();   // idempotent: two threads racing here both set the same attribute value
-    done[dev].store(1, std::memory_order_release);
-  }
-};
-
 // pfk_debug_set_* are inert unless the process opted in (include/pfk.h)
 #include <stdlib.h>
 static inline bool pfk_debug_knobs_enabled() {
   const char* e = getenv("PFK_DEBUG_KNOBS");
   return e && e[0] == '1' && e[1] == 0;
-}
-
-static inline int pfk_launch_status() {
-  return hipGetLastError() == hipSuccess ? PFK_OK : PFK_ERR_LAUNCH;
 }
 
 // Division of n < 2^31 by a launch-invariant d through a host-made multiplier (Granlund & Montgomery 1994, N = 32):

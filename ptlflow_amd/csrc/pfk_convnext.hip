@@ -9,7 +9,7 @@
 //   * after the last chunk each wave normalises eight pixels: mean and biased variance of the pixel's C values (two passes over
 //     the LDS row, wave reductions), then (x - mean) * rstd * weight + bias straight to `out`.
 // Nothing but the final rows goes back to memory: one read, one write per element.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -131,16 +131,10 @@ int launch_dwconv_ln(const float* in, int in_ld, const float* dw_w, const float*
                      float* out, int out_ld, int B, int H, int W, int C, hipStream_t st, float* xhat = nullptr, int xhat_ld = 0,
                      float* rstd = nullptr) {
   const size_t smem = (size_t)DW_PIX * (C + 4) * sizeof(float);
-  auto kern = dwconv_ln_kernel<K, TRAIN>;
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((size_t)DW_PIX * (DW_MAX_C + 4) * sizeof(float)));
-  });
+  constexpr size_t limit = (size_t)DW_PIX * (DW_MAX_C + 4) * sizeof(float);      // raised once for every C, launched with this C's bytes
   dim3 grid((unsigned)((W + DW_TX - 1) / DW_TX), (unsigned)((H + DW_TY - 1) / DW_TY), (unsigned)B);
-  hipLaunchKernelGGL(kern, grid, dim3(DW_THREADS), smem, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld, H, W, C, xhat, xhat_ld,
-                     rstd);
-  return pfk_launch_status();
+  return pfk_launch_lds<dwconv_ln_kernel<K, TRAIN>, limit>(grid, dim3(DW_THREADS), smem, st, in, in_ld, dw_w, dw_b, ln_w, ln_b, eps, out, out_ld,
+                                                           H, W, C, xhat, xhat_ld, rstd);
 }
 
 // ---- the bf16 twin (pfk_dwconv_layernorm_b16): bf16 rows in and out, fp32 arithmetic -------------------------------------------
@@ -302,7 +296,7 @@ int pfk_dwconv_layernorm_f32(const float* in, int in_ld, const float* dw_weight,
   if (k > 7 || C > DW_MAX_C || B > 65535 || (H + DW_TY - 1) / DW_TY > 65535) return PFK_ERR_UNSUPPORTED;
   if ((C & 3) || (in_ld & 3) || !pfk_aligned16(in)) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   // `out` must not overlap the input rows (other blocks still read the halo of pixels this block has written)
   const char* ib = reinterpret_cast<const char*>(in);
   const char* ie = reinterpret_cast<const char*>(in + (M - 1) * in_ld + C);
@@ -328,7 +322,7 @@ int pfk_dwconv_layernorm_train_f32(const float* in, int in_ld, const float* dw_w
   if (B > 65535 || (H + DW_TY - 1) / DW_TY > 65535) return PFK_ERR_UNSUPPORTED;
   if ((C & 3) || (in_ld & 3) || !pfk_aligned16(in)) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   // neither output may overlap the input rows (other blocks still read the halo of pixels this block has written)
   const char* ib = reinterpret_cast<const char*>(in);
   const char* ie = reinterpret_cast<const char*>(in + (M - 1) * in_ld + C);
@@ -355,7 +349,7 @@ int pfk_dwconv_layernorm_b16(const void* in_bf16, int in_ld, const float* dw_wei
   if (C > DW_MAX_C || B > 65535 || (H + BT_TY - 1) / BT_TY > 65535) return PFK_ERR_UNSUPPORTED;
   if ((C & 7) || (in_ld & 7) || (out_ld & 7) || !pfk_aligned16(in_bf16) || !pfk_aligned16(out_bf16)) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   const __bf16* in = static_cast<const __bf16*>(in_bf16);
   __bf16* out = static_cast<__bf16*>(out_bf16);
   // `out` must not overlap the input rows (other blocks still read the halo of pixels this block has written)
@@ -382,10 +376,10 @@ int pfk_dwconv_layernorm_train_b16(const void* in_bf16, int in_ld, const float* 
   if (k < 1 || !(k & 1) || k > 7 || C > DW_MAX_C) return PFK_ERR_BAD_ARG;
   if (B > 65535 || (H + BT_TY - 1) / BT_TY > 65535) return PFK_ERR_UNSUPPORTED;
   if ((C & 7) || (in_ld & 7) || (out_ld & 7) || (xhat_ld & 7) || !pfk_aligned16(in_bf16) || !pfk_aligned16(out_bf16) ||
-      !pfk_aligned16(xhat_bf16) || (reinterpret_cast<uintptr_t>(rstd) & 3u))
+      !pfk_aligned16(xhat_bf16) || !pfk_aligned<4>(rstd))
     return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   const __bf16* in = static_cast<const __bf16*>(in_bf16);
   __bf16* out = static_cast<__bf16*>(out_bf16);
   __bf16* xhat = static_cast<__bf16*>(xhat_bf16);

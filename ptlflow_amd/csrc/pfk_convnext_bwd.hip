@@ -15,7 +15,7 @@
 // LDS tiles, sums, partials, the parameter gradients — is the fp32 code.  What differs is how many channels a lane moves at once:
 // 16 bytes of a bf16 row (eight channels) in the LayerNorm and GELU kernels, 8 bytes (the (pixel, four channels) item) in the
 // depthwise one.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -334,7 +334,7 @@ int layernorm_bwd_entry(const T* xhat, int xhat_ld, const float* rstd, const flo
   if (!xhat || !rstd || !ln_weight || !dy || !du || !dgamma || !dbeta || !workspace || M <= 0 || C < Q || C > CB_MAX_C || (C & (Q - 1)) ||
       xhat_ld < C || dy_ld < C || du_ld < C)
     return PFK_ERR_BAD_ARG;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   if (workspace_bytes < pfk_layernorm_bwd_workspace_bytes(M, C)) return PFK_ERR_BAD_ARG;
   if (!rows_ok(xhat, xhat_ld) || !rows_ok(dy, dy_ld) || !rows_ok(du, du_ld) || !pfk_aligned16(workspace)) return PFK_ERR_ALIGNMENT;
   if (overlap(du, du_ld, dy, dy_ld, M, C) || overlap(du, du_ld, xhat, xhat_ld, M, C)) return PFK_ERR_BAD_ARG;      // out of place only
@@ -357,7 +357,7 @@ int dwconv_bwd_entry(const T* in, int in_ld, const T* du, int du_ld, const float
     return PFK_ERR_BAD_ARG;
   if (k < 1 || !(k & 1) || k > 7) return PFK_ERR_BAD_ARG;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;
   if (workspace_bytes < pfk_dwconv_bwd_workspace_bytes(B, H, W, C, k)) return PFK_ERR_BAD_ARG;
   if (!rows_ok(in, in_ld) || !rows_ok(du, du_ld) || !rows_ok(dx, dx_ld) || !pfk_aligned16(workspace)) return PFK_ERR_ALIGNMENT;
   // dx must not overlap du or in: other blocks still read the halo of pixels this block has written
@@ -377,7 +377,7 @@ int gelu_entry(bool bwd, const T* x, long long x_ld, const T* dy, long long dy_l
                pfk_stream_t stream) {
   constexpr int Q = QUANTUM<T>;
   if (!x || !out || (bwd && !dy) || M <= 0 || C < Q || (C & (Q - 1)) || x_ld < C || out_ld < C || (bwd && dy_ld < C)) return PFK_ERR_BAD_ARG;
-  if (M * (C / Q) >= 0x7fffffffLL * 256) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M * (C / Q) / 256)) return PFK_ERR_UNSUPPORTED;
   if (!rows_ok(x, x_ld) || !rows_ok(out, out_ld) || (bwd && !rows_ok(dy, dy_ld))) return PFK_ERR_ALIGNMENT;
   if (overlap(out, out_ld, x, x_ld, M, C) || (bwd && overlap(out, out_ld, dy, dy_ld, M, C))) return PFK_ERR_BAD_ARG;   // out of place only
   hipStream_t st = static_cast<hipStream_t>(stream);

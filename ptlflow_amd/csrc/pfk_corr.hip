@@ -6,7 +6,7 @@
 // sample position — the tap index — differs from the reference for ~7 % of integer coordinates
 // (SURVEY.md finding 3).  The only fused operations are the three explicit fmaf() of the
 // bilinear accumulation, which reproduce torch's CPU grid_sample bit for bit.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 #include "pfk_lookup.h"
 
 namespace {
@@ -361,14 +361,14 @@ int lookup_launch(const pfk_lookup_desc* d, pfk_stream_t stream) {
   a.L = d->num_levels; a.r = d->radius; a.B = d->B; a.h = d->h; a.w = d->w;
   a.coords = d->coords; a.out = d->out; a.out_ld = d->out_ld; a.out_bf16 = d->out_bf16;
   const long long M = (long long)d->B * d->h * d->w;
-  if (M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // the kernel's pixel arithmetic is 32-bit
+  if (!pfk_fits32(M)) return PFK_ERR_UNSUPPORTED;   // the kernel's pixel arithmetic is 32-bit
   hipStream_t st = static_cast<hipStream_t>(stream);
   if constexpr (BLK) {
     for (int l = 0; l < d->num_levels; ++l)     // 32-bit element offsets inside one source pixel's map
-      if ((long long)blocked_tiles_h(d->lvl_h[l]) * blocked_tiles_w(d->lvl_w[l]) * 32 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+      if (!pfk_fits32((long long)blocked_tiles_h(d->lvl_h[l]) * blocked_tiles_w(d->lvl_w[l]) * 32)) return PFK_ERR_UNSUPPORTED;
     if constexpr (sizeof(T) == 2)               // bf16 maps are read as aligned 32-bit pairs
       for (int l = 0; l < d->num_levels; ++l)
-        if (reinterpret_cast<uintptr_t>(d->levels[l]) & 3u) return PFK_ERR_ALIGNMENT;
+        if (!pfk_aligned<4>(d->levels[l])) return PFK_ERR_ALIGNMENT;
     // 8 pixels per workgroup from 28 160 source pixels up (a pyramid far beyond the 256 MB Infinity Cache: more windows in
     // flight per wave pay; 55x128 batch 8, iid field 60.7 -> 55.9 us, smooth 55.2 -> 54.7), 4 below (batch 1: 10.1 vs 12.2 us;
     // gpurun_out/r5c_lookup.log).  g_lookup_pix: 4 = this rule, 8 = always 8, 104 = always 4 (tuning knob).
@@ -437,7 +437,7 @@ int pfk_fmap_to_blocked_f32(const float* in, int in_ld, float* out, int out_ld, 
   if ((C & 3) || (in_ld & 3) || (out_ld & 3) || !pfk_aligned16(in) || !pfk_aligned16(out)) return PFK_ERR_ALIGNMENT;
   const int TH = blocked_tiles_h(H), TW = blocked_tiles_w(W);
   const long long total4 = (long long)B * TH * TW * 32 * (C / 4);
-  if ((total4 + 255) / 256 > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int((total4 + 255) / 256)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(fmap_to_blocked_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                      in_ld, out, out_ld, total4, C / 4, H, W, TH, TW);
   return pfk_launch_status();
@@ -457,7 +457,7 @@ int pfk_fmap_pool2x2_f32(const float* in, int in_ld, float* out, int out_ld, int
   const int Ho = H / 2, Wo = W / 2;
   const long long total4 = (long long)B * Ho * Wo * (C / 4);
   if (total4 == 0) return PFK_OK;
-  if ((total4 + 255) / 256 > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int((total4 + 255) / 256)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(fmap_pool2x2_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), in,
                      in_ld, out, out_ld, total4, C / 4, H, W, Ho, Wo);
   return pfk_launch_status();

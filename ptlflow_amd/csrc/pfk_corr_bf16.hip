@@ -156,7 +156,7 @@ int pfk_corr_volume_bf16(const void* f1_bf16, int ld1, const void* f2_bf16, int 
   if (ld1 < D || ld2 < D) return PFK_ERR_BAD_ARG;
   if (!pfk_aligned16(f1_bf16) || !pfk_aligned16(f2_bf16) || !pfk_aligned16(out_bf16) || (ld1 & 7) || (ld2 & 7) || (D & 7))
     return PFK_ERR_ALIGNMENT;
-  if ((long long)N1 * ld1 * 2 >= 0x7fffffffLL || (long long)N2 * ld2 * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32((long long)N1 * ld1 * 2) || !pfk_fits32((long long)N2 * ld2 * 2)) return PFK_ERR_UNSUPPORTED;
   CorrBfArgs g{};
   g.a = static_cast<const __bf16*>(f1_bf16); g.b = static_cast<const __bf16*>(f2_bf16); g.out = static_cast<__bf16*>(out_bf16);
   g.N1 = N1; g.N2 = N2; g.D = D; g.lda = ld1; g.ldb = ld2; g.scale = scale;
@@ -164,7 +164,7 @@ int pfk_corr_volume_bf16(const void* f1_bf16, int ld1, const void* f2_bf16, int 
   g.tiles_m = (N1 + TM - 1) / TM; g.tiles_n = (N2 + TN - 1) / TN;
   g.supertile = (g.tiles_m >= 32 && g.tiles_n >= 32) ? 16 : 0;
   const long long nblk = (long long)g.tiles_m * g.tiles_n;
-  if (nblk > 0x7fffffffLL || B > 65535) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(nblk) || B > 65535) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(corr_bf16_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), g);
   return pfk_launch_status();
 }

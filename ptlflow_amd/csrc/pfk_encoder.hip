@@ -7,7 +7,7 @@
 //   * normalise + relu (+ residual add + relu) elementwise pass.
 // The 3x3 / 1x1 convolutions of the residual blocks (stride 1 and 2) run on pfk_conv2d_f32 / pfk_conv2d_bf16s;
 // batch-norm in eval mode is folded into their weights by the host (ptlflow_amd/encoder.py).
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -219,8 +219,8 @@ int stem_launch(const float* img, const float* weight, const float* bias, TO* ou
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int tiles_x = (Wo + SM_COLS - 1) / SM_COLS, tiles_y = (Ho + SM_ROWS - 1) / SM_ROWS;
   const long long tiles = (long long)B * tiles_x * tiles_y;
-  if (tiles > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  if ((long long)3 * H * W >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;     // 32-bit offsets inside one image
+  if (!pfk_fits_int(tiles)) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32((long long)3 * H * W)) return PFK_ERR_UNSUPPORTED;     // 32-bit offsets inside one image
   const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);               // two workgroups per CU, persistent over the tile list
   if (cout == 64)
     hipLaunchKernelGGL((conv_stem_mfma_kernel<2, TO>), dim3(grid), dim3(256), 0, st, img, weight, bias, out, out_ld, H, W, Ho, Wo,
@@ -655,19 +655,11 @@ int stem2_launch_g(const float* img_a, long long sa, const float* img_b, long lo
   const int wgs = (tiles + G - 1) / G;
   const unsigned grid = (unsigned)(wgs < 256 ? wgs : 256);                   // one workgroup per CU, persistent over the tile list
   constexpr size_t smem = stem2_smem_bytes(G);
-  static pfk_device_once once[2];
-  if (img_b) {
-    auto kern = conv_stem2_mfma_kernel<G, 2, TO>;
-    once[1].run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out, out_ld, H, W, Ho, Wo, tiles_x,
-                       tiles_y, tiles, relu);
-    return pfk_launch_status();
-  }
-  auto kern = conv_stem2_mfma_kernel<G, 1, TO>;
-  once[0].run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out, out_ld, H, W, Ho, Wo, tiles_x,
-                     tiles_y, tiles, relu);
-  return pfk_launch_status();
+  if (img_b)
+    return pfk_launch_lds<conv_stem2_mfma_kernel<G, 2, TO>, smem>(dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out,
+                                                                  out_ld, H, W, Ho, Wo, tiles_x, tiles_y, tiles, relu);
+  return pfk_launch_lds<conv_stem2_mfma_kernel<G, 1, TO>, smem>(dim3(grid), dim3(256 * G), smem, st, img_a, img_b, sa, sb, weight, bias, out,
+                                                                out_ld, H, W, Ho, Wo, tiles_x, tiles_y, tiles, relu);
 }
 
 template <typename TO>
@@ -675,7 +667,7 @@ int stem2_launch(const float* img_a, long long sa, const float* img_b, long long
                  int out_ld, int B, int H, int W, int cin, int cout, int relu, hipStream_t st) {
   if (!img_a || !weight || !out || B <= 0 || H <= 0 || W <= 0 || cout <= 0 || out_ld < cout) return PFK_ERR_BAD_ARG;
   if (cin != (img_b ? 6 : 3)) return PFK_ERR_BAD_ARG;
-  if ((long long)3 * H * W >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;     // 32-bit offsets inside one image
+  if (!pfk_fits32((long long)3 * H * W)) return PFK_ERR_UNSUPPORTED;     // 32-bit offsets inside one image
   if (sa < (long long)3 * H * W || (img_b && sb < (long long)3 * H * W)) return PFK_ERR_BAD_ARG;
   if (cout != 64) return PFK_ERR_UNSUPPORTED;
   if (!pfk_aligned16(weight)) return PFK_ERR_ALIGNMENT;
@@ -785,7 +777,7 @@ int pfk_conv_stem_f32(const float* img, const float* weight, const float* bias, 
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int tpr = (Wo + STEM_TP - 1) / STEM_TP;
   const long long tiles = (long long)B * Ho * tpr;
-  if (tiles > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(tiles)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)tiles), dim3(256), 0, static_cast<hipStream_t>(stream), img, weight,
                      bias, out, out_ld, H, W, Ho, Wo, tpr, cout, relu);
   return pfk_launch_status();
@@ -794,7 +786,7 @@ int pfk_conv_stem_f32(const float* img, const float* weight, const float* bias, 
 int pfk_conv_stem_b16(const float* img, const float* weight, const float* bias, void* out_bf16, int out_ld, int B, int H, int W,
                       int cout, int relu, pfk_stream_t stream) {
   if (!img || !weight || !out_bf16 || B <= 0 || H <= 0 || W <= 0 || cout <= 0 || out_ld < cout) return PFK_ERR_BAD_ARG;
-  if (!pfk_aligned16(weight) || (reinterpret_cast<uintptr_t>(out_bf16) & 1u)) return PFK_ERR_ALIGNMENT;
+  if (!pfk_aligned16(weight) || !pfk_aligned<2>(out_bf16)) return PFK_ERR_ALIGNMENT;
   return stem_launch<__bf16>(img, weight, bias, static_cast<__bf16*>(out_bf16), out_ld, B, H, W, cout, relu, static_cast<hipStream_t>(stream));
 }
 
@@ -807,7 +799,7 @@ int pfk_conv_stem2_f32(const float* img_a, long long bstride_a, const float* img
 int pfk_conv_stem2_b16(const float* img_a, long long bstride_a, const float* img_b, long long bstride_b, const float* weight,
                        const float* bias, void* out_bf16, int out_ld, int B, int H, int W, int cin, int cout, int relu,
                        pfk_stream_t stream) {
-  if (reinterpret_cast<uintptr_t>(out_bf16) & 1u) return PFK_ERR_ALIGNMENT;
+  if (!pfk_aligned<2>(out_bf16)) return PFK_ERR_ALIGNMENT;
   return stem2_launch<__bf16>(img_a, bstride_a, img_b, bstride_b, weight, bias, static_cast<__bf16*>(out_bf16), out_ld, B, H, W, cin,
                               cout, relu, static_cast<hipStream_t>(stream));
 }
@@ -826,8 +818,8 @@ template <typename TX>
 static int instnorm_stats_launch(const TX* x, int ld, int B, int HW, int C, float eps, float* mean, float* rstd,
                                  void* workspace, long long workspace_bytes, pfk_stream_t stream) {
   if (!x || !mean || !rstd || !workspace || B <= 0 || HW <= 0 || C <= 0 || ld < C) return PFK_ERR_BAD_ARG;
-  if ((C & 3) || (ld & 3) || C > 1024 || (reinterpret_cast<uintptr_t>(x) & (sizeof(TX) * 4 - 1)) || !pfk_aligned16(mean) || !pfk_aligned16(rstd) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 31u))
+  if ((C & 3) || (ld & 3) || C > 1024 || !pfk_aligned(x, sizeof(TX) * 4) || !pfk_aligned16(mean) || !pfk_aligned16(rstd) ||
+      !pfk_aligned<32>(workspace))
     return PFK_ERR_ALIGNMENT;
   if (workspace_bytes < pfk_instnorm_workspace_bytes(B, C)) return PFK_ERR_BAD_ARG;
   const int nch = in_chunks(B);
@@ -869,7 +861,7 @@ int pfk_norm_bwd_f32(const float* x, int x_ld, const float* dy, int dy_ld, const
   if (!x || !dy || !mean || !rstd || !dx || !workspace || B <= 0 || HW <= 0 || C <= 0) return PFK_ERR_BAD_ARG;
   if (x_ld < C || dy_ld < C || dx_ld < C) return PFK_ERR_BAD_ARG;
   if ((C & 3) || (x_ld & 3) || (dy_ld & 3) || (dx_ld & 3) || C > 1024 || !pfk_aligned16(x) || !pfk_aligned16(dy) ||
-      !pfk_aligned16(dx) || !pfk_aligned16(mean) || !pfk_aligned16(rstd) || (reinterpret_cast<uintptr_t>(workspace) & 31u))
+      !pfk_aligned16(dx) || !pfk_aligned16(mean) || !pfk_aligned16(rstd) || !pfk_aligned<32>(workspace))
     return PFK_ERR_ALIGNMENT;
   if (workspace_bytes < pfk_norm_bwd_workspace_bytes(B, C)) return PFK_ERR_BAD_ARG;
   double* p1 = static_cast<double*>(workspace);
@@ -888,7 +880,7 @@ int pfk_norm_bwd_f32(const float* x, int x_ld, const float* dy, int dy_ld, const
     hipLaunchKernelGGL(norm_bwd_copy_kernel, dim3((total + 255) / 256), dim3(256), 0, st, d1, d2, sum_g, sum_gxhat, total);
   const long long M = (long long)B * HW;
   const long long blocks = (M * (C >> 2) + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(norm_bwd_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, x_ld, dy, dy_ld, mean, rstd, d1, d2, dx,
                      dx_ld, M, HW, C, relu);
   return pfk_launch_status();
@@ -925,7 +917,7 @@ int pfk_norm_apply_f32(const float* x, int x_ld, const float* mean, const float*
   const long long M = (long long)B * HW;
   const long long threads = M * (C >> 2);
   const long long blocks = (threads + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((norm_apply_kernel<float, float>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_ld,
                      mean, rstd, residual, residual_ld, out, out_ld, M, HW, C, relu, relu_after_residual);
   return pfk_launch_status();
@@ -942,7 +934,7 @@ int pfk_norm_apply_res_f32(const float* x, int x_ld, const float* mean, const fl
     return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * HW;
   const long long blocks = (M * (C >> 2) + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(norm_apply_res_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, x_ld, mean, rstd,
                      residual, residual_ld, res_mean, res_rstd, out, out_ld, M, HW, C, relu, res_relu, relu_after_residual);
   return pfk_launch_status();
@@ -952,14 +944,14 @@ int pfk_norm_apply_b16(const void* x, int x_bf16, int x_ld, const float* mean, c
                        int residual_ld, void* out_bf16, int out_ld, int B, int HW, int C, int relu,
                        int relu_after_residual, pfk_stream_t stream) {
   if (!x || !mean || !rstd || !out_bf16 || B <= 0 || HW <= 0 || C <= 0 || x_ld < C || out_ld < C) return PFK_ERR_BAD_ARG;
-  if ((C & 3) || (x_ld & 3) || (out_ld & 3) || (reinterpret_cast<uintptr_t>(x) & (x_bf16 ? 7u : 15u)) ||
-      (reinterpret_cast<uintptr_t>(out_bf16) & 7u) || !pfk_aligned16(mean) || !pfk_aligned16(rstd))
+  if ((C & 3) || (x_ld & 3) || (out_ld & 3) || !pfk_aligned(x, x_bf16 ? 8 : 16) ||
+      !pfk_aligned<8>(out_bf16) || !pfk_aligned16(mean) || !pfk_aligned16(rstd))
     return PFK_ERR_ALIGNMENT;
-  if (residual_bf16 && (residual_ld < C || (residual_ld & 3) || (reinterpret_cast<uintptr_t>(residual_bf16) & 7u))) return PFK_ERR_ALIGNMENT;
+  if (residual_bf16 && (residual_ld < C || (residual_ld & 3) || !pfk_aligned<8>(residual_bf16))) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * HW;
   const long long threads = M * (C >> 2);
   const long long blocks = (threads + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const __bf16* r16 = static_cast<const __bf16*>(residual_bf16);
   __bf16* o16 = static_cast<__bf16*>(out_bf16);

@@ -1,7 +1,7 @@
 // Pieces shared by the implicit-GEMM translation units (pfk_gemm.hip: fp32 MFMA; pfk_gemm_bf.hip: split-bf16 MFMA):
 // the kernel argument block, the buffer-descriptor helper and the fused epilogues.
 #pragma once
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace pfkg {
 
@@ -308,11 +308,10 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& a, const f32x16 (&a
 
 // alignment facts the float4 epilogue needs, evaluated where pointers are still integers
 static inline int gemm_vec_flags(const GemmArgs& a) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
   int f = 0;
-  if (a.out && al(a.out) && (((a.out_ld | a.out_coff) & 3) == 0) && ((a.o_bs & 3) == 0)) f |= 1;
-  if (!a.residual || (al(a.residual) && (a.residual_ld & 3) == 0)) f |= 2;
-  if (!a.bias || al(a.bias)) f |= 4;
+  if (a.out && pfk_aligned16(a.out) && (((a.out_ld | a.out_coff) & 3) == 0) && ((a.o_bs & 3) == 0)) f |= 1;
+  if (!a.residual || (pfk_aligned16(a.residual) && (a.residual_ld & 3) == 0)) f |= 2;
+  if (!a.bias || pfk_aligned16(a.bias)) f |= 4;
   return f;
 }
 

@@ -1060,35 +1060,24 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_pp_kernel(const GemmArgs a
 template <int EPI, int LD, int BPC, int ABL = 0>
 int launch_pp_one(const GemmArgs& g, unsigned G, hipStream_t st) {
   constexpr size_t smem = 3 * 128 * LD * sizeof(float);
-  auto kern = conv_gemm_pp_kernel<EPI, LD, BPC, ABL>;
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(kern, dim3(G), dim3(256), smem, st, g);
-  return pfk_launch_status();
+  return pfk_launch_lds<conv_gemm_pp_kernel<EPI, LD, BPC, ABL>, smem>(dim3(G), dim3(256), smem, st, g);
 }
 
 template <int LD, int BPC>
 int launch_pp_epi(const GemmArgs& g, int epi, unsigned G, hipStream_t st) {
-  switch (epi) {
-    case PFK_EPI_LINEAR: return launch_pp_one<PFK_EPI_LINEAR, LD, BPC>(g, G, st);
-    case PFK_EPI_GRU_ZR: return launch_pp_one<PFK_EPI_GRU_ZR, LD, BPC>(g, G, st);
-    case PFK_EPI_GRU_Q:  return launch_pp_one<PFK_EPI_GRU_Q, LD, BPC>(g, G, st);
-    default: return PFK_ERR_BAD_ARG;
-  }
+  return pfk_with_epilogue(epi, [&](auto e) { return launch_pp_one<decltype(e)::value, LD, BPC>(g, G, st); });
 }
 
 // variant bits: 1 = swizzled 48 KB LDS layout, 2 = per-XCD tile groups, 16 = whole tiles only; blocks per CU = 1 + ((variant >> 2) & 3)
 // (default: as many as the layout allows — 3 swizzled, 2 padded — when those bits are 0)
 int launch_pp(const GemmArgs& a, int epi, int batches, hipStream_t st, int variant, int abl = 0) {
   GemmArgs g = a;
-  if (a.M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(a.M)) return PFK_ERR_UNSUPPORTED;
   g.tiles_n = (a.b_rows + 63) / 64;
   g.pp_tiles_m = (int)((a.M + 63) / 64);
   const long long tiles_pb = (long long)g.pp_tiles_m * g.tiles_n;
   const long long tiles = tiles_pb * batches;
-  if (tiles <= 0 || tiles_pb > 0x7fffffffLL || tiles * a.sk_steps >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (tiles <= 0 || !pfk_fits_int(tiles_pb) || !pfk_fits32(tiles * a.sk_steps)) return PFK_ERR_UNSUPPORTED;
   g.pp_tiles_pb = (int)tiles_pb;
   g.pp_batches = batches;
   g.sk_tiles = tiles;
@@ -1105,7 +1094,7 @@ int launch_pp(const GemmArgs& a, int epi, int batches, hipStream_t st, int varia
   g.pp_whole = ((variant & 16) || a.sk_ws == nullptr || batches > 1 || a.sk_steps < 12) ? 1 : 0;
   if (g.pp_whole) { if (G > tiles) G = tiles; }
   else if (U / G < 6) G = U / 6 > 0 ? U / 6 : 1;   // keep segments long enough to amortise a fix-up
-  if (!g.pp_whole && U * (G + 1) >= 0x7fffffffLL) g.pp_whole = 1;   // the split's unit arithmetic is 32-bit
+  if (!g.pp_whole && !pfk_fits32(U * (G + 1))) g.pp_whole = 1;   // the split's unit arithmetic is 32-bit
   g.sk_groups = 1;
   if ((variant & 2) && tiles >= 64 && G >= 64) { g.sk_groups = 8; G -= G % 8; }
   if (abl) {   // timing ablations (results are garbage; scripts/conv_bench.py): linear epilogue, swizzled x3 or padded x2 only
@@ -1133,23 +1122,12 @@ int g_sk_variant = 6;     // padded layout, two blocks per CU, per-XCD groups: t
 template <int EPI, int LD, int BPC>
 int launch_sk_one(const GemmArgs& g, unsigned G, hipStream_t st) {
   constexpr size_t smem = 3 * 128 * LD * sizeof(float);
-  auto kern = conv_gemm_sk_kernel<EPI, LD, BPC>;
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(kern, dim3(G), dim3(256), smem, st, g);
-  return pfk_launch_status();
+  return pfk_launch_lds<conv_gemm_sk_kernel<EPI, LD, BPC>, smem>(dim3(G), dim3(256), smem, st, g);
 }
 
 template <int LD, int BPC>
 int launch_sk_epi(const GemmArgs& g, int epi, unsigned G, hipStream_t st) {
-  switch (epi) {
-    case PFK_EPI_LINEAR: return launch_sk_one<PFK_EPI_LINEAR, LD, BPC>(g, G, st);
-    case PFK_EPI_GRU_ZR: return launch_sk_one<PFK_EPI_GRU_ZR, LD, BPC>(g, G, st);
-    case PFK_EPI_GRU_Q:  return launch_sk_one<PFK_EPI_GRU_Q, LD, BPC>(g, G, st);
-    default: return PFK_ERR_BAD_ARG;
-  }
+  return pfk_with_epilogue(epi, [&](auto e) { return launch_sk_one<decltype(e)::value, LD, BPC>(g, G, st); });
 }
 
 int launch_sk(const GemmArgs& a, int epi, hipStream_t st, int variant) {
@@ -1162,7 +1140,7 @@ int launch_sk(const GemmArgs& a, int epi, hipStream_t st, int variant) {
   const long long U = g.sk_tiles * g.sk_steps;
   long long G = 256LL * bpc;
   if (U / G < 6) G = U / 6 > 0 ? U / 6 : 1; // keep segments long enough to amortise the pipeline prologue
-  if (U * (G + 1) >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // the kernel's unit arithmetic is 32-bit
+  if (!pfk_fits32(U * (G + 1))) return PFK_ERR_UNSUPPORTED;   // the kernel's unit arithmetic is 32-bit
   g.sk_groups = 1;
   if ((variant & 2) && g.sk_tiles >= 64 && G >= 64) { g.sk_groups = 8; G -= G % 8; }
   if (bpc == 2 && !swz) return launch_sk_epi<LDS_LD, 2>(g, epi, (unsigned)G, st);       // what the shipped library's heuristic selects
@@ -1182,18 +1160,13 @@ int launch_one(const GemmArgs& g, dim3 grid, hipStream_t st) {
   if constexpr (VARIANT == 0) {
     constexpr size_t smem = 2 * (BM + BN) * LDS_LD * sizeof(float);
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, EPI>), grid, dim3(256), smem, st, g);
+    return pfk_launch_status();
   } else {
     constexpr int G = VARIANT % 10, ABL = (VARIANT / 10) % 10, LD = VARIANT >= 100 ? LDS_LDX : LDS_LD;
     constexpr size_t smem = (size_t)G * 3 * (BM + BN) * LD * sizeof(float);
     static_assert(smem <= 160 * 1024, "LDS budget");
-    auto kern = conv_gemm_v3_kernel<BM, BN, WM, WN, EPI, G, ABL, LD>;
-    static pfk_device_once attr_once;   // one per template instantiation and device; safe with several host threads
-    attr_once.run([&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    });
-    hipLaunchKernelGGL(kern, grid, dim3(256 * G), smem, st, g);
+    return pfk_launch_lds<conv_gemm_v3_kernel<BM, BN, WM, WN, EPI, G, ABL, LD>, smem>(grid, dim3(256 * G), smem, st, g);
   }
-  return pfk_launch_status();
 }
 
 template <int BM, int BN, int WM, int WN, int VARIANT>
@@ -1202,16 +1175,11 @@ int launch_cfg(const GemmArgs& a, int epi, int batches, hipStream_t st) {
   const long long tiles_m = (a.M + BM - 1) / BM;
   g.tiles_n = (a.b_rows + BN - 1) / BN;
   const long long nblk = tiles_m * g.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (nblk <= 0 || !pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   dim3 grid((unsigned)nblk, (unsigned)batches);
   // both operand panels much larger than an XCD's L2: walk the grid in 16 x 16 supertiles (tile_of)
   g.supertile = (tiles_m >= 32 && g.tiles_n >= 32) ? 16 : 0;
-  switch (epi) {
-    case PFK_EPI_LINEAR: return launch_one<BM, BN, WM, WN, PFK_EPI_LINEAR, VARIANT>(g, grid, st);
-    case PFK_EPI_GRU_ZR: return launch_one<BM, BN, WM, WN, PFK_EPI_GRU_ZR, VARIANT>(g, grid, st);
-    case PFK_EPI_GRU_Q:  return launch_one<BM, BN, WM, WN, PFK_EPI_GRU_Q, VARIANT>(g, grid, st);
-    default: return PFK_ERR_BAD_ARG;
-  }
+  return pfk_with_epilogue(epi, [&](auto e) { return launch_one<BM, BN, WM, WN, decltype(e)::value, VARIANT>(g, grid, st); });
 }
 
 // the same for tiles only the LINEAR epilogue is instantiated on (the encoders' widths)
@@ -1222,7 +1190,7 @@ int launch_cfg_linear(const GemmArgs& a, int epi, int batches, hipStream_t st) {
   const long long tiles_m = (a.M + BM - 1) / BM;
   g.tiles_n = (a.b_rows + BN - 1) / BN;
   const long long nblk = tiles_m * g.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (nblk <= 0 || !pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   g.supertile = 0;
   return launch_one<BM, BN, WM, WN, PFK_EPI_LINEAR, VARIANT>(g, dim3((unsigned)nblk, (unsigned)batches), st);
 }
@@ -1236,7 +1204,7 @@ int g_small_swizzled = 0;   // tuning knob (pfk_debug_set_tile(301)): small grid
 int launch(const GemmArgs& a0, int epi, int batches, hipStream_t st) {
   GemmArgs a = a0;
   a.vec_flags = gemm_vec_flags(a);
-  if (a.M >= 0x7fffffffLL || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;   // 32-bit pixel arithmetic in the kernels
+  if (!pfk_fits32(a.M) || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;   // 32-bit pixel arithmetic in the kernels
   fastdiv_make((unsigned)a.Wo, a.wo_mul, a.wo_sh);
   fastdiv_make((unsigned)a.Ho, a.ho_mul, a.ho_sh);
   int cfg;
@@ -1253,7 +1221,7 @@ int launch(const GemmArgs& a0, int epi, int batches, hipStream_t st) {
     // Measured on MI355X (scripts/conv_bench.py, batch 1 / 4 / 8): 64x64 tiles with the 3-stage hand-interleaved pipeline win at
     // every batch size; what varies is the schedule around them.
     const double fill = (double)blocks64 / (256.0 * (double)((blocks64 + 255) / 256));
-    const bool sk_fits = blocks64 * (long long)a.sk_steps * (SK_MAX_BLOCKS + 1) < 0x7fffffffLL;   // 32-bit unit arithmetic
+    const bool sk_fits = pfk_fits32(blocks64 * (long long)a.sk_steps * (SK_MAX_BLOCKS + 1));   // 32-bit unit arithmetic
     // Stream-K where the tile grid quantises badly on 256 CUs and K is long enough to amortise segment prologues + fix-up.
     // Batch 1 (7040 pixels, round-2 sweep): z|r conv 440 tiles x 60 steps 72.5 -> 63.7 us, fh|mask conv1 880 x 36 80.5 -> 75.8,
     // convc2 330 x 72 80.4 -> 62.5; it loses for 220-tile launches (q 41.8 -> 43.5, conv 47.8 -> 48.2: one tile per CU is
@@ -1345,38 +1313,27 @@ int launch(const GemmArgs& a0, int epi, int batches, hipStream_t st) {
 
 inline int round_up32(int c) { return (c + 31) & ~31; }
 
-int conv_ktot(const pfk_conv_desc* d, int kpad) {
-  if (!d || d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
-  int k = 0;
-  for (int s = 0; s < d->num_src; ++s) k += d->kh * d->kw * ((d->src[s].channels + kpad - 1) / kpad * kpad);
-  return k;
-}
-
 // Validate a conv descriptor and fill everything but the weight operand.  kpad = channels per K-step (32 fp32, 64 bf16).
 int desc_to_args(const pfk_conv_desc* d, GemmArgs& a, int kpad) {
   if (d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
   if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0) return PFK_ERR_BAD_ARG;
   if (d->kh <= 0 || d->kw <= 0 || !(d->kh & 1) || !(d->kw & 1)) return PFK_ERR_BAD_ARG;
-  const pfk_conv_src* s = d->src;
   for (int i = 0; i < d->num_src; ++i) {
-    if (!s[i].ptr || s[i].channels <= 0 || s[i].ld < s[i].channels) return PFK_ERR_BAD_ARG;
-    if (!pfk_aligned16(s[i].ptr) || (s[i].ld & 3) || (s[i].channels & 3)) return PFK_ERR_ALIGNMENT;
+    const int rc = pfk_check_source(d->src[i], 4, 16);
+    if (rc != PFK_OK) return rc;
   }
-  a.src0 = s[0].ptr; a.ld0 = s[0].ld; a.ch0 = s[0].channels;
-  if (d->num_src > 1) { a.src1 = s[1].ptr; a.ld1 = s[1].ld; a.ch1 = s[1].channels; }
-  if (d->num_src > 2) { a.src2 = s[2].ptr; a.ld2 = s[2].ld; a.ch2 = s[2].channels; }
-  a.nsrc = d->num_src;
-  const int stride = d->stride > 0 ? d->stride : 1;
+  pfk_spread_sources(a, d);
+  const pfk_conv_geometry geo = pfk_conv_geom(d);
   a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw;
-  a.stride = stride; a.Ho = (d->H - 1) / stride + 1; a.Wo = (d->W - 1) / stride + 1;
+  a.stride = geo.stride; a.Ho = geo.Ho; a.Wo = geo.Wo;
   a.relu2 = d->relu_after_residual;
   a.bias = d->bias; a.b_rows = d->cout;
-  a.ktot = conv_ktot(d, kpad);
+  a.ktot = pfk_conv_k(d, kpad);
   a.relu = d->relu ? 1 : 0; a.scale = d->scale;     // (any non-zero `relu` is relu: ACT_GELU comes from the epilogue value only)
-  a.M = (long long)d->B * a.Ho * a.Wo;
+  a.M = geo.M_out;
   a.sk_steps = a.ktot / kpad;
   for (int i = 0; i < d->num_src; ++i)   // kernels address sources with 32-bit byte offsets
-    if ((long long)d->B * d->H * d->W * s[i].ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_source_fits32(d->src[i], geo.M_in, 4)) return PFK_ERR_UNSUPPORTED;
   switch (d->epilogue) {
     case PFK_EPI_LINEAR_GELU:   // the LINEAR epilogue with GELU in relu's place (pfk.h); launched as PFK_EPI_LINEAR
       if (d->relu) return PFK_ERR_BAD_ARG;
@@ -1436,9 +1393,9 @@ long long pfk_conv_workspace_bytes(void) { return (long long)SK_WS_BYTES; }
 
 long long pfk_conv_workspace_fault_offset(void) { return (long long)SK_MAX_BLOCKS * 64 * 64 * 4 + (long long)SK_FAULT_SLOT * 4; }
 
-int pfk_conv_ktot(const pfk_conv_desc* d) { return conv_ktot(d, 32); }
+int pfk_conv_ktot(const pfk_conv_desc* d) { return pfk_conv_k(d, 32); }
 
-int pfk_conv_ktot_bf16(const pfk_conv_desc* d) { return conv_ktot(d, 32); }
+int pfk_conv_ktot_bf16(const pfk_conv_desc* d) { return pfk_conv_k(d, 32); }
 
 int pfk_conv2d_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
   GemmArgs a{};
@@ -1447,7 +1404,7 @@ int pfk_conv2d_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
   const int rc = desc_to_args(d, a, 32);
   if (rc != PFK_OK) return rc;
   a.weight = d->weight;
-  if ((long long)d->cout * a.ktot * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32((long long)d->cout * a.ktot * 4)) return PFK_ERR_UNSUPPORTED;
   if (d->cout_active > 0 && d->cout_active < d->cout) {
     if (d->epilogue != PFK_EPI_LINEAR || (d->cout_active & 63)) return PFK_ERR_BAD_ARG;
     a.active_tiles_n = d->cout_active / 64;
@@ -1478,12 +1435,12 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
   }
   // problems with the longest K loop first: their tiles start in the first resident round and the short ones fill in behind them
   for (int i = 1; i < n; ++i)
-    for (int j = i; j > 0 && conv_ktot(&descs[order[j]], 32) > conv_ktot(&descs[order[j - 1]], 32); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    for (int j = i; j > 0 && pfk_conv_k(&descs[order[j]], 32) > pfk_conv_k(&descs[order[j - 1]], 32); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
   // 64 x 128 tiles (72 KB swizzled: two blocks per CU) where every problem's width is a multiple of 128 and its K loop is long — GMA's
   // per-pair `attn @ v` (cout 128, 220 K-steps): four pairs are 440 tiles = ONE resident round, against 880 tiles of 64 x 64 on 768
   // slots (a second round of 112 tiles); the same K order per output element either way: same bits
   bool wide = true;
-  for (int i = 0; i < n; ++i) wide = wide && (descs[i].cout % 128 == 0) && conv_ktot(&descs[i], 32) >= 64 * 32;
+  for (int i = 0; i < n; ++i) wide = wide && (descs[i].cout % 128 == 0) && pfk_conv_k(&descs[i], 32) >= 64 * 32;
   const int BN = wide ? 128 : 64;
   for (int i = 0; i < n; ++i) {
     const pfk_conv_desc* d = &descs[order[i]];
@@ -1491,9 +1448,9 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
     const int rc = desc_to_args(d, a, 32);
     if (rc != PFK_OK) return rc;
     a.weight = d->weight;
-    if ((long long)d->cout * a.ktot * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits32((long long)d->cout * a.ktot * 4)) return PFK_ERR_UNSUPPORTED;
     a.vec_flags = gemm_vec_flags(a);
-    if (a.M >= 0x7fffffffLL || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits32(a.M) || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;
     fastdiv_make((unsigned)a.Wo, a.wo_mul, a.wo_sh);
     fastdiv_make((unsigned)a.Ho, a.ho_mul, a.ho_sh);
     a.tiles_n = (a.b_rows + BN - 1) / BN;
@@ -1501,32 +1458,18 @@ int pfk_conv2d_group_f32(const pfk_conv_desc* descs, int n, pfk_stream_t stream)
     const long long nblk = ((a.M + 63) / 64) * a.tiles_n;
     g.first[i] = (int)total;
     total += nblk;
-    if (nblk <= 0 || total > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (nblk <= 0 || !pfk_fits_int(total)) return PFK_ERR_UNSUPPORTED;
   }
   g.first[n] = (int)total;
   g.n = n;
   // the swizzled 48 KB layout (three blocks per CU) from three tiles per CU up, the padded 55 KB one below — the single launches' rule
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (wide) {
-    constexpr size_t smem = (size_t)3 * (64 + 128) * LDS_LDX * sizeof(float);
-    auto kern = conv_gemm_v3_group_kernel<LDS_LDX, 128, 64>;
-    static pfk_device_once attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, st, g);
-  } else if (total >= 3 * 256) {
-    constexpr size_t smem = (size_t)3 * (64 + 64) * LDS_LDX * sizeof(float);
-    auto kern = conv_gemm_v3_group_kernel<LDS_LDX>;
-    static pfk_device_once attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, st, g);
-  } else {
-    constexpr size_t smem = (size_t)3 * (64 + 64) * LDS_LD * sizeof(float);
-    auto kern = conv_gemm_v3_group_kernel<LDS_LD>;
-    static pfk_device_once attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, st, g);
-  }
-  return pfk_launch_status();
+  const dim3 grid((unsigned)total), block(256);
+  constexpr size_t s_wide = (size_t)3 * (64 + 128) * LDS_LDX * sizeof(float), s_swz = (size_t)3 * (64 + 64) * LDS_LDX * sizeof(float),
+                   s_pad = (size_t)3 * (64 + 64) * LDS_LD * sizeof(float);
+  if (wide) return pfk_launch_lds<conv_gemm_v3_group_kernel<LDS_LDX, 128, 64>, s_wide>(grid, block, s_wide, st, g);
+  if (total >= 3 * 256) return pfk_launch_lds<conv_gemm_v3_group_kernel<LDS_LDX>, s_swz>(grid, block, s_swz, st, g);
+  return pfk_launch_lds<conv_gemm_v3_group_kernel<LDS_LD>, s_pad>(grid, block, s_pad, st, g);
 }
 
 int pfk_mask_upsample_f32(const float* x, int x_ld, int cin, const float* weight_perm, const float* bias_perm, float scale,
@@ -1534,7 +1477,7 @@ int pfk_mask_upsample_f32(const float* x, int x_ld, int cin, const float* weight
   if (!x || !weight_perm || !flow_pm || !out || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || x_ld < cin || flow_ld < 2) return PFK_ERR_BAD_ARG;
   if ((cin & 31) || (x_ld & 3) || !pfk_aligned16(x) || !pfk_aligned16(weight_perm)) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL || M * x_ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;     // 32-bit byte offsets / pixel arithmetic
+  if (!pfk_fits32(M) || !pfk_fits32(M * x_ld * 4)) return PFK_ERR_UNSUPPORTED;     // 32-bit byte offsets / pixel arithmetic
   GemmArgs a{};
   a.src0 = x; a.ld0 = x_ld; a.ch0 = cin; a.nsrc = 1;
   a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.stride = 1; a.kh = 1; a.kw = 1;
@@ -1544,14 +1487,9 @@ int pfk_mask_upsample_f32(const float* x, int x_ld, int cin, const float* weight
   fastdiv_make((unsigned)W, a.wo_mul, a.wo_sh);
   fastdiv_make((unsigned)H, a.ho_mul, a.ho_sh);
   const long long nblk = ((M + MU_BM - 1) / MU_BM) * 4;
-  if (nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   constexpr size_t smem = 2 * (MU_BM + MU_BN) * LDS_LDX * sizeof(float);
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mask_upsample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(mask_upsample_kernel, dim3((unsigned)nblk), dim3(256), smem, static_cast<hipStream_t>(stream), a);
-  return pfk_launch_status();
+  return pfk_launch_lds<mask_upsample_kernel, smem>(dim3((unsigned)nblk), dim3(256), smem, static_cast<hipStream_t>(stream), a);
 }
 
 int pfk_conv2d_bf16s(const pfk_conv_desc* d, const void* weight_planes, int nsplit, pfk_stream_t stream) {
@@ -1564,7 +1502,7 @@ int pfk_conv2d_bf16s(const pfk_conv_desc* d, const void* weight_planes, int nspl
   if (rc != PFK_OK) return rc;
   a.wbf = weight_planes;
   a.wbf_plane_bytes = (long long)d->cout * a.ktot * 2;
-  if (a.wbf_plane_bytes * nsplit >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(a.wbf_plane_bytes * nsplit)) return PFK_ERR_UNSUPPORTED;
   return launch_bf(a, d->epilogue, nsplit, static_cast<hipStream_t>(stream));
 }
 
@@ -1575,7 +1513,7 @@ int pfk_corr_volume_f32(const float* f1, int ld1, const float* f2, int ld2, floa
   if (!pfk_aligned16(f1) || !pfk_aligned16(f2) || (ld1 & 3) || (ld2 & 3) || (D & 3))
     return PFK_ERR_ALIGNMENT;
   if (ld2 != round_up32(D)) return PFK_ERR_UNSUPPORTED;  // f2 rows are read as packed weight rows
-  if ((long long)N1 * ld1 * 4 >= 0x7fffffffLL || (long long)N2 * ld2 * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32((long long)N1 * ld1 * 4) || !pfk_fits32((long long)N2 * ld2 * 4)) return PFK_ERR_UNSUPPORTED;
   GemmArgs a{};
   a.src0 = f1; a.ld0 = ld1; a.ch0 = D; a.nsrc = 1;
   a.H = 1; a.W = N1; a.Ho = 1; a.Wo = N1; a.stride = 1; a.kh = 1; a.kw = 1;

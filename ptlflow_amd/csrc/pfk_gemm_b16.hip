@@ -583,28 +583,18 @@ int launch_b16_one(const B16Args& a0, hipStream_t st) {
   const long long tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.b_rows + BN - 1) / BN;
   const long long nblk = tiles_m * a.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (nblk <= 0 || !pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   constexpr size_t smem = (size_t)NST * (BM + BN) * ROW16;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static_assert(WM * WN * 4096 * (BN / (32 * WN)) <= (int)smem, "the LDS epilogue needs 4 KB per wave and 32 columns");
-  auto kern = conv_gemm_b16_kernel<EPI, BM, BN, WM, WN, NST, ABL>;
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)(a.batches > 1 ? a.batches : 1)), dim3(64 * WM * WN), smem, st, a);
-  return pfk_launch_status();
+  const dim3 grid((unsigned)nblk, (unsigned)(a.batches > 1 ? a.batches : 1));
+  return pfk_launch_lds<conv_gemm_b16_kernel<EPI, BM, BN, WM, WN, NST, ABL>, smem>(grid, dim3(64 * WM * WN), smem, st, a);
 }
 
 template <int BM, int BN, int WM, int WN, int NST>
 int launch_b16_epi(const B16Args& a, int epi, hipStream_t st) {
-  switch (epi) {
-    case PFK_EPI_LINEAR: return launch_b16_one<PFK_EPI_LINEAR, BM, BN, WM, WN, NST>(a, st);
-    case PFK_EPI_GRU_ZR: return launch_b16_one<PFK_EPI_GRU_ZR, BM, BN, WM, WN, NST>(a, st);
-    case PFK_EPI_GRU_Q:  return launch_b16_one<PFK_EPI_GRU_Q, BM, BN, WM, WN, NST>(a, st);
-    case PFK_EPI_LINEAR_GELU: return launch_b16_one<PFK_EPI_LINEAR_GELU, BM, BN, WM, WN, NST>(a, st);
-    default: return PFK_ERR_BAD_ARG;
-  }
+  if (epi != PFK_EPI_LINEAR_GELU) return pfk_with_epilogue(epi, [&](auto e) { return launch_b16_one<decltype(e)::value, BM, BN, WM, WN, NST>(a, st); });
+  return launch_b16_one<PFK_EPI_LINEAR_GELU, BM, BN, WM, WN, NST>(a, st);      // K8b has a kernel of its own for it
 }
 
 int g_b16_cfg = 0;       // pfk_debug_set_b16(cfg): 0 = heuristic
@@ -785,13 +775,6 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_b16_kernel(const MuB16Ar
                                a.wo_sh, a.ho_mul, a.ho_sh, m0, quarter, wid * 32);
 }
 
-int b16_ktot(const pfk_conv_b16_desc* d) {
-  if (!d || d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
-  int k = 0;
-  for (int s = 0; s < d->num_src; ++s) k += d->kh * d->kw * ((d->src[s].channels + BK16 - 1) / BK16 * BK16);
-  return k;
-}
-
 }  // namespace
 
 extern "C" {
@@ -802,29 +785,24 @@ int pfk_debug_set_b16(int cfg) {
   return PFK_OK;
 }
 
-int pfk_conv_ktot_b16(const pfk_conv_b16_desc* d) { return b16_ktot(d); }
+int pfk_conv_ktot_b16(const pfk_conv_b16_desc* d) { return pfk_conv_k(d, BK16); }
 
 int pfk_mask_upsample_b16(const void* x_bf16, int x_ld, int cin, const void* weight_perm_bf16, const float* bias_perm, float scale,
                           const float* flow_pm, int flow_ld, float* out, int B, int H, int W, pfk_stream_t stream) {
   if (!x_bf16 || !weight_perm_bf16 || !flow_pm || !out || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || x_ld < cin || flow_ld < 2) return PFK_ERR_BAD_ARG;
   if ((cin & 63) || (x_ld & 7) || !pfk_aligned16(x_bf16) || !pfk_aligned16(weight_perm_bf16)) return PFK_ERR_ALIGNMENT;
   const long long M = (long long)B * H * W;
-  if (M >= 0x7fffffffLL || M * x_ld * 2 >= 0x7fffffffLL || (long long)MUB_ROWS * cin * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(M) || !pfk_fits32(M * x_ld * 2) || !pfk_fits32((long long)MUB_ROWS * cin * 2)) return PFK_ERR_UNSUPPORTED;
   MuB16Args a{};
   a.x = x_bf16; a.x_ld = x_ld; a.cin = cin; a.w = weight_perm_bf16; a.bias = bias_perm; a.scale = scale;
   a.flow = flow_pm; a.flow_ld = flow_ld; a.out = out; a.H = H; a.W = W; a.M = M;
   fastdiv_make((unsigned)W, a.wo_mul, a.wo_sh);
   fastdiv_make((unsigned)H, a.ho_mul, a.ho_sh);
   const long long nblk = ((M + MUB_BM - 1) / MUB_BM) * 4;
-  if (nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   constexpr size_t smem = 2 * (MUB_BM + MUB_BN) * ROW16;
   static_assert(MUB_BM * 9 * 8 <= (int)smem, "the epilogue's flow neighbourhoods reuse the staging LDS");
-  static pfk_device_once attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mask_upsample_b16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(mask_upsample_b16_kernel, dim3((unsigned)nblk), dim3(256), smem, static_cast<hipStream_t>(stream), a);
-  return pfk_launch_status();
+  return pfk_launch_lds<mask_upsample_b16_kernel, smem>(dim3((unsigned)nblk), dim3(256), smem, static_cast<hipStream_t>(stream), a);
 }
 
 }  // extern "C"
@@ -838,21 +816,21 @@ int conv2d_b16_impl(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
   if (d->kh <= 0 || d->kw <= 0 || !(d->kh & 1) || !(d->kw & 1) || d->kh * d->kw > 32) return PFK_ERR_BAD_ARG;
   if (!pfk_aligned16(d->weight)) return PFK_ERR_ALIGNMENT;
   B16Args a{};
+  const pfk_conv_geometry geo = pfk_conv_geom(d);
   for (int i = 0; i < d->num_src; ++i) {
     const pfk_conv_src_b16& s = d->src[i];
-    if (!s.ptr || s.channels <= 0 || s.ld < s.channels) return PFK_ERR_BAD_ARG;
-    if (!pfk_aligned16(s.ptr) || (s.ld & 7) || (s.channels & 7)) return PFK_ERR_ALIGNMENT;
-    if ((long long)d->B * d->H * d->W * s.ld * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;     // 32-bit byte offsets
+    const int rc = pfk_check_source(s, 8, 16);
+    if (rc != PFK_OK) return rc;
+    if (!pfk_source_fits32(s, geo.M_in, 2)) return PFK_ERR_UNSUPPORTED;     // 32-bit byte offsets
     a.src[i] = s.ptr; a.ld[i] = s.ld; a.ch[i] = s.channels;
   }
   a.nsrc = d->num_src;
-  const int stride = d->stride > 0 ? d->stride : 1;
-  a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw; a.stride = stride;
-  a.Ho = (d->H - 1) / stride + 1; a.Wo = (d->W - 1) / stride + 1;
-  a.M = (long long)d->B * a.Ho * a.Wo;
-  if (a.M >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
-  a.weight = d->weight; a.ktot = b16_ktot(d); a.b_rows = d->cout; a.steps = a.ktot / BK16;
-  if ((long long)d->cout * a.ktot * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw; a.stride = geo.stride;
+  a.Ho = geo.Ho; a.Wo = geo.Wo;
+  a.M = geo.M_out;
+  if (!pfk_fits32(a.M)) return PFK_ERR_UNSUPPORTED;
+  a.weight = d->weight; a.ktot = pfk_conv_k(d, BK16); a.b_rows = d->cout; a.steps = a.ktot / BK16;
+  if (!pfk_fits32((long long)d->cout * a.ktot * 2)) return PFK_ERR_UNSUPPORTED;
   a.bias = d->bias;
   if (d->bias && !pfk_aligned16(d->bias)) return PFK_ERR_ALIGNMENT;
   a.relu = d->relu; a.relu2 = d->relu_after_residual; a.scale = d->scale;
@@ -863,7 +841,7 @@ int conv2d_b16_impl(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
     const bool lin = d->epilogue == PFK_EPI_LINEAR || d->epilogue == PFK_EPI_LINEAR_GELU;
     const bool r16 = !lin || d->residual_bf16;
     const bool gru = !lin;                                 // the GRU epilogues read the term as 16-byte pieces
-    if ((reinterpret_cast<uintptr_t>(d->residual) & ((r16 && !gru) ? 7u : 15u)) || (d->residual_ld & (gru ? 7 : 3)) || (r16 && (d->cout & 3)))
+    if (!pfk_aligned(d->residual, (r16 && !gru) ? 8 : 16) || (d->residual_ld & (gru ? 7 : 3)) || (r16 && (d->cout & 3)))
       return PFK_ERR_ALIGNMENT;
     a.residual = d->residual; a.residual_ld = d->residual_ld; a.residual_bf16 = lin && d->residual_bf16;
   }
@@ -880,21 +858,21 @@ int conv2d_b16_impl(const pfk_conv_b16_desc* d, pfk_stream_t stream) {
     case PFK_EPI_LINEAR:
     case PFK_EPI_LINEAR_GELU:
       if (!d->out || d->out_ld < d->out_coff + d->cout) return PFK_ERR_BAD_ARG;
-      if ((d->out_ld & 3) || (d->out_coff & 3) || (reinterpret_cast<uintptr_t>(d->out) & (d->out_bf16 ? 7u : 15u))) return PFK_ERR_ALIGNMENT;
+      if ((d->out_ld & 3) || (d->out_coff & 3) || !pfk_aligned(d->out, d->out_bf16 ? 8 : 16)) return PFK_ERR_ALIGNMENT;
       a.out = d->out; a.out_ld = d->out_ld; a.out_coff = d->out_coff; a.out_bf16 = d->out_bf16;
       a.out_vec16 = d->out_bf16 && !d->residual && (d->batches <= 1 || (d->out_batch_stride & 7) == 0) &&
-                    !((reinterpret_cast<uintptr_t>(d->out) & 15u) || (d->out_ld & 7) || (d->out_coff & 7));
+                    pfk_aligned16(d->out) && !(d->out_ld & 7) && !(d->out_coff & 7);
       break;
     case PFK_EPI_GRU_ZR:      // (16-byte row pieces: Ch % 8 == 0, 16-byte aligned bf16 buffers, row strides multiples of 8 elements)
       if (!d->h_b16 || !d->aux_z || !d->aux_rh || (d->cout & 63)) return PFK_ERR_BAD_ARG;
-      if ((reinterpret_cast<uintptr_t>(d->h_b16) & 15u) || (d->h_b16_ld & 7) || (reinterpret_cast<uintptr_t>(d->aux_z) & 15u) ||
-          (reinterpret_cast<uintptr_t>(d->aux_rh) & 15u)) return PFK_ERR_ALIGNMENT;
+      if (!pfk_aligned16(d->h_b16) || (d->h_b16_ld & 7) || !pfk_aligned16(d->aux_z) ||
+          !pfk_aligned16(d->aux_rh)) return PFK_ERR_ALIGNMENT;
       a.h_b16 = const_cast<void*>(d->h_b16); a.hb_ld = d->h_b16_ld; a.aux_z = d->aux_z; a.aux_rh = d->aux_rh; a.ch_hidden = d->cout / 2;
       break;
     case PFK_EPI_GRU_Q:
       if (!d->h || !d->aux_z || (d->cout & 31)) return PFK_ERR_BAD_ARG;
-      if (!pfk_aligned16(d->h) || (d->h_ld & 3) || (reinterpret_cast<uintptr_t>(d->aux_z) & 15u)) return PFK_ERR_ALIGNMENT;
-      if (d->h_b16 && ((reinterpret_cast<uintptr_t>(d->h_b16) & 15u) || (d->h_b16_ld & 7) || d->h_b16_ld < d->cout)) return PFK_ERR_ALIGNMENT;
+      if (!pfk_aligned16(d->h) || (d->h_ld & 3) || !pfk_aligned16(d->aux_z)) return PFK_ERR_ALIGNMENT;
+      if (d->h_b16 && (!pfk_aligned16(d->h_b16) || (d->h_b16_ld & 7) || d->h_b16_ld < d->cout)) return PFK_ERR_ALIGNMENT;
       a.h = d->h; a.h_ld = d->h_ld; a.aux_z = d->aux_z; a.ch_hidden = d->cout;
       a.h_b16 = d->h_b16; a.hb_ld = d->h_b16_ld;
       break;

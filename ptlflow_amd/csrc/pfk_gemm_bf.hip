@@ -456,7 +456,7 @@ __global__ __launch_bounds__(64 * WM * WN, bf_blocks_per_cu(NS, BM, BN, SUB, WM 
 template <int EPI, int NS, int BM, int BN, int SUB, int WM = 2, int WN = 2, int NSETS = 2, bool BDMA = false>
 int launch_bf_one(const GemmArgs& a, hipStream_t st, long long row0, long long row1) {
   GemmArgs g = a;
-  if (a.M >= 0x7fffffffLL || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;   // 32-bit pixel arithmetic in the stager
+  if (!pfk_fits32(a.M) || a.Wo <= 0 || a.Ho <= 0) return PFK_ERR_UNSUPPORTED;   // 32-bit pixel arithmetic in the stager
   fastdiv_make((unsigned)a.Wo, g.wo_mul, g.wo_sh);
   fastdiv_make((unsigned)a.Ho, g.ho_mul, g.ho_sh);
   // output rows [row0, row1) of M (row0 a multiple of BM; row1 < 0: to the end)
@@ -466,27 +466,16 @@ int launch_bf_one(const GemmArgs& a, hipStream_t st, long long row0, long long r
   const long long tiles_m = (row1 - row0 + BM - 1) / BM;
   g.tiles_n = (a.b_rows + BN - 1) / BN;
   const long long nblk = tiles_m * g.tiles_n;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (nblk <= 0 || !pfk_fits_int(nblk)) return PFK_ERR_UNSUPPORTED;
   constexpr size_t smem = 2 * (size_t)SUB * NS * (BM + BN) * ROWB;
   static_assert(smem <= 160 * 1024, "LDS budget");
   static_assert(WM * WN * 4096 <= (int)smem, "the LDS epilogue needs 4 KB per wave");
-  auto kern = conv_gemm_bf_kernel<EPI, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>;
-  static pfk_device_once attr_once;   // one per template instantiation and device; safe with several host threads
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  });
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * WM * WN), smem, st, g);
-  return pfk_launch_status();
+  return pfk_launch_lds<conv_gemm_bf_kernel<EPI, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>, smem>(dim3((unsigned)nblk), dim3(64 * WM * WN), smem, st, g);
 }
 
 template <int NS, int BM, int BN, int SUB, int WM = 2, int WN = 2, int NSETS = 2, bool BDMA = false>
 int launch_bf_epi(const GemmArgs& g, int epi, hipStream_t st, long long row0, long long row1) {
-  switch (epi) {
-    case PFK_EPI_LINEAR: return launch_bf_one<PFK_EPI_LINEAR, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>(g, st, row0, row1);
-    case PFK_EPI_GRU_ZR: return launch_bf_one<PFK_EPI_GRU_ZR, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>(g, st, row0, row1);
-    case PFK_EPI_GRU_Q:  return launch_bf_one<PFK_EPI_GRU_Q, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>(g, st, row0, row1);
-    default: return PFK_ERR_BAD_ARG;
-  }
+  return pfk_with_epilogue(epi, [&](auto e) { return launch_bf_one<decltype(e)::value, NS, BM, BN, SUB, WM, WN, NSETS, BDMA>(g, st, row0, row1); });
 }
 
 // tile configurations: 1 = 64x64 (two sub-steps per barrier), 2 = 128x64, 3 = 128x128, 4 = 128x128 with eight waves (2 x 4: every

@@ -2,7 +2,7 @@
 // the 2-output flow head fused with the coordinate update, bilinear upsampling, layout changes.
 // None of them is GEMM-shaped enough to pay for a matrix-core tile; they are bandwidth/latency
 // bound and written for coalesced 64-lane access.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 
 namespace {
 
@@ -478,7 +478,7 @@ static int conv_cin2_launch(const float* in, int in_ld, const float* weight, con
       ((long long)B * c2_tx * c2_ty >= 256 || g_cin2_valu == 2)) {
     const int tiles_x = c2_tx, tiles_y = c2_ty;
     const long long tiles = (long long)B * tiles_x * tiles_y;
-    if (tiles > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits_int(tiles)) return PFK_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);       // two workgroups per CU, persistent over the tile list
     if (cout == 128)
       hipLaunchKernelGGL((conv_cin2_mfma_kernel<4, TO>), dim3(grid), dim3(256), 0, st, in, in_ld, weight, bias, out, out_ld, out_coff, H, W,
@@ -491,7 +491,7 @@ static int conv_cin2_launch(const float* in, int in_ld, const float* weight, con
   if (k == 3 || k == 5 || k == 7) {
     const int tpr = (W + 15) / 16;
     const long long tiles = (long long)B * H * tpr;
-    if (tiles > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits_int(tiles)) return PFK_ERR_UNSUPPORTED;
     dim3 grid((unsigned)tiles), block(256);
     if (k == 7) hipLaunchKernelGGL((conv_cin2_tiled_kernel<7, TO>), grid, block, 0, st, in, in_ld, weight, bias, out, out_ld, out_coff, H, W, tpr, cout, relu);
     else if (k == 5) hipLaunchKernelGGL((conv_cin2_tiled_kernel<5, TO>), grid, block, 0, st, in, in_ld, weight, bias, out, out_ld, out_coff, H, W, tpr, cout, relu);
@@ -500,7 +500,7 @@ static int conv_cin2_launch(const float* in, int in_ld, const float* weight, con
   }
   if constexpr (sizeof(TO) == 4) {
     const long long blocks = (M * cout + 255) / 256;
-    if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(conv_cin2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, in_ld, weight, bias, out, out_ld,
                        out_coff, M, H, W, k, cout, relu);
     return pfk_launch_status();
@@ -542,14 +542,14 @@ static int flow_delta_launch(const TI* in, int in_ld, int cin, const float* weig
                              float* flow_out, int flow_ld, __bf16* flow_b16, int flow_b16_ld, int B, int H, int W, pfk_stream_t stream) {
   if (!in || !weight || !coords0 || !coords1 || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
   if (cin <= 0 || in_ld < cin || (flow_out && flow_ld < 2) || (flow_b16 && flow_b16_ld < 2)) return PFK_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(in) & (sizeof(TI) * 4 - 1)) || !pfk_aligned16(weight) || (in_ld & 3) || (cin & 3))
+  if (!pfk_aligned(in, sizeof(TI) * 4) || !pfk_aligned16(weight) || (in_ld & 3) || (cin & 3))
     return PFK_ERR_ALIGNMENT;
   // 8 pixels per wave (fewest row loads) once that still gives every SIMD a few waves; 4 per wave below (batch 1: 7040 pixels)
   const long long rows = (long long)B * H;
   const int pixw = rows * ((W + 7) / 8) >= 4096 ? 8 : 4;
   const int tpr = (W + pixw - 1) / pixw;             // waves per image row
   const long long blocks = (rows * tpr + 3) / 4;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (pixw == 8)
     hipLaunchKernelGGL((flow_delta_kernel<8, TI>), dim3((unsigned)blocks), dim3(256), 0, st, in, in_ld, cin, weight, bias, coords0,
@@ -590,7 +590,7 @@ int pfk_upflow8_f32(const float* coords0, const float* coords1, float* out, int 
   if (!coords0 || !coords1 || !out || B <= 0 || H <= 0 || W <= 0) return PFK_ERR_BAD_ARG;
   const long long n = (long long)B * 64 * H * W;
   const long long blocks = (n + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(upflow8_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), coords0, coords1, out,
                      B, H, W);
   return pfk_launch_status();
@@ -628,7 +628,7 @@ int pfk_pm_to_cm_f32(const float* in, int in_ld, float* out, int out_ld, int B, 
 }
 
 int pfk_softmax_rows_f32(float* x, long long rows, int cols, long long ld, pfk_stream_t stream) {
-  if (!x || rows <= 0 || cols <= 0 || ld < cols || rows > 0x7fffffffLL) return PFK_ERR_BAD_ARG;
+  if (!x || rows <= 0 || cols <= 0 || ld < cols || !pfk_fits_int(rows)) return PFK_ERR_BAD_ARG;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, static_cast<hipStream_t>(stream), x, ld, cols);
   return pfk_launch_status();
 }

@@ -2,6 +2,7 @@
 // backward.  The arithmetic of a (coarse pixel, sub-pixel) is pfk_upsample.h's; this file is the lane layouts around it, the
 // cross-lane reductions of the backward and the C entry points.  Bandwidth-bound VALU kernels, compiled with -ffp-contract=off.
 // (The fused forms — mask head conv2 + softmax + upsampling, K13 / K13b — are in pfk_gemm.hip / pfk_gemm_b16.hip.)
+#include "pfk_launch.h"
 #include "pfk_upsample.h"
 
 #include <initializer_list>
@@ -249,7 +250,7 @@ bool up_args_ok(std::initializer_list<const void*> required, int B, int H, int W
 bool up_grid(long long items, int per_block, unsigned& blocks) {
   const long long n = (items + per_block - 1) / per_block;
   blocks = (unsigned)n;
-  return n <= 0x7fffffffLL;
+  return pfk_fits_int(n);
 }
 
 template <typename TM, int V, bool INFO>
@@ -300,7 +301,7 @@ int pfk_convex_upsample_pm_f32(const float* flow_pm, int flow_ld, const float* m
 int pfk_convex_upsample_pm_b16(const float* flow_pm, int flow_ld, const void* mask_bf16, int mask_ld, float* out,
                                int B, int H, int W, pfk_stream_t stream) {
   if (!up_args_ok({flow_pm, mask_bf16, out}, B, H, W, mask_ld, flow_ld)) return PFK_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(mask_bf16) & 7u) || !pfk_aligned16(out) || (mask_ld & 3)) return PFK_ERR_ALIGNMENT;
+  if (!pfk_aligned<8>(mask_bf16) || !pfk_aligned16(out) || (mask_ld & 3)) return PFK_ERR_ALIGNMENT;
   return launch_convex_upsample<__bf16, 4, false>(flow_pm, flow_ld, nullptr, 0, 0, static_cast<const __bf16*>(mask_bf16), mask_ld, out,
                                                   nullptr, B, H, W, stream);
 }

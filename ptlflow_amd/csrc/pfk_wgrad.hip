@@ -15,7 +15,7 @@
 // adds the slices in a fixed order (deterministic, no atomics) into the packed [cout][ktot] layout of the forward weight.
 // (A 128 x 128 tile with 64x64 wave tiles — half the LDS reads per MFMA — measured 5-30 % SLOWER on every training shape:
 // the loop is not LDS-bound, fewer resident waves per SIMD hurt more.)
-#include "pfk_common.h"
+#include "pfk_launch.h"
 #include "pfk_wgrad_reduce.h"   // wgrad_reduce_unpack_kernel: the slice reduction into PyTorch's layouts, shared with pfk_wgrad_b16.hip
 
 namespace {
@@ -238,34 +238,10 @@ __global__ __launch_bounds__(256) void gru_b2_kernel(const float* __restrict__ d
   store4(dh + p * C + c, load4_widen(dh + p * C + c) + g * rr);
 }
 
-int g_wgrad_variant = 0;   // 0: tile height by padding waste (pick_cb); 1 / 2 / 4: forced CB — pfk_debug_set_wgrad
+int g_wgrad_variant = 0;   // 0: tile height by padding waste (wgrad_pick_cb); 1 / 2 / 4: forced CB — pfk_debug_set_wgrad
 
-// 32-row output-channel blocks per tile: the tallest tile among {4, 2, 1} blocks that pads cout the least
-int pick_cb(int cout) {
-  if (g_wgrad_variant == 1 || g_wgrad_variant == 2 || g_wgrad_variant == 4) return g_wgrad_variant;
-  int best = 4, waste = (cout + 127) / 128 * 128 - cout;
-  const int w2 = (cout + 63) / 64 * 64 - cout, w1 = (cout + 31) / 32 * 32 - cout;
-  if (w2 < waste) { best = 2; waste = w2; }
-  if (w1 < waste) best = 1;
-  return best;
-}
-
-// blocks of the main launch for a tile height: (cout tiles) x (K chunk groups)
-long long wgrad_tiles(int cout, int chunks, int cb) { return (long long)((cout + 32 * cb - 1) / (32 * cb)) * ((chunks + 4 / cb - 1) / (4 / cb)); }
-
-int pick_splits(long long tiles, long long M, long long target = 1024) {
-  long long s = target / (tiles > 0 ? tiles : 1);
-  const long long max_s = M / 512 > 0 ? M / 512 : 1;     // >= 16 K-steps per slice
-  if (s > max_s) s = max_s;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
-}
-
-inline int ktot_of(const pfk_conv_desc* d) {
-  int k = 0;
-  for (int s = 0; s < d->num_src; ++s) k += d->kh * d->kw * ((d->src[s].channels + 31) / 32 * 32);
-  return k;
-}
+// slices of M output pixels: K-steps of 32 pixels, at least 16 (512 pixels) per slice
+int pick_splits(const WgradGrid& g, long long M) { return wgrad_pick_splits((long long)g.tiles_m * g.groups, M / 32, 16); }
 
 }  // namespace
 
@@ -275,58 +251,47 @@ int pfk_debug_set_wgrad(int variant) { if (!pfk_debug_knobs_enabled()) return PF
 
 long long pfk_conv_wgrad_workspace_bytes(const pfk_conv_desc* d, int with_bias) {
   if (!d || d->num_src < 1 || d->num_src > 3 || d->cout <= 0) return 0;
-  const int ktot = ktot_of(d) + (with_bias ? 32 : 0);
-  const int sd = d->stride > 1 ? d->stride : 1;
-  const long long M = (long long)d->B * ((d->H - 1) / sd + 1) * ((d->W - 1) / sd + 1);
+  const int ktot = pfk_conv_k(d, 32) + (with_bias ? 32 : 0);
+  const long long M = pfk_conv_geom(d).M_out;
   int splits = 1;
   for (int cb = 1; cb <= 4; cb *= 2) {        // any tile height may run (pfk_debug_set_wgrad): size for the largest split count
-    const int sc = pick_splits(wgrad_tiles(d->cout, ktot / 32, cb), M);
+    const int sc = pick_splits(wgrad_grid(d->cout, ktot, cb), M);
     splits = sc > splits ? sc : splits;
   }
   return splits > 1 ? (long long)splits * d->cout * ktot * (long long)sizeof(float) : 0;
 }
 
 // Validate, fill the kernel arguments (everything but `part`) and pick the split count.
-static int wgrad_plan(const pfk_conv_desc* d, const float* dy, int dy_ld, int with_bias, WgradArgs& a, int& cb, int& groups, int& splits) {
+static int wgrad_plan(const pfk_conv_desc* d, const float* dy, int dy_ld, int with_bias, WgradArgs& a, WgradGrid& g, int& splits) {
   if (!d || !dy || d->num_src < 1 || d->num_src > 3) return PFK_ERR_BAD_ARG;
   if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || dy_ld < d->cout) return PFK_ERR_BAD_ARG;
   if (d->kh <= 0 || d->kw <= 0 || !(d->kh & 1) || !(d->kw & 1) || d->stride < 0) return PFK_ERR_BAD_ARG;
   if ((d->cout & 3) || (dy_ld & 3) || !pfk_aligned16(dy)) return PFK_ERR_ALIGNMENT;
-  const pfk_conv_src* s = d->src;
-  const int sd = d->stride > 1 ? d->stride : 1;
-  const int Ho = (d->H - 1) / sd + 1, Wo = (d->W - 1) / sd + 1;
-  const long long M = (long long)d->B * Ho * Wo;                 // dY rows: the OUTPUT grid
-  const long long Min = (long long)d->B * d->H * d->W;           // source rows
+  const pfk_conv_geometry geo = pfk_conv_geom(d);                // dY has M_out rows (the OUTPUT grid), the sources M_in
   for (int i = 0; i < d->num_src; ++i) {
-    if (!s[i].ptr || s[i].channels <= 0 || s[i].ld < s[i].channels) return PFK_ERR_BAD_ARG;
-    if (!pfk_aligned16(s[i].ptr) || (s[i].ld & 3) || (s[i].channels & 3)) return PFK_ERR_ALIGNMENT;
-    if (Min * s[i].ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+    const int rc = pfk_check_source(d->src[i], 4, 16);
+    if (rc != PFK_OK) return rc;
+    if (!pfk_source_fits32(d->src[i], geo.M_in, 4)) return PFK_ERR_UNSUPPORTED;
   }
-  if (M * dy_ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(geo.M_out * dy_ld * 4)) return PFK_ERR_UNSUPPORTED;
   a = WgradArgs{};
-  a.src0 = s[0].ptr; a.ld0 = s[0].ld; a.ch0 = s[0].channels;
-  if (d->num_src > 1) { a.src1 = s[1].ptr; a.ld1 = s[1].ld; a.ch1 = s[1].channels; }
-  if (d->num_src > 2) { a.src2 = s[2].ptr; a.ld2 = s[2].ld; a.ch2 = s[2].channels; }
-  a.nsrc = d->num_src;
+  pfk_spread_sources(a, d);
   a.dy = dy; a.dy_ld = dy_ld; a.cout = d->cout;
-  a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw; a.M = M;
-  a.Ho = Ho; a.Wo = Wo; a.stride = sd;
+  a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw; a.M = geo.M_out;
+  a.Ho = geo.Ho; a.Wo = geo.Wo; a.stride = geo.stride;
   a.with_bias = with_bias ? 1 : 0;
-  a.ktot = ktot_of(d) + (with_bias ? 32 : 0);
+  a.ktot = pfk_conv_k(d, 32) + (with_bias ? 32 : 0);
   a.chunks = a.ktot / 32;
-  cb = pick_cb(d->cout);
-  a.tiles_m = (d->cout + 32 * cb - 1) / (32 * cb);
-  groups = (a.chunks + 4 / cb - 1) / (4 / cb);
-  splits = pick_splits((long long)a.tiles_m * groups, M);
-  a.px_per_split = ((M + splits - 1) / splits + 31) / 32 * 32;
+  g = wgrad_grid(d->cout, a.ktot, wgrad_pick_cb(d->cout, g_wgrad_variant));
+  a.tiles_m = g.tiles_m;
+  splits = pick_splits(g, geo.M_out);
+  a.px_per_split = ((geo.M_out + splits - 1) / splits + 31) / 32 * 32;
   return PFK_OK;
 }
 
-static void wgrad_run(const WgradArgs& a, int cb, int groups, int splits, hipStream_t st) {
-  const dim3 grid((unsigned)(a.tiles_m * groups), (unsigned)splits);
-  if (cb == 4) hipLaunchKernelGGL(conv_wgrad_kernel<4>, grid, dim3(256), 0, st, a);
-  else if (cb == 2) hipLaunchKernelGGL(conv_wgrad_kernel<2>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(conv_wgrad_kernel<1>, grid, dim3(256), 0, st, a);
+static void wgrad_run(const WgradArgs& a, const WgradGrid& g, int splits, hipStream_t st) {
+  const dim3 grid((unsigned)(g.tiles_m * g.groups), (unsigned)splits);
+  wgrad_launch_cb<conv_wgrad_kernel<4>, conv_wgrad_kernel<2>, conv_wgrad_kernel<1>>(g.cb, grid, st, a);
 }
 
 int pfk_conv_wgrad_f32(const pfk_conv_desc* d, const float* dy, int dy_ld, float* dw_packed, int with_bias, void* workspace,
@@ -334,8 +299,9 @@ int pfk_conv_wgrad_f32(const pfk_conv_desc* d, const float* dy, int dy_ld, float
   if (!dw_packed) return PFK_ERR_BAD_ARG;
   if (!pfk_aligned16(dw_packed)) return PFK_ERR_ALIGNMENT;
   WgradArgs a;
-  int cb, groups, splits;
-  const int rc = wgrad_plan(d, dy, dy_ld, with_bias, a, cb, groups, splits);
+  WgradGrid g;
+  int splits;
+  const int rc = wgrad_plan(d, dy, dy_ld, with_bias, a, g, splits);
   if (rc != PFK_OK) return rc;
   const long long n = (long long)d->cout * a.ktot;
   if (splits > 1) {
@@ -345,7 +311,7 @@ int pfk_conv_wgrad_f32(const pfk_conv_desc* d, const float* dy, int dy_ld, float
     a.part = dw_packed;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  wgrad_run(a, cb, groups, splits, st);
+  wgrad_run(a, g, splits, st);
   if (splits > 1)
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st,
                        static_cast<const float*>(workspace), dw_packed, n, splits);
@@ -355,7 +321,7 @@ int pfk_conv_wgrad_f32(const pfk_conv_desc* d, const float* dy, int dy_ld, float
 long long pfk_conv_wgrad_unpacked_workspace_bytes(const pfk_conv_desc* d, int with_bias) {
   if (!d || d->num_src < 1 || d->num_src > 3 || d->cout <= 0) return 0;
   const long long packed = pfk_conv_wgrad_workspace_bytes(d, with_bias);
-  const long long one = (long long)d->cout * (ktot_of(d) + (with_bias ? 32 : 0)) * (long long)sizeof(float);
+  const long long one = (long long)d->cout * (pfk_conv_k(d, 32) + (with_bias ? 32 : 0)) * (long long)sizeof(float);
   return packed > one ? packed : one;       // the slices always go through the workspace here, even a single one
 }
 
@@ -365,24 +331,18 @@ int pfk_conv_wgrad_unpacked_f32(const pfk_conv_desc* d, const int* real_channels
   if (!pfk_aligned16(workspace)) return PFK_ERR_ALIGNMENT;
   const int with_bias = db != nullptr;
   WgradArgs a;
-  int cb, groups, splits;
-  const int rc = wgrad_plan(d, dy, dy_ld, with_bias, a, cb, groups, splits);
+  WgradGrid g;
+  int splits;
+  const int rc = wgrad_plan(d, dy, dy_ld, with_bias, a, g, splits);
   if (rc != PFK_OK) return rc;
   const long long n = (long long)d->cout * a.ktot;
   if (workspace_bytes < splits * n * (long long)sizeof(float)) return PFK_ERR_BAD_ARG;
   a.part = static_cast<float*>(workspace);
-  UnpackArgs u{};
-  u.part = a.part; u.n = n; u.splits = splits; u.ktot = a.ktot; u.cout_real = cout_real; u.taps = d->kh * d->kw;
-  u.nseg = d->num_src; u.with_bias = with_bias; u.dw = dw; u.db = db; u.accumulate = accumulate != 0;
-  int first = 0;
-  for (int i = 0; i < d->num_src; ++i) {
+  for (int i = 0; i < d->num_src; ++i)
     if (real_channels[i] <= 0 || real_channels[i] > d->src[i].channels) return PFK_ERR_BAD_ARG;
-    u.first[i] = first; u.nreal[i] = real_channels[i]; u.cpad[i] = (d->src[i].channels + 31) / 32 * 32;
-    first += real_channels[i];
-  }
-  u.cin_total = first;
+  const UnpackArgs u = wgrad_unpack_args(d, real_channels, a.part, n, splits, a.ktot, cout_real, with_bias, dw, db, accumulate);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  wgrad_run(a, cb, groups, splits, st);
+  wgrad_run(a, g, splits, st);
   const long long total = (long long)cout_real * a.ktot;
   hipLaunchKernelGGL(wgrad_reduce_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u);
   return pfk_launch_status();
@@ -391,7 +351,7 @@ int pfk_conv_wgrad_unpacked_f32(const pfk_conv_desc* d, const int* real_channels
 static int gru_grid(long long M, int C, dim3* grid) {
   if (M <= 0 || C <= 0 || (C & 3)) return PFK_ERR_BAD_ARG;
   const long long blocks = (M * (C >> 2) + 255) / 256;
-  if (blocks > 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits_int(blocks)) return PFK_ERR_UNSUPPORTED;
   *grid = dim3((unsigned)blocks);
   return PFK_OK;
 }

@@ -19,7 +19,7 @@
 // Grid, tile shapes (CB = 32-row output-channel blocks per tile in {4, 2, 1}, one 32x32 accumulator per wave), the split of the
 // pixel range into slices and their fixed-order reduction into PyTorch's layouts are those of pfk_wgrad.hip
 // (pfk_wgrad_reduce.h); outputs and partial tiles are fp32.
-#include "pfk_common.h"
+#include "pfk_launch.h"
 #include "pfk_wgrad_reduce.h"
 
 namespace {
@@ -174,36 +174,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_b16_kernel(const WgradB16Args 
 
 int g_wgrad_b16_splits = 0;   // 0: by occupancy (pick_splits); n > 0: n slices (as far as the pixel range has K-steps) — pfk_debug_set_wgrad_b16
 
-// 32-row output-channel blocks per tile: the tallest tile among {4, 2, 1} blocks that pads cout the least
-int pick_cb(int cout) {
-  int best = 4, waste = (cout + 127) / 128 * 128 - cout;
-  const int w2 = (cout + 63) / 64 * 64 - cout, w1 = (cout + 31) / 32 * 32 - cout;
-  if (w2 < waste) { best = 2; waste = w2; }
-  if (w1 < waste) best = 1;
-  return best;
-}
-
-int pick_splits(long long tiles, long long M) {
-  const long long ksteps = (M + KS - 1) / KS;
-  long long s;
-  if (g_wgrad_b16_splits > 0) {
-    s = g_wgrad_b16_splits;
-  } else {
-    s = 1024 / (tiles > 0 ? tiles : 1);
-    const long long max_s = ksteps / 8 > 0 ? ksteps / 8 : 1;      // >= 8 K-steps (512 pixels) per slice
-    if (s > max_s) s = max_s;
-  }
-  if (s > ksteps) s = ksteps;
-  if (s > 64) s = 64;
-  return s < 1 ? 1 : (int)s;
-}
-
-inline int ktot_of(const pfk_conv_b16_desc* d) {
-  int k = 0;
-  for (int s = 0; s < d->num_src; ++s) k += d->kh * d->kw * ((d->src[s].channels + 31) / 32 * 32);
-  return k;
-}
-
 // The part of the plan that needs no pointers: tile height, grid and slices.
 struct Plan { int cb, tiles_m, groups, splits, ktot; long long M; };
 
@@ -220,13 +190,12 @@ bool shape_ok(const pfk_conv_b16_desc* d) {
 
 Plan plan_of(const pfk_conv_b16_desc* d, int with_bias) {
   Plan pl;
-  pl.ktot = ktot_of(d) + (with_bias ? 32 : 0);
+  pl.ktot = pfk_conv_k(d, 32) + (with_bias ? 32 : 0);
   pl.M = (long long)d->B * d->H * d->W;
-  pl.cb = pick_cb(d->cout);
-  pl.tiles_m = (d->cout + 32 * pl.cb - 1) / (32 * pl.cb);
-  const int nch = 4 / pl.cb, chunks = pl.ktot / 32;
-  pl.groups = (chunks + nch - 1) / nch;
-  pl.splits = pick_splits((long long)pl.tiles_m * pl.groups, pl.M);
+  const WgradGrid g = wgrad_grid(d->cout, pl.ktot, wgrad_pick_cb(d->cout));
+  pl.cb = g.cb; pl.tiles_m = g.tiles_m; pl.groups = g.groups;
+  // slices: K-steps of KS pixels (the last one partial), at least 8 (512 pixels) per slice
+  pl.splits = wgrad_pick_splits((long long)g.tiles_m * g.groups, (pl.M + KS - 1) / KS, 8, g_wgrad_b16_splits);
   return pl;
 }
 
@@ -259,15 +228,12 @@ int pfk_conv_wgrad_unpacked_b16(const pfk_conv_b16_desc* d, const int* real_chan
   for (int i = 0; i < d->num_src; ++i) {
     if (!s[i].ptr || real_channels[i] <= 0 || real_channels[i] > s[i].channels) return PFK_ERR_BAD_ARG;
     if (!pfk_aligned16(s[i].ptr)) return PFK_ERR_ALIGNMENT;
-    if (pl.M * s[i].ld * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;       // 32-bit byte offsets
+    if (!pfk_source_fits32(s[i], pl.M, 2)) return PFK_ERR_UNSUPPORTED;       // 32-bit byte offsets
   }
-  if (pl.M * dy_ld * 2 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(pl.M * dy_ld * 2)) return PFK_ERR_UNSUPPORTED;
 
   WgradB16Args a{};
-  a.src0 = s[0].ptr; a.ld0 = s[0].ld; a.ch0 = s[0].channels;
-  if (d->num_src > 1) { a.src1 = s[1].ptr; a.ld1 = s[1].ld; a.ch1 = s[1].channels; }
-  if (d->num_src > 2) { a.src2 = s[2].ptr; a.ld2 = s[2].ld; a.ch2 = s[2].channels; }
-  a.nsrc = d->num_src;
+  pfk_spread_sources(a, d);
   a.dy = dy; a.dy_ld = dy_ld; a.cout = d->cout;
   a.H = d->H; a.W = d->W; a.kh = d->kh; a.kw = d->kw; a.M = pl.M;
   a.with_bias = with_bias;
@@ -275,21 +241,11 @@ int pfk_conv_wgrad_unpacked_b16(const pfk_conv_b16_desc* d, const int* real_chan
   a.px_per_split = ((pl.M + pl.splits - 1) / pl.splits + KS - 1) / KS * KS;
   a.part = static_cast<float*>(workspace);
 
-  UnpackArgs u{};
-  u.part = a.part; u.n = n; u.splits = pl.splits; u.ktot = pl.ktot; u.cout_real = cout_real; u.taps = d->kh * d->kw;
-  u.nseg = d->num_src; u.with_bias = with_bias; u.dw = dw; u.db = db; u.accumulate = accumulate != 0;
-  int first = 0;
-  for (int i = 0; i < d->num_src; ++i) {
-    u.first[i] = first; u.nreal[i] = real_channels[i]; u.cpad[i] = (s[i].channels + 31) / 32 * 32;
-    first += real_channels[i];
-  }
-  u.cin_total = first;
+  const UnpackArgs u = wgrad_unpack_args(d, real_channels, a.part, n, pl.splits, pl.ktot, cout_real, with_bias, dw, db, accumulate);
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)(pl.tiles_m * pl.groups), (unsigned)pl.splits);
-  if (pl.cb == 4) hipLaunchKernelGGL(conv_wgrad_b16_kernel<4>, grid, dim3(256), 0, st, a);
-  else if (pl.cb == 2) hipLaunchKernelGGL(conv_wgrad_b16_kernel<2>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(conv_wgrad_b16_kernel<1>, grid, dim3(256), 0, st, a);
+  wgrad_launch_cb<conv_wgrad_b16_kernel<4>, conv_wgrad_b16_kernel<2>, conv_wgrad_b16_kernel<1>>(pl.cb, grid, st, a);
   const long long total = (long long)cout_real * pl.ktot;
   hipLaunchKernelGGL(wgrad_reduce_unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u);
   return pfk_launch_status();

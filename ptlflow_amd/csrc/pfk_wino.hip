@@ -869,6 +869,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_wino1d_f32_kernel(const Wino
   }
 }
 
+// (not pfk_with_epilogue: its LINEAR / GRU_ZR / GRU_Q order would instantiate, hence emit, the six kernels in another order)
 template <bool VERT>
 static void wino1d_launch_epi(const Wino1dArgs& a, int epilogue, unsigned nblk, hipStream_t st) {
   switch (epilogue) {
@@ -902,14 +903,14 @@ int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
     const pfk_conv_src& s = d->src[i];
     if (!s.ptr || s.channels <= 0 || s.ld < s.channels) return PFK_ERR_BAD_ARG;
     if (s.channels & 7) return PFK_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(s.ptr) & 3u) return PFK_ERR_ALIGNMENT;
-    if (M * s.ld * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
+    if (!pfk_aligned<4>(s.ptr)) return PFK_ERR_ALIGNMENT;
+    if (!pfk_source_fits32(s, M, 4)) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
     ktot += s.channels;
   }
   const int ch = d->epilogue == PFK_EPI_GRU_ZR ? d->cout / 2 : d->cout;
   if (d->epilogue == PFK_EPI_LINEAR) {
     if (!d->out || d->out_coff < 0 || d->out_ld < d->out_coff + d->cout) return PFK_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(d->out) & 3u) return PFK_ERR_ALIGNMENT;
+    if (!pfk_aligned<4>(d->out)) return PFK_ERR_ALIGNMENT;
   } else {
     // the gate epilogues move float4 pieces of rows: hidden width % 4, 16-byte aligned rows
     if (!d->h || !d->aux_z || d->h_ld < ch || (d->epilogue == PFK_EPI_GRU_ZR && (!d->aux_rh || (d->cout & 1))) || (ch & 3))
@@ -919,13 +920,13 @@ int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
         (d->residual && (d->residual_ld & 3)))
       return PFK_ERR_ALIGNMENT;
     // the row walk's 32-bit byte offsets: the context term, h, z and r*h up to the last pixel's last column
-    if ((d->residual && ((M - 1) * d->residual_ld + d->cout) * 4 >= 0x7fffffffLL) || ((M - 1) * d->h_ld + ch) * 4 >= 0x7fffffffLL ||
-        M * ch * 4 >= 0x7fffffffLL)
+    if ((d->residual && !pfk_fits32(((M - 1) * d->residual_ld + d->cout) * 4)) || !pfk_fits32(((M - 1) * d->h_ld + ch) * 4) ||
+        !pfk_fits32(M * ch * 4))
       return PFK_ERR_UNSUPPORTED;
   }
   if (!pfk_aligned16(d->weight)) return PFK_ERR_ALIGNMENT;
   const long long wfloats = pfk_conv_wino1d_weight_floats(ktot, d->cout);
-  if (wfloats * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(wfloats * 4)) return PFK_ERR_UNSUPPORTED;
   Wino1dArgs a{};
   const pfk_conv_src& s0 = d->src[0];
   const pfk_conv_src& s1 = d->src[d->num_src - 1];
@@ -938,7 +939,7 @@ int pfk_conv1d_wino_f32(const pfk_conv_desc* d, pfk_stream_t stream) {
   const long long ntiles = (long long)d->B * (vert ? d->W : d->H) * a.nt;
   a.ncb = (d->cout + WN1 - 1) / WN1;
   const long long nblk = (ntiles + WT - 1) / WT * a.ncb;
-  if (nblk >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(nblk)) return PFK_ERR_UNSUPPORTED;
   a.ntiles = (int)ntiles;
   a.weight = d->weight; a.w_bytes = (unsigned)(wfloats * 4);
   a.bias = d->bias;
@@ -982,31 +983,31 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream, co
   if (d->num_src != 1 || d->kh != 3 || d->kw != 3 || d->stride > 1 || d->epilogue != PFK_EPI_LINEAR)
     return PFK_ERR_UNSUPPORTED;
   if (!res && (d->residual || d->relu_after_residual)) return PFK_ERR_UNSUPPORTED;
-  if (res && (!d->residual || d->residual_ld < d->cout || (reinterpret_cast<uintptr_t>(d->residual) & 3u))) return PFK_ERR_BAD_ARG;
+  if (res && (!d->residual || d->residual_ld < d->cout || !pfk_aligned<4>(d->residual))) return PFK_ERR_BAD_ARG;
   const pfk_conv_src& s = d->src[0];
   if (!s.ptr || !d->weight || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->cout <= 0 || s.channels <= 0 ||
       s.ld < s.channels || d->out_coff < 0 || d->out_ld < d->out_coff + d->cout)
     return PFK_ERR_BAD_ARG;
   if (s.channels & 31) return PFK_ERR_UNSUPPORTED;
-  if (!pfk_aligned16(d->weight) || (reinterpret_cast<uintptr_t>(s.ptr) & 3u) || (reinterpret_cast<uintptr_t>(d->out) & 3u))
+  if (!pfk_aligned16(d->weight) || !pfk_aligned<4>(s.ptr) || !pfk_aligned<4>(d->out))
     return PFK_ERR_ALIGNMENT;
   const long long M = (long long)d->B * d->H * d->W;
   const long long src_bytes = ((M - 1) * s.ld + s.channels) * 4;
   const long long wfloats = pfk_conv_wino_weight_floats(s.channels, d->cout);
-  if (M * s.ld * 4 >= 0x7fffffffLL || wfloats * 4 >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
+  if (!pfk_source_fits32(s, M, 4) || !pfk_fits32(wfloats * 4)) return PFK_ERR_UNSUPPORTED;   // 32-bit byte offsets
   // the epilogue stores (and reads the residual) through buffer descriptors with 32-bit byte offsets from `out` (`residual`)
   const long long out_bytes = ((M - 1) * d->out_ld + d->out_coff + d->cout) * 4;
   const long long res_bytes = res ? ((M - 1) * d->residual_ld + d->cout) * 4 : 0;
-  if (out_bytes >= 0x7fffffffLL || res_bytes >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(out_bytes) || !pfk_fits32(res_bytes)) return PFK_ERR_UNSUPPORTED;
   int ncb = (d->cout + WN - 1) / WN;
   if (d->cout_active > 0 && d->cout_active < d->cout) {
     if (d->cout_active & (WN - 1)) return PFK_ERR_UNSUPPORTED;
     ncb = d->cout_active / WN;
     if (stats) return PFK_ERR_UNSUPPORTED;   // every column's sums are written
   }
-  if (norm && ((reinterpret_cast<uintptr_t>(f->in_mean) | reinterpret_cast<uintptr_t>(f->in_rstd)) & 3u)) return PFK_ERR_ALIGNMENT;
+  if (norm && (!pfk_aligned<4>(f->in_mean) || !pfk_aligned<4>(f->in_rstd))) return PFK_ERR_ALIGNMENT;
   if (stats) {
-    if (reinterpret_cast<uintptr_t>(f->workspace) & 7u) return PFK_ERR_ALIGNMENT;
+    if (!pfk_aligned<8>(f->workspace)) return PFK_ERR_ALIGNMENT;
     if (f->workspace_bytes < pfk_conv_wino_stats_workspace_bytes(d->B, d->H, d->W, d->cout)) return PFK_ERR_BAD_ARG;
   }
   WinoArgs a{};
@@ -1017,7 +1018,7 @@ static int wino_launch(const pfk_conv_desc* d, bool res, pfk_stream_t stream, co
   const long long ntiles = (long long)d->B * a.tpi;
   const long long nbi = wino_blocks_per_image(d->H, d->W);
   const long long nblk = (stats ? d->B * nbi : (ntiles + WT - 1) / WT) * ncb;
-  if (nblk >= 0x7fffffffLL || ntiles >= 0x7fffffffLL) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_fits32(nblk) || !pfk_fits32(ntiles)) return PFK_ERR_UNSUPPORTED;
   a.ntiles = (int)ntiles;
   a.nks = s.channels / WK;
   a.weight = d->weight; a.w_bytes = (unsigned)(wfloats * 4);

@@ -9,33 +9,13 @@ import ctypes
 
 import pytest
 
-import ptlflow_amd
-
-PFK_ERR_ALIGNMENT, PFK_ERR_UNSUPPORTED = -2, -3
-EPI_GRU_ZR, EPI_GRU_Q = 1, 2
-FP = ctypes.c_void_p
-
-
-class Src(ctypes.Structure):
-    _fields_ = [("ptr", FP), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class Desc(ctypes.Structure):      # pfk_conv_desc of include/pfk.h
-    _fields_ = [("src", Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", FP), ("bias", FP), ("cout", ctypes.c_int),
-                ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float), ("out", FP), ("out_ld", ctypes.c_int),
-                ("out_coff", ctypes.c_int), ("h", FP), ("h_ld", ctypes.c_int), ("aux_z", FP), ("aux_rh", FP), ("residual", FP),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int), ("workspace", FP),
-                ("workspace_bytes", ctypes.c_longlong), ("cout_active", ctypes.c_int), ("cout_split", ctypes.c_int)]
+import pfk_ctypes
+from pfk_ctypes import EPI_GRU_Q, EPI_GRU_ZR, PFK_ERR_ALIGNMENT, PFK_ERR_UNSUPPORTED, Desc, Src
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not ptlflow_amd.LIBPFK_PATH.exists():
-        from ptlflow_amd import _build
-        _build.build_all()
-    import torch  # noqa: F401  (load torch's HIP runtime first, as the product does)
-    lib = ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
+    lib = pfk_ctypes.lib()
     lib.pfk_conv1d_wino_f32.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p]
     lib.pfk_conv1d_wino_f32.restype = ctypes.c_int
     return lib

@@ -7,7 +7,8 @@ import re
 
 import pytest
 
-import ptlflow_amd
+import pfk_ctypes
+from pfk_ctypes import Desc as _Desc, Src as _Src
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("pfk_conv2d_wino_norm_f32", "pfk_conv2d_wino_stats_f32", "pfk_conv_wino_stats_workspace_bytes", "pfk_norm_apply_res_f32")
@@ -16,32 +17,13 @@ BAD_ARG, ALIGNMENT, UNSUPPORTED = -1, -2, -3
 
 @pytest.fixture(scope="module")
 def lib():
-    if not ptlflow_amd.LIBPFK_PATH.exists():
-        from ptlflow_amd import _build
-        _build.build_all()
-    import torch  # noqa: F401  (its bundled HIP runtime must be the one in the process)
-    lib = ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
+    lib = pfk_ctypes.lib()
     lib.pfk_conv_wino_stats_workspace_bytes.restype = ctypes.c_longlong
     P, I = ctypes.c_void_p, ctypes.c_int
     lib.pfk_conv2d_wino_norm_f32.argtypes = [P, P, P, I, P]
     lib.pfk_conv2d_wino_stats_f32.argtypes = [P, P, P, I, ctypes.c_float, P, P, P, ctypes.c_longlong, P]
     lib.pfk_norm_apply_res_f32.argtypes = [P, I, P, P, P, I, P, P, I, P, I, I, I, I, I, I, P]
     return lib
-
-
-class _Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _Desc(ctypes.Structure):
-    _fields_ = [("src", _Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("h", ctypes.c_void_p),
-                ("h_ld", ctypes.c_int), ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int),
-                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_longlong), ("cout_active", ctypes.c_int),
-                ("cout_split", ctypes.c_int)]
 
 
 def desc(**kw):

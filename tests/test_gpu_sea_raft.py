@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from pfk_ctypes import Desc as _Desc, DescB16 as _DescB16, Src as _Src, SrcB16 as _SrcB16
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sea_raft_update.pt")
@@ -62,37 +64,6 @@ def test_gelu_epilogue(gpu, M, cin, cout, ws):
     # relu together with the GELU epilogue is a bad argument, not a silent choice
     with pytest.raises(RuntimeError):
         torch.ops.pfk.conv2d([x.to(gpu)], 1, 1, M, 1, 1, wp, b.to(gpu), cout, 3, True, 1.0, out, None, None, None, workspace)
-
-
-class _Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _Desc(ctypes.Structure):
-    _fields_ = [("src", _Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("h", ctypes.c_void_p),
-                ("h_ld", ctypes.c_int), ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int),
-                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_longlong), ("cout_active", ctypes.c_int),
-                ("cout_split", ctypes.c_int)]
-
-
-class _SrcB16(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _DescB16(ctypes.Structure):
-    _fields_ = [("src", _SrcB16 * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("out_bf16", ctypes.c_int),
-                ("h", ctypes.c_void_p), ("h_ld", ctypes.c_int), ("h_b16", ctypes.c_void_p), ("h_b16_ld", ctypes.c_int),
-                ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("residual_ld", ctypes.c_int),
-                ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int), ("residual_bf16", ctypes.c_int),
-                ("batches", ctypes.c_int), ("src_batch_stride", ctypes.c_longlong), ("weight_batch_stride", ctypes.c_longlong),
-                ("out_batch_stride", ctypes.c_longlong), ("residual_batch_stride", ctypes.c_longlong)]
 
 
 def test_gelu_other_entry_points_refuse(gpu):

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from pfk_ctypes import Desc as _Desc, Src as _Src
 
 pytestmark = pytest.mark.gpu
 
@@ -124,21 +125,6 @@ def test_deterministic(gpu):
     a = _wino(src, B, H, W, wt, bias, cout, True, 1.0)
     for _ in range(3):
         assert torch.equal(_wino(src, B, H, W, wt, bias, cout, True, 1.0), a)
-
-
-class _Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _Desc(ctypes.Structure):
-    _fields_ = [("src", _Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("h", ctypes.c_void_p),
-                ("h_ld", ctypes.c_int), ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int),
-                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_longlong), ("cout_active", ctypes.c_int),
-                ("cout_split", ctypes.c_int)]
 
 
 def test_unsupported_arguments_return_the_error_status(gpu):

@@ -8,6 +8,8 @@ import os
 import pytest
 import torch
 
+from pfk_ctypes import DescB16 as _DescB16, SrcB16 as _SrcB16
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sea_raft_update.pt")
 GOLDEN_AUTOCAST = os.path.join(ROOT, "tests", "golden", "sea_raft_update_autocast.pt")
@@ -56,22 +58,6 @@ def test_dwconv_layernorm_b16_argument_checks(lib):
     assert _dw(lib, pa + 8, 384, pb, 384) == ALIGNMENT                # input rows not 16-byte aligned
     assert _dw(lib, pa, 384, pb + 8, 384) == ALIGNMENT                # output rows not 16-byte aligned
     assert _dw(lib, pa, 384, pa, 384) == BAD_ARG                      # out overlaps the input rows
-
-
-class _SrcB16(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _DescB16(ctypes.Structure):      # pfk_conv_b16_desc (include/pfk.h)
-    _fields_ = [("src", _SrcB16 * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("out_bf16", ctypes.c_int),
-                ("h", ctypes.c_void_p), ("h_ld", ctypes.c_int), ("h_b16", ctypes.c_void_p), ("h_b16_ld", ctypes.c_int),
-                ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("residual_ld", ctypes.c_int),
-                ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int), ("residual_bf16", ctypes.c_int),
-                ("batches", ctypes.c_int), ("src_batch_stride", ctypes.c_longlong), ("weight_batch_stride", ctypes.c_longlong),
-                ("out_batch_stride", ctypes.c_longlong), ("residual_batch_stride", ctypes.c_longlong)]
 
 
 def test_conv2d_gelu_b16_argument_checks(lib):

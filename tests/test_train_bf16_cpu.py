@@ -8,36 +8,17 @@ import re
 import pytest
 import torch
 
-import ptlflow_amd
+import pfk_ctypes
+from pfk_ctypes import DescB16 as Desc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("pfk_conv_wgrad_unpacked_b16", "pfk_conv_wgrad_unpacked_b16_workspace_bytes", "pfk_debug_set_wgrad_b16")
 BAD_ARG = -1
 
 
-class Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class Desc(ctypes.Structure):      # pfk_conv_b16_desc (include/pfk.h)
-    _fields_ = [("src", Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("out_bf16", ctypes.c_int),
-                ("h", ctypes.c_void_p), ("h_ld", ctypes.c_int), ("h_b16", ctypes.c_void_p), ("h_b16_ld", ctypes.c_int),
-                ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int),
-                ("residual_bf16", ctypes.c_int), ("batches", ctypes.c_int), ("src_batch_stride", ctypes.c_longlong),
-                ("weight_batch_stride", ctypes.c_longlong), ("out_batch_stride", ctypes.c_longlong),
-                ("residual_batch_stride", ctypes.c_longlong)]
-
-
 @pytest.fixture(scope="module")
 def lib():
-    if not ptlflow_amd.LIBPFK_PATH.exists():
-        from ptlflow_amd import _build
-        _build.build_all()
-    lib = ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
+    lib = pfk_ctypes.lib()
     lib.pfk_conv_wgrad_unpacked_b16_workspace_bytes.restype = ctypes.c_longlong
     lib.pfk_conv_wgrad_unpacked_b16_workspace_bytes.argtypes = [ctypes.POINTER(Desc), ctypes.c_int]
     lib.pfk_conv_wgrad_unpacked_b16.restype = ctypes.c_int

@@ -7,7 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import ptlflow_amd
+import pfk_ctypes
+from pfk_ctypes import Desc as _Desc, Src as _Src
 from ptlflow_amd.packing import WINO1D_G, pack_wino1d_weight, wino_slot
 
 G = torch.tensor(WINO1D_G, dtype=torch.float64)
@@ -171,25 +172,7 @@ def test_fp32_emulation_meets_the_engine_gate(model):
 
 @pytest.fixture(scope="module")
 def lib():
-    if not ptlflow_amd.LIBPFK_PATH.exists():
-        from ptlflow_amd import _build
-        _build.build_all()
-    return ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
-
-
-class _Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("ld", ctypes.c_int), ("channels", ctypes.c_int)]
-
-
-class _Desc(ctypes.Structure):
-    _fields_ = [("src", _Src * 3), ("num_src", ctypes.c_int), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
-                ("kh", ctypes.c_int), ("kw", ctypes.c_int), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p),
-                ("cout", ctypes.c_int), ("epilogue", ctypes.c_int), ("relu", ctypes.c_int), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("out_ld", ctypes.c_int), ("out_coff", ctypes.c_int), ("h", ctypes.c_void_p),
-                ("h_ld", ctypes.c_int), ("aux_z", ctypes.c_void_p), ("aux_rh", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("residual_ld", ctypes.c_int), ("stride", ctypes.c_int), ("relu_after_residual", ctypes.c_int),
-                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_longlong), ("cout_active", ctypes.c_int),
-                ("cout_split", ctypes.c_int)]
+    return pfk_ctypes.lib()
 
 
 def test_weight_size_helper(lib):
