@@ -1,6 +1,8 @@
 """The one ctypes mirror of include/pfk.h's convolution descriptors for the tests that call libpfk.so's C ABI directly.
 `tests/test_capi_status_table.py::test_ctypes_mirror_matches_header` compares every size and offset here with the header's."""
 import ctypes
+import os
+import re
 
 PFK_OK, PFK_ERR_BAD_ARG, PFK_ERR_ALIGNMENT, PFK_ERR_UNSUPPORTED, PFK_ERR_LAUNCH, PFK_ERR_DISABLED = 0, -1, -2, -3, -4, -5
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q, EPI_LINEAR_GELU = 0, 1, 2, 3
@@ -30,6 +32,13 @@ class DescB16(ctypes.Structure):   # pfk_conv_b16_desc
                 ("residual", _P), ("residual_ld", _I), ("stride", _I), ("relu_after_residual", _I), ("residual_bf16", _I),
                 ("batches", _I), ("src_batch_stride", _LL), ("weight_batch_stride", _LL), ("out_batch_stride", _LL),
                 ("residual_batch_stride", _LL)]
+
+
+def declared():
+    """every function name include/pfk.h declares (comments stripped)"""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pfk.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(pfk_[a-z0-9_]+)\s*\(", src)))
 
 
 def lib():

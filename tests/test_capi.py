@@ -7,6 +7,7 @@ import re
 import pytest
 
 import ptlflow_amd
+from pfk_ctypes import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,12 +19,6 @@ def lib():
         _build.build_all()
     import torch  # noqa: F401  (load torch's HIP runtime first, as the product does)
     return ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
-
-
-def declared():
-    src = open(os.path.join(ROOT, "include", "pfk.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pfk_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_exports_every_declared_symbol(lib):

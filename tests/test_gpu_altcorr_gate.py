@@ -3,7 +3,7 @@ window-sharing MFMA kernel on 8x4 / 8x8 patches, the overflow kernel, the plan k
 variant of each, and the atomics-based backward.  Every forward case runs with each kernel forced (`debug_set_altcorr` 1, 2, 3, 4)
 on fp32 and on bf16 maps.
 
-Gates (tests/test_gpu_raft_bwd_kernels.py's `gates`, tests/test_gpu_sea_train.py's `OP_TOL`, `SENTINEL`, `rel`):
+Gates (tests/op_gate.py's `gates`, `OP_TOL`, `SENTINEL`, `rel`, `guarded`):
  1. relative L2 <= 5e-6 against float64 on the CPU ON THE KERNEL'S OWN INPUTS (for bf16 maps: the bf16-rounded values), over the
     cells whose float64 reference is finite.  Forward reference: `oracle.raft_oracle.alt_corr_forward` on `.double()` copies —
     `floor(x)` and `x - floor(x)` of an fp32 value are exact in both precisions, so the tap positions are the kernel's and
@@ -75,32 +75,18 @@ import pytest
 import torch
 
 from oracle import raft_oracle as O
-from test_gpu_raft_bwd_kernels import U, flat_out, gates, tail_kept
-from test_gpu_sea_train import OP_TOL, SENTINEL, rel
+from op_gate import OP_TOL, SENTINEL, U, flat_out, gates, guarded, rel, tail_kept
 
 pytestmark = pytest.mark.gpu
 NAN, INF = float("nan"), float("inf")
 MODES = (1, 2, 3, 4)                    # per-pixel | window-sharing 8x4 | 8x8 | the overflow kernel on every patch
 DTYPES = (torch.float32, torch.bfloat16)
-GUARD = 64
 WS_NP_MAX = 512
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # harness
 # ---------------------------------------------------------------------------------------------------------------------
-def guarded(t, gpu):
-    """`t` as a contiguous 16-byte-aligned view in the middle of a NaN-filled flat buffer, >= 64 elements of guard on each side"""
-    assert t.dtype in (torch.float32, torch.bfloat16)
-    n = t.numel()
-    flat = torch.full((n + 2 * GUARD + 8,), NAN, dtype=t.dtype, device=gpu)
-    view = flat[GUARD:GUARD + n].view(t.shape)
-    view.copy_(t)
-    assert view.is_contiguous() and view.data_ptr() % 16 == 0
-    assert bool(torch.isnan(flat[:GUARD]).all()) and bool(torch.isnan(flat[GUARD + n:]).all())
-    return view
-
-
 def grid_xy(B, H, W):
     """[B, 1, H, W, 2] (x, y): the identity coordinate field of an H x W map"""
     return O.coords_grid(B, H, W).permute(0, 2, 3, 1)[:, None].contiguous()

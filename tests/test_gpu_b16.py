@@ -14,20 +14,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import pm, unpm
 
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 BF = torch.bfloat16
-
-
-def pm(x):     # NCHW -> pixel-major [B*H*W, C]
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous()
-
-
-def unpm(x, B, H, W):
-    return x.reshape(B, H, W, -1).permute(0, 3, 1, 2).float().cpu()
 
 
 def r16(x):    # round to bf16, keep fp32 storage
@@ -84,7 +76,7 @@ def test_conv_b16_linear(gpu, cfg, B, H, W, segs, cout, kh, kw, relu, out_b16):
         torch.ops.pfk.conv2d_b16(srcs, B, H, W, kh, kw, pack16(wt, offs), bias.cuda(), cout, EPI_LINEAR, relu, 0.25, out)
     finally:
         torch.ops.pfk.debug_set_b16(0)
-    close_b16(unpm(out, B, H, W), ref, out_b16)
+    close_b16(unpm(out, B, H, W).float(), ref, out_b16)
     assert bool((obuf[:, :8] == 5.0).all()) and bool((obuf[:, 8 + cout:] == 5.0).all()), "wrote outside its channel slice"
 
 
@@ -101,7 +93,7 @@ def test_conv_b16_padding_rows_are_zero_filled(gpu):
     big[W + 1: W + 1 + M] = pm(x).to(gpu, BF)
     out = torch.zeros(M, cout, device=gpu, dtype=BF)
     torch.ops.pfk.conv2d_b16([big[W + 1: W + 1 + M]], B, H, W, 3, 3, pack16(wt, [(0, cin, cin)]), None, cout, EPI_LINEAR, False, 1.0, out)
-    close_b16(unpm(out, B, H, W), ref, True)
+    close_b16(unpm(out, B, H, W).float(), ref, True)
 
 
 @pytest.mark.parametrize("B,H,W,Ch,Cm,passes", [
@@ -138,11 +130,11 @@ def test_gru_b16(gpu, B, H, W, Ch, Cm, passes):
         torch.ops.pfk.conv2d_b16([hxb[:, :Ch], hxb[:, Ch:]], B, H, W, kh, kw, pack16(torch.cat([wz, wr], 0), segs), None, 2 * Ch,
                                  EPI_GRU_ZR, False, 1.0, None, None, hxb[:, :Ch], z, rh, pm(ctx_zr).to(gpu, BF))
         # (the hardware exp / rcp of the gate epilogues are ~1 ulp each: far inside half a bf16 ulp)
-        assert (unpm(z, B, H, W) - zz).abs().max() <= 2.0 ** -8
-        assert (unpm(rh, B, H, W) - rr * hb).abs().max() <= 2.0 ** -8
+        assert (unpm(z, B, H, W).float() - zz).abs().max() <= 2.0 ** -8
+        assert (unpm(rh, B, H, W).float() - rr * hb).abs().max() <= 2.0 ** -8
         torch.ops.pfk.conv2d_b16([rh, hxb[:, Ch:]], B, H, W, kh, kw, pack16(wq, segs), None, Ch, EPI_GRU_Q, False, 1.0, None,
                                  hx32, hxb[:, :Ch], z, None, pm(ctx_q).to(gpu, BF))
-    got = unpm(hx32, B, H, W)
+    got = unpm(hx32, B, H, W).float()
     # z / r*h may round to the neighbouring bf16 value (1 ulp = 2^-8 relative) where the GPU's accumulation order lands on the other
     # side of a rounding boundary: that moves h by <= 2^-8 |q - h| per pass
     assert (got - href).abs().max() <= 1.2e-2
@@ -315,7 +307,7 @@ def test_conv_b16_strided(gpu, cin, cout, k, stride, H, W):
     out = torch.zeros(B * Ho * Wo, cout, device=gpu, dtype=BF)
     torch.ops.pfk.conv2d_b16([pm(x).to(gpu, BF)], B, H, W, k, k, pack16(wt, [(0, cin, cin)]), bias.cuda(), cout, EPI_LINEAR, True, 1.0, out,
                              None, None, None, None, pm(res).to(gpu, BF), stride, True)
-    close_b16(unpm(out, B, Ho, Wo), ref, True)
+    close_b16(unpm(out, B, Ho, Wo).float(), ref, True)
 
 
 @pytest.mark.parametrize("norm,small", [("instance", False), ("batch", False), ("instance", True), ("none", True)])

@@ -8,12 +8,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import pm
+
 pytestmark = pytest.mark.gpu
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous()
 
 
 def cases(n, seed):

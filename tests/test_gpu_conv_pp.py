@@ -14,15 +14,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import pm
+
 pytestmark = pytest.mark.gpu
 
 PP = {"swz3_xcd": 53, "pad2_xcd": 52, "swz3": 51, "swz2_xcd": 50 + 1 + 2 + 8, "swz3_xcd_whole": 53 + 16, "pad2_whole": 50 + 16}
 TILES = {"64x64_swz": 10, "64x128_swz": 11, "128x64_swz": 12, "128x128_swz": 13}
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous()
 
 
 def _cases():

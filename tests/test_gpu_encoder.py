@@ -10,24 +10,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import close, pm, unpm
 
 pytestmark = pytest.mark.gpu
-
-
-def close(a, b, rtol=2e-5, atol=2e-5):
-    a, b = a.float().cpu(), b.float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    assert bool((err <= tol).all()), f"max err {err.max().item():.3e} (ref max {b.abs().max().item():.3e})"
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().cuda()
-
-
-def unpm(x, B, H, W):
-    return x.view(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 @pytest.mark.parametrize("kernel", ["mfma", "valu", "mfma_bf16_out"])
@@ -78,7 +63,7 @@ def test_strided_conv(gpu, nsplit, B, H, W, cin, cout, k, stride):
     packed = pack_conv_weight(wt, [(0, cin, cin)])
     w = (packed if nsplit == 0 else split_bf16_planes(packed, nsplit)).cuda()
     out = torch.zeros(B * Ho * Wo, cout, device=gpu)
-    torch.ops.pfk.conv2d([pm(x)], B, H, W, k, k, w, bias.cuda(), cout, 0, True, 1.0, out, None, None, None, None, pm(res),
+    torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, k, k, w, bias.cuda(), cout, 0, True, 1.0, out, None, None, None, None, pm(res, "cuda"),
                          stride, True)
     close(unpm(out, B, Ho, Wo), ref)
 
@@ -94,14 +79,14 @@ def test_instance_norm(gpu, B, H, W, C):
     ws = torch.empty(ops.instnorm_workspace_bytes(B, C), device=gpu, dtype=torch.uint8)
     mean = torch.empty(B * C, device=gpu)
     rstd = torch.empty(B * C, device=gpu)
-    xp = pm(x)
+    xp = pm(x, "cuda")
     ops.instnorm_stats(xp, B, H * W, 1e-5, mean, rstd, ws)
     close(mean.view(B, C), x.mean(dim=(2, 3)), rtol=1e-5, atol=1e-6)
     close(rstd.view(B, C), 1.0 / torch.sqrt(x.var(dim=(2, 3), unbiased=False) + 1e-5), rtol=1e-5, atol=1e-6)
     out = torch.empty_like(xp)
     ops.norm_apply(xp, mean, rstd, None, out, B, H * W, True, False)
     close(unpm(out, B, H, W), ref1, rtol=1e-5, atol=1e-5)
-    ops.norm_apply(xp, mean, rstd, pm(res), xp, B, H * W, True, True)     # in place, with the residual
+    ops.norm_apply(xp, mean, rstd, pm(res, "cuda"), xp, B, H * W, True, True)     # in place, with the residual
     close(unpm(xp, B, H, W), ref2, rtol=1e-5, atol=1e-5)
 
 

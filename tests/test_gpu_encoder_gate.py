@@ -2,7 +2,7 @@
 two-image `stem2`), the stem weight gradient, the instance-norm statistics on fp32 and bf16 rows, `norm_apply` in its four
 instantiations, `norm_apply_res` and the norm backward — all twelve C entry points, through `torch.ops.pfk`.
 
-Gates on every kernel output (tests/test_gpu_raft_bwd_kernels.py's `gates`, tests/test_gpu_sea_train.py's `Rows`, `OP_TOL`, `SENTINEL`):
+Gates on every kernel output (tests/op_gate.py's `gates`, `gates_b16`, `Rows`, `OP_TOL`, `SENTINEL`):
  1. relative L2 <= 5e-6 against float64 on the CPU ON THE KERNEL'S OWN INPUTS (bf16 rows: the bf16 values; `mean` / `rstd` of the
     apply and backward kernels: the fp32 tensors the kernel gets).  A bf16 OUTPUT cannot meet 5e-6 (one rounding to 8 significand bits
     is 2^-9 on average); it must instead be, bit for bit, the round-to-nearest-even bf16 of the fp32 output of the same kernel body on
@@ -80,67 +80,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_raft_bwd_kernels import U, flat_out, gates, tail_kept
-from test_gpu_sea_train import SENTINEL, Rows, rel
+from op_gate import SENTINEL, Rows, flat_out, gates, gates_b16, guarded, record, same_bits, tail_kept
 
 pytestmark = pytest.mark.gpu
 NAN, INF = float("nan"), float("inf")
 F32, B16 = torch.float32, torch.bfloat16
-U16 = 2.0 ** -8                              # unit roundoff of bfloat16
 D = 2.0 ** -29                               # 2^-53 in units of 2^-24
 EPS = 1e-5
 EPS_D = float(torch.tensor(EPS, dtype=F32))  # what the kernels add to the variance: float32(eps), widened
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# harness
-# ---------------------------------------------------------------------------------------------------------------------
-class Rows16(Rows):
-    """`Rows` in bfloat16 (the sentinel, 3 * 2^12, is a bf16 value)"""
-
-    def __init__(self, M, C, gpu, values=None, pad=4):
-        super().__init__(M, C, gpu, None, pad)
-        self.flat = self.flat.to(B16)
-        self.full = self.flat[:M * self.ld].view(M, self.ld)
-        self.rows = self.full[:, :C]
-        if values is not None:
-            self.full.fill_(NAN)
-            self.rows.copy_(values)
-
-
-def make_rows(dtype, *args, **kw):
-    return (Rows16 if dtype == B16 else Rows)(*args, **kw)
-
-
-def guarded(t, gpu):
-    """`t` on the GPU as a contiguous view in the middle of a NaN-filled flat buffer, 64 floats on each side"""
-    flat = torch.full((t.numel() + 128,), NAN, device=gpu)
-    v = flat[64:64 + t.numel()].view(t.shape)
-    v.copy_(t)
-    return v
-
-
-def gates_b16(what, got, twin, ref, mag, k):
-    """a bf16 output: the rounding of its fp32 twin bit for bit (gate 1, see the module docstring) and gate 2 with the bf16 rounding"""
-    assert got.dtype == B16 and twin.dtype == F32
-    same = got == twin.to(B16)
-    assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} values are not the bf16 rounding of the fp32 kernel's"
-    got, ref, mag = got.double().cpu(), ref.double(), mag.double()
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
-    bound = k * U * mag * (1 + U16) + U16 * ref.abs()
-    err, zero = (got - ref).abs(), bound == 0
-    assert bool((got[zero] == 0).all()), f"{what}: elements that are exact zeros by contract are not"
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    r = rel(got, ref)
-    print(f"{what}: relL2 {r:.2e}  worst |err| / bound {ratio:.3f}")
-    assert ratio <= 1.0, f"{what}: per-element error {ratio:.3f} x the bound"
-    return r, ratio
-
-
-def record(name, results):
-    """one line per output kind for the module docstring: the worst of `results` [(relative L2, ratio to the bound), ...]"""
-    if results:
-        print(f"RECORD {name}: {max(r for r, _ in results):.1e} | {max(q for _, q in results):.3f}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -209,7 +156,7 @@ def stem_launcher(c, gpu, B, H, W, cout):
     xg, w = guarded(c["x"], gpu), c["w"].to(gpu)
 
     def launch(bias, relu, dtype):
-        out = make_rows(dtype, B * Ho * Wo, cout, gpu)
+        out = Rows(B * Ho * Wo, cout, gpu, dtype=dtype)
         torch.ops.pfk.conv_stem(xg, w, bias, out.rows, relu)
         return out
     return launch
@@ -256,7 +203,7 @@ def stem2_launcher(source, gpu, B, H, W):
         a, b = guarded(c["x"][:, :3].contiguous(), gpu), guarded(c["x"][:, 3:].contiguous(), gpu)
 
     def launch(bias, relu, dtype):
-        out = make_rows(dtype, B * Ho * Wo, 64, gpu)
+        out = Rows(B * Ho * Wo, 64, gpu, dtype=dtype)
         torch.ops.pfk.conv_stem2(a, b, w, bias, out.rows, relu)
         return out
     return c, launch
@@ -468,7 +415,7 @@ def test_instnorm_stats(gpu, B, HW, C, dtype):
     x[b_nan, HW - 1, c_nan], x[b_inf, HW // 2, c_inf] = NAN, INF
     bad[b_nan, c_nan] = bad[b_inf, c_inf] = True
     x = x.to(dtype)
-    rows = make_rows(dtype, B * HW, C, gpu, x.view(B * HW, C).to(gpu))
+    rows = Rows(B * HW, C, gpu, x.view(B * HW, C).to(gpu), dtype=dtype)
     need = ops.instnorm_workspace_bytes(B, C)
     assert need == (2 * B * in_chunks(B) * C + 2 * B * C) * 8
 
@@ -524,10 +471,6 @@ def per_pixel(t, B, HW, C):
     return t.double().view(B, 1, C).expand(B, HW, C).reshape(B * HW, C)
 
 
-def same_bits(a, b):
-    return torch.equal(a.view(torch.int16 if a.dtype == B16 else torch.int32), b.view(torch.int16 if b.dtype == B16 else torch.int32))
-
-
 @pytest.mark.parametrize("B,HW,C", NORM_SHAPES)
 def test_norm_apply(gpu, B, HW, C):
     """fp32 rows: no residual, an fp32 residual, in place (as the encoders call it).  Row strides C + 4 (x), C + 8 (residual),
@@ -579,8 +522,8 @@ def test_norm_apply_b16(gpu, B, HW, C):
         key = "x16" if x_dtype == B16 else "x"
         mean, rstd = c[key + "_mean"].to(gpu), c[key + "_rstd"].to(gpu)
         y = (x.double() - per_pixel(c[key + "_mean"], B, HW, C)) * per_pixel(c[key + "_rstd"], B, HW, C)
-        xr, xw = make_rows(x_dtype, M, C, gpu, x.to(gpu)), Rows(M, C, gpu, x.float().to(gpu))
-        rr, rw = Rows16(M, C, gpu, res16.to(gpu), pad=8), Rows(M, C, gpu, res16.float().to(gpu), pad=8)
+        xr, xw = Rows(M, C, gpu, x.to(gpu), dtype=x_dtype), Rows(M, C, gpu, x.float().to(gpu))
+        rr, rw = Rows(M, C, gpu, res16.to(gpu), pad=8, dtype=B16), Rows(M, C, gpu, res16.float().to(gpu), pad=8)
         for relu in (True, False):
             y1 = y.clamp_min(0) if relu else y
             for with_res, relu2 in ((False, False), (True, False), (True, True)):
@@ -592,7 +535,7 @@ def test_norm_apply_b16(gpu, B, HW, C):
                 ops.norm_apply(xw.rows, mean, rstd, rw.rows if with_res else None, twin.rows, B, HW, relu, relu2)
 
                 def run(inplace=False):
-                    out = Rows16(M, C, gpu, x.to(gpu)) if inplace else Rows16(M, C, gpu, pad=12)
+                    out = Rows(M, C, gpu, x.to(gpu), dtype=B16) if inplace else Rows(M, C, gpu, pad=12, dtype=B16)
                     ops.norm_apply(xr.rows if not inplace else out.rows, mean, rstd, rr.rows if with_res else None, out.rows, B, HW, relu, relu2)
                     return out
 

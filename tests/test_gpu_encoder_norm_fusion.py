@@ -22,6 +22,8 @@ import functools
 import pytest
 import torch
 
+from op_gate import close
+
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-5
@@ -46,12 +48,6 @@ def _stats(ops, x, B, HW):
     ws = torch.empty(ops.instnorm_workspace_bytes(B, C), device=x.device, dtype=torch.uint8)
     ops.instnorm_stats(x, B, HW, EPS, mean, rstd, ws)
     return mean, rstd
-
-
-def close(a, b, rtol, atol):
-    a, b = a.double().cpu(), b.double().cpu()
-    err, tol = (a - b).abs(), atol + rtol * b.abs()
-    assert bool((err <= tol).all()), f"max excess {(err - tol).max().item():.3e}, max err {err.max().item():.3e}"
 
 
 @pytest.mark.parametrize("relu", [True, False])
@@ -106,8 +102,8 @@ def test_statistics_in_the_epilogue(gpu, shape, norm, big_mean):
     if big_mean:
         m, s = o64[:, :, 3].mean(), o64[:, :, 3].std()
         assert abs(m) > 9e3 * s, (m, s)
-    close(mean.view(B, C), o64.mean(dim=1), rtol=1e-5, atol=1e-6)
-    close(rstd.view(B, C), 1.0 / torch.sqrt(o64.var(dim=1, unbiased=False) + EPS), rtol=1e-5, atol=1e-6)
+    close(mean.view(B, C), o64.mean(dim=1), rtol=1e-5, atol=1e-6, dtype=torch.float64)
+    close(rstd.view(B, C), 1.0 / torch.sqrt(o64.var(dim=1, unbiased=False) + EPS), rtol=1e-5, atol=1e-6, dtype=torch.float64)
     pm, pr = _stats(ops, ref, B, H * W)
     print(f"[{shape} norm={norm} big_mean={big_mean}] values that differ from instnorm_stats: mean {(pm != mean).sum().item()}, "
           f"rstd {(pr != rstd).sum().item()} of {B * C}")

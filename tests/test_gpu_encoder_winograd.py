@@ -14,20 +14,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import pm, unpm
 
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR = 0
 RATIO = 4.0
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().cuda()
-
-
-def unpm(x, B, H, W):
-    return x.reshape(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 @pytest.mark.parametrize("form", ["plain", "relu", "res"])
@@ -45,7 +37,7 @@ def test_kernels_at_encoder_shapes(gpu, B, H, W, C, form):
     if form == "res":
         ref = F.relu(res.double() + ref)
     ops = torch.ops.pfk
-    src, r = pm(x), pm(res)
+    src, r = pm(x, "cuda"), pm(res, "cuda")
     ow = torch.zeros(B * H * W, C, device=gpu)
     od = torch.zeros(B * H * W, C, device=gpu)
     ww, wd = pack_wino_weight(wt).cuda(), pack_conv_weight(wt, [(0, C, C)]).cuda()

@@ -12,27 +12,17 @@ import pytest
 import torch
 
 from oracle import raft_oracle as O
+from op_gate import OP_TOL, SENTINEL, bits, rel, round_up
 
 pytestmark = pytest.mark.gpu
-OP_TOL = 5e-6
 FACTOR = 2.0
 BF16 = torch.bfloat16
-
-
-def rel(a, b):
-    b = b.detach().double().cpu()
-    return float((a.detach().double().cpu() - b).norm() / b.norm().clamp_min(1e-300))
-
-
-def round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. pfk_softmax_rows_bwd_{f32,bf16}
 # ---------------------------------------------------------------------------------------------------------------------
 SOFTMAX_CASES = [(2 * 140, 140, 140), (2 * 140, 140, 144), (64, 396, 396), (8, 713, 716), (4, 1, 4)]
-SENTINEL = 12288.0        # exact in bf16 too
 
 
 def _softmax_inputs(rows, cols, ld, gpu):
@@ -93,10 +83,6 @@ def test_softmax_rows_bwd(gpu, rows, cols, ld):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. pfk_transpose_pack_{f32,b16}
 # ---------------------------------------------------------------------------------------------------------------------
-def _bits(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
 @pytest.mark.parametrize("B,N,ld_in,extra", [(2, 128, 128, 0), (2, 140, 145, 0), (2, 140, 140, 64), (2, 396, 396, 0), (1, 713, 713, 0)])
 def test_transpose_pack(gpu, B, N, ld_in, extra):
     ops = torch.ops.pfk
@@ -120,11 +106,11 @@ def test_transpose_pack(gpu, B, N, ld_in, extra):
             flat_o = torch.full((n + 64,), SENTINEL, device=gpu, dtype=dtype)
             outT, out = flat_t[:n].view(B, N, ld), flat_o[:n].view(B, N, ld)
             ops.transpose_pack(xg, outT, out if with_out else None)
-            assert torch.equal(_bits(outT[:, :, :N].cpu().contiguous()), _bits(want_t)), (dtype, "outT")
+            assert torch.equal(bits(outT[:, :, :N].cpu().contiguous()), bits(want_t)), (dtype, "outT")
             assert bool((outT[:, :, N:] == 0).all()), "pad columns of outT must be zero"
             assert bool((flat_t[n:] == SENTINEL).all())
             if with_out:
-                assert torch.equal(_bits(out[:, :, :N].cpu().contiguous()), _bits(want)), (dtype, "out")
+                assert torch.equal(bits(out[:, :, :N].cpu().contiguous()), bits(want)), (dtype, "out")
                 assert bool((out[:, :, N:] == 0).all()), "pad columns of out must be zero"
             else:
                 assert bool((flat_o == SENTINEL).all()), "out was written although none was given"

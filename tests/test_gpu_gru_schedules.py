@@ -20,7 +20,9 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from op_gate import close32, within_ulp
+from op_refs import conv64, ref_q, ref_zr
 
 pytestmark = pytest.mark.gpu
 
@@ -56,55 +58,6 @@ def _widths(spec, b16):
     row = round_up(spec.hidden + spec.x_channels, 8) if b16 else spec.hx_channels
     Ch, Ci = spec.hidden, spec.context
     return Ch, Ci, spec.x_channels - Ci, row - Ch - Ci, row
-
-
-def _ulp_bf16(v):
-    a = v.abs().double().clamp_min(2.0 ** -126)
-    return torch.pow(2.0, torch.floor(torch.log2(a)) - 7)
-
-
-def _within_ulp(got, ref, what):
-    """|got - bf16(ref)| <= 1 bf16 ulp of ref + 2^-16; returns the worst err / limit"""
-    err = (got.double().cpu() - ref.to(BF).double()).abs()
-    lim = _ulp_bf16(ref) + 2.0 ** -16
-    ratio = float((err / lim).max())
-    assert bool((err <= lim).all()), f"{what}: {int((err > lim).sum())} of {err.numel()} over one bf16 ulp, worst ratio {ratio:.2f}"
-    return ratio
-
-
-def _close32(got, ref, what):
-    """|got - ref| <= 3e-5 + 2e-5 |ref|; returns the worst err / limit"""
-    err = (got.double().cpu() - ref).abs()
-    lim = 3e-5 + 2e-5 * ref.abs()
-    ratio = float((err / lim).max())
-    assert bool((err <= lim).all()), f"{what}: {int((err > lim).sum())} of {err.numel()} outside 3e-5 + 2e-5|ref|, worst ratio {ratio:.2f}"
-    return ratio
-
-
-def _conv64(srcs, reals, weight, bias, res, b, h, w, kh, kw):
-    """fp64 'same' convolution of pixel-major rows: cat(src[:, :real]) x weight [cout, sum(reals), kh, kw] + bias + res, [M, cout]"""
-    x = torch.cat([s.cpu()[:, :r].double() for s, r in zip(srcs, reals)], 1)
-    x = x.reshape(b, h, w, -1).permute(0, 3, 1, 2)
-    v = F.conv2d(x, weight.double(), padding=(kh // 2, kw // 2)).permute(0, 2, 3, 1).reshape(b * h * w, -1)
-    if bias is not None:
-        v = v + bias.double().cpu()
-    if res is not None:
-        v = v + res.double().cpu()
-    return v
-
-
-def ref_zr(srcs, reals, weight, bias, res, h_rows, shape, k):
-    """z = sigmoid(v[:, :Ch]), r*h = sigmoid(v[:, Ch:]) * h, v = conv + bias + residual (K8b: h is the bf16 twin)"""
-    v = _conv64(srcs, reals, weight, bias, res, *shape, *k)
-    Ch = v.shape[1] // 2
-    return torch.sigmoid(v[:, :Ch]), torch.sigmoid(v[:, Ch:]) * h_rows.double().cpu()
-
-
-def ref_q(srcs, reals, weight, bias, res, z_rows, h_rows, shape, k):
-    """h' = (1 - z) h + z tanh(conv + bias + residual), on the z the z|r launch stored and the fp32 h"""
-    v = _conv64(srcs, reals, weight, bias, res, *shape, *k)
-    z, h = z_rows.double().cpu(), h_rows.double().cpu()
-    return (1 - z) * h + z * torch.tanh(v)
 
 
 def _report(tag, **ratios):
@@ -219,8 +172,8 @@ def test_f32_gates_every_schedule(gpu, cfg, wset, with_ctx):
     _pad_rows_untouched(t)
     zr_in = [act0[:, :Ch], act0[:, Ch + t["Ci"]:]]
     z_ref, rh_ref = ref_zr(zr_in, reals, t["wzr"], t["bzr"], t["ctx_zr"], act0[:, :Ch], shape, t["k"])
-    rz = _close32(t["z"][:M], z_ref, "z")
-    rr = _close32(t["rh"][:M], rh_ref, "r*h")
+    rz = close32(t["z"][:M], z_ref, "z")
+    rr = close32(t["rh"][:M], rh_ref, "r*h")
     z1, rh1 = t["z"].clone(), t["rh"].clone()
     _run_f32(t, EPI_GRU_Q, cfg)
     torch.cuda.synchronize()
@@ -228,7 +181,7 @@ def test_f32_gates_every_schedule(gpu, cfg, wset, with_ctx):
     assert torch.equal(t["z"], z1) and torch.equal(t["rh"], rh1), "q wrote into z / r*h"
     q_in = [rh1[:M], act0[:, Ch + t["Ci"]:]]
     h_ref = ref_q(q_in, reals, t["wq"], t["bq"], t["ctx_q"], z1[:M], act0[:, :Ch], shape, t["k"])
-    rq = _close32(t["act"][:, :Ch], h_ref, "h")
+    rq = close32(t["act"][:, :Ch], h_ref, "h")
     if with_ctx:
         assert torch.equal(t["ctx_zr_buf"], ctx0[0]) and torch.equal(t["ctx_q_buf"], ctx0[1]), "wrote into the context rows"
     _report(f"f32 cfg {cfg} {wset}", z=rz, rh=rr, h=rq)
@@ -276,8 +229,8 @@ def test_b16_gates_every_schedule(gpu, cfg, wset, with_ctx, twin):
     _pad_rows_untouched(t)
     zr_in = [act0[:, :Ch], act0[:, Ch + t["Ci"]:]]
     z_ref, rh_ref = ref_zr(zr_in, reals, t["wzr"], t["bzr"], t["ctx_zr"], act0[:, :Ch], shape, t["k"])
-    rz = _within_ulp(t["z"][:M], z_ref, "z")
-    rr = _within_ulp(t["rh"][:M], rh_ref, "r*h")
+    rz = within_ulp(t["z"][:M], z_ref, 2.0 ** -16, "z")
+    rr = within_ulp(t["rh"][:M], rh_ref, 2.0 ** -16, "r*h")
     z1, rh1 = t["z"].clone(), t["rh"].clone()
     if cfg in B16_NO_Q:
         with pytest.raises(RuntimeError):
@@ -292,7 +245,7 @@ def test_b16_gates_every_schedule(gpu, cfg, wset, with_ctx, twin):
     assert torch.equal(t["z"], z1) and torch.equal(t["rh"], rh1), "q wrote into z / r*h"
     q_in = [rh1[:M], act0[:, Ch + t["Ci"]:]]
     h_ref = ref_q(q_in, reals, t["wq"], t["bq"], t["ctx_q"], z1[:M], hx0[:, :Ch], shape, t["k"])
-    rq = _close32(t["hx32"][:, :Ch], h_ref, "h")
+    rq = close32(t["hx32"][:, :Ch], h_ref, "h")
     if twin:
         assert torch.equal(t["act"][:, :Ch], t["hx32"][:, :Ch].to(BF)), "the h twin is not bf16(h)"
     else:
@@ -325,12 +278,12 @@ def test_b16_linear_residual_every_schedule(gpu, cfg, wset, res_dtype, relu2):
     finally:
         torch.ops.pfk.debug_set_b16(0)
     torch.cuda.synchronize()
-    v = _conv64([act0[:, :Ch], act0[:, Ch + t["Ci"]:]], reals, t["wzr"], t["bzr"], None, *shape, *t["k"])
+    v = conv64([act0[:, :Ch], act0[:, Ch + t["Ci"]:]], reals, t["wzr"], t["bzr"], None, *shape, *t["k"])
     ref = res.double() + 0.5 * v.clamp_min(0)
     if relu2:
         ref = ref.clamp_min(0)
     got = obuf[:M, 8: 8 + cout]
-    r = _within_ulp(got, ref, "out") if res_dtype == BF else _close32(got, ref, "out")
+    r = within_ulp(got, ref, 2.0 ** -16, "out") if res_dtype == BF else close32(got, ref, "out")
     assert bool((obuf[M:] == SENTINEL).all()) and bool((obuf[:, :8] == SENTINEL).all()) and bool((obuf[:, 8 + cout:] == SENTINEL).all()), \
         "wrote outside its [M, cout] view"
     assert torch.equal(rbuf, rbuf0) and torch.equal(t["act"], act0), "wrote into an input"
@@ -404,13 +357,13 @@ def test_engine_gate_launches(gpu, path, model, b, h, w, zr_sched, q_sched):
         if epi == EPI_GRU_ZR:
             assert torch.equal(eng.hx, hx0) and (not b16 or torch.equal(eng.hxb, hxb0)), f"{what} wrote into the hx rows"
             z_ref, rh_ref = ref_zr(ins, [Ch, real], weight(key), bias, res0, (hxb0 if b16 else hx0)[:, :Ch], shape, (kh, kw))
-            check = _within_ulp if b16 else _close32
+            check = (lambda got, ref, what: within_ulp(got, ref, 2.0 ** -16, what)) if b16 else close32
             _report(f"{tag} {what}", z=check(eng.zbuf, z_ref, f"{what} z"), rh=check(eng.rh, rh_ref, f"{what} r*h"))
         else:
             assert torch.equal(eng.hx[:, Ch:], hx0[:, Ch:]), f"{what} wrote outside h"
             assert torch.equal(eng.zbuf, z0) and torch.equal(eng.rh, rh0), f"{what} wrote into z / r*h"
             h_ref = ref_q(ins, [Ch, real], weight(key), bias, res0, z0, hx0[:, :Ch], shape, (kh, kw))
-            _report(f"{tag} {what}", h=_close32(eng.hx[:, :Ch], h_ref, f"{what} h"))
+            _report(f"{tag} {what}", h=close32(eng.hx[:, :Ch], h_ref, f"{what} h"))
             if b16:
                 assert torch.equal(eng.hxb[:, Ch:], hxb0[:, Ch:]), f"{what} wrote outside the h twin"
                 assert torch.equal(eng.hxb[:, :Ch], eng.hx[:, :Ch].to(BF)), f"{what}: the h twin is not bf16(h)"

@@ -13,26 +13,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import close, pm, unpm
+from op_refs import coords_cases
 
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
-
-
-def close(a, b, rtol=2e-5, atol=2e-5):
-    a, b = a.float().cpu(), b.float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    assert bool((err <= tol).all()), f"max err {err.max().item():.3e} (ref max {b.abs().max().item():.3e})"
-
-
-def pm(x):  # NCHW cpu -> [M, C] gpu
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().cuda()
-
-
-def unpm(x, B, H, W):
-    return x.view(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 @pytest.mark.parametrize("B,h,w,D", [(1, 16, 24, 64), (2, 9, 13, 128), (1, 55, 128, 256)])
@@ -42,7 +28,7 @@ def test_corr_volume(gpu, B, h, w, D):
     ref = O.all_pairs_correlation(f1, f2)
     N = h * w
     out = torch.empty(B, N, N, device=gpu)
-    torch.ops.pfk.corr_volume(pm(f1).view(B, N, D), pm(f2).view(B, N, D), 1.0 / math.sqrt(D), out)
+    torch.ops.pfk.corr_volume(pm(f1, "cuda").view(B, N, D), pm(f2, "cuda").view(B, N, D), 1.0 / math.sqrt(D), out)
     close(out.view(B * N, 1, h, w), ref, rtol=1e-5, atol=2e-5)
 
 
@@ -56,26 +42,6 @@ def test_pool_bit_exact(gpu, M, H, W):
     assert torch.equal(out.cpu(), ref.view(M, H // 2, W // 2))
 
 
-def _coords_cases(B, h, w):
-    g = torch.Generator().manual_seed(7)
-    c0 = O.coords_grid(B, h, w)
-    yield "integer", c0
-    yield "fractional", c0 + torch.rand(B, 2, h, w, generator=g) * 16 - 8
-    yield "half", c0 + 0.5
-    yield "out_of_bounds", c0 + torch.randn(B, 2, h, w, generator=g) * 80
-    edge = c0.clone()
-    edge[:, 0] = torch.where(edge[:, 0] < w / 2, -0.25, w - 0.75)
-    edge[:, 1] = torch.where(edge[:, 1] < h / 2, -1.0, float(h - 1))
-    yield "edges", edge
-    bad = c0.clone()
-    bad[:, 0, 0, 0] = float("nan")
-    bad[:, 1, 0, 1] = float("inf")
-    bad[:, 0, 1, 0] = -float("inf")
-    bad[:, 0, 1, 1] = 3.0e9
-    bad[:, 1, 1, 2] = -2.5e7
-    yield "nonfinite", bad
-
-
 # (1, 47, 156, …) = KITTI 375×1242, the width with the most grid_sample round-trip index flips; (1, 46, 62, …) = Chairs
 @pytest.mark.parametrize("B,h,w,L,r", [(1, 16, 24, 4, 4), (2, 23, 39, 4, 3), (1, 55, 128, 4, 4), (1, 8, 16, 4, 4), (1, 13, 17, 2, 4),
                                        (1, 47, 156, 4, 4), (1, 46, 62, 4, 4), (1, 47, 156, 4, 3)])
@@ -86,7 +52,7 @@ def test_lookup_bit_exact(gpu, B, h, w, L, r):
     pyr = O.correlation_pyramid(f1, f2, L)
     lv = [p.view(B * h * w, p.shape[-2], p.shape[-1]).contiguous().cuda() for p in pyr]
     n = 2 * r + 1
-    for name, c in _coords_cases(B, h, w):
+    for name, c in coords_cases(B, h, w):
         ref = O.lookup(pyr, c, r)
         out = torch.full((B * h * w, L * n * n), -7.0, device=gpu)
         torch.ops.pfk.corr_lookup(lv, c.cuda(), r, out)
@@ -121,7 +87,7 @@ def test_lookup_blocked_bit_exact(gpu, B, h, w, L, r):
     for pix in (104, 8):         # 104 = always 4 pixels per workgroup, 8 = always 8 (the default picks by the pixel count)
         torch.ops.pfk.debug_set_lookup_pix(pix)
         try:
-            for name, c in _coords_cases(B, h, w):
+            for name, c in coords_cases(B, h, w):
                 ref = O.lookup(pyr, c, r)
                 out = torch.full((B * h * w, L * n * n), -7.0, device=gpu)
                 torch.ops.pfk.corr_lookup_blocked(lv, lh, lw, c.cuda(), r, out)
@@ -144,7 +110,7 @@ def test_lookup_blocked_bf16_maps_bit_exact(gpu, B, h, w, L, r):
     wide = [p.float() for p in pyr]
     lh, lw = [p.shape[-2] for p in pyr], [p.shape[-1] for p in pyr]
     n = 2 * r + 1
-    cases = [(name, c, O.lookup(wide, c, r)) for name, c in _coords_cases(B, h, w)]      # the oracle's answer, once per field
+    cases = [(name, c, O.lookup(wide, c, r)) for name, c in coords_cases(B, h, w)]      # the oracle's answer, once per field
     for fill in (0.0, 9.0):       # whatever the pad elements of the edge tiles hold must not leak into a sample
         lv = []
         for p in pyr:
@@ -209,7 +175,7 @@ def test_corr_block_layouts_agree(gpu, B, h, w, D, L, r, dtype, pyramid):
     assert a.layout == "rowmajor" and b.layout == "blocked" and b._levels[0].dim() == 2
     for pa, pb in zip(a.corr_pyramid, b.corr_pyramid):
         assert pa.shape == pb.shape and torch.equal(pa, pb)
-    for name, c in _coords_cases(B, h, w):
+    for name, c in coords_cases(B, h, w):
         ra, rb = a(c.cuda()), b(c.cuda())
         same = (ra == rb) | (torch.isnan(ra) & torch.isnan(rb))
         assert bool(same.all()), name
@@ -227,7 +193,7 @@ def test_lookup_variants_bit_exact(gpu, variant):
     n = 2 * r + 1
     torch.ops.pfk.debug_set_lookup_pix(variant)
     try:
-        for name, c in _coords_cases(B, h, w):
+        for name, c in coords_cases(B, h, w):
             ref = O.lookup(pyr, c, r)
             out = torch.full((B * h * w, L * n * n), -7.0, device=gpu)
             torch.ops.pfk.corr_lookup(lv, c.cuda(), r, out)
@@ -263,7 +229,7 @@ def test_conv_linear(gpu, B, H, W, cin, cout, kh, kw, relu):
     M = B * H * W
     buf = torch.full((M, cout + 12), 5.0, device=gpu)
     out = buf[:, 4:4 + cout]
-    torch.ops.pfk.conv2d([pm(x)], B, H, W, kh, kw, _packed(wt, [(0, cin, cin)]), bias.cuda(), cout, EPI_LINEAR, relu, 0.25,
+    torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, kh, kw, _packed(wt, [(0, cin, cin)]), bias.cuda(), cout, EPI_LINEAR, relu, 0.25,
                          out, None, None, None)
     close(unpm(out, B, H, W), ref)
     assert bool((buf[:, :4] == 5.0).all()) and bool((buf[:, 4 + cout:] == 5.0).all()), "wrote outside its channel slice"
@@ -280,7 +246,7 @@ def test_conv_all_tile_configs(gpu, tile):
     out = torch.zeros(B * H * W, cout, device=gpu)
     torch.ops.pfk.debug_set_tile(tile)
     try:
-        torch.ops.pfk.conv2d([pm(x)], B, H, W, 3, 3, _packed(wt, [(0, cin, cin)]), bias.cuda(), cout, EPI_LINEAR, False, 1.0,
+        torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, 3, 3, _packed(wt, [(0, cin, cin)]), bias.cuda(), cout, EPI_LINEAR, False, 1.0,
                              out, None, None, None)
     finally:
         torch.ops.pfk.debug_set_tile(-1)
@@ -323,7 +289,7 @@ def test_conv_stream_k(gpu, B, H, W, segs, cout, kh, kw):
     for c in segs:
         offs.append((o, c, c)); o += c
     packed = _packed(wt, offs)
-    srcs = [pm(x) for x in xs]
+    srcs = [pm(x, "cuda") for x in xs]
     M = B * H * W
     ws = torch.zeros(torch.ops.pfk.conv_workspace_bytes(), device=gpu, dtype=torch.uint8)
     outs, split = [], []
@@ -397,10 +363,10 @@ def test_conv_multi_source(gpu):
     bias = torch.randn(cout)
     ref = F.conv2d(torch.cat([a, b[:, :146], c], 1), wt, bias, padding=1)
     wide = torch.zeros(B * H * W, 300, device=gpu)
-    wide[:, 100:248] = pm(b)
+    wide[:, 100:248] = pm(b, "cuda")
     packed = _packed(wt, [(0, ca, ca), (ca, 146, 148), (ca + 146, cc, cc)])
     out = torch.zeros(B * H * W, cout, device=gpu)
-    torch.ops.pfk.conv2d([pm(a), wide[:, 100:248], pm(c)], B, H, W, 3, 3, packed, bias.cuda(), cout, EPI_LINEAR, False, 1.0,
+    torch.ops.pfk.conv2d([pm(a, "cuda"), wide[:, 100:248], pm(c, "cuda")], B, H, W, 3, 3, packed, bias.cuda(), cout, EPI_LINEAR, False, 1.0,
                          out, None, None, None)
     close(unpm(out, B, H, W), ref)
 
@@ -427,7 +393,7 @@ def test_gru(gpu, B, H, W, Ch, Cx, passes):
     ref = O.sepconv_gru(P, h, x) if len(passes) == 2 else O.conv_gru(P, h, x)
     from ptlflow_amd.packing import pack_conv_weight
     M = B * H * W
-    hx = torch.cat([pm(h), pm(x)], 1).contiguous()
+    hx = torch.cat([pm(h, "cuda"), pm(x, "cuda")], 1).contiguous()
     z = torch.zeros(M, Ch, device=gpu)
     rh = torch.zeros(M, Ch, device=gpu)
     for kh, kw, sfx in passes:
@@ -450,7 +416,7 @@ def test_conv_cin2(gpu, k, cout, W):
     ref = F.relu(F.conv2d(flow, wt, bias, padding=k // 2))
     from ptlflow_amd.packing import pack_cin2_weight
     buf = torch.zeros(B * H * W, 384, device=gpu)
-    buf[:, 382:384] = pm(flow)
+    buf[:, 382:384] = pm(flow, "cuda")
     out = torch.zeros(B * H * W, cout, device=gpu)
     torch.ops.pfk.conv_cin2(buf[:, 382:384], pack_cin2_weight(wt).cuda(), bias.cuda(), out, B, H, W, k, True)
     close(unpm(out, B, H, W), ref)
@@ -468,7 +434,7 @@ def test_conv_cin2_mfma_has_the_valu_kernels_bits(gpu, B, H, W, cout):
     bias = torch.randn(cout)
     ref = F.relu(F.conv2d(flow, wt, bias, padding=3))
     buf = torch.zeros(B * H * W, 8, device=gpu)
-    buf[:, 4:6] = pm(flow)
+    buf[:, 4:6] = pm(flow, "cuda")
     w = pack_cin2_weight(wt).cuda()
     for dt in (torch.float32, torch.bfloat16):
         outs = []
@@ -501,7 +467,7 @@ def test_flow_delta(gpu, B, H, W, cin):
     c1 = c0 + torch.randn(B, 2, H, W)
     from ptlflow_amd.packing import pack_flow_head_weight
     fm = torch.zeros(B * H * W, 512, device=gpu)
-    fm[:, :cin] = pm(x)
+    fm[:, :cin] = pm(x, "cuda")
     c1g = c1.clone().cuda()
     delta = torch.zeros(B, 2, H, W, device=gpu)
     hx = torch.zeros(B * H * W, 384, device=gpu)
@@ -522,17 +488,17 @@ def test_convex_upsample(gpu):
     mask = torch.randn(B, 576, H, W)
     ref = O.convex_upsample(flow, mask)
     out = torch.zeros(B, 2, 8 * H, 8 * W, device=gpu)
-    torch.ops.pfk.convex_upsample(flow.cuda(), pm(mask), out)
+    torch.ops.pfk.convex_upsample(flow.cuda(), pm(mask, "cuda"), out)
     close(out, ref, rtol=1e-5, atol=1e-5)
     out2 = torch.zeros_like(out)
     hx = torch.zeros(B * H * W, 384, device=gpu)
-    hx[:, 382:384] = pm(flow)
-    torch.ops.pfk.convex_upsample_pm(hx[:, 382:384], pm(mask), out2)
+    hx[:, 382:384] = pm(flow, "cuda")
+    torch.ops.pfk.convex_upsample_pm(hx[:, 382:384], pm(mask, "cuda"), out2)
     assert torch.equal(out, out2)
     # rows that are not 16-byte aligned take the one-pixel-per-wave kernel: same operation sequence, same bits as the
     # four-pixels-per-wave kernel above
     wide = torch.zeros(B * H * W, 577, device=gpu)
-    wide[:, :576] = pm(mask)
+    wide[:, :576] = pm(mask, "cuda")
     out3 = torch.zeros_like(out)
     torch.ops.pfk.convex_upsample(flow.cuda(), wide[:, :576], out3)
     assert torch.equal(out, out3)
@@ -555,7 +521,7 @@ def test_layout_roundtrip(gpu):
     x = torch.randn(2, 126, 7, 45)
     buf = torch.zeros(2 * 7 * 45, 384, device=gpu)
     torch.ops.pfk.nchw_to_pm(x.cuda(), buf[:, 256:382])
-    assert torch.equal(buf[:, 256:382].cpu(), pm(x).cpu())
+    assert torch.equal(buf[:, 256:382].cpu(), pm(x, "cuda").cpu())
     back = torch.zeros(2, 126, 7, 45, device=gpu)
     torch.ops.pfk.pm_to_nchw(buf[:, 256:382], back)
     assert torch.equal(back.cpu(), x)
@@ -583,7 +549,7 @@ def test_update_engine_step(gpu, small):
     eng.load_state(net.cuda(), inp.cuda())
     c0g, c1g = c0.cuda(), c1.clone().cuda()
     torch.ops.pfk.flow_from_coords(c0g, c1g, eng.flow_view)
-    eng.step(pm(corr), c0g, c1g)
+    eng.step(pm(corr, "cuda"), c0g, c1g)
     close(eng.net_nchw(), net_ref, rtol=5e-5, atol=5e-5)
     close(c1g, c1 + delta_ref, rtol=5e-5, atol=5e-5)
     if not small:
@@ -667,7 +633,7 @@ def test_conv2d_group_equals_single_launches(gpu, B, H, W, n):
         ref = F.conv2d(x, wt, bias, padding=k // 2)
         refs.append((F.relu(ref) if relu else ref) * scale)
         buf = torch.zeros(M, cin + 4, device=gpu)            # a view with a wider row stride, as the engine's slices are
-        buf[:, :cin] = pm(x)
+        buf[:, :cin] = pm(x, "cuda")
         srcs.append(buf[:, :cin]); ws.append(pack_conv_weight(wt, [(0, cin, cin)]).cuda()); bs.append(bias.cuda())
         outs.append(torch.full((M, cout + 8), -3.0, device=gpu)[:, :cout]); ks.append(k); relus.append(relu); scales.append(scale)
     torch.ops.pfk.conv2d_group(srcs, B, H, W, ks, ws, bs, relus, scales, outs, [])

@@ -3,7 +3,7 @@
 the convex-upsampling backward (`pfk_convex_upsample_bwd_f32`) and the GRU gate kernels (`pfk_gru_gates_*`, `pfk_gru_backward_*`).
 Until now they were reached only through `conv_pm`, `CorrBlock` autograd or whole training steps.
 
-Gates on every kernel output (tests/test_gpu_sea_train.py's harness: `Rows`, `OP_TOL`, `SENTINEL`):
+Gates on every kernel output (tests/op_gate.py's harness: `gates`, `Rows`, `flat_out`, `SENTINEL`):
  1. relative L2 <= 5e-6 against float64 on the CPU ON THE KERNEL'S OWN fp32 INPUTS;
  2. a per-element bound that needs no measurement.  An element that sums n products must satisfy
         |got - ref| <= (n + 2) * 2^-24 * sum_i |term_i|
@@ -38,48 +38,12 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import raft_oracle as O
-from test_gpu_kernels import _coords_cases
-from test_gpu_sea_train import OP_TOL, SENTINEL, Rows, rel
+from op_gate import FLOOR, SENTINEL, Rows, flat_out, gates, tail_kept
+from op_refs import convex_case, coords_cases
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24
-FLOOR = 1e-35
-
-
-def flat_out(shape, gpu):
-    """a contiguous output of `shape` at the start of a sentinel-filled flat buffer with 64 more floats behind it"""
-    n = math.prod(shape)
-    flat = torch.full((n + 64,), SENTINEL, device=gpu)
-    return flat, flat[:n].view(shape)
-
-
-def tail_kept(flat):
-    return bool((flat[flat.numel() - 64:] == SENTINEL).all())
-
-
-def gates(what, got, ref, mag, k, floor=0.0, keep=None):
-    """gates 1 and 2 on one output: `mag` the float64 sum of magnitudes per element, `k` the factor in front of 2^-24 (a number or
-    a tensor), `keep` a mask of the elements that take part (default: all).  Returns (relative L2, worst ratio to the bound)."""
-    got = got.detach().double().cpu()
-    ref, mag = ref.detach().double(), mag.detach().double()
-    assert got.shape == ref.shape == mag.shape, f"{what}: shapes {tuple(got.shape)} {tuple(ref.shape)} {tuple(mag.shape)}"
-    assert bool(torch.isfinite(got).all()), f"{what}: {int((~torch.isfinite(got)).sum())} non-finite values"
-    if keep is not None:
-        got, ref, mag = got[keep], ref[keep], mag[keep]
-        k = k[keep] if torch.is_tensor(k) else k
-    bound = k * U * mag + floor
-    err = (got - ref).abs()
-    zero = bound == 0
-    assert bool((got[zero] == 0).all()), f"{what}: {int((got[zero] != 0).sum())} elements that are exact zeros by contract are not"
-    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
-    r = rel(got, ref)
-    print(f"{what}: relL2 {r:.2e}  worst |err| / bound {ratio:.3f}")
-    assert r <= OP_TOL, f"{what}: relative L2 {r:.3e}"
-    assert ratio <= 1.0, f"{what}: per-element error {ratio:.3f} x the bound"
-    return r, ratio
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -324,11 +288,11 @@ def lookup_case(B, h, w, L, r):
     sum of magnitudes (the weights are >= 0, so that is the same gradient for |grad_out|)"""
     g = torch.Generator().manual_seed(h * 1000 + w + r)
     N, n = h * w, 2 * r + 1
-    assert [name for name, _ in _coords_cases(B, h, w)] == list(FAMILIES)
+    assert [name for name, _ in coords_cases(B, h, w)] == list(FAMILIES)
     pyr = [torch.randn(B * N, 1, a, b, generator=g, dtype=torch.float64).requires_grad_() for a, b in _level_sizes(h, w, L)]
     gos = [torch.randn(B, L * n * n, h, w, generator=g) for _ in range(2)]
     fams = {}
-    for name, coords in _coords_cases(B, h, w):
+    for name, coords in coords_cases(B, h, w):
         out = O.lookup(pyr, coords, r)
         ref = torch.autograd.grad((out * (gos[0].double() + gos[1].double())).sum(), pyr, retain_graph=True)
         mag = torch.autograd.grad((out * (gos[0].double().abs() + gos[1].double().abs())).sum(), pyr)
@@ -371,36 +335,6 @@ def test_corr_lookup_bwd(gpu, B, h, w, L, r, family):
 # ---------------------------------------------------------------------------------------------------------------------
 # convex upsampling backward
 # ---------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def convex_case(B, H, W, logit_scale):
-    g = torch.Generator().manual_seed(B * 100 + H * 10 + W + int(logit_scale))
-    flow = torch.randn(B, 2, H, W, generator=g) * 3
-    mask = torch.randn(B, 576, H, W, generator=g) * logit_scale
-    go = torch.randn(B, 2, 8 * H, 8 * W, generator=g)
-    f64, m64, g64 = flow.double().requires_grad_(), mask.double().requires_grad_(), go.double()
-    out = O.convex_upsample(f64, m64)
-    gflow, gmask = torch.autograd.grad((out * g64).sum(), (f64, m64), retain_graph=True)
-    (gflow_mag,) = torch.autograd.grad((out * g64.abs()).sum(), f64)        # the softmax weights are >= 0: sum of 8 w |g|
-    # magnitudes of dmask[k] = w_k (dw_k - sum_j w_j dw_j), dw_k = g_x v_x,k + g_y v_y,k
-    with torch.no_grad():
-        m = m64.view(B, 1, 9, 8, 8, H, W)
-        wgt = torch.softmax(m, dim=2)[:, 0]                                                          # [B, 9, 8, 8, H, W]
-        spread = (m.amax(2) - m.amin(2))[:, 0]                                                       # [B, 8, 8, H, W]
-        up = F.unfold(8 * f64, [3, 3], padding=1).view(B, 2, 9, 1, 1, H, W).abs()
-        gsub = g64.view(B, 2, H, 8, W, 8).permute(0, 1, 3, 5, 2, 4).abs()                            # [B, 2, sy, sx, H, W]
-        T = (gsub[:, :, None] * up).sum(1)                                                           # [B, 9, 8, 8, H, W]
-        gmask_mag = wgt * (T + (wgt * T).sum(1, keepdim=True))
-    pm = lambda t: t.reshape(B, 576, H, W).permute(0, 2, 3, 1).reshape(B * H * W, 576)
-    # K: a softmax weight is off by at most (2 spread + 19) units of 2^-24 relative — the rounded differences m_k - max in the
-    # numerator and in the denominator (spread each), expf within 2 ulp twice (4 + 4), nine additions, the reciprocal, the product;
-    # dmask then has its weight, dw_k (3 roundings), the dot (each term a weight, a dw, a product; nine additions), the subtraction
-    # and the last product: at most 2 (2 spread + 19) + 15 on the magnitudes above.
-    k_w = 2 * spread + 19
-    k_mask = pm((2 * k_w + 15)[:, None].expand(B, 9, 8, 8, H, W))
-    return {"flow": flow, "mask": mask, "go": go, "gflow": gflow, "gflow_mag": gflow_mag, "gmask": pm(gmask), "gmask_mag": pm(gmask_mag),
-            "k_mask": k_mask, "k_flow": 9 * 64 + float(k_w.max()) + 2}
-
-
 @pytest.mark.parametrize("layout", ["nchw", "pixel_major"])
 @pytest.mark.parametrize("B,H,W,logit_scale", [(2, 1, 5, 1.0), (1, 6, 1, 1.0), (2, 9, 13, 1.0), (2, 9, 13, 40.0)])
 def test_convex_upsample_bwd(gpu, B, H, W, logit_scale, layout):

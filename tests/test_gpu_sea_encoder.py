@@ -15,22 +15,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import close, unpm
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sea_raft_encoder.pt")
 ENC_SEED = 4100          # scripts/make_sea_raft_golden.py
 VARIANTS = (("resnet18", 3), ("resnet18", 6), ("resnet34", 3))
-
-
-def close(a, b, rtol=2e-5, atol=2e-5):
-    a, b = a.float().cpu(), b.float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    assert bool((err <= tol).all()), f"max err {err.max().item():.3e} (ref max {b.abs().max().item():.3e})"
-
-
-def unpm(x, B, H, W):
-    return x.view(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 # ------------------------------------------------------------------------------------------------------------- stem
@@ -130,10 +121,10 @@ def test_plain_winograd_entry_still_refuses_a_residual(gpu):
         torch.ops.pfk.conv2d_wino_res(x, 1, 6, 8, w, None, 64, True, 1.0, out, torch.zeros(48, 32, device=gpu), True)
     import ctypes
     import ptlflow_amd
-    from test_gpu_winograd import EPI_LINEAR, _Desc, _Src
+    from pfk_ctypes import EPI_LINEAR, Desc, Src
     lib = ctypes.CDLL(str(ptlflow_amd.LIBPFK_PATH))
-    d = _Desc()
-    d.src[0] = _Src(x.data_ptr(), 64, 64)
+    d = Desc()
+    d.src[0] = Src(x.data_ptr(), 64, 64)
     d.num_src, d.B, d.H, d.W, d.kh, d.kw = 1, 1, 6, 8, 3, 3
     d.weight, d.cout, d.epilogue, d.relu, d.scale = w.data_ptr(), 64, EPI_LINEAR, 1, 1.0
     d.out, d.out_ld = out.data_ptr(), 64

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sea_raft_update.pt")
 
 
+# local, not op_gate.close: the limit is tol * (1 + |ref|), with a shape check and the worst ratio in the message
 def _close(got, ref, tol=2e-5):
     got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
     assert got.shape == ref.shape, (got.shape, ref.shape)

@@ -8,21 +8,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import ulp_bf16, within_ulp
+
 pytestmark = pytest.mark.gpu
-
-
-def _ulp_bf16(v: torch.Tensor) -> torch.Tensor:
-    """one bf16 ulp at |v| (normal range; 2^-133 below it)"""
-    a = v.abs().double().clamp_min(2.0 ** -126)
-    return torch.pow(2.0, torch.floor(torch.log2(a)) - 7)
-
-
-def _within_ulp(got: torch.Tensor, ref: torch.Tensor, floor: float) -> None:
-    """|got - bf16(ref)| <= 1 bf16 ulp of ref + `floor`: the absolute error of the fp32 arithmetic before the rounding, which is
-    more than an ulp only for results within ~1e-5 of zero (torch's own fp32 forms miss a plain one-ulp bound there as well)"""
-    err = (got.double() - ref.to(torch.bfloat16).double()).abs()
-    lim = _ulp_bf16(ref) + floor
-    assert bool((err <= lim).all()), f"{(err > lim).sum().item()} of {err.numel()} over, worst ratio {float((err / lim).max()):.2f}"
 
 
 # ------------------------------------------------------------------------------------------------------------- dwconv + LayerNorm
@@ -49,7 +37,7 @@ def test_dwconv_layernorm_b16(gpu, B, H, W, C, k, pad):
     torch.ops.pfk.dwconv_layernorm_b16(inp, w.to(gpu).reshape(C, k * k).contiguous(), b.to(gpu), lw.to(gpu), lb.to(gpu), 1e-6, out,
                                        B, H, W, k)
     torch.cuda.synchronize()
-    _within_ulp(out.cpu(), ref, 2.0 ** -16)
+    within_ulp(out.cpu(), ref, 2.0 ** -16)
     if pad:
         assert bool(torch.isnan(out_buf[:, C:].float()).all()), "wrote past the C channels of its rows"
 
@@ -70,7 +58,7 @@ def test_conv2d_gelu_b16(gpu, M, cin, cout, out_dtype):
     torch.cuda.synchronize()
     got = out.double().cpu()
     if out_dtype == torch.bfloat16:      # the rounding of the output (half an ulp) and fp32 accumulation
-        lim = 0.5 * _ulp_bf16(ref) + 1e-5 * (1 + ref.abs())
+        lim = 0.5 * ulp_bf16(ref) + 1e-5 * (1 + ref.abs())
     else:
         lim = 2e-5 * (1 + ref.abs())
     err = (got - ref).abs()
@@ -244,7 +232,7 @@ def test_bilinear_f2_bf16_volume_against_oracle(gpu):
         f2l = f2_pm.view(B, h2, w2, D).permute(0, 3, 1, 2).cpu()
         ref = O.sea_correlation_pyramid(f1b, f2l.to(torch.bfloat16).float(), num_levels=1)[0]
         # (two fp32 sums of 256 products, the oracle's and K1's, in different orders: 2^-14 absolute near zero)
-        _within_ulp(gpu_pyr[lvl].reshape(ref.shape), ref.double(), 2.0 ** -14)
+        within_ulp(gpu_pyr[lvl].reshape(ref.shape), ref.double(), 2.0 ** -14)
     coords = O.coords_grid(B, h, w) + torch.randn(B, 2, h, w, generator=g) * 6
     pyr32 = [lv.float().reshape(B * h * w, 1, lv.shape[-2], lv.shape[-1]) for lv in gpu_pyr]
     want = O.lookup(pyr32, coords, r)

@@ -5,7 +5,7 @@ compositions of ptlflow_amd/train_sea.py and the seam `accelerate(model, sea_raf
 Gates.  Kernels and nodes: relative L2 <= 5e-6 against float64 torch on the CPU ON THE KERNEL'S OWN INPUTS (the project's fp32 op gate);
 the train forward's `out` must be `torch.equal` to `ops.dwconv_layernorm`.  Blocks and seam: 5e-4 of each tensor's scale against the
 torch stand-in (tests/sea_seam_model.py) in float64 (tests/test_gpu_train.py::test_update_block_training_step's gate).  The kernel tests
-use tests/test_gpu_gma_train.py's harness: NaN in the pad columns of the inputs, a sentinel in the pad columns of the outputs and past
+use tests/op_gate.py's harness: NaN in the pad columns of the inputs, a sentinel in the pad columns of the outputs and past
 the last row, the same bits on a second run.
 
 Measured on an MI355X: every kernel and node output <= 1.7e-7 (dweight <= 1.3e-7, dgamma <= 1.7e-7: no weight-gradient reduction needed
@@ -17,10 +17,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import BLOCK_TOL, OP_TOL, SENTINEL, Rows, nchw, pm, rel, scale_close
+from op_refs import dwconv_bwd_ref, gelu_bwd_ref, layernorm_bwd_ref
+
 pytestmark = pytest.mark.gpu
-OP_TOL = 5e-6
-BLOCK_TOL = 5e-4
-SENTINEL = 12288.0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sea_raft_update_grad.pt")
 
@@ -30,42 +30,10 @@ SHAPES = [(2, 1, 5, 384), (2, 13, 17, 384), (1, 8, 16, 36), (1, 4, 8, 4), (1, 9,
 CASES = [(*s, 7) for s in SHAPES] + [(2, 13, 17, 384, 3)]
 
 
-def rel(a, b):
-    b = b.detach().double().cpu()
-    return float((a.detach().double().cpu() - b).norm() / b.norm().clamp_min(1e-300))
-
-
-def scale_close(a, b, what, tol=BLOCK_TOL):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    scale = float(b.abs().max()) + 1e-12
-    err = float((a - b).abs().max())
-    print(f"{what}: max err {err:.3e} of scale {scale:.3e} ({err / scale:.2e})")
-    assert err <= tol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
-
-
-class Rows:
-    """[M, C] rows inside a flat buffer with row stride C + pad and 64 floats past the last row.  Inputs: NaN in the pad columns
-    (must not be read); outputs: the sentinel everywhere (pad columns and the tail must keep it)."""
-
-    def __init__(self, M, C, gpu, values=None, pad=4):
-        self.M, self.C, self.ld = M, C, C + pad
-        self.flat = torch.full((M * self.ld + 64,), SENTINEL, device=gpu)
-        self.full = self.flat[:M * self.ld].view(M, self.ld)
-        self.rows = self.full[:, :C]
-        if values is not None:
-            self.full.fill_(float("nan"))
-            self.rows.copy_(values)
-
-    def check_untouched(self, what):
-        assert bool((self.flat[self.M * self.ld:] == SENTINEL).all()), f"{what}: memory past the last row was written"
-        assert bool((self.full[:, self.C:] == SENTINEL).all()), f"{what}: pad columns of the output were written"
-
-
 @functools.lru_cache(maxsize=None)
 def case(B, H, W, C, k):
     """fp32 inputs of the three kernels and their float64 references, computed once per shape on the CPU.  Each kernel's reference
     is float64 arithmetic on that kernel's own fp32 inputs (x^, rstd and du are the rounded float64 values)."""
-    from test_sea_train_cpu import dwconv_bwd_ref, layernorm_bwd_ref
     g = torch.Generator().manual_seed(B * 1000 + H * 100 + W + C + k)
     M = B * H * W
     d = {"x": torch.randn(M, C, generator=g), "w": torch.randn(C, k * k, generator=g) / k, "b": 0.1 * torch.randn(C, generator=g),
@@ -152,7 +120,6 @@ def test_layernorm_bwd(gpu, B, H, W, C):
 
 
 def test_layernorm_bwd_one_row(gpu):
-    from test_sea_train_cpu import layernorm_bwd_ref
     g = torch.Generator().manual_seed(9)
     C = 384
     xhat, dy = torch.randn(1, C, generator=g), torch.randn(1, C, generator=g)
@@ -195,7 +162,6 @@ def test_dwconv_bwd(gpu, B, H, W, C, k):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,C", [(2 * 13 * 17, 512), (3, 4), (37, 36)])
 def test_gelu_rows(gpu, M, C):
-    from test_sea_train_cpu import gelu_bwd_ref
     ops = torch.ops.pfk
     g = torch.Generator().manual_seed(M + C)
     x, dy = torch.randn(M, C, generator=g) * 2.5, torch.randn(M, C, generator=g)
@@ -265,14 +231,6 @@ def test_gelu_node(gpu):
 BB, BH, BW = 2, 13, 17
 
 
-def _pm(t):
-    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
-
-
-def _nchw(t, B=BB, H=BH, W=BW):
-    return t.view(B, H, W, -1).permute(0, 3, 1, 2)
-
-
 @functools.lru_cache(maxsize=None)
 def block_reference():
     """the stand-in's update block and heads in float64 on the CPU at (2, 13, 17): inputs, outputs, every gradient"""
@@ -300,8 +258,8 @@ def _block_run(gpu, ref, cache, accumulate, calls=1):
     P = {k: v.to(gpu).requires_grad_(True) for k, v in ref["params"].items()}
     Pu = {k[len("update_block."):]: v for k, v in P.items() if k.startswith("update_block.")}
     Ph = {k: v for k, v in P.items() if not k.startswith("update_block.")}
-    xin = {k: _pm(v).contiguous().to(gpu).requires_grad_(True) for k, v in ref["x"].items()}
-    R = [_pm(r).contiguous().to(gpu) for r in ref["R"]]
+    xin = {k: pm(v, gpu).requires_grad_(True) for k, v in ref["x"].items()}
+    R = [pm(r, gpu) for r in ref["R"]]
     loss, outs = 0.0, None
     for _ in range(calls):
         h = sea_update_block_train_pm(Pu, sea_spec(324), xin["net"], xin["inp"], xin["corr"], xin["flow"], BB, BH, BW, 2, cache, accumulate)
@@ -316,9 +274,9 @@ def test_update_block_and_heads(gpu):
     ref = block_reference()
     outs, gin, gpar = _block_run(gpu, ref, {}, False)
     for name, a, b in zip(("net", "flow_head", "upsample_weight"), outs, ref["out"]):
-        scale_close(_nchw(a), b, name)
+        scale_close(nchw(a, BB, BH, BW), b, name)
     for k in gin:
-        scale_close(_nchw(gin[k]), ref["gin"][k], "d/d" + k)
+        scale_close(nchw(gin[k], BB, BH, BW), ref["gin"][k], "d/d" + k)
     for k in gpar:
         scale_close(gpar[k], ref["gpar"][k], k)
 
@@ -348,11 +306,11 @@ def test_convnext_block(gpu):
     out_ref = blk(xr)
     want = torch.autograd.grad((out_ref * R.double()).sum(), [xr] + list(blk.parameters()))
     P = {"b." + k: v.to(gpu).requires_grad_(True) for k, v in P32.items()}
-    xg = _pm(x).contiguous().to(gpu).requires_grad_(True)
+    xg = pm(x, gpu).requires_grad_(True)
     out = convnext_block_train_pm(P, "b.", xg, BB, BH, BW)
-    got = torch.autograd.grad((out * _pm(R).contiguous().to(gpu)).sum(), [xg] + list(P.values()))
-    scale_close(_nchw(out), out_ref, "out")
-    scale_close(_nchw(got[0]), want[0], "d/dx")
+    got = torch.autograd.grad((out * pm(R, gpu)).sum(), [xg] + list(P.values()))
+    scale_close(nchw(out, BB, BH, BW), out_ref, "out")
+    scale_close(nchw(got[0], BB, BH, BW), want[0], "d/dx")
     for name, a, b in zip(P32, got[1:], want[1:]):
         scale_close(a, b, name)
     # a block without gamma behaves as gamma = 1

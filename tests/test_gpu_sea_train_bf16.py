@@ -4,12 +4,12 @@ ptlflow_amd/train_sea.py with ``precision="bf16"`` and the seam
 ``accelerate(model, sea_raft_update=True, sea_raft_train=True, train_precision="bf16")``.
 
 Gates.
-* Kernels: the reference is float64 on each kernel's OWN inputs (bf16 values, fp32 parameters).  bf16 outputs: `_within_ulp` of
-  tests/test_gpu_sea_raft_bf16.py with its 2^-16 floor, |got - bf16(ref)| <= 1 bf16 ulp + floor; fp32 outputs (rstd, dgamma, dbeta,
+* Kernels: the reference is float64 on each kernel's OWN inputs (bf16 values, fp32 parameters).  bf16 outputs: `within_ulp` of
+  tests/op_gate.py with a 2^-16 floor, |got - bf16(ref)| <= 1 bf16 ulp + floor; fp32 outputs (rstd, dgamma, dbeta,
   dweight, dbias): the project's op gate, relative L2 <= 5e-6; `out` `torch.equal` to `ops.dwconv_layernorm_b16`.  The harness is
-  tests/test_gpu_sea_train.py's on bf16 buffers: NaN in the pad columns of the inputs, a sentinel in the pad columns of the outputs
+  tests/op_gate.py's on bf16 buffers: NaN in the pad columns of the inputs, a sentinel in the pad columns of the outputs
   and past the last row, the same bits on a second run.
-* Nodes, compositions and the whole loop: `gate()` / `FACTOR` of tests/test_gpu_train_bf16.py, imported — for every output and
+* Nodes, compositions and the whole loop: `within_2x_cpu_autocast` of tests/op_gate.py — for every output and
   gradient tensor the L2-relative error against float64 is at most 2x the error of the same torch modules (tests/sea_seam_model.py)
   on the CPU under ``torch.autocast("cpu", bfloat16)``, nothing skipped.
 """
@@ -19,13 +19,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_sea_raft_bf16 import _within_ulp
-from test_gpu_train_bf16 import gate, leaf
+from op_gate import OP_TOL, SENTINEL, Rows, leaf, nchw, pm, rel, within_2x_cpu_autocast, within_ulp
+from op_refs import dwconv_bwd_ref, gelu_bwd_ref, layernorm_bwd_ref
 
 pytestmark = pytest.mark.gpu
-OP_TOL = 5e-6
 ULP_FLOOR = 2.0 ** -16
-SENTINEL = 12288.0               # exact in bf16
 BF = torch.bfloat16
 
 # (B, H, W, C): smaller than a tile and than the 7x7 halo, two images | ragged tiles both ways, image boundary | exact tiles, a 32 + 8
@@ -34,42 +32,17 @@ SHAPES = [(2, 1, 5, 384), (2, 13, 17, 384), (1, 8, 16, 40), (1, 4, 8, 8), (1, 9,
 CASES = [(*s, 7) for s in SHAPES] + [(2, 13, 17, 384, 3)]
 
 
-def rel(a, b):
-    b = b.detach().double().cpu()
-    return float((a.detach().double().cpu() - b).norm() / b.norm().clamp_min(1e-300))
-
-
 def ulp_ok(got, ref, what):
     try:
-        _within_ulp(got.detach().cpu(), ref, ULP_FLOOR)
+        within_ulp(got.detach().cpu(), ref, ULP_FLOOR)
     except AssertionError as e:
         raise AssertionError(f"{what}: {e}") from None
-
-
-class Rows:
-    """[M, C] rows of `dtype` inside a flat buffer with row stride C + pad and 64 elements past the last row.  Inputs: NaN in the pad
-    columns (must not be read); outputs: the sentinel everywhere (pad columns and the tail must keep it)."""
-
-    def __init__(self, M, C, gpu, values=None, pad=8, dtype=BF):
-        self.M, self.C, self.ld = M, C, C + pad
-        self.flat = torch.full((M * self.ld + 64,), SENTINEL, device=gpu, dtype=dtype)
-        self.full = self.flat[:M * self.ld].view(M, self.ld)
-        self.rows = self.full[:, :C]
-        if values is not None:
-            assert values.dtype == dtype
-            self.full.fill_(float("nan"))
-            self.rows.copy_(values)
-
-    def check_untouched(self, what):
-        assert bool((self.flat[self.M * self.ld:] == SENTINEL).all()), f"{what}: memory past the last row was written"
-        assert bool((self.full[:, self.C:] == SENTINEL).all()), f"{what}: pad columns of the output were written"
 
 
 @functools.lru_cache(maxsize=None)
 def case(B, H, W, C, k):
     """bf16 inputs of the three kernels and their float64 references, computed once per shape on the CPU.  Each kernel's reference is
     float64 arithmetic on that kernel's own inputs: bf16 x, dy; x^ and du are the float64 values rounded to bf16, rstd to fp32."""
-    from test_sea_train_cpu import dwconv_bwd_ref, layernorm_bwd_ref
     g = torch.Generator().manual_seed(B * 1000 + H * 100 + W + C + k)
     M = B * H * W
     d = {"x": torch.randn(M, C, generator=g).to(BF), "w": torch.randn(C, k * k, generator=g) / k, "b": 0.1 * torch.randn(C, generator=g),
@@ -99,11 +72,11 @@ def test_dwconv_layernorm_train_b16(gpu, B, H, W, C, k):
     ops = torch.ops.pfk
     d = case(B, H, W, C, k)
     M = B * H * W
-    x = Rows(M, C, gpu, d["x"])
+    x = Rows(M, C, gpu, d["x"], pad=8, dtype=BF)
     par = [d[n].to(gpu) for n in ("w", "b", "gamma", "beta")]
 
     def run():
-        out, xhat = Rows(M, C, gpu, pad=16), Rows(M, C, gpu, pad=24)
+        out, xhat = Rows(M, C, gpu, pad=16, dtype=BF), Rows(M, C, gpu, pad=24, dtype=BF)
         rstd = torch.full((M + 64,), SENTINEL, device=gpu)
         ops.dwconv_layernorm_train_b16(x.rows, *par, 1e-6, out.rows, xhat.rows, rstd[:M], B, H, W, k)
         return out, xhat, rstd
@@ -133,11 +106,11 @@ def test_dwconv_layernorm_train_b16(gpu, B, H, W, C, k):
 def _run_layernorm_bwd(gpu, xhat, rstd, gamma, dy, refs, what):
     ops = torch.ops.pfk
     M, C = xhat.shape
-    xh, dyr = Rows(M, C, gpu, xhat), Rows(M, C, gpu, dy, pad=24)
+    xh, dyr = Rows(M, C, gpu, xhat, pad=8, dtype=BF), Rows(M, C, gpu, dy, pad=24, dtype=BF)
     rs, gm = rstd.to(gpu), gamma.to(gpu)
 
     def run():
-        du = Rows(M, C, gpu, pad=16)
+        du = Rows(M, C, gpu, pad=16, dtype=BF)
         vec = torch.full((2 * C + 64,), SENTINEL, device=gpu)
         ops.layernorm_bwd_b16(xh.rows, rs, gm, dyr.rows, du.rows, vec[:C], vec[C:2 * C])
         return du, vec
@@ -161,7 +134,6 @@ def test_layernorm_bwd_b16(gpu, B, H, W, C):
 
 
 def test_layernorm_bwd_b16_one_row(gpu):
-    from test_sea_train_cpu import layernorm_bwd_ref
     g = torch.Generator().manual_seed(9)
     C = 384
     xhat, dy = torch.randn(1, C, generator=g), torch.randn(1, C, generator=g).to(BF)
@@ -179,11 +151,11 @@ def test_dwconv_bwd_b16(gpu, B, H, W, C, k):
     ops = torch.ops.pfk
     d = case(B, H, W, C, k)
     M = B * H * W
-    x, du = Rows(M, C, gpu, d["x"]), Rows(M, C, gpu, d["du"], pad=16)
+    x, du = Rows(M, C, gpu, d["x"], pad=8, dtype=BF), Rows(M, C, gpu, d["du"], pad=16, dtype=BF)
     w = d["w"].to(gpu)
 
     def run():
-        dx = Rows(M, C, gpu, pad=24)
+        dx = Rows(M, C, gpu, pad=24, dtype=BF)
         vec = torch.full((C * k * k + C + 64,), SENTINEL, device=gpu)
         ops.dwconv_bwd_b16(x.rows, du.rows, w, dx.rows, vec[:C * k * k], vec[C * k * k:C * k * k + C], B, H, W, k)
         return dx, vec
@@ -200,7 +172,7 @@ def test_dwconv_bwd_b16(gpu, B, H, W, C, k):
     assert torch.equal(dx2.flat, dx.flat) and torch.equal(vec2, vec)
     # dbias is optional
     nb = torch.full((C * k * k + 64,), SENTINEL, device=gpu)
-    dx3 = Rows(M, C, gpu, pad=24)
+    dx3 = Rows(M, C, gpu, pad=24, dtype=BF)
     ops.dwconv_bwd_b16(x.rows, du.rows, w, dx3.rows, nb[:C * k * k], None, B, H, W, k)
     assert torch.equal(dx3.flat, dx.flat) and torch.equal(nb[:C * k * k], vec[:C * k * k]) and bool((nb[C * k * k:] == SENTINEL).all())
 
@@ -210,16 +182,15 @@ def test_dwconv_bwd_b16(gpu, B, H, W, C, k):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,C", [(2 * 13 * 17, 512), (3, 8), (37, 40)])
 def test_gelu_rows_b16(gpu, M, C):
-    from test_sea_train_cpu import gelu_bwd_ref
     ops = torch.ops.pfk
     g = torch.Generator().manual_seed(M + C)
     x, dy = (torch.randn(M, C, generator=g) * 2.5).to(BF), torch.randn(M, C, generator=g).to(BF)
     special = torch.tensor([30.0, -30.0, 1e30, -1e30]).to(BF)     # large |x|: y = x or 0, dx = dy or 0, never NaN
     x[0, :4] = special
-    xr, dyr = Rows(M, C, gpu, x), Rows(M, C, gpu, dy, pad=16)
+    xr, dyr = Rows(M, C, gpu, x, pad=8, dtype=BF), Rows(M, C, gpu, dy, pad=16, dtype=BF)
 
     def run():
-        y, dx = Rows(M, C, gpu), Rows(M, C, gpu, pad=24)
+        y, dx = Rows(M, C, gpu, pad=8, dtype=BF), Rows(M, C, gpu, pad=24, dtype=BF)
         ops.gelu_b16(xr.rows, y.rows)
         ops.gelu_bwd_b16(xr.rows, dyr.rows, dx.rows)
         return y, dx
@@ -243,14 +214,6 @@ def test_gelu_rows_b16(gpu, M, C):
 # nodes and compositions: 2x CPU autocast on every tensor
 # ---------------------------------------------------------------------------------------------------------------------
 BB, BH, BW = 2, 13, 17
-
-
-def _pm(t):
-    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
-
-
-def _nchw(t, B=BB, H=BH, W=BW):
-    return t.reshape(B, H, W, -1).permute(0, 3, 1, 2)
 
 
 def _seeded_block():
@@ -291,13 +254,13 @@ def test_dwconv_layernorm_node_bf16(gpu):
 
     ref64, cpu16 = _cpu_runs(cpu)
     P = {n: p.detach().to(gpu).requires_grad_() for n, p in blk.named_parameters() if n in names}
-    xg = _pm(x).contiguous().to(gpu).requires_grad_()
+    xg = pm(x, gpu).requires_grad_()
     out = dwconv_layernorm_pm(xg, *(P[n] for n in names), BB, BH, BW, precision="bf16")
     assert out.dtype == BF
     out.backward(R.reshape(-1, 384).to(gpu).to(BF))
     assert xg.grad.dtype == torch.float32 and all(p.grad.dtype == torch.float32 for p in P.values())
     assert P["dwconv.weight"].grad.shape == (384, 1, 7, 7)
-    gate({"out": _nchw(out), "d/dx": _nchw(xg.grad), **{"d/d" + n: P[n].grad for n in names}}, ref64, cpu16)
+    within_2x_cpu_autocast({"out": nchw(out, BB, BH, BW), "d/dx": nchw(xg.grad, BB, BH, BW), **{"d/d" + n: P[n].grad for n in names}}, ref64, cpu16)
 
 
 def test_gelu_node_bf16(gpu):
@@ -324,7 +287,7 @@ def test_gelu_node_bf16(gpu):
     y = gelu_pm(a, "bf16")
     assert a.dtype == BF and y.dtype == BF
     y.backward(R.to(gpu).to(BF))
-    gate({"y": y, "d/dx": xg.grad, "d/dpwconv1.weight": w.grad, "d/dpwconv1.bias": b.grad}, ref64, cpu16)
+    within_2x_cpu_autocast({"y": y, "d/dx": xg.grad, "d/dpwconv1.weight": w.grad, "d/dpwconv1.bias": b.grad}, ref64, cpu16)
 
 
 def test_convnext_block_bf16(gpu):
@@ -343,13 +306,13 @@ def test_convnext_block_bf16(gpu):
     ref64, cpu16 = _cpu_runs(cpu)
     for out_fp32 in (True, False):
         P = {"b." + n: p.detach().to(gpu).requires_grad_() for n, p in blk.named_parameters()}
-        xg = _pm(x).contiguous().to(gpu).requires_grad_()
+        xg = pm(x, gpu).requires_grad_()
         out = convnext_block_train_pm(P, "b.", xg, BB, BH, BW, precision="bf16", out_fp32=out_fp32)
         assert out.dtype == (torch.float32 if out_fp32 else BF)
-        (out * _pm(R).contiguous().to(gpu)).sum().backward()
+        (out * pm(R, gpu)).sum().backward()
         assert all(p.grad is not None and p.grad.dtype == torch.float32 for p in P.values())
         print(f"convnext block, out_fp32={out_fp32}")
-        gate({"out": _nchw(out), "d/dx": _nchw(xg.grad), **{"d/d" + n[2:]: p.grad for n, p in P.items()}}, ref64, cpu16)
+        within_2x_cpu_autocast({"out": nchw(out, BB, BH, BW), "d/dx": nchw(xg.grad, BB, BH, BW), **{"d/d" + n[2:]: p.grad for n, p in P.items()}}, ref64, cpu16)
 
 
 PARTS = ("update_block", "flow_head", "upsample_weight")
@@ -408,7 +371,7 @@ def test_two_chained_update_blocks_and_heads_bf16(gpu):
         for n, p in P[part].items():
             assert p.grad is not None and p.grad.dtype == torch.float32, (part, n)
             got[f"d/d{part}.{n}"] = p.grad
-    gate(got, ref64, cpu16, expect=[k for k in ref64 if k.startswith("d/d")])
+    within_2x_cpu_autocast(got, ref64, cpu16, expect=[k for k in ref64 if k.startswith("d/d")])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -533,6 +496,6 @@ def test_training_loop_through_the_seam_bf16(gpu):
         assert model.upsample_data.train_calls == 3
         assert all(got[k].dtype == torch.float32 for k in R)
         assert all(p.grad is not None and p.grad.dtype == torch.float32 for p in model.parameters())
-        gate(got, ref64, cpu16, expect=["d/d" + n for n, _ in model.named_parameters()])
+        within_2x_cpu_autocast(got, ref64, cpu16, expect=["d/d" + n for n, _ in model.named_parameters()])
     finally:
         patch.restore(model)

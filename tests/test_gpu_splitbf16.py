@@ -14,27 +14,12 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import close, pm, unpm
 
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
 TOL = {3: 2e-5, 2: 2e-4, 1: 4e-2}
-
-
-def close(a, b, rtol, atol):
-    a, b = a.float().cpu(), b.float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    assert bool((err <= tol).all()), f"max err {err.max().item():.3e} (ref max {b.abs().max().item():.3e})"
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().cuda()
-
-
-def unpm(x, B, H, W):
-    return x.view(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 def planes(weight, segs, nsplit):
@@ -65,7 +50,7 @@ def test_split_conv_linear(gpu, nsplit, B, H, W, cin, cout, kh, kw, relu):
     M = B * H * W
     buf = torch.full((M, cout + 12), 5.0, device=gpu)
     out = buf[:, 4:4 + cout]
-    torch.ops.pfk.conv2d([pm(x)], B, H, W, kh, kw, planes(wt, [(0, cin, cin)], nsplit), bias.cuda(), cout, EPI_LINEAR, relu,
+    torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, kh, kw, planes(wt, [(0, cin, cin)], nsplit), bias.cuda(), cout, EPI_LINEAR, relu,
                          0.25, out, None, None, None)
     close(unpm(out, B, H, W), ref, rtol=TOL[nsplit], atol=TOL[nsplit])
     assert bool((buf[:, :4] == 5.0).all()) and bool((buf[:, 4 + cout:] == 5.0).all()), "wrote outside its channel slice"
@@ -82,7 +67,7 @@ def test_plain_bf16_is_exact_on_bf16_operands(gpu, B, H, W, cin, cout, kh, kw, r
     if relu:
         ref = F.relu(ref)
     out = torch.zeros(B * H * W, cout, device=gpu)
-    torch.ops.pfk.conv2d([pm(x)], B, H, W, kh, kw, planes(wt, [(0, cin, cin)], 1), bias.cuda(), cout, EPI_LINEAR, relu, 1.0,
+    torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, kh, kw, planes(wt, [(0, cin, cin)], 1), bias.cuda(), cout, EPI_LINEAR, relu, 1.0,
                          out, None, None, None)
     close(unpm(out, B, H, W), ref, rtol=2e-5, atol=2e-5)
 
@@ -98,10 +83,10 @@ def test_split_conv_multi_source(gpu, nsplit):
     bias = torch.randn(cout)
     ref = F.conv2d(torch.cat([a, b[:, :146], c], 1).double(), wt.double(), bias.double(), padding=1).float()
     wide = torch.zeros(B * H * W, 300, device=gpu)
-    wide[:, 100:248] = pm(b)
+    wide[:, 100:248] = pm(b, "cuda")
     w = planes(wt, [(0, ca, ca), (ca, 146, 148), (ca + 146, cc, cc)], nsplit)
     out = torch.zeros(B * H * W, cout, device=gpu)
-    torch.ops.pfk.conv2d([pm(a), wide[:, 100:248], pm(c)], B, H, W, 3, 3, w, bias.cuda(), cout, EPI_LINEAR, False, 1.0,
+    torch.ops.pfk.conv2d([pm(a, "cuda"), wide[:, 100:248], pm(c, "cuda")], B, H, W, 3, 3, w, bias.cuda(), cout, EPI_LINEAR, False, 1.0,
                          out, None, None, None)
     close(unpm(out, B, H, W), ref, rtol=TOL[nsplit], atol=TOL[nsplit])
 
@@ -121,7 +106,7 @@ def test_split_gru_bf16x6(gpu, B, H, W, Ch, Cx, passes):
     x = torch.randn(B, Cx, H, W)
     ref = O.sepconv_gru(P, h, x) if len(passes) == 2 else O.conv_gru(P, h, x)
     M = B * H * W
-    hx = torch.cat([pm(h), pm(x)], 1).contiguous()
+    hx = torch.cat([pm(h, "cuda"), pm(x, "cuda")], 1).contiguous()
     z = torch.zeros(M, Ch, device=gpu)
     rh = torch.zeros(M, Ch, device=gpu)
     for kh, kw, sfx in passes:
@@ -167,7 +152,7 @@ def test_split_conv_tail_split(gpu, nsplit):
     wt = torch.randn(cout, cin, 3, 3) / math.sqrt(cin * 9)
     bias = torch.randn(cout)
     w = planes(wt, [(0, cin, cin)], nsplit)
-    xp = pm(x)
+    xp = pm(x, "cuda")
     outs = []
     for knob in (100, 190):                    # heuristic with / without the tail split
         torch.ops.pfk.debug_set_tile(knob)
@@ -270,7 +255,7 @@ def test_bf16x6_error_next_to_fp32_kernel_vs_float64(gpu, B, H, W, cin, cout, kh
     errs = {}
     for name, weight in (("fp32", pack_conv_weight(wt, [(0, cin, cin)]).cuda()), ("bf16x6", planes(wt, [(0, cin, cin)], 3))):
         out = torch.empty(M, cout, device=gpu)
-        torch.ops.pfk.conv2d([pm(x)], B, H, W, kh, kw, weight, bias.cuda(), cout, EPI_LINEAR, False, 1.0, out, None, None, None)
+        torch.ops.pfk.conv2d([pm(x, "cuda")], B, H, W, kh, kw, weight, bias.cuda(), cout, EPI_LINEAR, False, 1.0, out, None, None, None)
         d = (unpm(out, B, H, W).double().cpu() - ref).abs()
         errs[name] = (float(d.max()) / scale, float(d.pow(2).mean().sqrt()) / scale)
     print(f"conv {cin}->{cout} {kh}x{kw}: max / rms error over scale  fp32 {errs['fp32'][0]:.2e} / {errs['fp32'][1]:.2e}   "

@@ -13,47 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
+from op_gate import leaf, nchw, pm, within_2x_cpu_autocast
 
 pytestmark = pytest.mark.gpu
-FACTOR = 2.0
-
-
-def gate(got, ref64, cpu16, expect=None):
-    """got / ref64 / cpu16: {name: tensor}.  Every name of ref64 must be in `got` (nothing skipped)."""
-    assert set(got) == set(ref64) == set(cpu16), (sorted(set(ref64) ^ set(got)), sorted(set(ref64) ^ set(cpu16)))
-    if expect is not None:
-        assert set(expect) <= set(got), sorted(set(expect) - set(got))
-    scale_all = max(float(v.abs().max()) for v in ref64.values())
-    rows = []
-    for n, ref in ref64.items():
-        ref = ref.detach().double().cpu()
-        g, c = got[n], cpu16[n]
-        assert g is not None and c is not None, f"{n}: no value"
-        g, c = g.detach().double().cpu(), c.detach().double().cpu()
-        assert g.shape == ref.shape == c.shape, (n, g.shape, ref.shape, c.shape)
-        assert bool(torch.isfinite(g).all()), f"{n}: not finite"
-        den = max(float(ref.norm()), 1e-3 * scale_all * ref.numel() ** 0.5)
-        e_gpu, e_cpu = float((g - ref).norm()) / den, float((c - ref).norm()) / den
-        rows.append((e_gpu / max(e_cpu, 1e-30), n, e_gpu, e_cpu))
-    rows.sort(reverse=True)
-    for r in rows:
-        print("   ratio %.2f  %-40s  L2 err %.3e  (CPU autocast %.3e)" % r)
-    bad = [r for r in rows if r[2] > FACTOR * r[3]]
-    assert not bad, "worse than %.0fx CPU autocast: " % FACTOR + ", ".join("%s %.2e vs %.2e" % (r[1], r[2], r[3]) for r in bad)
-
-
-def leaf(t, dtype):
-    """A fresh leaf: `.to()` of the same dtype returns the tensor itself, and requires_grad_() would then mark the shared input."""
-    return t.detach().clone().to(dtype).requires_grad_()
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C)
-
-
-def nchw(x, B, H, W):
-    return x.reshape(B, H, W, x.shape[1]).permute(0, 3, 1, 2)
 
 
 # ------------------------------------------------------------------------------------------------------------------ (a)
@@ -93,7 +55,7 @@ def test_conv_pm_bf16(gpu, kh, kw, cins, bufs, cout, relu):
     for i, (s, c) in enumerate(zip(srcs, cins)):
         assert s.grad.dtype == torch.float32 and bool((s.grad[:, c:] == 0).all()), "gradient in a padding channel"
         got[f"dx{i}"] = nchw(s.grad[:, :c], B, H, W)
-    gate(got, ref64, cpu16)
+    within_2x_cpu_autocast(got, ref64, cpu16)
 
 
 # ------------------------------------------------------------------------------------------------------------------ (b)
@@ -133,7 +95,7 @@ def test_gru_pass_bf16(gpu, kh, kw):
     for k, v in G.items():
         assert v.grad is not None and v.grad.dtype == torch.float32, k
         got["d" + k] = v.grad
-    gate(got, ref64, cpu16, expect=["d" + k for k in P])
+    within_2x_cpu_autocast(got, ref64, cpu16, expect=["d" + k for k in P])
 
 
 # ------------------------------------------------------------------------------------------------------------------ (c)
@@ -191,7 +153,7 @@ def test_update_block_three_chained_calls_bf16(gpu):
     for k, v in L.items():
         assert v.grad is not None and v.grad.dtype == torch.float32, k
         got["d/d" + k] = v.grad
-    gate(got, ref64, cpu16, expect=["d/d" + k for k in holder.state_dict()])
+    within_2x_cpu_autocast(got, ref64, cpu16, expect=["d/d" + k for k in holder.state_dict()])
 
 
 # ------------------------------------------------------------------------------------------------------------------ (d)

@@ -49,6 +49,7 @@ def wide(t: torch.Tensor, ld: int, first: int = 0) -> torch.Tensor:
     return buf[:, first:first + t.shape[1]]
 
 
+# local, not op_gate's: this file also runs as a recording script, before the repository root is on sys.path
 def nchw(t: torch.Tensor, B, H, W) -> torch.Tensor:
     return t.view(B, H, W, -1).permute(0, 3, 1, 2).contiguous()
 

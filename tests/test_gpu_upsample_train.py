@@ -1,7 +1,7 @@
 """Training through the upsampling seams (K12e): the backward of SEA-RAFT's `upsample_data` (`pfk_convex_upsample_info_bwd_pm_f32`), the
 autograd node on it (`train_sea.upsample_data_train`) and `accelerate(model, train_upsample=True)` on seam B5 and on `upsample_data`.
 
-Kernel gates: 1-4 of tests/test_gpu_raft_bwd_kernels.py's docstring, with its harness.  The reference is float64 autograd through
+Kernel gates: 1-4 of tests/op_gate.py's docstring, with its harness.  The reference is float64 autograd through
 `sea_seam_model.upsample_data_torch` on the kernel's own fp32 inputs.  The per-element bounds are `convex_case`'s derivation with
 C = 2 + n_info channels in place of 2: a softmax weight is off by at most k_w = 2 spread + 19 units of 2^-24 relative; dw_k = sum_c g_c
 v_c,k has C products and C - 1 additions, 2C - 1 roundings where the two-channel kernel has 3, so
@@ -27,19 +27,14 @@ import torch
 import torch.nn.functional as F
 
 from sea_seam_model import upsample_data_torch
-from test_gpu_raft_bwd_kernels import FLOOR, convex_case, gates
-from test_gpu_sea_train import BLOCK_TOL, SENTINEL, Rows, scale_close
+from op_gate import BLOCK_TOL, FLOOR, SENTINEL, Rows, gates, pm, scale_close
+from op_refs import convex_case
 
 pytestmark = pytest.mark.gpu
 
 # (B, H, W, logit_scale, n_info): H = 1 | W = 1 | M = 234 (no multiple of 4; a batch boundary the neighbourhoods must not cross) |
 # a saturated softmax | n_info = 1, 8 (the maximum), 0
 CASES = [(2, 1, 5, 1.0, 4), (1, 6, 1, 1.0, 4), (2, 9, 13, 1.0, 4), (2, 9, 13, 40.0, 4), (2, 3, 5, 1.0, 1), (2, 3, 5, 1.0, 8), (2, 3, 5, 1.0, 0)]
-
-
-def _pm(t):
-    B, C, H, W = t.shape
-    return t.permute(0, 2, 3, 1).reshape(B * H * W, C)      # (C = 0 included)
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,11 +62,11 @@ def info_case(B, H, W, logit_scale, n):
         gsub = torch.cat([gf.double(), gi64], 1).view(B, -1, H, 8, W, 8).permute(0, 1, 3, 5, 2, 4).abs()   # [B, C, sy, sx, H, W]
         T = (gsub[:, :, None] * v.abs()[:, :, :, None, None]).sum(1)                                 # [B, 9, 8, 8, H, W]
         gmask_mag = wgt * (T + (wgt * T).sum(1, keepdim=True))
-    pm576 = lambda t: _pm(t.reshape(B, 576, H, W))
+    pm576 = lambda t: pm(t.reshape(B, 576, H, W))
     k_w = 2 * spread + 19
     k_mask = pm576((2 * k_w + 12 + (2 * C - 1))[:, None].expand(B, 9, 8, 8, H, W))
     return {"flow": flow, "info": info, "mask": mask, "gf": gf, "gi": gi, "gmask": pm576(gmask), "gmask_mag": pm576(gmask_mag),
-            "gflow": _pm(gflow), "gflow_mag": _pm(gflow_mag), "ginfo": _pm(ginfo)[:, :n], "ginfo_mag": _pm(ginfo_mag)[:, :n],
+            "gflow": pm(gflow), "gflow_mag": pm(gflow_mag), "ginfo": pm(ginfo)[:, :n], "ginfo_mag": pm(ginfo_mag)[:, :n],
             "k_mask": k_mask, "k_flow": 9 * 64 + float(k_w.max()) + 2}
 
 
@@ -82,9 +77,9 @@ class InfoRun:
     def __init__(self, gpu, B, H, W, logit_scale, n):
         self.gpu, self.n, self.M = gpu, n, B * H * W
         self.c = c = info_case(B, H, W, logit_scale, n)
-        self.flow = Rows(self.M, 2, gpu, _pm(c["flow"]), pad=2)
-        self.info = Rows(self.M, n, gpu, _pm(c["info"]), pad=4)
-        self.mask = Rows(self.M, 576, gpu, _pm(c["mask"]))
+        self.flow = Rows(self.M, 2, gpu, pm(c["flow"]), pad=2)
+        self.info = Rows(self.M, n, gpu, pm(c["info"]), pad=4)
+        self.mask = Rows(self.M, 576, gpu, pm(c["mask"]))
         self.gf, self.gi = c["gf"].to(gpu), c["gi"].to(gpu)
         assert (self.flow.ld, self.info.ld, self.mask.ld) == (4, n + 4, 580)
 
@@ -148,9 +143,9 @@ def test_agrees_with_raft_reference(gpu, logit_scale):
     """n_info = 0 against the float64 reference and bounds that hold `pfk_convex_upsample_bwd_f32` (test_convex_upsample_bwd)"""
     B, H, W = 2, 9, 13
     c, M = convex_case(B, H, W, logit_scale), B * H * W
-    flow = Rows(M, 2, gpu, _pm(c["flow"]), pad=2)
+    flow = Rows(M, 2, gpu, pm(c["flow"]), pad=2)
     none = Rows(M, 0, gpu, torch.empty(M, 0), pad=4)
-    mask = Rows(M, 576, gpu, _pm(c["mask"]))
+    mask = Rows(M, 576, gpu, pm(c["mask"]))
     gmask, gflow, ginfo = Rows(M, 576, gpu, pad=8), Rows(M, 2, gpu, pad=2), Rows(M, 0, gpu, pad=4)
     torch.ops.pfk.convex_upsample_info_bwd(flow.rows, none.rows, mask.rows, c["go"].to(gpu), None, gmask.rows, gflow.rows, ginfo.rows)
     torch.cuda.synchronize()
@@ -158,7 +153,7 @@ def test_agrees_with_raft_reference(gpu, logit_scale):
     assert bool((ginfo.flat == SENTINEL).all()), "n_info = 0 but the info gradient buffer was written"
     what = f"convex_upsample_info_bwd n_info 0 x{logit_scale:g} vs RAFT's reference"
     gates(what + " grad_mask", gmask.rows, c["gmask"], c["gmask_mag"], c["k_mask"], floor=FLOOR)
-    gates(what + " grad_flow", gflow.rows, _pm(c["gflow"]), _pm(c["gflow_mag"]), c["k_flow"], floor=FLOOR)
+    gates(what + " grad_flow", gflow.rows, pm(c["gflow"]), pm(c["gflow_mag"]), c["k_flow"], floor=FLOOR)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

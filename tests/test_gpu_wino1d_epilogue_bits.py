@@ -130,7 +130,8 @@ def test_epilogue_bits(gpu, case):
 
 @pytest.mark.parametrize("case", CASES)
 def test_fp64_gate_sentinels_and_repeat(gpu, case):
-    from test_gpu_winograd1d import _close32, ref_q, ref_zr
+    from op_gate import close32
+    from op_refs import ref_q, ref_zr
     r = run(case)
     M, Ch, Ci, real, a0 = r["M"], r["Ch"], r["Ci"], r["real"], r["act0"]
     reals = [Ch, real]
@@ -138,14 +139,14 @@ def test_fp64_gate_sentinels_and_repeat(gpu, case):
     assert bool((r["z"][M:] == SENTINEL).all()) and bool((r["rh"][M:] == SENTINEL).all()), "z|r wrote rows past M"
     assert r["zr_again"], "the same z|r launch gave other bits"
     z_ref, rh_ref = ref_zr([a0[:, :Ch], a0[:, Ch + Ci:]], reals, r["wzr"], r["bzr"], r["ctx0"]["zr"], a0[:, :Ch], r["shape"], r["k"])
-    rz, rr = _close32(r["z"][:M], z_ref, "z"), _close32(r["rh"][:M], rh_ref, "r*h")
+    rz, rr = close32(r["z"][:M], z_ref, "z"), close32(r["rh"][:M], rh_ref, "r*h")
     assert torch.equal(r["act_q"][:, Ch:], a0[:, Ch:]), "q wrote outside h"
     assert torch.equal(r["z_q"], r["z"]) and torch.equal(r["rh_q"], r["rh"]), "q wrote into z / r*h"
     assert r["q_again"], "the same q launch gave other bits"
     for n, b in r["bufs"].items():
         assert torch.equal(b, r["bufs0"][n]), "wrote into the context rows or their neighbours"
     h_ref = ref_q([r["rh"][:M], a0[:, Ch + Ci:]], reals, r["wq"], r["bq"], r["ctx0"]["q"], r["z"][:M], a0[:, :Ch], r["shape"], r["k"])
-    rq = _close32(r["act_q"][:, :Ch], h_ref, "h")
+    rq = close32(r["act_q"][:, :Ch], h_ref, "h")
     print(f"[ratio] wino1d epilogue {case} z={rz:.3f} rh={rr:.3f} h={rq:.3f}")
 
 

@@ -11,20 +11,12 @@ import torch.nn.functional as F
 
 from oracle import raft_oracle as O
 from pfk_ctypes import Desc as _Desc, Src as _Src
+from op_gate import pm, unpm
 
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR = 0
 RATIO = 4.0
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous().cuda()
-
-
-def unpm(x, B, H, W):
-    return x.reshape(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 def _case(B, H, W, cin, cout, seed=3):
@@ -61,7 +53,7 @@ def _direct(src, B, H, W, wt, bias, cout, relu, scale):
 
 def _check(B, H, W, cin, cout, relu, scale):
     x, wt, bias = _case(B, H, W, cin, cout)
-    src = pm(x)
+    src = pm(x, "cuda")
     ref = _ref64(x, wt, bias, relu, scale)
     ew = (unpm(_wino(src, B, H, W, wt, bias, cout, relu, scale), B, H, W).double() - ref).abs().max().item()
     ed = (unpm(_direct(src, B, H, W, wt, bias, cout, relu, scale), B, H, W).double() - ref).abs().max().item()
@@ -94,14 +86,14 @@ def test_strided_source_and_channel_slice(gpu):
     x, wt, bias = _case(B, H, W, cin, cout)
     M = B * H * W
     wide = torch.randn(M, cin + 40, device=gpu)
-    wide[:, 12:12 + cin] = pm(x)
+    wide[:, 12:12 + cin] = pm(x, "cuda")
     buf = torch.full((M, cout + 12), 5.0, device=gpu)
     out = buf[:, 4:4 + cout]
     _wino(wide[:, 12:12 + cin], B, H, W, wt, bias, cout, True, 1.0, out=out)
-    dense = _wino(pm(x), B, H, W, wt, bias, cout, True, 1.0)
+    dense = _wino(pm(x, "cuda"), B, H, W, wt, bias, cout, True, 1.0)
     assert torch.equal(out, dense)
     assert bool((buf[:, :4] == 5.0).all()) and bool((buf[:, 4 + cout:] == 5.0).all()), "wrote outside its channel slice"
-    ed = (unpm(_direct(pm(x), B, H, W, wt, bias, cout, True, 1.0), B, H, W).double() - _ref64(x, wt, bias, True, 1.0)).abs().max()
+    ed = (unpm(_direct(pm(x, "cuda"), B, H, W, wt, bias, cout, True, 1.0), B, H, W).double() - _ref64(x, wt, bias, True, 1.0)).abs().max()
     ew = (unpm(out, B, H, W).double() - _ref64(x, wt, bias, True, 1.0)).abs().max()
     assert ew <= RATIO * ed + 1e-6
 
@@ -110,7 +102,7 @@ def test_strided_source_and_channel_slice(gpu):
 def test_cout_active_has_the_full_launch_bits(gpu, B):
     H, W, cin, cout = 55, 128, 128, 512
     x, wt, bias = _case(B, H, W, cin, cout)
-    src = pm(x)
+    src = pm(x, "cuda")
     full = _wino(src, B, H, W, wt, bias, cout, True, 1.0)
     half = torch.full_like(full, 7.0)
     _wino(src, B, H, W, wt, bias, cout, True, 1.0, out=half, cout_active=256)
@@ -121,7 +113,7 @@ def test_cout_active_has_the_full_launch_bits(gpu, B):
 def test_deterministic(gpu):
     B, H, W, cin, cout = 8, 55, 128, 256, 192
     x, wt, bias = _case(B, H, W, cin, cout)
-    src = pm(x)
+    src = pm(x, "cuda")
     a = _wino(src, B, H, W, wt, bias, cout, True, 1.0)
     for _ in range(3):
         assert torch.equal(_wino(src, B, H, W, wt, bias, cout, True, 1.0), a)

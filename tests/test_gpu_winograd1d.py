@@ -1,6 +1,6 @@
 """`pfk_conv1d_wino_f32` (torch.ops.pfk.conv2d_wino1d): the SepConvGRU's 1x5 / 5x1 gate convolutions as 1-D Winograd F(4,5).
 
-Every result is compared against float64 restated on what the launch consumed (the helpers' logic of test_gpu_gru_schedules.py).
+Every result is compared against float64 restated on what the launch consumed (`ref_zr` / `ref_q` of tests/op_refs.py).
 Gates: the gate epilogues' own — z, r*h, h inside 3e-5 + 2e-5 |ref| — and for LINEAR |err| <= 2e-5 (1 + |ref|).  A gate relative to
 the direct kernel's error is deliberately not used: F(4,5)'s pre-activation error is 6 to 8 times the direct form's while staying
 at 6e-6 absolute (tests/test_wino1d_packing.py measures it on the CPU)."""
@@ -8,7 +8,9 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from op_gate import close32
+from op_refs import conv64, ref_q, ref_zr
 
 pytestmark = pytest.mark.gpu
 
@@ -22,39 +24,6 @@ PAD_ROWS = 64
 def _spec(model):
     from ptlflow_amd.update import basic_spec, gma_spec
     return {"raft": basic_spec, "gma": gma_spec}[model]()
-
-
-def _close32(got, ref, what):
-    """|got - ref| <= 3e-5 + 2e-5 |ref|; returns the worst err / limit"""
-    err = (got.double().cpu() - ref).abs()
-    lim = 3e-5 + 2e-5 * ref.abs()
-    ratio = float((err / lim).max())
-    assert bool((err <= lim).all()), f"{what}: {int((err > lim).sum())} of {err.numel()} outside 3e-5 + 2e-5|ref|, worst ratio {ratio:.2f}"
-    return ratio
-
-
-def _conv64(srcs, reals, weight, bias, res, b, h, w, kh, kw):
-    """fp64 'same' convolution of pixel-major rows: cat(src[:, :real]) x weight [cout, sum(reals), kh, kw] + bias + res, [M, cout]"""
-    x = torch.cat([s.cpu()[:, :r].double() for s, r in zip(srcs, reals)], 1)
-    x = x.reshape(b, h, w, -1).permute(0, 3, 1, 2)
-    v = F.conv2d(x, weight.double(), padding=(kh // 2, kw // 2)).permute(0, 2, 3, 1).reshape(b * h * w, -1)
-    if bias is not None:
-        v = v + bias.double().cpu()
-    if res is not None:
-        v = v + res.double().cpu()
-    return v
-
-
-def ref_zr(srcs, reals, weight, bias, res, h_rows, shape, k):
-    v = _conv64(srcs, reals, weight, bias, res, *shape, *k)
-    Ch = v.shape[1] // 2
-    return torch.sigmoid(v[:, :Ch]), torch.sigmoid(v[:, Ch:]) * h_rows.double().cpu()
-
-
-def ref_q(srcs, reals, weight, bias, res, z_rows, h_rows, shape, k):
-    v = _conv64(srcs, reals, weight, bias, res, *shape, *k)
-    z, h = z_rows.double().cpu(), h_rows.double().cpu()
-    return (1 - z) * h + z * torch.tanh(v)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the gate epilogues
@@ -95,7 +64,7 @@ def test_gates_ragged(gpu, wset, with_ctx):
     assert torch.equal(act, act0), "z|r wrote into the [h | context | motion] rows"
     assert bool((z[M:] == SENTINEL).all()) and bool((rh[M:] == SENTINEL).all()), "z|r wrote rows past M"
     z_ref, rh_ref = ref_zr([act0[:, :Ch], act0[:, Ch + Ci:]], reals, wzr, bzr, ctx["zr"], act0[:, :Ch], shape, k)
-    rz, rr = _close32(z[:M], z_ref, "z"), _close32(rh[:M], rh_ref, "r*h")
+    rz, rr = close32(z[:M], z_ref, "z"), close32(rh[:M], rh_ref, "r*h")
     z1, rh1 = z.clone(), rh.clone()
     # the same launch again (the gate epilogues' own store path: parked in LDS, walked as rows): identical bits
     z.fill_(SENTINEL), rh.fill_(SENTINEL)
@@ -108,7 +77,7 @@ def test_gates_ragged(gpu, wset, with_ctx):
     assert torch.equal(act[:, Ch:], act0[:, Ch:]), "q wrote outside h"
     assert torch.equal(z, z1) and torch.equal(rh, rh1), "q wrote into z / r*h"
     h_ref = ref_q([rh1[:M], act0[:, Ch + Ci:]], reals, wq, bq, ctx["q"], z1[:M], act0[:, :Ch], shape, k)
-    rq = _close32(act[:, :Ch], h_ref, "h")
+    rq = close32(act[:, :Ch], h_ref, "h")
     h1 = act[:, :Ch].clone()
     act[:, :Ch] = act0[:, :Ch]      # q updates h in place: the same launch again from the same h
     torch.ops.pfk.conv2d_wino1d([rh[:M], motion], B, H, W, kh, kw, pq, bq, Ch, EPI_GRU_Q, False, 1.0, None, act[:, :Ch], z, None, ctx["q"])
@@ -139,7 +108,7 @@ def _linear(b, h, w, kh, kw, cin, cout, relu=False, scale=1.0, seed=0, src_ld=No
     assert torch.equal(buf, buf0), "wrote into its source"
     assert bool((frame[M:] == SENTINEL).all()), "wrote rows past M"
     assert bool((frame[:, cout:] == SENTINEL).all()), "wrote columns past cout"
-    v = _conv64([src], [cin], wt, bias, None, b, h, w, kh, kw)
+    v = conv64([src], [cin], wt, bias, None, b, h, w, kh, kw)
     if relu:
         v = torch.relu(v)
     v = v * scale
@@ -256,5 +225,5 @@ def test_engine_rule(gpu):
                              eng.h_view, eng.zbuf, None, eng.workspace, eng.ctx["q" + sfx])
     torch.cuda.synchronize()
     assert torch.equal(eng.hx[:, :Ch], h_d), "winograd=False is not the direct path"
-    r = _close32(h_w, h_d.double().cpu(), "h through F(4,5) against h through the direct kernels")
+    r = close32(h_w, h_d.double().cpu(), "h through F(4,5) against h through the direct kernels")
     print(f"[engine] batch {b}: worst |h_winograd - h_direct| / (3e-5 + 2e-5 |h|) = {r:.3f}")

@@ -27,6 +27,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from op_gate import pm, unpm
+
 pytestmark = pytest.mark.gpu
 
 EPI_LINEAR = 0
@@ -61,15 +63,6 @@ for _f, (_relu, _relu2, _scale) in RES_FORMS.items():
 RES["EC_resoff3"] = dict(shape="C", relu=True, relu2=True, scale=0.25, src_off=12, src_ld=104, out_ld=256, out_off=32, res_ld=200,
                          res_off=3)
 CASES = {**PLAIN, **RES}
-
-
-def pm(x):
-    B, C, H, W = x.shape
-    return x.permute(0, 2, 3, 1).reshape(B * H * W, C).contiguous()
-
-
-def unpm(x, B, H, W):
-    return x.reshape(B, H, W, -1).permute(0, 3, 1, 2).cpu()
 
 
 @functools.lru_cache(maxsize=None)

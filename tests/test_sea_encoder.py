@@ -241,5 +241,5 @@ def test_stem2_symbols_validate_their_arguments_without_a_gpu(lib):
 
 def test_winograd_residual_symbol_refuses_without_a_gpu(lib):
     assert lib.pfk_conv2d_wino_res_f32(None, None) == -1
-    from test_capi import declared
+    from pfk_ctypes import declared
     assert {"pfk_conv2d_wino_res_f32", "pfk_conv_stem2_f32", "pfk_conv_stem2_b16"} <= set(declared())

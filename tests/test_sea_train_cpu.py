@@ -14,6 +14,8 @@ import torch.nn.functional as F
 
 import ptlflow_amd
 from oracle import ref_loader
+from op_gate import rel
+from op_refs import dwconv_bwd_ref, gelu_bwd_ref, layernorm_bwd_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sea_raft_update_grad.pt")
@@ -133,38 +135,6 @@ def test_accelerate_argument_errors():
 # ---------------------------------------------------------------------------------------------------------------------
 # the formulas of include/pfk.h in float64 against autograd
 # ---------------------------------------------------------------------------------------------------------------------
-def layernorm_bwd_ref(xhat, rstd, gamma, dy):
-    """(b): rows [M, C]"""
-    g = dy * gamma
-    du = rstd[:, None] * (g - g.mean(1, keepdim=True) - xhat * (g * xhat).mean(1, keepdim=True))
-    return du, (dy * xhat).sum(0), dy.sum(0)
-
-
-def dwconv_bwd_ref(x, du, w, B, H, W):
-    """(c): rows [M, C], w [C, k, k]; shifts written out tap by tap, zero outside the image, never across images"""
-    C, k = w.shape[0], w.shape[-1]
-    R = k // 2
-    xi, di = x.view(B, H, W, C), du.view(B, H, W, C)
-    xp, dp = F.pad(xi, (0, 0, R, R, R, R)), F.pad(di, (0, 0, R, R, R, R))
-    dx = torch.zeros_like(xi)
-    dw = torch.zeros_like(w)
-    for ky in range(k):
-        for kx in range(k):
-            # du[(y - ky + R, x - kx + R)] = dp[y - ky + 2R, x - kx + 2R];  in[(y + ky - R, x + kx - R)] = xp[y + ky, x + kx]
-            dx = dx + w[:, ky, kx] * dp[:, 2 * R - ky:2 * R - ky + H, 2 * R - kx:2 * R - kx + W]
-            dw[:, ky, kx] = (di * xp[:, ky:ky + H, kx:kx + W]).sum((0, 1, 2))
-    return dx.reshape(-1, C), dw, du.sum(0)
-
-
-def gelu_bwd_ref(x, dy):
-    """(d)"""
-    return dy * (0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-x * x / 2) / math.sqrt(2 * math.pi))
-
-
-def rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300))
-
-
 @pytest.mark.parametrize("B,H,W,C,k,zero", [(2, 5, 6, 8, 7, False), (1, 9, 11, 12, 3, False), (2, 4, 7, 16, 5, True), (1, 1, 5, 8, 7, True)])
 def test_formulas_equal_autograd(B, H, W, C, k, zero):
     g = torch.Generator().manual_seed(B * 100 + H * 10 + k)
