@@ -30,8 +30,8 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, eligible
-from .packing import pack_conv_operand, pack_wino_weight
-from .update import CONV_PRECISIONS, EPI_LINEAR
+from .conv_path import resolve
+from .packing import pack_wino_weight
 
 # (name, cin, cout, stride, has_downsample) of the six residual blocks, extractor.py:150-153
 _BLOCKS = (("layer1.0", 64, 64, 1, False), ("layer1.1", 64, 64, 1, False), ("layer2.0", 64, 96, 2, True), ("layer2.1", 96, 96, 1, False),
@@ -76,15 +76,12 @@ class EncoderEngine:
         self.wino_min_pixels = WINO_MIN_PIXELS if wino_min_pixels is None else wino_min_pixels
         if norm not in ("instance", "batch", "none"):
             raise ValueError(norm)
-        if conv_precision not in CONV_PRECISIONS:
-            raise ValueError(f"conv_precision must be one of {sorted(CONV_PRECISIONS)}, got {conv_precision!r}")
+        # "bf16": K8b (`pfk_conv2d_b16`, UpdateEngine's docstring) — bf16 activation storage between the layers, instance norms
+        # included (statistics and normalisation in fp32 arithmetic on the bf16 rows, as F.instance_norm under autocast)
+        self.path = resolve(conv_precision)
         self.ops = torch.ops.pfk
         self.norm = norm
         self.device = device
-        self.nsplit = CONV_PRECISIONS[conv_precision]
-        # "bf16": K8b (`pfk_conv2d_b16`, UpdateEngine's docstring) — bf16 activation storage between the layers, instance norms
-        # included (statistics and normalisation in fp32 arithmetic on the bf16 rows, as F.instance_norm under autocast)
-        self.b16 = conv_precision == "bf16"
         self._ws: Optional[torch.Tensor] = None
         self.winograd = True       # False: the direct kernel everywhere (A/B timing, tests); "always": Winograd wherever its weight exists
         self.fuse_norms = True     # False: every instance norm as its own statistics and apply launches (A/B timing, tests)
@@ -110,8 +107,8 @@ class EncoderEngine:
         fp32 engine of a non-small encoder, square and of a width in the threshold table, also the transformed weight of the Winograd
         kernels `_use_wino` may select"""
         cin = w.shape[1]
-        W[key + ".w"], W[key + ".b"] = pack_conv_operand(w, [(0, cin, cin)], self.b16, self.nsplit), b
-        if wino and self.nsplit == 0 and not self.b16 and not self.small and cin == w.shape[0] and cin in self.wino_min_pixels:
+        W[key + ".w"], W[key + ".b"] = self.path.pack(w, [(0, cin, cin)]), b
+        if wino and self.path.fp32_tiles and not self.small and cin == w.shape[0] and cin in self.wino_min_pixels:
             W[key + ".ww"] = pack_wino_weight(w.cpu()).to(self.device)
 
     def pack(self, P: Dict[str, torch.Tensor]) -> None:
@@ -135,17 +132,12 @@ class EncoderEngine:
     # ------------------------------------------------------------------ kernels
     def _conv(self, x, B, H, W, k, key, cout, stride=1, relu=False, residual=None, relu2=False, fp32_out=None):
         M = B * _out(H, stride) * _out(W, stride)
-        if self.b16:
-            # bf16 rows out, also in front of an instance norm: under the reference's autocast switch a convolution returns a
-            # 16-bit tensor and F.instance_norm (fp32 arithmetic) reads that — statistics and normalisation of the rounded values
-            # (half the bytes of the three passes over the largest activations of the forward); fp32 only for the network's output
-            out = torch.empty(M, cout, device=self.device, dtype=torch.float32 if fp32_out else torch.bfloat16)
-            self.ops.conv2d_b16([x], B, H, W, k, k, self.w[key + ".w"], self.w[key + ".b"], cout, EPI_LINEAR, relu, 1.0, out,
-                                None, None, None, None, residual, stride, relu2)
-            return out
-        out = torch.empty(M, cout, device=self.device, dtype=torch.float32)
-        self.ops.conv2d([x], B, H, W, k, k, self.w[key + ".w"], self.w[key + ".b"], cout, EPI_LINEAR, relu, 1.0, out,
-                        None, None, None, None, residual, stride, relu2)
+        # bf16 rows out on K8b, also in front of an instance norm: under the reference's autocast switch a convolution returns a
+        # 16-bit tensor and F.instance_norm (fp32 arithmetic) reads that — statistics and normalisation of the rounded values
+        # (half the bytes of the three passes over the largest activations of the forward); fp32 only for the network's output
+        out = torch.empty(M, cout, device=self.device, dtype=torch.float32 if fp32_out else self.path.dtype)
+        self.path.conv(self.ops, srcs=[x], B=B, H=H, W=W, kh=k, kw=k, weight=self.w[key + ".w"], bias=self.w[key + ".b"], cout=cout,
+                       out=out, relu=relu, residual=residual, stride=stride, relu2=relu2)
         return out
 
     def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
@@ -227,7 +219,7 @@ class EncoderEngine:
         mean = torch.empty(B * C, device=self.device, dtype=torch.float32)
         rstd = torch.empty(B * C, device=self.device, dtype=torch.float32)
         self.ops.instnorm_stats(x, B, HW, EPS, mean, rstd, self._workspace(self.ops.instnorm_workspace_bytes(B, C)))
-        out = torch.empty(x.shape[0], C, device=self.device, dtype=torch.bfloat16) if (self.b16 and x.dtype != torch.bfloat16) else x
+        out = torch.empty(x.shape[0], C, device=self.device, dtype=torch.bfloat16) if (self.path.b16 and x.dtype != torch.bfloat16) else x
         self.ops.norm_apply(x, mean, rstd, residual, out, B, HW, relu, relu2)      # (bf16 rows: in place, like the fp32 path)
         return out
 
@@ -291,18 +283,18 @@ class EncoderEngine:
         if B > max_b:
             return torch.cat([self(img[i:i + max_b]) for i in range(0, B, max_b)], 0)
         # K8b: the MFMA stem kernels round to bf16 themselves (widths 32 / 64), also in front of an instance norm (`_conv`'s note)
-        stem_b16 = self.b16 and self.stem_dim in (32, 64)
+        stem_b16 = self.path.b16 and self.stem_dim in (32, 64)
         x = torch.empty(B * H1 * W1, self.stem_dim, device=self.device, dtype=torch.bfloat16 if stem_b16 else torch.float32)
         self._stem(img, x)
         # the norm passes folded into the Winograd launches: the fp32 BasicEncoder / ResNet engines with instance norm
-        fused = self.fuse_norms and self.norm == "instance" and self.nsplit == 0 and not self.b16 and not self.small
+        fused = self.fuse_norms and self.norm == "instance" and self.path.fp32_tiles and not self.small
         xst = None
         name0, _, cout0, stride0, _ = self.blocks[0]
         if fused and stride0 == 1 and self._use_wino(f"{name0}.conv1", cout0, B * H1 * W1):
             xst = (*self._stats(x, B, H1 * W1), True)      # the stem's output stays raw: the first block normalises it on load
         elif self.norm == "instance":
             x = self._inorm(x, B, H1 * W1, relu=True)
-        elif self.b16 and not stem_b16:
+        elif self.path.b16 and not stem_b16:
             x = x.to(torch.bfloat16)
         h, w = H1, W1
         for name, _cin, cout, stride, ds in self.blocks:

@@ -40,6 +40,7 @@ import torch
 
 from . import load_native
 from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixel_rows
+from .conv_path import PRECISIONS, check_precision
 from .corr import get_corr_block as _pfk_get_corr_block
 from .encoder import PfkEncoder
 from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
@@ -118,11 +119,9 @@ def _sea_precision(sea_raft_update, option: str = "sea_raft_update") -> Optional
     """`accelerate`'s `sea_raft_update` / `sea_raft_encoders` -> the SEA seams' precision, None = not installed"""
     if sea_raft_update is False or sea_raft_update is None:
         return None
-    if sea_raft_update is True or sea_raft_update == "fp32":
+    if sea_raft_update is True:
         return "fp32"
-    if sea_raft_update == "bf16":
-        return "bf16"
-    raise ValueError(f"{option} must be False, True, 'fp32' or 'bf16', got {sea_raft_update!r}")
+    return check_precision(sea_raft_update, PRECISIONS, option, "False, True, 'fp32' or 'bf16'")
 
 
 # (module of the class, class name) of SEA-RAFT's ResNet encoders (sea_raft/extractor.py:6-116); wrapped only with
@@ -655,8 +654,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     `pfk_convex_upsample_info_bwd_pm_f32`, counted in the seam's ``train_calls``.  Everything else, and every
     gradient graph while it is off, goes to the model's own method.  Raises ValueError when the model gets neither seam, and on a
     SEA-RAFT model unless ``sea_raft_update`` is True or "fp32".  A second call with another value switches the installed seams."""
-    from .train import check_precision
-    check_precision(train_precision, "train_precision")
+    check_precision(train_precision, PRECISIONS, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
         raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path sits behind the fp32 seams; "

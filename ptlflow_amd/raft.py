@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import load_native
+from .conv_path import FP32, PRECISIONS, check_precision
 from .corr import AlternateCorrBlock, CorrBlock
 from .update import SMALL_GRID_PIXELS, UpdateEngine, UpdateSpec, basic_spec, gma_spec, small_spec
 from .synth import synth_state_dict, update_block_shapes
@@ -151,8 +152,7 @@ class RAFT(nn.Module):
         # trains under torch.autocast(bfloat16): forward, data and weight gradients on the bf16 matrix cores (ptlflow_amd/train.py,
         # DESIGN.md K12b); encoders, volume, lookup, upsampling, the hidden state and every parameter gradient stay fp32.
         # (`conv_precision` below is about inference only.)
-        from .train import check_precision
-        self.train_precision = check_precision(train_precision, "train_precision")
+        self.train_precision = check_precision(train_precision, PRECISIONS, "train_precision")
         # None: the mask tail as ONE kernel that never writes the [M, 576] mask (`UpdateEngine.mask_upsample`; bit-identical
         # to the two launches) where it pays, from `SMALL_GRID_PIXELS` up; True / False: always (where the kernel applies) / never.
         self.fuse_mask_upsample = fuse_mask_upsample
@@ -626,7 +626,6 @@ class GMA(RAFT):
         """Attention.forward, content-only, one head (gma_utils.py:50-78) on libpfk: `to_qk` as two 1x1 convolutions on the
         MFMA conv kernel (q and k land in their own pixel-major matrices), the N x N similarity as K1 (`pfk_corr_volume_f32`
         with scale = dim_head^-0.5: the same all-pairs inner product as the correlation volume), and an in-place row softmax."""
-        from .packing import pack_conv_weight
         ops = torch.ops.pfk
         B, C, h, w = inp.shape
         N = h * w
@@ -637,7 +636,7 @@ class GMA(RAFT):
         key = (wv.data_ptr(), wv._version, wv.device)
         if getattr(self, "_qk_key", None) != key:
             wq, wk = wv.detach().float().chunk(2, dim=0)
-            self._qk_w = (pack_conv_weight(wq.contiguous(), [(0, C, C)]), pack_conv_weight(wk.contiguous(), [(0, C, C)]))
+            self._qk_w = (FP32.pack(wq.contiguous(), [(0, C, C)]), FP32.pack(wk.contiguous(), [(0, C, C)]))
             self._qk_key = key
         x = inp.float().permute(0, 2, 3, 1)
         x = x.reshape(B * N, C) if x.is_contiguous() else x.contiguous().view(B * N, C)
@@ -645,7 +644,7 @@ class GMA(RAFT):
         q = torch.empty(B * N, d, device=inp.device, dtype=torch.float32)
         k = torch.empty(B * N, d, device=inp.device, dtype=torch.float32)
         for wt, dst in zip(self._qk_w, (q, k)):
-            ops.conv2d([x], B, h, w, 1, 1, wt, None, d, 0, False, 1.0, dst, None, None, None, None)
+            FP32.conv(ops, srcs=[x], B=B, H=h, W=w, kh=1, kw=1, weight=wt, bias=None, cout=d, out=dst)
         attn = torch.empty(B, N, N, device=inp.device, dtype=torch.float32)
         ops.corr_volume(q.view(B, N, d), k.view(B, N, d), float(att.scale), attn)
         ops.softmax_rows(attn)

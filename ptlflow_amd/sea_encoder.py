@@ -30,9 +30,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from ._seam import WrappedModule, eligible, pixel_rows
+from .conv_path import PRECISIONS, check_precision
 from .encoder import EncoderEngine, _out
 
-SEA_ENCODER_PRECISIONS = ("fp32", "bf16")
 STEM_DIM = 64              # the width pfk_conv_stem2 is built for (every shipped `initial_dim`)
 # Winograd rule of the fp32 engine: width -> the fewest pixels (B * H * W of the launch) at which `pfk_conv2d_wino_f32` /
 # `pfk_conv2d_wino_res_f32` measured faster than `pfk_conv2d_f32` (scripts/wino_res_bench.py, table in DESIGN.md §SEA-RAFT); a width
@@ -119,9 +119,7 @@ class ResNetFPNEngine(EncoderEngine):
     """Packed weights of one ResNetFPN; `engine(x)` maps ``x`` [B, 3 or 6, H, W] fp32 to [B, out_dim, H/8, W/8] (channels-last)."""
 
     def __init__(self, params: Dict[str, torch.Tensor], device: torch.device, precision: str = "fp32"):
-        if precision not in SEA_ENCODER_PRECISIONS:
-            raise ValueError(f"precision must be one of {SEA_ENCODER_PRECISIONS}, got {precision!r}")
-        self.precision = precision
+        self.precision = check_precision(precision, PRECISIONS)
         shapes = {k: tuple(v.shape) for k, v in params.items()}
         table = block_table(shapes)
         if table is None:
@@ -161,7 +159,7 @@ class ConvEngine(EncoderEngine):
 
     @torch.no_grad()
     def __call__(self, rows: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
-        if self.b16 and rows.dtype != torch.bfloat16:
+        if self.path.b16 and rows.dtype != torch.bfloat16:
             rows = rows.to(torch.bfloat16)        # what autocast does to the convolution's input
         y = self._conv3(rows, B, H, W, "conv", self.out_dim, relu=False, fp32_out=True)
         return y.view(B, H, W, self.out_dim).permute(0, 3, 1, 2)
@@ -190,9 +188,7 @@ class PfkResNetEncoder(WrappedModule):
         self._last_version = -1
 
     def set_precision(self, precision: str) -> None:
-        if precision not in SEA_ENCODER_PRECISIONS:
-            raise ValueError(f"precision must be one of {SEA_ENCODER_PRECISIONS}, got {precision!r}")
-        if precision != self.precision:
+        if check_precision(precision, PRECISIONS) != self.precision:
             self.precision = precision
             self._engine, self._versions, self._last_out = None, None, None
 

@@ -49,12 +49,9 @@ from typing import Dict, Optional
 import torch
 
 from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixel_rows
-from .packing import pack_conv_operand
-from .update import EPI_LINEAR, UpdateEngine, UpdateSpec, corr_rows
+from .conv_path import EPI_LINEAR, EPI_LINEAR_GELU, PRECISIONS, check_precision
+from .update import UpdateEngine, UpdateSpec, corr_rows
 
-SEA_PRECISIONS = ("fp32", "bf16")
-
-EPI_LINEAR_GELU = 3        # enum pfk_epilogue (include/pfk.h)
 LN_EPS = 1e-6              # sea_raft/layer.py:57 (LayerNorm(dim, eps=1e-6))
 
 
@@ -105,10 +102,8 @@ class SeaUpdateEngine(UpdateEngine):
 
     def __init__(self, params: Dict[str, torch.Tensor], spec: UpdateSpec, device: torch.device, num_blocks: int = 2,
                  precision: str = "fp32"):
-        if precision not in SEA_PRECISIONS:
-            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
         self.num_blocks = int(num_blocks)
-        self.precision = precision
+        self.precision = check_precision(precision, PRECISIONS)
         super().__init__(params, spec, device, precision)
 
     # ------------------------------------------------------------------ weights
@@ -126,9 +121,7 @@ class SeaUpdateEngine(UpdateEngine):
         def g(name):
             return P[name].detach().to(device=dev, dtype=torch.float32)
 
-        def pk(weight, segments):      # (bf16: rounded once from the fp32, gamma-folded weight)
-            return pack_conv_operand(weight, segments, self.b16, self.nsplit)
-
+        pk = self.path.pack            # (bf16: rounded once from the fp32, gamma-folded weight)
         C = self.spec.hx_channels
         w = self.w
         for i in range(self.num_blocks):
@@ -159,7 +152,7 @@ class SeaUpdateEngine(UpdateEngine):
         super().bind(B, H, W)
         M, dev = B * H * W, self.device
         C = self.spec.hx_channels
-        dt = torch.bfloat16 if self.b16 else torch.float32
+        dt = self.path.dtype
         self.ln = torch.zeros(M, C, device=dev, dtype=dt)
         self.mid = torch.zeros(M, self.mid_channels, device=dev, dtype=dt)
         self.res = torch.zeros(M, C, device=dev, dtype=dt)
@@ -171,7 +164,7 @@ class SeaUpdateEngine(UpdateEngine):
         into hx[:, :128], which the next block (and the heads) read."""
         B, H, W = self._shape
         C = self.spec.hx_channels
-        if self.b16:
+        if self.path.b16:
             for i in range(self.num_blocks):
                 self.ops.dwconv_layernorm_b16(self.hxb, self.w[f"dw{i}.w"], self.w[f"dw{i}.b"], self.w[f"ln{i}.w"], self.w[f"ln{i}.b"],
                                               LN_EPS, self.ln, B, H, W, 7)
@@ -200,7 +193,7 @@ class SeaUpdateEngine(UpdateEngine):
         bf16 path, `flow` into hx's flow slice (mirrored into hxb).  `corr`: the lookup's fp32 rows on the fp32 path, read as
         they are; NCHW on the bf16 path, copied into corr16.  Returns the rows `update` reads."""
         s = self.spec
-        if self.b16:
+        if self.path.b16:
             def put(src, dst):         # any float NCHW -> the [M, C] rows `dst`, converting the dtype
                 self.nchw_view(dst).copy_(src.permute(0, 2, 3, 1))
         else:
@@ -215,7 +208,7 @@ class SeaUpdateEngine(UpdateEngine):
         else:
             put(flow, self.flow_view)
         self.flow_changed()            # bf16: the fp32 flow (convf1's input) mirrored into hxb (the ConvNeXt blocks' input)
-        if not self.b16:
+        if not self.path.b16:
             return corr
         put(corr, self.corr16[:, : s.corr_channels])
         return self.corr16
@@ -223,7 +216,7 @@ class SeaUpdateEngine(UpdateEngine):
     def stage_net(self, net: torch.Tensor) -> None:
         """`net` (any float NCHW) into the h slice of hx, or of hxb on the bf16 path"""
         dst = self.act[:, : self.spec.hidden]
-        if self.b16:
+        if self.path.b16:
             self.nchw_view(dst).copy_(net.permute(0, 2, 3, 1))
         else:
             self.ops.nchw_to_pm(net.contiguous(), dst)
@@ -248,7 +241,7 @@ class SeaUpdateEngine(UpdateEngine):
 
     def net_nchw(self) -> torch.Tensor:
         """the net state as NCHW with channels-last strides: a view of hx's h slice, or of hxb's on the bf16 path"""
-        if not self.b16:
+        if not self.path.b16:
             return super().net_nchw()
         B, H, W = self._shape
         return self.hxb[:, : self.spec.hidden].unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
@@ -271,9 +264,7 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
 
     def __init__(self, ref_block: torch.nn.Module, num_blocks: int, corr_channels: int, precision: str = "fp32"):
         super().__init__(ref_block)
-        if precision not in SEA_PRECISIONS:
-            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
-        self.precision = precision
+        self.precision = check_precision(precision, PRECISIONS)
         self.spec = sea_spec(corr_channels)
         self.num_blocks = num_blocks
         self._heads: Dict[str, torch.nn.Module] = {}   # "flow_head" / "upsample_weight" -> the model's modules (set by patch)
@@ -326,9 +317,7 @@ class PfkSeaRaftUpdateBlock(WrappedModule):
 
     def set_precision(self, precision: str) -> None:
         """switch the kernel path (a second `accelerate` with another `sea_raft_update`): the engine is rebuilt on the next call"""
-        if precision not in SEA_PRECISIONS:
-            raise ValueError(f"precision must be one of {SEA_PRECISIONS}, got {precision!r}")
-        if precision != self.precision:
+        if check_precision(precision, PRECISIONS) != self.precision:
             self.precision = precision
             self._engine, self._versions = None, None
             self._inp_ref, self._inp_version = None, -1

@@ -47,10 +47,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import load_native
-from .packing import pack_conv_weight, round_up
-
-EPI_LINEAR = 0
+from . import conv_path, load_native
+from .conv_path import PRECISIONS  # noqa: F401  (re-exported: tests and the seams import it from here)
+from .packing import round_up
 
 
 def _segments(srcs: Sequence[torch.Tensor], real: Sequence[int]) -> List[Tuple[int, int, int]]:
@@ -158,14 +157,11 @@ def step_params(packs: ConvPacks, *params):
     return packs.alias
 
 
-PRECISIONS = ("fp32", "bf16")
 BF16 = torch.bfloat16
 
 
 def check_precision(precision: str, what: str = "precision") -> str:
-    if precision not in PRECISIONS:
-        raise ValueError(f"{what} must be one of {PRECISIONS}, got {precision!r}")
-    return precision
+    return conv_path.check_precision(precision, PRECISIONS, what)
 
 
 def _rows_b16(s: torch.Tensor) -> torch.Tensor:
@@ -177,10 +173,17 @@ def _rows_b16(s: torch.Tensor) -> torch.Tensor:
 
 
 class _Kernels:
-    """What the two training precisions differ in — everything else of `_ConvPM` and `_GruPass` is written once.  This is the
-    fp32 instance: fp32 operands, channel counts in multiples of 4, packed weights in K chunks of 32 channels, outputs as wide
-    as the weight, any odd kernel and stride."""
-    name, dtype, quantum, kpad, pads_cout = "fp32", torch.float32, 4, 32, False
+    """What the two training precisions differ in — everything else of `_ConvPM` and `_GruPass` is written once.  Name, operand
+    dtype, channel quantum, the packed weight and the forward launch are the conv path's (conv_path.py); the autograd-only parts are
+    here.  This is the fp32 instance: fp32 operands, channel counts in multiples of 4, packed weights in K chunks of 32 channels,
+    outputs as wide as the weight, any odd kernel and stride."""
+    path, pads_cout = conv_path.FP32, False
+    workspace = staticmethod(_workspace)      # the stream-K scratch of the forward kernel
+
+    name = property(lambda self: self.path.name)
+    dtype = property(lambda self: self.path.dtype)
+    quantum = property(lambda self: self.path.quantum)
+    pack = property(lambda self: self.path.pack)
 
     def check(self, g: _Geometry, srcs) -> None:
         """Refuses what the kernels do not cover."""
@@ -202,12 +205,9 @@ class _Kernels:
         """Width of the output rows (and of the bias and the forward weight's rows) the forward kernel is given."""
         return round_up(cout, self.quantum) if self.pads_cout else cout
 
-    def pack(self, w: torch.Tensor, segs) -> torch.Tensor:
-        return pack_conv_weight(w, segs, kpad=self.kpad).to(self.dtype).contiguous()
-
     def conv(self, srcs, g: _Geometry, wpack, bias, cout: int, relu: bool, out, residual=None, stride: int = 1) -> None:
-        torch.ops.pfk.conv2d(list(srcs), g.B, g.H, g.W, g.kh, g.kw, wpack, bias, cout, EPI_LINEAR, relu, 1.0, out, None, None, None,
-                             _workspace(out.device), residual, stride)
+        self.path.conv(torch.ops.pfk, srcs=list(srcs), B=g.B, H=g.H, W=g.W, kh=g.kh, kw=g.kw, weight=wpack, bias=bias, cout=cout,
+                       out=out, relu=relu, workspace=self.workspace(out.device), residual=residual, stride=stride)
 
     def wgrad(self, srcs, dY, g: _Geometry, dW, db, reals, accumulate: bool) -> None:
         torch.ops.pfk.conv_wgrad_unpacked(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, g.stride, accumulate)
@@ -216,8 +216,9 @@ class _Kernels:
 class _KernelsB16(_Kernels):
     """bf16 operands on ``pfk_conv2d_b16`` / ``pfk_conv_wgrad_unpacked_b16``: channel counts in multiples of 8, K chunks of 64
     channels, output rows padded to 8 channels (a 2-channel head); stride 1 and at most 32 taps."""
-    name, dtype, quantum, kpad, pads_cout = "bf16", BF16, 8, 64, True
+    path, pads_cout = conv_path.BF16_ROWS, True
     rows = staticmethod(_rows_b16)
+    workspace = staticmethod(lambda device: None)
 
     def check(self, g, srcs):
         if g.stride != 1:
@@ -228,10 +229,6 @@ class _KernelsB16(_Kernels):
 
     def operand(self, t):
         return t.to(BF16)
-
-    def conv(self, srcs, g, wpack, bias, cout, relu, out, residual=None, stride=1):
-        torch.ops.pfk.conv2d_b16(list(srcs), g.B, g.H, g.W, g.kh, g.kw, wpack, bias, cout, EPI_LINEAR, relu, 1.0, out, None, None, None,
-                                 None, residual)
 
     def wgrad(self, srcs, dY, g, dW, db, reals, accumulate):
         torch.ops.pfk.conv_wgrad_unpacked_b16(list(srcs), dY, g.B, g.H, g.W, g.kh, g.kw, dW, db, reals, accumulate)
@@ -506,11 +503,11 @@ class AttnState:
     both with zero pad columns, written in one pass by `pfk_transpose_pack_*`.  ``map``: with a step sink, the map's alias behind
     an `_AttnFlush` node — what the uses of the step hang on in the autograd graph; None otherwise: the state holds no reference to
     the caller's tensor (a cache that outlives the step must not keep the map and its graph alive), the uses take it directly."""
-    __slots__ = ("map", "B", "H", "W", "N", "ld", "b16", "P", "PT", "wt", "sink", "uses", "dcat", "vcat", "__weakref__")
+    __slots__ = ("map", "B", "H", "W", "N", "ld", "path", "P", "PT", "wt", "sink", "uses", "dcat", "vcat", "__weakref__")
 
     @property
     def dtype(self):
-        return BF16 if self.b16 else torch.float32
+        return self.path.dtype
 
     def target(self, attention: torch.Tensor) -> torch.Tensor:
         """The tensor a use passes to `_AttnMatmul` as the receiver of the map's gradient."""
@@ -526,13 +523,13 @@ def pack_attention(attention: torch.Tensor, B: int, H: int, W: int, precision: s
         raise ValueError(f"attention must be [B, 1, N, N] = {(B, 1, N, N)} (one head), got {tuple(attention.shape)}")
     load_native()
     st = AttnState()
-    st.B, st.H, st.W, st.N, st.b16 = B, H, W, N, check_precision(precision) == "bf16"
-    st.ld = round_up(N, 8 if st.b16 else 4)
+    st.B, st.H, st.W, st.N, st.path = B, H, W, N, _KERNELS[check_precision(precision)].path
+    st.ld = round_up(N, st.path.quantum)
     a = attention.detach().float().reshape(B, N, N)
     if a.stride(2) != 1 or a.stride(0) != N * a.stride(1):
         a = a.contiguous()
     st.PT = torch.empty(B, N, st.ld, device=a.device, dtype=st.dtype)
-    if not st.b16 and st.ld == N and a.is_contiguous():
+    if not st.path.b16 and st.ld == N and a.is_contiguous():
         st.P = a                                  # already a legal operand: only the transpose is written
         torch.ops.pfk.transpose_pack(a, st.PT, None)
     else:
@@ -552,14 +549,15 @@ def _attn_gemm(st: AttnState, A: torch.Tensor, x: torch.Tensor, out: torch.Tenso
     B, N, C = st.B, st.N, x.shape[1]
     wt = st.wt.get(C)
     if wt is None:       # pad columns stay zero; the columns below N are rewritten by every use (same stream: no hazard)
-        wt = st.wt[C] = torch.zeros(B, C, round_up(st.ld, 64 if st.b16 else 32), device=x.device, dtype=st.dtype)
-    if st.b16:
+        wt = st.wt[C] = torch.zeros(B, C, round_up(st.ld, st.path.kchunk), device=x.device, dtype=st.dtype)
+    gemm = dict(B=1, H=st.H, W=st.W, kh=1, kw=1, bias=None, cout=C)
+    if st.path.b16:
         wt[:, :, :N].copy_(x.view(B, N, C).transpose(1, 2))
-        ops.conv2d_b16([A], 1, st.H, st.W, 1, 1, wt, None, C, EPI_LINEAR, False, 1.0, out.view(B, N, C), None, None, None, None, None)
+        st.path.conv(ops, srcs=[A], weight=wt, out=out.view(B, N, C), **gemm)
         return
     ops.pm_to_cm(x, wt)
     if B == 1:
-        ops.conv2d([A[0]], 1, st.H, st.W, 1, 1, wt[0], None, C, EPI_LINEAR, False, 1.0, out, None, None, None, _workspace(x.device))
+        st.path.conv(ops, srcs=[A[0]], weight=wt[0], out=out, workspace=_workspace(x.device), **gemm)
         return
     none = x.new_empty(0)
     for b0 in range(0, B, 4):      # up to four pairs' tiles resident together (`UpdateEngine._aggregate`)
@@ -612,7 +610,7 @@ class _AttnMatmul(torch.autograd.Function):
     def forward(ctx, amap, v, st: AttnState):
         if v.shape[1] % 32:
             raise ValueError(f"_AttnMatmul: the value width must be a multiple of 32, got {v.shape[1]}")
-        v = _rows_b16(v) if st.b16 else v.float().contiguous()
+        v = _rows_b16(v) if st.path.b16 else v.float().contiguous()
         out = torch.empty(v.shape[0], v.shape[1], device=v.device, dtype=torch.float32)
         _attn_gemm(st, st.P, v, out)
         ctx.st, ctx.slot = st, st.uses
@@ -624,7 +622,7 @@ class _AttnMatmul(torch.autograd.Function):
     def backward(ctx, dAgg):
         (v,), st = ctx.saved_tensors, ctx.st
         M, C = v.shape
-        d = _rows_b16(dAgg.to(BF16)) if st.b16 else dAgg.float().contiguous()
+        d = _rows_b16(dAgg.to(BF16)) if st.path.b16 else dAgg.float().contiguous()
         dV = None
         if ctx.needs_input_grad[1]:
             dV = torch.empty(M, C, device=v.device, dtype=v.dtype)

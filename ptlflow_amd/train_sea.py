@@ -34,17 +34,18 @@ import torch
 
 from . import load_native
 from ._seam import pixel_rows
-from .train import _KERNELS, BF16, _nchw, _pm, check_precision, conv_pm, packs_for
+from .conv_path import BF16_ROWS, FP32, ConvPath
+from .train import _KERNELS, _nchw, _pm, check_precision, conv_pm, packs_for
 
 LN_EPS = 1e-6              # sea_raft/layer.py:57
 
 
 class _RowKernels:
-    """What the two precisions of the row nodes (`_DwconvLayerNorm`, `_Gelu`) differ in: the element type of the rows, its channel
-    quantum (16 bytes) and the entries' suffix."""
+    """What the two precisions of the row nodes (`_DwconvLayerNorm`, `_Gelu`) differ in: the element type of the rows and its channel
+    quantum (16 bytes), both the conv path's, and the entries' suffix."""
 
-    def __init__(self, dtype: torch.dtype, quantum: int, suffix: str):
-        self.dtype, self.quantum, self.suffix = dtype, quantum, suffix
+    def __init__(self, path: ConvPath, suffix: str):
+        self.dtype, self.quantum, self.suffix = path.dtype, path.quantum, suffix
 
     def rows(self, t: torch.Tensor) -> torch.Tensor:
         """rows the row kernels read: the element type, unit channel stride, 16-byte aligned rows"""
@@ -60,7 +61,7 @@ class _RowKernels:
         return getattr(torch.ops.pfk, name + self.suffix)
 
 
-_ROWS = {"fp32": _RowKernels(torch.float32, 4, ""), "bf16": _RowKernels(BF16, 8, "_b16")}
+_ROWS = {"fp32": _RowKernels(FP32, ""), "bf16": _RowKernels(BF16_ROWS, "_b16")}
 
 
 class _DwconvLayerNorm(torch.autograd.Function):

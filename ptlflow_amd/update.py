@@ -34,10 +34,9 @@ import torch
 
 from . import load_native
 from ._seam import WrappedModule, pixel_rows
-from .packing import (pack_cin2_weight, pack_conv_operand, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight,
-                      permute_mask_head, round_up, split_bf16_planes)
-
-EPI_LINEAR, EPI_GRU_ZR, EPI_GRU_Q = 0, 1, 2
+from .conv_path import EPI_GRU_Q, EPI_GRU_ZR, EPI_LINEAR, resolve
+from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight, permute_mask_head,
+                      round_up, split_bf16_planes)
 
 
 @dataclass(frozen=True)
@@ -149,9 +148,6 @@ WINO1D_MIN_PIXELS = 28160
 # 1 the same 34 us); the flow-head-only `fh` launch of the kernels without `cout_active` (no launch in the stream-K window there).
 SMALL_GRID_PIXELS = 28160
 
-# conv_precision -> number of bf16 planes per operand (0 = the fp32 matrix-core path, the default and the parity path)
-CONV_PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2, "bf16x6": 3}
-
 
 class UpdateEngine:
     """``hoist_context`` (default on): the GRU convolutions of raft/update.py:60-71 / :27-30 run over
@@ -171,17 +167,14 @@ class UpdateEngine:
                  conv_precision: str = "fp32", hoist_context: bool = True):
         load_native()
         self.hoist_context = bool(hoist_context)
-        if conv_precision not in CONV_PRECISIONS:
-            raise ValueError(f"conv_precision must be one of {sorted(CONV_PRECISIONS)}, got {conv_precision!r}")
         self.conv_precision = conv_precision
-        self.nsplit = CONV_PRECISIONS[conv_precision]
         # "bf16" = BASELINE config 3's precision as the reference's reduced-precision switch gives it (model_benchmark.py:317-319 /
         # torch.autocast: every convolution reads and writes 16-bit tensors): K8b, `pfk_conv2d_b16` — bf16 ACTIVATION STORAGE between
         # this engine's own kernels (producer epilogues emit bf16 once), both GEMM operands by LDS-DMA; the recurrent state h, the
         # coordinates / flow and every accumulator stay fp32.  GMA's aggregate branch runs on a bf16 copy of the attention map (what
-        # `attn @ v` reads under autocast: half the bytes of the 198 MB-per-pair operand that every iteration streams).  CCMR (the
-        # caller's torch module reads the motion features) keeps the split kernel with one plane (fp32 storage).
-        self.b16 = conv_precision == "bf16" and not spec.external_aggregate
+        # `attn @ v` reads under autocast: half the bytes of the 198 MB-per-pair operand that every iteration streams).  The other
+        # names are the fp32 tile kernels ("fp32", the default and the parity path) and the split kernel (conv_path.py).
+        self.path = resolve(conv_precision, spec.external_aggregate)
         self.ops = torch.ops.pfk
         self.spec = spec
         self.device = device
@@ -205,12 +198,8 @@ class UpdateEngine:
         def g(name):
             return P[name].detach().to(device=dev, dtype=torch.float32)
 
-        def seg1(c):
-            return [(0, c, round_up(c, 8 if self.b16 else 4))]
-
-        def pk(weight, segments):
-            return pack_conv_operand(weight, segments, self.b16, self.nsplit)
-
+        path = self.path
+        pk, seg1 = path.pack, path.segment
         w: Dict[str, torch.Tensor] = {}
         real = s.hidden + s.x_channels
         self._real_cin = {"c1": s.corr_channels, "c2": s.c1, "f2": s.f1, "cv": (s.c2 if s.c2 else s.c1) + s.f2,
@@ -234,7 +223,7 @@ class UpdateEngine:
         w["cv.w"] = pk(g("encoder.conv.weight"), seg1(cf))
         w["cv.b"] = g("encoder.conv.bias").contiguous()
         Ch = s.hidden
-        hxc = round_up(s.hidden + s.x_channels, 8) if self.b16 else s.hx_channels      # (the bf16 twin of hx has 16-byte rows)
+        hxc = round_up(s.hidden + s.x_channels, path.quantum)      # the rows the convolutions read: hx, or its bf16 twin (16-byte rows)
         real = Ch + s.x_channels
         for kh, kw, sfx in s.gru_passes:
             wz, wr, wq = (g(f"gru.conv{k}{sfx}.weight") for k in "zrq")
@@ -247,7 +236,7 @@ class UpdateEngine:
                 wzr = torch.cat([wz, wr], 0)
                 w[f"zr{sfx}.w"] = pk(wzr, rest)
                 w[f"q{sfx}.w"] = pk(wq, rest)
-                if self.nsplit == 0 and not self.b16 and (kh, kw) in ((1, 5), (5, 1)) and rest[1][2] % 8 == 0 and Ch % 8 == 0:
+                if path.fp32_tiles and (kh, kw) in ((1, 5), (5, 1)) and rest[1][2] % 8 == 0 and Ch % 8 == 0:
                     # F(4,5)-transformed twins of the per-iteration gate convolutions (U = G g, once per pack; see _use_wino1d)
                     w[f"zr{sfx}.w1d"] = pack_wino1d_weight(wzr, rest)
                     w[f"q{sfx}.w1d"] = pack_wino1d_weight(wq, rest)
@@ -270,12 +259,12 @@ class UpdateEngine:
             assert mask_hidden == g("mask.0.weight").shape[0], "mask.2 reads mask.0's output"
             w["mk.w"] = pk(g("mask.2.weight"), seg1(mask_hidden))
             w["mk.b"] = g("mask.2.bias").contiguous()
-            if self.nsplit == 0 and s.mask_channels == 576 and mask_hidden % 32 == 0 and mask_hidden == s.fh_hidden:
+            if path.fp32_tiles and s.mask_channels == 576 and mask_hidden % 32 == 0 and mask_hidden == s.fh_hidden:
                 # fused mask conv2 + softmax + convex upsampling (`pfk_mask_upsample_f32`): the 1x1 weight / bias with their rows in
                 # the kernel's [quarter][tile][32] order (packing.permute_mask_head, include/pfk.h); `fm` is split at fh_hidden, so
                 # the fused kernel is only armed where the two hidden widths agree
                 w["mku.w"], w["mku.b"] = permute_mask_head(pack_conv_weight(g("mask.2.weight"), seg1(mask_hidden)), w["mk.b"])
-            elif self.b16 and s.mask_channels == 576 and mask_hidden % 64 == 0 and mask_hidden == s.fh_hidden:
+            elif path.b16 and s.mask_channels == 576 and mask_hidden % 64 == 0 and mask_hidden == s.fh_hidden:
                 # K13b (`pfk_mask_upsample_b16`): the same row order, bf16 (whole 64-channel K-steps: the packed K is the plain channel order)
                 wp, bp = permute_mask_head(pack_conv_weight(g("mask.2.weight"), seg1(mask_hidden)), w["mk.b"])
                 w["mku.w"], w["mku.b"] = wp.to(torch.bfloat16).contiguous(), bp
@@ -294,7 +283,7 @@ class UpdateEngine:
         if "flow_head.conv2.weight" in P:     # (SEA-RAFT's 6-channel flow head conv2 is packed by its own engine, sea_update.py)
             w["fh2.w"] = pack_flow_head_weight(g("flow_head.conv2.weight"))
             w["fh2.b"] = g("flow_head.conv2.bias").contiguous()
-        if self.nsplit == 0 and not self.b16:
+        if path.fp32_tiles:
             # Winograd-transformed twins of the update block's 3x3 stride-1 single-source convolutions (U = G g G^T, once per pack)
             fm = torch.cat([g("flow_head.conv1.weight"), g("mask.0.weight")], 0) if s.has_mask else g("flow_head.conv1.weight")
             wino = {"cv": g("encoder.conv.weight"), "fm": fm, "f2": g("encoder.convf2.weight")}
@@ -309,16 +298,16 @@ class UpdateEngine:
     def bind(self, B: int, H: int, W: int) -> None:
         if self._shape == (B, H, W):
             return
-        s, dev = self.spec, self.device
+        s, dev, path = self.spec, self.device, self.path
         M = B * H * W
         z = lambda c: torch.zeros(M, c, device=dev, dtype=torch.float32)  # noqa: E731
         # activations between this engine's kernels: fp32, or bf16 on the K8b path
-        a = (lambda c: torch.zeros(M, c, device=dev, dtype=torch.bfloat16)) if self.b16 else z  # noqa: E731
+        a = lambda c: torch.zeros(M, c, device=dev, dtype=path.dtype)  # noqa: E731
         self.hx = z(s.hx_channels)
         # K8b: the 16-bit twin of hx the convolutions read — same channel layout; h is mirrored by the q epilogue, the motion
         # features are written here only, the flow by the flow-head kernel (both widths)
-        self.hxb = a(round_up(s.hidden + s.x_channels, 8)) if self.b16 else None
-        self.corr16 = a(round_up(s.corr_channels, 8)) if self.b16 else None      # the lookup's output (pad columns stay zero)
+        self.hxb = a(round_up(s.hidden + s.x_channels, path.quantum)) if path.b16 else None
+        self.corr16 = a(round_up(s.corr_channels, path.quantum)) if path.b16 else None      # the lookup's output (pad columns stay zero)
         self.cor1 = a(s.c1) if s.c2 else None   # SmallMotionEncoder: convc1 writes corflo[:, :c1] directly
         self.corflo = a((s.c2 if s.c2 else s.c1) + s.f2)
         self.flo1 = a(s.f1)
@@ -338,10 +327,8 @@ class UpdateEngine:
         if s.aggregate and not s.external_aggregate:
             N = H * W
             self.vbuf = a(s.motion_channels)
-            if self.b16:      # K-contiguous B operand of the batched attn @ v GEMM: [B][C][N padded to the kernel's 64-wide K-steps]
-                self.vT = torch.zeros(B, s.motion_channels, round_up(round_up(N, 8), 64), device=dev, dtype=torch.bfloat16)
-            else:
-                self.vT = torch.zeros(B, s.motion_channels, round_up(N, 32), device=dev, dtype=torch.float32)
+            # K-contiguous B operand of the attn @ v GEMM(s): [B][C][N padded to the path's K chunk] (bf16 rows: ONE batched GEMM)
+            self.vT = torch.zeros(B, s.motion_channels, round_up(N, path.kchunk), device=dev, dtype=path.dtype)
             self.attn = None
         # scratch for the stream-K conv schedules (partials + flags), one per stream that may run convolutions concurrently: the
         # main chain, the flow branch of the motion encoder and the mask branch (RAFT._iterate's forked mode) — with its own
@@ -398,27 +385,32 @@ class UpdateEngine:
             self._fault_event = torch.cuda.Event()
             self._fault_event.record()
 
+    @property
+    def b16(self) -> bool:
+        """this engine is on bf16 rows (K8b); what the loop schedule (`raft.loop_schedule`) and the seams ask"""
+        return self.path.b16
+
     # views into hx
     @property
     def act(self):
         """the buffer the convolutions read their [h | inp | motion | flow] operand from: hx, or its bf16 twin (K8b)"""
-        return self.hxb if self.b16 else self.hx
+        return self.hxb if self.path.b16 else self.hx
 
     @property
     def lookup_out(self):
         """where the caller's lookup should write for this engine (None: the correlation block's own fp32 buffer)"""
-        return self.corr16 if self.b16 else None
+        return self.corr16 if self.path.b16 else None
 
     def flow_changed(self) -> None:
         """the flow slice of hx was written by something other than `flow_delta` (loop prologue, the drop-in seam): mirror it"""
-        if self.b16:
+        if self.path.b16:
             s = self.spec
             o = s.hidden + s.context + s.enc_out
             self.hxb[:, o: o + 2].copy_(self.hx[:, o: o + 2])
 
     def state_changed(self) -> None:
         """h / inp slices of hx were (re)loaded: mirror them into the bf16 twin"""
-        if self.b16:
+        if self.path.b16:
             n = self.spec.hidden + self.spec.context
             self.hxb[:, :n].copy_(self.hx[:, :n])
 
@@ -448,7 +440,7 @@ class UpdateEngine:
         N = H * W
         if attn.dim() != 4 or attn.shape[0] != B or attn.shape[1] != 1 or attn.shape[2] != N or attn.shape[3] != N:
             raise RuntimeError(f"attention must be [B,1,N,N] with one head, got {tuple(attn.shape)}")
-        if self.b16:      # the bf16 copy the per-iteration GEMM streams (rows padded to 16 bytes, pad columns zero), once per forward
+        if self.path.b16:      # the bf16 copy the per-iteration GEMM streams (rows padded to 16 bytes, pad columns zero), once per forward
             a = torch.zeros(B, N, round_up(N, 8), device=attn.device, dtype=torch.bfloat16) if N % 8 else \
                 torch.empty(B, N, N, device=attn.device, dtype=torch.bfloat16)
             a[:, :, :N].copy_(attn.reshape(B, N, N))
@@ -468,22 +460,22 @@ class UpdateEngine:
         N = H * W
         o = s.hidden + s.context
         mc = s.motion_channels
-        if self.b16:
+        if self.path.b16:
             # K8b: v = to_v(mf) in bf16, V^T by one small strided copy, then ONE batched GEMM over the pairs —
             # out[b] = mf[b] + gamma * attn[b] @ v[b] with the bf16 attention map as the LDS-DMA'd A operand
             hxb = self.hxb.view(B, N, self.hxb.shape[1])
             self._conv([self.hxb[:, o: o + mc]], 1, 1, "tv", mc, relu=False, out=self.vbuf)
             self.vT[:, :, :N].copy_(self.vbuf.view(B, N, mc).transpose(1, 2))
             t0 = self.tic() if self.profile is not None else None
-            self.ops.conv2d_b16([self.attn], 1, H, W, 1, 1, self.vT, None, mc, EPI_LINEAR, False, self.gamma,
-                                hxb[:, :, o + mc: o + 2 * mc], None, None, None, None, hxb[:, :, o: o + mc])
+            self.path.conv(self.ops, srcs=[self.attn], B=1, H=H, W=W, kh=1, kw=1, weight=self.vT, bias=None, cout=mc, scale=self.gamma,
+                           out=hxb[:, :, o + mc: o + 2 * mc], residual=hxb[:, :, o: o + mc])
             if t0 is not None:      # `ag`, here and below: FLOPs only, deliberately — no byte count was ever defined for it (bench.py: None)
                 self.toc(t0, "ag", 2.0 * B * N * N * mc)
             return
         mf = self.hx[:, o: o + mc]
         self._conv([mf], 1, 1, "tv", mc, relu=False, out=self.vbuf)
         self.ops.pm_to_cm(self.vbuf, self.vT)
-        if self.nsplit == 0 and B > 1:
+        if self.path.fp32_tiles and B > 1:
             # fp32: the pairs' `attn[b] @ v[b]` are INDEPENDENT GEMMs of 110 x 2 = 220 tiles each (one block per CU on 220 CUs, one
             # wave per SIMD: 0.45 of the matrix peak) — as ONE grouped grid (`pfk_conv2d_group_f32`, up to four problems per launch)
             # the 880 tiles of four pairs are resident together, three blocks per CU.  Same tiles, same K order: same bits.
@@ -502,9 +494,9 @@ class UpdateEngine:
             src = self.attn[b]
             t0 = self.tic() if self.profile is not None else None
             # split modes: V^T changes every iteration, so its bf16 planes are cut here (three tiny elementwise kernels)
-            vt = self.vT[b] if self.nsplit == 0 else split_bf16_planes(self.vT[b], self.nsplit)
-            self.ops.conv2d([src], 1, H, W, 1, 1, vt, None, mc, EPI_LINEAR, False, self.gamma,
-                            self.hx[rows, o + mc: o + 2 * mc], None, None, None, self.workspace, self.hx[rows, o: o + mc])
+            vt = split_bf16_planes(self.vT[b], self.path.planes) if self.path.planes else self.vT[b]
+            self.path.conv(self.ops, srcs=[src], B=1, H=H, W=W, kh=1, kw=1, weight=vt, bias=None, cout=mc, scale=self.gamma,
+                           out=self.hx[rows, o + mc: o + 2 * mc], workspace=self.workspace, residual=self.hx[rows, o: o + mc])
             if t0 is not None:
                 self.toc(t0, "ag", 2.0 * N * N * mc)
 
@@ -533,7 +525,7 @@ class UpdateEngine:
 
     # ------------------------------------------------------------------ one iteration
     def _conv(self, srcs: List[torch.Tensor], kh, kw, key, cout, relu=True, scale=1.0, out=None,
-              epi=EPI_LINEAR, h=None, z=None, rh=None, workspace=True, residual=None, cout_active=0, cout_split=0):
+              epi=EPI_LINEAR, h=None, h_b16=None, z=None, rh=None, workspace=True, residual=None, cout_active=0, cout_split=0):
         B, H, W = self._shape
         t0 = self.tic() if self.profile is not None else None
         # a stream-K workspace belongs to ONE stream: `workspace` = True (the main chain's), a branch's own tensor, or False
@@ -544,14 +536,10 @@ class UpdateEngine:
                                    h, z, rh, residual)
         elif self._use_wino(key, cout, B * H * W):
             self.ops.conv2d_wino(srcs[0], B, H, W, self.w[key + ".ww"], self.w.get(key + ".b"), cout, relu, scale, out, cout_active)
-        elif self.b16:
-            # K8b: z|r reads h from the bf16 twin (r * h is rounded to bf16 anyway), q updates the fp32 h and mirrors it
-            hb = self.hxb[:, : self.spec.hidden] if epi != EPI_LINEAR else None
-            self.ops.conv2d_b16(srcs, B, H, W, kh, kw, self.w[key + ".w"], self.w.get(key + ".b"), cout, epi, relu, scale,
-                                out, h if epi == EPI_GRU_Q else None, hb, z, rh, residual)
         else:
-            self.ops.conv2d(srcs, B, H, W, kh, kw, self.w[key + ".w"], self.w.get(key + ".b"), cout, epi, relu, scale,
-                            out, h, z, rh, ws, residual, 1, False, cout_active, cout_split)
+            # (positionally, in `ConvPath.conv`'s order: the per-iteration path, see its docstring)
+            self.path.conv(self.ops, srcs, B, H, W, kh, kw, self.w[key + ".w"], self.w.get(key + ".b"), cout, out, epi, relu, scale,
+                           h, h_b16, z, rh, ws, residual, 1, False, cout_active, cout_split)
         if t0 is not None:
             cin = self._real_cin[key]
             if cout_active:
@@ -559,7 +547,7 @@ class UpdateEngine:
             # algorithmic work: 2 * pixels * cout * taps * real input channels (padding is not work)
             # algorithmic HBM bytes: every input channel read once, every output written once, the weight once (fp32)
             self.toc(t0, key, 2.0 * B * H * W * cout * kh * kw * cin,
-                     (2.0 if self.b16 else 4.0) * (B * H * W * (cin + cout) + cout * kh * kw * cin))
+                     self.path.element_bytes * (B * H * W * (cin + cout) + cout * kh * kw * cin))
 
     def _use_wino(self, key: str, cout: int, pixels: int) -> bool:
         """`pfk_conv2d_wino_f32` for `fm`, `c2`, `cv` (their transformed weights exist on the fp32 engine only, see pack) where
@@ -608,7 +596,7 @@ class UpdateEngine:
     @property
     def can_group(self) -> bool:
         """the grouped launch exists for the fp32 tile kernel (`pfk_conv2d_group_f32`)"""
-        return self.nsplit == 0 and not self.b16
+        return self.path.fp32_tiles
 
     @property
     def wants_grouped_motion(self) -> bool:
@@ -674,17 +662,17 @@ class UpdateEngine:
         s = self.spec
         Ch = s.hidden
         act = self.act
+        # the gate epilogues' state: the fp32 h, its bf16 twin where there is one (which of the two a launch gets: `ConvPath.conv`), z
+        gate = dict(h=self.h_view, h_b16=self.hxb[:, :Ch] if self.path.b16 else None, z=self.zbuf)
         if self.hoist_context:
             rest = act[:, Ch + s.context:]          # x without the context slice: motion features [| aggregated ones] | pad
             for kh, kw, sfx in s.gru_passes:
-                self._conv([act[:, :Ch], rest], kh, kw, "zr" + sfx, 2 * Ch, epi=EPI_GRU_ZR, h=self.h_view, z=self.zbuf, rh=self.rh,
-                           residual=self.ctx["zr" + sfx])
-                self._conv([self.rh, rest], kh, kw, "q" + sfx, Ch, epi=EPI_GRU_Q, h=self.h_view, z=self.zbuf,
-                           residual=self.ctx["q" + sfx])
+                self._conv([act[:, :Ch], rest], kh, kw, "zr" + sfx, 2 * Ch, epi=EPI_GRU_ZR, rh=self.rh, residual=self.ctx["zr" + sfx], **gate)
+                self._conv([self.rh, rest], kh, kw, "q" + sfx, Ch, epi=EPI_GRU_Q, residual=self.ctx["q" + sfx], **gate)
             return
         for kh, kw, sfx in s.gru_passes:
-            self._conv([act], kh, kw, "zr" + sfx, 2 * Ch, epi=EPI_GRU_ZR, h=self.h_view, z=self.zbuf, rh=self.rh)
-            self._conv([self.rh, act[:, Ch:]], kh, kw, "q" + sfx, Ch, epi=EPI_GRU_Q, h=self.h_view, z=self.zbuf)
+            self._conv([act], kh, kw, "zr" + sfx, 2 * Ch, epi=EPI_GRU_ZR, rh=self.rh, **gate)
+            self._conv([self.rh, act[:, Ch:]], kh, kw, "q" + sfx, Ch, epi=EPI_GRU_Q, **gate)
 
     def motion_and_gru(self, corr_pm: torch.Tensor, grouped: bool = False, prev_mask: bool = False) -> None:
         """update.py:104-112 (encoder) + :58-73 / :24-32 (GRU); `flow` must already be in hx.  `grouped`: `motion_grouped`
@@ -718,12 +706,12 @@ class UpdateEngine:
         split points of the 880-tile grid — and skips the mask half's column tiles, so the flow half has the full launch's bits
         whatever the schedule (round 4 could only drop the mask half where neither form fell into the stream-K window)."""
         s = self.spec
-        if s.has_mask and self.nsplit == 0 and s.fh_hidden % 64 == 0:
+        if s.has_mask and self.path.fp32_tiles and s.fh_hidden % 64 == 0:
             # `cout_split`: a stream-K schedule (batch 1) walks the column tiles of the two halves interleaved — in BOTH forms of the
             # launch, so that they share their split points (same bits) and the half launch still balances its blocks
             self._conv([self.h_view], 3, 3, "fm", 2 * s.fh_hidden, out=self.fm, cout_active=0 if want_mask else s.fh_hidden,
                        cout_split=s.fh_hidden)
-        elif s.has_mask and not want_mask and (self.b16 or self.pixels >= SMALL_GRID_PIXELS):
+        elif s.has_mask and not want_mask and (self.path.b16 or self.pixels >= SMALL_GRID_PIXELS):
             # split-bf16 / K8b kernels (no `cout_active`): the flow-head-only weights, where no launch is in the stream-K window
             self._conv([self.act[:, : s.hidden]], 3, 3, "fh", s.fh_hidden, out=self.fm[:, : s.fh_hidden])
         else:
@@ -733,7 +721,7 @@ class UpdateEngine:
                    write_flow: bool = True) -> None:
         """flow-head conv2 + `coords1 += delta`, `flow = coords1 - coords0` (update.py:14, raft.py:174,178) on the flow half of fm"""
         s = self.spec
-        if self.b16:      # bf16 hidden activation in; the flow goes to hx (fp32: 7x7 convolution, upsampling) and to its bf16 twin
+        if self.path.b16:      # bf16 hidden activation in; the flow goes to hx (fp32: 7x7 convolution, upsampling) and to its bf16 twin
             o = s.hidden + s.context + s.enc_out
             self.ops.flow_delta(self.fm[:, : s.fh_hidden], self.w["fh2.w"], self.w["fh2.b"], coords0, coords1, delta_out,
                                 self.flow_view if write_flow else None, self.hxb[:, o: o + 2] if write_flow else None)
@@ -762,7 +750,7 @@ class UpdateEngine:
         self.ops.mask_upsample(x, self.w["mku.w"], self.w["mku.b"], 0.25, self.flow_view, flow_up)
         if t0 is not None:
             M = x.shape[0]
-            eb = 2.0 if self.b16 else 4.0       # activation / weight element size; flow in and 8x flow out are fp32 on both paths
+            eb = self.path.element_bytes        # activation / weight element size; flow in and 8x flow out are fp32 on both paths
             self.toc(t0, "mku", 2.0 * M * 576 * s.fh_hidden, eb * (M * s.fh_hidden + 576 * s.fh_hidden) + 4.0 * (2 * M + 2 * 64 * M))
 
     def step(self, corr_pm: torch.Tensor, coords0: torch.Tensor, coords1: torch.Tensor, want_mask: bool = True) -> None:
