@@ -121,7 +121,7 @@ def _run(cmd) -> None:
 
 def build_libpfk(force: bool = False) -> Path:
     OBJ.mkdir(exist_ok=True)
-    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_launch.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h",
+    headers = [INCLUDE / "pfk.h", CSRC / "pfk_common.h", CSRC / "pfk_launch.h", CSRC / "pfk_conv_k.h", CSRC / "pfk_gemm.h", CSRC / "pfk_lookup.h",
                CSRC / "pfk_upsample.h", CSRC / "pfk_wgrad_reduce.h"]
     tree = source_hash()
     objs, jobs = [], []

@@ -1,9 +1,25 @@
 // Pieces shared by the implicit-GEMM translation units (pfk_gemm.hip: fp32 MFMA; pfk_gemm_bf.hip: split-bf16 MFMA):
 // the kernel argument block, the buffer-descriptor helper and the fused epilogues.
 #pragma once
+#include "pfk_conv_k.h"   // the K order every stager walks: conv_k_advance, conv_k_decode
 #include "pfk_launch.h"
 
 namespace pfkg {
+
+// Output row p (= (b * Ho + yo) * Wo + xo, batch folded into M) -> input coordinates (px, py) and input row prow of its centre tap;
+// ok = the row lies inside M.  32-bit arithmetic on the host-made multipliers of the argument block (GemmArgs, B16Args: M < 2^31).
+struct ConvPixel { int px, py, prow; bool ok; };
+template <class A>
+__host__ __device__ __forceinline__ ConvPixel conv_pixel(const A& a, unsigned p) {
+  ConvPixel r;
+  r.ok = (long long)p < a.M;
+  const unsigned prow_o = fastdiv_u32(p, a.wo_mul, a.wo_sh);          // b*Ho + yo
+  const unsigned bimg = fastdiv_u32(prow_o, a.ho_mul, a.ho_sh);
+  r.px = (int)(p - prow_o * (unsigned)a.Wo) * a.stride;
+  r.py = (int)(prow_o - bimg * (unsigned)a.Ho) * a.stride;
+  r.prow = (int)((bimg * (unsigned)a.H + (unsigned)r.py) * (unsigned)a.W + (unsigned)r.px);
+  return r;
+}
 
 struct GemmArgs {
   const float* src0; const float* src1; const float* src2;

@@ -56,7 +56,7 @@ struct Stager {
   static constexpr int B_PT = BN / 32;
   // uniform
   int H, W, kh, kw, ph, pw, nsrc;
-  int ld0, ld1, ld2, ch0, ch1, ch2;
+  int ld0, ld1, ld2, ch0, ch1, ch2;   // (ch0..2 consecutive: seek() hands &ch0 to conv_k_decode)
   __amdgpu_buffer_rsrc_t rs0, rs1, rs2, rsw, rs;
   int cld, cch;
   int seg = 0, ky = 0, kx = 0, c0 = 0, kofs = 0;
@@ -100,13 +100,8 @@ struct Stager {
     rsw = buffer_rsrc(a.weight + batch * a.b_bs);
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
-      const unsigned p = (unsigned)m0 + (unsigned)(r0 + 32 * i);
-      pok[i] = (long long)p < a.M;
-      const unsigned prow_o = fastdiv_u32(p, a.wo_mul, a.wo_sh);          // b*Ho + yo
-      const unsigned bimg = fastdiv_u32(prow_o, a.ho_mul, a.ho_sh);
-      px[i] = (int)(p - prow_o * (unsigned)a.Wo) * a.stride;              // input coordinates of the centre tap
-      py[i] = (int)(prow_o - bimg * (unsigned)a.Ho) * a.stride;
-      prow[i] = (int)((bimg * (unsigned)a.H + (unsigned)py[i]) * (unsigned)a.W + (unsigned)px[i]);
+      const ConvPixel c = conv_pixel(a, (unsigned)m0 + (unsigned)(r0 + 32 * i));
+      pok[i] = c.ok; px[i] = c.px; py[i] = c.py; prow[i] = c.prow;
     }
 #pragma unroll
     for (int i = 0; i < B_PT; ++i) {
@@ -143,15 +138,9 @@ struct Stager {
 
   // Position the iterator at K-step `step` (stream-K segments start mid-tile).
   __device__ __forceinline__ void seek(int step) {
-    const int taps = kh * kw;
-    int r = step, sg = 0, cps = (ch0 + BK - 1) / BK;
-    if (nsrc > 1 && r >= taps * cps) {
-      r -= taps * cps; sg = 1; cps = (ch1 + BK - 1) / BK;
-      if (nsrc > 2 && r >= taps * cps) { r -= taps * cps; sg = 2; cps = (ch2 + BK - 1) / BK; }
-    }
-    const int tap = r / cps;
-    seg = sg; ky = tap / kw; kx = tap - ky * kw; c0 = (r - tap * cps) * BK; kofs = step * BK;
-    set_segment(sg);
+    const ConvKPos k = conv_k_decode<BK>(step, kh, kw, nsrc, &ch0);
+    seg = k.seg; ky = k.ky; kx = k.kx; c0 = k.c0; kofs = step * BK;
+    set_segment(k.seg);
     set_tap();
   }
 
@@ -160,14 +149,9 @@ struct Stager {
   // made hipcc keep them in a scratch array and lose the uniformity of everything derived from it (waterfall loops around
   // every buffer load of the K loop).  GemmArgs keeps src0..2 / ld0..2 / ch0..2 contiguous for this.
   __device__ __forceinline__ void seek_args(const GemmArgs& a, long long batch, int step) {
-    const int taps = kh * kw;
-    int r = step, sg = 0, cps = (a.ch0 + BK - 1) / BK;
-    if (nsrc > 1 && r >= taps * cps) {
-      r -= taps * cps; sg = 1; cps = (a.ch1 + BK - 1) / BK;
-      if (nsrc > 2 && r >= taps * cps) { r -= taps * cps; sg = 2; cps = (a.ch2 + BK - 1) / BK; }
-    }
-    const int tap = r / cps;
-    seg = sg; ky = tap / kw; kx = tap - ky * kw; c0 = (r - tap * cps) * BK; kofs = step * BK;
+    const ConvKPos k = conv_k_decode<BK>(step, kh, kw, nsrc, &a.ch0);
+    const int sg = k.seg;
+    seg = sg; ky = k.ky; kx = k.kx; c0 = k.c0; kofs = step * BK;
     const float* const* srcv = &a.src0;
     const float* p = srcv[sg];
     if (sg == 0) p += batch * a.a_bs;
@@ -225,22 +209,8 @@ struct Stager {
     else *reinterpret_cast<f32x4*>(stage + BM * LD + (r0 + 32 * (q - A_PT)) * LD + scol) = rb[q - A_PT];
   }
 
-  __device__ __forceinline__ void advance() {
-    kofs += BK;
-    c0 += BK;
-    if (c0 >= cch) {
-      c0 = 0;
-      if (++kx == kw) {
-        kx = 0;
-        if (++ky == kh) {
-          ky = 0;
-          ++seg;
-          if (seg < nsrc) set_segment(seg);
-        }
-      }
-      set_tap();
-    }
-  }
+  // (one K-step forward is conv_k_advance<BK>(st), called by the kernels themselves: through a forwarding member the K loops of
+  //  the 3-stage kernels came out with other scalar moves)
 
   __device__ __forceinline__ void store(float* dA, float* dB) const {
 #pragma unroll
@@ -346,7 +316,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
   zero_acc<MT, NT>(acc);
 
   st.load();
-  st.advance();
+  conv_k_advance<BK>(st);
   st.store(sA, sB);
   __syncthreads();
 
@@ -366,7 +336,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
     mma_rest<MT, NT>(acc, fr, cA, cB, ko);
     __builtin_amdgcn_sched_barrier(0);
     st.store(sA + (buf ^ 1) * BM * LDS_LD, sB + (buf ^ 1) * BN * LDS_LD);   // last step: zeros into a dead buffer
-    if (more) st.advance();
+    if (more) conv_k_advance<BK>(st);
     __syncthreads();
   }
   epilogue_lds<MT, NT, EPI>(a, acc, m0 + wm0, n0 + wn0, lane, batch, smem, wid);   // behind the loop's final barrier
@@ -438,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_kernel(const GemmArgs a)
   zero_acc<MT, NT>(acc);
 
   st.load();
-  st.advance();
+  conv_k_advance<BK>(st);
   st.store(sA, sB);
   __syncthreads();
 
@@ -458,7 +428,7 @@ __global__ __launch_bounds__(256, 2) void mask_upsample_kernel(const GemmArgs a)
     mma_rest_ld<MT, NT, LD>(acc, fr, cA, cB, ko);
     __builtin_amdgcn_sched_barrier(0);
     st.store(sA + (buf ^ 1) * BM * LD, sB + (buf ^ 1) * BN * LD);
-    if (more) st.advance();
+    if (more) conv_k_advance<BK>(st);
     __syncthreads();
   }
 
@@ -581,7 +551,7 @@ __device__ __forceinline__ void conv_gemm_v3_body(const GemmArgs& a, const int b
   const int S = st.total_steps();
   const int my_steps = (S - grp + GROUPS - 1) / GROUPS;
   const int max_steps = (S + GROUPS - 1) / GROUPS;   // same trip count for every wave (barriers)
-  if (GROUPS > 1 && grp) st.advance();
+  if (GROUPS > 1 && grp) conv_k_advance<BK>(st);
 
   f32x16 acc[MT][NT];
   zero_acc<MT, NT>(acc);
@@ -593,15 +563,15 @@ __device__ __forceinline__ void conv_gemm_v3_body(const GemmArgs& a, const int b
   // prologue: steps 0 and 1 into LDS, step 2 into registers (dead steps load zeros)
   st.load(0 < my_steps);
 #pragma unroll
-  for (int g = 0; g < GROUPS; ++g) st.advance();
+  for (int g = 0; g < GROUPS; ++g) conv_k_advance<BK>(st);
   st.store(s_cur, s_cur + BM * LD);
   st.load(1 < my_steps);
 #pragma unroll
-  for (int g = 0; g < GROUPS; ++g) st.advance();
+  for (int g = 0; g < GROUPS; ++g) conv_k_advance<BK>(st);
   st.store(s_nxt, s_nxt + BM * LD);
   st.load(2 < my_steps);
 #pragma unroll
-  for (int g = 0; g < GROUPS; ++g) st.advance();
+  for (int g = 0; g < GROUPS; ++g) conv_k_advance<BK>(st);
   __syncthreads();
 
   const int foff_a = (wm0 + (lane & 31)) * LD;
@@ -616,7 +586,7 @@ __device__ __forceinline__ void conv_gemm_v3_body(const GemmArgs& a, const int b
                             j + 3 < my_steps, ko, std::make_integer_sequence<int, 16 * MT * NT>{});
     if constexpr (ABL != 6) {
 #pragma unroll
-      for (int g = 0; g < GROUPS; ++g) st.advance();
+      for (int g = 0; g < GROUPS; ++g) conv_k_advance<BK>(st);
     }
     float* t = s_cur; s_cur = s_nxt; s_nxt = s_fill; s_fill = t;
     if constexpr (ABL != 5) __syncthreads();
@@ -711,6 +681,16 @@ __global__ __launch_bounds__(256) void conv_gemm_v3_group_kernel(const GemmGroup
 constexpr int SK_MAX_BLOCKS = 768;    // three resident blocks per CU on the swizzled 48 KB layout
 constexpr int SK_FAULT_SLOT = 1024;   // u32 index in the flag region (flags use [0, 768)): sticky count of timed-out fix-ups
 constexpr size_t SK_WS_BYTES = (size_t)SK_MAX_BLOCKS * (64 * 64 * 4 + 64);   // partials + flags (flags after the partials)
+// THE HAND-OFF of a 64x64 partial, written out in conv_gemm_sk_kernel and again in conv_gemm_pp_kernel (as sk_publish / sk_take
+// functions both kernels came out with other instructions and registers — profiles/r24_a_k_walk.md); the two copies follow this:
+//   publish (block d, segment without the tile's last K-step): each wave stores its 16 accumulator rows to slot d of sk_ws, waits
+//     vmcnt(0), barrier; thread 0: agent-scope release fence, vmcnt(0), relaxed agent-scope store of 1 to sk_flags[d].
+//   take (the tile's owner, for each lower rank k of its group that covers the tile, highest first; slot = grp + k * X): thread 0
+//     spins on sk_flags[slot] with s_sleep, at most 2^24 times — a timed-out wait counts in sk_flags[SK_FAULT_SLOT] and sets
+//     s_lost — then agent-scope acquire fence and a store of 0 that hands the flag back (one consumer per contribution: the
+//     region is all-zero again at kernel end); barrier; every wave adds slot's 16 rows.  After the last contributor a set s_lost
+//     turns the tile into NaN, which every consumer downstream propagates into the flow.
+// Why it cannot deadlock is variant 4's argument above: an owner only waits on lower dispatch indices.
 
 // LD = LDS row stride (36: padded, 55 KB per block; 32: XOR-swizzled, 48 KB), BPC = resident blocks per CU the launch counts on.
 // a.sk_groups == 8: the tile list is cut into 8 contiguous ranges at TILE boundaries, one per XCD (blockIdx.x % 8 — the hardware's
@@ -772,22 +752,22 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_sk_kernel(const GemmArgs a
     float* s_cur = smem;
     float* s_nxt = smem + STAGE;
     float* s_fill = smem + 2 * STAGE;
-    st.load(0 < nsteps); st.advance(); st.store(s_cur, s_cur + BM * LD);
-    st.load(1 < nsteps); st.advance(); st.store(s_nxt, s_nxt + BM * LD);
-    st.load(2 < nsteps); st.advance();
+    st.load(0 < nsteps); conv_k_advance<BK>(st); st.store(s_cur, s_cur + BM * LD);
+    st.load(1 < nsteps); conv_k_advance<BK>(st); st.store(s_nxt, s_nxt + BM * LD);
+    st.load(2 < nsteps); conv_k_advance<BK>(st);
     __syncthreads();
     Frags<MT, NT> f0, f1;
     frag_read<MT, NT, LD>(f0, s_cur + foff_a, s_cur + foff_b, ko, 0);
     for (int j = 0; j < nsteps; ++j) {
       v3_step<BM, BN, MT, NT, 0, LD>(acc, f0, f1, st, s_cur + foff_a, s_cur + foff_b, s_nxt + foff_a, s_nxt + foff_b, s_fill,
                                  j + 3 < nsteps, ko, std::make_integer_sequence<int, 16 * MT * NT>{});
-      st.advance();
+      conv_k_advance<BK>(st);
       float* t = s_cur; s_cur = s_nxt; s_nxt = s_fill; s_fill = t;
       __syncthreads();
     }
 
     if (s1 < S) {
-      // contribution: partial -> workspace slot of this block, then publish
+      // contribution: partial -> workspace slot of this block, then publish (THE HAND-OFF, at SK_MAX_BLOCKS)
       float* mine = a.sk_ws + ((long long)d * 4 + wid) * (16 * 64) + lane;
 #pragma unroll
       for (int r = 0; r < 16; ++r) mine[r * 64] = acc[0][0][r];
@@ -800,7 +780,7 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_sk_kernel(const GemmArgs a
       }
     } else {
       if (s0 > 0) {
-        // owner of a split tile: add the partials of the group's blocks rank-1, rank-2, ... that cover [tbeg, lo)
+        // owner of a split tile: take (THE HAND-OFF, at SK_MAX_BLOCKS) the partials of the group's blocks rank-1, rank-2, ... that cover [tbeg, lo)
         for (int k = rank - 1; k >= 0; --k) {
           const int slot = grp + k * X;                // that block's dispatch index
           if (tid == 0) {
@@ -809,17 +789,14 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_sk_kernel(const GemmArgs a
               __builtin_amdgcn_s_sleep(4);
               if (++spins > (1u << 24)) {
                 // bounded spin (no hang under preemption / a debugger) — but a contribution that never arrived must not pass
-                // for a result: count it in the workspace's sticky fault word (pfk_conv_workspace_fault_offset) and poison
-                // this tile with NaN, which every consumer downstream propagates into the flow.
+                // for a result: the workspace's sticky fault word (pfk_conv_workspace_fault_offset) and a NaN tile
                 atomicAdd(a.sk_flags + SK_FAULT_SLOT, 1u);
                 s_lost = 1;
                 break;
               }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            // every contribution has exactly one consumer (this owner): hand the flag back as 0, so the flag region is all-zero
-            // again when the kernel ends and the next launch needs no memset in front of it
-            __hip_atomic_store(a.sk_flags + slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.sk_flags + slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // single consumer: hand it back as 0
           }
           __syncthreads();
           const float* theirs = a.sk_ws + ((long long)slot * 4 + wid) * (16 * 64) + lane;
@@ -906,7 +883,7 @@ __device__ __forceinline__ void pp_decode(const GemmArgs& a, int tile, long long
 // the stager moves ONE step forward in the block's flattened (segment, K-step) order
 template <int LD>
 __device__ __forceinline__ void pp_advance(const GemmArgs& a, Stager<64, 64, LD>& st, SegIter& ps, int& left) {
-  if (--left > 0) { st.advance(); return; }
+  if (--left > 0) { conv_k_advance<BK>(st); return; }
   int t, s0, s1, rel;
   if (!ps.next(t, s0, s1, rel)) return;     // past the block's last step: the remaining loads are dead (live = false)
   long long m0, batch; int n0;
@@ -1002,7 +979,7 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_pp_kernel(const GemmArgs a
     // and f0 already holds the next segment's first fragments (read from s_cur before the barrier).
 
     if (s1 < S) {
-      // contribution: partial -> workspace slot of this block, then publish
+      // contribution: partial -> workspace slot of this block, then publish (THE HAND-OFF, at SK_MAX_BLOCKS)
       float* mine = a.sk_ws + ((long long)d * 4 + wid) * (16 * 64) + lane;
 #pragma unroll
       for (int r = 0; r < 16; ++r) mine[r * 64] = acc[0][0][r];
@@ -1015,7 +992,7 @@ __global__ __launch_bounds__(256, BPC) void conv_gemm_pp_kernel(const GemmArgs a
       }
     } else {
       if (s0 > 0) {
-        // owner of a split tile: add the partials of the group's blocks rank-1, rank-2, ... that cover [tbeg, tbeg + s0)
+        // owner of a split tile: take (THE HAND-OFF, at SK_MAX_BLOCKS) the partials of the group's blocks rank-1, rank-2, ... that cover [tbeg, tbeg + s0)
         // (remainder unit space: tile `rel` of the group's remainder starts at unit rel * S, block k's share at k * Ur / Gx)
         const int tbeg = rel * S;
         for (int k = rank - 1; k >= 0; --k) {

@@ -90,13 +90,10 @@ struct Stager16 {
     wave_off = (unsigned)__builtin_amdgcn_readfirstlane(t >> 6) * 1024u;
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
-      const unsigned p = (unsigned)m0 + (unsigned)(r0 + RPP * i);
-      const bool pok = (long long)p < a.M;
-      const unsigned prow_o = fastdiv_u32(p, a.wo_mul, a.wo_sh);            // b*Ho + yo
-      const unsigned bimg = fastdiv_u32(prow_o, a.ho_mul, a.ho_sh);
-      const int px = (int)(p - prow_o * (unsigned)a.Wo) * a.stride;         // input coordinates of the centre tap
-      const int py = (int)(prow_o - bimg * (unsigned)a.Ho) * a.stride;
-      prow[i] = (int)((bimg * (unsigned)a.H + (unsigned)py) * (unsigned)a.W + (unsigned)px);
+      const ConvPixel c = conv_pixel(a, (unsigned)m0 + (unsigned)(r0 + RPP * i));
+      const bool pok = c.ok;
+      const int px = c.px, py = c.py;
+      prow[i] = c.prow;
       // taps inside the image: tx in [pw - px, W + pw - px), ty likewise — two bit ranges, combined row by row
       const int x_lo = max(pw - px, 0), x_hi = min(a.W + pw - px, kw), y_lo = max(ph - py, 0), y_hi = min(a.H + ph - py, kh);
       const unsigned xm = (pok && x_hi > x_lo) ? ((1u << x_hi) - 1u) & ~((1u << x_lo) - 1u) : 0u;
@@ -127,24 +124,6 @@ struct Stager16 {
     for (int i = 0; i < A_PT; ++i) aoff[i] = ((vmask[i] >> tap) & 1u) ? abase[i] + toff : OOB;
   }
 
-  __device__ __forceinline__ void advance() {
-    kofs += BK16;
-    c0 += BK16;
-    if (c0 >= cch) {
-      c0 = 0;
-      ++tap;
-      if (++kx == kw) {
-        kx = 0;
-        if (++ky == kh) {
-          ky = 0; tap = 0;
-          ++seg;
-          if (seg < nsrc) set_segment(seg);
-        }
-      }
-      set_tap();
-    }
-  }
-
   // One K-step's pieces into `stage`.  Past the end of K every A lane is out of range (zeros) and B is parked on K-step 0 (valid
   // memory, multiplied by zeros): the K loop stays branch-free and the counted vmcnt uniform.
   int abl = 0;      // PFK_BENCH_VARIANTS ablations 6 / 7: the A pieces of every tap but the first fetch nothing (6: zero-fill, 7: not issued)
@@ -172,7 +151,7 @@ struct Stager16 {
   __device__ __forceinline__ void piece_at(char* stage) const { piece<I>(stage, i_live, i_cok, i_coff, i_koff); }
   __device__ __forceinline__ void end_issue() {
     ++pos;
-    if (pos < total) advance();
+    if (pos < total) conv_k_advance<BK16, true>(*this);
   }
   template <int... I>
   __device__ __forceinline__ void issue_seq(char* stage, std::integer_sequence<int, I...>) {

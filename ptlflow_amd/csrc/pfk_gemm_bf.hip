@@ -76,13 +76,8 @@ struct StagerBF {
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
       // multiplier arithmetic (launch_bf fills the multipliers; M < 2^31): three instructions per division instead of ~100
-      const unsigned p = (unsigned)m0 + (unsigned)(r0 + RP * i);
-      pok[i] = (long long)p < a.M;
-      const unsigned prow_o = fastdiv_u32(p, a.wo_mul, a.wo_sh);            // b*Ho + yo
-      const unsigned bimg = fastdiv_u32(prow_o, a.ho_mul, a.ho_sh);
-      px[i] = (int)(p - prow_o * (unsigned)a.Wo) * a.stride;                // input coordinates of the centre tap
-      py[i] = (int)(prow_o - bimg * (unsigned)a.Ho) * a.stride;
-      prow[i] = (int)((bimg * (unsigned)a.H + (unsigned)py[i]) * (unsigned)a.W + (unsigned)px[i]);
+      const ConvPixel c = conv_pixel(a, (unsigned)m0 + (unsigned)(r0 + RP * i));
+      pok[i] = c.ok; px[i] = c.px; py[i] = c.py; prow[i] = c.prow;
     }
     // BDMA: lane (row r0, physical chunk t & 3) fetches the LOGICAL chunk that belongs there
     const int c8b = BDMA ? (((t & 3) ^ ((r0 >> 2) & 3)) * 8) : c8;
@@ -111,23 +106,6 @@ struct StagerBF {
     for (int i = 0; i < A_PT; ++i) {
       const bool ok = pok[i] && (unsigned)(py[i] + dy) < (unsigned)H && (unsigned)(px[i] + dx) < (unsigned)W;
       aoff[i] = ok ? abase[i] + toff : OOB;
-    }
-  }
-
-  __device__ __forceinline__ void advance() {
-    kofs += BKB;
-    c0 += BKB;
-    if (c0 >= cch) {
-      c0 = 0;
-      if (++kx == kw) {
-        kx = 0;
-        if (++ky == kh) {
-          ky = 0;
-          ++seg;
-          if (seg < nsrc) set_segment(seg);
-        }
-      }
-      set_tap();
     }
   }
 
@@ -160,7 +138,7 @@ struct StagerBF {
   }
   __device__ __forceinline__ void load_done() {
     ++pos;
-    if (pos < total) advance();
+    if (pos < total) conv_k_advance<BKB>(*this);
   }
   // plane PL of half Hf (4 floats) of row chunk (U, I) of set S -> dwords 2*Hf, 2*Hf+1 of pa[PL]; the running
   // residual lives in `sr` between the planes of one half

@@ -107,6 +107,7 @@ __device__ __forceinline__ void mask_upsample_epilogue(const f32x16 (&acc)[1][5]
     const unsigned p = (unsigned)m0 + (unsigned)pl;
     f32x2 v = {0.f, 0.f};
     if ((long long)p < M) {
+      // (restates conv_pixel of pfk_gemm.h for stride 1, here and below: this epilogue gets loose scalars, no argument block)
       const unsigned prow = fastdiv_u32(p, wo_mul, wo_sh);          // b*H + y
       const unsigned bimg = fastdiv_u32(prow, ho_mul, ho_sh);
       const int x = (int)(p - prow * W), y = (int)(prow - bimg * H);

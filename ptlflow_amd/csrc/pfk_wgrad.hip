@@ -35,28 +35,6 @@ struct WgradArgs {
   long long px_per_split; // multiple of 32
 };
 
-// One (source, tap, 32-channel) entry of the forward kernel's K enumeration.
-struct ChunkRef { const float* src; int ld, cch, c0, dy, dx, bias, live; };
-
-__device__ __forceinline__ ChunkRef chunk_ref(const WgradArgs& a, int chunk) {
-  ChunkRef c;
-  const int taps = a.kh * a.kw;
-  int r = chunk, cps = (a.ch0 + 31) >> 5;
-  c.src = a.src0; c.ld = a.ld0; c.cch = a.ch0;
-  if (a.nsrc > 1 && r >= taps * cps) {
-    r -= taps * cps; cps = (a.ch1 + 31) >> 5; c.src = a.src1; c.ld = a.ld1; c.cch = a.ch1;
-    if (a.nsrc > 2 && r >= taps * cps) { r -= taps * cps; cps = (a.ch2 + 31) >> 5; c.src = a.src2; c.ld = a.ld2; c.cch = a.ch2; }
-  }
-  c.live = chunk < a.chunks;
-  c.bias = a.with_bias && chunk == a.chunks - 1;
-  const bool plain = c.live && !c.bias;
-  const int tap = plain ? r / cps : 0;
-  c.c0 = plain ? (r - tap * cps) * 32 : 0;
-  c.dy = plain ? tap / a.kw - (a.kh >> 1) : 0;
-  c.dx = plain ? tap % a.kw - (a.kw >> 1) : 0;
-  return c;
-}
-
 // CB = 32-row output-channel blocks per tile (4, 2 or 1); the block's four waves cover CB co-blocks x NCH = 4 / CB consecutive K
 // chunks, one 32x32 accumulator each, so the tile is (32 CB) output channels x (32 NCH) K columns.  The host picks CB to waste
 // the fewest MFMAs on channel padding (cout = 64: CB 2, not half-empty 128-row tiles; 96 and 192: three exact 32- / 64-row tiles).
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
   bool c_ok[NCH], is_bias[NCH], yok[CB];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    const ChunkRef c = chunk_ref(a, grp * NCH + i);
+    const auto c = chunk_ref(a, grp * NCH + i);
     rsx[i] = buffer_rsrc(c.src);
     tap_off[i] = (c.dy * a.W + c.dx) * c.ld + c.c0 + q * 4;
     cdy[i] = c.dy; cdx[i] = c.dx; cld[i] = c.ld;

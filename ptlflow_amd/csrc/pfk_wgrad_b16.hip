@@ -41,28 +41,6 @@ struct WgradB16Args {
   long long px_per_split; // multiple of KS
 };
 
-// One (source, tap, 32-channel) entry of the K enumeration.
-struct ChunkRef { const void* src; int ld, cch, c0, dy, dx, bias, live; };
-
-__device__ __forceinline__ ChunkRef chunk_ref(const WgradB16Args& a, int chunk) {
-  ChunkRef c;
-  const int taps = a.kh * a.kw;
-  int r = chunk, cps = (a.ch0 + 31) >> 5;
-  c.src = a.src0; c.ld = a.ld0; c.cch = a.ch0;
-  if (a.nsrc > 1 && r >= taps * cps) {
-    r -= taps * cps; cps = (a.ch1 + 31) >> 5; c.src = a.src1; c.ld = a.ld1; c.cch = a.ch1;
-    if (a.nsrc > 2 && r >= taps * cps) { r -= taps * cps; cps = (a.ch2 + 31) >> 5; c.src = a.src2; c.ld = a.ld2; c.cch = a.ch2; }
-  }
-  c.live = chunk < a.chunks;
-  c.bias = a.with_bias && chunk == a.chunks - 1;
-  const bool plain = c.live && !c.bias;
-  const int tap = plain ? r / cps : 0;
-  c.c0 = plain ? (r - tap * cps) * 32 : 0;
-  c.dy = plain ? tap / a.kw - (a.kh >> 1) : 0;
-  c.dx = plain ? tap % a.kw - (a.kw >> 1) : 0;
-  return c;
-}
-
 // 4 rows x 16 columns of 16-bit elements per 16-lane group, delivered column-major (ds_read_b64_tr_b16)
 __device__ __forceinline__ s16x4 tr_read(const unsigned short* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
@@ -95,7 +73,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_b16_kernel(const WgradB16Args 
   bool c_ok[NCH], is_bias[NCH], yok[CB];
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    const ChunkRef c = chunk_ref(a, grp * NCH + i);
+    const auto c = chunk_ref(a, grp * NCH + i);
     rsx[i] = buffer_rsrc(c.src);
     tap_off[i] = (c.dy * a.W + c.dx) * c.ld + c.c0 + q * 8;
     cdy[i] = c.dy; cdx[i] = c.dx; cld[i] = c.ld;

@@ -5,6 +5,7 @@
 // [splits][cout][ktot] whose K enumeration is (source, tap, channel padded to 32) [+ one 32-column bias chunk].
 // In front of it, what the two launchers plan alike: tile height, grid, pixel slices and the launch by tile height.
 #pragma once
+#include "pfk_conv_k.h"   // chunk_ref: the main kernels' (source, tap, chunk) entries, in the K order this file's kernel inverts
 #include "pfk_launch.h"
 
 namespace {

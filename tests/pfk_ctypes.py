@@ -41,6 +41,19 @@ def declared():
     return sorted(set(re.findall(r"\b(pfk_[a-z0-9_]+)\s*\(", src)))
 
 
+def rocm_clang():
+    """the clang that stands next to hipcc, for the small host programs some tests compile; None where there is none"""
+    import shutil
+    from pathlib import Path
+    from ptlflow_amd import _build
+    hipcc = shutil.which(_build.HIPCC) or shutil.which("hipcc")
+    cands = []
+    if hipcc:
+        bindir = Path(os.path.realpath(hipcc)).parent
+        cands += [bindir / "amdclang", bindir / "clang", bindir.parent / "llvm" / "bin" / "clang", bindir.parent / "lib" / "llvm" / "bin" / "clang"]
+    return next((str(c) for c in cands if c.exists()), None)
+
+
 def lib():
     """libpfk.so through ctypes (built first where the tree has none); torch's HIP runtime is loaded before it, as the product does."""
     import ptlflow_amd

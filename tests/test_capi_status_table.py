@@ -8,8 +8,6 @@ wrongly) accepted would be a launch on them.  Without one an accepted case answe
 import ctypes
 import importlib.util
 import json
-import os
-import shutil
 import subprocess
 from pathlib import Path
 
@@ -65,19 +63,9 @@ MIRRORS = {"pfk_conv_src": pfk_ctypes.Src, "pfk_conv_src_b16": pfk_ctypes.SrcB16
            "pfk_conv_b16_desc": pfk_ctypes.DescB16}
 
 
-def _rocm_clang():
-    from ptlflow_amd import _build
-    hipcc = shutil.which(_build.HIPCC) or shutil.which("hipcc")
-    cands = []
-    if hipcc:
-        bindir = Path(os.path.realpath(hipcc)).parent
-        cands += [bindir / "amdclang", bindir / "clang", bindir.parent / "llvm" / "bin" / "clang", bindir.parent / "lib" / "llvm" / "bin" / "clang"]
-    return next((str(c) for c in cands if c.exists()), None)
-
-
 def test_ctypes_mirror_matches_header(tmp_path):
     """sizeof and every offsetof of the four structs, printed by a C program compiled against include/pfk.h"""
-    clang = _rocm_clang()
+    clang = pfk_ctypes.rocm_clang()
     if clang is None:
         pytest.skip("no ROCm clang next to hipcc")
     lines = "".join(f"  O({cname}, {f});\n" for cname, cls in MIRRORS.items() for f, _ in cls._fields_)
