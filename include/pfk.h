@@ -819,6 +819,47 @@ int pfk_pm_to_nchw_f32(const float* in, int in_ld, int in_coff, float* out, int 
 int pfk_pm_to_cm_f32(const float* in, int in_ld, float* out, int out_ld, int B, int C, int N,
                      pfk_stream_t stream);
 
+/* ---- K14: CCMR's XCiT motion aggregator (ccmr/xcit.py, XCiT(128, depth 1, 8 heads, mlp_ratio 1, separate=True); additions, ABI 7) ----
+ * fp32 pixel-major rows [M][ld] of which only the C real columns are read or written; rows 16-byte aligned, ld % 4 == 0 (ld in
+ * floats, 64-bit: no 2 GB limit on a span).  Deterministic: no atomics, every sum in an order fixed by the shape.  Arguments are
+ * validated before the device is touched: PFK_ERR_BAD_ARG / PFK_ERR_ALIGNMENT, PFK_ERR_UNSUPPORTED for a width the kernels are not
+ * built for.  The dense layers between them are pfk_conv2d_f32 / pfk_conv2d_group_f32 launches.
+ *
+ * pfk_layernorm_rows_f32: out[p][c] = (in[p][c] - mean_p) * rstd_p [* weight[c]] [+ bias[c]], mean over the C channels of the row,
+ * then the biased variance about it, rstd = 1 / sqrt(var + eps).  weight / bias [C], 16-byte aligned, either may be NULL.
+ * C % 4 == 0, 4 <= C <= 512.  out == in with the same ld is allowed, any other overlap is PFK_ERR_BAD_ARG. */
+int pfk_layernorm_rows_f32(const float* in, long long in_ld, const float* weight, const float* bias, float eps, float* out,
+                           long long out_ld, long long M, int C, pfk_stream_t stream);
+
+/* pfk_xca_map_f32: XCA_separate's attention map (ccmr/xcit.py:211-229).  qk [B*N][qk_ld]: columns [0, heads*dh) are q, the next
+ * heads*dh are k, column head*dh + d within each; temperature [heads]; A [B][heads][dh][dh] contiguous:
+ *   A[b,h,i,j] = softmax_j( temperature[h] * (sum_n q[n,h,i] k[n,h,j]) / (max(|q_{h,i}|, 1e-12) * max(|k_{h,j}|, 1e-12)) ),
+ * the norms over the N tokens of image b.  One pass over the rows forms the Gram and both norms per 256-token chunk (fp32) into
+ * the workspace; the chunks are summed in order in double.  heads == 8 and dh == 16, anything else PFK_ERR_UNSUPPORTED.
+ * workspace: pfk_xca_map_workspace_bytes(B, N, heads, dh) bytes (< 0: the status), 16-byte aligned, overlapping nothing. */
+long long pfk_xca_map_workspace_bytes(int B, long long N, int heads, int dh);
+int pfk_xca_map_f32(const float* qk, long long qk_ld, const float* temperature, float* A, void* workspace, long long workspace_bytes, int B,
+                    long long N, int heads, int dh, pfk_stream_t stream);
+
+/* The local patch interaction of XCABlock (ccmr/xcit.py:98-139, :298-299) around its GroupNorm, p = (b*H + y)*W + x, C == 128:
+ *   pfk_xcit_lpi1_f32:  u = GELU(dw3x3(LN(x)) + dw_bias), LN with ln_weight / ln_bias [C] and ln_eps; the sums of u and u^2 of every
+ *                       block and channel group (double) go to the workspace;
+ *   pfk_xcit_lpi2_f32:  the GroupNorm statistics of each image (groups == 8 groups of C / 8 channels over H*W pixels, biased variance,
+ *                       gn_eps) are finished from those partials in block order, in double; then
+ *                       x2 = x + gamma * (dw3x3(GN(u)) + dw_bias),  t = LN(x2) [* ln_weight] [+ ln_bias]   (ln_weight / ln_bias may be NULL).
+ * dw_weight [C][9] (tap ky*3 + kx), "same" zero padding of the NORMALISED tensor: a tap outside the image contributes exactly 0, and
+ * no tap leaves its image.  Any H, W >= 1.  Per-channel vectors 16-byte aligned.  No output may overlap an input, another output or
+ * the workspace.  workspace: pfk_xcit_lpi_workspace_bytes(B, H, W) bytes (< 0: the status), 16-byte aligned, the same for both
+ * entries: lpi2 reads what lpi1 left there.  C != 128 or groups != 8: PFK_ERR_UNSUPPORTED. */
+long long pfk_xcit_lpi_workspace_bytes(int B, int H, int W);
+int pfk_xcit_lpi1_f32(const float* x, long long x_ld, const float* ln_weight, const float* ln_bias, float ln_eps, const float* dw_weight,
+                      const float* dw_bias, float* u, long long u_ld, void* workspace, long long workspace_bytes, int B, int H, int W,
+                      int C, pfk_stream_t stream);
+int pfk_xcit_lpi2_f32(const float* u, long long u_ld, const float* gn_weight, const float* gn_bias, float gn_eps, int groups,
+                      const float* dw_weight, const float* dw_bias, const float* gamma, const float* x, long long x_ld, float* x2,
+                      long long x2_ld, const float* ln_weight, const float* ln_bias, float ln_eps, float* t, long long t_ld, void* workspace,
+                      long long workspace_bytes, int B, int H, int W, int C, pfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

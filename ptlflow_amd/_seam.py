@@ -10,18 +10,11 @@ from typing import Optional
 import torch
 
 
-class WrappedModule(torch.nn.Module):
-    """A drop-in for the model's sub-module `ref`: `ref`'s children are re-registered under their own names (state_dict keys,
-    checkpoints and optimizers are unchanged) and `ref` itself is kept in a list (not registered twice in the module tree)."""
-
-    def __init__(self, ref: torch.nn.Module):
-        super().__init__()
-        for name, child in ref.named_children():
-            self.add_module(name, child)
-        self._ref = [ref]
-        self.training = ref.training
-        self._engine = None
-        self._versions = None
+class EngineSlot:
+    """One engine and the versions of the tensors it was packed from: what `WrappedModule` keeps for its own module, and what a
+    wrapper keeps for each further module it serves (`PfkUpdateBlock`'s XCiT aggregators, one per scale)."""
+    _engine = None
+    _versions = None
 
     def _engine_for(self, device, tensors, build, repack=None):
         """`_engine`, made by `build()` when there is none for `device`.  When a tensor of `tensors` (parameters, buffers) changed
@@ -33,6 +26,20 @@ class WrappedModule(torch.nn.Module):
             repack(self._engine)
         self._versions = v
         return self._engine
+
+
+class WrappedModule(torch.nn.Module, EngineSlot):
+    """A drop-in for the model's sub-module `ref`: `ref`'s children are re-registered under their own names (state_dict keys,
+    checkpoints and optimizers are unchanged) and `ref` itself is kept in a list (not registered twice in the module tree)."""
+
+    def __init__(self, ref: torch.nn.Module):
+        super().__init__()
+        for name, child in ref.named_children():
+            self.add_module(name, child)
+        self._ref = [ref]
+        self.training = ref.training
+        self._engine = None
+        self._versions = None
 
 
 def eligible(tensors, params=(), dtypes=None, autocast=None) -> bool:

@@ -1123,6 +1123,72 @@ void gru_backward_zr(const Tensor& d_rh, const Tensor& h, const Tensor& r, Tenso
                                    dzr, dense(op, dh, "dh", F32, AtLeast{M * C}).f32(), M, (int)C, cur_stream()), op);
 }
 
+// ---- K14: CCMR's XCiT motion aggregator (pfk_xcit.hip).  fp32 row views [M, C] of wider buffers; only C columns are touched.
+void layernorm_rows(const Tensor& in, const c10::optional<Tensor>& weight, const c10::optional<Tensor>& bias, double eps, Tensor out) {
+  OpScope scope(in);
+  const Rows i = rows("layernorm_rows", in, "inp", F32);
+  const Rows o = rows("layernorm_rows", out, "out", F32).expect(i.rows, i.cols);
+  const float* w = dense("layernorm_rows", weight, "weight", F32, i.cols).f32();
+  const float* b = dense("layernorm_rows", bias, "bias", F32, i.cols).f32();
+  check_ok(pfk_layernorm_rows_f32(i.f32(), i.ld, w, b, (float)eps, o.f32(), o.ld, i.rows, (int)i.cols, cur_stream()), "layernorm_rows");
+}
+
+// qk [B*N, 2 * heads * dh] view (q | k), temperature [heads] (any shape with that many elements), A [B, heads, dh, dh] contiguous
+void xca_map(const Tensor& qk, const Tensor& temperature, Tensor A, int64_t B, int64_t N) {
+  OpScope scope(qk);
+  TORCH_CHECK(A.dim() == 4 && A.size(0) == B && A.size(2) == A.size(3), "xca_map: A must be [B, heads, dh, dh]");
+  const int64_t heads = A.size(1), dh = A.size(2);
+  const Rows q = rows("xca_map", qk, "qk", F32).expect(B * N, 2 * heads * dh);
+  const float* t = dense("xca_map", temperature, "temperature", F32, heads).f32();
+  float* a = dense("xca_map", A, "A", F32, B * heads * dh * dh).f32();
+  const long long need = pfk_xca_map_workspace_bytes((int)B, N, (int)heads, (int)dh);
+  check_ok(need < 0 ? (int)need : PFK_OK, "xca_map");
+  auto ws = byte_workspace(need, qk);
+  check_ok(pfk_xca_map_f32(q.f32(), q.ld, t, a, ws.second, need, (int)B, N, (int)heads, (int)dh, cur_stream()), "xca_map");
+}
+
+int64_t xcit_lpi_workspace_bytes(int64_t B, int64_t H, int64_t W) { return pfk_xcit_lpi_workspace_bytes((int)B, (int)H, (int)W); }
+
+// x [B*H*W, C] view -> u [B*H*W, C] view; dw_weight [C, 1, 3, 3] or [C, 9] contiguous; workspace: xcit_lpi_workspace_bytes(B, H, W) bytes
+void xcit_lpi1(const Tensor& x, const Tensor& ln_weight, const Tensor& ln_bias, double ln_eps, const Tensor& dw_weight,
+               const Tensor& dw_bias, Tensor u, Tensor workspace, int64_t B, int64_t H, int64_t W) {
+  OpScope scope(x);
+  const Rows i = rows("xcit_lpi1", x, "x", F32).expect(B * H * W, AtLeast{0});
+  const int64_t C = i.cols;
+  const Rows o = rows("xcit_lpi1", u, "u", F32).expect(B * H * W, C);
+  const float* lw = dense("xcit_lpi1", ln_weight, "ln_weight", F32, C).f32();
+  const float* lb = dense("xcit_lpi1", ln_bias, "ln_bias", F32, C).f32();
+  const float* dw = dense("xcit_lpi1", dw_weight, "dw_weight [C, 9]", F32, C * 9).f32();
+  const float* db = dense("xcit_lpi1", dw_bias, "dw_bias", F32, C).f32();
+  void* ws = dense("xcit_lpi1", workspace, "workspace", Raw).raw();
+  check_ok(pfk_xcit_lpi1_f32(i.f32(), i.ld, lw, lb, (float)ln_eps, dw, db, o.f32(), o.ld, ws, (long long)workspace.nbytes(), (int)B, (int)H,
+                             (int)W, (int)C, cur_stream()),
+           "xcit_lpi1");
+}
+
+// u, x [B*H*W, C] views -> x2, t [B*H*W, C] views; the workspace xcit_lpi1 filled for this u
+void xcit_lpi2(const Tensor& u, const Tensor& gn_weight, const Tensor& gn_bias, double gn_eps, int64_t groups, const Tensor& dw_weight,
+               const Tensor& dw_bias, const Tensor& gamma, const Tensor& x, Tensor x2, const c10::optional<Tensor>& ln_weight,
+               const c10::optional<Tensor>& ln_bias, double ln_eps, Tensor t, Tensor workspace, int64_t B, int64_t H, int64_t W) {
+  OpScope scope(u);
+  const Rows ui = rows("xcit_lpi2", u, "u", F32).expect(B * H * W, AtLeast{0});
+  const int64_t C = ui.cols;
+  const Rows xi = rows("xcit_lpi2", x, "x", F32).expect(B * H * W, C);
+  const Rows xo = rows("xcit_lpi2", x2, "x2", F32).expect(B * H * W, C);
+  const Rows to = rows("xcit_lpi2", t, "t", F32).expect(B * H * W, C);
+  const float* gw = dense("xcit_lpi2", gn_weight, "gn_weight", F32, C).f32();
+  const float* gb = dense("xcit_lpi2", gn_bias, "gn_bias", F32, C).f32();
+  const float* dw = dense("xcit_lpi2", dw_weight, "dw_weight [C, 9]", F32, C * 9).f32();
+  const float* db = dense("xcit_lpi2", dw_bias, "dw_bias", F32, C).f32();
+  const float* gm = dense("xcit_lpi2", gamma, "gamma", F32, C).f32();
+  const float* lw = dense("xcit_lpi2", ln_weight, "ln_weight", F32, C).f32();
+  const float* lb = dense("xcit_lpi2", ln_bias, "ln_bias", F32, C).f32();
+  void* ws = dense("xcit_lpi2", workspace, "workspace", Raw).raw();
+  check_ok(pfk_xcit_lpi2_f32(ui.f32(), ui.ld, gw, gb, (float)gn_eps, (int)groups, dw, db, gm, xi.f32(), xi.ld, xo.f32(), xo.ld, lw, lb,
+                             (float)ln_eps, to.f32(), to.ld, ws, (long long)workspace.nbytes(), (int)B, (int)H, (int)W, (int)C, cur_stream()),
+           "xcit_lpi2");
+}
+
 int64_t abi_version() { return pfk_abi_version(); }
 int64_t conv_workspace_bytes() { return pfk_conv_workspace_bytes(); }
 int64_t conv_workspace_fault_offset() { return pfk_conv_workspace_fault_offset(); }
@@ -1240,6 +1306,14 @@ TORCH_LIBRARY(pfk, m) {
   m.def("convex_upsample_bwd(Tensor flow, Tensor mask, Tensor grad_out, Tensor(a!) grad_mask, Tensor(b!) grad_flow) -> ()");
   m.def("convex_upsample_info_bwd(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor grad_flow_up, Tensor? grad_info_up, "
         "Tensor(a!) grad_mask, Tensor(b!) grad_flow_pm, Tensor(c!) grad_info_pm) -> ()");
+  m.def("layernorm_rows(Tensor inp, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> ()");
+  m.def("xca_map(Tensor qk, Tensor temperature, Tensor(a!) A, int B, int N) -> ()");
+  m.def("xcit_lpi_workspace_bytes(int B, int H, int W) -> int", &xcit_lpi_workspace_bytes);
+  m.def("xcit_lpi1(Tensor x, Tensor ln_weight, Tensor ln_bias, float ln_eps, Tensor dw_weight, Tensor dw_bias, Tensor(a!) u, "
+        "Tensor(b!) workspace, int B, int H, int W) -> ()");
+  m.def("xcit_lpi2(Tensor u, Tensor gn_weight, Tensor gn_bias, float gn_eps, int groups, Tensor dw_weight, Tensor dw_bias, Tensor gamma, "
+        "Tensor x, Tensor(a!) x2, Tensor? ln_weight, Tensor? ln_bias, float ln_eps, Tensor(b!) t, Tensor(c!) workspace, int B, int H, "
+        "int W) -> ()");
   m.def("nchw_to_pm(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_nchw(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_cm(Tensor inp, Tensor(a!) out) -> ()");
@@ -1290,6 +1364,10 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("corr_volume_bwd", &corr_volume_bwd);
   m.impl("convex_upsample_bwd", &convex_upsample_bwd);
   m.impl("convex_upsample_info_bwd", &convex_upsample_info_bwd);
+  m.impl("layernorm_rows", &layernorm_rows);
+  m.impl("xca_map", &xca_map);
+  m.impl("xcit_lpi1", &xcit_lpi1);
+  m.impl("xcit_lpi2", &xcit_lpi2);
   m.impl("nchw_to_pm", &nchw_to_pm);
   m.impl("pm_to_nchw", &pm_to_nchw);
   m.impl("pm_to_cm", &pm_to_cm);

@@ -46,6 +46,7 @@ from .encoder import PfkEncoder
 from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
 from .sea_update import HEAD_SHAPES, PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam, sea_block_shapes
 from .update import PfkUpdateBlock, UpdateSpec, basic_spec, ccmr_spec, gma_spec, ms_raft_plus_spec, small_spec
+from .xcit import register_xcit_aggregator  # noqa: F401  (the hook for further aggregator classes, next to the other register_* calls)
 
 _ORIG = "_pfk_original_get_corr_block"
 
@@ -605,7 +606,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
-               sea_raft_train: bool = False, train_upsample: bool = False) -> torch.nn.Module:
+               sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -653,7 +654,14 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     autocast, the behaviour probe passed): forward on the inference kernel, backward on `pfk_convex_upsample_bwd_f32` /
     `pfk_convex_upsample_info_bwd_pm_f32`, counted in the seam's ``train_calls``.  Everything else, and every
     gradient graph while it is off, goes to the model's own method.  Raises ValueError when the model gets neither seam, and on a
-    SEA-RAFT model unless ``sea_raft_update`` is True or "fp32".  A second call with another value switches the installed seams."""
+    SEA-RAFT model unless ``sea_raft_update`` is True or "fp32".  A second call with another value switches the installed seams.
+    ``ccmr_aggregator`` (default False): on a CCMR model, the update block also runs the scales' XCiT motion aggregators
+    (``update_block.aggregator[i]``, ccmr/xcit.py) on the kernels of xcit.py instead of calling the modules in torch:
+    the attention branch folded into one GEMM per image once per (forward, scale), seven launches per iteration on the update engine's
+    own rows.  It serves eval-mode calls outside grad mode and autocast on fp32 GPU tensors with ``conv_precision="fp32"``, and only
+    when every aggregator is a served class (`register_xcit_aggregator`) that passes `xcit.match_xcit_aggregator`; every other call
+    runs the modules as before.  Served calls are counted in ``update_block.aggregator_calls``.  A second call with another value
+    switches the path."""
     check_precision(train_precision, PRECISIONS, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
@@ -680,6 +688,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
     if update_block and isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
         model.update_block.train_precision = train_precision
+        model.update_block.set_ccmr_aggregator(ccmr_aggregator)
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
     if sea:
         model.update_block.sea_train = bool(sea_raft_train)

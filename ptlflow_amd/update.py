@@ -32,8 +32,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import load_native
-from ._seam import WrappedModule, pixel_rows
+from . import load_native, xcit
+from ._seam import EngineSlot, WrappedModule, pixel_rows
 from .conv_path import EPI_GRU_Q, EPI_GRU_ZR, EPI_LINEAR, resolve
 from .packing import (pack_cin2_weight, pack_conv_weight, pack_flow_head_weight, pack_wino1d_weight, pack_wino_weight, permute_mask_head,
                       round_up, split_bf16_planes)
@@ -801,6 +801,35 @@ class PfkUpdateBlock(WrappedModule):
         self._attn_ref, self._attn_version = None, -1
         self._skip = None      # patch._DeadWorkSkip when `accelerate(model)` found the loop's dead work provably dead (patch.py)
         self._last_out = None  # the `net` tensor handed back by the previous call: the same OBJECT coming in marks the next iteration
+        # CCMR, `accelerate(model, ccmr_aggregator=True)`: the scales' XCiT aggregators on the kernels (xcit.py)
+        self.ccmr_aggregator = False
+        self.aggregator_calls = 0     # calls the aggregator engines served
+        self._agg_ok = False          # every `aggregator[i]` is a served class and matches (decided when the option is set)
+        self._agg_slots: Dict[int, EngineSlot] = {}
+
+    def set_ccmr_aggregator(self, on: bool) -> None:
+        """`accelerate`'s ``ccmr_aggregator``: on only for a block with an external aggregate slot whose `aggregator` modules all
+        match (`xcit.match_xcit_aggregator`, of a served class); off drops the engines."""
+        self.ccmr_aggregator = bool(on)
+        aggs = getattr(self._ref[0], "aggregator", None)
+        self._agg_ok = bool(on) and self.spec.external_aggregate and self.spec.motion_channels == xcit.DIM and aggs is not None \
+            and len(aggs) > 0 and all(xcit.served(m) and xcit.match_xcit_aggregator(m) for m in aggs)
+        if not self._agg_ok:
+            self._agg_slots = {}
+
+    def _aggregator_engine(self, level_index: int, eng: UpdateEngine, tensors, grad: bool) -> Optional["xcit.XcitAggregatorEngine"]:
+        """the engine that serves this call's `aggregator[level_index]`, or None: option on and every aggregator matched, eval,
+        no grad mode, no autocast, fp32 CUDA tensors, the fp32 convolution path, fp32 parameters"""
+        if not self._agg_ok or self.training or grad or torch.is_autocast_enabled("cuda") or not eng.path.fp32_tiles:
+            return None
+        if any(t is None or not t.is_cuda or t.dtype != torch.float32 for t in tensors):
+            return None
+        module = self._ref[0].aggregator[level_index]
+        params = list(module.parameters())
+        if module.training or any(p.dtype != torch.float32 for p in params):
+            return None
+        slot = self._agg_slots.setdefault(int(level_index), EngineSlot())
+        return slot._engine_for(eng.device, params, lambda: xcit.XcitAggregatorEngine(module, eng.device), lambda e: e.pack())
 
     def _get_engine(self, device) -> UpdateEngine:
         return self._engine_for(device, self.parameters(),
@@ -836,10 +865,11 @@ class PfkUpdateBlock(WrappedModule):
                                                     self.train_precision, attention)
                 return h.to(net.dtype), (None if mask is None else mask.to(net.dtype)), delta.to(net.dtype)
             return self._ref[0](net, inp, corr, flow, *extra, **kw)
+        grad = torch.is_grad_enabled()      # (the aggregator engines serve no-grad calls only, whether or not anything requires grad)
         with torch.no_grad():
-            return self._forward_kernels(net, inp, corr, flow, attention, args.get("global_context"), args.get("level_index", 0))
+            return self._forward_kernels(net, inp, corr, flow, attention, args.get("global_context"), args.get("level_index", 0), grad)
 
-    def _forward_kernels(self, net, inp, corr, flow, attention=None, global_context=None, level_index=0):
+    def _forward_kernels(self, net, inp, corr, flow, attention=None, global_context=None, level_index=0, grad=False):
         if not net.is_cuda:
             raise RuntimeError("PfkUpdateBlock needs GPU tensors (no CPU fallback)")
         eng = self._get_engine(net.device)
@@ -881,9 +911,15 @@ class PfkUpdateBlock(WrappedModule):
             # CCMR (ccmr/update.py:152-163): motion encoder on the kernels, the scale's XCiT block — the reference's own module,
             # torch — on the NCHW view of the motion features, its output into the aggregate slot of hx, then GRU + heads
             eng.motion(corr_pm)
-            mf = eng.motion_view.unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
-            mfg = self._ref[0].aggregator[level_index](global_context, mf)
-            ops.nchw_to_pm(mfg.float().contiguous(), eng.aggregate_view)
+            agg = self._aggregator_engine(level_index, eng, (net, global_context), grad) if self.ccmr_aggregator else None
+            if agg is not None:
+                # K14: the same module on the rows, motion_view -> aggregate_view; its per-scale part once per (forward, scale)
+                agg.run(global_context, eng.motion_view, eng.aggregate_view, B, H, W, refresh=new_forward)
+                self.aggregator_calls += 1
+            else:
+                mf = eng.motion_view.unflatten(0, (B, H, W)).permute(0, 3, 1, 2)
+                mfg = self._ref[0].aggregator[level_index](global_context, mf)
+                ops.nchw_to_pm(mfg.float().contiguous(), eng.aggregate_view)
             eng.gru()
         else:
             if eng.spec.aggregate:
