@@ -860,6 +860,37 @@ int pfk_xcit_lpi2_f32(const float* u, long long u_ld, const float* gn_weight, co
                       long long x2_ld, const float* ln_weight, const float* ln_bias, float ln_eps, float* t, long long t_ld, void* workspace,
                       long long workspace_bytes, int B, int H, int W, int C, pfk_stream_t stream);
 
+/* ---- K15: the multi-scale GroupNorm encoders (ccmr/extractor.py, ms_raft_plus/extractor.py: `fnet` / `cnet` of CCMR, CCMR+, MS-RAFT+;
+ * additions, ABI 7) ----
+ * fp32 pixel-major rows x[B*HW][ld] of which only columns [0, C) are read or written; rows 16-byte aligned, every ld % 4 == 0 (ld in
+ * floats).  Memory-bound row kernels, 16-byte accesses.  Deterministic: no atomics, every sum in an order fixed by the shape.
+ * Arguments are validated before the device is touched.
+ *
+ * pfk_groupnorm_stats_f32: nn.GroupNorm statistics (biased variance, eps inside the sqrt) over groups of `group_size` CONSECUTIVE
+ * channels, per (image, group) over HW * group_size values, finished into the affine pair the apply pass reads, both [B][C] fp32:
+ *   scale[b][c] = rstd_g * gamma[c],   shift[b][c] = beta[c] - mean_g * rstd_g * gamma[c]      (g = c / group_size)
+ * One pass over x: sum(x) and sum(x*x) in double per 256-pixel chunk of an image, the chunks added in a fixed order, var =
+ * E[x^2] - mean^2 and the pair evaluated in double and rounded to fp32 once.  gamma / beta [C] are required (PFK_ERR_BAD_ARG).
+ * group_size must be 8 — the group of every GroupNorm in those encoders — with C % 8 == 0 and C <= 1024: anything else
+ * PFK_ERR_UNSUPPORTED.  workspace: pfk_groupnorm_workspace_bytes(B, HW, C) bytes (< 0: the status), 8-byte aligned. */
+long long pfk_groupnorm_workspace_bytes(int B, int HW, int C);
+int pfk_groupnorm_stats_f32(const float* x, int ld, int B, int HW, int C, int group_size, const float* gamma, const float* beta,
+                            float eps, float* scale, float* shift, void* workspace, long long workspace_bytes, pfk_stream_t stream);
+
+/* out = relu?(x * scale[b][c] + shift[b][c]) ; if residual: out = relu_after?(residual + out)  — pfk_norm_apply_f32's contract with
+ * the affine pair of pfk_groupnorm_stats_f32 in place of mean / rstd (x * scale + shift is one fused multiply-add).  scale / shift
+ * [B][C], 16-byte aligned, C % 4 == 0.  x, residual and out each have their own ld; out may alias x. */
+int pfk_affine_apply_f32(const float* x, int x_ld, const float* scale, const float* shift, const float* residual, int residual_ld,
+                         float* out, int out_ld, int B, int HW, int C, int relu, int relu_after_residual, pfk_stream_t stream);
+
+/* Bilinear resize of rows in[B*Hi*Wi][in_ld] to out[B*Ho*Wo][out_ld], channels [0, C), C % 4 == 0: F.interpolate(mode="bilinear",
+ * align_corners=False), which for upsizing is also torchvision's TF.resize (antialias on) — the source coordinate of output o is
+ * (o + 0.5) * in / out - 0.5 clamped to the image, the two taps per axis weighted linearly, edge taps replicated; no tap leaves its
+ * image.  Coordinates and weights come from integer arithmetic (no rounded coordinate).  Any Ho >= Hi and Wo >= Wi (the same size: a
+ * copy); downsizing needs another filter: PFK_ERR_UNSUPPORTED, as is 2 * Ho * Hi or 2 * Wo * Wi >= 2^31.  out must not overlap in. */
+int pfk_resize_bilinear_pm_f32(const float* in, int in_ld, float* out, int out_ld, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                               pfk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

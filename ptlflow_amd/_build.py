@@ -52,6 +52,7 @@ HIP_SOURCES = [
     ("pfk_convnext.hip", []),                 # SEA-RAFT: depthwise conv + LayerNorm of the ConvNeXt block
     ("pfk_convnext_bwd.hip", []),             # K12d: LayerNorm / depthwise conv backward, GELU rows (training the ConvNeXt block)
     ("pfk_xcit.hip", []),                     # K14: CCMR's XCiT motion aggregator (LayerNorm rows, XCA map, local patch interaction)
+    ("pfk_msenc.hip", []),                    # K15: GroupNorm statistics / affine apply / bilinear resize of the multi-scale encoders
     ("pfk_stamp.hip", []),                    # pfk_source_hash(): compiled with -DPFK_SOURCE_HASH=<tree hash>
 ]
 # PFK_BENCH_VARIANTS=1 (tuning scripts only: scripts/conv_bench.py, scripts/conv_b16_bench.py) compiles the timing ablations and the

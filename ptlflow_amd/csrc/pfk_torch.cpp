@@ -1189,6 +1189,47 @@ void xcit_lpi2(const Tensor& u, const Tensor& gn_weight, const Tensor& gn_bias, 
            "xcit_lpi2");
 }
 
+// ---- K15: the multi-scale GroupNorm encoders (pfk_msenc.hip) ----
+int64_t groupnorm_workspace_bytes(int64_t B, int64_t HW, int64_t C) { return pfk_groupnorm_workspace_bytes((int)B, (int)HW, (int)C); }
+
+// x [B*HW, C] view, gamma / beta [C] -> scale, shift [B*C]; workspace: groupnorm_workspace_bytes(B, HW, C) bytes
+void groupnorm_stats(const Tensor& x, int64_t B, int64_t HW, int64_t group_size, const Tensor& gamma, const Tensor& beta, double eps,
+                     Tensor scale, Tensor shift, Tensor workspace) {
+  OpScope scope(x);
+  const Rows a = rows("groupnorm_stats", x, "x", F32).expect(B * HW, AtLeast{0});
+  const int64_t C = a.cols;
+  const float* gp = dense("groupnorm_stats", gamma, "gamma [C]", F32, C).f32();
+  const float* bp = dense("groupnorm_stats", beta, "beta [C]", F32, C).f32();
+  float* sc = dense("groupnorm_stats", scale, "scale [B*C]", F32, B * C).f32();
+  float* sh = dense("groupnorm_stats", shift, "shift [B*C]", F32, B * C).f32();
+  void* ws = dense("groupnorm_stats", workspace, "workspace", Raw).raw();
+  check_ok(pfk_groupnorm_stats_f32(a.f32(), a.ld, (int)B, (int)HW, (int)C, (int)group_size, gp, bp, (float)eps, sc, sh, ws,
+                                   (long long)workspace.nbytes(), cur_stream()), "groupnorm_stats");
+}
+
+void affine_apply(const Tensor& x, const Tensor& scale, const Tensor& shift, const c10::optional<Tensor>& residual, Tensor out, int64_t B,
+                  int64_t HW, bool relu, bool relu_after_residual) {
+  OpScope scope(x);
+  const Rows a = rows("affine_apply", x, "x", F32).expect(B * HW, AtLeast{0});
+  const int64_t C = a.cols;
+  const Rows o = rows("affine_apply", out, "out", F32).expect(B * HW, C);
+  const float* sc = dense("affine_apply", scale, "scale [B*C]", F32, B * C).f32();
+  const float* sh = dense("affine_apply", shift, "shift [B*C]", F32, B * C).f32();
+  Rows r;
+  if (residual.has_value()) r = rows("affine_apply", *residual, "residual", F32).expect(B * HW, C);
+  check_ok(pfk_affine_apply_f32(a.f32(), a.ld, sc, sh, r.f32(), r.ld, o.f32(), o.ld, (int)B, (int)HW, (int)C, relu, relu_after_residual,
+                                cur_stream()), "affine_apply");
+}
+
+// inp [B*Hi*Wi, C] view -> out [B*Ho*Wo, C] view
+void resize_bilinear_pm(const Tensor& in, Tensor out, int64_t B, int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo) {
+  OpScope scope(in);
+  const Rows i = rows("resize_bilinear_pm", in, "inp", F32).expect(B * Hi * Wi, AtLeast{0});
+  const Rows o = rows("resize_bilinear_pm", out, "out", F32).expect(B * Ho * Wo, i.cols);
+  check_ok(pfk_resize_bilinear_pm_f32(i.f32(), i.ld, o.f32(), o.ld, (int)B, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)i.cols, cur_stream()),
+           "resize_bilinear_pm");
+}
+
 int64_t abi_version() { return pfk_abi_version(); }
 int64_t conv_workspace_bytes() { return pfk_conv_workspace_bytes(); }
 int64_t conv_workspace_fault_offset() { return pfk_conv_workspace_fault_offset(); }
@@ -1314,6 +1355,12 @@ TORCH_LIBRARY(pfk, m) {
   m.def("xcit_lpi2(Tensor u, Tensor gn_weight, Tensor gn_bias, float gn_eps, int groups, Tensor dw_weight, Tensor dw_bias, Tensor gamma, "
         "Tensor x, Tensor(a!) x2, Tensor? ln_weight, Tensor? ln_bias, float ln_eps, Tensor(b!) t, Tensor(c!) workspace, int B, int H, "
         "int W) -> ()");
+  m.def("groupnorm_workspace_bytes(int B, int HW, int C) -> int", &groupnorm_workspace_bytes);
+  m.def("groupnorm_stats(Tensor x, int B, int HW, int group_size, Tensor gamma, Tensor beta, float eps, Tensor(a!) scale, "
+        "Tensor(b!) shift, Tensor(c!) workspace) -> ()");
+  m.def("affine_apply(Tensor x, Tensor scale, Tensor shift, Tensor? residual, Tensor(a!) out, int B, int HW, bool relu, "
+        "bool relu_after_residual) -> ()");
+  m.def("resize_bilinear_pm(Tensor inp, Tensor(a!) out, int B, int Hi, int Wi, int Ho, int Wo) -> ()");
   m.def("nchw_to_pm(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_nchw(Tensor inp, Tensor(a!) out) -> ()");
   m.def("pm_to_cm(Tensor inp, Tensor(a!) out) -> ()");
@@ -1368,6 +1415,9 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("xca_map", &xca_map);
   m.impl("xcit_lpi1", &xcit_lpi1);
   m.impl("xcit_lpi2", &xcit_lpi2);
+  m.impl("groupnorm_stats", &groupnorm_stats);
+  m.impl("affine_apply", &affine_apply);
+  m.impl("resize_bilinear_pm", &resize_bilinear_pm);
   m.impl("nchw_to_pm", &nchw_to_pm);
   m.impl("pm_to_nchw", &pm_to_nchw);
   m.impl("pm_to_cm", &pm_to_cm);

@@ -4,8 +4,9 @@ Reference: ptlflow/models/raft/extractor.py:122-194 (``BasicEncoder``: 7x7/2 ste
 1/2, 1/4, 1/8 resolution, 1x1 output conv; ``norm_fn`` = ``instance`` for fnet, ``batch`` for cnet; gma/ and the other
 RAFT descendants reuse it) and :197-267 (``SmallEncoder`` of raft_small: the same skeleton at widths 32/64/96 with
 ``BottleneckBlock``s — 1x1 -> 3x3 (stride) -> 1x1, :62-119).  ``EncoderEngine`` is the one engine body of these and of SEA-RAFT's
-ResNetFPN (sea_encoder.py): pack loop, Winograd rule, block and forward are written once; an encoder is its block table, its
-state_dict names, its stem launch and its module's ``WINO_MIN_PIXELS``.  Activations stay pixel-major ``[B*H*W, C]`` between kernels:
+ResNetFPN (sea_encoder.py) and, subclassed, of the multi-scale GroupNorm encoders (ms_encoder.py): pack loop, Winograd rule, block
+and forward are written once; an encoder is its block table, its state_dict names, its stem launch and its module's
+``WINO_MIN_PIXELS``.  Activations stay pixel-major ``[B*H*W, C]`` between kernels:
 
 * stem                     -> ``pfk_conv_stem_f32`` (reads the NCHW image)
 * 3x3 / 1x1, stride 1 / 2  -> ``pfk_conv2d_f32`` or ``pfk_conv2d_bf16s`` (implicit GEMM; bias, relu, residual add and the
@@ -66,6 +67,9 @@ class EncoderEngine:
     What differs between BasicEncoder, SmallEncoder and SEA-RAFT's ResNetFPN (sea_encoder.py) is data: the block table, the state_dict
     names, the stem's input channels and the Winograd threshold table — the module's own dict object, read at call time."""
 
+    NORMS = ("instance", "batch", "none")      # the `norm_fn`s this engine body implements (ms_encoder.py: "group")
+    widest_row = 128      # floats of the widest activation row at half resolution (32 for the small encoder; same bound)
+
     def __init__(self, params: Dict[str, torch.Tensor], norm: str, device: torch.device, conv_precision: str = "fp32",
                  small: bool = False, *, blocks=None, names=None, input_dim: int = 3, wino_min_pixels: Optional[Dict[int, int]] = None):
         load_native()
@@ -74,7 +78,7 @@ class EncoderEngine:
         self.names = names if names is not None else (_SMALL_NAMES if small else _NAMES)
         self.input_dim = input_dim
         self.wino_min_pixels = WINO_MIN_PIXELS if wino_min_pixels is None else wino_min_pixels
-        if norm not in ("instance", "batch", "none"):
+        if norm not in self.NORMS:
             raise ValueError(norm)
         # "bf16": K8b (`pfk_conv2d_b16`, UpdateEngine's docstring) — bf16 activation storage between the layers, instance norms
         # included (statistics and normalisation in fp32 arithmetic on the bf16 rows, as F.instance_norm under autocast)
@@ -107,9 +111,13 @@ class EncoderEngine:
         fp32 engine of a non-small encoder, square and of a width in the threshold table, also the transformed weight of the Winograd
         kernels `_use_wino` may select"""
         cin = w.shape[1]
-        W[key + ".w"], W[key + ".b"] = self.path.pack(w, [(0, cin, cin)]), b
+        W[key + ".w"], W[key + ".b"] = self.path.pack(w, self._segments(key, cin)), b
         if wino and self.path.fp32_tiles and not self.small and cin == w.shape[0] and cin in self.wino_min_pixels:
             W[key + ".ww"] = pack_wino_weight(w.cpu()).to(self.device)
+
+    def _segments(self, key: str, cin: int):
+        """the sources of the convolution under `key`, as `packing.pack_conv_weight` takes them: one buffer of `cin` channels"""
+        return [(0, cin, cin)]
 
     def pack(self, P: Dict[str, torch.Tensor]) -> None:
         W: Dict[str, torch.Tensor] = {}
@@ -263,8 +271,8 @@ class EncoderEngine:
 
     def _max_batch(self, H1: int, W1: int) -> int:
         """images per pass that keep every activation matrix under `max_matrix_bytes` (32-bit byte offsets in the conv kernels); the
-        widest activation row: 128 floats at half resolution (32 for the small encoder; same bound)"""
-        return max(1, self.max_matrix_bytes // (H1 * W1 * 128 * 4))
+        widest activation row: `widest_row` floats at half resolution"""
+        return max(1, self.max_matrix_bytes // (H1 * W1 * self.widest_row * 4))
 
     def _stem(self, img: torch.Tensor, x: torch.Tensor) -> None:
         self.ops.conv_stem(img, self.w["stem.w"], self.w["stem.b"], x, self.norm != "instance")

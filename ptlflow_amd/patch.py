@@ -43,6 +43,8 @@ from ._seam import ProbedMethodSeam, WrappedModule, carries_grad, eligible, pixe
 from .conv_path import PRECISIONS, check_precision
 from .corr import get_corr_block as _pfk_get_corr_block
 from .encoder import PfkEncoder
+from .ms_encoder import _MS_CLASSES, PfkMultiScaleEncoder, describe_multiscale_encoder, served as _ms_encoder_served
+from .ms_encoder import register_multiscale_encoder  # noqa: F401  (next to the other register_* hooks)
 from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
 from .sea_update import HEAD_SHAPES, PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam, sea_block_shapes
 from .update import PfkUpdateBlock, UpdateSpec, basic_spec, ccmr_spec, gma_spec, ms_raft_plus_spec, small_spec
@@ -606,7 +608,8 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
-               sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False) -> torch.nn.Module:
+               sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False,
+               multiscale_encoders: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -661,7 +664,13 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     own rows.  It serves eval-mode calls outside grad mode and autocast on fp32 GPU tensors with ``conv_precision="fp32"``, and only
     when every aggregator is a served class (`register_xcit_aggregator`) that passes `xcit.match_xcit_aggregator`; every other call
     runs the modules as before.  Served calls are counted in ``update_block.aggregator_calls``.  A second call with another value
-    switches the path."""
+    switches the path.
+    ``multiscale_encoders`` (default False): on a CCMR, CCMR+ or MS-RAFT+ model, replace the multi-scale GroupNorm encoders `fnet` /
+    `cnet` (ccmr/extractor.py, ms_raft_plus/extractor.py) by the kernels of ms_encoder.py: GroupNorm, the bilinear
+    resize and the concatenating convolutions of the bottom-up path on pixel-major rows.  Installed on an encoder only when it is a
+    served class (`register_multiscale_encoder`) that `ms_encoder.describe_multiscale_encoder` accepts.  The wrapper serves eval-mode
+    calls outside grad mode and autocast on fp32 GPU tensors with fp32 parameters (``engine_calls``); every other call runs the
+    reference module (``fallback_calls``).  ``conv_precision`` is not read.  A second call with another value switches the path."""
     check_precision(train_precision, PRECISIONS, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
@@ -714,6 +723,14 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
             enc = getattr(model, attr, None)
             if enc is not None and not isinstance(enc, PfkEncoder) and match_encoder(enc):
                 setattr(model, attr, PfkEncoder(enc, conv_precision, small=type(enc).__name__ == "SmallEncoder"))
+    for attr in ("fnet", "cnet"):
+        enc = getattr(model, attr, None)
+        if isinstance(enc, PfkMultiScaleEncoder) and not multiscale_encoders:
+            setattr(model, attr, enc._ref[0])
+        elif multiscale_encoders and isinstance(enc, torch.nn.Module) and _ms_encoder_served(enc):
+            desc = describe_multiscale_encoder(enc)
+            if desc is not None:
+                setattr(model, attr, PfkMultiScaleEncoder(enc, desc, _MS_CLASSES[(type(enc).__module__, type(enc).__name__)]))
     if upsample and callable(getattr(model, "upsample_flow", None)) and not isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam):
         _shadow(model, upsample_flow=_UpsampleSeam(model.upsample_flow))
     both = isinstance(getattr(model, "update_block", None), PfkUpdateBlock) and isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam)
