@@ -28,6 +28,7 @@
  *   pfk_flow_delta_f32    ptlflow/models/raft/update.py:10,14 (FlowHead.conv2) fused with
  *                         ptlflow/models/raft/raft.py:174,178 (flow = coords1-coords0; coords1 += d)
  *   pfk_convex_upsample_f32  ptlflow/models/raft/raft.py:112-123 RAFT.upsample_flow
+ *   pfk_convex_upsample2_f32  ptlflow/models/ccmr/ccmr.py:128-139 CCMR.upsample_flow(scale=2) (ms_raft_plus.py:133-144 likewise)
  *   pfk_dwconv_layernorm_f32  ptlflow/models/sea_raft/layer.py:54-58,71-75 (ConvNextBlock dwconv + norm)
  *   pfk_convex_upsample_info_pm_f32  ptlflow/models/sea_raft/sea_raft.py:147-163 SEARAFT.upsample_data
  *   pfk_dwconv_layernorm_b16 / pfk_conv2d_gelu_b16 / pfk_convex_upsample_info_pm_b16  the same on the bf16 (K8b) path
@@ -473,6 +474,15 @@ int pfk_flow_from_coords_f32(const float* coords0, const float* coords1, float* 
  * (already multiplied by 0.25); out [B][2][8h][8w] NCHW. */
 int pfk_convex_upsample_f32(const float* flow, const float* mask, int mask_ld, float* out,
                             int B, int H, int W, pfk_stream_t stream);
+/* `upsample_flow(flow, mask, scale=2)` of the multi-scale families (ccmr/ccmr.py:128-139, ms_raft_plus/ms_raft_plus.py:133-144):
+ * softmax over the 9 taps, convex combination of the zero-padded 3x3 neighbourhood of 2*flow, pixel-shuffle to 2x resolution.
+ * flow NCHW [B][2][H][W] (flow_ld == 0) or pixel-major rows flow[p*flow_ld + 0..1] (flow_ld >= 2); mask pixel-major fp32 logits
+ * [M][mask_ld], mask_ld >= 36, channel c = k*4 + sy*2 + sx (the update block's 0.25 already applied); out [B][2][2H][2W] NCHW.
+ * No alignment is required beyond the elements' own: 8-byte aligned mask and out with an even mask_ld take 8-byte accesses,
+ * anything else 4-byte ones, with the same bits.  PFK_ERR_BAD_ARG: a null pointer, a non-positive size, mask_ld < 36, flow_ld == 1
+ * or negative; PFK_ERR_UNSUPPORTED: more pixels than a launch grid holds.  (Added within ABI 7: an addition only.) */
+int pfk_convex_upsample2_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, float* out,
+                             int B, int H, int W, pfk_stream_t stream);
 /* upflow8 (raft/utils.py:94-96, the mask-less upsampling of raft_small): out [B][2][8H][8W] = 8 * bilinear(coords1 - coords0,
  * size 8x, align_corners = True); coords NCHW [B][2][H][W].  Index / weight arithmetic as torch's upsample_bilinear2d. */
 int pfk_upflow8_f32(const float* coords0, const float* coords1, float* out, int B, int H, int W, pfk_stream_t stream);

@@ -104,6 +104,13 @@ class ProbedMethodSeam:
         """the context the method runs in during the probe"""
         return contextlib.nullcontext()
 
+    def _probe_pair(self, *key):
+        return self.original, self._kernel
+
+    def _refusal(self, *key):
+        """the warning of a failed probe"""
+        return self.refusal
+
     def _verdict(self, attr: str, device, *key) -> bool:
         """the probe's verdict cached in `attr`, probing on first use (`key`: what `_probe_args` varies on)"""
         ok = getattr(self, attr)
@@ -116,12 +123,14 @@ class ProbedMethodSeam:
 
     def _probe(self, device, *key) -> bool:
         """`_probe_args(device, *key)` -> (the method's arguments, the kernel's); True when their outputs agree in shape and to
-        1e-5 of the largest magnitude"""
+        1e-5 of the largest magnitude.  `_probe_pair(*key)` names the two sides: (`original`, `_kernel`) unless a seam that serves
+        more than one form of the call says otherwise."""
         want_args, got_args = self._probe_args(device, *key)
         try:
+            original, kernel = self._probe_pair(*key)
             with torch.no_grad(), self._probe_context():
-                want = self.original(*want_args)
-            got = self._kernel(*got_args)
+                want = original(*want_args)
+            got = kernel(*got_args)
             if torch.is_tensor(got):
                 want, got = (want,), (got,)
             ok = len(want) == len(got) and all(
@@ -130,5 +139,5 @@ class ProbedMethodSeam:
         except Exception:
             ok = False
         if not ok:
-            warnings.warn(self.refusal, RuntimeWarning, stacklevel=4)
+            warnings.warn(self._refusal(*key), RuntimeWarning, stacklevel=4)
         return ok

@@ -458,6 +458,27 @@ void convex_upsample_pm(const Tensor& flow_pm, const Tensor& mask, Tensor out) {
   check_ok(pfk_convex_upsample_pm_f32(f.f32(), f.ld, m.f32(), m.ld, o.ptr, o.B, o.H, o.W, cur_stream()), "convex_upsample_pm");
 }
 
+// `upsample_flow(flow, mask, scale=2)` (ccmr/ccmr.py:128-139): flow NCHW [B, 2, H, W] contiguous (convex_upsample2) or pixel-major
+// [M, >=2] rows (convex_upsample2_pm), mask [M, 36] fp32 rows, out [B, 2, 2H, 2W]
+void convex_upsample2_impl(const char* op, bool pm, const Tensor& flow, const Tensor& mask, const Tensor& out) {
+  OpScope scope(flow);
+  const Up8 o = up8(op, out, "out", 2);
+  const Rows m = rows(op, mask, "mask", F32).expect(o.rows(), 36);
+  const float* fp;
+  int flow_ld = 0;
+  if (pm) {
+    const Rows f = rows(op, flow, "flow_pm", F32).expect(o.rows(), AtLeast{2});
+    fp = f.f32(); flow_ld = (int)f.ld;
+  } else {
+    fp = dense(op, flow, "flow", F32, 2 * o.rows()).f32();
+    TORCH_CHECK(flow.dim() == 4 && flow.size(0) == o.B && flow.size(1) == 2 && flow.size(2) == o.H && flow.size(3) == o.W, op,
+                ": flow [B, 2, H, W] contiguous, out [B, 2, 2H, 2W]");
+  }
+  check_ok(pfk_convex_upsample2_f32(fp, flow_ld, m.f32(), m.ld, o.ptr, o.B, o.H, o.W, cur_stream()), op);
+}
+void convex_upsample2(const Tensor& flow, const Tensor& mask, Tensor out) { convex_upsample2_impl("convex_upsample2", false, flow, mask, out); }
+void convex_upsample2_pm(const Tensor& flow_pm, const Tensor& mask, Tensor out) { convex_upsample2_impl("convex_upsample2_pm", true, flow_pm, mask, out); }
+
 // SEARAFT.upsample_data: flow_pm [M, >=2] / info_pm [M, >=n] / mask [M, 576] views, flow_out [B, 2, 8H, 8W], info_out [B, n, 8H, 8W];
 // the mask fp32 (convex_upsample_info_pm) or bf16 (convex_upsample_info_pm_b16)
 void convex_upsample_info_pm_impl(const char* op, Elem mask_elem, const Tensor& flow_pm, const Tensor& info_pm, const Tensor& mask,
@@ -1316,6 +1337,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("flow_from_coords(Tensor coords0, Tensor coords1, Tensor(a!) flow_out) -> ()");
   m.def("convex_upsample(Tensor flow, Tensor mask, Tensor(a!) out) -> ()");
   m.def("convex_upsample_pm(Tensor flow_pm, Tensor mask, Tensor(a!) out) -> ()");
+  m.def("convex_upsample2(Tensor flow, Tensor mask, Tensor(a!) out) -> ()");
+  m.def("convex_upsample2_pm(Tensor flow_pm, Tensor mask, Tensor(a!) out) -> ()");
   m.def("convex_upsample_info_pm(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor(a!) flow_out, Tensor(b!) info_out) -> ()");
   m.def("dwconv_layernorm(Tensor inp, Tensor dw_weight, Tensor? dw_bias, Tensor ln_weight, Tensor ln_bias, float eps, Tensor(a!) out, "
         "int B, int H, int W, int k) -> ()");
@@ -1388,6 +1411,8 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("flow_from_coords", &flow_from_coords);
   m.impl("convex_upsample", &convex_upsample);
   m.impl("convex_upsample_pm", &convex_upsample_pm);
+  m.impl("convex_upsample2", &convex_upsample2);
+  m.impl("convex_upsample2_pm", &convex_upsample2_pm);
   m.impl("mask_upsample", &mask_upsample);
   m.impl("convex_upsample_info_pm", &convex_upsample_info_pm);
   m.impl("dwconv_layernorm", &dwconv_layernorm);

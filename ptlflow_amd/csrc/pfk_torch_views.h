@@ -119,16 +119,17 @@ void fill_sources(Desc& d, at::TensorList srcs, int64_t n_rows, Elem e, const ch
 // output rows of a strided convolution (padding k/2): B * Ho * Wo
 int64_t out_rows(int64_t B, int64_t H, int64_t W, int64_t stride) { return B * ((H - 1) / stride + 1) * ((W - 1) / stride + 1); }
 
-// B, H, W of the 1/8-resolution grid, taken from a contiguous float32 [B, 2, 8H, 8W] tensor
+// B, H, W of the 1/8-resolution grid, taken from a contiguous float32 [B, 2, 8H, 8W] tensor (`scale`: of the 1/scale grid)
 struct Up8 {
   int B = 0, H = 0, W = 0;
   float* ptr = nullptr;
   int64_t rows() const { return (int64_t)B * H * W; }
 };
-Up8 up8(const char* op, const Tensor& t, const char* name) {
+Up8 up8(const char* op, const Tensor& t, const char* name, int scale = 8) {
   const Ptr p = dense(op, t, name, F32);
-  TORCH_CHECK(t.dim() == 4 && t.size(1) == 2 && t.size(2) % 8 == 0 && t.size(3) % 8 == 0, op, ": ", name, " must be [B, 2, 8H, 8W] contiguous");
-  return {(int)t.size(0), (int)(t.size(2) / 8), (int)(t.size(3) / 8), p.f32()};
+  TORCH_CHECK(t.dim() == 4 && t.size(1) == 2 && t.size(2) % scale == 0 && t.size(3) % scale == 0, op, ": ", name, " must be [B, 2, ", scale,
+              "H, ", scale, "W] contiguous");
+  return {(int)t.size(0), (int)(t.size(2) / scale), (int)(t.size(3) / scale), p.f32()};
 }
 
 // scratch from the caching allocator on `like`'s device: the tensor that owns it and its pointer (null when need == 0)

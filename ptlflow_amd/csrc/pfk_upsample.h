@@ -1,7 +1,9 @@
 // Convex upsampling — RAFT.upsample_flow (raft/raft.py:112-123) and SEARAFT.upsample_data (sea_raft.py:147-163) — the arithmetic of
 // one (coarse pixel, sub-pixel), written ONCE: softmax over the nine mask logits, then the convex combination of the zero-padded 3x3
-// neighbourhood of 8 x flow (and of the info channels, no factor).  Every kernel that upsamples or differentiates the upsampling
-// calls these helpers: the unfused forward and the two backward kernels (pfk_upsample.hip), the fused mask-head kernels K13
+// neighbourhood of S x flow (and of the info channels, no factor).  S is the upsampling factor, a template argument of the geometry
+// helpers that defaults to RAFT's 8; CCMR / MS-RAFT+ upsample by 2 (ccmr/ccmr.py:128-139, `scale=2`: 9 * 4 = 36 mask channels).
+// Every kernel that upsamples or differentiates the upsampling
+// calls these helpers: the unfused forwards and the two backward kernels (pfk_upsample.hip), the fused mask-head kernels K13
 // (pfk_gemm.hip) and K13b (pfk_gemm_b16.hip).  That is what makes their promises hold — fused = unfused, four pixels per wave = one
 // pixel per wave, the info kernel's flow = the plain kernel's, the training node's forward = the inference kernel — bit for bit
 // (tests/test_gpu_upsample_bits.py holds the bits themselves).
@@ -59,16 +61,17 @@ __device__ __forceinline__ UpPixel up_pixel(long long p, int H, int W) {
   return {b, y, pix - y * W};
 }
 
-// sub-pixel (sy, sx) of coarse pixel (y, x) inside one [8H][8W] plane
+// sub-pixel (sy, sx) of coarse pixel (y, x) inside one [S H][S W] plane
+template <int S = 8>
 __device__ __forceinline__ long long up_out_offset(int y, int x, int sy, int sx, int W) {
-  return (long long)(8 * y + sy) * (8 * W) + 8 * x + sx;
+  return (long long)(S * y + sy) * (S * W) + S * x + sx;
 }
 
-// Neighbour k = 3 (dy + 1) + (dx + 1) of pixel (y, x) of the image whose first pixel has index img = b * H * W: v[0..1] = 8 x flow
+// Neighbour k = 3 (dy + 1) + (dx + 1) of pixel (y, x) of the image whose first pixel has index img = b * H * W: v[0..1] = S x flow
 // (exact: a power of two), v[2 + i] = info channel i < n_info; zero outside the image (F.unfold's padding).  Flow NCHW (flow_ld == 0)
 // or pixel-major rows (flow_ld >= 2); info rows.  One tap per call; the caller makes the product img once for the nine taps, and the
 // two flow layouts differ in the addresses only, so the two loads of a tap issue together.
-template <int NI>
+template <int NI, int S = 8>
 __device__ __forceinline__ void up_tap(int k, const float* __restrict__ flow, int flow_ld, const float* __restrict__ info, int info_ld,
                                        int n_info, long long img, int y, int x, int H, int W, float (&v)[2 + NI]) {
   const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
@@ -78,8 +81,8 @@ __device__ __forceinline__ void up_tap(int k, const float* __restrict__ flow, in
     const long long q = img + (long long)yy * W + xx;
     const float* fx = flow_ld > 0 ? flow + q * flow_ld : flow + q + img;
     const float* fy = flow_ld > 0 ? fx + 1 : fx + (long long)H * W;
-    v[0] = 8.0f * *fx;
-    v[1] = 8.0f * *fy;
+    v[0] = (float)S * *fx;
+    v[1] = (float)S * *fy;
     if (NI > 0) {
       const float* fi = info + q * info_ld;
 #pragma unroll

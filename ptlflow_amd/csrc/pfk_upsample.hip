@@ -74,6 +74,64 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Forward by 2: `upsample_flow(flow, mask, scale=2)` of ccmr/ccmr.py:128-139 / ms_raft_plus/ms_raft_plus.py:133-144.  36 mask logits
+// per coarse pixel, channel c = k * 4 + sy * 2 + sx; out [B][2][2H][2W].  The 8x layout gives a wave the 64 sub-pixels of a pixel;
+// here a pixel has four, so a lane owns one (coarse pixel, sy): the sub-pixels sx = 0, 1 of nine taps are nine 8-byte pieces of the
+// pixel's 144-byte mask row, and the two results of a channel are one 8-byte store.  A wave holds 32 consecutive pixels, lanes
+// 0..31 the upper output row (sy = 0) and lanes 32..63 the lower: each half wave writes 256 contiguous bytes per channel, and the
+// nine reads of the wave together cover the pixels' mask rows exactly once (32 x 144 contiguous bytes where mask_ld == 36).
+// VEC: mask rows and output 8-byte aligned (mask_ld even); otherwise the same lanes use 4-byte accesses.  Same arithmetic
+// (up_softmax9 + up_combine on up_tap<0, 2>) either way: same bits.
+// ------------------------------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void convex_upsample2_kernel(const float* __restrict__ flow, int flow_ld,
+                                                               const float* __restrict__ mask, int mask_ld, float* __restrict__ out,
+                                                               long long M, int H, int W) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // blockDim.x is a multiple of 64
+  const int lane = threadIdx.x & 63, sy = lane >> 5;
+  const long long p = (t >> 6) * 32 + (lane & 31);
+  if (p >= M) return;
+  const UpPixel px = up_pixel(p, H, W);
+  const long long img = px.b * ((long long)H * W);
+  const float* mrow = mask + p * mask_ld + sy * 2;
+  float m[2][9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    if constexpr (VEC) {
+      const f32x2 w = *reinterpret_cast<const f32x2*>(mrow + k * 4);
+      m[0][k] = w[0];
+      m[1][k] = w[1];
+    } else {
+      m[0][k] = mrow[k * 4];
+      m[1][k] = mrow[k * 4 + 1];
+    }
+  }
+  float v[2][9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    float f[2];
+    up_tap<0, 2>(k, flow, flow_ld, nullptr, 0, 0, img, px.y, px.x, H, W, f);
+    v[0][k] = f[0];
+    v[1][k] = f[1];
+  }
+  up_softmax9(m[0]);
+  up_softmax9(m[1]);
+  const long long HW4 = (long long)H * W * 4;
+  const long long at = up_out_offset<2>(px.y, px.x, sy, 0, W);
+#pragma unroll
+  for (int ch = 0; ch < 2; ++ch) {
+    const float o0 = up_combine(m[0], v[ch]), o1 = up_combine(m[1], v[ch]);
+    float* dst = out + (px.b * 2 + ch) * HW4 + at;
+    if constexpr (VEC) {
+      *reinterpret_cast<f32x2*>(dst) = f32x2{o0, o1};
+    } else {
+      dst[0] = o0;
+      dst[1] = o1;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Backward of upsample_flow.  Forward, per coarse pixel p and sub-pixel (sy, sx) = lane:
 //     w_k = softmax_k(mask[p][k*64 + lane]),   out[c][8y+sy][8x+sx] = sum_k w_k * 8 * flow[c][nbr_k(p)]   (zero outside)
 // One wave per coarse pixel, lane = sub-pixel (as the forward's V = 1):
@@ -238,12 +296,14 @@ __global__ __launch_bounds__(256) void convex_upsample_bwd_gather_kernel(const f
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
-// What all nine entry points check first: the pointers every one of them needs, the grid, the mask row stride and the flow layout
-// (pixel-major rows of at least two floats; 0 = NCHW where the entry point reads it).
-bool up_args_ok(std::initializer_list<const void*> required, int B, int H, int W, int mask_ld, int flow_ld, bool nchw_ok = false) {
+// What all ten entry points check first: the pointers every one of them needs, the grid, the mask row stride (at least the
+// `mask_channels` = 9 S^2 logits of a pixel) and the flow layout (pixel-major rows of at least two floats; 0 = NCHW where the entry
+// point reads it).
+bool up_args_ok(std::initializer_list<const void*> required, int B, int H, int W, int mask_ld, int flow_ld, bool nchw_ok = false,
+                int mask_channels = 576) {
   for (const void* ptr : required)
     if (!ptr) return false;
-  return B > 0 && H > 0 && W > 0 && mask_ld >= 576 && (flow_ld >= 2 || (nchw_ok && flow_ld == 0));
+  return B > 0 && H > 0 && W > 0 && mask_ld >= mask_channels && (flow_ld >= 2 || (nchw_ok && flow_ld == 0));
 }
 
 // blocks of `per_block` items; false where the count does not fit a grid dimension
@@ -317,6 +377,18 @@ int pfk_convex_upsample_info_pm_b16(const float* flow_pm, int flow_ld, const flo
                                     pfk_stream_t stream) {
   return convex_upsample_info<__bf16>(flow_pm, flow_ld, info_pm, info_ld, n_info, static_cast<const __bf16*>(mask_bf16), mask_ld, flow_out,
                                       info_out, B, H, W, stream);
+}
+
+int pfk_convex_upsample2_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, float* out, int B, int H, int W,
+                             pfk_stream_t stream) {
+  if (!up_args_ok({flow, mask, out}, B, H, W, mask_ld, flow_ld, true, 36)) return PFK_ERR_BAD_ARG;
+  const long long M = (long long)B * H * W;
+  unsigned blocks;
+  if (!up_grid(M, 32, blocks)) return PFK_ERR_UNSUPPORTED;      // one wave of 32 pixels per block: these grids are a few thousand pixels
+  const bool vec = pfk_aligned<8>(mask) && pfk_aligned<8>(out) && (mask_ld & 1) == 0;
+  hipLaunchKernelGGL(vec ? convex_upsample2_kernel<true> : convex_upsample2_kernel<false>, dim3(blocks), dim3(64), 0,
+                     static_cast<hipStream_t>(stream), flow, flow_ld, mask, mask_ld, out, M, H, W);
+  return pfk_launch_status();
 }
 
 long long pfk_convex_upsample_bwd_workspace_bytes(int B, int H, int W) {

@@ -209,9 +209,12 @@ def _with_corr_channels(spec: UpdateSpec, corr_channels: int) -> UpdateSpec:
     return replace(spec, corr_channels=corr_channels)
 
 
-def register_update_block(module: str, cls: str, factory: Callable[[int], UpdateSpec]) -> None:
-    """Declare another family's update block to be one of the three implementations above (shape check still applies)."""
+def register_update_block(module: str, cls: str, factory: Callable[[int], UpdateSpec], foreign_prefix: Optional[str] = None) -> None:
+    """Declare another family's update block to be one of the three implementations above (shape check still applies).
+    `foreign_prefix`: parameters under it belong to a sub-module the wrapper keeps calling as is (CCMR's `aggregator.`)."""
     _UPDATE_BLOCKS[(module, cls)] = factory
+    if foreign_prefix:
+        _FOREIGN_PREFIX[(module, cls)] = foreign_prefix
 
 
 def register_encoder(module: str, cls: str = "BasicEncoder") -> None:
@@ -367,7 +370,13 @@ class _UpsampleSeam(ProbedMethodSeam):
     neighbourhood — keeps its own code).  CPU tensors, other mask widths and dtypes always take the original; so do gradient
     graphs, unless `train_upsample` is set (`accelerate(model, train_upsample=True)`): then the plain call on two CUDA fp32 tensors
     with grad mode on, something requiring grad and no autocast runs `train.convex_upsample` (`pfk_convex_upsample_f32` forward,
-    `pfk_convex_upsample_bwd_f32` backward) and is counted in `train_calls`.  The dead-work skip is never active in grad mode."""
+    `pfk_convex_upsample_bwd_f32` backward) and is counted in `train_calls`.  The dead-work skip is never active in grad mode.
+
+    `multiscale` (`accelerate(model, multiscale_upsample=True)`): the seam also serves `upsample_flow(flow, mask, scale=2)` /
+    `(flow, mask, 2)` of the multi-scale families (ccmr/ccmr.py:196,213, ms_raft_plus/ms_raft_plus.py:199,209) with
+    `pfk_convex_upsample2_f32` — CUDA fp32 tensors, a 36-channel mask, an eval-mode model, no gradient graph, no autocast, behind a
+    probe of its own (`ok2`: `original(flow, mask, scale=2)` against the kernel; separate from `ok`).  Every other scale, extra
+    arguments, CPU tensors and gradient graphs go to the model's method as before.  Served calls count in `calls`."""
 
     refusal = "ptlflow_amd: this model's upsample_flow is not RAFT's 8x convex upsampling; seam B5 keeps the model's own method"
 
@@ -376,6 +385,60 @@ class _UpsampleSeam(ProbedMethodSeam):
         self.skip = None        # `_DeadWorkSkip` shared with seam B3 (accelerate(..., skip_dead_upsample=True)), else None
         self.train_upsample = False    # `accelerate(train_upsample=True)`: gradient-graph calls run `train.convex_upsample`
         self.train_calls = 0           # calls served by it
+        self.multiscale = False        # `accelerate(multiscale_upsample=True)`: `scale=2` calls run `pfk_convex_upsample2_f32`
+        self.ok2 = None                # the x2 probe's verdict (None = not probed yet)
+
+    @staticmethod
+    def _kernel2(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        B, _, H, W = flow.shape
+        rows = pixel_rows(mask, torch.float32)      # PfkUpdateBlock's mask: a view, no copy
+        if rows is None:      # (`.contiguous()`: a plain NCHW mask of one image reshapes to a VIEW with channel stride H * W)
+            rows = mask.permute(0, 2, 3, 1).contiguous().view(B * H * W, 36)
+        out = torch.empty(B, 2, 2 * H, 2 * W, device=flow.device, dtype=torch.float32)
+        torch.ops.pfk.convex_upsample2(flow.contiguous(), rows, out)
+        return out
+
+    refusal2 = ("ptlflow_amd: this model's upsample_flow(flow, mask, scale=2) is not the x2 convex upsampling of the multi-scale "
+                "families; seam B5 keeps the model's own method for scale=2 calls")
+
+    def _refusal(self, *key):
+        return self.refusal2 if key == (2,) else self.refusal
+
+    def _probe_pair(self, *key):
+        if key == (2,):
+            return (lambda flow, mask: self.original(flow, mask, scale=2)), self._kernel2
+        return super()._probe_pair(*key)
+
+    @staticmethod
+    def _scale2_call(args, kwargs):
+        """(flow, mask) of a call shaped `(flow, mask, scale=2)` or `(flow, mask, 2)`, else None"""
+        if len(args) == 3 and not kwargs:
+            scale = args[2]
+        elif len(args) == 2 and set(kwargs) == {"scale"}:
+            scale = kwargs["scale"]
+        else:
+            return None
+        if type(scale) is not int or scale != 2 or not (torch.is_tensor(args[0]) and torch.is_tensor(args[1])):
+            return None
+        return args[0], args[1]
+
+    def _serve2(self, flow: torch.Tensor, mask: torch.Tensor):
+        """the x2 upsampling of a served call, or None: the call is the model's own method's"""
+        skip = self.skip if isinstance(self.skip, _MultiScaleSkip) else None
+        if skip is not None and skip.upsample_is_dead():
+            # the block call before this one left its mask out: the answer never falls through to `original` on that stale view
+            if skip.first_upsample_since_block() and not torch.is_grad_enabled():
+                self.calls += 1
+                return skip.scratch(flow)
+            skip.recover()      # a second reader of a mask the schedule held for dead: compute it after all, skip nothing more
+        shapes = flow.dim() == 4 and flow.shape[1] == 2 and mask.dim() == 4 and mask.shape[1] == 36 \
+            and flow.shape[0] == mask.shape[0] and flow.shape[2:] == mask.shape[2:]
+        model = getattr(self.original, "__self__", None)
+        if not shapes or getattr(model, "training", False) or not eligible((flow, mask), dtypes=(torch.float32,), autocast=False) \
+                or not self._verdict("ok2", flow.device, 2):
+            return None
+        self.calls += 1
+        return self._kernel2(flow, mask)
 
     @staticmethod
     def _kernel(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -386,13 +449,18 @@ class _UpsampleSeam(ProbedMethodSeam):
         torch.ops.pfk.convex_upsample(flow.contiguous(), pm, out)
         return out
 
-    def _probe_args(self, device):
+    def _probe_args(self, device, scale: int = 8):
         g = torch.Generator().manual_seed(5)
         flow = (torch.randn(2, 2, 5, 7, generator=g) * 3).to(device)
-        mask = torch.randn(2, 576, 5, 7, generator=g).to(device)
+        mask = torch.randn(2, 9 * scale * scale, 5, 7, generator=g).to(device)
         return (flow, mask), (flow, mask)
 
     def __call__(self, *args, **kwargs):
+        if self.multiscale:
+            fm = self._scale2_call(args, kwargs)
+            out = self._serve2(*fm) if fm is not None else None
+            if out is not None:
+                return out
         # Other families give `upsample_flow` more arguments — ccmr.py:213 / ms_raft_plus.py:199 pass `scale=`, dip a `rate`,
         # rapidflow / dpflow a `factor`, gmflow (feature, bilinear, upsample_factor): anything but the plain two-tensor
         # positional call is the model's own business and goes to its own method exactly as it was written.
@@ -411,7 +479,7 @@ class _UpsampleSeam(ProbedMethodSeam):
         if not (shapes and eligible(args, dtypes=(torch.float32,)) and self._verdict("ok", flow.device)):
             return self.original(flow, mask)
         self.calls += 1
-        if self.skip is not None:
+        if isinstance(self.skip, _DeadWorkSkip):      # (a `_MultiScaleSkip` schedules the `scale=2` calls above only)
             if self.skip.upsample_is_dead():
                 return self.skip.scratch(flow)      # a non-final iteration's prediction: eval drops it (raft/raft.py:186-192)
             eng = self.skip.take_deferred(mask)
@@ -529,8 +597,8 @@ class _DeadWorkSkip:
         self._scratch = None
         self._deferred = None   # (engine, data_ptr of the mask view handed out) of a live call whose mask conv2 was left to seam B5
 
-    def begin_forward(self, fp32: bool = True) -> None:
-        """`fp32` = the state tensors of this forward are float32.  A half / bf16 model (`model.half()`, validate.py:243-244) gets
+    def begin_forward(self, fp32: bool = True, device=None, grid=None) -> None:
+        """`fp32` = the state tensors of this forward are float32 (`device`, `grid`: read by `_MultiScaleSkip` only).  A half / bf16 model (`model.half()`, validate.py:243-244) gets
         its tensors back as fresh casts, so the block cannot tell the calls of one forward apart by storage: nothing is skipped
         for it (the counter used to restart on every call and the final mask was never computed)."""
         m = self._model()
@@ -577,6 +645,203 @@ class _DeadWorkSkip:
         return self._scratch
 
 
+# (module, class) whose `forward` was checked to be a multi-scale loop of this kind (ccmr/ccmr.py:179-230,
+# ms_raft_plus/ms_raft_plus.py:183-226): scale `index` runs `self.iters[index]` block calls on a `net` made fresh per scale; every
+# block call is followed by one `self.upsample_flow(..., up_mask, scale=2)` whose result goes through `upflow2` /
+# `postprocess_predictions` into a list that eval drops (only the last `flow_up` is returned, as `flows` and `flow_small`); the first
+# iteration of a scale `index >= 1` calls `self.upsample_flow(..., up_mask, scale=2)` once more BEFORE its block call, on the previous
+# scale's last mask; `up_mask` has no other reader.  So within a scale only the last block call's mask is live.
+_MULTISCALE_LOOPS = {
+    ("ptlflow.models.ccmr.ccmr", "CCMR"),                      # CCMRPlus inherits forward and upsample_flow
+    ("ptlflow.models.ms_raft_plus.ms_raft_plus", "MSRAFTPlus"),
+}
+
+
+def register_multiscale_loop(module: str, cls: str) -> None:
+    """Declare that `module.cls.forward` (and `upsample_flow`) is a multi-scale loop of that kind — checked by whoever registers it."""
+    _MULTISCALE_LOOPS.add((module, cls))
+
+
+def _iters_list_ok(it) -> bool:
+    return isinstance(it, (list, tuple)) and len(it) > 0 and all(type(n) is int and n >= 1 for n in it)
+
+
+class _MultiScaleSkip:
+    """The dead-work skip for a per-scale iteration list (`accelerate(model, multiscale_upsample=True)`), shared by
+    seam B3 and seam B5 as `_DeadWorkSkip` is.  A forward pre-hook on the model (`start_forward`) restarts the count and re-reads
+    `model.iters`; every `begin_forward` from the block (a fresh `net`) moves to the next scale.  Within scale k the mask is live
+    on block call `iters[k] - 1` only; an `upsample_flow(scale=2)` call is dead exactly when the block call before it was.
+
+    Armed per forward, at its first block call, only when: eval mode, grad mode off, no autocast, fp32 state, `model.iters` a
+    list / tuple of positive ints (no bools), and the x2 probe's verdict is True (probed there, outside stream capture; never on
+    `ok2 is None`).  Disarmed for the rest of the forward — everything is computed — when the bookkeeping does not add up: a scale
+    that began before the previous one had exactly `iters[k]` calls, a grid that is not twice the previous scale's, more scales
+    than `len(iters)`, more calls than `iters[k]`, a block call without a pre-hook before it.  Re-armed only by the next pre-hook.
+
+    Counters, per forward: `block_calls`, `masks_skipped`, `scratch_answers`."""
+
+    skip_dead = True
+    fuse = False      # no fused mask-conv2 + upsampling form for 36 channels
+
+    def __init__(self, model: torch.nn.Module, seam: "_UpsampleSeam"):
+        import weakref
+        self._model = weakref.ref(model)
+        self._seam = weakref.ref(seam)
+        self._hook = self._end_hook = None
+        self._scratch = {}
+        self._reset()
+
+    def _reset(self) -> None:
+        self.iters = ()
+        self.armed = False
+        self._pending = False     # a pre-hook fired and the forward's first block call has not asked yet
+        self.scale = -1
+        self.call = 0             # block calls of the scale in flight
+        self._grid = None
+        self._dead_now = False
+        self._ups_since_block = 0
+        self._grad = True         # grad mode where the forward began (the block runs its kernels under no_grad: it cannot tell)
+        self.block_calls = self.masks_skipped = self.scratch_answers = 0
+
+    # ---- the model's forward pre-hook
+    def start_forward(self, module=None, args=None):
+        self._reset()
+        m = self._model()
+        it = getattr(m, "iters", None) if m is not None else None
+        if _iters_list_ok(it):
+            self.iters = tuple(it)
+        self._pending = True
+        self._grad = torch.is_grad_enabled()
+
+    def end_forward(self, module=None, args=None, output=None):
+        """the model's forward is over (or died): nothing is dead outside a forward — a direct `model.upsample_flow(..., scale=2)`
+        from user code never gets the scratch tensor"""
+        self.armed = False
+        self._pending = False
+        self._dead_now = False
+
+    def install(self, model: torch.nn.Module) -> None:
+        self._hook = model.register_forward_pre_hook(self.start_forward)
+        self._end_hook = model.register_forward_hook(self.end_forward, always_call=True)
+
+    def remove(self) -> None:
+        for h in (self._hook, self._end_hook):
+            if h is not None:
+                h.remove()
+        self._hook = self._end_hook = None
+
+    def _conditions(self) -> bool:
+        m = self._model()
+        return bool(m is not None and not m.training and not self._grad and not torch.is_autocast_enabled("cuda"))
+
+    # ---- seam B3
+    def begin_forward(self, fp32: bool = True, device=None, grid=None) -> None:
+        """a block call on a fresh `net`: the next scale begins (`grid` = its (H, W))"""
+        if self._pending:
+            self._pending = False
+            seam = self._seam()
+            self.armed = bool(fp32 and self.iters and self._conditions() and seam is not None and seam.multiscale
+                              and device is not None and seam._verdict("ok2", device, 2) is True)
+        elif self.armed:
+            g = self._grid
+            if self.call != self.iters[self.scale] or self.scale + 1 >= len(self.iters) or not fp32 \
+                    or g is None or grid is None or tuple(grid) != (2 * g[0], 2 * g[1]):
+                self.armed = False
+        self.scale += 1
+        self.call = 0
+        self._grid = tuple(grid) if grid is not None else None
+
+    def next_call(self) -> bool:
+        """per block call (after `begin_forward` on a scale's first); True when this call's mask is dead"""
+        self._pending = False       # a block call that did not begin a scale: this forward stays unarmed
+        dead = False
+        if self.armed:
+            if not self._conditions() or self.scale < 0 or self.call >= self.iters[self.scale]:
+                self.armed = False
+            else:
+                dead = self.call < self.iters[self.scale] - 1
+        self.call += 1
+        self.block_calls += 1
+        self.masks_skipped += int(dead)
+        self._dead_now = dead
+        self._ups_since_block = 0
+        return dead
+
+    def may_defer(self) -> bool:
+        return False
+
+    def defer(self, engine, mask_view) -> None:
+        pass
+
+    def take_deferred(self, mask):
+        return None
+
+    # ---- seam B5
+    def upsample_is_dead(self) -> bool:
+        return self._dead_now
+
+    def first_upsample_since_block(self) -> bool:
+        self._ups_since_block += 1
+        return self._ups_since_block == 1
+
+    def recover(self) -> None:
+        """The mask of the block call before was left out and has a reader after all (a scale that ended early): compute it from
+        the block's state, which that call left complete, and skip nothing more in this forward."""
+        m = self._model()
+        self.armed = False
+        self._dead_now = False
+        m.update_block.fill_mask()
+
+    def scratch(self, flow: torch.Tensor) -> torch.Tensor:
+        B, _, H, W = flow.shape
+        key = (B, 2, 2 * H, 2 * W, flow.device)
+        if key not in self._scratch:
+            self._scratch[key] = torch.zeros(key[:4], device=flow.device, dtype=torch.float32)
+        self.scratch_answers += 1
+        return self._scratch[key]
+
+
+def _multiscale_skip_for(model: torch.nn.Module, warn: bool = True):
+    """The multi-scale skip state, or None (with a warning saying why, when the caller asked for the skip explicitly)."""
+    import warnings
+    why = None
+    fwd, ups = _defining_class(model, "forward"), _defining_class(model, "upsample_flow")
+    it = getattr(model, "iters", None)
+    seam = model.__dict__.get("upsample_flow")
+    block = getattr(model, "update_block", None)
+    if fwd is None or (fwd.__module__, fwd.__name__) not in _MULTISCALE_LOOPS:
+        why = (f"`forward` is defined by {getattr(fwd, '__module__', '?')}.{getattr(fwd, '__name__', '?')}, not by one of the multi-scale "
+               "loops checked to return only the last prediction in eval")
+    elif ups is None or (ups.__module__, ups.__name__) not in _MULTISCALE_LOOPS:
+        why = "`upsample_flow` is overridden"
+    elif not _iters_list_ok(it):
+        why = f"`model.iters` is not a non-empty list of positive ints ({it!r})"
+    elif model.training:
+        why = "the model is in train mode (every prediction enters the loss)"
+    elif not (isinstance(block, PfkUpdateBlock) and block.spec.has_mask and block.spec.mask_channels == 36
+              and isinstance(seam, _UpsampleSeam)):
+        why = "seams B3 (an update block with a x2 mask head) and B5 are not both installed"
+    if why is not None:
+        if warn:
+            warnings.warn(f"ptlflow_amd: skip_dead_upsample refused, every iteration keeps its mask head + upsampling: {why}",
+                          RuntimeWarning, stacklevel=3)
+        return None
+    return _MultiScaleSkip(model, seam)
+
+
+def _drop_skip(model: torch.nn.Module) -> None:
+    skip = model.__dict__.pop(_SKIP, None)
+    if skip is None:
+        return
+    if isinstance(skip, _MultiScaleSkip):
+        skip.remove()
+    if isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
+        model.update_block._skip = None
+    seam = model.__dict__.get("upsample_flow")
+    if isinstance(seam, _UpsampleSeam):
+        seam.skip = None
+
+
 def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bool = True, fuse: bool = True):
     """The shared skip state, or None (with a warning saying why, when the caller asked for it explicitly) when skipping is not
     provably output-preserving for this model."""
@@ -609,7 +874,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
                sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False,
-               multiscale_encoders: bool = False) -> torch.nn.Module:
+               multiscale_encoders: bool = False, multiscale_upsample: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -670,7 +935,19 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     resize and the concatenating convolutions of the bottom-up path on pixel-major rows.  Installed on an encoder only when it is a
     served class (`register_multiscale_encoder`) that `ms_encoder.describe_multiscale_encoder` accepts.  The wrapper serves eval-mode
     calls outside grad mode and autocast on fp32 GPU tensors with fp32 parameters (``engine_calls``); every other call runs the
-    reference module (``fallback_calls``).  ``conv_precision`` is not read.  A second call with another value switches the path."""
+    reference module (``fallback_calls``).  ``conv_precision`` is not read.  A second call with another value switches the path.
+    ``multiscale_upsample`` (default False): on a CCMR, CCMR+ or MS-RAFT+ model, seam B5 also serves the loop's
+    `upsample_flow(flow, mask, scale=2)` calls with the x2 convex-upsampling kernel — CUDA fp32 tensors with a
+    36-channel mask, eval mode, no gradient graph, no autocast, after a behaviour probe of its own; every other call reaches the
+    model's method as before.  With it, ``skip_dead_upsample`` (``None`` or ``True``) extends to these models' per-scale iteration
+    lists: within scale k the mask head runs on block call ``iters[k] - 1`` only and the `upsample_flow` calls after a dead block
+    call return a scratch tensor; `flows` and `flow_small` stay bit-identical to ``skip_dead_upsample=False``.  It needs `forward`
+    and `upsample_flow` of a loop checked by reading it (`register_multiscale_loop`), ``model.iters`` a non-empty list of positive
+    ints, eval mode and both seams; ``True`` warns with the reason when it is refused.  Re-armed per forward by a forward pre-hook
+    on the model (train mode, grad mode, a bf16 model or a changed ``iters`` are honoured); any inconsistency in the loop's call
+    pattern turns it off for the rest of that forward.  The intermediate `up_mask` / `flow_up` tensors are not valid in eval while it
+    is active.  Counters: ``model.update_block._skip.block_calls / masks_skipped / scratch_answers``.  A second call with another
+    value switches it; `restore` removes the hook and the state."""
     check_precision(train_precision, PRECISIONS, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
@@ -733,8 +1010,22 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                 setattr(model, attr, PfkMultiScaleEncoder(enc, desc, _MS_CLASSES[(type(enc).__module__, type(enc).__name__)]))
     if upsample and callable(getattr(model, "upsample_flow", None)) and not isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam):
         _shadow(model, upsample_flow=_UpsampleSeam(model.upsample_flow))
+    seam5 = model.__dict__.get("upsample_flow")
+    if isinstance(seam5, _UpsampleSeam):
+        seam5.multiscale = bool(multiscale_upsample)
+    # a model of a multi-scale family (a subclass included: `_multiscale_skip_for` says why it is refused) takes the per-scale skip
+    ms_loop = bool(multiscale_upsample) and any((c.__module__, c.__name__) in _MULTISCALE_LOOPS for c in type(model).__mro__)
+    if isinstance(model.__dict__.get(_SKIP), _MultiScaleSkip) and (not ms_loop or skip_dead_upsample is False):
+        _drop_skip(model)
+    if ms_loop and _SKIP not in model.__dict__ and skip_dead_upsample is not False:
+        skip = _multiscale_skip_for(model, warn=skip_dead_upsample is True)
+        if skip is not None:
+            skip.install(model)
+            model.__dict__[_SKIP] = skip
+            model.update_block._skip = skip
+            seam5.skip = skip
     both = isinstance(getattr(model, "update_block", None), PfkUpdateBlock) and isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam)
-    if _SKIP not in model.__dict__ and (skip_dead_upsample is True or both) \
+    if not ms_loop and _SKIP not in model.__dict__ and (skip_dead_upsample is True or both) \
             and not (skip_dead_upsample is False and fuse_mask_upsample is False):
         skip = _dead_work_skip_for(model, warn=skip_dead_upsample is True, skip_dead=skip_dead_upsample is not False,
                                    fuse=fuse_mask_upsample is not False)
@@ -754,10 +1045,7 @@ def restore(model: torch.nn.Module) -> torch.nn.Module:
     if state is not None:
         for h in state["handles"]:
             h.remove()
-    if _SKIP in model.__dict__:
-        del model.__dict__[_SKIP]
-        if isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
-            model.update_block._skip = None
+    _drop_skip(model)
     _unshadow(model, _UpsampleSeam, "upsample_flow")
     mod = sys.modules.get(type(model).__module__)
     if mod is not None and hasattr(mod, _ORIG):

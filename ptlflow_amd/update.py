@@ -831,6 +831,13 @@ class PfkUpdateBlock(WrappedModule):
         slot = self._agg_slots.setdefault(int(level_index), EngineSlot())
         return slot._engine_for(eng.device, params, lambda: xcit.XcitAggregatorEngine(module, eng.device), lambda e: e.pack())
 
+    def fill_mask(self) -> None:
+        """The mask of the call before, which left it out (`want_mask=False`): fh|mask conv1 again in full on the hidden state that
+        call wrote (the flow half gets the bits it has), then mask conv2 — into the view that call handed out."""
+        with torch.no_grad():
+            self._engine.heads_conv1(True)
+            self._engine.mask_head()
+
     def _get_engine(self, device) -> UpdateEngine:
         return self._engine_for(device, self.parameters(),
                                 lambda: UpdateEngine(dict(self.named_parameters()), self.spec, device, self.conv_precision),
@@ -888,7 +895,7 @@ class PfkUpdateBlock(WrappedModule):
             ops.nchw_to_pm(net.float().contiguous(), eng.h_view)
             eng.state_changed()
             if self._skip is not None:
-                self._skip.begin_forward(fp32=net.dtype == torch.float32)
+                self._skip.begin_forward(fp32=net.dtype == torch.float32, device=net.device, grid=(H, W))
         # §8 f2: on the non-final iterations of an eval forward nobody reads the mask (patch._DeadWorkSkip)
         dead_mask = self._skip is not None and eng.spec.has_mask and self._skip.next_call()
         if new_forward or inp is not self._inp_ref or inp._version != self._inp_version:
