@@ -85,7 +85,10 @@ int pfk_debug_set_wgrad(int variant);      /* weight-gradient tile height: 0 = b
 /* ---- K1: all-pairs correlation --------------------------------------------------------------
  * out[b][i][j] = scale * sum_d f1[b][i][d] * f2[b][j][d]        (fp32 MFMA, exact fp32 products)
  * f1 [B][N1][ld1], f2 [B][N2][ld2] pixel-major, D channels used; out [B][N1][N2] row-major,
- * i.e. for source pixel i a full [h2][w2] map — the reference's [B*N,1,h2,w2] volume. */
+ * i.e. for source pixel i a full [h2][w2] map — the reference's [B*N,1,h2,w2] volume.
+ * D % 4 == 0 and ld2 == D rounded up to a multiple of 32: the rows of f2 are read as packed weight rows, all ld2 columns of them,
+ * against f1 channels that read as zero past D — so the columns [D, ld2) of f2 must hold zeros (anything finite gives the same
+ * result; a NaN or inf there poisons the row's outputs).  The columns [D, ld1) of f1 are never read. */
 int pfk_corr_volume_f32(const float* f1, int ld1, const float* f2, int ld2, float* out,
                         int B, int N1, int N2, int D, float scale, pfk_stream_t stream);
 

@@ -10,6 +10,8 @@ The fp64 op gate.  A kernel output is compared with float64 arithmetic on the CP
     has an fp32 twin;
  3. `Rows`, `flat_out` / `tail_kept`, `guarded`: NaN where an input must not be read, a sentinel where an output must not be written;
  4. a second run on fresh output buffers gives the same bits (`same_bits`, or `torch.equal` on `.flat`).
+`arm` / `ws_after` put the stream-K workspace of pfk_conv2d_f32 under the same kind of guard: partial tiles read before they are
+written are NaN, and the flag region must be zero again after every launch.
 Blocks and seams are compared with `scale_close` (`BLOCK_TOL` of each tensor's scale); 16-bit training with `within_2x_cpu_autocast`."""
 import math
 
@@ -138,11 +140,14 @@ def gates(what, got, ref, mag, k, floor=0.0, keep=None):
 
 def gates_b16(what, got, twin, ref, mag, k):
     """a bf16 output: the rounding of its fp32 twin bit for bit (in place of gate 1: the twin passed it) and gate 2 with the bf16
-    rounding on top of the fp32 bound"""
-    assert got.dtype == torch.bfloat16 and twin.dtype == torch.float32
-    same = got == twin.to(torch.bfloat16)
-    assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} values are not the bf16 rounding of the fp32 kernel's"
-    got, ref, mag = got.double().cpu(), ref.double(), mag.double()
+    rounding on top of the fp32 bound, k * 2^-24 * mag * (1 + 2^-8) + 2^-8 |ref|.  `twin=None` (a kernel without an fp32 form of the
+    same body): gate 2 alone — it implies a relative L2 of at most 2^-8 (1 + eps), so bf16 needs no threshold of its own."""
+    assert got.dtype == torch.bfloat16 and (twin is None or twin.dtype == torch.float32)
+    if twin is not None:
+        same = got == twin.to(torch.bfloat16)
+        assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} values are not the bf16 rounding of the fp32 kernel's"
+    got, ref, mag = got.detach().double().cpu(), ref.detach().double(), mag.detach().double()
+    assert got.shape == ref.shape == mag.shape, f"{what}: shapes {tuple(got.shape)} {tuple(ref.shape)} {tuple(mag.shape)}"
     assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
     bound = k * U * mag * (1 + U16) + U16 * ref.abs()
     err, zero = (got - ref).abs(), bound == 0
@@ -190,28 +195,31 @@ def within_2x_cpu_autocast(got, ref64, cpu16, expect=None):
 # guarded buffers
 # ---------------------------------------------------------------------------------------------------------------------
 class Rows:
-    """[M, C] rows of `dtype` inside a flat buffer with row stride C + pad and 64 elements past the last row.  Inputs (`values`
-    given): NaN in the pad columns, which must not be read; outputs: the sentinel everywhere (pad columns and the tail must keep it)."""
+    """[M, C] rows of `dtype` inside a flat buffer with row stride lead + C + pad and 64 elements past the last row; the rows start
+    `lead` columns into the wide rows (a channel slice; lead = 1 or 2: a view that is not 16-byte aligned).  Inputs (`values` given):
+    NaN in the lead and pad columns, which must not be read (`nan_tail`: behind the last row too); outputs: the sentinel everywhere
+    (lead and pad columns and the tail must keep it)."""
 
-    def __init__(self, M, C, device, values=None, pad=4, dtype=torch.float32):
-        self.M, self.C, self.ld = M, C, C + pad
+    def __init__(self, M, C, device, values=None, pad=4, dtype=torch.float32, lead=0, nan_tail=False):
+        self.M, self.C, self.ld, self.lead = M, C, lead + C + pad, lead
         self.flat = torch.full((M * self.ld + GUARD,), SENTINEL, device=device, dtype=dtype)
         self.full = self.flat[:M * self.ld].view(M, self.ld)
-        self.rows = self.full[:, :C]
+        self.rows = self.full[:, lead:lead + C]
         if values is not None:
             assert values.dtype == dtype
-            self.full.fill_(float("nan"))
+            (self.flat if nan_tail else self.full).fill_(float("nan"))
             self.rows.copy_(values)
 
     def check_untouched(self, what):
         assert bool((self.flat[self.M * self.ld:] == SENTINEL).all()), f"{what}: memory past the last row was written"
-        assert bool((self.full[:, self.C:] == SENTINEL).all()), f"{what}: pad columns of the output were written"
+        assert bool((self.full[:, self.lead + self.C:] == SENTINEL).all()), f"{what}: pad columns of the output were written"
+        assert bool((self.full[:, :self.lead] == SENTINEL).all()), f"{what}: columns in front of the output slice were written"
 
 
-def flat_out(shape, device):
-    """a contiguous fp32 output of `shape` at the start of a sentinel-filled flat buffer with 64 more floats behind it"""
+def flat_out(shape, device, dtype=torch.float32):
+    """a contiguous output of `shape` at the start of a sentinel-filled flat buffer with 64 more elements behind it"""
     n = math.prod(shape)
-    flat = torch.full((n + GUARD,), SENTINEL, device=device)
+    flat = torch.full((n + GUARD,), SENTINEL, device=device, dtype=dtype)
     return flat, flat[:n].view(shape)
 
 
@@ -229,3 +237,36 @@ def guarded(t, device):
     assert view.is_contiguous() and view.data_ptr() % 16 == 0
     assert bool(torch.isnan(flat[:GUARD]).all()) and bool(torch.isnan(flat[GUARD + n:]).all())
     return view
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the stream-K workspace of pfk_conv2d_f32 (cfg 9): 768 partial tiles of 64 x 64 floats, then one 64-byte flag slot per block
+# ---------------------------------------------------------------------------------------------------------------------
+SK_BLOCKS, SK_FLAG_BYTES = 768, 64
+
+
+def ws_regions(ws):
+    """(partials, flags) of a uint8 workspace of `pfk_conv_workspace_bytes()` bytes"""
+    flags = ws.numel() - SK_BLOCKS * SK_FLAG_BYTES
+    return ws[:flags], ws[flags:]
+
+
+def arm(ws):
+    """0xFF over the partials (a partial read before it is written shows up as NaN); the flags stay zero"""
+    ws_regions(ws)[0].fill_(0xFF)
+
+
+def ws_after(ws, split_expected, what):
+    """after a launch on an armed workspace: no fix-up timed out, the flag region is zero again, and partial tiles were written if and
+    only if `split_expected` (None: either); returns whether they were"""
+    part, flags = ws_regions(ws)
+    off = torch.ops.pfk.conv_workspace_fault_offset()
+    assert int(ws[off: off + 4].view(torch.int32).item()) == 0, f"{what}: stream-K fix-up timed out"
+    assert not bool(flags.any()), f"{what}: the flag region is not zero after the launch"
+    touched = bool((part != 0xFF).any())
+    if split_expected is not None:
+        if split_expected:
+            assert touched, f"{what}: no partial tile was written: the launch did not run split stream-K tiles"
+        else:
+            assert not touched, f"{what}: partial tiles were written: the launch ran stream-K, not a tile grid"
+    return touched

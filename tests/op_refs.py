@@ -121,3 +121,138 @@ def convex_case(B, H, W, logit_scale):
     k_mask = pm((2 * k_w + 15)[:, None].expand(B, 9, 8, 8, H, W))
     return {"flow": flow, "mask": mask, "go": go, "gflow": gflow, "gflow_mag": gflow_mag, "gmask": pm(gmask), "gmask_mag": pm(gmask_mag),
             "k_mask": k_mask, "k_flow": 9 * 64 + float(k_w.max()) + 2}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the LINEAR epilogue of pfk_conv2d_f32 / pfk_conv2d_group_f32 and the all-pairs correlation volumes, restated on what a launch consumes
+# ---------------------------------------------------------------------------------------------------------------------
+GRID = (2, 11, 13)          # M = 286 = 4 * 64 + 30 = 2 * 128 + 30; the image boundary (pixel 143) falls inside a tile
+GRID_S2 = (3, 13, 15)       # stride 2: Ho x Wo = 7 x 8, M = 168 = 128 + 40
+GRID_WIDE = (2, 7, 11)      # M = 154
+
+# name: grid, (kh, kw), stride, sources [(real channels, view width)], cout, activation, scale, bias, residual, relu2
+LINEAR_CASES = {
+    # the cases of tests/test_gpu_linear_schedules.py that run on every schedule
+    "motion":      (GRID, (3, 3), 1, [(64, 64), (146, 148), (2, 4)], 126, "relu", 1.0, True, False, False),
+    "mask_head":   (GRID, (1, 1), 1, [(256, 256)], 576, "none", 0.25, True, False, False),
+    "res_block":   (GRID, (3, 3), 1, [(96, 96)], 96, "relu", 1.0, True, True, True),
+    "down_s2":     (GRID_S2, (3, 3), 2, [(64, 64)], 96, "relu", 1.0, True, True, True),
+    "down_1x1_s2": (GRID_S2, (1, 1), 2, [(64, 64)], 96, "none", 1.0, True, False, False),
+    "sep_1x5":     (GRID, (1, 5), 1, [(128, 128), (128, 128)], 128, "none", 1.0, True, False, False),
+    "sep_5x1":     (GRID, (5, 1), 1, [(128, 128), (128, 128)], 128, "none", 1.0, False, False, False),
+    "k7":          (GRID, (7, 7), 1, [(3, 4)], 40, "relu", 1.0, True, False, False),
+    "convc1":      (GRID, (1, 1), 1, [(324, 324)], 256, "relu", 1.0, True, False, False),          # the last chunk holds 4 channels
+    "res_scaled":  (GRID, (3, 3), 1, [(48, 48)], 72, "relu", 0.37, True, True, False),             # a residual AND a scale != 1
+    "motion_res":  (GRID, (3, 3), 1, [(64, 64), (146, 148), (2, 4)], 126, "relu", 1.0, True, True, False),   # the alignment fall-backs
+    "gelu_motion": (GRID, (3, 3), 1, [(64, 64), (146, 148), (2, 4)], 126, "gelu", 1.0, True, False, False),
+    "gelu_res":    (GRID, (3, 3), 1, [(96, 96)], 96, "gelu", 0.5, True, True, False),
+    "active":      (GRID, (3, 3), 1, [(128, 128)], 128, "relu", 1.0, True, False, False),          # cout_active 64 / cout_split 64
+    # the problems of the grouped launches
+    "g_c1":        (GRID, (1, 1), 1, [(324, 324)], 256, "relu", 1.0, True, True, False),
+    "g_k3":        (GRID, (3, 3), 1, [(64, 64)], 96, "relu", 0.5, True, True, False),
+    "g_mask":      (GRID, (1, 1), 1, [(256, 256)], 576, "none", 0.25, False, True, False),
+    "g_sw0":       (GRID, (1, 1), 1, [(32, 32)], 4990, "relu", 1.0, True, True, False),
+    "g_sw1":       (GRID, (1, 1), 1, [(36, 36)], 4992, "none", 0.5, True, True, False),
+    "g_wide0":     (GRID_WIDE, (1, 1), 1, [(2048, 2048)], 128, "none", 0.37, False, True, False),
+    "g_wide1":     (GRID_WIDE, (1, 1), 1, [(2080, 2080)], 256, "relu", 1.0, True, True, False),
+}
+
+
+def conv_out_hw(H, W, stride):
+    """the output grid of a 'same'-padded convolution of stride `stride`"""
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def _rows_of(t):
+    """NCHW -> pixel-major [B * H * W, C]"""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+def _images_of(rows, B, H, W):
+    return rows.reshape(B, H, W, -1).permute(0, 3, 1, 2)
+
+
+def linear_act64(pre, act):
+    if act == "relu":
+        return pre.clamp_min(0)
+    if act == "gelu":
+        return 0.5 * pre * (1 + torch.erf(pre / math.sqrt(2)))
+    return pre
+
+
+@functools.lru_cache(maxsize=None)
+def linear_case(name):
+    """One LINEAR launch, once per case: fp32 inputs exactly as the launch consumes them — `xs` [M_in, view width] rows per source
+    (columns past `real` hold finite garbage: they meet zero weights), the conv weight `w` over the real channels, its packed form and
+    `segs`, `bias`, `residual` [M_out, cout], `scale` (the float32 value, widened) — and in float64
+        ref = relu2?( residual + scale * act(sum x w + bias) )        mag = |scale| (sum |x| |w| + |bias|) + |residual|
+    with `pre` = sum x w + bias.  k = n + 4, n = kh kw sum(real) + [bias]: n roundings of the running sum in any order (stream-K
+    partials included), one for the scale, one for the residual add, two to spare; relu is 1-Lipschitz."""
+    from ptlflow_amd.packing import pack_conv_weight
+    (B, H, W), (kh, kw), stride, sources, cout, act, scale, with_bias, with_res, relu2 = LINEAR_CASES[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)) * 31 + cout)
+    rnd = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
+    Ho, Wo = conv_out_hw(H, W, stride)
+    M_in, M_out = B * H * W, B * Ho * Wo
+    xs = [rnd(M_in, width) for _, width in sources]
+    cin = sum(real for real, _ in sources)
+    w = rnd(cout, cin, kh, kw) / math.sqrt(cin * kh * kw)
+    bias = rnd(cout) * 0.3 if with_bias else None
+    residual = rnd(M_out, cout) if with_res else None
+    scale32 = float(torch.tensor(scale, dtype=torch.float32))
+    segs, first = [], 0
+    for real, width in sources:
+        segs.append((first, real, width))
+        first += real
+    x64 = _images_of(torch.cat([x[:, :real].double() for x, (real, _) in zip(xs, sources)], 1), B, H, W)
+    pad = (kh // 2, kw // 2)
+    pre = _rows_of(F.conv2d(x64, w.double(), None, stride=stride, padding=pad))
+    mag = _rows_of(F.conv2d(x64.abs(), w.double().abs(), None, stride=stride, padding=pad))
+    if with_bias:
+        pre, mag = pre + bias.double(), mag + bias.double().abs()
+    ref, mag = scale32 * linear_act64(pre, act), abs(scale32) * mag
+    if with_res:
+        ref, mag = residual.double() + ref, mag + residual.double().abs()
+    if relu2:
+        ref = ref.clamp_min(0)
+    n = kh * kw * cin + int(with_bias)
+    return {"name": name, "grid": (B, H, W), "out_grid": (B, Ho, Wo), "k": (kh, kw), "stride": stride, "sources": sources, "reals": [r for r, _ in sources],
+            "cout": cout, "act": act, "relu": act == "relu", "scale": scale32, "relu2": relu2, "M_in": M_in, "M": M_out,
+            "xs": xs, "w": w, "segs": segs, "packed": pack_conv_weight(w, segs), "bias": bias, "residual": residual,
+            "pre": pre, "ref": ref, "mag": mag, "K": n + 4, "steps": sum(kh * kw * ((width + 31) // 32) for _, width in sources)}
+
+
+def linear_torch32(c):
+    """torch's own fp32 CPU arithmetic of the same op: [M_out, cout]"""
+    B, H, W = c["grid"]
+    x = _images_of(torch.cat([x[:, :real] for x, real in zip(c["xs"], c["reals"])], 1), B, H, W)
+    v = _rows_of(F.conv2d(x, c["w"], c["bias"], stride=c["stride"], padding=(c["k"][0] // 2, c["k"][1] // 2)))
+    v = F.relu(v) if c["act"] == "relu" else F.gelu(v) if c["act"] == "gelu" else v
+    v = v * c["scale"]
+    if c["residual"] is not None:
+        v = c["residual"] + v
+    return F.relu(v) if c["relu2"] else v
+
+
+# (B, N1, N2, D) of tests/test_gpu_volume_gate.py
+VOLUMES_F32 = [(2, 117, 130, 64), (2, 132, 120, 128), (1, 2050, 2114, 32), (2, 2050, 4000, 32), (2, 150, 140, 36)]
+VOLUMES_B16 = [(2, 130, 117, 40), (2, 132, 132, 64), (1, 257, 264, 72), (1, 40, 9, 8), (1, 4100, 4230, 8), (2, 70, 133, 40)]
+
+
+@functools.lru_cache(maxsize=2)
+def volume_case(B, N1, N2, D, dtype):
+    """The all-pairs correlation out[b, i, j] = scale * <a[b, i], b[b, j]> on fp32 or bf16 rows: `a` [B, N1, D], `b` [B, N2, D] in
+    `dtype`, scale = float32(1 / sqrt(D)), and in float64 ref = scale * sum a b, mag = |scale| sum |a| |b|; K = D + 3 (D roundings
+    of the sum in any order, one for the scale, two to spare; bf16 x bf16 products are exact in fp32)."""
+    g = torch.Generator().manual_seed(B * 1009 + N1 * 31 + N2 * 7 + D)
+    a, b = torch.randn(B, N1, D, generator=g).to(dtype), torch.randn(B, N2, D, generator=g).to(dtype)
+    scale = float(torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32))
+    a64, b64 = a.double(), b.double()
+    return {"a": a, "b": b, "scale": scale, "K": D + 3, "ref": scale * torch.bmm(a64, b64.transpose(1, 2)),
+            "mag": abs(scale) * torch.bmm(a64.abs(), b64.abs().transpose(1, 2))}
+
+
+def volume_torch32(c, d=None):
+    """torch's fp32 CPU arithmetic of the volume over the first `d` channels (default: all), rounded to the inputs' dtype"""
+    a, b = c["a"][..., :d].float(), c["b"][..., :d].float()
+    return (torch.bmm(a, b.transpose(1, 2)) * c["scale"]).to(c["a"].dtype)

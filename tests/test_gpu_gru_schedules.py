@@ -21,7 +21,7 @@ import math
 import pytest
 import torch
 
-from op_gate import close32, within_ulp
+from op_gate import arm, close32, within_ulp, ws_after
 from op_refs import conv64, ref_q, ref_zr
 
 pytestmark = pytest.mark.gpu
@@ -62,29 +62,6 @@ def _widths(spec, b16):
 
 def _report(tag, **ratios):
     print(f"[ratio] {tag} " + " ".join(f"{k}={v:.3f}" for k, v in ratios.items()))
-
-
-# ---------------------------------------------------------------------------------------------------------------- stream-K workspace
-def _ws_regions(ws):
-    flags = ws.numel() - 768 * 64            # pfk_gemm.hip: 768 partial tiles, then one 64-byte flag slot per block
-    return ws[:flags], ws[flags:]
-
-
-def _arm(ws):
-    """0xFF over the partials (a partial read before it is written shows up as NaN); the flags stay zero"""
-    _ws_regions(ws)[0].fill_(0xFF)
-
-
-def _ws_after(ws, split_expected, what):
-    part, flags = _ws_regions(ws)
-    off = torch.ops.pfk.conv_workspace_fault_offset()
-    assert int(ws[off: off + 4].view(torch.int32).item()) == 0, f"{what}: stream-K fix-up timed out"
-    assert not bool(flags.any()), f"{what}: the flag region is not zero after the launch"
-    touched = bool((part != 0xFF).any())
-    if split_expected:
-        assert touched, f"{what}: no partial tile was written: the launch did not run split stream-K tiles"
-    else:
-        assert not touched, f"{what}: partial tiles were written: the launch ran stream-K, not a tile grid"
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. forced schedules
@@ -143,7 +120,7 @@ def _run_f32(t, epi, cfg):
     ws = None
     if cfg == 9:
         ws = torch.zeros(torch.ops.pfk.conv_workspace_bytes(), device="cuda", dtype=torch.uint8)
-        _arm(ws)
+        arm(ws)
     if epi == EPI_GRU_ZR:
         args = ([act[:, :Ch], motion], t["pzr"], t["bzr"], 2 * Ch, t["z"], t["rh"], t["ctx_zr"])
     else:
@@ -156,7 +133,7 @@ def _run_f32(t, epi, cfg):
     finally:
         torch.ops.pfk.debug_set_tile(-1)
     if ws is not None:
-        _ws_after(ws, True, f"cfg 9 epilogue {epi}")
+        ws_after(ws, True, f"cfg 9 epilogue {epi}")
 
 
 @pytest.mark.parametrize("with_ctx", [True, False], ids=["ctx", "noctx"])
@@ -345,12 +322,12 @@ def test_engine_gate_launches(gpu, path, model, b, h, w, zr_sched, q_sched):
         hx0, hxb0 = eng.hx.clone(), (eng.hxb.clone() if b16 else None)
         z0, rh0, res0 = eng.zbuf.clone(), eng.rh.clone(), (residual.clone() if residual is not None else None)
         if not b16:
-            _arm(eng.workspace)
+            arm(eng.workspace)
         orig(srcs, kh, kw, key, cout, epi=epi, h=h, z=z, rh=rh, residual=residual, **kw_)
         torch.cuda.synchronize()
         what = f"{key} ({sched})"
         if not b16:
-            _ws_after(eng.workspace, sched == "sk", what)
+            ws_after(eng.workspace, sched == "sk", what)
         if residual is not None:
             assert torch.equal(residual, res0), f"{what} wrote into its context rows"
         bias = eng.w.get(key + ".b")

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import raft_oracle as O
-from op_gate import close, pm, unpm
+from op_gate import arm, close, pm, unpm, ws_after
 from op_refs import coords_cases
 
 pytestmark = pytest.mark.gpu
@@ -256,17 +256,13 @@ def test_conv_all_tile_configs(gpu, tile):
 def _stream_k_launch(ws, launch):
     """`launch()` forced onto the stream-K schedule (cfg 9) with the partials of `ws` set to 0xFF bytes (NaN: a partial read before
     it is written poisons its tile); returns whether partials were written.  The flag region and the fault word must be zero after."""
-    flags = ws.numel() - 768 * 64       # 768 partial tiles of 64x64 fp32, then the flag region (pfk_gemm.hip SK_WS_BYTES)
-    ws[:flags].fill_(0xFF)
+    arm(ws)
     torch.ops.pfk.debug_set_tile(9)
     try:
         launch()
     finally:
         torch.ops.pfk.debug_set_tile(-1)
-    off = torch.ops.pfk.conv_workspace_fault_offset()
-    assert int(ws[off: off + 4].view(torch.int32).item()) == 0, "a stream-K fix-up timed out"
-    assert not bool(ws[flags:].any()), "the stream-K flags are not zero after the launch"
-    return bool((ws[:flags] != 0xFF).any())
+    return ws_after(ws, None, "forced stream-K")
 
 
 @pytest.mark.parametrize("B,H,W,segs,cout,kh,kw", [

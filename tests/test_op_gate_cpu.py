@@ -4,9 +4,11 @@ import math
 
 import pytest
 import torch
+import torch.nn.functional as F
 
-from op_gate import (FLOOR, GUARD, OP_TOL, SENTINEL, U, Rows, close, close32, flat_out, gates, gates_b16, guarded, rel, scale_close,
-                     tail_kept, ulp_bf16, within_ulp)
+import op_refs
+from op_gate import (FLOOR, GUARD, OP_TOL, SENTINEL, SK_BLOCKS, SK_FLAG_BYTES, U, Rows, arm, close, close32, flat_out, gates, gates_b16,
+                     guarded, rel, scale_close, tail_kept, ulp_bf16, within_ulp, ws_regions)
 
 CPU = torch.device("cpu")
 F32, B16, F64 = torch.float32, torch.bfloat16, torch.float64
@@ -186,6 +188,28 @@ def test_rows(dtype, pad):
             r.check_untouched("out")
 
 
+@pytest.mark.parametrize("lead", [1, 2, 4])
+def test_rows_as_a_slice_of_wider_rows(lead):
+    M, C, pad = 5, 12, 3
+    values = torch.randn(M, C, generator=torch.Generator().manual_seed(1))
+    inp = Rows(M, C, CPU, values, pad=pad, lead=lead, nan_tail=True)
+    assert inp.ld == lead + C + pad and inp.rows.stride() == (inp.ld, 1) and inp.rows.storage_offset() == lead and torch.equal(inp.rows, values)
+    assert bool(torch.isnan(inp.full[:, :lead]).all()) and bool(torch.isnan(inp.full[:, lead + C:]).all())
+    assert bool(torch.isnan(inp.flat[M * inp.ld:]).all()), "nan_tail: NaN behind the last row"
+    r = Rows(M, C, CPU, pad=pad, lead=lead)
+    r.rows.copy_(values)
+    r.check_untouched("out")
+    r.full[3, lead - 1] = 1.0
+    with pytest.raises(AssertionError, match="out: columns in front of the output slice were written"):
+        r.check_untouched("out")
+    r = Rows(M, C, CPU, pad=pad, lead=lead)
+    r.full[0, lead + C] = 1.0
+    with pytest.raises(AssertionError, match="out: pad columns of the output were written"):
+        r.check_untouched("out")
+    flat, view = flat_out((3, 4), CPU, B16)
+    assert flat.dtype == B16 and view.dtype == B16 and tail_kept(flat)
+
+
 def test_sentinel_is_a_bf16_value():
     assert float(torch.tensor(SENTINEL).to(B16)) == SENTINEL == 3 * 2.0 ** 12
 
@@ -298,3 +322,141 @@ def test_scale_close_at_the_limit():
     with pytest.raises(AssertionError):
         scale_close(ref * (1 + 1e-3), ref, "t")                                   # the default: BLOCK_TOL = 5e-4 of the scale
     scale_close(ref * (1 + 4e-4), ref, "t")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the LINEAR and volume references of tests/op_refs.py
+# ---------------------------------------------------------------------------------------------------------------------
+def test_gates_b16_without_a_twin():
+    n = 7
+    p, ref, mag = products(n)
+    got = left_to_right(p).to(B16)
+    r, ratio = gates_b16("b", got, None, ref, mag, n + 2)
+    assert ratio <= 1.0 and r <= 2.0 ** -8 * (1 + 1e-3)
+    off = got.clone()
+    off[9] = bf16_next(off[9], 2)                    # two bf16 ulps off: outside half an ulp + the fp32 bound
+    with pytest.raises(AssertionError, match="x the bound"):
+        gates_b16("b", off, None, ref, mag, n + 2)
+    with pytest.raises(AssertionError):
+        gates_b16("b", got.float(), None, ref, mag, n + 2)
+    with pytest.raises(AssertionError, match="shapes"):
+        gates_b16("b", got[:-1], None, ref, mag, n + 2)
+
+
+def test_ws_regions_and_arm():
+    ws = torch.zeros(SK_BLOCKS * (64 * 64 * 4 + SK_FLAG_BYTES), dtype=torch.uint8)     # pfk_gemm.hip SK_WS_BYTES
+    part, flags = ws_regions(ws)
+    assert part.numel() == SK_BLOCKS * 64 * 64 * 4 and flags.numel() == SK_BLOCKS * SK_FLAG_BYTES
+    arm(ws)
+    assert bool((part == 0xFF).all()) and not bool(flags.any())
+    assert bool(torch.isnan(part.view(F32)).all()), "an armed partial reads as NaN"
+
+
+def linear_restated(c):
+    """`linear_case`'s formula once more, independently: explicit loops over sources, taps and output pixels in float64"""
+    (B, H, W), (Bo, Ho, Wo), (kh, kw), s = c["grid"], c["out_grid"], c["k"], c["stride"]
+    out = torch.zeros(c["M"], c["cout"], dtype=F64)
+    w64, first = c["w"].double(), 0
+    for x, real in zip(c["xs"], c["reals"]):
+        img = x[:, :real].double().reshape(B, H, W, real)
+        for ky in range(kh):
+            for kx in range(kw):
+                wt = w64[:, first:first + real, ky, kx]                              # [cout, real]
+                for b in range(B):
+                    for yo in range(Ho):
+                        for xo in range(Wo):
+                            y, xx = yo * s + ky - kh // 2, xo * s + kx - kw // 2
+                            if 0 <= y < H and 0 <= xx < W:
+                                out[(b * Ho + yo) * Wo + xo] += wt @ img[b, y, xx]
+        first += real
+    if c["bias"] is not None:
+        out = out + c["bias"].double()
+    out = torch.where(out < 0, torch.zeros_like(out), out) if c["act"] == "relu" else out
+    out = out * c["scale"]
+    if c["residual"] is not None:
+        out = c["residual"].double() + out
+    return torch.where(out < 0, torch.zeros_like(out), out) if c["relu2"] else out
+
+
+def test_linear_case_equals_its_restatement(monkeypatch):
+    """(a) a tiny shape with stride 2, two sources (one with pad channels), a residual, a scale and relu2"""
+    monkeypatch.setitem(op_refs.LINEAR_CASES, "tiny_s2", ((2, 5, 6), (3, 3), 2, [(8, 8), (6, 8)], 12, "relu", 0.37, True, True, True))
+    c = op_refs.linear_case("tiny_s2")
+    assert c["out_grid"] == (2, 3, 3) and c["M"] == 18 and c["K"] == 9 * 14 + 1 + 4 and c["steps"] == 18
+    assert c["packed"].shape == (12, 9 * 64) and c["scale"] == float(torch.tensor(0.37, dtype=F32))
+    want = linear_restated(c)
+    assert float((c["ref"] - want).abs().max()) <= 1e-13 * float(want.abs().max())
+    assert bool((c["ref"] == 0).any()) and bool((c["mag"] > 0).all())
+    # the pad channels of the second source take no part
+    assert bool((c["packed"].view(12, 2, 9, 32)[:, 1, :, 6:] == 0).all())
+
+
+@pytest.mark.parametrize("name", list(op_refs.LINEAR_CASES))
+def test_torch_fp32_passes_the_linear_gates(name):
+    """(b) the reference alone stays inside the gates: torch's fp32 CPU convolution of the same op"""
+    c = op_refs.linear_case(name)
+    got = op_refs.linear_torch32(c)
+    if c["act"] == "gelu":
+        assert rel(got, c["ref"]) <= OP_TOL
+    else:
+        gates(name, got, c["ref"], c["mag"], c["K"])
+
+
+@pytest.mark.parametrize("case", op_refs.VOLUMES_F32 + op_refs.VOLUMES_B16, ids=str)
+def test_torch_fp32_passes_the_volume_gates(case):
+    b16 = case in op_refs.VOLUMES_B16
+    c = op_refs.volume_case(*case, B16 if b16 else F32)
+    got = op_refs.volume_torch32(c)
+    if b16:
+        gates_b16(str(case), got, None, c["ref"], c["mag"], c["K"])
+    else:
+        gates(str(case), got, c["ref"], c["mag"], c["K"])
+
+
+def fails(what, got, c, b16=False):
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        (gates_b16(what, got, None, c["ref"], c["mag"], c["K"]) if b16 else gates(what, got, c["ref"], c["mag"], c["K"]))
+
+
+def test_linear_mutations_fail_a_gate():
+    """(c) each of these is a correct fp32 output with one thing wrong"""
+    c = op_refs.linear_case("res_block")
+    good = op_refs.linear_torch32(c)
+    gates("res_block", good, c["ref"], c["mag"], c["K"])
+    B, H, W = c["grid"]
+    # one tap (ky, kx) = (1, 0) dropped at the border pixel (1, 5, W - 1) — the residual keeps the output away from relu2's zero
+    p = (1 * H + 5) * W + (W - 1)
+    tap = c["w"][:, :, 1, 0] @ c["xs"][0][p - 1]
+    pre32 = F.relu(c["pre"].float()[p])
+    got = good.clone()
+    got[p] = F.relu(c["residual"][p] + F.relu(c["pre"].float()[p] - tap))
+    assert not torch.equal(got[p], F.relu(c["residual"][p] + pre32))
+    fails("tap dropped", got, c)
+    # relu2 omitted
+    fails("relu2 omitted", c["residual"] + F.relu(c["pre"].float()), c)
+    # one output row of image 1 taken from image 0
+    got = good.clone()
+    got[H * W + 3 * W: H * W + 4 * W] = good[3 * W: 4 * W]
+    fails("row of the other image", got, c)
+    # the residual added before the scale
+    c = op_refs.linear_case("res_scaled")
+    gates("res_scaled", op_refs.linear_torch32(c), c["ref"], c["mag"], c["K"])
+    fails("residual before the scale", (c["residual"] + F.relu(c["pre"].float())) * c["scale"], c)
+
+
+def test_volume_mutations_fail_a_gate():
+    # batch 1 written with stride N1 * N2 - 1
+    for case, dt in (((2, 117, 130, 64), F32), ((2, 130, 117, 40), B16)):
+        c = op_refs.volume_case(*case, dt)
+        good = op_refs.volume_torch32(c)
+        n = case[1] * case[2]
+        flat = torch.zeros(2 * n, dtype=dt)
+        flat[:n] = good[0].reshape(-1)
+        flat[n - 1: 2 * n - 1] = good[1].reshape(-1)
+        flat[n - 1] = good[0].reshape(-1)[-1]          # (the last element of batch 0 written after batch 1's first)
+        fails("batch stride", flat.view(good.shape), c, dt == B16)
+    # the last partial K chunk dropped: 36 = 32 + 4 channels of the fp32 kernel, 72 = 64 + 8 of the bf16 one
+    c = op_refs.volume_case(2, 150, 140, 36, F32)
+    fails("partial chunk", op_refs.volume_torch32(c, 32), c)
+    c = op_refs.volume_case(1, 257, 264, 72, B16)
+    fails("partial chunk bf16", op_refs.volume_torch32(c, 64), c, True)
