@@ -828,7 +828,8 @@ int pfk_nchw_to_pm_f32(const float* in, float* out, int out_ld, int out_coff, in
 int pfk_pm_to_nchw_f32(const float* in, int in_ld, int in_coff, float* out, int B, int C, int H,
                        int W, pfk_stream_t stream);
 /* pixel-major [B*N][in_ld] -> channel-major out[b][c][n] with row stride out_ld >= N (a K-contiguous "weight"
- * operand for pfk_conv2d_f32, e.g. GMA's value matrix V^T, gma_utils.py:103-105) */
+ * operand for pfk_conv2d_f32, e.g. GMA's value matrix V^T, gma_utils.py:103-105).  The pad columns [N, out_ld) of a row are not
+ * written: they keep what the caller put there (zeros, where a consumer reads them). */
 int pfk_pm_to_cm_f32(const float* in, int in_ld, float* out, int out_ld, int B, int C, int N,
                      pfk_stream_t stream);
 

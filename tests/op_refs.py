@@ -256,3 +256,192 @@ def volume_torch32(c, d=None):
     """torch's fp32 CPU arithmetic of the volume over the first `d` channels (default: all), rounded to the inputs' dtype"""
     a, b = c["a"][..., :d].float(), c["b"][..., :d].float()
     return (torch.bmm(a, b.transpose(1, 2)) * c["scale"]).to(c["a"].dtype)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the refinement loop's small direct kernels (pfk_misc.hip, the forward of pfk_upsample.hip), restated on what a launch consumes
+# ---------------------------------------------------------------------------------------------------------------------
+CIN2_GRIDS = [(2, 3, 21), (1, 1, 1), (2, 9, 33)]                 # shorter than the 7x7 halo with a 5-pixel last tile; one pixel; two images
+CIN2_MFMA_GRIDS = CIN2_GRIDS + [(1, 5, 33), (2, 5, 4163)]        # 2 x 2 tiles with one-row / one-column tails; 524 tiles > the 512-block grid
+FLOW_DELTA_GRIDS4 = [(2, 2, 5), (2, 1, 3), (1, 3, 9)]            # the 4-pixel kernel
+FLOW_DELTA_GRIDS8 = [(2, 1024, 9), (4, 1024, 5)]                 # the 8-pixel kernel: B H ceil(W / 8) = 4096
+UP_GRIDS = [(1, 1, 1), (2, 1, 5), (1, 6, 1), (2, 5, 7)]
+UP_SCALES = [1.0, 40.0, 60.0]
+UPFLOW_GRIDS = [(1, 1, 1), (1, 1, 5), (2, 6, 1), (2, 9, 13)]
+LAYOUT_SHAPES = [(2, 33, 3, 11), (1, 1, 1, 1), (2, 126, 7, 45)]
+SOFTMAX_COLS = [1, 5, 140, 257, 713]
+SOFTMAX_ROWS = 7
+
+
+def taps64(x, w, k):
+    """'same' k x k convolution written tap by tap: x [B, H, W, cin], w [k * k, cin, cout] (tap-major), zero outside the image and
+    never across images -> [B, H, W, cout], in x's dtype.  A NaN in x reaches exactly the outputs whose window covers it."""
+    B, H, W, _ = x.shape
+    R = k // 2
+    xp = F.pad(x, (0, 0, R, R, R, R))
+    out = torch.zeros(B, H, W, w.shape[2], dtype=x.dtype)
+    for ky in range(k):
+        for kx in range(k):
+            out = out + xp[:, ky:ky + H, kx:kx + W] @ w[ky * k + kx]
+    return out
+
+
+def window_mask(B, H, W, b, y, x, R):
+    """[B, H, W] bool: the pixels of image b whose (2R + 1)^2 window covers (y, x)"""
+    m = torch.zeros(B, H, W, dtype=torch.bool)
+    m[b, max(0, y - R):y + R + 1, max(0, x - R):x + R + 1] = True
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def cin2_case(B, H, W, k, cout, relu=True, with_bias=True, nan_at=None):
+    """pfk_conv_cin2: `rows` [M, 2] fp32 flow, the packed weight [k * k, 2, cout] and `bias` as the launch consumes them, and in float64,
+    by a tap loop over the packed weight,  ref = relu?(bias + sum x w),  mag = |bias| + sum |x| |w|,  K = 2 k k + 2 (n = 2 k k products
+    in any order; relu is 1-Lipschitz and keeps an exact zero where mag is 0).  `nan_at` = (y, x): the y component of that flow pixel of
+    image 1 is NaN, `nan` [M, cout] the outputs whose window covers it (ref and mag are NaN there and only there)."""
+    from ptlflow_amd.packing import pack_cin2_weight
+    g = torch.Generator().manual_seed(((B * 131 + H) * 131 + W) * 131 + k * 17 + cout)
+    flow = torch.randn(B, 2, H, W, generator=g) * 3
+    w = torch.randn(cout, 2, k, k, generator=g) / k
+    bias = torch.randn(cout, generator=g) * 0.3 if with_bias else None
+    nan = torch.zeros(B, H, W, dtype=torch.bool)
+    if nan_at is not None:
+        flow[1, 1, nan_at[0], nan_at[1]] = float("nan")
+        nan = window_mask(B, H, W, 1, *nan_at, k // 2)
+    packed = pack_cin2_weight(w)
+    x64, w64 = flow.double().permute(0, 2, 3, 1), packed.double()
+    pre, mag = taps64(x64, w64, k), taps64(x64.abs(), w64.abs(), k)
+    if with_bias:
+        pre, mag = pre + bias.double(), mag + bias.double().abs()
+    ref = pre.clamp_min(0) if relu else pre
+    M = B * H * W
+    return {"grid": (B, H, W), "k": k, "cout": cout, "relu": relu, "flow": flow, "rows": _rows_of(flow).contiguous(), "w": w, "packed": packed,
+            "bias": bias, "ref": ref.reshape(M, cout), "mag": mag.reshape(M, cout), "K": 2 * k * k + 2,
+            "nan": nan.reshape(M, 1).expand(M, cout).clone()}
+
+
+def cin2_torch32(c, flow=None, w=None):
+    """torch's fp32 CPU convolution of the same op: [M, cout]"""
+    v = F.conv2d(c["flow"] if flow is None else flow, c["w"] if w is None else w, c["bias"], padding=c["k"] // 2)
+    return _rows_of(F.relu(v) if c["relu"] else v)
+
+
+@functools.lru_cache(maxsize=None)
+def flow_delta_case(B, H, W, cin, dtype=torch.float32, nan_corners=False):
+    """pfk_flow_delta: `x` [M, cin] rows in `dtype`, FlowHead.conv2's weight `w` [2, cin, 3, 3], its packed form [9, 2, cin], `bias` [2],
+    `c0` / `c1` [B, 2, H, W], and in float64 on the widened rows  delta = bias + sum x w,  mag = |bias| + sum |x| |w|  [B, 2, H, W],
+    K = 9 cin + 2.  `nan_corners`: the input rows of the four corner pixels of image 1 are NaN; `nan` marks their 3x3 neighbours in
+    image 1 — were the row above y = 0 of image 1 image 0's last row, image 0's last row would be NaN too."""
+    from ptlflow_amd.packing import pack_flow_head_weight
+    g = torch.Generator().manual_seed(((B * 131 + H) * 131 + W) * 131 + cin)
+    M = B * H * W
+    x = torch.randn(M, cin, generator=g).to(dtype)
+    w = torch.randn(2, cin, 3, 3, generator=g) / math.sqrt(9 * cin)
+    bias = torch.randn(2, generator=g) * 0.3
+    c0 = O.coords_grid(B, H, W)
+    c1 = c0 + torch.randn(B, 2, H, W, generator=g) * 2
+    nan = torch.zeros(B, H, W, dtype=torch.bool)
+    if nan_corners:
+        img = x.view(B, H, W, cin)
+        for y in (0, H - 1):
+            for xx in (0, W - 1):
+                img[1, y, xx] = float("nan")
+                nan |= window_mask(B, H, W, 1, y, xx, 1)
+    packed = pack_flow_head_weight(w)
+    x64, w64 = x.double().view(B, H, W, cin), packed.double().transpose(1, 2)          # [9, cin, 2]
+    b64 = bias.double().view(1, 2, 1, 1)
+    ref = taps64(x64, w64, 3).permute(0, 3, 1, 2) + b64
+    mag = taps64(x64.abs(), w64.abs(), 3).permute(0, 3, 1, 2) + b64.abs()
+    return {"grid": (B, H, W), "cin": cin, "x": x, "w": w, "packed": packed, "bias": bias, "c0": c0, "c1": c1, "ref": ref, "mag": mag,
+            "K": 9 * cin + 2, "nan": nan[:, None].expand(B, 2, H, W).clone()}
+
+
+def flow_delta_torch32(c, x=None):
+    """torch's fp32 CPU convolution on the widened rows: [B, 2, H, W]"""
+    B, H, W = c["grid"]
+    x = c["x"].float() if x is None else x
+    return F.conv2d(_images_of(x, B, H, W), c["w"][:, :x.shape[1]], c["bias"], padding=1)
+
+
+def convex_fwd64(flow, mask, info=None):
+    """The forward x8 convex upsampling in float64 on the fp32 values a launch reads: flow [B, 2, H, W], mask [B, 576, H, W] (bf16
+    logits widened), info [B, n, H, W] or None ->  ref, mag, k  [B, 2 + n, 8H, 8W]  with
+        w_k = softmax_k(mask[k, sy, sx]),   ref = sum_k w_k v_k,   mag = sum_k w_k |v_k|,   v = 8 flow (exact) or info, zero outside
+    the image.  k = k_w + 11 per element: k_w = 2 spread + 19 is the relative error of a weight in units of 2^-24 (`convex_case`'s
+    comment; spread = max - min of the nine logits, over the finite ones: expf(-inf) is an exact 0), and the combination adds one
+    rounding for each product and nine additions, one to spare."""
+    B, _, H, W = flow.shape
+    m = mask.double().view(B, 1, 9, 8, 8, H, W)
+    wgt = torch.softmax(m, dim=2)
+    top = m.amax(2, keepdim=True)
+    spread = (top - torch.where(torch.isinf(m), top, m).amin(2, keepdim=True))[:, :, 0]               # [B, 1, 8, 8, H, W]
+    v = 8 * flow.double() if info is None else torch.cat([8 * flow.double(), info.double()], 1)
+    C = v.shape[1]
+    nb = F.unfold(v, [3, 3], padding=1).view(B, C, 9, 1, 1, H, W)
+    up = lambda t: t.permute(0, 1, 4, 2, 5, 3).reshape(B, C, 8 * H, 8 * W)        # noqa: E731   [B, C, sy, sx, H, W] -> [B, C, 8H, 8W]
+    return up((wgt * nb).sum(2)), up((wgt * nb.abs()).sum(2)), up((2 * spread + 30).expand(B, C, 8, 8, H, W))
+
+
+@functools.lru_cache(maxsize=None)
+def convex_fwd_case(B, H, W, logit_scale, b16=False, zero_image=None):
+    """fp32 `flow` [B, 2, H, W], `info` [B, 8, H, W] (a launch with n_info channels reads the first n) and `mask` [B, 576, H, W] logits
+    (`b16`: bf16), with `convex_fwd64` of them (channels 0, 1 the flow, 2.. the info); `zero_image`: that image's flow is zero"""
+    g = torch.Generator().manual_seed(B * 1000 + H * 100 + W * 10 + int(logit_scale) + 5)
+    flow = torch.randn(B, 2, H, W, generator=g) * 3
+    info = torch.randn(B, 8, H, W, generator=g)
+    mask = torch.randn(B, 576, H, W, generator=g) * logit_scale
+    if b16:
+        mask = mask.to(torch.bfloat16)
+    if zero_image is not None:
+        flow[zero_image] = 0.0
+    ref, mag, k = convex_fwd64(flow, mask.float(), info)
+    return {"grid": (B, H, W), "flow": flow, "info": info, "mask": mask, "ref": ref, "mag": mag, "k": k}
+
+
+def upflow8_axis(n_in):
+    """the kernel's index arithmetic along one axis, in fp32 as its comment gives it: (i0, i1, lambda1) for the 8 n_in outputs"""
+    n_out = 8 * n_in
+    scale = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32)
+    src = scale * torch.arange(n_out, dtype=torch.float32)
+    i0 = src.to(torch.int64)                                    # truncation; src >= 0
+    lam1 = src - i0.to(torch.float32)
+    i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+    return i0, i1, lam1
+
+
+@functools.lru_cache(maxsize=None)
+def upflow8_case(B, H, W):
+    """pfk_upflow8: `c0`, `c1` [B, 2, H, W] and, with the fp32 indices and lambdas of `upflow8_axis`, the float64 blend of c1 - c0:
+    ref = 8 sum ly lx v,  mag = 8 sum ly lx |v|  [B, 2, 8H, 8W];  K = 8: the difference, the two 1 - lambda, the four products in two
+    levels and two additions are at most 7 roundings on the path of a term, and the factor 8 is exact."""
+    g = torch.Generator().manual_seed(B * 100 + H * 10 + W)
+    c0 = torch.randn(B, 2, H, W, generator=g) * 30
+    c1 = c0 + torch.randn(B, 2, H, W, generator=g) * 4
+    v = c1.double() - c0.double()
+    y0, y1, ly = upflow8_axis(H)
+    x0, x1, lx = upflow8_axis(W)
+    ly, lx = ly.double()[:, None], lx.double()[None, :]
+    ref, mag = 0.0, 0.0
+    for yi, wy in ((y0, 1 - ly), (y1, ly)):
+        for xi, wx in ((x0, 1 - lx), (x1, lx)):
+            t = v[:, :, yi][:, :, :, xi]
+            ref, mag = ref + wy * wx * t, mag + wy * wx * t.abs()
+    return {"grid": (B, H, W), "c0": c0, "c1": c1, "ref": 8 * ref, "mag": 8 * mag, "K": 8}
+
+
+@functools.lru_cache(maxsize=None)
+def softmax_rows_case(cols, logit_scale):
+    """pfk_softmax_rows: `x` [7, cols] fp32 logits (row 3 holds -inf in all but two columns where cols >= 3), p = softmax in float64 and
+    k = 2 spread_row + cols + 19: the rounded differences x - max in the numerator and the denominator (spread each), expf twice, cols
+    additions, the division (spread over the finite logits: expf(-inf) is an exact 0)"""
+    g = torch.Generator().manual_seed(cols * 7 + int(logit_scale))
+    x = torch.randn(SOFTMAX_ROWS, cols, generator=g) * logit_scale
+    if cols >= 3:
+        keep = torch.zeros(cols, dtype=torch.bool)
+        keep[[1, cols - 1]] = True
+        x[3, ~keep] = float("-inf")
+    x64 = x.double()
+    top = x64.amax(1, keepdim=True)
+    spread = top - torch.where(torch.isinf(x64), top, x64).amin(1, keepdim=True)
+    p = torch.softmax(x64, dim=1)
+    return {"x": x, "ref": p, "mag": p, "k": (2 * spread + cols + 19).expand(SOFTMAX_ROWS, cols)}

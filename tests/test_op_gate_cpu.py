@@ -460,3 +460,247 @@ def test_volume_mutations_fail_a_gate():
     fails("partial chunk", op_refs.volume_torch32(c, 32), c)
     c = op_refs.volume_case(1, 257, 264, 72, B16)
     fails("partial chunk bf16", op_refs.volume_torch32(c, 64), c, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the refinement loop's small direct kernels (tests/test_gpu_loop_kernels_gate.py): each reference against an independent restatement,
+# torch's fp32 arithmetic inside the gates (the bounds are conditions, not measurements), and fp32 results with one thing wrong outside
+# ---------------------------------------------------------------------------------------------------------------------
+def same64(got, want, what):
+    assert got.shape == want.shape, what
+    assert float((got - want).abs().max()) <= 1e-12 * max(float(want.abs().max()), 1e-30), what
+
+
+def tall(x):
+    """[B, C, H, W] as ONE image of B H rows: what a kernel sees that walks from an image into its neighbour instead of padding"""
+    B, C, H, W = x.shape
+    return x.permute(1, 0, 2, 3).reshape(1, C, B * H, W)
+
+
+def untall(x, B):
+    _, C, BH, W = x.shape
+    return x.view(C, B, BH // B, W).permute(1, 0, 2, 3)
+
+
+CIN2_CPU = [(g, k, cout) for g in op_refs.CIN2_GRIDS for k, cout in ((3, 130), (5, 1), (7, 64), (1, 5), (9, 5))] + \
+           [((1, 5, 33), 7, 128), ((2, 5, 4163), 7, 64)]
+
+
+@pytest.mark.parametrize("grid,k,cout", CIN2_CPU, ids=str)
+def test_cin2_reference_and_torch_fp32(grid, k, cout):
+    c = op_refs.cin2_case(*grid, k, cout)
+    assert c["packed"].shape == (k * k, 2, cout) and c["K"] == 2 * k * k + 2 and not bool(c["nan"].any())
+    want = op_refs._rows_of(F.relu(F.conv2d(c["flow"].double(), c["w"].double(), c["bias"].double(), padding=k // 2)))
+    same64(c["ref"], want, "cin2 reference")
+    assert bool((c["mag"] >= c["ref"].abs() * (1 - 1e-12)).all())
+    gates(f"cin2 {grid} k{k} cout{cout}", op_refs.cin2_torch32(c), c["ref"], c["mag"], c["K"])
+
+
+def test_cin2_nan_reaches_its_window_only():
+    B, H, W, k = 2, 9, 33, 7
+    c = op_refs.cin2_case(B, H, W, k, 64, nan_at=(2, 31))
+    nan = c["nan"].view(B, H, W, 64)
+    assert torch.equal(torch.isnan(c["ref"]), c["nan"]) and torch.equal(torch.isnan(c["mag"]), c["nan"])
+    assert not bool(nan[0].any()) and bool(nan[1, :6, 28:33].all()) and int(nan[..., 0].sum()) == 6 * 5
+    clean = op_refs.cin2_case(B, H, W, k, 64)
+    assert torch.equal(c["ref"][~c["nan"]], clean["ref"][~c["nan"]])
+
+
+def test_cin2_mutations_fail_a_gate():
+    c = op_refs.cin2_case(2, 3, 21, 7, 64)
+    gates("cin2", op_refs.cin2_torch32(c), c["ref"], c["mag"], c["K"])
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("x / y weight planes swapped", op_refs.cin2_torch32(c, w=c["w"][:, [1, 0]]), c["ref"], c["mag"], c["K"])
+    wrapped = untall(F.relu(F.conv2d(tall(c["flow"]), c["w"], c["bias"], padding=3)), 2)
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("wraps into the neighbouring image", op_refs._rows_of(wrapped), c["ref"], c["mag"], c["K"])
+
+
+FLOW_DELTA_CPU = [(g, cin, F32) for g in op_refs.FLOW_DELTA_GRIDS4 for cin in (4, 36, 128, 260, 512)] + \
+                 [(g, cin, F32) for g in op_refs.FLOW_DELTA_GRIDS8 for cin in (8, 260)] + [((2, 2, 5), 260, B16), ((4, 1024, 5), 8, B16)]
+
+
+@pytest.mark.parametrize("grid,cin,dtype", FLOW_DELTA_CPU, ids=str)
+def test_flow_delta_reference_and_torch_fp32(grid, cin, dtype):
+    c = op_refs.flow_delta_case(*grid, cin, dtype)
+    B, H, W = grid
+    assert c["x"].dtype == dtype and c["packed"].shape == (9, 2, cin) and c["K"] == 9 * cin + 2
+    want = F.conv2d(op_refs._images_of(c["x"].double(), B, H, W), c["w"].double(), c["bias"].double(), padding=1)
+    same64(c["ref"], want, "flow_delta reference")
+    gates(f"flow_delta {grid} cin{cin}", op_refs.flow_delta_torch32(c), c["ref"], c["mag"], c["K"])
+
+
+def test_flow_delta_nan_corners_reach_their_neighbours_only():
+    for grid in op_refs.FLOW_DELTA_GRIDS4[:2]:
+        B, H, W = grid
+        c = op_refs.flow_delta_case(*grid, 36, F32, nan_corners=True)
+        assert torch.equal(torch.isnan(c["ref"]), c["nan"]) and not bool(c["nan"][0].any())
+        want = torch.zeros(H, W, dtype=torch.bool)
+        for y in range(H):
+            for x in range(W):
+                want[y, x] = min(y, H - 1 - y) <= 1 and min(x, W - 1 - x) <= 1
+        assert torch.equal(c["nan"][1, 0], want) and torch.equal(c["nan"][1, 1], want)
+
+
+def test_flow_delta_mutations_fail_a_gate():
+    c = op_refs.flow_delta_case(2, 2, 5, 260)
+    gates("flow_delta", op_refs.flow_delta_torch32(c), c["ref"], c["mag"], c["K"])
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("channels >= 256 dropped", op_refs.flow_delta_torch32(c, c["x"][:, :256]), c["ref"], c["mag"], c["K"])
+    # the row above y = 0 of image b > 0 read from image b - 1's last row (zeros above image 0)
+    x = op_refs._images_of(c["x"], 2, 2, 5)
+    xp = F.pad(x, (1, 1, 1, 1))
+    xp[1:, :, 0, 1:-1] = x[:-1, :, -1, :]
+    got = F.conv2d(xp, c["w"], c["bias"])
+    assert torch.equal(got[0], op_refs.flow_delta_torch32(c)[0])
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("image b - 1's last row above y = 0", got, c["ref"], c["mag"], c["K"])
+
+
+def up_restated(flow, mask, info, dtype, tap=lambda dy, dx: 3 * dy + dx, swap_s=False, flow_factor=8.0, info_factor=1.0, sub_max=True):
+    """pfk_upsample.h operation by operation in `dtype`: max in tap order, exp(m - max), the sum in tap order, one reciprocal, e * inv;
+    then sum_k w_k v_k in tap order, a multiply and an add.  The keyword arguments are the mutations."""
+    B, _, H, W = flow.shape
+    m = mask.to(dtype).view(B, 9, 8, 8, H, W)
+    if swap_s:
+        m = m.transpose(2, 3)
+    e = torch.exp(m - m.amax(1, keepdim=True)) if sub_max else torch.exp(m)
+    s = e[:, 0]
+    for k in range(1, 9):
+        s = s + e[:, k]
+    w = e * (1.0 / s)[:, None]
+    v = torch.cat([flow_factor * flow.to(dtype), info_factor * info.to(dtype)], 1)
+    vp = F.pad(v, (1, 1, 1, 1))
+    out = torch.zeros(B, v.shape[1], 8, 8, H, W, dtype=dtype)
+    for dy in range(3):
+        for dx in range(3):
+            out = out + w[:, tap(dy, dx)][:, None] * vp[:, :, dy:dy + H, dx:dx + W][:, :, None, None]
+    return out.permute(0, 1, 4, 2, 5, 3).reshape(B, v.shape[1], 8 * H, 8 * W)
+
+
+@pytest.mark.parametrize("scale", op_refs.UP_SCALES)
+@pytest.mark.parametrize("grid", op_refs.UP_GRIDS, ids=str)
+@pytest.mark.parametrize("b16", [False, True])
+def test_convex_forward_reference_and_fp32(grid, scale, b16):
+    c = op_refs.convex_fwd_case(*grid, scale, b16)
+    assert c["mask"].dtype == (B16 if b16 else F32) and c["ref"].shape == (grid[0], 10, 8 * grid[1], 8 * grid[2])
+    same64(c["ref"], up_restated(c["flow"], c["mask"], c["info"], F64), "convex forward reference")
+    assert float(c["k"].min()) >= 30.0 and bool((c["mag"] >= c["ref"].abs() * (1 - 1e-12)).all())
+    what = f"convex forward {grid} x{scale}"
+    _, q = gates(what + " (the kernel's order)", up_restated(c["flow"], c["mask"], c["info"], F32), c["ref"], c["mag"], c["k"], floor=FLOOR)
+    assert q <= 0.5
+    from oracle import raft_oracle as O
+    _, q = gates(what + " (torch.softmax)", O.convex_upsample(c["flow"], c["mask"].float()), c["ref"][:, :2], c["mag"][:, :2], c["k"][:, :2], floor=FLOOR)
+    assert q <= 0.5
+
+
+def test_convex_forward_needs_the_floor():
+    """at saturated logits a weight underflows in fp32 and its term is lost whole: only the absolute floor admits that"""
+    c = op_refs.convex_fwd_case(2, 5, 7, 60.0)
+    with pytest.raises(AssertionError, match="x the bound"):
+        gates("no floor", up_restated(c["flow"], c["mask"], c["info"], F32), c["ref"], c["mag"], c["k"])
+
+
+def test_convex_forward_zero_image_and_infinite_logits():
+    c = op_refs.convex_fwd_case(2, 5, 7, 1.0, False, 0)
+    assert bool((c["ref"][0, :2] == 0).all()) and bool((c["mag"][0, :2] == 0).all()) and bool((c["mag"][1] > 0).all()) and bool((c["mag"][0, 2:] > 0).all())
+    flow, info = c["flow"], c["info"]
+    for keep in (0, 4, 8):
+        m = torch.full((2, 9, 64, 5, 7), float("-inf"))
+        m[:, keep] = c["mask"].view(2, 9, 64, 5, 7)[:, keep]
+        ref, mag, k = op_refs.convex_fwd64(flow, m.view(2, 576, 5, 7), info)
+        dy, dx = keep // 3 - 1, keep % 3 - 1
+        nb = F.pad(torch.cat([8 * flow, info], 1), (1, 1, 1, 1))[:, :, 1 + dy:6 + dy, 1 + dx:8 + dx]
+        assert torch.equal(ref, nb.double().repeat_interleave(8, 2).repeat_interleave(8, 3)), keep
+        assert bool((k == 30).all()) and torch.equal(mag, ref.abs())
+
+
+def test_convex_forward_mutations_fail_a_gate():
+    c = op_refs.convex_fwd_case(2, 5, 7, 1.0)
+    args = (c["flow"], c["mask"], c["info"], F32)
+    gates("convex forward", up_restated(*args), c["ref"], c["mag"], c["k"], floor=FLOOR)
+    for what, kw in (("taps transposed", dict(tap=lambda dy, dx: 3 * dx + dy)), ("sy and sx swapped", dict(swap_s=True)),
+                     ("factor 8 on the info", dict(info_factor=8.0)), ("no factor 8 on the flow", dict(flow_factor=1.0))):
+        with pytest.raises(AssertionError, match="x the bound|relative L2"):
+            gates(what, up_restated(*args, **kw), c["ref"], c["mag"], c["k"], floor=FLOOR)
+    # without the max subtraction expf overflows at scale 60: inf / inf
+    c = op_refs.convex_fwd_case(2, 5, 7, 60.0)
+    gates("convex forward x60", up_restated(c["flow"], c["mask"], c["info"], F32), c["ref"], c["mag"], c["k"], floor=FLOOR)
+    with pytest.raises(AssertionError, match="non-finite|x the bound|relative L2"):
+        gates("no max subtraction", up_restated(c["flow"], c["mask"], c["info"], F32, sub_max=False), c["ref"], c["mag"], c["k"], floor=FLOOR)
+
+
+def upflow8_restated(c, clamp=True):
+    """the kernel thread by thread in fp32, reading c1 - c0 from a flat array with NaN behind its last element (`clamp=False`: i1 =
+    i0 + 1 whatever i0: the read past a row or past the array)"""
+    B, H, W = c["grid"]
+    flat = torch.cat([(c["c1"] - c["c0"]).reshape(-1), torch.full((W + 2,), float("nan"))])
+    y0, y1, ly = op_refs.upflow8_axis(H)
+    x0, x1, lx = op_refs.upflow8_axis(W)
+    if not clamp:
+        y1, x1 = y0 + 1, x0 + 1
+    ly1, lx1 = ly[:, None], lx[None, :]
+    ly0, lx0 = 1.0 - ly1, 1.0 - lx1
+    out = torch.empty(B * 2, 8 * H, 8 * W)
+    for p in range(B * 2):
+        at = lambda yi, xi: flat[p * H * W + yi[:, None] * W + xi[None, :]]        # noqa: E731
+        out[p] = 8.0 * (ly0 * (lx0 * at(y0, x0) + lx1 * at(y0, x1)) + ly1 * (lx0 * at(y1, x0) + lx1 * at(y1, x1)))
+    return out.view(B, 2, 8 * H, 8 * W)
+
+
+@pytest.mark.parametrize("grid", op_refs.UPFLOW_GRIDS, ids=str)
+def test_upflow8_reference_and_torch_fp32(grid):
+    c = op_refs.upflow8_case(*grid)
+    B, H, W = grid
+    # the reference pixel by pixel
+    v = c["c1"].double() - c["c0"].double()
+    (y0, y1, ly), (x0, x1, lx) = op_refs.upflow8_axis(H), op_refs.upflow8_axis(W)
+    want = torch.empty(B, 2, 8 * H, 8 * W, dtype=F64)
+    for yo in range(8 * H):
+        for xo in range(8 * W):
+            a, b = float(ly[yo]), float(lx[xo])
+            want[:, :, yo, xo] = 8 * ((1 - a) * ((1 - b) * v[:, :, y0[yo], x0[xo]] + b * v[:, :, y0[yo], x1[xo]]) +
+                                      a * ((1 - b) * v[:, :, y1[yo], x0[xo]] + b * v[:, :, y1[yo], x1[xo]]))
+    same64(c["ref"], want, "upflow8 reference")
+    assert int(y1.max()) == H - 1 and int(x1.max()) == W - 1 and float(ly.min()) >= 0 and float(lx.max()) < 1
+    _, q = gates(f"upflow8 {grid} (the kernel's order)", upflow8_restated(c), c["ref"], c["mag"], c["K"])
+    assert q <= 0.7
+    torch32 = 8 * F.interpolate(c["c1"] - c["c0"], size=(8 * H, 8 * W), mode="bilinear", align_corners=True)
+    _, q = gates(f"upflow8 {grid} (F.interpolate)", torch32, c["ref"], c["mag"], c["K"])
+    assert q <= 0.7
+
+
+def test_upflow8_mutations_fail_a_gate():
+    c = op_refs.upflow8_case(2, 9, 13)
+    wrong = 8 * F.interpolate(c["c1"] - c["c0"], size=(72, 104), mode="bilinear", align_corners=False)
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("align_corners=False", wrong, c["ref"], c["mag"], c["K"])
+    # i1 unclamped: at the last row / column lambda1 is 0 and the product with the element read past the end still is not
+    for grid in ((2, 9, 13), (1, 1, 5), (2, 6, 1)):
+        c = op_refs.upflow8_case(*grid)
+        with pytest.raises(AssertionError, match="non-finite|x the bound|relative L2"):
+            gates("i1 unclamped", upflow8_restated(c, clamp=False), c["ref"], c["mag"], c["K"])
+
+
+@pytest.mark.parametrize("scale", [1.0, 30.0])
+@pytest.mark.parametrize("cols", op_refs.SOFTMAX_COLS)
+def test_softmax_rows_reference_and_torch_fp32(cols, scale):
+    c = op_refs.softmax_rows_case(cols, scale)
+    want = torch.empty(op_refs.SOFTMAX_ROWS, cols, dtype=F64)
+    for r in range(op_refs.SOFTMAX_ROWS):
+        row = [float(t) for t in c["x"][r]]
+        top = max(row)
+        e = [math.exp(t - top) for t in row]
+        want[r] = torch.tensor([t / math.fsum(e) for t in e], dtype=F64)
+    same64(c["ref"], want, "softmax_rows reference")
+    if cols >= 3:
+        assert int((c["ref"][3] == 0).sum()) == cols - 2 and int(torch.isinf(c["x"]).sum()) == cols - 2
+    _, q = gates(f"softmax_rows {cols} x{scale}", torch.softmax(c["x"], 1), c["ref"], c["mag"], c["k"], floor=FLOOR)
+    assert q <= 0.3
+
+
+def test_softmax_rows_mutation_fails_a_gate():
+    c = op_refs.softmax_rows_case(140, 1.0)
+    wide = F.pad(c["x"], (0, 4))                     # ld = cols + 4, zeros in the pad columns
+    with pytest.raises(AssertionError, match="x the bound|relative L2"):
+        gates("normalised over ld", torch.softmax(wide, 1)[:, :140], c["ref"], c["mag"], c["k"], floor=FLOOR)
