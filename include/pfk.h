@@ -874,6 +874,29 @@ int pfk_xcit_lpi2_f32(const float* u, long long u_ld, const float* gn_weight, co
                       long long x2_ld, const float* ln_weight, const float* ln_bias, float ln_eps, float* t, long long t_ld, void* workspace,
                       long long workspace_bytes, int B, int H, int W, int C, pfk_stream_t stream);
 
+/* ---- K17: CCMR's per-scale context grouping `model.xcit[i]` (ccmr/ccmr.py:191, the same XCiT with separate=False; additions, ABI 7) ----
+ * The rules of K14 hold: fp32, 16-byte aligned rows with ld % 4 == 0, no atomics, arguments validated before the device is touched.
+ *
+ * pfk_xcit_tokens_f32: one pass from the NCHW tensor in[b][c][y][x] (contiguous, C == 128) to the block's token rows, p = (b*H + y)*W + x:
+ *   x0[p][c] = in[b][c][y][x] + pos[y*W + x][c]      (pos [H*W][C] contiguous, 16-byte aligned, may be NULL: nothing is added)
+ *   xh[p][c] = (x0[p][c] - mean_p) * rstd_p           mean over the C channels, then the biased variance about it (two passes over
+ *                                                     the registers, never E[x^2] - mean^2), rstd = 1 / sqrt(var + eps); no affine.
+ * pfk_xcit_tokens_pm_f32: the same from pixel-major input rows in[p][in_ld] (a channels-last tensor), in_ld >= C, in_ld % 4 == 0.
+ * x0_ld, xh_ld >= C.  No output may overlap the other output, `in` or `pos`.  C != 128: PFK_ERR_UNSUPPORTED. */
+int pfk_xcit_tokens_f32(const float* in, const float* pos, float eps, float* x0, long long x0_ld, float* xh, long long xh_ld, int B, int C,
+                        int H, int W, pfk_stream_t stream);
+int pfk_xcit_tokens_pm_f32(const float* in, long long in_ld, const float* pos, float eps, float* x0, long long x0_ld, float* xh,
+                           long long xh_ld, int B, int C, int H, int W, pfk_stream_t stream);
+
+/* pfk_xca_fold_f32: everything of XCA between its value projection and `proj` is linear in the values, so behind the attention map
+ * A [B][heads][dh][dh] (pfk_xca_map_f32) the branch is one affine map per image on LayerNorm(x) without affine:
+ *   M[b] = wp blockdiag(A[b]) wv   [C][C],      c[b] = wp (blockdiag(A[b]) bv) + bp   [C],      C = heads * dh,
+ * with wv [C][C] = W_v diag(ln.weight), bv [C] = W_v ln.bias + b_v, wp [C][C] = diag(gamma) W_proj, bp [C] = gamma * b_proj, all
+ * contiguous and 16-byte aligned.  Each element is one fmaf chain in ascending index order.  heads == 8 and dh == 16, anything else
+ * PFK_ERR_UNSUPPORTED.  M and c overlap nothing. */
+int pfk_xca_fold_f32(const float* A, const float* wv, const float* bv, const float* wp, const float* bp, float* M, float* c, int B,
+                     int heads, int dh, pfk_stream_t stream);
+
 /* ---- K15: the multi-scale GroupNorm encoders (ccmr/extractor.py, ms_raft_plus/extractor.py: `fnet` / `cnet` of CCMR, CCMR+, MS-RAFT+;
  * additions, ABI 7) ----
  * fp32 pixel-major rows x[B*HW][ld] of which only columns [0, C) are read or written; rows 16-byte aligned, every ld % 4 == 0 (ld in

@@ -1210,6 +1210,46 @@ void xcit_lpi2(const Tensor& u, const Tensor& gn_weight, const Tensor& gn_bias, 
            "xcit_lpi2");
 }
 
+// ---- K17: CCMR's per-scale context grouping (pfk_xcit.hip) ----
+// inp [B, 128, H, W] contiguous, pos [H*W, 128] contiguous or None -> x0, xh [B*H*W, 128] views
+void xcit_tokens(const Tensor& in, const c10::optional<Tensor>& pos, double eps, Tensor x0, Tensor xh) {
+  OpScope scope(in);
+  const float* ip = dense("xcit_tokens", in, "inp", F32).f32();
+  TORCH_CHECK(in.dim() == 4, "xcit_tokens: inp must be [B,C,H,W] contiguous");
+  const int64_t B = in.size(0), C = in.size(1), H = in.size(2), W = in.size(3);
+  const Rows a = rows("xcit_tokens", x0, "x0", F32).expect(B * H * W, C);
+  const Rows h = rows("xcit_tokens", xh, "xh", F32).expect(B * H * W, C);
+  const float* pp = dense("xcit_tokens", pos, "pos [H*W, C]", F32, H * W * C).f32();
+  check_ok(pfk_xcit_tokens_f32(ip, pp, (float)eps, a.f32(), a.ld, h.f32(), h.ld, (int)B, (int)C, (int)H, (int)W, cur_stream()), "xcit_tokens");
+}
+
+// the same from the pixel-major rows inp [B*H*W, 128] (a view) of a channels-last tensor
+void xcit_tokens_pm(const Tensor& in, const c10::optional<Tensor>& pos, double eps, Tensor x0, Tensor xh, int64_t B, int64_t H, int64_t W) {
+  OpScope scope(in);
+  const Rows i = rows("xcit_tokens_pm", in, "inp", F32).expect(B * H * W, AtLeast{0});
+  const int64_t C = i.cols;
+  const Rows a = rows("xcit_tokens_pm", x0, "x0", F32).expect(B * H * W, C);
+  const Rows h = rows("xcit_tokens_pm", xh, "xh", F32).expect(B * H * W, C);
+  const float* pp = dense("xcit_tokens_pm", pos, "pos [H*W, C]", F32, H * W * C).f32();
+  check_ok(pfk_xcit_tokens_pm_f32(i.f32(), i.ld, pp, (float)eps, a.f32(), a.ld, h.f32(), h.ld, (int)B, (int)C, (int)H, (int)W, cur_stream()),
+           "xcit_tokens_pm");
+}
+
+// A [B, heads, dh, dh], wv / wp [C, C], bv / bp [C] -> M [B, C, C], c [B, C], all contiguous
+void xca_fold(const Tensor& A, const Tensor& wv, const Tensor& bv, const Tensor& wp, const Tensor& bp, Tensor M, Tensor c) {
+  OpScope scope(A);
+  TORCH_CHECK(A.dim() == 4 && A.size(2) == A.size(3), "xca_fold: A must be [B, heads, dh, dh]");
+  const int64_t B = A.size(0), heads = A.size(1), dh = A.size(2), C = heads * dh;
+  const float* ap = dense("xca_fold", A, "A", F32, B * heads * dh * dh).f32();
+  const float* wvp = dense("xca_fold", wv, "wv [C, C]", F32, C * C).f32();
+  const float* bvp = dense("xca_fold", bv, "bv", F32, C).f32();
+  const float* wpp = dense("xca_fold", wp, "wp [C, C]", F32, C * C).f32();
+  const float* bpp = dense("xca_fold", bp, "bp", F32, C).f32();
+  float* mp = dense("xca_fold", M, "M [B, C, C]", F32, B * C * C).f32();
+  float* cp = dense("xca_fold", c, "c [B, C]", F32, B * C).f32();
+  check_ok(pfk_xca_fold_f32(ap, wvp, bvp, wpp, bpp, mp, cp, (int)B, (int)heads, (int)dh, cur_stream()), "xca_fold");
+}
+
 // ---- K15: the multi-scale GroupNorm encoders (pfk_msenc.hip) ----
 int64_t groupnorm_workspace_bytes(int64_t B, int64_t HW, int64_t C) { return pfk_groupnorm_workspace_bytes((int)B, (int)HW, (int)C); }
 
@@ -1378,6 +1418,9 @@ TORCH_LIBRARY(pfk, m) {
   m.def("xcit_lpi2(Tensor u, Tensor gn_weight, Tensor gn_bias, float gn_eps, int groups, Tensor dw_weight, Tensor dw_bias, Tensor gamma, "
         "Tensor x, Tensor(a!) x2, Tensor? ln_weight, Tensor? ln_bias, float ln_eps, Tensor(b!) t, Tensor(c!) workspace, int B, int H, "
         "int W) -> ()");
+  m.def("xcit_tokens(Tensor inp, Tensor? pos, float eps, Tensor(a!) x0, Tensor(b!) xh) -> ()");
+  m.def("xcit_tokens_pm(Tensor inp, Tensor? pos, float eps, Tensor(a!) x0, Tensor(b!) xh, int B, int H, int W) -> ()");
+  m.def("xca_fold(Tensor A, Tensor wv, Tensor bv, Tensor wp, Tensor bp, Tensor(a!) M, Tensor(b!) c) -> ()");
   m.def("groupnorm_workspace_bytes(int B, int HW, int C) -> int", &groupnorm_workspace_bytes);
   m.def("groupnorm_stats(Tensor x, int B, int HW, int group_size, Tensor gamma, Tensor beta, float eps, Tensor(a!) scale, "
         "Tensor(b!) shift, Tensor(c!) workspace) -> ()");
@@ -1440,6 +1483,9 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("xca_map", &xca_map);
   m.impl("xcit_lpi1", &xcit_lpi1);
   m.impl("xcit_lpi2", &xcit_lpi2);
+  m.impl("xcit_tokens", &xcit_tokens);
+  m.impl("xcit_tokens_pm", &xcit_tokens_pm);
+  m.impl("xca_fold", &xca_fold);
   m.impl("groupnorm_stats", &groupnorm_stats);
   m.impl("affine_apply", &affine_apply);
   m.impl("resize_bilinear_pm", &resize_bilinear_pm);

@@ -8,6 +8,10 @@
 //   pfk_xcit_lpi1_f32        u = GELU(dw3x3(LN3(x)) + b1) and the per-block GroupNorm sums of u (double) into the workspace
 //   pfk_xcit_lpi2_f32        statistics finished in block order, then x2 = x + gamma3 * (dw3x3(GN(u)) + b2) and t = LN2(x2)
 //
+// K17 — the same block with separate=False (CCMR's per-scale context grouping, `model.xcit[i]`) adds the two once-per-scale kernels
+//   pfk_xcit_tokens_f32      NCHW (or pixel-major, _pm) input -> x0 = rows(in) + pos and xh = LayerNorm(x0) without affine, one pass
+//   pfk_xca_fold_f32         the attention branch behind the map as one affine map per image: M_b, c_b
+//
 // The two LPI kernels own a 4 x 8 tile of pixels and all 128 channels, as dwconv_ln_kernel does (pfk_convnext.hip): the 6 x 10 halo is
 // staged in LDS ALREADY NORMALISED, so a tap outside the image contributes exactly 0 (the reference pads the normalised tensor) and no
 // tap crosses into the next image.  Thread (column qx = tid / 32, float4 group g = tid % 32) forms the four pixels of its tile column;
@@ -307,6 +311,138 @@ __global__ __launch_bounds__(XC_THREADS) void lpi2_kernel(const float* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------------ K17: NCHW -> token rows + LN1
+// A block owns TK_PX consecutive pixels n = y * W + x of one image, which are consecutive floats of every channel plane.  Wave w loads
+// the planes w, w + 4, ... (lane = pixel: one 256-byte line per load) into LDS; then a half-wave holds one pixel's 128 channels as a
+// float4 per lane (lane g: channels 4g .. 4g+3), as lpi2_kernel does for LN2.
+// LDS image: channel c = 4g + e of pixel p at  e * TK_PLANE + g * TK_ROW + p,  TK_ROW = TK_PX + 1 (odd).  ds_write_b32 and ds_read_b32
+// bank on (address / 4) % 32 within a 32-lane half.  The store (one channel, 32 consecutive pixels per half) walks 32 consecutive
+// words; the transposed read (one pixel and e, g = 0 .. 31 per half) walks g * 65 = g (mod 32): both conflict-free.  A plain
+// [128][65] image puts g and g + 8 on one bank (4g * 65 = 4g mod 32): 4-way.
+constexpr int TK_PX = 64;
+constexpr int TK_ROW = TK_PX + 1;
+constexpr int TK_PLANE = XC_G4 * TK_ROW;
+
+// x0 = v + pos, xh = LayerNorm(x0) without affine for the pixel this half-wave holds (g = its lane's float4 group); dead pixels (past
+// the image) run the same shuffles on zeros and store nothing
+__device__ __forceinline__ void tokens_finish(f32x4 v, const float* __restrict__ pos, long long n, long long row, int g, bool live, float eps,
+                                              float* __restrict__ x0, long long x0_ld, float* __restrict__ xh, long long xh_ld) {
+  if (live && pos != nullptr) v = v + *reinterpret_cast<const f32x4*>(pos + n * XC_C + 4 * g);
+  if (live) *reinterpret_cast<f32x4*>(x0 + row * x0_ld + 4 * g) = v;
+  const float m = wave_sum<32>((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / XC_C);
+  v -= m;
+  const float rs = 1.0f / sqrtf(wave_sum<32>((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3])) * (1.0f / XC_C) + eps);
+  if (live) *reinterpret_cast<f32x4*>(xh + row * xh_ld + 4 * g) = v * rs;
+}
+
+__global__ __launch_bounds__(XC_THREADS) void tokens_nchw_kernel(const float* __restrict__ in, const float* __restrict__ pos, float eps,
+                                                                 float* __restrict__ x0, long long x0_ld, float* __restrict__ xh,
+                                                                 long long xh_ld, int N) {
+  __shared__ float tile[4 * TK_PLANE];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n0 = blockIdx.x * TK_PX;
+  const long long b = blockIdx.y;
+  const float* src = in + b * XC_C * (long long)N;
+  const bool have = n0 + lane < N;
+#pragma unroll 8
+  for (int c = wv; c < XC_C; c += XC_THREADS / 64)
+    tile[(c & 3) * TK_PLANE + (c >> 2) * TK_ROW + lane] = have ? src[(long long)c * N + n0 + lane] : 0.f;
+  __syncthreads();
+  const int g = tid & 31, hw = tid >> 5;
+  for (int p = hw; p < TK_PX; p += XC_THREADS / 32) {
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = tile[e * TK_PLANE + g * TK_ROW + p];
+    const long long n = n0 + p;
+    tokens_finish(v, pos, n, b * N + n, g, n < N, eps, x0, x0_ld, xh, xh_ld);      // (the same for the 32 lanes of the pixel)
+  }
+}
+
+// the same from pixel-major input rows (a channels-last tensor): no transpose, one pixel per half-wave
+__global__ __launch_bounds__(XC_THREADS) void tokens_pm_kernel(const float* __restrict__ in, long long in_ld, const float* __restrict__ pos,
+                                                               float eps, float* __restrict__ x0, long long x0_ld, float* __restrict__ xh,
+                                                               long long xh_ld, int N) {
+  const int g = threadIdx.x & 31;
+  const long long n = (long long)blockIdx.x * (XC_THREADS / 32) + (threadIdx.x >> 5);
+  const long long row = (long long)blockIdx.y * N + n;
+  const bool live = n < N;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (live) v = *reinterpret_cast<const f32x4*>(in + row * in_ld + 4 * g);
+  tokens_finish(v, pos, n, row, g, live, eps, x0, x0_ld, xh, xh_ld);
+}
+
+// ------------------------------------------------------------------------------------------------ K17: the folded attention branch
+// M_b = Wp blockdiag(A_b) Wv and c_b = Wp blockdiag(A_b) bv + bp for Wp = diag(gamma1) W_proj, bp = gamma1 * b_proj and the
+// LN1-folded value projection Wv, bv.  Block (column tile, image): T = blockdiag(A_b) Wv[:, tile] (16 products per element), then
+// M_b[:, tile] = Wp T with Wp staged 32 columns at a time.  Every sum is one fmaf chain in ascending index order.
+constexpr int FD_NC = 16;                     // columns of M per block
+constexpr int FD_KC = 32;                     // columns of Wp per stage
+constexpr int FD_WLD = FD_KC + 4;             // row stride of the staged Wp: 16-byte rows, the 4 rows of a wave 36 words apart
+constexpr int FD_R = XC_C * FD_NC / XC_THREADS;      // outputs per thread: rows mg + 16 r
+static_assert(XC_THREADS / FD_NC * FD_R == XC_C, "the thread grid covers the 128 rows");
+
+__global__ __launch_bounds__(XC_THREADS) void xca_fold_kernel(const float* __restrict__ A, const float* __restrict__ wv,
+                                                              const float* __restrict__ bv, const float* __restrict__ wp,
+                                                              const float* __restrict__ bp, float* __restrict__ M, float* __restrict__ c) {
+  __shared__ float a_s[XCA_GRAM];
+  __shared__ float wv_s[XC_C * FD_NC];
+  __shared__ float t_s[XC_C * FD_NC];
+  __shared__ __attribute__((aligned(16))) float wp_s[XC_C * FD_WLD];
+  __shared__ float tb_s[XC_C];
+  const int tid = threadIdx.x;
+  const int n0 = blockIdx.x * FD_NC;
+  const long long b = blockIdx.y;
+  const float* Ab = A + b * XCA_GRAM;
+  for (int e = tid; e < XCA_GRAM; e += XC_THREADS) a_s[e] = Ab[e];
+  for (int e = tid; e < XC_C * FD_NC; e += XC_THREADS) wv_s[e] = wv[(e / FD_NC) * XC_C + n0 + (e % FD_NC)];
+  __syncthreads();
+  const int n = tid % FD_NC, mg = tid / FD_NC;
+#pragma unroll
+  for (int r = 0; r < FD_R; ++r) {
+    const int k = mg + (XC_THREADS / FD_NC) * r, h = k / XC_DH;
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < XC_DH; ++j) t = fmaf(a_s[k * XC_DH + j], wv_s[(h * XC_DH + j) * FD_NC + n], t);
+    t_s[k * FD_NC + n] = t;
+  }
+  if (blockIdx.x == 0 && tid < XC_C) {
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < XC_DH; ++j) t = fmaf(a_s[tid * XC_DH + j], bv[(tid / XC_DH) * XC_DH + j], t);
+    tb_s[tid] = t;
+  }
+  float acc[FD_R];
+#pragma unroll
+  for (int r = 0; r < FD_R; ++r) acc[r] = 0.f;
+  float cacc = 0.f;
+  for (int k0 = 0; k0 < XC_C; k0 += FD_KC) {
+    __syncthreads();                                           // t_s / tb_s are written; the previous stage's reads are done
+    for (int e = tid; e < XC_C * (FD_KC / 4); e += XC_THREADS) {
+      const int m = e / (FD_KC / 4), q = e % (FD_KC / 4);
+      *reinterpret_cast<f32x4*>(wp_s + m * FD_WLD + 4 * q) = *reinterpret_cast<const f32x4*>(wp + m * XC_C + k0 + 4 * q);
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int kk = 0; kk < FD_KC; kk += 4) {
+      float tv[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tv[e] = t_s[(k0 + kk + e) * FD_NC + n];
+#pragma unroll
+      for (int r = 0; r < FD_R; ++r) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(wp_s + (mg + (XC_THREADS / FD_NC) * r) * FD_WLD + kk);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[r] = fmaf(w[e], tv[e], acc[r]);
+      }
+    }
+    if (blockIdx.x == 0 && tid < XC_C)
+      for (int kk = 0; kk < FD_KC; ++kk) cacc = fmaf(wp_s[tid * FD_WLD + kk], tb_s[k0 + kk], cacc);
+  }
+  float* Mb = M + b * XC_C * XC_C;
+#pragma unroll
+  for (int r = 0; r < FD_R; ++r) Mb[(mg + (XC_THREADS / FD_NC) * r) * XC_C + n0 + n] = acc[r];
+  if (blockIdx.x == 0 && tid < XC_C) c[b * XC_C + tid] = cacc + bp[tid];
+}
+
 // [b, e) byte ranges of M rows of C floats with row stride ld
 struct row_range { const char *b, *e; };
 row_range rows_of(const float* p, long long ld, long long M, int C) {
@@ -436,6 +572,65 @@ int pfk_xcit_lpi2_f32(const float* u, long long u_ld, const float* gn_weight, co
   dim3 grid((unsigned)((W + LP_TX - 1) / LP_TX), (unsigned)((H + LP_TY - 1) / LP_TY), (unsigned)B);
   hipLaunchKernelGGL(lpi2_kernel, grid, dim3(XC_THREADS), 0, st, u, u_ld, stats, gn_weight, gn_bias, dw_weight, dw_bias, gamma, x, x_ld,
                      x2, x2_ld, ln_weight, ln_bias, ln_eps, t, t_ld, H, W);
+  return pfk_launch_status();
+}
+
+// the checks the two token entries share (`in_bytes`: the extent of the input as the entry addresses it)
+static int tokens_check(const float* in, long long in_bytes, const float* pos, float eps, float* x0, long long x0_ld, float* xh,
+                        long long xh_ld, int B, int C, int H, int W) {
+  if (!in || !x0 || !xh || B <= 0 || H <= 0 || W <= 0 || C < 4 || !(eps >= 0.f)) return PFK_ERR_BAD_ARG;
+  if (x0_ld < C || xh_ld < C) return PFK_ERR_BAD_ARG;
+  if (C & 3) return PFK_ERR_ALIGNMENT;
+  const long long N = (long long)H * W;
+  if (C != XC_C || B > 65535 || !pfk_fits32((long long)B * N) || N >= 0x7fffffffLL - TK_PX) return PFK_ERR_UNSUPPORTED;
+  if ((x0_ld & 3) || (xh_ld & 3) || !pfk_aligned16(x0) || !pfk_aligned16(xh) || (pos && !pfk_aligned16(pos))) return PFK_ERR_ALIGNMENT;
+  const row_range a = rows_of(x0, x0_ld, B * N, C), h = rows_of(xh, xh_ld, B * N, C);
+  if (overlap(a, h) || overlap(a, in, in_bytes) || overlap(h, in, in_bytes)) return PFK_ERR_BAD_ARG;
+  if (pos && (overlap(a, pos, N * C * 4) || overlap(h, pos, N * C * 4))) return PFK_ERR_BAD_ARG;
+  return PFK_OK;
+}
+
+int pfk_xcit_tokens_f32(const float* in, const float* pos, float eps, float* x0, long long x0_ld, float* xh, long long xh_ld, int B, int C,
+                        int H, int W, pfk_stream_t stream) {
+  const int st = tokens_check(in, (long long)B * C * H * W * 4, pos, eps, x0, x0_ld, xh, xh_ld, B, C, H, W);
+  if (st != PFK_OK) return st;
+  const long long N = (long long)H * W;
+  dim3 grid((unsigned)((N + TK_PX - 1) / TK_PX), (unsigned)B);
+  hipLaunchKernelGGL(tokens_nchw_kernel, grid, dim3(XC_THREADS), 0, static_cast<hipStream_t>(stream), in, pos, eps, x0, x0_ld, xh, xh_ld,
+                     (int)N);
+  return pfk_launch_status();
+}
+
+int pfk_xcit_tokens_pm_f32(const float* in, long long in_ld, const float* pos, float eps, float* x0, long long x0_ld, float* xh,
+                           long long xh_ld, int B, int C, int H, int W, pfk_stream_t stream) {
+  if (in && C > 0 && in_ld < C) return PFK_ERR_BAD_ARG;
+  const long long rows = (long long)B * H * W;
+  const int st = tokens_check(in, rows > 0 ? ((rows - 1) * in_ld + C) * 4 : 0, pos, eps, x0, x0_ld, xh, xh_ld, B, C, H, W);
+  if (st != PFK_OK) return st;
+  if ((in_ld & 3) || !pfk_aligned16(in)) return PFK_ERR_ALIGNMENT;
+  const long long N = (long long)H * W;
+  dim3 grid((unsigned)((N + XC_THREADS / 32 - 1) / (XC_THREADS / 32)), (unsigned)B);
+  hipLaunchKernelGGL(tokens_pm_kernel, grid, dim3(XC_THREADS), 0, static_cast<hipStream_t>(stream), in, in_ld, pos, eps, x0, x0_ld, xh,
+                     xh_ld, (int)N);
+  return pfk_launch_status();
+}
+
+int pfk_xca_fold_f32(const float* A, const float* wv, const float* bv, const float* wp, const float* bp, float* M, float* c, int B,
+                     int heads, int dh, pfk_stream_t stream) {
+  if (!A || !wv || !bv || !wp || !bp || !M || !c || B <= 0 || heads <= 0 || dh <= 0) return PFK_ERR_BAD_ARG;
+  if (heads != XC_HEADS || dh != XC_DH || B > 65535) return PFK_ERR_UNSUPPORTED;
+  if (!pfk_aligned16(A) || !pfk_aligned16(wv) || !pfk_aligned16(bv) || !pfk_aligned16(wp) || !pfk_aligned16(bp) || !pfk_aligned16(M) ||
+      !pfk_aligned16(c))
+    return PFK_ERR_ALIGNMENT;
+  const long long m_bytes = (long long)B * XC_C * XC_C * 4, c_bytes = (long long)B * XC_C * 4, w_bytes = (long long)XC_C * XC_C * 4;
+  const row_range mr = {(const char*)M, (const char*)M + m_bytes}, cr = {(const char*)c, (const char*)c + c_bytes};
+  if (overlap(mr, c, c_bytes)) return PFK_ERR_BAD_ARG;
+  for (const row_range& o : {mr, cr})
+    if (overlap(o, A, (long long)B * XCA_GRAM * 4) || overlap(o, wv, w_bytes) || overlap(o, wp, w_bytes) || overlap(o, bv, XC_C * 4) ||
+        overlap(o, bp, XC_C * 4))
+      return PFK_ERR_BAD_ARG;
+  hipLaunchKernelGGL(xca_fold_kernel, dim3(XC_C / FD_NC, (unsigned)B), dim3(XC_THREADS), 0, static_cast<hipStream_t>(stream), A, wv, bv, wp,
+                     bp, M, c);
   return pfk_launch_status();
 }
 

@@ -48,7 +48,9 @@ from .ms_encoder import register_multiscale_encoder  # noqa: F401  (next to the 
 from .sea_encoder import PfkInitConv, PfkResNetEncoder, match_init_conv, match_resnet_fpn
 from .sea_update import HEAD_SHAPES, PfkSeaRaftUpdateBlock, _SeaHeadSeam, _UpsampleDataSeam, sea_block_shapes
 from .update import PfkUpdateBlock, UpdateSpec, basic_spec, ccmr_spec, gma_spec, ms_raft_plus_spec, small_spec
+from .xcit import PfkXcitContext, match_xcit_context, served_context
 from .xcit import register_xcit_aggregator  # noqa: F401  (the hook for further aggregator classes, next to the other register_* calls)
+from .xcit import register_xcit_context  # noqa: F401  (likewise for the context grouping modules `model.xcit[i]`)
 
 _ORIG = "_pfk_original_get_corr_block"
 
@@ -869,12 +871,26 @@ def _dead_work_skip_for(model: torch.nn.Module, warn: bool = True, skip_dead: bo
     return _DeadWorkSkip(model, skip_dead=skip_dead, fuse=fuse)
 
 
+def _set_ccmr_context(model: torch.nn.Module, on: bool) -> None:
+    """`model.xcit[i]` -> `PfkXcitContext` (all elements or none), or back to the reference modules"""
+    mods = getattr(model, "xcit", None)
+    if not isinstance(mods, torch.nn.ModuleList) or len(mods) == 0:
+        return
+    for i, m in enumerate(mods):
+        if isinstance(m, PfkXcitContext) and not on:
+            mods[i] = m._ref[0]
+    if on and all(isinstance(m, PfkXcitContext) or (served_context(m) and match_xcit_context(m)) for m in mods):
+        for i, m in enumerate(mods):
+            if not isinstance(m, PfkXcitContext):
+                mods[i] = PfkXcitContext(m)
+
+
 def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = True,
                conv_precision: str = "fp32", encoders: bool = True, upsample: bool = True,
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
                sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False,
-               multiscale_encoders: bool = False, multiscale_upsample: bool = False) -> torch.nn.Module:
+               multiscale_encoders: bool = False, multiscale_upsample: bool = False, ccmr_context: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -947,7 +963,15 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     on the model (train mode, grad mode, a bf16 model or a changed ``iters`` are honoured); any inconsistency in the loop's call
     pattern turns it off for the rest of that forward.  The intermediate `up_mask` / `flow_up` tensors are not valid in eval while it
     is active.  Counters: ``model.update_block._skip.block_calls / masks_skipped / scratch_answers``.  A second call with another
-    value switches it; `restore` removes the hook and the state."""
+    value switches it; `restore` removes the hook and the state.
+    ``ccmr_context`` (default False): on a CCMR or CCMR+ model, replace the per-scale context grouping modules ``model.xcit[i]``
+    (ccmr/ccmr.py:191: the XCiT block with one input) by `xcit.PfkXcitContext`: the NCHW input to token rows and
+    LayerNorm in one kernel, the attention branch folded into one GEMM per image by `pfk_xca_fold_f32`, then the aggregator's tail;
+    ten launches per call.  Installed only when EVERY element of ``model.xcit`` is a served class (`register_xcit_context`) that passes
+    `xcit.match_xcit_context`.  A wrapper serves eval-mode calls outside grad mode and autocast on an fp32 GPU tensor [B, 128, H, W]
+    (NCHW-contiguous or dense channels-last) with fp32 parameters (``engine_calls``); every other call runs the reference module
+    (``fallback_calls``).  With it and the three options above every module a CCMR forward calls has a kernel path, and the forward
+    repeats its bits.  ``conv_precision`` is not read.  A second call with another value switches it; `restore` undoes it."""
     check_precision(train_precision, PRECISIONS, "train_precision")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
@@ -1008,9 +1032,10 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
             desc = describe_multiscale_encoder(enc)
             if desc is not None:
                 setattr(model, attr, PfkMultiScaleEncoder(enc, desc, _MS_CLASSES[(type(enc).__module__, type(enc).__name__)]))
+    _set_ccmr_context(model, bool(ccmr_context))
     if upsample and callable(getattr(model, "upsample_flow", None)) and not isinstance(model.__dict__.get("upsample_flow"), _UpsampleSeam):
         _shadow(model, upsample_flow=_UpsampleSeam(model.upsample_flow))
-    seam5 = model.__dict__.get("upsample_flow")
+    seam5 =model.__dict__.get("upsample_flow")
     if isinstance(seam5, _UpsampleSeam):
         seam5.multiscale = bool(multiscale_upsample)
     # a model of a multi-scale family (a subclass included: `_multiscale_skip_for` says why it is refused) takes the per-scale skip
@@ -1055,4 +1080,5 @@ def restore(model: torch.nn.Module) -> torch.nn.Module:
     for name, child in list(model._modules.items()):      # update_block, fnet / cnet, SEA-RAFT's heads
         if isinstance(child, WrappedModule):
             setattr(model, name, child._ref[0])
+    _set_ccmr_context(model, False)
     return model
