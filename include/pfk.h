@@ -35,7 +35,11 @@
  *   pfk_altcorr_forward_f32  ptlflow/utils/external/alt_cuda_corr/correlation_kernel.cu:258-285 (alt_cuda_corr.forward)
  *   pfk_corr_lookup_bwd_f32 / pfk_corr_volume_bwd_f32 / pfk_convex_upsample_bwd_f32
  *                         what torch.autograd runs for corr.py:29-64 and raft.py:112-123 in a training step (train.py;
- *                         gradients reach fmap1 / fmap2 only, `coords` is detached at raft.py:171)
+ *                         gradients reach fmap1 / fmap2; RAFT detaches `coords` at raft.py:171, so these three give it none)
+ *   pfk_corr_lookup_coords_bwd_f32  the sampling grid's gradient of the same grid_sample backward (raft/utils.py:67-75), for the
+ *                         loops whose `coords1` carries one: ms_raft_plus.py:197-202 / ccmr.py:194-204 rebuild it from
+ *                         `upsample_flow(..., up_mask, scale=2)` after the detach at the first iteration of a finer scale
+ *   pfk_convex_upsample2_bwd_f32  what torch.autograd runs for ccmr.py:128-139 / ms_raft_plus.py:133-144 with scale = 2
  *   pfk_convex_upsample_info_bwd_pm_f32  what torch.autograd runs for sea_raft.py:147-163 in a training step (train_sea.py)
  * The native plug-in precedent in the reference is alt_cuda_corr
  * (ptlflow/utils/external/alt_cuda_corr/correlation.cpp:23-54: pybind forward/backward on raw
@@ -173,6 +177,33 @@ typedef struct {
 } pfk_lookup_bwd_desc;
 int pfk_corr_lookup_bwd_f32(const pfk_lookup_bwd_desc* d, pfk_stream_t stream);
 
+/* ---- coordinate gradient of K3 (training of the multi-scale loops; added within ABI 7: an addition only) -------------------
+ * levels[l]: the level-l volume the forward read, ROW-MAJOR fp32, one [lvl_h][lvl_w] map per source pixel at row stride lvl_ld[l]
+ * floats (>= lvl_h*lvl_w; the training path's pyramid: lvl_ld = lvl_h*lvl_w).  grad_out [B*N][grad_out_ld] as above.
+ * grad_coords [B][2][h][w] (x then y) is WRITTEN, not accumulated:
+ *   grad_x[p] = sum over levels l and taps (i, j) of grad_out[p][l][i][j] * 2^-l * [(v10 - v00)(1 - wy) + (v11 - v01) wy]
+ *   grad_y[p] = ...                                                      * 2^-l * [(v01 - v00)(1 - wx) + (v11 - v10) wx]
+ * with v.. the four values around the tap's sample point (x/2^l + i - r, y/2^l + j - r) — v10 one column to the right, v01 one row
+ * down, 0 outside the map — and wx, wy its fractional parts, floor and weights taken from the forward's fp32 round trip: what
+ * grid_sample's backward gives the grid, times the chain of corr.py:45-52.  Non-finite coordinates, coordinates too large for the
+ * map and every tap of a 1-pixel-high or -wide level contribute exactly 0 (as to grad_levels above): a finite grad_out never yields
+ * a NaN.  One wave per source pixel, one fixed-order wave sum per component: deterministic, no atomics.  Status codes as
+ * pfk_corr_lookup_bwd_f32 (+ BAD_ARG for a null level or grad_coords). */
+typedef struct {
+  const float* levels[PFK_MAX_LEVELS];
+  int lvl_h[PFK_MAX_LEVELS];
+  int lvl_w[PFK_MAX_LEVELS];
+  long long lvl_ld[PFK_MAX_LEVELS];
+  int num_levels;
+  int radius;      /* 1..4 */
+  int B, h, w;
+  const float* coords;    /* [B][2][h][w], the coordinates the forward was called with */
+  const float* grad_out;
+  int grad_out_ld;
+  float* grad_coords;     /* [B][2][h][w] */
+} pfk_lookup_coords_bwd_desc;
+int pfk_corr_lookup_coords_bwd_f32(const pfk_lookup_coords_bwd_desc* d, pfk_stream_t stream);
+
 /* ---- backward of K1 for one batch element and one pyramid level (training) -----------------------------------
  * The level-l volume is C = scale * F1 . F2_l^T with F2_l the (avg-pooled / bilinearly halved) target feature map, so
  *   df1[i][d]  = (accumulate_df1 ? df1[i][d] : 0) + scale * sum_j dC[i][j] * f2[j][d]         i < N1   (fp32 MFMA GEMM)
@@ -194,6 +225,19 @@ long long pfk_convex_upsample_bwd_workspace_bytes(int B, int H, int W);
 int pfk_convex_upsample_bwd_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, const float* grad_out,
                                 float* grad_mask, int grad_mask_ld, float* grad_flow, void* workspace, long long workspace_bytes,
                                 int B, int H, int W, pfk_stream_t stream);
+
+/* ---- backward of pfk_convex_upsample2_f32 (`upsample_flow(flow, mask, scale=2)`; added within ABI 7: an addition only) -------
+ * flow and mask as pfk_convex_upsample2_f32 reads them (flow_ld == 0: NCHW, else pixel-major rows; 36 logits per mask row);
+ * grad_out [B][2][2H][2W] -> grad_mask pixel-major [M][grad_mask_ld] (36 columns written, grad_mask_ld >= 36) and grad_flow, NCHW
+ * [B][2][H][W] (grad_flow_ld == 0) or pixel-major rows grad_flow[p*grad_flow_ld + 0..1] (grad_flow_ld >= 2).  8-byte aligned mask,
+ * grad_mask and grad_out with even row strides take 8-byte accesses, anything else 4-byte ones, with the same bits.
+ * workspace: pfk_convex_upsample2_bwd_workspace_bytes(B, H, W) bytes.  Deterministic (no atomics, a fixed summation order).
+ * PFK_ERR_BAD_ARG: a null pointer, a non-positive size, mask_ld or grad_mask_ld < 36, a row stride of 1 or a negative one, a
+ * workspace that is too small; PFK_ERR_UNSUPPORTED: more pixels than a launch grid holds. */
+long long pfk_convex_upsample2_bwd_workspace_bytes(int B, int H, int W);
+int pfk_convex_upsample2_bwd_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, const float* grad_out,
+                                 float* grad_mask, int grad_mask_ld, float* grad_flow, int grad_flow_ld, void* workspace,
+                                 long long workspace_bytes, int B, int H, int W, pfk_stream_t stream);
 
 /* ---- backward of pfk_convex_upsample_info_pm_f32 (SEARAFT.upsample_data, sea_raft/sea_raft.py:147-163), fp32, pixel-major -----
  * flow_pm / info_pm / mask as the forward reads them (columns 0..1, 0..n_info-1, 0..575 of their rows; 0 <= n_info <= 8, info_pm

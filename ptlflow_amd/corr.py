@@ -58,7 +58,8 @@ class _PyramidToken(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fmap1, fmap2, block):
         block._build(fmap1.detach(), fmap2.detach())
-        block._zero_grad_levels()
+        # (frozen maps under `coords_grad`: no lookup ever scatters into the level gradients, so none are allocated)
+        block._zero_grad_levels(allocate=fmap1.requires_grad or fmap2.requires_grad)
         # weak: block -> _token -> grad_fn (this ctx) -> block would be a reference cycle that keeps a step's N x N pyramid and
         # its equally large gradient buffers alive until the cyclic GC runs.  Every lookup node holds the block strongly, and
         # this backward only runs when a lookup's gradient reaches the token, so the block is alive whenever it is needed.
@@ -80,7 +81,10 @@ class _PyramidToken(torch.autograd.Function):
 
 class _LookupFn(torch.autograd.Function):
     """One pyramid lookup -> pixel-major [B*h*w, C]; backward adds d(out) into the block's level-gradient buffers through the
-    forward's bilinear weights (`pfk_corr_lookup_bwd_f32`).  `coords` is detached by every caller (raft.py:171)."""
+    forward's bilinear weights (`pfk_corr_lookup_bwd_f32`).  RAFT, GMA and SEA-RAFT detach `coords` before every lookup
+    (raft.py:171), so it gets no gradient there.  The multi-scale loops rebuild it from `upsample_flow(..., up_mask, scale=2)` AFTER
+    the detach at the first iteration of every scale but the coarsest (ms_raft_plus.py:197-202, ccmr.py:194-204): a block built with
+    ``coords_grad=True`` returns grid_sample's gradient of the sampling grid for such a call (`pfk_corr_lookup_coords_bwd_f32`)."""
 
     @staticmethod
     def forward(ctx, token, coords, block):
@@ -88,6 +92,7 @@ class _LookupFn(torch.autograd.Function):
         c = coords.detach().float().contiguous()
         _ops().corr_lookup(block._levels, c, block.radius, out)
         ctx.block, ctx.coords = block, c
+        ctx.coords_dtype = coords.dtype
         return out
 
     @staticmethod
@@ -96,19 +101,29 @@ class _LookupFn(torch.autograd.Function):
         g = g.float()
         if g.dim() != 2 or g.stride(1) != 1:
             g = g.reshape(-1, b.channels).contiguous()
-        _ops().corr_lookup_bwd(b.grad_levels, b._lvl_h, b._lvl_w, ctx.coords, b.radius, g)
-        return torch.zeros(1, device=g.device, dtype=torch.float32), None, None
+        if ctx.needs_input_grad[0]:
+            _ops().corr_lookup_bwd(b.grad_levels, b._lvl_h, b._lvl_w, ctx.coords, b.radius, g)
+        gc = None
+        if b.coords_grad and ctx.needs_input_grad[1]:
+            gc = torch.empty_like(ctx.coords)
+            _ops().corr_lookup_coords_bwd(b._levels, ctx.coords, b.radius, g, gc)
+            gc = gc.to(ctx.coords_dtype)
+        return (torch.zeros(1, device=g.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None), gc, None
 
 
 class CorrBlock:
-    """All-pairs correlation pyramid + radius-r lookup on the GPU.  ``coords`` is detached by every caller (raft.py:171), so
-    no coordinate gradient exists; when a feature map requires grad (training) the block records an autograd graph whose
-    backward runs on libpfk too (`_PyramidToken` / `_LookupFn`) and delivers the gradients of ``fmap1`` / ``fmap2``."""
+    """All-pairs correlation pyramid + radius-r lookup on the GPU.  When a feature map requires grad (training) the block records
+    an autograd graph whose backward runs on libpfk too (`_PyramidToken` / `_LookupFn`) and delivers the gradients of ``fmap1`` /
+    ``fmap2``.  RAFT-style loops detach ``coords`` before every lookup (raft.py:171) and no coordinate gradient exists; the
+    multi-scale loops hand in coordinates that carry one (`_LookupFn`), which ``coords_grad=True`` serves and the default drops."""
 
     def __init__(self, fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, radius: int = 4,
                  pyramid: str = "avgpool", volume_dtype: Optional[torch.dtype] = None, channels_last: bool = True,
-                 layout: Optional[str] = None):
-        """``layout``: ``"blocked"`` (4 x 8-element tiles, module docstring; the default without a gradient graph) or ``"rowmajor"``
+                 layout: Optional[str] = None, coords_grad: bool = False):
+        """``coords_grad``: a lookup of the training graph whose ``coords`` require grad also returns their gradient
+        (`pfk_corr_lookup_coords_bwd_f32`; ``False``: none, as ever — what `accelerate(model, multiscale_train=True)` switches).
+
+        ``layout``: ``"blocked"`` (4 x 8-element tiles, module docstring; the default without a gradient graph) or ``"rowmajor"``
         (the reference's ``[B*N, h_l, w_l]`` maps; what the training graph's backward kernels address, forced there).
 
         ``channels_last``: the tensor a lookup returns is a channels-last VIEW of the pixel-major buffer (what this package's
@@ -132,6 +147,7 @@ class CorrBlock:
         self.num_levels = num_levels
         self.radius = radius
         self.channels_last = channels_last
+        self.coords_grad = bool(coords_grad)
         self.pyramid_mode = pyramid
         if pyramid not in ("avgpool", "bilinear_f2"):
             raise ValueError(f"unknown pyramid mode {pyramid!r}")
@@ -146,7 +162,8 @@ class CorrBlock:
         self._shape = None
         self.grad_levels: List[torch.Tensor] = []
         self._token: Optional[torch.Tensor] = None
-        needs_graph = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
+        # (`coords_grad`: the coordinates may carry a gradient when the maps carry none — frozen encoders — so grad mode alone decides)
+        needs_graph = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad or self.coords_grad)
         if volume_dtype is None:
             volume_dtype = torch.bfloat16 if fmap1.dtype == torch.bfloat16 and not needs_graph else torch.float32
         if volume_dtype not in (torch.float32, torch.bfloat16):
@@ -259,11 +276,16 @@ class CorrBlock:
         return self._rowmajor_cache
 
     # ------------------------------------------------------------------ training (autograd) side
-    def _zero_grad_levels(self) -> None:
+    def _zero_grad_levels(self, allocate: bool = True) -> None:
         """Gradient buffers of the pyramid levels: one [h_l][w_l] map per source pixel at a row stride padded to a multiple
-        of 4 floats (so a buffer is directly the A operand / dY operand of the two backward GEMMs); zeroed once per step."""
+        of 4 floats (so a buffer is directly the A operand / dY operand of the two backward GEMMs); zeroed once per step.
+        ``allocate=False``: the level sizes only (a graph that delivers a coordinate gradient and no feature-map gradient)."""
         M = self.B * self.h * self.w
         sizes = list(self._lvl_hw)
+        self._lvl_h, self._lvl_w = [s[0] for s in sizes], [s[1] for s in sizes]
+        if not allocate:
+            self.grad_levels = []
+            return
         if len(self.grad_levels) != len(sizes) or any(g.shape[0] != M or g.shape[1] != (hl * wl + 3) // 4 * 4
                                                       for g, (hl, wl) in zip(self.grad_levels, sizes)):
             dev = self._levels[0].device
@@ -412,9 +434,10 @@ class AlternateCorrBlock:
 
 def get_corr_block(fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: int = 4, radius: int = 4,
                    alternate_corr: bool = False, pyramid: str = "avgpool", volume_dtype: Optional[torch.dtype] = None,
-                   channels_last: bool = True):
-    """Same signature as ptlflow/models/raft/corr.py:104-118; ``alternate_corr=True`` selects the on-demand block."""
+                   channels_last: bool = True, coords_grad: bool = False):
+    """Same signature as ptlflow/models/raft/corr.py:104-118; ``alternate_corr=True`` selects the on-demand block (which has no
+    coordinate gradient: the reference calls `alt_cuda_corr.forward` outside autograd)."""
     if alternate_corr:
         return AlternateCorrBlock(fmap1, fmap2, num_levels=num_levels, radius=radius)
     return CorrBlock(fmap1, fmap2, num_levels=num_levels, radius=radius, pyramid=pyramid, volume_dtype=volume_dtype,
-                     channels_last=channels_last)
+                     channels_last=channels_last, coords_grad=coords_grad)

@@ -1,10 +1,12 @@
 // Backward kernels of the correlation path — what torch.autograd executes for
 // ptlflow/models/raft/corr.py:29-64 (grid_sample backward, avg_pool2d backward, matmul backward)
-// in a training step (train.py, raft-train1-chairs.yaml).  `coords` arrives detached (raft.py:171), so the only gradients on
-// the correlation path are those of the two feature maps.
+// in a training step (train.py, raft-train1-chairs.yaml).  RAFT, GMA and SEA-RAFT hand the lookup detached `coords` (raft.py:171), so
+// the only gradients on their correlation path are those of the two feature maps; the multi-scale loops (ms_raft_plus.py:197-202,
+// ccmr.py:194-204) hand in coordinates that carry one, which the coordinate-gradient kernel below serves.
 //
 //   lookup backward   d(out)[p][l][i][j]  ->  += into the pixel's own level-l gradient map, through the same four bilinear
 //                     weights and tap indices the forward used (pfk_lookup.h: shared arithmetic, -ffp-contract=off);
+//   lookup coordinate gradient   d(out)[p][l][i][j] -> d(coords)[p]: grid_sample's grid gradient through the same floor and weights;
 //   volume backward   level l's volume is  C_l = s * F1 . pool^l(F2)^T  (pooling the target dims of the volume == correlating
 //                     with the pooled feature map: both are linear and touch the same index sets), so
 //                       dF1      += s * dC_l . F2_l            -> pfk_conv2d_f32 as a plain K-contiguous GEMM (K = target pixels)
@@ -146,6 +148,80 @@ __global__ __launch_bounds__(256) void lookup_bwd_kernel(const LookupBwdArgs a) 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Coordinate gradient of the lookup: what grid_sample's backward hands the sampling grid, through corr.py:45-52 (coords / 2^l + the
+// window offset, normalise, un-normalise: the chain's factors cancel but for 2^-l).  The multi-scale loops need it — they rebuild
+// `coords1` from `upsample_flow(..., up_mask, scale=2)` AFTER the detach at the first iteration of every scale but the coarsest
+// (ms_raft_plus.py:197-202, ccmr.py:194-204).  One wave per source pixel, four per block; the L (2r+1)^2 taps are one flat list over
+// the lanes (162 taps: 3 passes, 324: 6).  A tap derives its sample point through pfk_lookup.h's round trip exactly as the forward,
+//     d out / dx = 2^-l [(v10 - v00)(1 - wy) + (v11 - v01) wy],   d out / dy = 2^-l [(v01 - v00)(1 - wx) + (v11 - v10) wx]
+// with values outside the map 0, multiplies by d(out) and adds into two lane sums; one butterfly per component ends it (fixed order,
+// no atomics).  The four values of a tap are read straight from the pixel's map through the cache: the window of a level is at most
+// 12 x 12 floats that the wave's lanes touch in the same pass, and unlike the forward there is one multiply-add per value, not a
+// whole output element — staging the window in LDS first would cost the same loads plus a wave-wide wait.
+// A tap whose round-trip coordinate is not finite or beyond 1e9 (NaN / inf coordinates, a 1-pixel-high or -wide level: x / 0 in the
+// round trip; pfk_lookup.h's `safe_base` bound) contributes exactly 0.
+// ------------------------------------------------------------------------------------------------------------------
+struct LookupCoordsBwdArgs {
+  const float* lv[PFK_MAX_LEVELS];
+  int lh[PFK_MAX_LEVELS];
+  int lw[PFK_MAX_LEVELS];
+  long long lld[PFK_MAX_LEVELS];
+  int L, B, h, w;
+  const float* coords;
+  const float* gout;
+  int gout_ld;
+  float* gcoords;
+};
+
+template <int R>
+__global__ __launch_bounds__(256) void lookup_coords_bwd_kernel(const LookupCoordsBwdArgs a) {
+  constexpr int n = 2 * R + 1, nn = n * n;
+  const int lane = threadIdx.x & 63;
+  const unsigned M = (unsigned)a.B * (unsigned)a.h * (unsigned)a.w;   // < 2^31 (checked by the host)
+  const unsigned p = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (p >= M) return;                                                  // whole waves leave
+  const unsigned N = (unsigned)(a.h * a.w);
+  const unsigned b = p / N, pix = p - b * N;
+  const float* cb = a.coords + (size_t)b * 2 * N + pix;
+  const float cx0 = cb[0], cy0 = cb[N];
+  const float* grow = a.gout + (size_t)p * (unsigned)a.gout_ld;
+  float ax = 0.f, ay = 0.f;
+  const int taps = a.L * nn;
+  for (int t = lane; t < taps; t += 64) {
+    const int l = t / nn, k = t - l * nn;
+    const int i = k / n, j = k - i * n;
+    const int Hl = a.lh[l], Wl = a.lw[l];
+    const float inv = 1.0f / (float)(1 << l);
+    const float cx = cx0 * inv, cy = cy0 * inv;
+    const float ix = roundtrip(cx + (float)(i - R), (float)(Wl - 1), (float)(Wl - 1) * 0.5f);
+    const float iy = roundtrip(cy + (float)(j - R), (float)(Hl - 1), (float)(Hl - 1) * 0.5f);
+    if (!(fabsf(ix) < 1.0e9f && fabsf(iy) < 1.0e9f)) continue;      // NaN compares false
+    const float x0 = floorf(ix), y0 = floorf(iy);
+    const float wx = ix - x0, wy = iy - y0;
+    const int xi = (int)x0, yi = (int)y0;
+    const float* map = a.lv[l] + (size_t)p * (size_t)a.lld[l];
+    const bool in_x0 = (unsigned)xi < (unsigned)Wl, in_x1 = (unsigned)(xi + 1) < (unsigned)Wl;
+    const bool in_y0 = (unsigned)yi < (unsigned)Hl, in_y1 = (unsigned)(yi + 1) < (unsigned)Hl;
+    const float v00 = (in_y0 && in_x0) ? map[yi * Wl + xi] : 0.f;
+    const float v10 = (in_y0 && in_x1) ? map[yi * Wl + xi + 1] : 0.f;
+    const float v01 = (in_y1 && in_x0) ? map[(yi + 1) * Wl + xi] : 0.f;
+    const float v11 = (in_y1 && in_x1) ? map[(yi + 1) * Wl + xi + 1] : 0.f;
+    const float dx = (v10 - v00) * (1.0f - wy) + (v11 - v01) * wy;
+    const float dy = (v01 - v00) * (1.0f - wx) + (v11 - v10) * wx;
+    const float g = grow[t] * inv;
+    ax += g * dx;
+    ay += g * dy;
+  }
+  ax = wave_sum(ax);
+  ay = wave_sum(ay);
+  if (lane == 0) {
+    float* dst = a.gcoords + (size_t)b * 2 * N + pix;
+    dst[0] = ax;
+    dst[N] = ay;
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, long long n, float s) {
   const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= n) return;
@@ -184,6 +260,35 @@ int pfk_corr_lookup_bwd_f32(const pfk_lookup_bwd_desc* d, pfk_stream_t stream) {
     case 2: hipLaunchKernelGGL((lookup_bwd_kernel<BPIX, 2>), grid, block, 0, st, a); break;
     case 3: hipLaunchKernelGGL((lookup_bwd_kernel<BPIX, 3>), grid, block, 0, st, a); break;
     default: hipLaunchKernelGGL((lookup_bwd_kernel<BPIX, 4>), grid, block, 0, st, a); break;
+  }
+  return pfk_launch_status();
+}
+
+int pfk_corr_lookup_coords_bwd_f32(const pfk_lookup_coords_bwd_desc* d, pfk_stream_t stream) {
+  if (!d || !d->coords || !d->grad_out || !d->grad_coords) return PFK_ERR_BAD_ARG;
+  if (d->num_levels < 1 || d->num_levels > PFK_MAX_LEVELS) return PFK_ERR_BAD_ARG;
+  if (d->radius < 1 || d->radius > 4) return PFK_ERR_UNSUPPORTED;
+  if (d->B <= 0 || d->h <= 0 || d->w <= 0) return PFK_ERR_BAD_ARG;
+  const int n = 2 * d->radius + 1;
+  if (d->grad_out_ld < d->num_levels * n * n) return PFK_ERR_BAD_ARG;
+  LookupCoordsBwdArgs a{};
+  for (int l = 0; l < d->num_levels; ++l) {
+    if (!d->levels[l] || d->lvl_h[l] <= 0 || d->lvl_w[l] <= 0) return PFK_ERR_BAD_ARG;
+    if (d->lvl_ld[l] < (long long)d->lvl_h[l] * d->lvl_w[l]) return PFK_ERR_BAD_ARG;
+    if (!pfk_fits_int((long long)d->lvl_h[l] * d->lvl_w[l])) return PFK_ERR_UNSUPPORTED;
+    a.lv[l] = d->levels[l]; a.lh[l] = d->lvl_h[l]; a.lw[l] = d->lvl_w[l]; a.lld[l] = d->lvl_ld[l];
+  }
+  a.L = d->num_levels; a.B = d->B; a.h = d->h; a.w = d->w;
+  a.coords = d->coords; a.gout = d->grad_out; a.gout_ld = d->grad_out_ld; a.gcoords = d->grad_coords;
+  if (!pfk_fits32((long long)d->B * d->h * d->w)) return PFK_ERR_UNSUPPORTED;
+  const long long blocks = ((long long)d->B * d->h * d->w + 3) / 4;
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (d->radius) {
+    case 1: hipLaunchKernelGGL(lookup_coords_bwd_kernel<1>, grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL(lookup_coords_bwd_kernel<2>, grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL(lookup_coords_bwd_kernel<3>, grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL(lookup_coords_bwd_kernel<4>, grid, block, 0, st, a); break;
   }
   return pfk_launch_status();
 }

@@ -755,6 +755,30 @@ void corr_lookup_bwd(at::TensorList grad_levels, at::IntArrayRef lvl_h, at::IntA
   check_ok(pfk_corr_lookup_bwd_f32(&d, cur_stream()), op);
 }
 
+// coordinate gradient of corr_lookup: levels [B*N, h_l, w_l] row-major fp32 maps (the training pyramid), grad_coords [B, 2, h, w] written
+void corr_lookup_coords_bwd(at::TensorList levels, const Tensor& coords, int64_t radius, const Tensor& grad_out, Tensor grad_coords) {
+  OpScope scope(coords);
+  const char* op = "corr_lookup_coords_bwd";
+  TORCH_CHECK(levels.size() >= 1 && levels.size() <= PFK_MAX_LEVELS, op, ": 1..8 levels");
+  pfk_lookup_coords_bwd_desc d{};
+  d.coords = dense(op, coords, "coords", F32).f32();
+  TORCH_CHECK(coords.dim() == 4 && coords.size(1) == 2, op, ": coords [B,2,h,w] contiguous");
+  d.B = coords.size(0); d.h = coords.size(2); d.w = coords.size(3);
+  const int64_t M = (int64_t)d.B * d.h * d.w;
+  for (size_t l = 0; l < levels.size(); ++l) {
+    const Tensor& t = levels[l];
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == M && t.size(1) >= 1 && t.size(2) >= 1, op, ": every level must be a [B*h*w, h_l, w_l] map");
+    d.levels[l] = dense(op, t, "level", F32).f32();
+    d.lvl_h[l] = t.size(1); d.lvl_w[l] = t.size(2); d.lvl_ld[l] = t.size(1) * t.size(2);
+  }
+  d.num_levels = levels.size(); d.radius = radius;
+  const int n = 2 * radius + 1;
+  const Rows g = rows(op, grad_out, "grad_out", F32).expect(M, AtLeast{(int64_t)d.num_levels * n * n});
+  d.grad_out = g.f32(); d.grad_out_ld = g.ld;
+  d.grad_coords = dense(op, grad_coords, "grad_coords [B,2,h,w]", F32, 2 * M).f32();
+  check_ok(pfk_corr_lookup_coords_bwd_f32(&d, cur_stream()), op);
+}
+
 // backward of corr_volume for one pyramid level, all batch elements: dC [B,N1,ldc] (columns >= N2 zero), f1 [B,N1,D],
 // f2cm [B,D,ld2cm] channel-major zero-padded -> df1 [B,N1,D] (+= when accumulate), df2 [B,ldc,Dpad]
 void corr_volume_bwd(const Tensor& dC, int64_t N2, const Tensor& f1, const Tensor& f2cm, double scale, Tensor df1, bool accumulate,
@@ -797,6 +821,34 @@ void convex_upsample_bwd(const Tensor& flow, const Tensor& mask, const Tensor& g
   const long long need = pfk_convex_upsample_bwd_workspace_bytes(g.B, g.H, g.W);
   const auto ws = byte_workspace(need, mask);
   check_ok(pfk_convex_upsample_bwd_f32(fp, flow_ld, m.f32(), m.ld, g.ptr, gm.f32(), gm.ld, gf, ws.second, need, g.B, g.H, g.W, cur_stream()), op);
+}
+
+// backward of convex_upsample2(_pm): flow and grad_flow NCHW [B,2,H,W] contiguous or pixel-major [M, >=2] / [M, 2] rows, each on its own;
+// mask / grad_mask [M, 36] row views, grad_out [B, 2, 2H, 2W]
+void convex_upsample2_bwd(const Tensor& flow, const Tensor& mask, const Tensor& grad_out, Tensor grad_mask, Tensor grad_flow) {
+  OpScope scope(mask);
+  const char* op = "convex_upsample2_bwd";
+  const Up8 g = up8(op, grad_out, "grad_out", 2);
+  const int64_t M = g.rows();
+  const float* fp; int flow_ld = 0;
+  if (flow.dim() == 2) { const Rows f = rows(op, flow, "flow", F32).expect(M, AtLeast{2}); fp = f.f32(); flow_ld = f.ld; }
+  else {
+    fp = dense(op, flow, "flow", F32, 2 * M).f32();
+    TORCH_CHECK(flow.dim() == 4 && flow.size(0) == g.B && flow.size(1) == 2 && flow.size(2) == g.H && flow.size(3) == g.W, op,
+                ": flow [B,2,H,W] contiguous or pixel-major [M,2+]");
+  }
+  float* gf; int gflow_ld = 0;
+  if (grad_flow.dim() == 2) { const Rows r = rows(op, grad_flow, "grad_flow", F32).expect(M, 2); gf = r.f32(); gflow_ld = r.ld; }
+  else {
+    gf = dense(op, grad_flow, "grad_flow [B,2,H,W]", F32, 2 * M).f32();
+    TORCH_CHECK(grad_flow.dim() == 4 && grad_flow.size(0) == g.B && grad_flow.size(1) == 2 && grad_flow.size(2) == g.H &&
+                grad_flow.size(3) == g.W, op, ": grad_flow [B,2,H,W] contiguous or pixel-major [M,2]");
+  }
+  const Rows m = rows(op, mask, "mask", F32).expect(M, 36), gm = rows(op, grad_mask, "grad_mask", F32).expect(M, 36);
+  const long long need = pfk_convex_upsample2_bwd_workspace_bytes(g.B, g.H, g.W);
+  const auto ws = byte_workspace(need, mask);
+  check_ok(pfk_convex_upsample2_bwd_f32(fp, flow_ld, m.f32(), m.ld, g.ptr, gm.f32(), gm.ld, gf, gflow_ld, ws.second, need, g.B, g.H, g.W,
+                                        cur_stream()), op);
 }
 
 // backward of convex_upsample_info_pm (fp32 mask): row views as the forward's, grad_flow_up [B, 2, 8H, 8W], grad_info_up
@@ -1408,6 +1460,8 @@ TORCH_LIBRARY(pfk, m) {
   m.def("corr_lookup_bwd(Tensor(a!)[] grad_levels, int[] lvl_h, int[] lvl_w, Tensor coords, int radius, Tensor grad_out) -> ()");
   m.def("corr_volume_bwd(Tensor dC, int N2, Tensor f1, Tensor f2cm, float scale, Tensor(a!) df1, bool accumulate, Tensor(b!) df2) -> ()");
   m.def("convex_upsample_bwd(Tensor flow, Tensor mask, Tensor grad_out, Tensor(a!) grad_mask, Tensor(b!) grad_flow) -> ()");
+  m.def("convex_upsample2_bwd(Tensor flow, Tensor mask, Tensor grad_out, Tensor(a!) grad_mask, Tensor(b!) grad_flow) -> ()");
+  m.def("corr_lookup_coords_bwd(Tensor[] levels, Tensor coords, int radius, Tensor grad_out, Tensor(a!) grad_coords) -> ()");
   m.def("convex_upsample_info_bwd(Tensor flow_pm, Tensor info_pm, Tensor mask, Tensor grad_flow_up, Tensor? grad_info_up, "
         "Tensor(a!) grad_mask, Tensor(b!) grad_flow_pm, Tensor(c!) grad_info_pm) -> ()");
   m.def("layernorm_rows(Tensor inp, Tensor? weight, Tensor? bias, float eps, Tensor(a!) out) -> ()");
@@ -1478,6 +1532,8 @@ TORCH_LIBRARY_IMPL(pfk, CUDA, m) {
   m.impl("corr_lookup_bwd", &corr_lookup_bwd);
   m.impl("corr_volume_bwd", &corr_volume_bwd);
   m.impl("convex_upsample_bwd", &convex_upsample_bwd);
+  m.impl("convex_upsample2_bwd", &convex_upsample2_bwd);
+  m.impl("corr_lookup_coords_bwd", &corr_lookup_coords_bwd);
   m.impl("convex_upsample_info_bwd", &convex_upsample_info_bwd);
   m.impl("layernorm_rows", &layernorm_rows);
   m.impl("xca_map", &xca_map);

@@ -1,5 +1,5 @@
-// Convex upsampling, unfused: RAFT.upsample_flow (raft/raft.py:112-123) and SEARAFT.upsample_data (sea_raft.py:147-163), forward and
-// backward.  The arithmetic of a (coarse pixel, sub-pixel) is pfk_upsample.h's; this file is the lane layouts around it, the
+// Convex upsampling, unfused: RAFT.upsample_flow (raft/raft.py:112-123), its scale = 2 form of the multi-scale loops
+// (ccmr/ccmr.py:128-139) and SEARAFT.upsample_data (sea_raft.py:147-163), forward and backward.  The arithmetic of a (coarse pixel, sub-pixel) is pfk_upsample.h's; this file is the lane layouts around it, the
 // cross-lane reductions of the backward and the C entry points.  Bandwidth-bound VALU kernels, compiled with -ffp-contract=off.
 // (The fused forms — mask head conv2 + softmax + upsampling, K13 / K13b — are in pfk_gemm.hip / pfk_gemm_b16.hip.)
 #include "pfk_launch.h"
@@ -268,6 +268,91 @@ __global__ __launch_bounds__(256) void convex_upsample_info_bwd_kernel(const flo
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Backward of the upsampling by 2, in the forward's lane layout (convex_upsample2_kernel): a lane owns one (coarse pixel, sy) and
+// holds the sub-pixels sx = 0, 1 of nine taps — nine 8-byte pieces of the pixel's mask row, nine 8-byte pieces of its mask-gradient
+// row, and 8 bytes of each channel of the upsampled gradient.  Per sub-pixel, as the x8 kernel above:
+//     dw_k = g_x * vx_k + g_y * vy_k;   dmask[p][k*4 + sy*2 + sx] = w_k * (dw_k - sum_j w_j dw_j)
+//     dflow[c][nbr_k(p)] += 2 * sum over the pixel's four sub-pixels of w_k * g_c
+// The four sub-pixels: two in the lane, the other two in the lane 32 away.  ONE v_permlane32_swap per tap finishes both channels:
+// with vdst = the x sum and src = the y sum, lanes 0..31 end up holding (own x, upper x) and lanes 32..63 (lower y, own y), so the
+// lower half adds and stores channel 0 of part[p][k][.] and the upper half channel 1 — nine swaps per lane where two butterflies
+// through ds_bpermute (`__shfl_xor(v, 32)`) would take eighteen LDS-crossbar operations.  The gather kernel below (C = 2) adds the
+// <= 9 contributions of each flow pixel in tap order: no atomics, a fixed order, the same bits every run.
+// Both lanes of a pixel leave together at `p >= M`, so a swap never reads a lane that is gone.
+// VEC: mask rows, mask-gradient rows and the upsampled gradient 8-byte aligned (even row strides); otherwise 4-byte accesses.
+// ------------------------------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void convex_upsample2_bwd_kernel(const float* __restrict__ flow, int flow_ld,
+                                                                   const float* __restrict__ mask, int mask_ld,
+                                                                   const float* __restrict__ gout, float* __restrict__ gmask,
+                                                                   int gmask_ld, float* __restrict__ part, long long M, int H,
+                                                                   int W) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // blockDim.x is a multiple of 64
+  const int lane = threadIdx.x & 63, sy = lane >> 5;
+  const long long p = (t >> 6) * 32 + (lane & 31);
+  if (p >= M) return;
+  const UpPixel px = up_pixel(p, H, W);
+  const long long img = px.b * ((long long)H * W);
+  const float* mrow = mask + p * mask_ld + sy * 2;
+  float m[2][9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    if constexpr (VEC) {
+      const f32x2 w = *reinterpret_cast<const f32x2*>(mrow + k * 4);
+      m[0][k] = w[0];
+      m[1][k] = w[1];
+    } else {
+      m[0][k] = mrow[k * 4];
+      m[1][k] = mrow[k * 4 + 1];
+    }
+  }
+  up_softmax9(m[0]);
+  up_softmax9(m[1]);
+  const long long HW4 = (long long)H * W * 4;
+  const long long at = up_out_offset<2>(px.y, px.x, sy, 0, W);
+  float g[2][2];      // [channel][sx]
+#pragma unroll
+  for (int ch = 0; ch < 2; ++ch) {
+    const float* src = gout + (px.b * 2 + ch) * HW4 + at;
+    if constexpr (VEC) {
+      const f32x2 w = *reinterpret_cast<const f32x2*>(src);
+      g[ch][0] = w[0];
+      g[ch][1] = w[1];
+    } else {
+      g[ch][0] = src[0];
+      g[ch][1] = src[1];
+    }
+  }
+  float dw[2][9], dot[2] = {0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    float v[2];
+    up_tap<0, 2>(k, flow, flow_ld, nullptr, 0, 0, img, px.y, px.x, H, W, v);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      dw[s][k] = g[0][s] * v[0] + g[1][s] * v[1];
+      dot[s] += m[s][k] * dw[s][k];
+    }
+  }
+  float* grow = gmask + p * gmask_ld + sy * 2;
+  float* prow = part + p * 18 + sy;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float d0 = m[0][k] * (dw[0][k] - dot[0]), d1 = m[1][k] * (dw[1][k] - dot[1]);
+    if constexpr (VEC) {
+      *reinterpret_cast<f32x2*>(grow + k * 4) = f32x2{d0, d1};
+    } else {
+      grow[k * 4] = d0;
+      grow[k * 4 + 1] = d1;
+    }
+    const float cxv = m[0][k] * g[0][0] + m[1][k] * g[0][1];
+    const float cyv = m[0][k] * g[1][0] + m[1][k] * g[1][1];
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(cxv), __float_as_uint(cyv), false, false);
+    prow[k * 2] = 2.0f * (__uint_as_float(r[0]) + __uint_as_float(r[1]));      // sy = 0: channel x, sy = 1: channel y
+  }
+}
+
 // grad[p][c] = sum_k part[pixel (y - ky + 1, x - kx + 1)][k][c], k ascending (the pixels whose k-th neighbour is p); one thread per
 // (pixel, channel).  c < 2 goes to the flow gradient — NCHW [B][2][H][W] (gflow_ld == 0: RAFT) or pixel-major rows — the rest to the
 // info rows.
@@ -296,7 +381,7 @@ __global__ __launch_bounds__(256) void convex_upsample_bwd_gather_kernel(const f
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
-// What all ten entry points check first: the pointers every one of them needs, the grid, the mask row stride (at least the
+// What all eleven entry points check first: the pointers every one of them needs, the grid, the mask row stride (at least the
 // `mask_channels` = 9 S^2 logits of a pixel) and the flow layout (pixel-major rows of at least two floats; 0 = NCHW where the entry
 // point reads it).
 bool up_args_ok(std::initializer_list<const void*> required, int B, int H, int W, int mask_ld, int flow_ld, bool nchw_ok = false,
@@ -409,6 +494,33 @@ int pfk_convex_upsample_bwd_f32(const float* flow, int flow_ld, const float* mas
   hipLaunchKernelGGL(convex_upsample_bwd_kernel, dim3(blocks), dim3(256), 0, st, flow, flow_ld, mask, mask_ld, grad_out, grad_mask,
                      grad_mask_ld, part, M, H, W);
   hipLaunchKernelGGL(convex_upsample_bwd_gather_kernel, dim3(gather_blocks), dim3(256), 0, st, part, 2, grad_flow, 0, nullptr, 0, M, H, W);
+  return pfk_launch_status();
+}
+
+long long pfk_convex_upsample2_bwd_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return (long long)B * H * W * 18 * (long long)sizeof(float);
+}
+
+int pfk_convex_upsample2_bwd_f32(const float* flow, int flow_ld, const float* mask, int mask_ld, const float* grad_out,
+                                 float* grad_mask, int grad_mask_ld, float* grad_flow, int grad_flow_ld, void* workspace,
+                                 long long workspace_bytes, int B, int H, int W, pfk_stream_t stream) {
+  if (!up_args_ok({flow, mask, grad_out, grad_mask, grad_flow, workspace}, B, H, W, mask_ld, flow_ld, true, 36)) return PFK_ERR_BAD_ARG;
+  if (grad_mask_ld < 36 || !(grad_flow_ld >= 2 || grad_flow_ld == 0)) return PFK_ERR_BAD_ARG;
+  if (workspace_bytes < pfk_convex_upsample2_bwd_workspace_bytes(B, H, W)) return PFK_ERR_BAD_ARG;
+  const long long M = (long long)B * H * W;
+  unsigned blocks, gather_blocks;
+  if (!up_grid(M, 32, blocks) || !up_grid(M * 2, 256, gather_blocks)) return PFK_ERR_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const bool vec = pfk_aligned<8>(mask) && (mask_ld & 1) == 0 && pfk_aligned<8>(grad_mask) && (grad_mask_ld & 1) == 0 &&
+                   pfk_aligned<8>(grad_out);
+  // as the forward: one wave of 32 pixels per block (these grids are a few thousand pixels; 64 against 256 threads measured
+  // within the spread there, and small blocks spread a small grid over more CUs)
+  hipLaunchKernelGGL(vec ? convex_upsample2_bwd_kernel<true> : convex_upsample2_bwd_kernel<false>, dim3(blocks), dim3(64), 0, st, flow,
+                     flow_ld, mask, mask_ld, grad_out, grad_mask, grad_mask_ld, part, M, H, W);
+  hipLaunchKernelGGL(convex_upsample_bwd_gather_kernel, dim3(gather_blocks), dim3(256), 0, st, part, 2, grad_flow, grad_flow_ld, nullptr, 0,
+                     M, H, W);
   return pfk_launch_status();
 }
 

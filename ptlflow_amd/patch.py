@@ -318,23 +318,28 @@ def _supported_envelope(fmap1: torch.Tensor, fmap2: torch.Tensor, num_levels: in
 
 # the accelerated model instance whose forward is running publishes its lookup layout here (None: no such forward on this context)
 _LAYOUT: "contextvars.ContextVar[Optional[bool]]" = contextvars.ContextVar("pfk_lookup_channels_last", default=None)
+# ... and whether its lookups return a coordinate gradient (`accelerate(model, multiscale_train=True)`)
+_COORDS_GRAD: "contextvars.ContextVar[bool]" = contextvars.ContextVar("pfk_lookup_coords_grad", default=False)
 _LAYOUT_HOOKS = "_pfk_layout_hooks"
 
 
-def _bracket_forward_with_layout(model: torch.nn.Module, channels_last: bool) -> None:
-    """forward pre-hook / hook pair on the INSTANCE: sets `_LAYOUT` for the duration of its forward (re-entrant: a token stack)."""
+def _bracket_forward_with_layout(model: torch.nn.Module, channels_last: bool, coords_grad: bool = False) -> None:
+    """forward pre-hook / hook pair on the INSTANCE: sets `_LAYOUT` and `_COORDS_GRAD` for the duration of its forward (re-entrant:
+    a token stack)."""
     state = model.__dict__.get(_LAYOUT_HOOKS)
     if state is not None:
-        state["channels_last"] = channels_last
+        state["channels_last"], state["coords_grad"] = channels_last, coords_grad
         return
-    state = {"channels_last": channels_last, "tokens": []}
+    state = {"channels_last": channels_last, "coords_grad": coords_grad, "tokens": []}
 
     def pre(_m, _args, _kwargs=None):
-        state["tokens"].append(_LAYOUT.set(state["channels_last"]))
+        state["tokens"].append((_LAYOUT.set(state["channels_last"]), _COORDS_GRAD.set(state["coords_grad"])))
 
     def post(_m, _args, _out):
         if state["tokens"]:
-            _LAYOUT.reset(state["tokens"].pop())
+            layout, coords_grad = state["tokens"].pop()
+            _COORDS_GRAD.reset(coords_grad)
+            _LAYOUT.reset(layout)
 
     state["handles"] = (model.register_forward_pre_hook(pre), model.register_forward_hook(post, always_call=True))
     model.__dict__[_LAYOUT_HOOKS] = state
@@ -354,7 +359,8 @@ def _make_corr_hook(module_name: str, original):
             cl = _LAYOUT.get()
             if cl is None:
                 cl = get_corr_block.channels_last
-            return _pfk_get_corr_block(fmap1, fmap2, num_levels=num_levels, radius=radius, pyramid=pyramid, channels_last=cl)
+            return _pfk_get_corr_block(fmap1, fmap2, num_levels=num_levels, radius=radius, pyramid=pyramid, channels_last=cl,
+                                       coords_grad=_COORDS_GRAD.get())
         return original(fmap1=fmap1, fmap2=fmap2, num_levels=num_levels, radius=radius, alternate_corr=alternate_corr, **kw)
 
     get_corr_block.pyramid = pyramid
@@ -378,7 +384,12 @@ class _UpsampleSeam(ProbedMethodSeam):
     `(flow, mask, 2)` of the multi-scale families (ccmr/ccmr.py:196,213, ms_raft_plus/ms_raft_plus.py:199,209) with
     `pfk_convex_upsample2_f32` — CUDA fp32 tensors, a 36-channel mask, an eval-mode model, no gradient graph, no autocast, behind a
     probe of its own (`ok2`: `original(flow, mask, scale=2)` against the kernel; separate from `ok`).  Every other scale, extra
-    arguments, CPU tensors and gradient graphs go to the model's method as before.  Served calls count in `calls`."""
+    arguments, CPU tensors and gradient graphs go to the model's method as before.  Served calls count in `calls`.
+
+    `multiscale_train` (`accelerate(model, multiscale_train=True)`, independent of `multiscale`): a `scale=2` call of either shape that
+    carries a gradient graph — CUDA fp32 tensors, a 36-channel mask, grad mode on with something requiring grad, no autocast, the
+    `ok2` probe passed — runs `train.convex_upsample2` (`pfk_convex_upsample2_f32` forward, `pfk_convex_upsample2_bwd_f32` backward)
+    and is counted in `train_calls`."""
 
     refusal = "ptlflow_amd: this model's upsample_flow is not RAFT's 8x convex upsampling; seam B5 keeps the model's own method"
 
@@ -388,6 +399,7 @@ class _UpsampleSeam(ProbedMethodSeam):
         self.train_upsample = False    # `accelerate(train_upsample=True)`: gradient-graph calls run `train.convex_upsample`
         self.train_calls = 0           # calls served by it
         self.multiscale = False        # `accelerate(multiscale_upsample=True)`: `scale=2` calls run `pfk_convex_upsample2_f32`
+        self.multiscale_train = False  # `accelerate(multiscale_train=True)`: `scale=2` calls with a gradient graph run `train.convex_upsample2`
         self.ok2 = None                # the x2 probe's verdict (None = not probed yet)
 
     @staticmethod
@@ -457,10 +469,27 @@ class _UpsampleSeam(ProbedMethodSeam):
         mask = torch.randn(2, 9 * scale * scale, 5, 7, generator=g).to(device)
         return (flow, mask), (flow, mask)
 
+    def _train2(self, flow: torch.Tensor, mask: torch.Tensor):
+        """the x2 upsampling of a call that carries a gradient graph (`multiscale_train`), or None"""
+        shapes = flow.dim() == 4 and flow.shape[1] == 2 and mask.dim() == 4 and mask.shape[1] == 36 \
+            and flow.shape[0] == mask.shape[0] and flow.shape[2:] == mask.shape[2:]
+        if not shapes or not carries_grad((flow, mask)) or not self._verdict("ok2", flow.device, 2):
+            return None
+        from .train import convex_upsample2
+        self.train_calls += 1
+        rows = pixel_rows(mask, torch.float32)      # PfkUpdateBlock's training mask: a view
+        if rows is None:
+            rows = mask.permute(0, 2, 3, 1).reshape(-1, 36)
+        return convex_upsample2(flow, rows)
+
     def __call__(self, *args, **kwargs):
-        if self.multiscale:
+        if self.multiscale or self.multiscale_train:
             fm = self._scale2_call(args, kwargs)
-            out = self._serve2(*fm) if fm is not None else None
+            out = None
+            if fm is not None and self.multiscale_train:
+                out = self._train2(*fm)
+            if out is None and fm is not None and self.multiscale:
+                out = self._serve2(*fm)
             if out is not None:
                 return out
         # Other families give `upsample_flow` more arguments — ccmr.py:213 / ms_raft_plus.py:199 pass `scale=`, dip a `rate`,
@@ -890,7 +919,8 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
                skip_dead_upsample: Optional[bool] = None, fuse_mask_upsample: Optional[bool] = None,
                sea_raft_update=False, sea_raft_encoders=False, train_precision: str = "fp32",
                sea_raft_train: bool = False, train_upsample: bool = False, ccmr_aggregator: bool = False,
-               multiscale_encoders: bool = False, multiscale_upsample: bool = False, ccmr_context: bool = False) -> torch.nn.Module:
+               multiscale_encoders: bool = False, multiscale_upsample: bool = False, ccmr_context: bool = False,
+               multiscale_train: bool = False) -> torch.nn.Module:
     """Patch seams B1/B3/B4 (+ B5, the model's `upsample_flow` method) of a ptlflow model instance in place and return it.
 
     ``conv_precision``: "fp32" (default, the parity path) or a split-bf16 mode of the convolutions
@@ -971,8 +1001,24 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     `xcit.match_xcit_context`.  A wrapper serves eval-mode calls outside grad mode and autocast on an fp32 GPU tensor [B, 128, H, W]
     (NCHW-contiguous or dense channels-last) with fp32 parameters (``engine_calls``); every other call runs the reference module
     (``fallback_calls``).  With it and the three options above every module a CCMR forward calls has a kernel path, and the forward
-    repeats its bits.  ``conv_precision`` is not read.  A second call with another value switches it; `restore` undoes it."""
+    repeats its bits.  ``conv_precision`` is not read.  A second call with another value switches it; `restore` undoes it.
+    ``multiscale_train`` (default False; fp32 only: with ``train_precision="bf16"`` it raises ValueError): a training step of a
+    CCMR, CCMR+ or MS-RAFT+ refinement loop on the kernels.  (1) The update block's native training path also takes
+    these models' blocks — a 36-channel mask, and CCMR's external aggregate slot, whose per-scale `aggregator` module stays torch
+    autograd on the NCHW view of the motion features — for fp32 CUDA calls outside autocast with ``conv_precision="fp32"``; served
+    calls count in ``update_block.train_calls``.  (2) Seam B5 serves `upsample_flow(flow, mask, scale=2)` / `(flow, mask, 2)` calls
+    that carry a gradient graph with `train.convex_upsample2` (backward: `pfk_convex_upsample2_bwd_f32`), behind the ``ok2`` probe,
+    counted in the seam's ``train_calls``.  (3) The lookups of seam B1 return the gradient of their coordinates
+    (`pfk_corr_lookup_coords_bwd_f32`): these loops rebuild `coords1` from `upsample_flow(..., up_mask, scale=2)` after the detach
+    at the first iteration of every scale but the coarsest, so the previous scale's last mask receives a gradient through the
+    lookup — which an accelerated model drops (returns zero for) while the option is off.  Under the option a lookup block built
+    in grad mode keeps the row-major fp32 pyramid whether or not the feature maps require grad.  The on-demand (`alternate_corr`)
+    block has no coordinate gradient, as in the reference.  Independent of ``multiscale_upsample``, whose skip is never armed in
+    grad mode.  Off: every such call takes the reference's autograd, as before.  A second call with another value switches it;
+    `restore` undoes it."""
     check_precision(train_precision, PRECISIONS, "train_precision")
+    if multiscale_train and train_precision != "fp32":
+        raise ValueError(f"multiscale_train=True is fp32 only (its training kernels are fp32), got train_precision={train_precision!r}")
     sea_precision = _sea_precision(sea_raft_update)
     if sea_raft_train and sea_precision != "fp32":
         raise ValueError(f"sea_raft_train=True needs sea_raft_update=True or 'fp32' (the training path sits behind the fp32 seams; "
@@ -998,6 +1044,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
             model.update_block = PfkUpdateBlock(model.update_block, spec, conv_precision)
     if update_block and isinstance(getattr(model, "update_block", None), PfkUpdateBlock):
         model.update_block.train_precision = train_precision
+        model.update_block.multiscale_train = bool(multiscale_train)
         model.update_block.set_ccmr_aggregator(ccmr_aggregator)
     sea = sea_precision is not None and _install_sea_raft(model, sea_precision)
     if sea:
@@ -1011,7 +1058,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     hook = getattr(mod, "get_corr_block", None)
     if corr and hasattr(mod, _ORIG) and hasattr(hook, "channels_last"):      # (default for callers that are not a model's forward)
         hook.channels_last = sea or isinstance(getattr(model, "update_block", None), PfkUpdateBlock)
-        _bracket_forward_with_layout(model, hook.channels_last)
+        _bracket_forward_with_layout(model, hook.channels_last, bool(multiscale_train))
     cb = getattr(model, "corr_block", None)
     if corr and isinstance(cb, torch.nn.Module) and (type(cb).__module__, type(cb).__name__) in _BILINEAR_VOLUMES \
             and not isinstance(cb.__dict__.get(_VOLUME_SEAM), _LearnableVolumeSeam):
@@ -1038,6 +1085,7 @@ def accelerate(model: torch.nn.Module, corr: bool = True, update_block: bool = T
     seam5 =model.__dict__.get("upsample_flow")
     if isinstance(seam5, _UpsampleSeam):
         seam5.multiscale = bool(multiscale_upsample)
+        seam5.multiscale_train = bool(multiscale_train)
     # a model of a multi-scale family (a subclass included: `_multiscale_skip_for` says why it is refused) takes the per-scale skip
     ms_loop = bool(multiscale_upsample) and any((c.__module__, c.__name__) in _MULTISCALE_LOOPS for c in type(model).__mro__)
     if isinstance(model.__dict__.get(_SKIP), _MultiScaleSkip) and (not ms_loop or skip_dead_upsample is False):

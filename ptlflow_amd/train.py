@@ -750,18 +750,24 @@ def _attention_state(attention: torch.Tensor, B: int, H: int, W: int, cache: Opt
 
 def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, H: int, W: int, cache: Optional[dict] = None,
                           accumulate_wgrad: bool = False, attention: Optional[torch.Tensor] = None, hoist_context: bool = True,
-                          context_owner: Optional[torch.Tensor] = None, precision: str = "fp32"):
+                          context_owner: Optional[torch.Tensor] = None, precision: str = "fp32", aggregator=None,
+                          global_context: Optional[torch.Tensor] = None):
     """BasicUpdateBlock.forward / SmallUpdateBlock.forward (update.py:144-153 / :122-128) with every convolution on
     ``conv_pm``, on pixel-major tensors: ``h`` [M, Ch], ``i`` [M, Ci], ``c`` [M, corr channels], ``f`` [M, 2] ->
     ``(h', mask [M, 576] | None, delta [M, 2])``.  ``P``: the block's named parameters; ``cache``: a dict that keeps the packed
     weights between the recurrent calls of one training step.  ``accumulate_wgrad`` (only with a ``cache`` that is created per
     step): the recurrent calls add their weight gradients into one buffer per parameter (`ConvPacks.acc`, `_Flush`).
     ``precision="bf16"``: the convolutions on the bf16 matrix cores (module docstring); inputs and outputs stay fp32 rows.
-    ``attention`` (GMA, `spec.aggregate`): the map [B, 1, N, N] of this forward, fp32; its gradient flows back to it."""
+    ``attention`` (GMA, `spec.aggregate`): the map [B, 1, N, N] of this forward, fp32; its gradient flows back to it.
+    ``aggregator`` / ``global_context`` (CCMR, `spec.external_aggregate`, ccmr/update.py:152-163): the caller's module of this scale
+    and its first argument.  It stays torch autograd: it runs on the NCHW view of the motion features and its result fills the
+    second motion slot of the GRU input, where GMA's branch puts `mf + gamma * attn @ v`.  The mask is [M, `spec.mask_channels`]."""
     acc = accumulate_wgrad and cache is not None
     k = _KERNELS[check_precision(precision)]
     b16 = k.dtype == BF16
-    if spec.aggregate and attention is None:
+    if spec.external_aggregate and aggregator is None:
+        raise ValueError("update_block_train_pm: a block with an external aggregate slot needs the scale's aggregator module")
+    if spec.aggregate and not spec.external_aggregate and attention is None:
         raise ValueError("update_block_train_pm: a block with GMA's aggregate branch needs the attention map [B, 1, N, N]")
 
     def conv(srcs, name, relu=False, real=None, prec=precision, out_fp32=False):
@@ -784,7 +790,11 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
                  if hoist else None)
     x_real = spec.x_channels - (spec.context if hoist else 0)
     parts = [out, f] if hoist else [i, out, f]
-    if spec.aggregate:
+    if spec.external_aggregate:
+        mf = torch.cat([out.float(), f], 1)
+        mfg = _pm(aggregator(global_context, _nchw(mf, B, H, W)))
+        parts = [mf, mfg] if hoist else [i, mf, mfg]
+    elif spec.aggregate:
         mf = torch.cat([out, f], 1)
         v = conv([mf], "aggregator.to_v")                                        # 1x1, no bias
         att = _attention_state(attention, B, H, W, cache, acc, precision)       # packed once per step (P and P^T, fp32 or bf16)
@@ -821,12 +831,15 @@ def update_block_train_pm(P: Dict[str, torch.Tensor], spec, h, i, c, f, B: int, 
 
 
 def update_block_train(P: Dict[str, torch.Tensor], spec, net, inp, corr, flow, cache: Optional[dict] = None,
-                       precision: str = "fp32", attention: Optional[torch.Tensor] = None):
+                       precision: str = "fp32", attention: Optional[torch.Tensor] = None, aggregator=None,
+                       global_context: Optional[torch.Tensor] = None):
     """NCHW face of `update_block_train_pm` (what `PfkUpdateBlock` calls from the reference's loop):
-    NCHW in, NCHW out: ``(net, mask | None, delta_flow)``; ``attention``: GMA's map [B, 1, N, N]."""
+    NCHW in, NCHW out: ``(net, mask | None, delta_flow)``; ``attention``: GMA's map [B, 1, N, N]; ``aggregator`` /
+    ``global_context``: CCMR's module of this scale and its first argument."""
     B, _, H, W = net.shape
     h, mask, delta = update_block_train_pm(P, spec, _pm(net), _pm(inp), _pm(corr), _pm(flow), B, H, W, cache, context_owner=inp,
-                                           precision=precision, attention=attention)
+                                           precision=precision, attention=attention, aggregator=aggregator,
+                                           global_context=global_context)
     return _nchw(h, B, H, W), (None if mask is None else _nchw(mask, B, H, W)), _nchw(delta, B, H, W)
 
 
@@ -861,6 +874,37 @@ class _ConvexUpsample(torch.autograd.Function):
 def convex_upsample(flow: torch.Tensor, mask_pm: torch.Tensor) -> torch.Tensor:
     load_native()
     return _ConvexUpsample.apply(flow, mask_pm)
+
+
+class _ConvexUpsample2(torch.autograd.Function):
+    """`upsample_flow(flow, mask, scale=2)` of the multi-scale loops (ccmr/ccmr.py:128-139, ms_raft_plus/ms_raft_plus.py:133-144):
+    flow [B,2,H,W] (NCHW), mask pixel-major [B*H*W, 36] (already x0.25; any row stride) -> [B,2,2H,2W]; forward and both gradients
+    on libpfk (`pfk_convex_upsample2_f32`, `pfk_convex_upsample2_bwd_f32`)."""
+
+    @staticmethod
+    def forward(ctx, flow, mask):
+        flow = flow.float().contiguous()
+        mask = mask.float()
+        if mask.stride(1) != 1:
+            mask = mask.contiguous()
+        B, _, H, W = flow.shape
+        out = torch.empty(B, 2, 2 * H, 2 * W, device=flow.device, dtype=torch.float32)
+        torch.ops.pfk.convex_upsample2(flow, mask, out)
+        ctx.save_for_backward(flow, mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        flow, mask = ctx.saved_tensors
+        gmask = torch.empty(mask.shape[0], 36, device=mask.device, dtype=torch.float32)
+        gflow = torch.empty_like(flow)
+        torch.ops.pfk.convex_upsample2_bwd(flow, mask, g.float().contiguous(), gmask, gflow)
+        return gflow, gmask
+
+
+def convex_upsample2(flow: torch.Tensor, mask_pm: torch.Tensor) -> torch.Tensor:
+    load_native()
+    return _ConvexUpsample2.apply(flow, mask_pm)
 
 
 def sequence_loss(flow_preds: Sequence[torch.Tensor], flow_gt: torch.Tensor, valid: torch.Tensor, gamma: float = 0.8,

@@ -796,6 +796,10 @@ class PfkUpdateBlock(WrappedModule):
         # "fp32" | "bf16": precision of the native training path's convolutions (ptlflow_amd/train.py; `accelerate(train_precision=)`)
         self.train_precision = "fp32"
         self._train_cache: dict = {}  # packed weights of the training path, keyed by parameter versions
+        # `accelerate(model, multiscale_train=True)`: the native training path also takes the multi-scale blocks — a
+        # 36-channel mask (x2 upsampling), CCMR's external aggregate slot — in fp32
+        self.multiscale_train = False
+        self.train_calls = 0          # calls the native training path served
         self.spec = spec
         self._inp_ref, self._inp_version = None, -1      # strong references: the address cannot be recycled while cached
         self._attn_ref, self._attn_version = None, -1
@@ -861,16 +865,30 @@ class PfkUpdateBlock(WrappedModule):
         if torch.is_grad_enabled() and (net.requires_grad or any(p.requires_grad for p in self.parameters())):
             # training graph: every convolution forward / dgrad / wgrad on the MFMA kernel through the
             # differentiable composition of ptlflow_amd/train.py — GMA's block included: `attention` goes through, the aggregate
-            # runs on `train._AttnMatmul` and the map's gradient flows back to the caller's tensor; CCMR's external aggregate, CPU
-            # tensors and split-bf16 modes keep the reference module's own autograd.  train_precision "bf16" puts the composition
-            # on the bf16 matrix cores whatever the inference precision is.
+            # runs on `train._AttnMatmul` and the map's gradient flows back to the caller's tensor; CPU tensors and split-bf16
+            # modes keep the reference module's own autograd, and so do the multi-scale blocks (a 36-channel mask, CCMR's external
+            # aggregate) unless `multiscale_train` is set: the branch below.  train_precision "bf16" puts the composition on the
+            # bf16 matrix cores whatever the inference precision is.
             if (self.native_backward and net.is_cuda and not self.spec.external_aggregate and self.spec.mask_channels == 576
                     and (attention is not None or not self.spec.aggregate)
                     and (self.conv_precision == "fp32" or self.train_precision == "bf16")):
                 from .train import update_block_train
                 h, mask, delta = update_block_train(dict(self.named_parameters()), self.spec, net, inp, corr, flow, self._train_cache,
                                                     self.train_precision, attention)
+                self.train_calls += 1
                 return h.to(net.dtype), (None if mask is None else mask.to(net.dtype)), delta.to(net.dtype)
+            # K18: the multi-scale blocks (36 mask logits; CCMR's: the scale's aggregator stays the caller's torch module), fp32
+            if (self.multiscale_train and self.native_backward and net.is_cuda and self.spec.mask_channels == 36
+                    and (self.spec.external_aggregate or not self.spec.aggregate)
+                    and self.conv_precision == "fp32" and self.train_precision == "fp32"
+                    and net.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                    and (not self.spec.external_aggregate or args.get("global_context") is not None)):
+                from .train import update_block_train
+                agg = self._ref[0].aggregator[args.get("level_index", 0)] if self.spec.external_aggregate else None
+                h, mask, delta = update_block_train(dict(self.named_parameters()), self.spec, net, inp, corr, flow, self._train_cache,
+                                                    "fp32", None, agg, args.get("global_context"))
+                self.train_calls += 1
+                return h, mask, delta
             return self._ref[0](net, inp, corr, flow, *extra, **kw)
         grad = torch.is_grad_enabled()      # (the aggregator engines serve no-grad calls only, whether or not anything requires grad)
         with torch.no_grad():
